@@ -2,6 +2,7 @@
 """Headline benchmark: ResNet-50 W8A8 per-channel fake-quant forward (BASELINE.json configs[2]).
 
     python bench.py --gpus N --steps K --warmup W [--scaling strong] [--model resnet50|repvgg_a1|mobileone_s1|resnet18]
+                    [--dump-outputs DIR] [--full]
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE come from the environment), or on its own - without
     WORLD_SIZE in the environment `python bench.py --gpus N` starts that launcher itself as a child process BEFORE anything
@@ -21,10 +22,15 @@ built (the reference re-quantises 0.2 GB of weights per forward: 0.5 % of the st
 Inputs are resident in HBM when the timed region starts.  Weak scaling by default (512 images on every GPU, no collective
 in the steady state); `--scaling strong` splits a fixed global batch of 4096.
 
-One JSON line on rank 0.  Besides the contract fields:
+A plain run sets up, calibrates, warms up, times the K steps and prints one JSON line on rank 0 with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); every timed step is the same call of the same plan.
+--dump-outputs DIR then writes what the last timed step returned (the logits) as DIR/logits.npy, float32, at most 64 MB
+(a fixed, seeded sample of rows beyond that; DIR/logits_rank<r>.npy per rank when N > 1); inputs and weights are seeded.
+--full adds, outside the timed region:
   roofline             the kernel with the largest share of the step - since round 2 the chain kernel (a block's last 1x1
                        convolution + shortcut + ReLU + quantiser + the next block's first 1x1, csrc/conv_chain_i8.hip):
-                       algorithmic bytes / HIP-event durations of its launches in the first timed step, on the launch stream;
+                       algorithmic bytes / HIP-event durations of its launches in one single-stream step run just before the
+                       timed region (--profiled-steps), on the launch stream;
                        `traffic` comes from the committed rocprofv3 PMC passes of the same command (`traffic_measured_in_run`
                        says so: counters cannot be read from inside the process)
   roofline_second_kernel  the same for the other int8 kernel (csrc/conv_i8.hip: 3x3s, stage 3 / 4 block ends, first 1x1s, fc)
@@ -55,6 +61,8 @@ import os
 import statistics
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd")]
@@ -192,7 +200,8 @@ def dry_run(args, world, rank):
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        coll = collective_report(torch.device("cpu"), world, args.backend, 0)     # the same object a real N > 1 line carries
+        if args.full:
+            coll = collective_report(torch.device("cpu"), world, args.backend, 0)     # the same object a real N > 1 --full line carries
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps({"metric": f"{args.model} fake-quant fwd images/sec", "value": 0.0, "unit": "images/s", "n_gpus": world,
@@ -201,6 +210,23 @@ def dry_run(args, world, rank):
                           "config": {"workload": "dry run of the launcher and the rendezvous", "global_batch": args.batch * world,
                                      "parallelism": f"dp{world} (batch-sharded replicas)", "backend": args.backend},
                           **({"collective": coll} if coll else {})}), flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outputs, budget=DUMP_BYTES):
+    """--dump-outputs: every array of `outputs` (name -> tensor) as DIR/<name>.npy in float32.  An array whose share of `budget`
+    is too small for all its rows keeps a fixed, seeded sample of rows (in their original order), so that two builds run with
+    the same arguments dump the same elements."""
+    os.makedirs(directory, exist_ok=True)
+    share = budget // max(len(outputs), 1)
+    for name, t in outputs.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > share:
+            keep = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(2333))[:max(share // (a[0].numel() * 4), 1)]
+            a = a[keep.sort().values]
+        np.save(os.path.join(directory, name + ".npy"), a.numpy())
 
 
 def families(records):
@@ -441,10 +467,11 @@ def main():
                     help="fused plan only: split each step's batch over this many HIP streams (dlmc.utils.fuse.StreamedPlan, "
                          "bit-identical results; 2 gives +5-9 %% on ResNet-50 b512: the ramp and tail of one layer's launch overlap "
                          "the other half-batch's neighbouring layer).  The steps that carry per-kernel HIP events "
-                         "(--profiled-steps, the first of the timed region) run on ONE stream, so that the roofline objects "
+                         "(--full, --profiled-steps, in front of the timed region) run on ONE stream, so that the roofline objects "
                          "describe kernels that had the chip to themselves, as the rocprofv3 summaries do")
     ap.add_argument("--profiled-steps", type=int, default=1,
-                    help="timed steps whose launches carry HIP events (per-kernel durations for the roofline objects)")
+                    help="--full: single-stream steps in front of the timed region whose launches carry HIP events (per-kernel "
+                         "durations for the roofline objects)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-budget", type=float, default=8.0, help="seconds of CPU work for the all-cores leg of cpu_baseline (half of it again on one thread)")
@@ -456,7 +483,14 @@ def main():
     ap.add_argument("--no-fake-quant-leg", dest="fq_leg", action="store_false",
                     help="skip `roofline_fake_quant_resnet50`: three forwards of the same model in `--conv fp32 --plan modules` form behind the "
                          "headline region (the stand-alone fake-quant kernels' own roofline on the whole network)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, outside the timed region: first batch, per-kernel rooflines, the "
+                         "fake-quant leg, other_configs, collective report, cpu_baseline (--no-* above switch parts of it off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     args.int8 = args.conv == "int8"
     if args.batch is None:
         args.batch = 1024 if args.model == "mobileone_s1" else 512
@@ -516,7 +550,7 @@ def main():
     with torch.no_grad():
         model(x)                                 # the first forward calibrates (observer + all-reduce); not timed
         calib_allreduces = Wr.ALLREDUCE_CALLS    # collectives this rank issued in it (one per activation observer when world > 1)
-        if args.conv == "int8":
+        if args.conv == "int8" and args.full:
             # SURVEY 8(d) config 3 also asks for the first batch (observers on): re-arm every wrapper's observer and time ONE
             # more calibrating forward (the first one above also paid the one-time costs: code-object loads, allocator growth)
             def rearm():
@@ -557,32 +591,37 @@ def main():
             model = StreamedPlan(model, args.streams)
         for _ in range(args.warmup):
             model(x)
-        if model is not single:
-            single(x)
-        # Per-kernel HIP events (two marker packets per launch, ~4 us each on the queue) are recorded in the FIRST step of
-        # the timed region only: instrumenting all K steps costs the step 5-6 % (9.4 vs 8.85 ms), one step costs 1/K of it.
         K.PROFILE.reset()
+        if args.full:
+            # Per-kernel HIP events (two marker packets per launch, ~4 us each on the queue) cost an instrumented step 5-6 %
+            # (9.4 vs 8.85 ms): they are recorded on single-stream steps of their own, in front of the timed region.
+            if model is not single:
+                single(x)
+            K.PROFILE.enabled = True
+            for _ in range(args.profiled_steps):
+                single(x)
+            K.PROFILE.enabled = False
         barrier()
         t0 = time.perf_counter()
-        for i in range(args.steps):
-            K.PROFILE.enabled = i < args.profiled_steps
-            (single if K.PROFILE.enabled else model)(x)
+        for _ in range(args.steps):
+            y = model(x)
         barrier()
         elapsed = time.perf_counter() - t0
-        K.PROFILE.enabled = False
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits" if world == 1 else f"logits_rank{rank}": y}, DUMP_BYTES // world)
 
-    # per-kernel-family HIP-event durations of the timed region (rank 0's launches)
+    # per-kernel-family HIP-event durations of the profiled steps (rank 0's launches)
     fam = families(K.PROFILE.records)
-    coll = collective_report(dev, world, args.backend, calib_allreduces) if world > 1 else None
+    coll = collective_report(dev, world, args.backend, calib_allreduces) if world > 1 and args.full else None
 
     def other_configs():
         """BASELINE configs[3]'s and [4]'s networks, a short run each after the headline region (every rank takes part)."""
-        if not (args.other_configs and args.fused and args.model == "resnet50"):
+        if not (args.full and args.other_configs and args.fused and args.model == "resnet50"):
             return None
         return {name: side_config(name, b, args, dev, world, rank, barrier) for name, b in (("repvgg_a1", 512), ("mobileone_s1", 1024))}
     if rank != 0:
@@ -592,7 +631,30 @@ def main():
         return
 
     images = args.batch * world * args.steps
-    psteps = max(1, min(args.profiled_steps, args.steps))   # steps that carried HIP events
+    out = {
+        "metric": "ResNet-50 W8A8 fake-quant fwd images/sec" if args.model == "resnet50" else
+                  f"{args.model} {'W4A8' if w4a8 else 'W8A8'} fake-quant fwd images/sec",
+        "value": round(images / elapsed, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": args.scaling, "vs_baseline": None,
+        # the arithmetic of the step: int8 x int8 -> int32 on the matrix cores with fp32 quantise / dequantise (int8 mode), or fp32
+        "dtype": "i8" if args.int8 else "f32", "data": "synthetic",
+        "config": {"workload": (f"{args.model} W4A8 fake-quant forward (QBase family: W minmax_channel u4 asymmetric per channel, "
+                                f"A minmax_tensor u8), deploy form, " if w4a8 else
+                                f"{args.model} W8A8 per-channel fake-quant forward (FSPTQ forms: W minmax_channel s8, "
+                                f"A minmax_tensor u8), {'BatchNorm kept' if args.keep_bn else 'BN folded first as in FSPTQuant.py:67'}, ") +
+                               f"{'fused int8 MFMA conv/linear' if args.int8 else 'fp32 conv of the fake-quantised operands'}, "
+                               f"{'frozen execution plan (epilogue-fused ReLU / shortcut / next-layer codes; block end + next 1x1 as one launch; weight codes quantised once at plan build), ' if args.fused else ''}"
+                               f"{str(args.streams) + ' HIP streams per GPU, ' if args.fused and args.streams > 1 and not w4a8 else ''}"
+                               f"224x224 {'relu(N(0,1))' if args.input == 'halfnormal' else 'N(0,1)'} pixels, batch {args.batch} per GPU, scales frozen",
+                   "global_batch": args.batch * world, "parallelism": f"dp{world} (batch-sharded replicas)"},
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    psteps = max(1, args.profiled_steps)   # steps that carried HIP events
 
     def roof(name, f, kernel, note=None, ops=0):
         ach = f["bytes"] / (f["ms"] * 1e-3) / 1e9 if f["ms"] > 0 else 0.0
@@ -620,7 +682,7 @@ def main():
     halo = fam.get("conv3x3_halo", empty)         # the halo-tile 3x3 kernel (csrc/conv3x3_i8.hip): its own family since round 4
     chain = fam.get("conv_chain", empty)          # block end + next 1x1 in one kernel (csrc/conv_chain_i8.hip)
     conv_ops, chain_ops = conv.get("ops", 0), chain.get("ops", 0)     # 2 x MACs, recorded per launch (kernels.PROFILE)
-    # `roofline` describes the kernel of this project with the largest share of the timed region
+    # `roofline` describes the kernel of this project with the largest share of the profiled step
     second_roof = third_roof = fourth_roof = None
     if max(conv["ms"], chain["ms"], halo["ms"]) > fq["ms"]:
         if args.fused:
@@ -698,23 +760,7 @@ def main():
         del a
     qbytes = sum(f["bytes"] for k, f in fam.items() if k.startswith("fq"))
     qms = sum(f["ms"] for k, f in fam.items() if k.startswith("fq"))
-    out = {
-        "metric": "ResNet-50 W8A8 fake-quant fwd images/sec" if args.model == "resnet50" else
-                  f"{args.model} {'W4A8' if w4a8 else 'W8A8'} fake-quant fwd images/sec",
-        "value": round(images / elapsed, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None,
-        # the arithmetic of the step: int8 x int8 -> int32 on the matrix cores with fp32 quantise / dequantise (int8 mode), or fp32
-        "dtype": "i8" if args.int8 else "f32", "data": "synthetic",
-        "config": {"workload": (f"{args.model} W4A8 fake-quant forward (QBase family: W minmax_channel u4 asymmetric per channel, "
-                                f"A minmax_tensor u8), deploy form, " if w4a8 else
-                                f"{args.model} W8A8 per-channel fake-quant forward (FSPTQ forms: W minmax_channel s8, "
-                                f"A minmax_tensor u8), {'BatchNorm kept' if args.keep_bn else 'BN folded first as in FSPTQuant.py:67'}, ") +
-                               f"{'fused int8 MFMA conv/linear' if args.int8 else 'fp32 conv of the fake-quantised operands'}, "
-                               f"{'frozen execution plan (epilogue-fused ReLU / shortcut / next-layer codes; block end + next 1x1 as one launch; weight codes quantised once at plan build), ' if args.fused else ''}"
-                               f"{str(args.streams) + ' HIP streams per GPU (the ' + str(min(args.profiled_steps, args.steps)) + ' profiled step(s) on one), ' if args.fused and args.streams > 1 and not w4a8 else ''}"
-                               f"224x224 {'relu(N(0,1))' if args.input == 'halfnormal' else 'N(0,1)'} pixels, batch {args.batch} per GPU, scales frozen",
-                   "global_batch": args.batch * world, "parallelism": f"dp{world} (batch-sharded replicas)"},
+    out.update({
         **({"first_batch": {"ms": round(first_batch_ms, 2), "images_per_s": round(args.batch * world / (first_batch_ms * 1e-3), 1),
                             "how": first_batch_how, "module_path_ms": round(first_batch_module_ms, 2),
                             "what": "one forward with every observer on (min/max and all-reduce(MAX) per activation quantiser, per-channel "
@@ -735,7 +781,7 @@ def main():
                        "share_of_step": round(qms / psteps / (elapsed / args.steps * 1e3), 4),
                        "families": {k: {"launches": f["launches"], "GBps": round(f["bytes"] / (f["ms"] * 1e-3) / 1e9, 1)}
                                     for k, f in fam.items() if f["ms"] > 0}},
-    }
+    })
     if args.model == "resnet50":
         # 85 315 584 B per image of activations + 204 023 296 B of weights per forward at 8 B per
         # fake-quantised element; "5.49 ms at roofline" for batch 512.  The whole step (convolutions included) against that.

@@ -287,6 +287,23 @@ def test_bench_refuses_counter_tails_that_are_not_the_step_s_launches(tmp_path):
     assert got is None and "no profiles" in why
 
 
+def test_bench_dump_outputs_float32_within_budget_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per output; one over its share of the byte budget keeps a fixed, seeded sample of its rows,
+    the same from call to call (two builds dump the same elements), in their original order."""
+    import numpy as np
+    import bench
+    y = torch.arange(512 * 1000, dtype=torch.float64).reshape(512, 1000)
+    bench.dump_outputs(str(tmp_path / "all"), {"logits": y})
+    a = np.load(tmp_path / "all" / "logits.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.float().numpy())
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"logits": y}, budget=100 * 1000 * 4 + 5)
+    s1, s2 = np.load(tmp_path / "s1" / "logits.npy"), np.load(tmp_path / "s2" / "logits.npy")
+    assert s1.shape == (100, 1000) and s1.nbytes <= 100 * 1000 * 4 + 5 and np.array_equal(s1, s2)
+    rows = s1[:, 0] / 1000
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, y.float().numpy()[rows.astype(np.int64)])
+
+
 def test_chunk_major_block_tensor_round_trip_on_the_host():
     """kernels.ChunkMajor (the fp32 block tensor between two chain kernels, DLMCQ_FP32_*_CHUNK_MAJOR): [K / 64][N H W][64] planes of the same
     values - conversions and windows are plain tensor arithmetic, checked here without a GPU; the kernels' side of it: tests/test_gpu_chain.py."""
