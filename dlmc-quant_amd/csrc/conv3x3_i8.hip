@@ -449,6 +449,7 @@ bool conv3x3_halo_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
   if (R != 3 || S != 3 || (stride != 1 && stride != 2) || pad != 1 || dilation != 1 || dual || out || ep.residual || ep.w_off || !ep.codes)
     return false;
   if (C % 64 != 0 || K % 64 != 0 || !aligned16(ep.codes)) return false;
+  if (ep.relu == DLMCQ_ACT_RELU6) return false;                       // (ReLU only: ReLU6 layers take the tiled kernel)
   if (stride == 2 && ((H | W) & 1)) return false;                      // (odd sizes: the generic kernel)
   const int64_t P = H / stride, Q = W / stride;                        // pad 1, 3 x 3: P = H for stride 1, H / 2 for even H at stride 2
   if (stride == 2 && Q + 1 > 62) return false;                         // a phase tile of 256 + Wp + 2 positions in 20 pieces

@@ -489,6 +489,7 @@ namespace dlmcq {
 #endif
 bool conv3x3_pipe_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t stride, const ConvEpi& ep, int cus) {
   if (stride != 1 || !(C == 128 || C == 256 || C == 512) || K % 128 != 0 || K > PIPE_KMAX || !epi_plain(ep)) return false;
+  if (ep.relu == DLMCQ_ACT_RELU6) return false;                                   // (ReLU only: ReLU6 layers take the tiled kernel)
   if (W + 1 > 62) return false;                                                   // six halo pieces per wave
   const int64_t MQ = N * (H + 1) * (W + 1);
   const int64_t ntiles = ((MQ + 255) / 256) * (K / 128);

@@ -574,6 +574,7 @@ static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C
                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                         int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi,
                         int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
+  if (relu == DLMCQ_ACT_RELU6 || relu2 == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only: the flags below read any non-zero value as ReLU)
   if (q_lo != 0 || q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
   const bool w3cm = (q2_form & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (q2_form & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
   // (a call without a shortcut tensor - the convolution-shortcut form - or without an output has ONE fp32 tensor: its layout is the call's)

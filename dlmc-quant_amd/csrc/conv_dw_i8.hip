@@ -53,7 +53,9 @@ struct DwTab {       // per channel, in LDS: two 16-byte records, each stored [p
 // FAST (round 4): 1 / 2 = codes-only layer with the plain quantiser, asymmetric / symmetric weights - what conv_dw3p2_i8_kernel<FAST> does for
 // stride 1 (the fp32 chain on channel pairs, all four quantiser quads behind one branch, border taps as out-of-range buffer loads
 // when the zero point is 0, table runs per lane), here for any stride (MobileOne's four stride-2 layers).  0 = everything else.
-template <int FAST>
+// R6 (every kernel of this file): ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan on top of the ReLU, in fp32 before the value is
+// stored or quantised (conv_epilogue.h)
+template <int FAST, bool R6 = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* __restrict__ x, const int8_t* __restrict__ w,
                                                                  float* __restrict__ out, const float* __restrict__ bias,
                                                                  const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
           v[2 * jp] = r.x;
           v[2 * jp + 1] = r.y;
         }
-        vq[d] = v;
+        vq[d] = R6 ? cap6_nan4(v) : v;
         continue;
       }
 #pragma unroll
@@ -214,6 +216,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
         v[j] = r;
       }
       if (ep.relu && !fold) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
+      if constexpr (R6) v = cap6_nan4(v);
       const int64_t at = (int64_t)pix * g.C4 * 4 + c + d * 4;
       if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
       if (ep.codes) codes[d] = eq.code4(v);
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
 // of channels (v_pk_mul_f32 / v_pk_add_f32 on constants stored as pairs: the same roundings, half the instructions), the
 // quantiser of both pixels behind one branch with its clamp left to v_cvt_pk_u8_f32 (EpiQuant::code4n_plain), no flag tests per
 // element.  0 = everything else, as before.  Bit-identical where both apply.
-template <int FAST>
+template <int FAST, bool R6 = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4* __restrict__ x, const int8_t* __restrict__ w,
                                                                    float* __restrict__ out, const float* __restrict__ bias,
                                                                    const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -391,7 +394,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
           vA[2 * jp] = rA.x; vA[2 * jp + 1] = rA.y;
           vB[2 * jp] = rB.x; vB[2 * jp + 1] = rB.y;
         }
-        const f32x4 vv[2] = {vA, vB};
+        const f32x4 vv[2] = {R6 ? cap6_nan4(vA) : vA, R6 ? cap6_nan4(vB) : vB};
         uint32_t ww[2];
         eq.code4n_plain(vv, ww);
         codesA[d] = ww[0];
@@ -431,6 +434,10 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
         vA = f32x4{relu_nan(vA.x), relu_nan(vA.y), relu_nan(vA.z), relu_nan(vA.w)};
         vB = f32x4{relu_nan(vB.x), relu_nan(vB.y), relu_nan(vB.z), relu_nan(vB.w)};
       }
+      if constexpr (R6) {
+        vA = cap6_nan4(vA);
+        vB = cap6_nan4(vB);
+      }
       const int64_t at = pixA * C + c + d * 4;
       if (out) {
         __builtin_nontemporal_store(vA, reinterpret_cast<f32x4*>(out + at));
@@ -450,6 +457,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
 }
 
 // Any R, S <= 7 and C % 4 == 0: one dword of codes per thread and tap.
+template <bool R6 = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw_i8_kernel(const uint32_t* __restrict__ x, const uint32_t* __restrict__ w,
                                                                 float* __restrict__ out, const float* __restrict__ bias,
                                                                 const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -494,6 +502,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw_i8_kernel(const uint32_t*
       v = f32x4{v.x + bb.x, v.y + bb.y, v.z + bb.z, v.w + bb.w};
     }
     if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
+    if constexpr (R6) v = cap6_nan4(v);
     const int64_t at = (int64_t)pix * g.C4 * 4 + c;
     if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
     if (ep.codes) __builtin_nontemporal_store(eq.code4(v), reinterpret_cast<uint32_t*>(ep.codes + at));
@@ -531,7 +540,7 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
   g.qdiv = make_fastdiv((uint32_t)Q);
   g.pdiv = make_fastdiv((uint32_t)P);
   ConvEpi ep{};
-  ep.relu = relu != 0;
+  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
   ep.codes = static_cast<uint8_t*>(codes);
   ep.q_scale = q_scale;
   ep.q_zp = q_zero_point;
@@ -549,16 +558,21 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
   }
   if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
   const bool wide = R == 3 && S == 3 && C % 16 == 0 && C <= 2048 && aligned16(x) && (!codes || aligned16(codes));
+  const bool r6 = ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
   if (wide && stride == 1 && pad == 1 && C <= 1024) {     // two output pixels per thread (LDS: 48 B per channel)
     g.cdiv = make_fastdiv((uint32_t)(C / 16));
     const int64_t qpairs = (Q + 1) / 2;
     g.qdiv = make_fastdiv((uint32_t)qpairs);
     const int64_t b16 = (N * P * qpairs * (C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
     const int fast = (!out && epi_plain(ep)) ? (w_offset ? 1 : 2) : 0;
-#define DLMCQ_DWP2(F) hipLaunchKernelGGL(conv_dw3p2_i8_kernel<F>, dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), (size_t)(C / 16) * (3 * 17 * 16), st, \
-                                         static_cast<const u32x4*>(x), w, out, bias, in_scale, in_zero_point, w_scale, w_offset, g,              \
-                                         x_is_unsigned ? 0 : 1, ep)
-    if (fast == 1) DLMCQ_DWP2(1);
+#define DLMCQ_DWP2(...) hipLaunchKernelGGL((conv_dw3p2_i8_kernel<__VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), (size_t)(C / 16) * (3 * 17 * 16), st, \
+                                           static_cast<const u32x4*>(x), w, out, bias, in_scale, in_zero_point, w_scale, w_offset, g,              \
+                                           x_is_unsigned ? 0 : 1, ep)
+    if (r6) {
+      if (fast == 1) DLMCQ_DWP2(1, true);
+      else if (fast == 2) DLMCQ_DWP2(2, true);
+      else DLMCQ_DWP2(0, true);
+    } else if (fast == 1) DLMCQ_DWP2(1);
     else if (fast == 2) DLMCQ_DWP2(2);
     else DLMCQ_DWP2(0);
 #undef DLMCQ_DWP2
@@ -567,17 +581,24 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
     const int64_t b16 = (N * P * Q * (C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
     // every workgroup packs the layer's weights into its LDS table first: a grid of a few workgroups per CU, each walking many pixels
     const int fast = (!out && epi_plain(ep)) ? (w_offset ? 1 : 2) : 0;
-#define DLMCQ_DW3(F) hipLaunchKernelGGL(conv_dw3_i8_kernel<F>, dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK),                 \
+#define DLMCQ_DW3(F, ...) hipLaunchKernelGGL((conv_dw3_i8_kernel<F __VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), \
                                         F ? (size_t)(C / 16) * (17 * 16 + 9 * 16 + 9 * 8) : (size_t)C * sizeof(DwTab), st, static_cast<const u32x4*>(x), w, \
                                         out, bias, in_scale, in_zero_point, w_scale, w_offset, g, x_is_unsigned ? 0 : 1, ep)
-    if (fast == 1) DLMCQ_DW3(1);
+    if (r6) {
+      if (fast == 1) DLMCQ_DW3(1, , true);
+      else if (fast == 2) DLMCQ_DW3(2, , true);
+      else DLMCQ_DW3(0, , true);
+    } else if (fast == 1) DLMCQ_DW3(1);
     else if (fast == 2) DLMCQ_DW3(2);
     else DLMCQ_DW3(0);
 #undef DLMCQ_DW3
   } else {
-    hipLaunchKernelGGL(conv_dw_i8_kernel, dim3((uint32_t)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(DLMCQ_BLOCK), 0, st,
-                       static_cast<const uint32_t*>(x), reinterpret_cast<const uint32_t*>(w), out, bias, in_scale, in_zero_point, w_scale,
-                       w_offset, g, x_is_unsigned ? 0 : 1, ep);
+#define DLMCQ_DWG(...) hipLaunchKernelGGL((conv_dw_i8_kernel<__VA_ARGS__>), dim3((uint32_t)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(DLMCQ_BLOCK), 0, st, \
+                                          static_cast<const uint32_t*>(x), reinterpret_cast<const uint32_t*>(w), out, bias, in_scale, in_zero_point, w_scale, \
+                                          w_offset, g, x_is_unsigned ? 0 : 1, ep)
+    if (r6) DLMCQ_DWG(true);
+    else DLMCQ_DWG();
+#undef DLMCQ_DWG
   }
   return launch_status();
 }

@@ -49,7 +49,8 @@ constexpr int DWM_TP = 192;      // output positions per tile (128: +2.6 % time 
 
 // XS: the input codes are signed bytes (int8 codes, or an unsigned quantiser's codes handed over as `code - 128`): no re-centring
 // of the fragments (4 vector instructions per MFMA otherwise)
-template <int HPW, bool XS>
+// R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan in fp32 before the quantiser (whose byte conversion is the lower bound)
+template <int HPW, bool XS, bool R6 = false>
 __global__ __launch_bounds__(256, 3) void conv_dwm_i8_kernel(DwmArgs a, ConvEpi ep) {
   constexpr int HALO = HPW * 4 * 1024;                 // bytes of one halo buffer (16 positions x 64 B per piece)
   constexpr int NHB = 2;                               // halo buffers: the halo of tile t + NHB - 1 is requested while tile t is worked on (three: no faster)
@@ -185,6 +186,10 @@ __global__ __launch_bounds__(256, 3) void conv_dwm_i8_kernel(DwmArgs a, ConvEpi 
           v[jp >> 1][2 * (jp & 1)] = r.x;
           v[jp >> 1][2 * (jp & 1) + 1] = r.y;
         }
+        if constexpr (R6) {
+          v[0] = cap6_nan4(v[0]);
+          v[1] = cap6_nan4(v[1]);
+        }
         uint32_t wq[2];
         eq.code4n_plain(v, wq);
         // (16-byte segment s of position p sits in slot s ^ ((p >> 2) & 3), like the halo tiles: unswizzled, the 32 positions of a
@@ -266,10 +271,13 @@ int conv_dwm_launch(const int8_t* x, const int8_t* w, const float* bias, const f
   const int maxg = (a.ntiles + 7) & ~7;
   if (ngroups > maxg) ngroups = maxg;
   const dim3 grid((uint32_t)(ngroups * a.nchunks)), block(256);
-#define DLMCQ_DWM_GO(HP_)                                                                         \
-  do {                                                                                            \
-    if (x_signed) hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, true>), grid, block, 0, st, a, ep);  \
-    else hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, false>), grid, block, 0, st, a, ep);          \
+#define DLMCQ_DWM_GO(HP_)                                                                                     \
+  do {                                                                                                        \
+    if (ep.relu == DLMCQ_ACT_RELU6) {                                                                         \
+      if (x_signed) hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, true, true>), grid, block, 0, st, a, ep);       \
+      else hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, false, true>), grid, block, 0, st, a, ep);               \
+    } else if (x_signed) hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, true>), grid, block, 0, st, a, ep);       \
+    else hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, false>), grid, block, 0, st, a, ep);                      \
   } while (0)
   if (hpw <= 4) DLMCQ_DWM_GO(4);
   else DLMCQ_DWM_GO(5);

@@ -363,6 +363,7 @@ extern "C" int dlmcq_conv2d_dwpw_i8_nhwc(const void* x, const void* dw_table, in
                                          const float* pw_in_scale, const float* w_scale, const float* w_offset, int64_t K,
                                          int32_t relu, void* codes, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo,
                                          int32_t q2_hi, int32_t q2_form, float q2_ste_g, dlmcq_stream_t stream) {
+  if (dw_relu == DLMCQ_ACT_RELU6 || relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
   if (N < 0 || H < 1 || W < 1 || C < 64 || (C & 63) || (K != 128 && K != 192 && K != 512)) return DLMCQ_EINVAL;
   if (N == 0) return DLMCQ_OK;
   if (!x || !dw_table || !q_scale || !w || !wsum || !pw_in_scale || !w_scale || !codes || !q2_scale) return DLMCQ_EINVAL;

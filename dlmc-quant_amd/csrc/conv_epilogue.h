@@ -23,7 +23,7 @@ struct ConvEpi {
   const float* q_zp;
   float q_lo, q_hi, q_g;
   int q_form;
-  int relu;
+  int relu;                // DLMCQ_ACT_*: 0 none, 1 ReLU, 2 ReLU6 (the upper bound: a compile-time flag of the kernels that implement it)
   uint32_t q_xor;          // 0x80808080 when the codes are stored as int8 `code - 128` (DLMCQ_EMIT_SHIFT128), else 0
   uint32_t ctl;            // host side only: DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED as passed in `q_form`
   // observer partials of the fp32 OUTPUT (dlmcq_conv2d_i8_nhwc_fused_observed; the tiled kernel only): every workgroup writes the
@@ -74,6 +74,12 @@ __device__ __forceinline__ f32x4 relu4_nan(const f32x4& y) {
       : [y0] "v"(y.x), [y1] "v"(y.y), [y2] "v"(y.z), [y3] "v"(y.w));
   return f32x4{o0, o1, o2, o3};
 }
+
+// ReLU6's upper bound (DLMCQ_ACT_RELU6): v > 6 ? 6 : v, in fp32 before the value is stored or quantised - a compare and a select, so
+// NaN and -0 pass (v_min_f32 would turn NaN into 6).  The lower bound is the kernel's ReLU (applied, or folded into the quantiser's
+// clamp: code(relu(cap6(v))) = max(code(cap6(v)), code(0)) as for ReLU alone).  The kernels take it as a compile-time flag.
+__device__ __forceinline__ float cap6_nan(float v) { return v > 6.0f ? 6.0f : v; }
+__device__ __forceinline__ f32x4 cap6_nan4(const f32x4& v) { return f32x4{cap6_nan(v.x), cap6_nan(v.y), cap6_nan(v.z), cap6_nan(v.w)}; }
 
 struct EpiQuant {   // the consumer's constants, resolved once per thread
   // |t - rint(t)| must stay below this for the fast path to stand (see code4_fast): 0.5 minus the bound on |t - (d + zadd)| at

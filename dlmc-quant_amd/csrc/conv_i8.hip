@@ -48,7 +48,9 @@ namespace dlmcq {
 //     quantises them and holds 16 finished bytes: no transposition of fp32 values through LDS or DPP, the ReLU folded into the
 //     quantiser's clamp, per-channel constants by broadcast ds_read_b128.  ~10 vector instructions per output element instead
 //     of ~20; the code tile (1 B per element) goes through LDS once so that the stores are whole rows.
-template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false>
+// R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - the upper bound cap6_nan on top of the kernel's ReLU, in fp32 before the value is stored
+// or quantised (conv_epilogue.h); single-layer instantiations only (the dual entry point refuses it)
+template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false>
 __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : (SWAP && BN == 64 && ADIR && !ASYM ? 5 : SWAP && BN == 128 && ADIR && !ASYM ? 3 : ADIR || BN == 64 ? (ASYM ? 3 : 4) : 3))) void conv_i8_mfma_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w, float* __restrict__ out, const float* __restrict__ bias,
     const int32_t* __restrict__ wsum, const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -430,6 +432,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
           const f32x4 wo = *reinterpret_cast<const f32x4*>(par + (3 * BN + cb + 4 * q) * 4);
           y[q] = f32x4{y[q].x + s0f * wo.x, y[q].y + s0f * wo.y, y[q].z + s0f * wo.z, y[q].w + s0f * wo.w};
         }
+        if constexpr (R6) y[q] = cap6_nan4(y[q]);   // (the lower bound is folded into the quantiser)
       }
       uint32_t wq[4];
       bool uq[4];
@@ -561,6 +564,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
           const int64_t at = row * g.K + col;
           if (ep.residual) v = f32x4{v.x + idt[it].x, v.y + idt[it].y, v.z + idt[it].z, v.w + idt[it].w};
           if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
+          if constexpr (R6) v = cap6_nan4(v);
           if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
           if (ep.mm) { mm_add(v.x); mm_add(v.y); mm_add(v.z); mm_add(v.w); }
           if (ep.codes) {
@@ -614,6 +618,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
       if (ASYM) v = v + s0r[ASYM ? i : 0] * woff[ASYM ? j : 0];
       if (ep.residual) v = v + ep.residual[at];
       if (ep.relu) v = relu_nan(v);
+      if constexpr (R6) v = cap6_nan(v);
       if (out) __builtin_nontemporal_store(v, out + at);
       if (ep.mm) mm_add(v);
       if (ep.codes) ep.codes[at] = (uint8_t)eq.exact(v);
@@ -796,34 +801,42 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
     if (mm_count) *mm_count = nwg;
   }
 #define DLMCQ_CONV_ARGS dim3((uint32_t)nwg), dim3(256), 0, st, xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, s2
-  if (seg2) {
-    if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, true, true>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, true, true>), DLMCQ_CONV_ARGS);
-  } else if (ep.w_off && plan.swap && ep.codes && !out && !ep.residual && K % plan.bn == 0 && aligned16(ep.codes)) {
-    if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, true>), DLMCQ_CONV_ARGS);
-    else if (plan.bn == 192) hipLaunchKernelGGL((conv_i8_mfma_kernel<192, false, true, true, 0, true>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, true>), DLMCQ_CONV_ARGS);
-  } else if (ep.w_off) {     // asymmetric per-channel weights (activations direct: the row sums come from their fragments)
-    if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true>), DLMCQ_CONV_ARGS);
-  } else if (swap_ok && plan.bn == 256) {
-    if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, true, false, 0, true>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, false, false, 0, true>), DLMCQ_CONV_ARGS);
-  } else if (swap_ok) {
-    if (plan.bn == 64) {
-      if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, true>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false, false, 0, true>), DLMCQ_CONV_ARGS);
+  // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound (the dual entry point refuses it)
+  auto launch = [&](auto r6) {
+    constexpr bool R6 = decltype(r6)::value;
+    if (seg2) {
+      if constexpr (!R6) {
+        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, true, true>), DLMCQ_CONV_ARGS);
+        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, true, true>), DLMCQ_CONV_ARGS);
+      }
+    } else if (ep.w_off && plan.swap && ep.codes && !out && !ep.residual && K % plan.bn == 0 && aligned16(ep.codes)) {
+      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
+      else if (plan.bn == 192) hipLaunchKernelGGL((conv_i8_mfma_kernel<192, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
+    } else if (ep.w_off) {     // asymmetric per-channel weights (activations direct: the row sums come from their fragments)
+      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, false, R6>), DLMCQ_CONV_ARGS);
+    } else if (swap_ok && plan.bn == 256) {
+      if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+    } else if (swap_ok) {
+      if (plan.bn == 64) {
+        if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+        else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+      } else {
+        if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
+      }
+    } else if (!plan.adir) {
+      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false, false, 0, false, R6>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false, false, 0, false, R6>), DLMCQ_CONV_ARGS);
     } else {
-      if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, true>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false, false, 0, true>), DLMCQ_CONV_ARGS);
+      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, false, R6>), DLMCQ_CONV_ARGS);
     }
-  } else if (!plan.adir) {
-    if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false>), DLMCQ_CONV_ARGS);
-  } else {
-    if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true>), DLMCQ_CONV_ARGS);
-    else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true>), DLMCQ_CONV_ARGS);
-  }
+  };
+  if (ep.relu == DLMCQ_ACT_RELU6) launch(std::true_type{});
+  else launch(std::false_type{});
 #undef DLMCQ_CONV_ARGS
   return launch_status();
 }
@@ -832,7 +845,7 @@ static ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const 
                         int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g) {
   ConvEpi ep{};
   ep.residual = residual;
-  ep.relu = relu != 0;
+  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
   ep.codes = static_cast<uint8_t*>(codes);
   ep.q_scale = q_scale;
   ep.q_zp = q_zero_point;
@@ -939,6 +952,7 @@ extern "C" int dlmcq_conv2d_i8_nhwc_dual(const void* x, const int8_t* w, float* 
                                          int32_t x2_is_unsigned, int32_t relu, void* codes, const float* q_scale,
                                          const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
                                          float q_ste_g, dlmcq_stream_t stream) {
+  if (relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (no dual instantiation carries ReLU6's bound)
   ConvSeg2 s2{};
   const int rc = make_seg2(s2, N, K, x2, w2, bias2, wsum2, in_scale2, in_zero_point2, w_scale2, H2, W2, C2, R2, S2, stride2,
                            pad2, dilation2, x2_is_unsigned);
@@ -1012,6 +1026,7 @@ extern "C" int dlmcq_x_conv2d_i8_tuned(const void* x, const int8_t* w, float* ou
                                        int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream,
                                        int32_t bn, int32_t adir, int32_t pp_nbuf, int32_t pp_wps) {
   const ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  if (pp_wps != 0 && relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (the lab variants below have no ReLU6 instantiations)
   if (pp_wps > 0) {
     const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1, Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
     if (C % CV_BK || K % bn || P < 1 || Q < 1 || N * P * Q >= (1ll << 31)) return DLMCQ_EINVAL;

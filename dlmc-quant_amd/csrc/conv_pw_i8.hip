@@ -40,7 +40,8 @@ constexpr int PW_WPS(int c, int bn) { return c >= 1024 ? 1 : (c >= 512 ? 3 : 4);
 
 // LAB (lab library only, what-bounds-the-block experiments: results are garbage): 1 = clock stamps of one wave, 2 = no activation
 // loads, 4 = no MFMAs, 6 = epilogue without its arithmetic, 7 = no epilogue and no stores, 8 = no stores, 9 = non-temporal stores
-template <int C, int BN, int NTP, bool ASYM, int NW, int LAB = 0>
+// R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan in fp32 before the quantiser (whose byte conversion is the lower bound)
+template <int C, int BN, int NTP, bool ASYM, int NW, int LAB = 0, bool R6 = false>
 __global__ __launch_bounds__(NW * 64, PW_WPS(C, BN)) void conv_pw_i8_kernel(PwArgs a, ConvEpi ep) {
   constexpr int S = C / 64;             // 64-byte K steps
   constexpr int NA = C / 32;            // A fragments (16 bytes per lane each)
@@ -234,6 +235,7 @@ __global__ __launch_bounds__(NW * 64, PW_WPS(C, BN)) void conv_pw_i8_kernel(PwAr
             yb = yb + s0f2 * f32x2{wo.z, wo.w};
           }
           y[q] = f32x4{ya.x, ya.y, yb.x, yb.y};
+          if constexpr (R6) y[q] = cap6_nan4(y[q]);
         }
         uint32_t wq[4];
         eq.code4n_plain(y, wq);
@@ -301,7 +303,7 @@ bool conv_pw_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int6
   return true;
 }
 
-template <int C, int BN, bool ASYM, int LAB = 0>
+template <int C, int BN, bool ASYM, int LAB = 0, bool R6 = false>
 static int pw_go(const PwArgs& a0, const ConvEpi& ep, hipStream_t st) {
   constexpr int WPS = PW_WPS(C, BN);
   constexpr int LDS1 = C * BN + 4 * BN * 4, STG = 4 * 32 * (BN + 16);   // weights + constants; one 4-wave workgroup's code stages
@@ -326,7 +328,7 @@ static int pw_go(const PwArgs& a0, const ConvEpi& ep, hipStream_t st) {
   const int maxg = ((a.nblk + NW - 1) / NW + 7) & ~7;
   if (ngroups > maxg) ngroups = maxg;
   constexpr int NTP = BN == 192 ? 3 : (C >= 512 ? 1 : 2);      // (64-wide slices: one pass of two blocks)
-  auto kern = conv_pw_i8_kernel<C, BN, NTP, ASYM, NW, LAB>;
+  auto kern = conv_pw_i8_kernel<C, BN, NTP, ASYM, NW, LAB, R6>;
   static bool attr_set = false;
   if (!attr_set) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -359,8 +361,11 @@ int conv_pw_launch(const int8_t* x, const int8_t* w, const float* bias, const in
 #undef DLMCQ_PWL
 #endif
   if (lab) return DLMCQ_EINVAL;
-#define DLMCQ_PW(CC, BB)                                         \
-  if (C == CC && bn == BB) return asym ? pw_go<CC, BB, true>(a, ep, st) : pw_go<CC, BB, false>(a, ep, st);
+  const bool r6 = ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
+#define DLMCQ_PW(CC, BB)                                                                                       \
+  if (C == CC && bn == BB)                                                                                     \
+    return r6 ? (asym ? pw_go<CC, BB, true, 0, true>(a, ep, st) : pw_go<CC, BB, false, 0, true>(a, ep, st))     \
+              : (asym ? pw_go<CC, BB, true>(a, ep, st) : pw_go<CC, BB, false>(a, ep, st));
   DLMCQ_PW_PAIRS(DLMCQ_PW)
 #undef DLMCQ_PW
   return DLMCQ_EINVAL;

@@ -322,6 +322,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_pwr_i8_kernel(PwrArgs a,
 bool conv_pwr_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
                       int32_t dilation, const ConvEpi& ep, const float* out, const ConvSeg2* seg2) {
   if (R != 1 || S != 1 || pad != 0 || dilation != 1 || !ep.relu || ep.w_off) return false;
+  if (ep.relu == DLMCQ_ACT_RELU6) return false;                 // (ReLU only: ReLU6 block ends take the tiled kernel)
   if (ep.codes ? !epi_plain(ep) : !out) return false;            // (other quantisers: the tiled kernel)
   const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
   const int64_t M = N * P * Q;

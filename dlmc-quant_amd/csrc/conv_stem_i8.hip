@@ -147,7 +147,8 @@ constexpr int ST_EP_LD = 68;   // floats per staged row (64 + 4 pad)
 // consecutive channels of ONE pixel (the weight fragments are loaded in the matching row order), so the epilogue needs no
 // transposition through LDS, folds the ReLU into the quantiser's clamp and reads its per-channel constants, pre-multiplied once
 // per workgroup, as broadcast ds_read_b128; the per-pixel code sum of ASYM is a per-lane scalar.
-template <int R, bool ASYM = false, bool SWAP = false>
+// R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan on top of the ReLU, in fp32 before the value is stored or quantised
+template <int R, bool ASYM = false, bool SWAP = false, bool R6 = false>
 __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __restrict__ x, const int8_t* __restrict__ w,
                                                            float* __restrict__ out, const float* __restrict__ bias,
                                                            const int32_t* __restrict__ wsum, const float* __restrict__ s_in,
@@ -296,6 +297,7 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
             yb = yb + s0f2 * f32x2{wo.z, wo.w};
           }
           y[q4] = f32x4{ya.x, ya.y, yb.x, yb.y};
+          if constexpr (R6) y[q4] = cap6_nan4(y[q4]);     // (the lower bound is folded into the quantiser)
         }
         uint32_t wq[4];
         if (plainq) {
@@ -346,6 +348,7 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
       if (row < g.M && col < g.K) {
         const int64_t at = row * g.K + col;
         if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
+        if constexpr (R6) v = cap6_nan4(v);
         if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
         if (ep.codes) __builtin_nontemporal_store(eq.code4(v), reinterpret_cast<uint32_t*>(ep.codes + at));
       }
@@ -692,7 +695,7 @@ static int stem_launch(const void* xpad, const int8_t* w, float* out, const floa
   g.pdiv = make_fastdiv((uint32_t)P);
   ConvEpi ep{};
   ep.w_off = w_offset;
-  ep.relu = relu != 0;
+  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
   ep.codes = static_cast<uint8_t*>(codes);
   ep.q_scale = q_scale;
   ep.q_zp = q_zero_point;
@@ -708,22 +711,28 @@ static int stem_launch(const void* xpad, const int8_t* w, float* out, const floa
 #define DLMCQ_STEM_ARGS grid, dim3(256), 0, st, xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep
 #define DLMCQ_STEM_CASE(RR) \
   case RR:                  \
-    if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<RR, true>), DLMCQ_STEM_ARGS); \
-    else hipLaunchKernelGGL((conv_stem_i8_kernel<RR, false>), DLMCQ_STEM_ARGS);         \
+    if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<RR, true, false, R6>), DLMCQ_STEM_ARGS); \
+    else hipLaunchKernelGGL((conv_stem_i8_kernel<RR, false, false, R6>), DLMCQ_STEM_ARGS);         \
     break;
-  // 3 x 3 first layers that emit only codes (RepVGG, MobileOne): the swapped epilogue
-  if (R == 3 && !out && codes && K % 64 == 0 && aligned16(codes)) {
-    if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, true>), DLMCQ_STEM_ARGS);
-    else hipLaunchKernelGGL((conv_stem_i8_kernel<3, false, true>), DLMCQ_STEM_ARGS);
-    return launch_status();
-  }
-  switch ((int)R) {
-    DLMCQ_STEM_CASE(1) DLMCQ_STEM_CASE(2) DLMCQ_STEM_CASE(3) DLMCQ_STEM_CASE(4) DLMCQ_STEM_CASE(5) DLMCQ_STEM_CASE(6)
-    default:
-      if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<7, true>), DLMCQ_STEM_ARGS);
-      else hipLaunchKernelGGL((conv_stem_i8_kernel<7, false>), DLMCQ_STEM_ARGS);
-      break;
-  }
+  // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound
+  auto launch = [&](auto r6) {
+    constexpr bool R6 = decltype(r6)::value;
+    // 3 x 3 first layers that emit only codes (RepVGG, MobileOne): the swapped epilogue
+    if (R == 3 && !out && codes && K % 64 == 0 && aligned16(codes)) {
+      if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, true, R6>), DLMCQ_STEM_ARGS);
+      else hipLaunchKernelGGL((conv_stem_i8_kernel<3, false, true, R6>), DLMCQ_STEM_ARGS);
+      return;
+    }
+    switch ((int)R) {
+      DLMCQ_STEM_CASE(1) DLMCQ_STEM_CASE(2) DLMCQ_STEM_CASE(3) DLMCQ_STEM_CASE(4) DLMCQ_STEM_CASE(5) DLMCQ_STEM_CASE(6)
+      default:
+        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<7, true, false, R6>), DLMCQ_STEM_ARGS);
+        else hipLaunchKernelGGL((conv_stem_i8_kernel<7, false, false, R6>), DLMCQ_STEM_ARGS);
+        break;
+    }
+  };
+  if (ep.relu == DLMCQ_ACT_RELU6) launch(std::true_type{});
+  else launch(std::false_type{});
 #undef DLMCQ_STEM_CASE
 #undef DLMCQ_STEM_ARGS
   return launch_status();
@@ -782,6 +791,7 @@ extern "C" int dlmcq_conv2d_i8_stem_pool_fused(const void* xpad, const int8_t* w
                                                int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
                                                const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                                int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
+  if (relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
   if (N < 0 || Hp < 1 || Wp < 1 || K < 4 || K > 64 || (K & 3) || R < 1 || R > ST_MAXR || S < 1 || S > 8 || stride < 1)
     return DLMCQ_EINVAL;
   if (Hp < R || Wp < S) return DLMCQ_EINVAL;

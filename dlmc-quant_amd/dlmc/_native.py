@@ -35,6 +35,7 @@ PIPELINED = 0x1000       # DLMCQ_PIPELINED (opt-in): the persistent, software-pi
 ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE = 1, 2, 3, 4, 5, 6, 7
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
              ROUTE_DWM: "conv_dwm", ROUTE_HALO3X3_PIPE: "conv3x3_pipe"}     # the profile tag (bench.py's kernel families) of each route
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2   # DLMCQ_ACT_*: the `relu` argument of the fused convolution entry points
 Y_DEQUANT, Y_CODES = 0, 1
 CODES_NONE, CODES_I8, CODES_P4 = 0, 1, 2
 MINMAX_ABSMAX, MINMAX_MINMAX, MINMAX_NEGMIN = 0, 1, 2

@@ -425,16 +425,26 @@ class EmitCodes:
         return self.form | (N.EMIT_SHIFT128 if self.shift128 else 0)
 
 
+def _act(relu, act):
+    """The activation argument of the fused entry points (DLMCQ_ACT_*): `act` when given (N.ACT_NONE / ACT_RELU / ACT_RELU6),
+    else ReLU or nothing as `relu` says."""
+    if act is None:
+        return int(bool(relu))
+    if act not in (N.ACT_NONE, N.ACT_RELU, N.ACT_RELU6):
+        raise ValueError(f"unknown activation {act!r} (dlmc._native.ACT_NONE / ACT_RELU / ACT_RELU6)")
+    return int(act)
+
+
 def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding=0, dilation=1,
               residual=None, relu=False, emit=None, want_out=True, w_offset=None, force_tiled=False, pipelined=False, observe=False,
-              out_chunk_major=False):
+              out_chunk_major=False, act=None):
     """Fused int8 conv / linear on the matrix cores.  `codes`: uint8/int8 activation codes, logically
     (N, C, H, W) in channels_last memory, or (N, C) for a linear layer.  Returns fp32 (N, K, P, Q) in
     channels_last memory (or (N, K)).
 
     Epilogue options (dlmcq_conv2d_i8_nhwc_fused): `residual` (fp32, the output's shape and layout) is added,
-    `relu` applied, and with `emit=EmitCodes(...)` the consumer's activation codes of the result are written as
-    well; the return value is then `(out, out_codes)`, `out` being None when `want_out=False`.
+    `relu` applied (or the activation `act` names: `act=N.ACT_RELU6` is F.relu6), and with `emit=EmitCodes(...)` the consumer's
+    activation codes of the result are written as well; the return value is then `(out, out_codes)`, `out` being None when `want_out=False`.
     `w_offset` ([K] fp32): asymmetric per-channel weights w' = qw * s_w[k] + w_offset[k] (dlmcq_conv2d_i8_nhwc_asym).
     `force_tiled` (DLMCQ_FORCE_TILED): the generic tiled kernel even where the library's dispatch would pick a specialised one -
     the same results bit for bit; tests compare the two on one tensor, tools time them on one box.  `pipelined` (DLMCQ_PIPELINED, opt-in):
@@ -462,7 +472,8 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         if linear:
             return torch.empty((n, K), dtype=dtype, device=codes.device)
         return torch.empty((n, K, P, Q), dtype=dtype, device=codes.device, memory_format=torch.channels_last)
-    fused = residual is not None or relu or emit is not None or w_offset is not None or (observe and want_out)
+    act = _act(relu, act)
+    fused = residual is not None or act or emit is not None or w_offset is not None or (observe and want_out)
     if not want_out and emit is None:
         raise ValueError("conv2d_i8: nothing to produce (want_out=False without emit)")
     if w_offset is not None:
@@ -509,7 +520,7 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         if w_offset is not None:
             def call(extra=0):
                 return N.lib.dlmcq_conv2d_i8_nhwc_asym(
-                    *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), int(bool(relu)), N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
+                    *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
                     lo, hi, form | extra, g, N.stream_ptr())
         elif observe and out is not None:
             cap = int(N.lib.dlmcq_conv2d_i8_observed_partials(n * P * Q, K))
@@ -518,12 +529,12 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
 
             def call(extra=0):
                 return N.lib.dlmcq_conv2d_i8_nhwc_fused_observed(
-                    *args, N.ptr(residual), int(bool(relu)), N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
+                    *args, N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
                     N.ptr(partials), 3 * cap, ctypes.byref(count), N.stream_ptr())
         else:
             def call(extra=0):
                 return N.lib.dlmcq_conv2d_i8_nhwc_fused(
-                    *args, N.ptr(residual), int(bool(relu)), N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
+                    *args, N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
                     N.stream_ptr())
         cm_bits = 0
         if icm or ocm:
@@ -551,10 +562,10 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
 
 
 def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, stride=1, padding=0, relu=False, emit=None, want_out=True,
-                 force_tiled=False):
+                 force_tiled=False, act=None):
     """Depthwise convolution on activation codes (dlmcq_conv2d_dw_i8_nhwc).  codes: (N, C, H, W) uint8/int8 channels_last,
     C % 4 == 0; wq: int8 [R, S, C] (tap-major); per-channel w_scale / w_offset / bias [C].  Returns fp32 (N, C, P, Q)
-    channels_last, or `(out, codes)` with `emit`."""
+    channels_last, or `(out, codes)` with `emit`.  `relu` / `act` as in conv2d_i8."""
     _no_shift(emit, "conv2d_dw_i8")
     N.require_gpu(codes, wq)
     n, c, h, w_ = codes.shape
@@ -587,7 +598,7 @@ def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, strid
     def call(extra=0):
         return N.lib.dlmcq_conv2d_dw_i8_nhwc(
             N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
-            n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), int(bool(relu)), N.ptr(out_codes),
+            n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
             N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.stream_ptr())
     # (the profile tag - conv_dw: the vector kernels, conv_dwm: the matrix-core kernel - from the library's own dispatch, DLMCQ_ROUTE_ONLY)
     tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_dw"
@@ -952,12 +963,14 @@ def quantize_weight_stem(w, scale, lo, hi):
 
 
 def conv2d_i8_stem(xpad, wq, wsum, bias, in_scale, in_zp, w_scale, S, stride=1, relu=False, emit=None, want_out=True, pool=False,
-                   w_offset=None, channels=4):
+                   w_offset=None, channels=4, act=None):
     """The first-layer convolution on padded NHWC4 codes (quantize_pad_nhwc4 / quantize_weight_stem).  Returns fp32
     (N, K, P, Q) channels_last, or `(out, codes)` with `emit` (see conv2d_i8).  `pool=True` (K <= 64): followed by
     MaxPool2d(3, 2, 1) in the same kernel - the results are the pooled tensors.  `w_offset` ([K] fp32, with the image's real
-    channel count `channels`): asymmetric per-channel weights (dlmcq_conv2d_i8_stem_asym; not with `pool`)."""
+    channel count `channels`): asymmetric per-channel weights (dlmcq_conv2d_i8_stem_asym; not with `pool`).  `relu` / `act` as in
+    conv2d_i8 (the pooling kernel: ReLU only)."""
     _no_shift(emit, "conv2d_i8_stem")
+    act = _act(relu, act)
     N.require_gpu(xpad, wq)
     n, hp, wp, _ = xpad.shape
     K_, R = wq.shape[0], wq.shape[1]
@@ -995,13 +1008,13 @@ def conv2d_i8_stem(xpad, wq, wsum, bias, in_scale, in_zp, w_scale, S, stride=1, 
                        lambda: N.check(N.lib.dlmcq_conv2d_i8_stem_asym(
                            N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
                            N.ptr(w_offset), int(channels), n, hp, wp, K_, R, int(S), int(stride), int(xpad.dtype == torch.uint8),
-                           int(bool(relu)), N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.stream_ptr())),
+                           act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.stream_ptr())),
                        2 * n * K_ * ((hp - R) // stride + 1) * ((wp - S) // stride + 1) * R * S * int(channels))
         return (out, out_codes) if emit is not None else out
     PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
                    lambda: N.check((N.lib.dlmcq_conv2d_i8_stem_pool_fused if pool else N.lib.dlmcq_conv2d_i8_stem_fused)(
                        N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
-                       n, hp, wp, K_, R, int(S), int(stride), int(xpad.dtype == torch.uint8), int(bool(relu)), N.ptr(out_codes),
+                       n, hp, wp, K_, R, int(S), int(stride), int(xpad.dtype == torch.uint8), act, N.ptr(out_codes),
                        N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.stream_ptr())),
                    2 * n * K_ * ((hp - R) // stride + 1) * ((wp - S) // stride + 1) * R * S * 3)
     return (out, out_codes) if emit is not None else out

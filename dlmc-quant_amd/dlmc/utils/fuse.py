@@ -151,11 +151,14 @@ def _frozen_spec_(mod, kind):
 class _PlanLayer(nn.Module):
     """Common part of the plan nodes: frozen quantiser constants, the consumer's emit spec, pooling on codes."""
 
-    def __init__(self, layer, spec, relu=False, emit=None, want_out=True, pool=None):
+    def __init__(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False):
         super().__init__()
         self.layer = layer
         self.act, w_scale, self.w_lo, self.w_hi, self.kind, w_off, self._w_codes = spec
         self.relu, self.emit, self.want_out, self.pool = bool(relu), emit, bool(want_out), pool
+        # ReLU6 fused into the epilogue (DLMCQ_ACT_RELU6).  `relu` keeps meaning ReLU alone: the chain / dual / block-end decisions and
+        # the kernels that know no upper bound read it, and they leave ReLU6 layers alone
+        self.relu6 = bool(relu6)
         k = layer.weight.shape[0]
         # channel counts that are no multiple of 64 (the K step of the matrix-core kernel) are zero-padded: padded output
         # channels have zero weights and bias, so their value is 0 and their code is the consumer's code of 0
@@ -210,6 +213,10 @@ class _PlanLayer(nn.Module):
     def _zp(self, codes):
         """The zero point that goes with `codes`: int8 codes of an unsigned quantiser are shifted codes (see __init__)."""
         return self.zp_shift if (codes.dtype == torch.int8 and self.act.lo >= 0) else self.act.zp
+
+    def _act_arg(self):
+        """The layer's activation as the kernels' `act` argument (DLMCQ_ACT_*)."""
+        return N.ACT_RELU6 if self.relu6 else (N.ACT_RELU if self.relu else N.ACT_NONE)
 
     def _finish(self, out, codes):
         if self.pool is not None:
@@ -317,9 +324,9 @@ class Int8Layer(_PlanLayer):
         kw = self._conv_kw()
         if self.w_off is not None:
             kw["w_offset"] = self.w_off
-        if self.relu or residual is not None or emit is not None or self.w_off is not None:
+        if self.relu or self.relu6 or residual is not None or emit is not None or self.w_off is not None:
             res = K.conv2d_i8(codes, self.wq, self.wsum, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale,
-                              residual=residual, relu=self.relu, emit=emit, want_out=self.want_out,
+                              residual=residual, act=self._act_arg(), emit=emit, want_out=self.want_out,
                               out_chunk_major=getattr(self, "out_cm", False), **kw)
             out, out_codes = res if emit is not None else (res, None)
         else:
@@ -351,7 +358,7 @@ class DwInt8Layer(Int8Layer):
         numel = self._real_numel(codes)
         emit = self._emit_for(codes.shape[0], self.k, *self._out_hw(codes))
         res = K.conv2d_dw_i8(codes, self.wq, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale, self.w_off,
-                             stride=lay.stride[0], padding=lay.padding[0], relu=self.relu, emit=emit, want_out=self.want_out)
+                             stride=lay.stride[0], padding=lay.padding[0], act=self._act_arg(), emit=emit, want_out=self.want_out)
         out, out_codes = res if emit is not None else (res, None)
         return self._finish(out, out_codes)
 
@@ -459,6 +466,8 @@ def _dwpw_pass(gm, report):
         if type(dw) is not DwInt8Layer or len(nd.args) != 1:
             continue
         lay = dw.layer
+        if dw.relu6:          # (the fused unit's kernel: ReLU only)
+            continue
         if not (tuple(lay.weight.shape[2:]) == (3, 3) and lay.stride[0] == 1 and lay.padding[0] == 1 and lay.dilation[0] == 1 and dw.pool is None and
                 dw.emit is not None and not dw.want_out and (dw.emit.lo, dw.emit.hi) == (0, 255) and not dw.emit_shift and dw.k_pad % 64 == 0):
             continue
@@ -470,7 +479,7 @@ def _dwpw_pass(gm, report):
             continue
         npw = next(iter(g1.users))
         pw = modules.get(npw.target) if npw.op == "call_module" else None
-        if type(pw) is not Int8Layer or npw.args != (g1,):
+        if type(pw) is not Int8Layer or npw.args != (g1,) or pw.relu6:
             continue
         pl = pw.layer
         if not (pl.weight.dim() == 4 and tuple(pl.weight.shape[2:]) == (1, 1) and pl.stride[0] == 1 and pl.padding[0] == 0 and pw.pool is None and
@@ -502,7 +511,7 @@ def _pointwise(plan):
     lay = plan.layer
     return (type(plan) is Int8Layer and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and lay.stride[0] == 1 and
             lay.padding[0] == 0 and plan.w_off is None and plan.pool is None and plan.k_pad == plan.k and plan.c_pad == plan.c and
-            not plan.act.needs_g)
+            not plan.act.needs_g and not plan.relu6)          # (the chain kernel: ReLU only)
 
 
 def _chain_pass(gm, report):
@@ -667,13 +676,13 @@ class StemLayer(_PlanLayer):
         pad, st = lay.padding[0], lay.stride[0]
         k, _, r, s = lay.weight.shape
         emit = self._emit_for(x.shape[0], k, (x.shape[2] + 2 * pad - r) // st + 1, (x.shape[3] + 2 * pad - s) // st + 1)
-        in_kernel = self.pool == (3, 2, 1) and k <= 64 and self.w_off is None      # conv + ReLU + MaxPool2d(3, 2, 1) + quantiser: one kernel
+        in_kernel = self.pool == (3, 2, 1) and k <= 64 and self.w_off is None and not self.relu6   # conv + ReLU + MaxPool2d(3, 2, 1) + quantiser: one kernel
         # an unsigned image quantiser's codes go into the padded buffer re-centred (`code - 128`: what the matrix cores multiply),
         # so the first-layer kernels need not xor every operand fragment they read; the zero point moves with them
         shifted = act.lo >= 0
         xpad = K.quantize_pad_nhwc4(x, act.scale, act.zp, act.lo, act.hi, act.form, pad, g=act.g(numel), shift128=shifted)
         res = K.conv2d_i8_stem(xpad, self.wq, self.wsum, lay.bias, self._in_scale(numel), self.zp_shift if shifted else act.zp, self.w_scale, s, stride=st,
-                               relu=self.relu, emit=emit, want_out=self.want_out, pool=in_kernel, w_offset=self.w_off, channels=self.c)
+                               act=self._act_arg(), emit=emit, want_out=self.want_out, pool=in_kernel, w_offset=self.w_off, channels=self.c)
         out, out_codes = res if emit is not None else (res, None)
         return (out, out_codes) if in_kernel else self._finish(out, out_codes)
 
@@ -688,13 +697,14 @@ class FusionReport:
 
     def __init__(self):
         self.layers = self.relu = self.residual = self.emit = self.fp32_outputs = self.stem = self.pooled = self.dual = 0
+        self.relu6 = 0        # ReLU6 (nn.ReLU6, nn.Hardtanh(0, 6), F.relu6, F.hardtanh(x, 0, 6)) fused; `relu` counts ReLU alone
         self.chained = 0      # block end + next block's 1x1 pairs running as one kernel
         self.chunk_major = 0  # fp32 block outputs kept chunk-major between two kernels that walk them chunk by chunk (_block_layout_pass)
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
         self.skipped = []
 
     def __repr__(self):
-        return (f"FusionReport(int8 layers={self.layers}, relu fused={self.relu}, residual fused={self.residual}, "
+        return (f"FusionReport(int8 layers={self.layers}, relu fused={self.relu}, relu6 fused={self.relu6}, residual fused={self.residual}, "
                 f"code-emitting={self.emit}, fp32 outputs kept={self.fp32_outputs}, stem layers={self.stem}, "
                 f"pools on codes={self.pooled}, dual (conv + shortcut conv) kernels={self.dual}, chained pairs={self.chained} (fp32 outputs chunk-major: {self.chunk_major}), "
                 f"depthwise + pointwise units={self.dwpw}, "
@@ -730,6 +740,27 @@ def _is_relu(node, modules):
     if node.op == "call_function":
         return node.target in _RELU_FNS
     return node.op == "call_method" and node.target in ("relu", "relu_")
+
+
+def _is_relu6(node, modules):
+    """ReLU6 in the forms the plan fuses: nn.ReLU6, nn.Hardtanh(0, 6), F.relu6 (inplace or not), F.hardtanh(x, 0, 6).  Its own
+    predicate - _is_relu is shared with EagerFused, whose kernels know ReLU alone."""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        return isinstance(m, nn.Hardtanh) and type(m) in (nn.ReLU6, nn.Hardtanh) and m.min_val == 0.0 and m.max_val == 6.0
+    if node.op != "call_function":
+        return False
+    if node.target is F.relu6:
+        return len(node.args) == 1 and set(node.kwargs) <= {"inplace"}
+    if node.target in (F.hardtanh, F.hardtanh_):
+        names = ("min_val", "max_val", "inplace") if node.target is F.hardtanh else ("min_val", "max_val")
+        if len(node.args) > 1 + len(names) or not set(node.kwargs) <= set(names):
+            return False
+        given = dict(zip(names, node.args[1:]), **node.kwargs)
+        lo, hi = given.get("min_val", -1.0), given.get("max_val", 1.0)
+        return (isinstance(lo, (int, float)) and isinstance(hi, (int, float)) and not isinstance(lo, bool) and not isinstance(hi, bool)
+                and float(lo) == 0.0 and float(hi) == 6.0)
+    return False
 
 
 def _pool_params(node, modules):
@@ -943,7 +974,8 @@ def _codes_from_blob(mod_name, blob, layer):
     return q.reshape(rec["shape"]).to(torch.int16)
 
 
-def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True):
+def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
+                   relu6=True):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -957,7 +989,10 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     W4A8, batch 1024, the unit takes 270 us either way at 28^2 and 14^2 (148 + 123 and 108 + 114 us as two launches) - both halves
     are bound by their vector arithmetic (~24 instructions per depthwise element), which fusing does not remove.
     `block_layout=False` keeps every fp32 block tensor row-major (channels_last) instead of chunk-major between two chain kernels
-    (_block_layout_pass; A/B and tests)."""
+    (_block_layout_pass; A/B and tests).
+    `relu6=False` keeps every ReLU6 (nn.ReLU6, nn.Hardtanh(0, 6), F.relu6, F.hardtanh(x, 0, 6)) a separate op after an fp32 output
+    instead of fusing it into the layer's epilogue (DLMCQ_ACT_RELU6) - the plan before ReLU6 fusion, for A/B runs and tests.  The
+    dual, chain and depthwise + pointwise kernels know ReLU alone: a layer ending in ReLU6 runs on its own kernel."""
     if model.training:
         raise RuntimeError("fuse_inference: the plan is for inference - call model.eval() first")
     report = report if report is not None else FusionReport()
@@ -1005,7 +1040,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         if spec is None:
             continue
         # ---- the chain  layer -> (+ shortcut) -> ReLU, each link the sole user of the previous one ----
-        chain, last, residual, relu = [node], node, None, False
+        chain, last, residual, relu, act6 = [node], node, None, False, False
         users = list(last.users)
         # (the stem kernel has no shortcut input; a layer whose output channels are zero-padded to a multiple of 64 - MobileNetV2's
         #  24 / 96 / 160-channel projections, CIFAR ResNets' 16 / 32 - computes a k_pad-wide tile: the k-wide fp32 shortcut does not
@@ -1023,6 +1058,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             chain.append(users[0])
             last = users[0]
             users = list(last.users)
+        elif relu6 and len(users) == 1 and _is_relu6(users[0], modules):
+            act6 = True
+            chain.append(users[0])
+            last = users[0]
+            users = list(last.users)
         # ---- a max-pool read only by int8 layers of one quantiser runs on the codes (monotone quantiser) ----
         pool = None
         if len(users) == 1 and _pool_params(users[0], modules) is not None and modules[node.target].weight.shape[0] % 4 == 0:
@@ -1031,7 +1071,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             on_codes = cons and all(c is not None for c in cons) and len({c.key for c in cons}) == 1
             # the first-layer kernel pools in fp32 itself (any consumers); elsewhere the pool runs on the emitted codes
             in_stem = (spec[4] == "stem" and _pool_params(mp, modules) == (3, 2, 1) and modules[node.target].weight.shape[0] <= 64 and
-                       spec[5] is None)       # (the pooling first-layer kernel has no weight-offset term)
+                       spec[5] is None and not act6)   # (the pooling first-layer kernel has no weight-offset term, and ReLU alone)
             if on_codes or in_stem:
                 pool = _pool_params(mp, modules)
                 chain.append(mp)
@@ -1061,7 +1101,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         # the shortcut is itself a not-yet-planned int8 convolution read by nobody else: one dual kernel
         other = spec_of(residual) if residual is not None and residual.op == "call_module" else None
         dual = (other is not None and other[4] == "gemm" and spec[5] is None and other[5] is None and list(residual.users) == [chain[1]] and
-                modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4)
+                modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4 and not act6)   # (dual kernel: ReLU alone)
         if dry_run:       # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
             gm.add_module(name, _DryNode())
         else:
@@ -1072,7 +1112,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             spec = from_blob(node.target, spec)
             if other is not None and dual:
                 other = from_blob(residual.target, other)
-            plan = cls(modules[node.target], spec, relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool)
+            plan = cls(modules[node.target], spec, relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
             # codes of an unsigned-byte quantiser read only by matrix-core layers (no channel padding, no pooling on the way)
             # travel re-centred (see _PlanLayer.__init__); the consumers recognise them by dtype
             def takes_shifted(u):
@@ -1115,6 +1155,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         report.stem += spec[4] == "stem"
         report.pooled += pool is not None
         report.relu += relu
+        report.relu6 += act6
         report.residual += residual is not None
         report.emit += emit is not None
         report.fp32_outputs += bool(fp32_needed or emit is None)

@@ -10,6 +10,7 @@ counts; tests pin the totals to SURVEY.md section 8(d):
     ResNet-18 : 21 layers, 2 183 168 input elems/img, 11 678 912 weight elems
     ResNet-50 : 54 layers, 10 664 448 input elems/img, 25 502 912 weight elems (4.089 GMAC/img)
     RepVGG-A1 (deploy): 23 layers, 2 459 904 input elems/img, 12 783 296 weight elems
+    MobileNetV2: 53 layers, 6 767 200 input elems/img, 3 469 760 weight elems (300 774 272 MAC/img)
 """
 import torch
 from torch import nn
@@ -183,6 +184,51 @@ class MobileOneDeploy(nn.Module):
         return self.linear(torch.flatten(self.gap(x), 1))
 
 
+def _conv_bn_relu6(cin, cout, k, stride=1, groups=1):
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout),
+                         nn.ReLU6(inplace=True))
+
+
+class InvertedResidual(nn.Module):
+    """MobileNetV2's unit: 1x1 expansion (t > 1) + depthwise 3x3 + linear 1x1 projection, BN after every convolution, ReLU6 after
+    the first two; the identity shortcut where stride is 1 and the width is kept."""
+
+    def __init__(self, cin, cout, stride, t):
+        super().__init__()
+        hidden = cin * t
+        self.use_res = stride == 1 and cin == cout
+        layers = [_conv_bn_relu6(cin, hidden, 1)] if t != 1 else []
+        layers += [_conv_bn_relu6(hidden, hidden, 3, stride, groups=hidden), nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
+        self.conv = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.conv(x) if self.use_res else self.conv(x)
+
+
+class MobileNetV2(nn.Module):
+    """MobileNetV2 (public architecture, Sandler et al. 2018) in torchvision's module layout - `features.N.0` convolutions with their
+    BatchNorm at `features.N.1` (merge_bn's default mapping), `nn.ReLU6`, dropout + linear head.  Width 1.0: 3 504 872 parameters."""
+
+    SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))   # t, c, n, s
+
+    def __init__(self, num_classes=1000, dropout=0.2):
+        super().__init__()
+        cin = 32
+        feats = [_conv_bn_relu6(3, cin, 3, stride=2)]
+        for t, c, n, s in self.SETTINGS:
+            for j in range(n):
+                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t))
+                cin = c
+        feats.append(_conv_bn_relu6(cin, 1280, 1))
+        self.features = nn.Sequential(*feats)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.classifier = nn.Sequential(nn.Dropout(dropout), nn.Linear(1280, num_classes))
+        _init(self)
+
+    def forward(self, x):
+        return self.classifier(torch.flatten(self.pool(self.features(x)), 1))
+
+
 def _init(model):
     for m in model.modules():
         if isinstance(m, nn.Conv2d):
@@ -211,7 +257,12 @@ def mobileone_s1_deploy(num_classes=1000):
     return MobileOneDeploy(num_classes=num_classes)
 
 
-MODELS = {"resnet18": resnet18, "resnet50": resnet50, "repvgg_a1": repvgg_a1_deploy, "mobileone_s1": mobileone_s1_deploy}
+def mobilenet_v2(num_classes=1000):
+    return MobileNetV2(num_classes=num_classes)
+
+
+MODELS = {"resnet18": resnet18, "resnet50": resnet50, "repvgg_a1": repvgg_a1_deploy, "mobileone_s1": mobileone_s1_deploy,
+          "mobilenet_v2": mobilenet_v2}
 
 
 def layer_table(model, x):

@@ -115,6 +115,16 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
 #define DLMCQ_ROUTE_DWM 6     /* conv_dwm_i8_kernel (csrc/conv_dwm_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3_PIPE 7 /* conv3x3_pipe_i8_kernel (csrc/conv3x3_pipe_i8.hip) */
 
+/* ---- the activation of a fused epilogue: the `relu` / `relu2` / `relu3` / `dw_relu` arguments of the convolution entry points ----
+ * DLMCQ_ACT_RELU6 is  v = v < 0 ? 0 : (v > 6 ? 6 : v)  (torch.nn.functional.relu6; NaN stays NaN, -0 stays -0), applied in fp32
+ * before the value is stored or quantised.  It is implemented by dlmcq_conv2d_i8_nhwc_fused / _fused_observed / _asym,
+ * dlmcq_conv2d_dw_i8_nhwc and dlmcq_conv2d_i8_stem_fused / _stem_asym; every other entry point with an activation argument
+ * returns DLMCQ_EINVAL for it before anything is launched (dual, chain, dual-chain, dwpw, stem_pool_fused).  Every other
+ * non-zero value keeps its earlier meaning, ReLU. */
+#define DLMCQ_ACT_NONE 0
+#define DLMCQ_ACT_RELU 1
+#define DLMCQ_ACT_RELU6 2
+
 /* ---- what is written to `y` ---- */
 #define DLMCQ_Y_DEQUANT 0 /* the fake-quantised value y */
 #define DLMCQ_Y_CODES 1   /* the integer code q as fp32 (reference `quantize`, utils.py:1-2) */
@@ -383,7 +393,9 @@ int dlmcq_conv2d_i8_nhwc_f32(const void* x, const int8_t* w, float* out, const f
  * into the epilogue, so the fp32 output, the ReLU pass, the residual add and the consumer's quantise pass stop
  * being separate trips through HBM.  In order, per output element v = in_scale*w_scale[k]*SUM + bias[k]:
  *   residual != NULL : v = v + residual[n,p,q,k]          (fp32 NHWC, the output's shape: the block's shortcut)
- *   relu != 0        : v = v < 0 ? 0 : v                  (torch.relu; NaN stays NaN)
+ *   relu == 1        : v = v < 0 ? 0 : v                  (DLMCQ_ACT_RELU: torch.relu; NaN stays NaN)
+ *   relu == 2        : v = v < 0 ? 0 : (v > 6 ? 6 : v)    (DLMCQ_ACT_RELU6: F.relu6; the specialised kernels without the bound
+ *                                                          - halo-tile 3x3, pipelined 3x3, block-end pointwise - are not chosen)
  *   out != NULL      : out[n,p,q,k] = v
  *   codes != NULL    : codes[n,p,q,k] = the consumer's activation code of v: forms EMULATE / QBASE /
  *                      ZEROPOINT / SYMMETRIC of dlmcq_fake_quant_f32 with (q_scale, q_zero_point, q_lo, q_hi,
@@ -434,7 +446,7 @@ int dlmcq_conv2d_i8_nhwc_asym(const void* x, const int8_t* w, float* out, const 
 /* Depthwise 3x3 convolution (groups = channels; the MobileOne / MobileNet unit, modules/conv.py:13-19 with `groups`) on
  * activation codes, HBM-bound (1 byte in, 1 byte out): plain vector arithmetic, no matrix cores.  x: NHWC codes (uint8 if
  * x_is_unsigned), C % 4 == 0; w: int8 codes [R*S][C] (tap-major); per-channel w_scale and optional w_offset (asymmetric
- * weights as above), bias; zero padding (x' = 0).  Epilogue as dlmcq_conv2d_i8_nhwc_fused: ReLU, fp32 NHWC out and / or the
+ * weights as above), bias; zero padding (x' = 0).  Epilogue as dlmcq_conv2d_i8_nhwc_fused: ReLU or ReLU6, fp32 NHWC out and / or the
  * consumer's codes.   out = s_in * ( s_w[c] * SUM (q - zp) * qw  +  o_w[c] * SUM (q - zp) ) + bias[c]   (exact integer sums). */
 int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
                             const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N, int64_t H,
@@ -454,6 +466,7 @@ int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const fl
  *                           quantiser = the pointwise layer's input quantiser, range [0, 255]; pw_in_scale: the scale the pointwise
  *                           layer dequantises with (= q_scale, or its grad_scale value for QBase); w: int8 [K][C], K in {128, 192,
  *                           512}, with wsum / w_scale / optional w_offset / bias [K]; codes: [N][H][W][K] under (q2_*).
+ *                           dw_relu or relu = DLMCQ_ACT_RELU6: DLMCQ_EINVAL.
  */
 int dlmcq_dwpw_pack_table(const int8_t* w, const float* bias, const float* in_scale, const float* in_zero_point,
                           const float* w_scale, const float* w_offset, int64_t C, int32_t x_is_unsigned, void* table,
@@ -469,7 +482,7 @@ int dlmcq_conv2d_dwpw_i8_nhwc(const void* x, const void* dw_table, int32_t dw_as
 /*
  * Two convolutions into ONE output: out = conv(x, w) + conv(x2, w2), each dequantised with its own scales and bias
  * and summed in fp32 (one addition, as `out += identity` does it in a residual block whose shortcut is a
- * convolution), then the epilogue of dlmcq_conv2d_i8_nhwc_fused.  Both pairs must give the same [N, P, Q, K] output;
+ * convolution), then the epilogue of dlmcq_conv2d_i8_nhwc_fused (relu = DLMCQ_ACT_RELU6: DLMCQ_EINVAL).  Both pairs must give the same [N, P, Q, K] output;
  * the second pair has its own input size, channel count, filter size, stride, padding and dilation (the 1x1/2
  * downsample next to the block's last 1x1).  Neither addend is written to memory.
  */
@@ -496,7 +509,7 @@ int dlmcq_conv2d_i8_nhwc_dual(const void* x, const int8_t* w, float* out, const 
  * x: [M][C] codes; w: [K][C]; residual (required) / out: fp32 [M][K]; w2: [K2][K]; codes2: [M][K2].
  * Q must be an unsigned 8-bit quantiser (q_lo = 0, q_hi = 255: the second reduction reads uint8 codes).
  * Supported: (C, K2) in {(64,64), (64,128), (128,128), (128,256), (256,256)}, K % 64 == 0, M*K*4 < 2^31 - 64 Ki
- * (anything else: DLMCQ_EINVAL / DLMCQ_ERANGE; callers fall back to the two separate calls).
+ * (anything else: DLMCQ_EINVAL / DLMCQ_ERANGE; callers fall back to the two separate calls).  relu or relu2 = DLMCQ_ACT_RELU6: DLMCQ_EINVAL.
  * rows_per_tile: pixels per workgroup, 1..64; <= 0: 64.  x, w, w2, residual, out, codes and codes2 must be 16-byte aligned
  * (DLMCQ_EALIGN otherwise).
  */
@@ -516,7 +529,7 @@ int dlmcq_conv2d_i8_nhwc_chain(const void* x, const int8_t* w, float* out, const
  *     codes3 = Q3( ReLU?( conv1x1( Q(v), w3 ) + bias3 ) )
  * bit-identical to dlmcq_conv2d_i8_nhwc_dual followed by dlmcq_conv2d_i8_nhwc_fused on its codes.  x: [N][H][W][C] codes
  * (stride 1); x2: [N][H2][W2][C2] codes with (H2 - 1) / stride2 + 1 == H (likewise W); w: [K][C]; w2: [K][C2]; w3: [K3][K].
- * Supported: (C, C2, K3) in {(64, 64, 64), (128, 256, 128)}; K % 64 == 0; N*H*W*K*4 < 2^31 - 64 Ki.
+ * Supported: (C, C2, K3) in {(64, 64, 64), (128, 256, 128)}; K % 64 == 0; N*H*W*K*4 < 2^31 - 64 Ki.  relu or relu3 = DLMCQ_ACT_RELU6: DLMCQ_EINVAL.
  */
 int dlmcq_conv2d_i8_nhwc_dual_chain(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
                                     const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N,
@@ -551,7 +564,7 @@ int dlmcq_quantize_weight_stem_i8(const float* w, int8_t* wq, int32_t* wsum, con
 /*
  * The convolution of modules/conv.py:18-19 for such a layer: out[n,p,q,k] = in_scale*w_scale[k]*SUM (x - zp)*wq
  * + bias[k] over the padded codes (P = (Hp - R)/stride + 1, Q = (Wp - S)/stride + 1, dilation 1), then the
- * epilogue of dlmcq_conv2d_i8_nhwc_fused (ReLU, fp32 NHWC output and / or the consumer's codes).  K % 4 == 0.
+ * epilogue of dlmcq_conv2d_i8_nhwc_fused (ReLU or ReLU6, fp32 NHWC output and / or the consumer's codes).  K % 4 == 0.
  */
 int dlmcq_conv2d_i8_stem_fused(const void* xpad, const int8_t* w, float* out, const float* bias,
                                const int32_t* wsum, const float* in_scale, const float* in_zero_point,
@@ -571,7 +584,7 @@ int dlmcq_conv2d_i8_stem_asym(const void* xpad, const int8_t* w, float* out, con
 
 /*
  * dlmcq_conv2d_i8_stem_fused followed by ReLU (if asked) and nn.MaxPool2d(3, 2, 1) in ONE kernel, K <= 64: out / codes
- * are the POOLED tensor [N, (P+1)/2.., (Q+1)/2.., K].  The pool runs on the fp32 values (the reference's order: ReLU,
+ * are the POOLED tensor [N, (P+1)/2.., (Q+1)/2.., K]; relu = DLMCQ_ACT_RELU6: DLMCQ_EINVAL.  The pool runs on the fp32 values (the reference's order: ReLU,
  * max-pool, fake-quant; NaN propagates as in torch), so only the pooled quarter of the outputs is quantised and
  * nothing un-pooled is ever written.
  */
