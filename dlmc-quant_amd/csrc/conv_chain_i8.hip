@@ -576,6 +576,7 @@ static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C
                         int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
   if (relu == DLMCQ_ACT_RELU6 || relu2 == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only: the flags below read any non-zero value as ReLU)
   if (q_lo != 0 || q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
+  if (q2_form & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED)) return DLMCQ_EINVAL;   // (no other kernel, no route query here)
   const bool w3cm = (q2_form & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (q2_form & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
   // (a call without a shortcut tensor - the convolution-shortcut form - or without an output has ONE fp32 tensor: its layout is the call's)
   const bool icm = (C2 == 0 && a.residual) ? (q2_form & DLMCQ_FP32_IN_CHUNK_MAJOR) != 0 : ocm;

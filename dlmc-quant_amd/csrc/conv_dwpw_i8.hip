@@ -371,7 +371,7 @@ extern "C" int dlmcq_conv2d_dwpw_i8_nhwc(const void* x, const void* dw_table, in
   if (!aligned16(x) || !aligned16(dw_table) || !aligned16(w) || !aligned16(codes)) return DLMCQ_EALIGN;
   ConvEpi ep1{}, ep2{};
   if (q2_lo > q2_hi || q2_lo < -128 || q2_hi > 255 || q2_hi - q2_lo > 255 || q_form < DLMCQ_FORM_EMULATE || q_form > DLMCQ_FORM_SYMMETRIC ||
-      !epi_set_form(ep2, q2_form, q2_lo, q2_hi))
+      q2_form < DLMCQ_FORM_EMULATE || q2_form > DLMCQ_FORM_SYMMETRIC || !epi_set_form(ep2, q2_form, q2_lo, q2_hi))   // (no flag bits: SHIFT128 included)
     return DLMCQ_EINVAL;
   DwPwArgs a{};
   a.Wp = (int)W + 1;

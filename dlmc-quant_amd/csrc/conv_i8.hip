@@ -892,7 +892,9 @@ extern "C" int dlmcq_conv2d_i8_nhwc_fused_observed(const void* x, const int8_t* 
   if (!partials || !partials_count || !out) return DLMCQ_EINVAL;
   const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / (stride > 0 ? stride : 1) + 1;
   const int64_t Q = (W + 2 * pad - dilation * (S - 1) - 1) / (stride > 0 ? stride : 1) + 1;
-  if (partials_capacity < (int64_t)dlmcq_conv2d_i8_observed_partials(N * P * Q, K)) return DLMCQ_ESCRATCH;
+  if (K < 1 || N * P * Q < 1) return DLMCQ_EINVAL;        // (the query below is 0 there: no capacity check would stand)
+  // three planes of `observed_partials` floats each (max, min, |x| bits: ConvEpi::mm)
+  if (partials_capacity < 3 * (int64_t)dlmcq_conv2d_i8_observed_partials(N * P * Q, K)) return DLMCQ_ESCRATCH;
   ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   ep.mm = partials;
   return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,

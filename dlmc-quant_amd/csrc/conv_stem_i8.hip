@@ -626,7 +626,9 @@ extern "C" int dlmcq_quantize_pad_nhwc4(const float* x, void* out, const float* 
   if (N < 0 || C < 1 || C > 4 || H < 1 || W < 1 || pad < 0 || lo > hi || lo < -128 || hi > 255 || hi - lo > 255)
     return DLMCQ_EINVAL;
   ConvEpi q{};                          // the image quantiser, evaluated by EpiQuant (needs a non-null `codes` to resolve)
-  if (!epi_set_form(q, form, lo, hi)) return DLMCQ_EINVAL;      // (DLMCQ_EMIT_SHIFT128: the buffer holds `code - 128`, border included)
+  if ((form & ~DLMCQ_EMIT_SHIFT128) < DLMCQ_FORM_EMULATE || (form & ~DLMCQ_EMIT_SHIFT128) > DLMCQ_FORM_SYMMETRIC ||
+      !epi_set_form(q, form, lo, hi))     // (the form and DLMCQ_EMIT_SHIFT128 only: no control bits)
+    return DLMCQ_EINVAL;      // (DLMCQ_EMIT_SHIFT128: the buffer holds `code - 128`, border included)
   if (N == 0) return DLMCQ_OK;
   if (!x || !out || !scale) return DLMCQ_EINVAL;
   if (!aligned4(out)) return DLMCQ_EALIGN;

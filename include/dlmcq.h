@@ -93,6 +93,7 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
 #define DLMCQ_FP32_IN_CHUNK_MAJOR 0x2000
 #define DLMCQ_FP32_OUT_CHUNK_MAJOR 0x4000
 /* Two control bits, OR-able into the `q_form` argument of dlmcq_conv2d_i8_nhwc_fused / _asym / _dual and dlmcq_conv2d_dw_i8_nhwc.
+ * The chain, dual-chain, dwpw and quantize_pad_nhwc4 entry points return DLMCQ_EINVAL for them and for DLMCQ_PIPELINED in any form argument.
  * DLMCQ_FORCE_TILED: the call runs on the generic kernel of its family (conv_i8_mfma_kernel; conv_dw3*_i8_kernel for the
  * depthwise entry point) even where the library's dispatch would hand it to a specialised one (halo-tile 3x3, weight-resident
  * pointwise, block-end pointwise, matrix-core depthwise).  Same results bit for bit; it exists so that a specialised kernel and
@@ -420,7 +421,7 @@ int dlmcq_conv2d_i8_nhwc_fused(const void* x, const int8_t* w, float* out, const
  * (observer.hip's partial layout; capacity >= 3 * dlmcq_conv2d_i8_observed_partials(N P Q, K) floats, else DLMCQ_ESCRATCH);
  * dlmcq_minmax_finalize_f32 reduces them to what dlmcq_minmax_f32 gives for the tensor - max and min are exact, so bit for bit.
  * `*partials_count` (written on the host before the call returns) is 0 when the dispatch hands the call to a kernel without the
- * observing epilogue (the block-end pointwise kernel): observe the tensor with dlmcq_minmax_f32 then. */
+ * observing epilogue (the block-end pointwise kernel): observe the tensor with dlmcq_minmax_f32 then.  K < 1 or N P Q < 1: DLMCQ_EINVAL. */
 size_t dlmcq_conv2d_i8_observed_partials(int64_t M, int64_t K);
 int dlmcq_conv2d_i8_nhwc_fused_observed(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
                                         const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N,

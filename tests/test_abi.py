@@ -83,3 +83,26 @@ def test_a_stale_library_override_is_reported_and_ignored():
     assert r.stdout.strip().endswith(os.path.join("dlmc-quant_amd", "libdlmcq.so")) and "ignored" in r.stderr
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(env, DLMCQ_LAB_TOOLS="1"), timeout=240)
     assert r.returncode != 0 and "lab override: loading /nonexistent/libother.so" in r.stderr      # named, printed, and then a hard failure
+
+
+def test_observed_entry_point_checks_all_three_partial_planes():
+    """dlmcq_conv2d_i8_nhwc_fused_observed writes three planes of dlmcq_conv2d_i8_observed_partials(M, K) floats: a capacity of one
+    float less is DLMCQ_ESCRATCH, exactly three planes pass (answered with DLMCQ_ROUTE_ONLY: nothing is launched on the placeholder
+    pointers, whatever the library decides), and a call with no output pixels or no output channels is DLMCQ_EINVAL."""
+    from dlmc import _native as N
+    f = N.lib.dlmcq_conv2d_i8_nhwc_fused_observed
+    p = ctypes.c_void_p(4096)
+    count = ctypes.c_int64(0)
+    n, h, w, c, k = 4, 32, 32, 64, 128
+    cap = int(N.lib.dlmcq_conv2d_i8_observed_partials(n * h * w, k))
+    assert cap > 1
+
+    def call(n_, h_, w_, k_, capacity):
+        return f(p, p, p, None, p, p, None, p, n_, h_, w_, c, k_, 1, 1, 1, 0, 1, 1, None, 0, None, None, None, 0, 0,
+                 N.ROUTE_ONLY, 0.0, p, capacity, ctypes.byref(count), None)
+    assert call(n, h, w, k, cap) == -3
+    assert call(n, h, w, k, 3 * cap - 1) == -3
+    assert N.route(call(n, h, w, k, 3 * cap)) == N.ROUTE_TILED
+    assert call(n, h, w, 0, 3 * cap) == -1          # K < 1
+    assert call(0, h, w, k, 3 * cap) == -1          # N P Q < 1
+    assert call(n, h, w, k, -1) == -3
