@@ -55,7 +55,9 @@ struct DwTab {       // per channel, in LDS: two 16-byte records, each stored [p
 // when the zero point is 0, table runs per lane), here for any stride (MobileOne's four stride-2 layers).  0 = everything else.
 // R6 (every kernel of this file): ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan on top of the ReLU, in fp32 before the value is
 // stored or quantised (conv_epilogue.h)
-template <int FAST, bool R6 = false>
+// XOFF (the 3 x 3 kernels; dlmcq_conv2d_dw_i8_nhwc_xoff): a float activation offset - a border pixel's value loses o * (its out-of-bounds
+// taps' weights), ep.x_off / ep.x_tap (conv_epilogue.h xoff_border4), after the bias, before the ReLU
+template <int FAST, bool R6 = false, bool XOFF = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* __restrict__ x, const int8_t* __restrict__ w,
                                                                  float* __restrict__ out, const float* __restrict__ bias,
                                                                  const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -103,6 +105,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
   // codes-only layers: the ReLU is folded into the quantiser's clamp (code(relu(v)) = max(code(v), code(0)): conv_epilogue.h)
   const bool fold = ep.relu && !out && ep.codes;
   const EpiQuant eq(ep, fold);
+  const float xo = XOFF ? ep.x_off[0] : 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t pix = fdiv((uint32_t)i, g.cdiv);                 // (cdiv divides by C / 16 here)
     const int c16 = (int)((uint32_t)i - pix * (uint32_t)C16);
@@ -195,6 +198,8 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
           v[2 * jp] = r.x;
           v[2 * jp + 1] = r.y;
         }
+        if constexpr (XOFF)
+          if (!inside) v = xoff_sub4(v, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0, 3, 3, 1, g.H, g.W));
         vq[d] = R6 ? cap6_nan4(v) : v;
         continue;
       }
@@ -215,6 +220,8 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
         if (bias) r = r + tp.z;
         v[j] = r;
       }
+      if constexpr (XOFF)
+        if (!inside) v = xoff_sub4(v, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0, 3, 3, 1, g.H, g.W));
       if (ep.relu && !fold) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
       if constexpr (R6) v = cap6_nan4(v);
       const int64_t at = (int64_t)pix * g.C4 * 4 + c + d * 4;
@@ -237,7 +244,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3_i8_kernel(const u32x4* _
 // of channels (v_pk_mul_f32 / v_pk_add_f32 on constants stored as pairs: the same roundings, half the instructions), the
 // quantiser of both pixels behind one branch with its clamp left to v_cvt_pk_u8_f32 (EpiQuant::code4n_plain), no flag tests per
 // element.  0 = everything else, as before.  Bit-identical where both apply.
-template <int FAST, bool R6 = false>
+template <int FAST, bool R6 = false, bool XOFF = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4* __restrict__ x, const int8_t* __restrict__ w,
                                                                    float* __restrict__ out, const float* __restrict__ bias,
                                                                    const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -293,6 +300,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
   const uint32_t xw = x_signed ? 0u : 0x80808080u;
   const bool fold = ep.relu && !out && ep.codes;
   const EpiQuant eq(ep, fold);
+  const float xo = XOFF ? ep.x_off[0] : 0.0f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t pr = fdiv((uint32_t)i, g.cdiv);                  // (cdiv divides by C / 16)
     const int c16 = (int)((uint32_t)i - pr * (uint32_t)C16);
@@ -394,6 +402,10 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
           vA[2 * jp] = rA.x; vA[2 * jp + 1] = rA.y;
           vB[2 * jp] = rB.x; vB[2 * jp + 1] = rB.y;
         }
+        if constexpr (XOFF) {      // pixel A: columns w0 .. w0 + 2, pixel B: w0 + 1 .. w0 + 3
+          if (xoff_is_border(h0, w0, 3, 3, 1, g.H, g.W)) vA = xoff_sub4(vA, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0, 3, 3, 1, g.H, g.W));
+          if (xoff_is_border(h0, w0 + 1, 3, 3, 1, g.H, g.W)) vB = xoff_sub4(vB, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0 + 1, 3, 3, 1, g.H, g.W));
+        }
         const f32x4 vv[2] = {R6 ? cap6_nan4(vA) : vA, R6 ? cap6_nan4(vB) : vB};
         uint32_t ww[2];
         eq.code4n_plain(vv, ww);
@@ -429,6 +441,10 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw3p2_i8_kernel(const u32x4*
         }
         vA[j] = rA;
         vB[j] = rB;
+      }
+      if constexpr (XOFF) {
+        if (xoff_is_border(h0, w0, 3, 3, 1, g.H, g.W)) vA = xoff_sub4(vA, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0, 3, 3, 1, g.H, g.W));
+        if (xoff_is_border(h0, w0 + 1, 3, 3, 1, g.H, g.W)) vB = xoff_sub4(vB, xo, xoff_border4(ep.x_tap, C, c + d * 4, h0, w0 + 1, 3, 3, 1, g.H, g.W));
       }
       if (ep.relu && !fold) {
         vA = f32x4{relu_nan(vA.x), relu_nan(vA.y), relu_nan(vA.z), relu_nan(vA.w)};
@@ -513,12 +529,11 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw_i8_kernel(const uint32_t*
 
 using namespace dlmcq;
 
-extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
-                                       const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N,
-                                       int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                                       int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
-                                       const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
-                                       dlmcq_stream_t stream) {
+static int dw_launch(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale, const float* in_zero_point,
+                     const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S,
+                     int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
+                     const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream,
+                     const float* x_off = nullptr, const float* x_tap = nullptr) {
   if (N < 0 || H < 1 || W < 1 || C < 4 || (C & 3) || R < 1 || S < 1 || R > 7 || S > 7 || stride < 1 || pad < 0) return DLMCQ_EINVAL;
   const int64_t P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;
@@ -548,16 +563,20 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
   ep.q_hi = (float)q_hi;
   ep.q_g = q_ste_g;
   ep.q_form = q_form;
+  ep.x_off = x_off;
+  ep.x_tap = x_tap;
+  const bool xoff = x_off != nullptr;
   const int64_t total = N * P * Q * (C / 4);
   const int64_t blocks = (total + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!(ctl & DLMCQ_FORCE_TILED) && conv_dwm_applies(N, H, W, C, R, S, stride, pad, ep, out, x)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores
+  if (!(ctl & DLMCQ_FORCE_TILED) && !xoff && conv_dwm_applies(N, H, W, C, R, S, stride, pad, ep, out, x)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores
     if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DWM;
     return conv_dwm_launch(static_cast<const int8_t*>(x), w, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C,
                            x_is_unsigned ? 0 : 1, ep, st);
   }
-  if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
   const bool wide = R == 3 && S == 3 && C % 16 == 0 && C <= 2048 && aligned16(x) && (!codes || aligned16(codes));
+  if (xoff && !wide) return DLMCQ_EINVAL;           // (the border term: the 3 x 3 kernels only)
+  if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
   const bool r6 = ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
   if (wide && stride == 1 && pad == 1 && C <= 1024) {     // two output pixels per thread (LDS: 48 B per channel)
     g.cdiv = make_fastdiv((uint32_t)(C / 16));
@@ -568,7 +587,15 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
 #define DLMCQ_DWP2(...) hipLaunchKernelGGL((conv_dw3p2_i8_kernel<__VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), (size_t)(C / 16) * (3 * 17 * 16), st, \
                                            static_cast<const u32x4*>(x), w, out, bias, in_scale, in_zero_point, w_scale, w_offset, g,              \
                                            x_is_unsigned ? 0 : 1, ep)
-    if (r6) {
+    if (xoff) {
+      if (r6) {
+        if (fast == 1) DLMCQ_DWP2(1, true, true);
+        else if (fast == 2) DLMCQ_DWP2(2, true, true);
+        else DLMCQ_DWP2(0, true, true);
+      } else if (fast == 1) DLMCQ_DWP2(1, false, true);
+      else if (fast == 2) DLMCQ_DWP2(2, false, true);
+      else DLMCQ_DWP2(0, false, true);
+    } else if (r6) {
       if (fast == 1) DLMCQ_DWP2(1, true);
       else if (fast == 2) DLMCQ_DWP2(2, true);
       else DLMCQ_DWP2(0, true);
@@ -584,7 +611,15 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
 #define DLMCQ_DW3(F, ...) hipLaunchKernelGGL((conv_dw3_i8_kernel<F __VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), \
                                         F ? (size_t)(C / 16) * (17 * 16 + 9 * 16 + 9 * 8) : (size_t)C * sizeof(DwTab), st, static_cast<const u32x4*>(x), w, \
                                         out, bias, in_scale, in_zero_point, w_scale, w_offset, g, x_is_unsigned ? 0 : 1, ep)
-    if (r6) {
+    if (xoff) {
+      if (r6) {
+        if (fast == 1) DLMCQ_DW3(1, , true, true);
+        else if (fast == 2) DLMCQ_DW3(2, , true, true);
+        else DLMCQ_DW3(0, , true, true);
+      } else if (fast == 1) DLMCQ_DW3(1, , false, true);
+      else if (fast == 2) DLMCQ_DW3(2, , false, true);
+      else DLMCQ_DW3(0, , false, true);
+    } else if (r6) {
       if (fast == 1) DLMCQ_DW3(1, , true);
       else if (fast == 2) DLMCQ_DW3(2, , true);
       else DLMCQ_DW3(0, , true);
@@ -601,4 +636,27 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
 #undef DLMCQ_DWG
   }
   return launch_status();
+}
+
+extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
+                                       const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N,
+                                       int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad,
+                                       int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
+                                       const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                                       dlmcq_stream_t stream) {
+  return dw_launch(x, w, out, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C, R, S, stride, pad, x_is_unsigned, relu, codes,
+                   q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream);
+}
+
+extern "C" int dlmcq_conv2d_dw_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
+                                            const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N,
+                                            int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad,
+                                            int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
+                                            const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                                            const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
+  if (!in_offset || !tap_sums) return DLMCQ_EINVAL;
+  if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
+  // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
+  return dw_launch(x, w, out, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C, R, S, stride, pad, x_is_unsigned, relu, codes,
+                   q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream, pad > 0 ? in_offset : nullptr, pad > 0 ? tap_sums : nullptr);
 }

@@ -32,7 +32,46 @@ struct ConvEpi {
   // tensor: modules/base.py:82-94 -> ops.py:20-34) comes out of the launch that produces the tensor.
   float* mm;
   int mm_np;
+  // float activation offset (the *_xoff entry points; the XOFF instantiations): x^ = q * s^ + o with a per-tensor float o (`x_off`, a
+  // device scalar) that no integer zero point represents.  The caller folds o * SUM_{all taps} tap[k] into the bias; the epilogue of a
+  // BORDER pixel subtracts o * SUM_{out-of-bounds taps} tap[k][r][s] (`x_tap`: fp32 [R * S][K], the per-tap sums of the dequantised
+  // weights over the real input channels), because zero padding pads x^ with 0, which is no code (xoff_border4 below)
+  const float* x_off;
+  const float* x_tap;
 };
+
+// The border sum of the XOFF epilogues for 4 consecutive channels c .. c + 3 of one output pixel whose receptive field starts at
+// (h0, w0): SUM over the taps (r, s) that fall outside the H x W image of tap[(r * S + s) * K + c ..], summed r-major, s ascending
+// (one fixed order: reproducible results).  `tap` 16-byte aligned, K and c multiples of 4.
+__device__ __forceinline__ bool xoff_is_border(int h0, int w0, int R, int S, int dil, int H, int W) {
+  return h0 < 0 || w0 < 0 || h0 + (R - 1) * dil >= H || w0 + (S - 1) * dil >= W;
+}
+__device__ __forceinline__ f32x4 xoff_border4(const float* tap, int K, int c, int h0, int w0, int R, int S, int dil, int H, int W) {
+  f32x4 b = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int r = 0; r < R; ++r) {
+    const bool rok = (uint32_t)(h0 + r * dil) < (uint32_t)H;
+    for (int s = 0; s < S; ++s) {
+      if (rok && (uint32_t)(w0 + s * dil) < (uint32_t)W) continue;
+      const f32x4 t = *reinterpret_cast<const f32x4*>(tap + (int64_t)(r * S + s) * K + c);
+      b = f32x4{b.x + t.x, b.y + t.y, b.z + t.z, b.w + t.w};
+    }
+  }
+  return b;
+}
+// ... one channel (layers whose K is no multiple of 4)
+__device__ __forceinline__ float xoff_border1(const float* tap, int K, int c, int h0, int w0, int R, int S, int dil, int H, int W) {
+  float b = 0.0f;
+  for (int r = 0; r < R; ++r) {
+    const bool rok = (uint32_t)(h0 + r * dil) < (uint32_t)H;
+    for (int s = 0; s < S; ++s)
+      if (!(rok && (uint32_t)(w0 + s * dil) < (uint32_t)W)) b = b + tap[(int64_t)(r * S + s) * K + c];
+  }
+  return b;
+}
+// v - o * border, as ONE fused multiply-add per element (after the bias and the weight-offset term, before residual / ReLU / quantiser)
+__device__ __forceinline__ f32x4 xoff_sub4(const f32x4& v, float o, const f32x4& b) {
+  return f32x4{__builtin_fmaf(-o, b.x, v.x), __builtin_fmaf(-o, b.y, v.y), __builtin_fmaf(-o, b.z, v.z), __builtin_fmaf(-o, b.w, v.w)};
+}
 
 // `q_form` argument of an entry point -> (form, shifted-emission flag); false = invalid
 static inline bool epi_set_form(ConvEpi& ep, int32_t q_form, int32_t q_lo, int32_t q_hi) {

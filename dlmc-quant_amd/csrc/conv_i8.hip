@@ -50,7 +50,9 @@ namespace dlmcq {
 //     of ~20; the code tile (1 B per element) goes through LDS once so that the stores are whole rows.
 // R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - the upper bound cap6_nan on top of the kernel's ReLU, in fp32 before the value is stored
 // or quantised (conv_epilogue.h); single-layer instantiations only (the dual entry point refuses it)
-template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false>
+// XOFF: a float activation offset (dlmcq_conv2d_i8_nhwc_xoff; ep.x_off / ep.x_tap): a border pixel's value loses o * (its out-of-bounds taps'
+// weight sums), conv_epilogue.h xoff_border4; the unswapped single-pair A-direct instantiations only
+template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false, bool XOFF = false>
 __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : (SWAP && BN == 64 && ADIR && !ASYM ? 5 : SWAP && BN == 128 && ADIR && !ASYM ? 3 : ADIR || BN == 64 ? (ASYM ? 3 : 4) : 3))) void conv_i8_mfma_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w, float* __restrict__ out, const float* __restrict__ bias,
     const int32_t* __restrict__ wsum, const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -87,6 +89,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   constexpr int PAR_BYTES = NPAR * BN * 4;
   static_assert(!(ASYM && DUAL), "asymmetric weights: single pair only");
   static_assert(!(SWAP && DUAL), "SWAP: codes-only layers with one operand pair");
+  static_assert(!(XOFF && (SWAP || DUAL || !ADIR)), "XOFF: the unswapped single-pair A-direct epilogue");
   __shared__ __attribute__((aligned(1024))) int8_t lds[LDS_BYTES + PAR_BYTES + (ASYM ? 4 * 32 * 4 : 0)];
 
   // XCD-aware tile order: the workgroups that share an activation tile (same row block, different column blocks) are
@@ -461,6 +464,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   // ---- epilogue: one rounding chain  v = (acc + (shift - zp) * SUM qw) * (s_in * s_w[k]) + b[k] ----
   const float sin = s_in[0];
   const EpiQuant eq(ep);
+  const float xo = XOFF ? ep.x_off[0] : 0.0f;
   float mult[NT], p_bias[NT], woff[ASYM ? NT : 1];
   int corr[NT];
 #pragma unroll
@@ -562,6 +566,12 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
         f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * EP_LD + ec);
         if (row < g.M && col < g.K) {
           const int64_t at = row * g.K + col;
+          if constexpr (XOFF) {
+            int xn, xh0, xw0;
+            row_origin(g, (uint32_t)row, xn, xh0, xw0);
+            if (xoff_is_border(xh0, xw0, g.R, g.S, g.dil, g.H, g.W))
+              v = xoff_sub4(v, xo, xoff_border4(ep.x_tap, g.K, col, xh0, xw0, g.R, g.S, g.dil, g.H, g.W));
+          }
           if (ep.residual) v = f32x4{v.x + idt[it].x, v.y + idt[it].y, v.z + idt[it].z, v.w + idt[it].w};
           if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
           if constexpr (R6) v = cap6_nan4(v);
@@ -616,6 +626,12 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
       float v = dequant1(acc[j][i] + corr[j], mult[j], p_bias[j]);
       if (DUAL) v = v + extra[DUAL ? j : 0][i];
       if (ASYM) v = v + s0r[ASYM ? i : 0] * woff[ASYM ? j : 0];
+      if constexpr (XOFF) {
+        int xn, xh0, xw0;
+        row_origin(g, (uint32_t)row, xn, xh0, xw0);
+        if (xoff_is_border(xh0, xw0, g.R, g.S, g.dil, g.H, g.W))
+          v = __builtin_fmaf(-xo, xoff_border1(ep.x_tap, g.K, col, xh0, xw0, g.R, g.S, g.dil, g.H, g.W), v);
+      }
       if (ep.residual) v = v + ep.residual[at];
       if (ep.relu) v = relu_nan(v);
       if constexpr (R6) v = cap6_nan(v);
@@ -750,7 +766,16 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   if (!forced && ep.w_off && plan.bn == 64 && K % 192 == 0 && plan.swap && ep.codes && !out && !ep.residual && aligned16(ep.codes)) plan.bn = 192;
   // the specialised kernels, unless the caller (DLMCQ_FORCE_TILED) or a lab plan keeps the call on this file's kernel;
   // DLMCQ_ROUTE_ONLY: the decision is the answer, nothing is launched
-  const bool special = plan.halo && !(ep.ctl & DLMCQ_FORCE_TILED), route_only = (ep.ctl & DLMCQ_ROUTE_ONLY) != 0;
+  // a float activation offset (ep.x_off) runs on the XOFF instantiations of this file's kernel only: the specialised kernels decline
+  // it, and its tiles are the unswapped A-direct ones (64 or 128 channels)
+  const bool xoff = ep.x_off != nullptr;
+  if (xoff) {
+    if (seg2 || forced) return DLMCQ_EINVAL;
+    plan.swap = false;
+    plan.adir = true;
+    if (plan.bn != 64) plan.bn = 128;
+  }
+  const bool special = plan.halo && !(ep.ctl & DLMCQ_FORCE_TILED) && !xoff, route_only = (ep.ctl & DLMCQ_ROUTE_ONLY) != 0;
   float* const mm_req = ep.mm;
   ep.mm = nullptr;                    // (the specialised kernels below do not write partials)
   // (only the block-end kernel knows the chunk-major form of the fp32 block tensors: a call that carries the bits and would land
@@ -804,7 +829,15 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound (the dual entry point refuses it)
   auto launch = [&](auto r6) {
     constexpr bool R6 = decltype(r6)::value;
-    if (seg2) {
+    if (xoff) {
+      if (ep.w_off) {
+        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
+        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
+      } else {
+        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, true>), DLMCQ_CONV_ARGS);
+        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, false, R6, true>), DLMCQ_CONV_ARGS);
+      }
+    } else if (seg2) {
       if constexpr (!R6) {
         if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, true, true>), DLMCQ_CONV_ARGS);
         else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, true, true>), DLMCQ_CONV_ARGS);
@@ -911,6 +944,25 @@ extern "C" int dlmcq_conv2d_i8_nhwc_asym(const void* x, const int8_t* w, float* 
   if (!w_offset) return DLMCQ_EINVAL;
   ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   ep.w_off = w_offset;
+  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
+                     x_is_unsigned, stream, ep);
+}
+
+extern "C" int dlmcq_conv2d_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                         const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R,
+                                         int64_t S, int32_t stride, int32_t pad, int32_t dilation, int32_t x_is_unsigned,
+                                         const float* residual, int32_t relu, void* codes, const float* q_scale,
+                                         const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                                         const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
+  if (!in_offset || !tap_sums) return DLMCQ_EINVAL;
+  if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
+  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  ep.w_off = w_offset;
+  if (pad > 0) {      // (unpadded: no tap is ever out of bounds - the folded bias is the whole term, and every kernel may take the call)
+    ep.x_off = in_offset;
+    ep.x_tap = tap_sums;
+  }
   return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
                      x_is_unsigned, stream, ep);
 }

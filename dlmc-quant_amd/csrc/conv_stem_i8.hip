@@ -28,12 +28,15 @@ struct ImgGeom {
   FastDiv wdiv, hdiv;
 };
 
+// CODE0 (DLMCQ_PAD_CODE0): the border holds code 0 instead of the code of x' = 0 - the padding of a float-offset quantiser, whose
+// zero has no code (the *_xoff first-layer entry point takes the difference as its border term)
+template <bool CODE0 = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void quantize_pad_nhwc4_kernel(const float* __restrict__ x, uint32_t* __restrict__ out,
                                                                          ImgGeom g, ConvEpi q) {
   // the quantiser is EpiQuant::code4 (conv_epilogue.h): the four forms' arithmetic at ~10 operations per element instead of
   // a correctly rounded division each (this kernel was bound by them, not by HBM), bit-identical codes
   const EpiQuant eq(q);
-  const uint32_t border = eq.code4(f32x4{0.0f, 0.0f, 0.0f, 0.0f});   // x' = 0 (zero padding of the fake-quantised image) in every channel
+  const uint32_t border = CODE0 ? q.q_xor : eq.code4(f32x4{0.0f, 0.0f, 0.0f, 0.0f});   // x' = 0 (zero padding of the fake-quantised image) in every channel
   const uint32_t keep = g.C >= 4 ? 0xffffffffu : (1u << (8 * g.C)) - 1u;   // bytes of channels that do not exist stay 0
   const int64_t total = (int64_t)g.N * g.Hp * g.Wp;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -61,10 +64,11 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void quantize_pad_nhwc4_kernel(const f
 // group of a load touches two whole cache lines instead of half of one, and the quantiser runs on the C real channels only
 // (code4 on a channel-planar quad, bytes dealt to the four pixel words by v_perm_b32).  Same bytes as the kernel above.
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte store at a 4-byte-aligned address
+template <bool CODE0 = false>
 __global__ __launch_bounds__(DLMCQ_BLOCK) void quantize_pad_nhwc4_x4_kernel(const float* __restrict__ x, uint32_t* __restrict__ out,
                                                                             ImgGeom g, ConvEpi q, FastDiv gdiv, int groups) {
   const EpiQuant eq(q);
-  const uint32_t border = eq.code4(f32x4{0.0f, 0.0f, 0.0f, 0.0f});
+  const uint32_t border = CODE0 ? q.q_xor : eq.code4(f32x4{0.0f, 0.0f, 0.0f, 0.0f});
   const int64_t total = (int64_t)g.N * g.Hp * groups;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t t = fdiv((uint32_t)i, gdiv);
@@ -133,6 +137,7 @@ struct StemGeom {
   int64_t M;     // N*P*Q
   int ntiles;    // ceil(M / 32)
   FastDiv qdiv, pdiv;
+  int xpad;      // XOFF only: the padding the buffer carries (image = rows / columns xpad .. Hp - xpad - 1 / Wp - xpad - 1)
 };
 
 constexpr int ST_MAXR = 7;
@@ -148,7 +153,9 @@ constexpr int ST_EP_LD = 68;   // floats per staged row (64 + 4 pad)
 // transposition through LDS, folds the ReLU into the quantiser's clamp and reads its per-channel constants, pre-multiplied once
 // per workgroup, as broadcast ds_read_b128; the per-pixel code sum of ASYM is a per-lane scalar.
 // R6: ReLU6 (ep.relu == DLMCQ_ACT_RELU6) - cap6_nan on top of the ReLU, in fp32 before the value is stored or quantised
-template <int R, bool ASYM = false, bool SWAP = false, bool R6 = false>
+// XOFF (dlmcq_conv2d_i8_stem_xoff; unswapped only): a float activation offset - a border pixel's value loses o * (its out-of-bounds taps'
+// weight sums), ep.x_off / ep.x_tap (conv_epilogue.h xoff_border4), before the ReLU
+template <int R, bool ASYM = false, bool SWAP = false, bool R6 = false, bool XOFF = false>
 __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __restrict__ x, const int8_t* __restrict__ w,
                                                            float* __restrict__ out, const float* __restrict__ bias,
                                                            const int32_t* __restrict__ wsum, const float* __restrict__ s_in,
@@ -163,7 +170,9 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
   const int zpi = (int)__builtin_rintf(zpf);
   const float sin = s_in[0];
   const EpiQuant eq(ep, SWAP && ep.relu);
-  const bool plainq = epi_plain(ep);         // unsigned bytes, no zero point: EpiQuant::code4n_plain (one uniform branch per 16 channels)
+  const bool plainq = epi_plain(ep);
+  static_assert(!(XOFF && SWAP), "XOFF: the unswapped epilogue");
+  const float xo = XOFF ? ep.x_off[0] : 0.0f;         // unsigned bytes, no zero point: EpiQuant::code4n_plain (one uniform branch per 16 channels)
 
   // weights of this slab: fragment (r, j) = 16 bytes of channel n0 + j*32 + (lane & 31), taps hsel*4 .. +3
   // (SWAP: row d of a block is channel 16 ((d >> 2) & 1) + 4 (d >> 3) + (d & 3): accumulator register i = channel 16 hsel + i)
@@ -347,6 +356,14 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
       f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * ST_EP_LD + ec);
       if (row < g.M && col < g.K) {
         const int64_t at = row * g.K + col;
+        if constexpr (XOFF) {
+          const uint32_t t = fdiv((uint32_t)row, g.qdiv);
+          const int q = (int)((uint32_t)row - t * (uint32_t)g.Q);
+          const uint32_t nn = fdiv(t, g.pdiv);
+          const int p = (int)(t - nn * (uint32_t)g.P);
+          const int h0 = p * g.stride - g.xpad, w0 = q * g.stride - g.xpad, H = g.Hp - 2 * g.xpad, W = g.Wp - 2 * g.xpad;
+          if (xoff_is_border(h0, w0, R, g.S, 1, H, W)) v = xoff_sub4(v, xo, xoff_border4(ep.x_tap, g.K, col, h0, w0, R, g.S, 1, H, W));
+        }
         if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
         if constexpr (R6) v = cap6_nan4(v);
         if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
@@ -625,6 +642,8 @@ extern "C" int dlmcq_quantize_pad_nhwc4(const float* x, void* out, const float* 
                                         dlmcq_stream_t stream) {
   if (N < 0 || C < 1 || C > 4 || H < 1 || W < 1 || pad < 0 || lo > hi || lo < -128 || hi > 255 || hi - lo > 255)
     return DLMCQ_EINVAL;
+  const bool code0 = (form & DLMCQ_PAD_CODE0) != 0;   // (this entry point's own flag: every other one refuses the bit)
+  form &= ~DLMCQ_PAD_CODE0;
   ConvEpi q{};                          // the image quantiser, evaluated by EpiQuant (needs a non-null `codes` to resolve)
   if ((form & ~DLMCQ_EMIT_SHIFT128) < DLMCQ_FORM_EMULATE || (form & ~DLMCQ_EMIT_SHIFT128) > DLMCQ_FORM_SYMMETRIC ||
       !epi_set_form(q, form, lo, hi))     // (the form and DLMCQ_EMIT_SHIFT128 only: no control bits)
@@ -651,12 +670,20 @@ extern "C" int dlmcq_quantize_pad_nhwc4(const float* x, void* out, const float* 
     const int groups = (int)(W / 4);
     const int64_t items = N * g.Hp * groups;
     const int64_t b4 = (items + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
-    hipLaunchKernelGGL(quantize_pad_nhwc4_x4_kernel, dim3((uint32_t)(b4 < 65536 ? b4 : 65536)), dim3(DLMCQ_BLOCK), 0,
-                       reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q, make_fastdiv((uint32_t)groups), groups);
+    if (code0)
+      hipLaunchKernelGGL(quantize_pad_nhwc4_x4_kernel<true>, dim3((uint32_t)(b4 < 65536 ? b4 : 65536)), dim3(DLMCQ_BLOCK), 0,
+                         reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q, make_fastdiv((uint32_t)groups), groups);
+    else
+      hipLaunchKernelGGL(quantize_pad_nhwc4_x4_kernel<false>, dim3((uint32_t)(b4 < 65536 ? b4 : 65536)), dim3(DLMCQ_BLOCK), 0,
+                         reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q, make_fastdiv((uint32_t)groups), groups);
     return launch_status();
   }
-  hipLaunchKernelGGL(quantize_pad_nhwc4_kernel, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(DLMCQ_BLOCK), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q);
+  if (code0)
+    hipLaunchKernelGGL(quantize_pad_nhwc4_kernel<true>, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(DLMCQ_BLOCK), 0,
+                       reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q);
+  else
+    hipLaunchKernelGGL(quantize_pad_nhwc4_kernel<false>, dim3((uint32_t)(blocks < 65536 ? blocks : 65536)), dim3(DLMCQ_BLOCK), 0,
+                       reinterpret_cast<hipStream_t>(stream), x, static_cast<uint32_t*>(out), g, q);
   return launch_status();
 }
 
@@ -676,7 +703,7 @@ static int stem_launch(const void* xpad, const int8_t* w, float* out, const floa
                        const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t C, int64_t N, int64_t Hp,
                        int64_t Wp, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
                        const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
-                       dlmcq_stream_t stream) {
+                       dlmcq_stream_t stream, const float* x_off = nullptr, const float* x_tap = nullptr, int32_t x_pad = 0) {
   if (N < 0 || Hp < 1 || Wp < 1 || K < 1 || R < 1 || R > ST_MAXR || S < 1 || S > 8 || stride < 1) return DLMCQ_EINVAL;
   if (Hp < R || Wp < S || (K & 3)) return DLMCQ_EINVAL;
   const int64_t P = (Hp - R) / stride + 1, Q = (Wp - S) / stride + 1;
@@ -695,8 +722,11 @@ static int stem_launch(const void* xpad, const int8_t* w, float* out, const floa
   g.ntiles = (int)((M + 31) / 32);
   g.qdiv = make_fastdiv((uint32_t)Q);
   g.pdiv = make_fastdiv((uint32_t)P);
+  g.xpad = x_pad;
   ConvEpi ep{};
   ep.w_off = w_offset;
+  ep.x_off = x_off;
+  ep.x_tap = x_tap;
   ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
   ep.codes = static_cast<uint8_t*>(codes);
   ep.q_scale = q_scale;
@@ -719,6 +749,16 @@ static int stem_launch(const void* xpad, const int8_t* w, float* out, const floa
   // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound
   auto launch = [&](auto r6) {
     constexpr bool R6 = decltype(r6)::value;
+    if (x_off) {       // (the entry point has checked R: 3 or 7)
+      if (R == 3) {
+        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, false, R6, true>), DLMCQ_STEM_ARGS);
+        else hipLaunchKernelGGL((conv_stem_i8_kernel<3, false, false, R6, true>), DLMCQ_STEM_ARGS);
+      } else {
+        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<7, true, false, R6, true>), DLMCQ_STEM_ARGS);
+        else hipLaunchKernelGGL((conv_stem_i8_kernel<7, false, false, R6, true>), DLMCQ_STEM_ARGS);
+      }
+      return;
+    }
     // 3 x 3 first layers that emit only codes (RepVGG, MobileOne): the swapped epilogue
     if (R == 3 && !out && codes && K % 64 == 0 && aligned16(codes)) {
       if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, true, R6>), DLMCQ_STEM_ARGS);
@@ -759,6 +799,21 @@ extern "C" int dlmcq_conv2d_i8_stem_asym(const void* xpad, const int8_t* w, floa
   if (!w_offset || C < 1 || C > 4) return DLMCQ_EINVAL;
   return stem_launch(xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, w_offset, C, N, Hp, Wp, K, R, S, stride,
                      x_is_unsigned, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream);
+}
+
+extern "C" int dlmcq_conv2d_i8_stem_xoff(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                         const float* w_offset, int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
+                                         int64_t S, int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes,
+                                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                                         float q_ste_g, const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
+  if (!in_offset || !tap_sums || C < 1 || C > 4 || pad < 0 || 2 * (int64_t)pad >= Hp || 2 * (int64_t)pad >= Wp) return DLMCQ_EINVAL;
+  if (pad > 0 && R != 3 && R != 7) return DLMCQ_EINVAL;     // (the XOFF instantiations: 3 x 3 and 7 x 7 filters)
+  if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
+  // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
+  return stem_launch(xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, w_offset, w_offset ? C : 4, N, Hp, Wp, K, R, S, stride,
+                     x_is_unsigned, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream, pad > 0 ? in_offset : nullptr,
+                     pad > 0 ? tap_sums : nullptr, pad);
 }
 
 extern "C" int dlmcq_maxpool_codes_nhwc(const void* x, void* y, int64_t N, int64_t H, int64_t W, int64_t C, int32_t kernel,

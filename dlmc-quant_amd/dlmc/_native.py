@@ -31,6 +31,7 @@ FORCE_TILED = 0x400      # DLMCQ_FORCE_TILED: OR-able into q_form of conv2d_i8_n
 ROUTE_ONLY = 0x800       # DLMCQ_ROUTE_ONLY: launch nothing, return which kernel the dispatch picks (ROUTE_*)
 FP32_IN_CHUNK_MAJOR = 0x2000   # DLMCQ_FP32_IN_CHUNK_MAJOR: a chain call's fp32 shortcut is [K / 64][M][64] (kernels.ChunkMajor)
 FP32_OUT_CHUNK_MAJOR = 0x4000  # DLMCQ_FP32_OUT_CHUNK_MAJOR: ... and / or its fp32 block output
+PAD_CODE0 = 0x8000       # DLMCQ_PAD_CODE0: quantize_pad_nhwc4's border holds code 0 (a float-offset quantiser's padding)
 PIPELINED = 0x1000       # DLMCQ_PIPELINED (opt-in): the persistent, software-pipelined halo-tile 3x3 kernel where it applies
 ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE = 1, 2, 3, 4, 5, 6, 7
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
@@ -87,6 +88,12 @@ SIGNATURES = {
                                                 _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_conv2d_dw_i8_nhwc": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
                                               _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_conv2d_i8_nhwc_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p, _p, _p]),
+    "dlmcq_conv2d_dw_i8_nhwc_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                   _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p, _p, _p]),
+    "dlmcq_conv2d_i8_stem_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
+                                                _i32, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p, _p, _p]),
     "dlmcq_dwpw_pack_table": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p]),
     "dlmcq_conv2d_dwpw_i8_nhwc": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32,
                                                 _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),

@@ -437,7 +437,7 @@ def _act(relu, act):
 
 def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding=0, dilation=1,
               residual=None, relu=False, emit=None, want_out=True, w_offset=None, force_tiled=False, pipelined=False, observe=False,
-              out_chunk_major=False, act=None):
+              out_chunk_major=False, act=None, in_offset=None, tap_sums=None):
     """Fused int8 conv / linear on the matrix cores.  `codes`: uint8/int8 activation codes, logically
     (N, C, H, W) in channels_last memory, or (N, C) for a linear layer.  Returns fp32 (N, K, P, Q) in
     channels_last memory (or (N, K)).
@@ -453,8 +453,12 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
     `out._dlmcq_mm = (partials, count, version)` when the kernel that ran has the observing epilogue; `minmax_from_partials` reduces them.
     `residual` may be a ChunkMajor and `out_chunk_major` asks for the fp32 output as one (the block tensors between chain kernels): the
     block-end kernel (csrc/conv_pwr_i8.hip) takes them so; where the library's dispatch hands the call to another kernel a ChunkMajor
-    residual is converted first (a copy) and the output comes back as an ordinary tensor."""
+    residual is converted first (a copy) and the output comes back as an ordinary tensor.
+    `in_offset` (fp32 device scalar o) with `tap_sums` (fp32 [R * S, K]): a float activation offset (dlmcq_conv2d_i8_nhwc_xoff) - `bias`
+    must already hold o * tap_sums.sum(0); border pixels lose o * (their out-of-bounds taps' sums).  Not with `observe`."""
     N.require_gpu(codes, wq)
+    if (in_offset is None) != (tap_sums is None):
+        raise ValueError("conv2d_i8: in_offset and tap_sums go together")
     linear = codes.dim() == 2
     if linear:
         n, c = codes.shape
@@ -473,7 +477,9 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
             return torch.empty((n, K), dtype=dtype, device=codes.device)
         return torch.empty((n, K, P, Q), dtype=dtype, device=codes.device, memory_format=torch.channels_last)
     act = _act(relu, act)
-    fused = residual is not None or act or emit is not None or w_offset is not None or (observe and want_out)
+    fused = residual is not None or act or emit is not None or w_offset is not None or (observe and want_out) or in_offset is not None
+    if in_offset is not None and observe:
+        raise ValueError("conv2d_i8: the offset entry point has no observing form")
     if not want_out and emit is None:
         raise ValueError("conv2d_i8: nothing to produce (want_out=False without emit)")
     if w_offset is not None:
@@ -517,7 +523,15 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
             lo, hi, form, g = emit.lo, emit.hi, emit.form_arg, emit.g
         nbytes = codes.numel() + wq.numel() + out_elems * (4 * (out is not None) + 4 * (residual is not None) + (emit is not None))
         form |= (N.FORCE_TILED if force_tiled else 0) | (N.PIPELINED if pipelined else 0)
-        if w_offset is not None:
+        if in_offset is not None:
+            in_offset = _f32c(in_offset, ref).reshape(-1)
+            tap_sums = _f32c(tap_sums.detach(), ref).contiguous()
+
+            def call(extra=0):
+                return N.lib.dlmcq_conv2d_i8_nhwc_xoff(
+                    *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
+                    lo, hi, form | extra, g, N.ptr(in_offset), N.ptr(tap_sums), N.stream_ptr())
+        elif w_offset is not None:
             def call(extra=0):
                 return N.lib.dlmcq_conv2d_i8_nhwc_asym(
                     *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
@@ -540,7 +554,7 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         if icm or ocm:
             # chunk-major block tensors: only where the block-end kernel takes the call, with one layout for its fp32 tensors (the
             # library's own dispatch answers: DLMCQ_ROUTE_ONLY).  Otherwise: the ordinary layout, the residual converted
-            if (w_offset is None and not (observe and out is not None) and (residual is None or out is None or icm == ocm)
+            if (w_offset is None and in_offset is None and not (observe and out is not None) and (residual is None or out is None or icm == ocm)
                     and N.route(call(N.ROUTE_ONLY)) == N.ROUTE_PWR):
                 cm_bits = (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
             else:
@@ -562,10 +576,13 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
 
 
 def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, stride=1, padding=0, relu=False, emit=None, want_out=True,
-                 force_tiled=False, act=None):
+                 force_tiled=False, act=None, in_offset=None, tap_sums=None):
     """Depthwise convolution on activation codes (dlmcq_conv2d_dw_i8_nhwc).  codes: (N, C, H, W) uint8/int8 channels_last,
     C % 4 == 0; wq: int8 [R, S, C] (tap-major); per-channel w_scale / w_offset / bias [C].  Returns fp32 (N, C, P, Q)
-    channels_last, or `(out, codes)` with `emit`.  `relu` / `act` as in conv2d_i8."""
+    channels_last, or `(out, codes)` with `emit`.  `relu` / `act` as in conv2d_i8.  `in_offset` / `tap_sums` ([R * S, C]): a float
+    activation offset, as in conv2d_i8 (dlmcq_conv2d_dw_i8_nhwc_xoff: 3 x 3 layers, C % 16 == 0)."""
+    if (in_offset is None) != (tap_sums is None):
+        raise ValueError("conv2d_dw_i8: in_offset and tap_sums go together")
     _no_shift(emit, "conv2d_dw_i8")
     N.require_gpu(codes, wq)
     n, c, h, w_ = codes.shape
@@ -595,11 +612,21 @@ def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, strid
     oe = n * c * P * Q
     form |= N.FORCE_TILED if force_tiled else 0
 
-    def call(extra=0):
-        return N.lib.dlmcq_conv2d_dw_i8_nhwc(
-            N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
-            n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
-            N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.stream_ptr())
+    if in_offset is not None:
+        in_offset = _f32c(in_offset, codes).reshape(-1)
+        tap_sums = _f32c(tap_sums.detach(), codes).contiguous()
+
+        def call(extra=0):
+            return N.lib.dlmcq_conv2d_dw_i8_nhwc_xoff(
+                N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
+                n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
+                N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.ptr(in_offset), N.ptr(tap_sums), N.stream_ptr())
+    else:
+        def call(extra=0):
+            return N.lib.dlmcq_conv2d_dw_i8_nhwc(
+                N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
+                n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
+                N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.stream_ptr())
     # (the profile tag - conv_dw: the vector kernels, conv_dwm: the matrix-core kernel - from the library's own dispatch, DLMCQ_ROUTE_ONLY)
     tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_dw"
     PROFILE.launch(tag, codes.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)), lambda: N.check(call()), 2 * oe * R * S)
@@ -926,11 +953,12 @@ def conv2d_i8_dual_chain(a, b, c3, relu=True, emit=None, want_out=True, want_cod
     return out, codes, codes3
 
 
-def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=False):
+def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=False, pad_code0=False):
     """Image batch (N, C <= 4, H, W) fp32, any memory format -> activation codes in a zero-point-padded NHWC
     buffer, 4 bytes per pixel: uint8/int8 tensor (N, H + 2 pad, W + 2 pad, 4) (a view of a slightly larger
     allocation: the stem kernel over-reads up to 32 bytes).  `shift128` (unsigned ranges): the buffer holds int8 `code - 128`
-    (DLMCQ_EMIT_SHIFT128); the first-layer kernels then take it as signed codes with the zero point `zp - 128`."""
+    (DLMCQ_EMIT_SHIFT128); the first-layer kernels then take it as signed codes with the zero point `zp - 128`.  `pad_code0`
+    (DLMCQ_PAD_CODE0): the border holds code 0, not the code of x' = 0 - a float-offset quantiser's padding (conv2d_i8_stem `in_offset`)."""
     N.require_gpu(x)
     if x.dim() != 4 or x.shape[1] > 4 or x.dtype != torch.float32:
         raise ValueError("quantize_pad_nhwc4 takes an fp32 (N, C <= 4, H, W) tensor")
@@ -943,7 +971,7 @@ def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=
     zero_point = None if zero_point is None else _f32c(zero_point, x).reshape(-1)
     PROFILE.launch("fq_image", x.numel() * 4 + n * hp * wp * 4, lambda: N.check(N.lib.dlmcq_quantize_pad_nhwc4(
         N.ptr(x), N.ptr(flat), N.ptr(scale), N.ptr(zero_point), n, c, h, w, *x.stride(), int(pad), int(lo), int(hi),
-        int(form) | (N.EMIT_SHIFT128 if shift128 else 0), float(g), N.stream_ptr())))
+        int(form) | (N.EMIT_SHIFT128 if shift128 else 0) | (N.PAD_CODE0 if pad_code0 else 0), float(g), N.stream_ptr())))
     return flat[:n * hp * wp * 4].view(n, hp, wp, 4)
 
 
@@ -963,13 +991,16 @@ def quantize_weight_stem(w, scale, lo, hi):
 
 
 def conv2d_i8_stem(xpad, wq, wsum, bias, in_scale, in_zp, w_scale, S, stride=1, relu=False, emit=None, want_out=True, pool=False,
-                   w_offset=None, channels=4, act=None):
+                   w_offset=None, channels=4, act=None, in_offset=None, tap_sums=None, pad=0):
     """The first-layer convolution on padded NHWC4 codes (quantize_pad_nhwc4 / quantize_weight_stem).  Returns fp32
     (N, K, P, Q) channels_last, or `(out, codes)` with `emit` (see conv2d_i8).  `pool=True` (K <= 64): followed by
     MaxPool2d(3, 2, 1) in the same kernel - the results are the pooled tensors.  `w_offset` ([K] fp32, with the image's real
     channel count `channels`): asymmetric per-channel weights (dlmcq_conv2d_i8_stem_asym; not with `pool`).  `relu` / `act` as in
-    conv2d_i8 (the pooling kernel: ReLU only)."""
+    conv2d_i8 (the pooling kernel: ReLU only).  `in_offset` / `tap_sums` ([R * S, K]) with `pad` (the buffer's padding, filled with
+    code 0: quantize_pad_nhwc4(pad_code0=True)): a float activation offset, as in conv2d_i8 (dlmcq_conv2d_i8_stem_xoff; R = 3 or 7)."""
     _no_shift(emit, "conv2d_i8_stem")
+    if (in_offset is None) != (tap_sums is None) or (in_offset is not None and pool):
+        raise ValueError("conv2d_i8_stem: in_offset needs tap_sums and no pool")
     act = _act(relu, act)
     N.require_gpu(xpad, wq)
     n, hp, wp, _ = xpad.shape
@@ -1000,6 +1031,18 @@ def conv2d_i8_stem(xpad, wq, wsum, bias, in_scale, in_zp, w_scale, S, stride=1, 
         q_zp = None if emit.zero_point is None else _f32c(emit.zero_point, xpad).reshape(-1)
         lo, hi, form, g = emit.lo, emit.hi, emit.form, emit.g
     oe = n * K_ * P * Q
+    if in_offset is not None:
+        w_offset = None if w_offset is None else _f32c(w_offset.detach(), xpad).reshape(-1)
+        in_offset = _f32c(in_offset, xpad).reshape(-1)
+        tap_sums = _f32c(tap_sums.detach(), xpad).contiguous()
+        PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
+                       lambda: N.check(N.lib.dlmcq_conv2d_i8_stem_xoff(
+                           N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
+                           N.ptr(w_offset), int(channels), n, hp, wp, K_, R, int(S), int(stride), int(pad), int(xpad.dtype == torch.uint8),
+                           act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.ptr(in_offset), N.ptr(tap_sums),
+                           N.stream_ptr())),
+                       2 * n * K_ * P * Q * R * S * int(channels))
+        return (out, out_codes) if emit is not None else out
     if w_offset is not None:
         if pool:
             raise ValueError("conv2d_i8_stem: the pooling kernel has no weight-offset term")

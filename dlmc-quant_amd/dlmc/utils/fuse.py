@@ -39,8 +39,12 @@ __all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "Stem
 class _ActSpec:
     """One wrapper's frozen activation quantiser, as a producer has to evaluate it."""
 
-    def __init__(self, scale, zp, lo, hi, form, needs_g):
+    def __init__(self, scale, zp, lo, hi, form, needs_g, xoff=False):
         self.scale, self.zp, self.lo, self.hi, self.form, self.needs_g = scale, zp, int(lo), int(hi), form, needs_g
+        # xoff (fuse_inference(act_offsets=True)): `zp` is a QBase FLOAT offset o (x^ = q * s^ + o), not an integer zero point.  It is
+        # what quantises and emits this tensor's codes (q = R(clamp((x - o) / s^))); the consumer's kernel sees zero point 0, o * (weight
+        # sums) folded into its bias and, for padded layers, the border term of the *_xoff entry points (DESIGN.md 5.13)
+        self.xoff = bool(xoff)
         self.key = (form, self.lo, self.hi, float(scale.reshape(-1)[0]), 0.0 if zp is None else float(zp.reshape(-1)[0]),
                     needs_g)
         # what a PRODUCER is told: a zero point of 0 (every post-ReLU tensor) goes as "none" - the kernels' plain-quantiser paths
@@ -82,7 +86,7 @@ def plan_kind(mod):
     return None
 
 
-def _frozen_spec(mod):
+def _frozen_spec(mod, act_offsets=False):
     """(_ActSpec, weight scale, weight lo, weight hi, kind, weight offset, weight-code function) if `mod` can run on an
     int8 kernel with frozen scales.  The last two are None for symmetric per-tensor / per-channel weights quantised by
     quantize_weight_krsc; asymmetric (offset = channel minimum, ops.py:129-136) or QBase per-channel weights carry their
@@ -90,7 +94,7 @@ def _frozen_spec(mod):
     kind = plan_kind(mod)
     if kind is None:
         return None
-    spec = _frozen_spec_(mod, kind)
+    spec = _frozen_spec_(mod, kind, act_offsets)
     if spec is None:
         return None
     if len(spec) == 4:
@@ -98,7 +102,19 @@ def _frozen_spec(mod):
     return spec[:4] + (kind,) + spec[4:]
 
 
-def _frozen_spec_(mod, kind):
+def _xoff_kernel_exists(mod, kind):
+    """Whether a layer whose input quantiser has a float offset has a kernel with the border term (include/dlmcq.h, the *_xoff entry
+    points).  Unpadded layers need none (the folded bias is the whole term); padded depthwise layers need a 3 x 3 filter (the vector
+    kernels, <= 2048 channels once padded to 64), padded first layers a 3 x 3 or 7 x 7 one.  Anything else keeps its fp32 path."""
+    w = mod.weight
+    if w.dim() != 4 or int(mod.padding[0]) == 0 or kind == "gemm":
+        return True
+    if kind == "dw":
+        return tuple(w.shape[2:]) == (3, 3) and _ceil64(w.shape[0]) <= 2048
+    return w.shape[2] in (3, 7)          # "stem"
+
+
+def _frozen_spec_(mod, kind, act_offsets=False):
     if isinstance(mod, FSPTQBase):
         if not (mod.act_quant and mod.wt_quant) or mod.in_scale.numel() != 1:
             return None
@@ -128,11 +144,13 @@ def _frozen_spec_(mod, kind):
         lo, hi = mod.wt_min_val, mod.wt_max_val
         if not (_byte_range(mod.in_min_val, mod.in_max_val) and _byte_range(lo, hi)):
             return None
-        if float(mod.in_offset.abs().max()) != 0:
-            return None                  # a float activation offset has no integer zero point (padding must be a code)
+        xoff = float(mod.in_offset.abs().max()) != 0
+        if xoff and not (act_offsets and mod.in_offset.numel() == 1 and _xoff_kernel_exists(mod, kind)):
+            return None                  # a float activation offset has no integer zero point (padding must be a code): act_offsets=True
         asym = mod.wt_offset is not None and float(mod.wt_offset.abs().max()) != 0
-        act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(), None, mod.in_min_val, mod.in_max_val,
-                       N.FORM_QBASE, True)
+        act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(),
+                       mod.in_offset.detach().to(torch.float32).reshape(-1)[:1].clone() if xoff else None, mod.in_min_val, mod.in_max_val,
+                       N.FORM_QBASE, True, xoff=xoff)
         g_w = 1 / math.sqrt(mod.weight.numel() * hi)
         s_hat = ste_scale_value(mod.wt_scale, g_w).clone()
         if not (per_channel or asym or hi > 127 or kind == "dw"):
@@ -171,16 +189,39 @@ class _PlanLayer(nn.Module):
         self.register_buffer("w_off", None if w_off is None else self._padk(w_off.to(w_scale.device), 0.0), persistent=False)
         self.register_buffer("bias_pad", None if layer.bias is None or self.k_pad == k else self._padk(layer.bias.detach().float(), 0.0),
                              persistent=False)
-        self._zp_fill = int(0 if self.act.zp is None else float(self.act.zp.reshape(-1)[0]))   # (read once: no host sync in forward)
+        # the zero point the KERNELS see: a float offset (act.xoff) is none - its codes pad with code 0 and its term is in the bias / border
+        self._kzp = None if self.act.xoff else self.act.zp
+        self._zp_fill = int(0 if self._kzp is None else float(self._kzp.reshape(-1)[0]))   # (read once: no host sync in forward)
         # A producer may hand an unsigned-byte quantiser's codes over as int8 `code - 128` (EmitCodes.shift128: what the matrix
         # cores multiply anyway, so the consumer's kernel need not re-centre every operand byte it reads); this node then runs
         # with the zero point `zp - 128` - the same integers.  `emit_shift`: this node emits ITS consumers' codes that way.
         self.emit_shift = False
         zs = None
         if self.act.lo >= 0:
-            zs = (torch.zeros(1, device=w_scale.device) if self.act.zp is None else self.act.zp.detach().float().reshape(-1)[:1]) - 128.0
+            zs = (torch.zeros(1, device=w_scale.device) if self._kzp is None else self._kzp.detach().float().reshape(-1)[:1]) - 128.0
         self.register_buffer("zp_shift", zs, persistent=False)
         self._deq = {}     # QBase dequantises with s^ = grad_scale(s, g(numel)): one tiny tensor per input size
+        for name in ("bias_fold", "x_off", "tap_sums"):
+            self.register_buffer(name, None, persistent=False)
+        self.xoff_padded = False     # the border term runs in the kernel (the *_xoff entry points)
+
+    def _fold_offset(self, tap):
+        """A float activation offset o (act.xoff): `tap` [k_pad, R, S] (float64, on the device) = per output channel and tap the sum of the
+        dequantised weights over the REAL input channels.  o * SUM_{taps} tap goes into the bias (float64, rounded once); a padded layer
+        keeps the fp32 taps [R * S, k_pad] for its border term."""
+        o = self.act.zp.detach().to(torch.float64).reshape(-1)[:1].to(tap.device)
+        b = torch.zeros(self.k_pad, dtype=torch.float64, device=tap.device)
+        if self.layer.bias is not None:
+            b[:self.k] = self.layer.bias.detach().to(torch.float64).reshape(-1)
+        self.register_buffer("bias_fold", (b + o * tap.sum(dim=(1, 2))).to(torch.float32).contiguous(), persistent=False)
+        self.register_buffer("x_off", self.act.zp.detach().to(torch.float32).reshape(-1)[:1].to(tap.device).contiguous(), persistent=False)
+        lay = self.layer
+        self.xoff_padded = lay.weight.dim() == 4 and int(lay.padding[0]) > 0
+        if self.xoff_padded:
+            self.register_buffer("tap_sums", tap.permute(1, 2, 0).reshape(-1, tap.shape[0]).to(torch.float32).contiguous(), persistent=False)
+
+    def _xoff_kw(self):
+        return dict(in_offset=self.x_off, tap_sums=self.tap_sums) if self.xoff_padded else {}
 
     def _padk(self, v, fill):
         v = v.detach().reshape(-1)
@@ -189,6 +230,8 @@ class _PlanLayer(nn.Module):
         return torch.cat([v, torch.full((self.k_pad - v.numel(),), fill, dtype=v.dtype, device=v.device)]).contiguous()
 
     def _bias(self):
+        if self.bias_fold is not None:
+            return self.bias_fold
         return self.layer.bias if self.bias_pad is None else self.bias_pad
 
     def _in_scale(self, numel):
@@ -212,7 +255,7 @@ class _PlanLayer(nn.Module):
 
     def _zp(self, codes):
         """The zero point that goes with `codes`: int8 codes of an unsigned quantiser are shifted codes (see __init__)."""
-        return self.zp_shift if (codes.dtype == torch.int8 and self.act.lo >= 0) else self.act.zp
+        return self.zp_shift if (codes.dtype == torch.int8 and self.act.lo >= 0) else self._kzp
 
     def _act_arg(self):
         """The layer's activation as the kernels' `act` argument (DLMCQ_ACT_*)."""
@@ -273,6 +316,13 @@ class Int8Layer(_PlanLayer):
             wsum = full.sum(dim=(1, 2, 3)).to(torch.int32).contiguous()
         self.register_buffer("wq", wq, persistent=False)
         self.register_buffer("wsum", wsum, persistent=False)
+        if self.act.xoff:
+            q = wq.reshape(self.k_pad, -1, self.c_pad)[:, :, :c].to(torch.float64)               # [K, R * S, real C]
+            tap = q.sum(dim=2) * self.w_scale.to(torch.float64)[:, None]
+            if self.w_off is not None:
+                tap = tap + c * self.w_off.to(torch.float64)[:, None]
+            r, s_ = (w.shape[2], w.shape[3]) if w.dim() == 4 else (1, 1)
+            self._fold_offset(tap.reshape(self.k_pad, r, s_))
 
     def _codes(self, x):
         """The activation codes of `x` (already codes, or fp32 quantised here in one pass), channel-padded for the kernel."""
@@ -285,6 +335,10 @@ class Int8Layer(_PlanLayer):
         c_pad = getattr(self, "c_pad", x.shape[1])
         if x.dim() == 4 and x.shape[1] != c_pad:
             x = _pad_channels(x, c_pad, self._zp_fill)
+        elif act.xoff and x.dim() == 4 and self.c != c_pad and self.w_off is not None:
+            # a producer's padded output channels carry ITS code of 0, which is no zero point under a float offset; the asymmetric-weight
+            # term sums the codes of every channel, so they must hold code 0 (the value the tap sums assume) - in place, for every taker alike
+            x[:, self.c:] = -128 if (x.dtype == torch.int8 and act.lo >= 0) else 0
         return x
 
     def _real_numel(self, codes):
@@ -324,7 +378,8 @@ class Int8Layer(_PlanLayer):
         kw = self._conv_kw()
         if self.w_off is not None:
             kw["w_offset"] = self.w_off
-        if self.relu or self.relu6 or residual is not None or emit is not None or self.w_off is not None:
+        kw.update(self._xoff_kw())
+        if self.relu or self.relu6 or residual is not None or emit is not None or self.w_off is not None or self.xoff_padded:
             res = K.conv2d_i8(codes, self.wq, self.wsum, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale,
                               residual=residual, act=self._act_arg(), emit=emit, want_out=self.want_out,
                               out_chunk_major=getattr(self, "out_cm", False), **kw)
@@ -351,6 +406,12 @@ class DwInt8Layer(Int8Layer):
         full = torch.zeros((self.k_pad,) + tuple(q.shape[2:]), dtype=torch.int16, device=q.device)
         full[:self.k] = q[:, 0]
         self.register_buffer("wq", full.permute(1, 2, 0).contiguous().to(torch.int8), persistent=False)   # [R, S, C]
+        if self.act.xoff:
+            tap = full.to(torch.float64) * self.w_scale.to(torch.float64)[:, None, None]             # one real input channel per output channel
+            if self.w_off is not None:
+                tap = tap + self.w_off.to(torch.float64)[:, None, None]
+                tap[self.k:] = 0.0
+            self._fold_offset(tap)
 
     def forward(self, x):
         lay, act = self.layer, self.act
@@ -358,7 +419,8 @@ class DwInt8Layer(Int8Layer):
         numel = self._real_numel(codes)
         emit = self._emit_for(codes.shape[0], self.k, *self._out_hw(codes))
         res = K.conv2d_dw_i8(codes, self.wq, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale, self.w_off,
-                             stride=lay.stride[0], padding=lay.padding[0], act=self._act_arg(), emit=emit, want_out=self.want_out)
+                             stride=lay.stride[0], padding=lay.padding[0], act=self._act_arg(), emit=emit, want_out=self.want_out,
+                             **self._xoff_kw())
         out, out_codes = res if emit is not None else (res, None)
         return self._finish(out, out_codes)
 
@@ -466,7 +528,7 @@ def _dwpw_pass(gm, report):
         if type(dw) is not DwInt8Layer or len(nd.args) != 1:
             continue
         lay = dw.layer
-        if dw.relu6:          # (the fused unit's kernel: ReLU only)
+        if dw.relu6 or dw.act.xoff:          # (the fused unit's kernel: ReLU only, no float activation offset)
             continue
         if not (tuple(lay.weight.shape[2:]) == (3, 3) and lay.stride[0] == 1 and lay.padding[0] == 1 and lay.dilation[0] == 1 and dw.pool is None and
                 dw.emit is not None and not dw.want_out and (dw.emit.lo, dw.emit.hi) == (0, 255) and not dw.emit_shift and dw.k_pad % 64 == 0):
@@ -479,7 +541,9 @@ def _dwpw_pass(gm, report):
             continue
         npw = next(iter(g1.users))
         pw = modules.get(npw.target) if npw.op == "call_module" else None
-        if type(pw) is not Int8Layer or npw.args != (g1,) or pw.relu6:
+        # (nor a pointwise layer whose input quantiser has a float offset: the unit's kernel takes the depthwise output's quantiser
+        #  zero point as the pointwise operand's integer zero point)
+        if type(pw) is not Int8Layer or npw.args != (g1,) or pw.relu6 or pw.act.xoff:
             continue
         pl = pw.layer
         if not (pl.weight.dim() == 4 and tuple(pl.weight.shape[2:]) == (1, 1) and pl.stride[0] == 1 and pl.padding[0] == 0 and pw.pool is None and
@@ -669,6 +733,12 @@ class StemLayer(_PlanLayer):
             wq, wsum = full.to(torch.int8).contiguous(), q.sum(dim=(1, 2, 3)).to(torch.int32).contiguous()
         self.register_buffer("wq", wq, persistent=False)
         self.register_buffer("wsum", wsum, persistent=False)
+        if self.act.xoff:
+            _, _, r, s_ = layer.weight.shape
+            tap = wq[:, :, :s_, :self.c].to(torch.float64).sum(dim=3) * self.w_scale.to(torch.float64)[:, None, None]   # [K, R, S]
+            if self.w_off is not None:
+                tap = tap + self.c * self.w_off.to(torch.float64)[:, None, None]
+            self._fold_offset(tap)
 
     def forward(self, x):
         lay, act = self.layer, self.act
@@ -676,13 +746,16 @@ class StemLayer(_PlanLayer):
         pad, st = lay.padding[0], lay.stride[0]
         k, _, r, s = lay.weight.shape
         emit = self._emit_for(x.shape[0], k, (x.shape[2] + 2 * pad - r) // st + 1, (x.shape[3] + 2 * pad - s) // st + 1)
-        in_kernel = self.pool == (3, 2, 1) and k <= 64 and self.w_off is None and not self.relu6   # conv + ReLU + MaxPool2d(3, 2, 1) + quantiser: one kernel
+        in_kernel = self.pool == (3, 2, 1) and k <= 64 and self.w_off is None and not self.relu6 and not act.xoff   # conv + ReLU + MaxPool2d(3, 2, 1) + quantiser: one kernel
         # an unsigned image quantiser's codes go into the padded buffer re-centred (`code - 128`: what the matrix cores multiply),
         # so the first-layer kernels need not xor every operand fragment they read; the zero point moves with them
         shifted = act.lo >= 0
-        xpad = K.quantize_pad_nhwc4(x, act.scale, act.zp, act.lo, act.hi, act.form, pad, g=act.g(numel), shift128=shifted)
-        res = K.conv2d_i8_stem(xpad, self.wq, self.wsum, lay.bias, self._in_scale(numel), self.zp_shift if shifted else act.zp, self.w_scale, s, stride=st,
-                               act=self._act_arg(), emit=emit, want_out=self.want_out, pool=in_kernel, w_offset=self.w_off, channels=self.c)
+        # (a float offset pads with code 0 - its zero has no code - and the kernel takes the difference as its border term)
+        xpad = K.quantize_pad_nhwc4(x, act.scale, act.zp, act.lo, act.hi, act.form, pad, g=act.g(numel), shift128=shifted, pad_code0=act.xoff)
+        xkw = dict(self._xoff_kw(), pad=pad) if self.xoff_padded else {}
+        res = K.conv2d_i8_stem(xpad, self.wq, self.wsum, self._bias() if act.xoff else lay.bias, self._in_scale(numel),
+                               self.zp_shift if shifted else self._kzp, self.w_scale, s, stride=st, act=self._act_arg(), emit=emit,
+                               want_out=self.want_out, pool=in_kernel, w_offset=self.w_off, channels=self.c, **xkw)
         out, out_codes = res if emit is not None else (res, None)
         return (out, out_codes) if in_kernel else self._finish(out, out_codes)
 
@@ -701,6 +774,7 @@ class FusionReport:
         self.chained = 0      # block end + next block's 1x1 pairs running as one kernel
         self.chunk_major = 0  # fp32 block outputs kept chunk-major between two kernels that walk them chunk by chunk (_block_layout_pass)
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
+        self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
         self.skipped = []
 
     def __repr__(self):
@@ -975,7 +1049,7 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True):
+                   relu6=True, act_offsets=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -992,7 +1066,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     (_block_layout_pass; A/B and tests).
     `relu6=False` keeps every ReLU6 (nn.ReLU6, nn.Hardtanh(0, 6), F.relu6, F.hardtanh(x, 0, 6)) a separate op after an fp32 output
     instead of fusing it into the layer's epilogue (DLMCQ_ACT_RELU6) - the plan before ReLU6 fusion, for A/B runs and tests.  The
-    dual, chain and depthwise + pointwise kernels know ReLU alone: a layer ending in ReLU6 runs on its own kernel."""
+    dual, chain and depthwise + pointwise kernels know ReLU alone: a layer ending in ReLU6 runs on its own kernel.
+    `act_offsets=True` also plans QBase layers whose activation quantiser has a per-tensor FLOAT offset (x^ = q * s^ + o: the
+    unsigned min/max quantiser of any tensor that can go negative - shortcut sums, normalised images): producers emit their codes
+    with that offset, the offset times the weight sums goes into the bias, and padded layers run the border term of the *_xoff
+    entry points.  Off by default: the plan without it is the plan as it was."""
     if model.training:
         raise RuntimeError("fuse_inference: the plan is for inference - call model.eval() first")
     report = report if report is not None else FusionReport()
@@ -1010,7 +1088,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             return None
         if node.target not in specs:
             mod = modules[node.target]
-            specs[node.target] = _frozen_spec(mod) if isinstance(mod, (QBase, FSPTQBase)) else None
+            specs[node.target] = _frozen_spec(mod, act_offsets) if isinstance(mod, (QBase, FSPTQBase)) else None
             if specs[node.target] is None and isinstance(mod, (QBase, FSPTQBase, RootQBase)):
                 report.skipped.append(node.target)
         return specs[node.target]
@@ -1071,7 +1149,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             on_codes = cons and all(c is not None for c in cons) and len({c.key for c in cons}) == 1
             # the first-layer kernel pools in fp32 itself (any consumers); elsewhere the pool runs on the emitted codes
             in_stem = (spec[4] == "stem" and _pool_params(mp, modules) == (3, 2, 1) and modules[node.target].weight.shape[0] <= 64 and
-                       spec[5] is None and not act6)   # (the pooling first-layer kernel has no weight-offset term, and ReLU alone)
+                       spec[5] is None and not act6 and not spec[0].xoff)   # (the pooling first-layer kernel has no weight-offset term, and ReLU alone)
             if on_codes or in_stem:
                 pool = _pool_params(mp, modules)
                 chain.append(mp)
@@ -1101,7 +1179,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         # the shortcut is itself a not-yet-planned int8 convolution read by nobody else: one dual kernel
         other = spec_of(residual) if residual is not None and residual.op == "call_module" else None
         dual = (other is not None and other[4] == "gemm" and spec[5] is None and other[5] is None and list(residual.users) == [chain[1]] and
-                modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4 and not act6)   # (dual kernel: ReLU alone)
+                modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4 and not act6 and   # (dual kernel: ReLU alone)
+                not any(sp[0].xoff and int(modules[t].padding[0]) > 0 for sp, t in ((spec, node.target), (other, residual.target))))
         if dry_run:       # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
             gm.add_module(name, _DryNode())
         else:
@@ -1156,6 +1235,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         report.pooled += pool is not None
         report.relu += relu
         report.relu6 += act6
+        report.act_offset += spec[0].xoff + (dual and other[0].xoff)
         report.residual += residual is not None
         report.emit += emit is not None
         report.fp32_outputs += bool(fp32_needed or emit is None)

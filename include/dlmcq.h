@@ -108,6 +108,10 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * K loop) instead of the plain halo-tile kernel.  Same bytes; measured 12 - 20 % SLOWER than the plain kernel (round 5, LABNOTES 15), hence
  * not the default - kept built and tested for same-box A/B timing. */
 #define DLMCQ_PIPELINED 0x1000
+/* DLMCQ_PAD_CODE0 (the `form` of dlmcq_quantize_pad_nhwc4 only; every other entry point returns DLMCQ_EINVAL for it): the padded border
+ * holds code 0 (with DLMCQ_EMIT_SHIFT128: the byte 0x80) instead of the code of x' = 0.  The padding of a float-offset quantiser
+ * (x^ = q * s^ + o, o no code) for dlmcq_conv2d_i8_stem_xoff with a zero point of 0. */
+#define DLMCQ_PAD_CODE0 0x8000
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */
@@ -603,6 +607,44 @@ int dlmcq_conv2d_i8_stem_pool_fused(const void* xpad, const int8_t* w, float* ou
  */
 int dlmcq_maxpool_codes_nhwc(const void* x, void* y, int64_t N, int64_t H, int64_t W, int64_t C, int32_t kernel,
                              int32_t stride, int32_t pad, int32_t x_is_unsigned, dlmcq_stream_t stream);
+
+/* ---- float activation offsets: the *_xoff convolution entry points ----
+ * A QBase activation quantiser with a per-tensor FLOAT offset o (x^ = q * s^ + o, modules/base.py:96-102; ops.py:20-34 sets
+ * o = min(x) for unsigned ranges) has no integer zero point, and zero padding pads x^ with 0, which is no code.  With
+ * T[k](p,q) = SUM over the IN-BOUNDS taps (r,s) of tap[k][r][s], tap[k][r][s] = SUM_c (real channels) w^[k,c,r,s]:
+ *     out[n,p,q,k] = s^ * SUM_in q * w^  +  o * T[k](p,q)  +  bias[k]
+ * The first term is what the fused / _asym calls compute (the caller passes `in_zero_point` as for integer codes - usually NULL - and
+ * pads with that zero point's code: padded taps then add exactly 0).  The caller folds o * SUM_{all taps} tap[k] into `bias` (build
+ * time; `bias` must not be NULL then), and these entry points subtract  o * SUM_{out-of-bounds taps} tap[k][r][s]  at border pixels
+ * only, as ONE fused multiply-add after the bias and weight-offset terms, before residual / activation / quantiser.  The border sum
+ * is taken in fp32, r-major, s ascending.
+ *   in_offset: device fp32 scalar o.  tap_sums: device fp32 [R * S][K] (16-byte aligned), tap-major.  Both non-NULL (else EINVAL).
+ *   w_offset: NULL for symmetric weights, else as in the _asym calls.
+ * Unpadded layers (pad = 0) have no border: the call is then the fused / _asym call itself (in_offset and tap_sums unused).
+ * Routes: dlmcq_conv2d_i8_nhwc_xoff runs on conv_i8_mfma_kernel (unswapped epilogue, 64 / 128-channel tiles): the halo-tile, pipelined
+ * 3x3 and pointwise kernels decline it (DLMCQ_ROUTE_ONLY answers DLMCQ_ROUTE_TILED); no dual form.  dlmcq_conv2d_dw_i8_nhwc_xoff:
+ * 3 x 3 layers with C % 16 == 0, C <= 2048, 16-byte-aligned codes (the two vector kernels; the matrix-core depthwise kernel
+ * declines: DLMCQ_ROUTE_DW), anything else EINVAL.  dlmcq_conv2d_i8_stem_xoff: R = 3 or 7 (unswapped epilogue), `pad` = the padding
+ * of the NHWC4 buffer (dlmcq_quantize_pad_nhwc4 with DLMCQ_PAD_CODE0), `C` the image's real channels; no pooling form.  DLMCQ_ACT_*
+ * as in the fused calls.  No offset variant exists for the pooling first layer, dwpw, chain, dual or dual-chain calls. */
+int dlmcq_conv2d_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                              const float* in_scale, const float* in_zero_point, const float* w_scale, const float* w_offset,
+                              int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride,
+                              int32_t pad, int32_t dilation, int32_t x_is_unsigned, const float* residual, int32_t relu, void* codes,
+                              const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                              float q_ste_g, const float* in_offset, const float* tap_sums, dlmcq_stream_t stream);
+int dlmcq_conv2d_dw_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
+                                 const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N, int64_t H,
+                                 int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad, int32_t x_is_unsigned,
+                                 int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                                 int32_t q_hi, int32_t q_form, float q_ste_g, const float* in_offset, const float* tap_sums,
+                                 dlmcq_stream_t stream);
+int dlmcq_conv2d_i8_stem_xoff(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                              const float* in_scale, const float* in_zero_point, const float* w_scale, const float* w_offset,
+                              int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R, int64_t S, int32_t stride,
+                              int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
+                              const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                              const float* in_offset, const float* tap_sums, dlmcq_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Per-layer timing of the fused plan (HIP events around every plan node).  python tools/plan_profile.py [model] [batch]
-(model mobileone_s1 is profiled as BASELINE config 5: QBase W4A8, asymmetric per-channel weights)"""
+"""Per-layer timing of the fused plan (HIP events around every plan node).  python tools/plan_profile.py [model] [batch] [qbase] [act_offsets]
+(model mobileone_s1 is profiled as BASELINE config 5: QBase W4A8, asymmetric per-channel weights; `qbase` profiles any other model under that
+quantiser too, `act_offsets` builds the plan with fuse_inference(act_offsets=True))"""
 import json
 import os
 import sys
@@ -19,8 +20,12 @@ name = sys.argv[1] if len(sys.argv) > 1 else "resnet50"
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 dev = "cuda:0"
 torch.manual_seed(2333)
-if name == "mobileone_s1":
+qbase = name == "mobileone_s1" or "qbase" in sys.argv[3:]
+act_offsets = "act_offsets" in sys.argv[3:]
+if qbase:
     model = W.MODELS[name]().to(dev).eval()
+    if name != "mobileone_s1":
+        model = merge_bn(model, inplace=True, allow_missing=True)
     quantize_model(model, {"weight": {"enable": True, "type": "minmax_channel", "args": {"n_bits": 4, "signed": False}},
                            "input": {"enable": True, "type": "minmax_tensor", "args": {"n_bits": 8, "signed": False}},
                            "exclude_layers": [], "override_options": []}, None)
@@ -32,7 +37,7 @@ else:
 recs = []
 with torch.no_grad():
     model(x)
-    plan = fuse_inference(model)
+    plan = fuse_inference(model, act_offsets=act_offsets)
     for _ in range(2):
         plan(x)
 
