@@ -3,9 +3,9 @@
 Everything here is plumbing: shape bookkeeping, output allocation and the current-stream handle.
 The arithmetic happens in libdlmcq.so; tensors that are not on the GPU are refused (no fallback).
 """
-import math
-
+import collections
 import ctypes
+import math
 
 import torch
 
@@ -42,11 +42,6 @@ class _Profile:
 
 
 PROFILE = _Profile()
-
-
-def _no_shift(emit, what):
-    if emit is not None and emit.shift128:
-        raise ValueError(f"{what}: this entry point does not emit shifted codes (EmitCodes.shift128)")
 
 
 def _f32c(t, like):
@@ -435,12 +430,93 @@ def _act(relu, act):
     return int(act)
 
 
+# ---- operand marshalling shared by the int8 convolution wrappers below (tensors -> the positional arguments of include/dlmcq.h)
+def _flat(t, like, k=None):
+    """A scale / zero point / offset operand as a flat contiguous fp32 tensor on `like`'s device: None stays None, a tensor is detached,
+    a Python number becomes one entry.  With `k`, a single entry is broadcast to `k` entries (a copy; [k] entries pass as they are)."""
+    if t is None:
+        return None
+    t = _f32c(t.detach() if isinstance(t, torch.Tensor) else t, like).reshape(-1)
+    return t.expand(k).contiguous() if k is not None and t.numel() == 1 else t
+
+
+def _bias_c(bias):
+    return None if bias is None else bias.detach().contiguous()
+
+
+def _nhwc(t):
+    """4-D `t` in channels_last memory (a copy only when it is not already)."""
+    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+
+
+def _out_hw(h, w, r, s, stride=1, padding=0, dilation=1):
+    """Output (P, Q) of an r x s convolution (or pooling window) over h x w."""
+    return (h + 2 * padding - dilation * (r - 1) - 1) // stride + 1, (w + 2 * padding - dilation * (s - 1) - 1) // stride + 1
+
+
+def _quantiser(emit, alloc, like, shifted, what):
+    """The consumer's quantiser `emit` (EmitCodes or None) as the seven values every fused entry point ends with: (codes tensor,
+    q_scale, q_zp, lo, hi, form, g), the codes allocated by `alloc(dtype)`.  `shifted`: whether the entry point takes the shifted
+    emission (EmitCodes.shift128, carried in the form); where it does not, asking for it is an error."""
+    if emit is None:
+        return None, None, None, 0, 0, 0, 0.0
+    if emit.shift128 and not shifted:
+        raise ValueError(f"{what}: this entry point does not emit shifted codes (EmitCodes.shift128)")
+    return (alloc(emit.dtype), _flat(emit.scale, like), _flat(emit.zero_point, like), emit.lo, emit.hi,
+            emit.form_arg if shifted else emit.form, emit.g)
+
+
+def _q_args(q, flags=0):
+    """_quantiser's values as call arguments, `flags` (DLMCQ_FORCE_TILED, DLMCQ_ROUTE_ONLY, ...) or-ed into the form."""
+    codes, q_scale, q_zp, lo, hi, form, g = q
+    return N.ptr(codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | flags, g
+
+
+def _as_chunk_major(out):
+    """A channels_last fp32 (N, K, P, Q) tensor the kernel wrote chunk-major: the same memory, read as [K / 64][M][64]."""
+    n, k, p, q = out.shape
+    return ChunkMajor(out.permute(0, 2, 3, 1).reshape(k // 64, n * p * q, 64), out.shape)
+
+
+# One convolution operand, marshalled: `codes` in the kernel's layout, `keep` the small tensors made for the call (alive until it is
+# issued), `shape` of the output, and the two argument runs in the order of include/dlmcq.h as a SECOND operand has them - `ptrs`
+# (x, w, bias, wsum, in_scale, in_zero_point, w_scale) and `geom` (H, W, C, R, S, stride, pad, dilation, x_is_unsigned)
+_Operand = collections.namedtuple("_Operand", "codes keep shape ptrs geom")
+
+
+def _operand(t):
+    """The operand dict `t` (codes, wq, wsum, bias, in_scale, in_zp, w_scale, optional stride / padding / dilation; codes (N, C, H, W),
+    or (N, C) for a linear layer) as an _Operand.  A one-entry `w_scale` is broadcast to [K]."""
+    codes, wq = t["codes"], t["wq"]
+    N.require_gpu(codes, wq)
+    K_, R, S, _ = wq.shape
+    st, pd, dl = int(t.get("stride", 1)), int(t.get("padding", 0)), int(t.get("dilation", 1))
+    if codes.dim() == 2:
+        codes = codes.contiguous()
+        (n, c), h, w_ = codes.shape, 1, 1
+        shape = (n, K_)
+    else:
+        codes = _nhwc(codes)
+        n, c, h, w_ = codes.shape
+        shape = (n, K_) + _out_hw(h, w_, R, S, st, pd, dl)
+    bias, si, zp, ws = _bias_c(t["bias"]), _flat(t["in_scale"], codes), _flat(t["in_zp"], codes), _flat(t["w_scale"], codes, K_)
+    ptrs = (N.ptr(codes), N.ptr(wq), N.ptr(bias), N.ptr(t["wsum"]), N.ptr(si), N.ptr(zp), N.ptr(ws))
+    return _Operand(codes, (bias, si, zp, ws), shape, ptrs, (h, w_, c, R, S, st, pd, dl, int(codes.dtype == torch.uint8)))
+
+
+def _head(o, out):
+    """The eight pointers every entry point starts with: a first operand's, the fp32 output (or None) after the weights."""
+    x, w, *rest = o.ptrs
+    return (x, w, N.ptr(out), *rest)
+
+
 def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding=0, dilation=1,
               residual=None, relu=False, emit=None, want_out=True, w_offset=None, force_tiled=False, pipelined=False, observe=False,
               out_chunk_major=False, act=None, in_offset=None, tap_sums=None):
     """Fused int8 conv / linear on the matrix cores.  `codes`: uint8/int8 activation codes, logically
     (N, C, H, W) in channels_last memory, or (N, C) for a linear layer.  Returns fp32 (N, K, P, Q) in
-    channels_last memory (or (N, K)).
+    channels_last memory (or (N, K)).  The operands are marshalled by `_operand`: scales and zero point as `_flat` takes them, a
+    one-entry `w_scale` broadcast to [K], codes in another layout copied.
 
     Epilogue options (dlmcq_conv2d_i8_nhwc_fused): `residual` (fp32, the output's shape and layout) is added,
     `relu` applied (or the activation `act` names: `act=N.ACT_RELU6` is F.relu6), and with `emit=EmitCodes(...)` the consumer's
@@ -456,181 +532,128 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
     residual is converted first (a copy) and the output comes back as an ordinary tensor.
     `in_offset` (fp32 device scalar o) with `tap_sums` (fp32 [R * S, K]): a float activation offset (dlmcq_conv2d_i8_nhwc_xoff) - `bias`
     must already hold o * tap_sums.sum(0); border pixels lose o * (their out-of-bounds taps' sums).  Not with `observe`."""
-    N.require_gpu(codes, wq)
     if (in_offset is None) != (tap_sums is None):
         raise ValueError("conv2d_i8: in_offset and tap_sums go together")
+    o = _operand(dict(codes=codes, wq=wq, wsum=wsum, bias=bias, in_scale=in_scale, in_zp=in_zp, w_scale=w_scale, stride=stride,
+                      padding=padding, dilation=dilation))
+    codes, shape = o.codes, o.shape      # (codes: the device / dtype anchor for the small parameter tensors)
     linear = codes.dim() == 2
-    if linear:
-        n, c = codes.shape
-        h = w_ = 1
-        codes = codes.contiguous()
-    else:
-        n, c, h, w_ = codes.shape
-        if not codes.is_contiguous(memory_format=torch.channels_last):
-            codes = codes.contiguous(memory_format=torch.channels_last)
-    K, R, S, _ = wq.shape
-    P = (h + 2 * padding - dilation * (R - 1) - 1) // stride + 1
-    Q = (w_ + 2 * padding - dilation * (S - 1) - 1) // stride + 1
+    (n, K), (h, w_, c, R, S, st, pd, dl, uns) = shape[:2], o.geom
+    geo = (n, h, w_, c, K, R, S, st, pd, dl, uns)
 
     def alloc(dtype):
         if linear:
-            return torch.empty((n, K), dtype=dtype, device=codes.device)
-        return torch.empty((n, K, P, Q), dtype=dtype, device=codes.device, memory_format=torch.channels_last)
+            return torch.empty(shape, dtype=dtype, device=codes.device)
+        return torch.empty(shape, dtype=dtype, device=codes.device, memory_format=torch.channels_last)
     act = _act(relu, act)
     fused = residual is not None or act or emit is not None or w_offset is not None or (observe and want_out) or in_offset is not None
     if in_offset is not None and observe:
         raise ValueError("conv2d_i8: the offset entry point has no observing form")
     if not want_out and emit is None:
         raise ValueError("conv2d_i8: nothing to produce (want_out=False without emit)")
-    if w_offset is not None:
-        w_offset = _f32c(w_offset.detach(), codes).reshape(-1)
     out = alloc(torch.float32) if want_out else None
-    ref = codes   # device / dtype anchor for the small parameter tensors
-    w_scale = _f32c(w_scale.detach(), ref).reshape(-1)
-    if w_scale.numel() == 1:
-        w_scale = w_scale.expand(K).contiguous()
-    in_scale = _f32c(in_scale.detach(), ref).reshape(-1)
-    in_zp = None if in_zp is None else _f32c(in_zp, ref).reshape(-1)
-    bias = None if bias is None else bias.detach().contiguous()
-    args = (N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
-            n, h, w_, c, K, R, S, int(stride), int(padding), int(dilation), int(codes.dtype == torch.uint8))
-    out_elems = n * K * P * Q
+    head = _head(o, out)
+    out_elems = math.prod(shape)
     ops = 2 * out_elems * c * R * S
+    if not fused:
+        if force_tiled:
+            raise ValueError("conv2d_i8: force_tiled needs an epilogue (the plain fp32 entry point always runs the tiled kernel)")
+        PROFILE.launch("conv_i8", codes.numel() + out_elems * 4 + wq.numel(),
+                       lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_f32(*head, *geo, N.stream_ptr())), ops)
+        return out
+    icm = isinstance(residual, ChunkMajor)
+    ocm = bool(out_chunk_major) and out is not None and not linear
+    if residual is not None:
+        if tuple(residual.shape) != shape or residual.dtype != torch.float32:
+            raise ValueError("conv2d_i8: residual must be fp32 of the output's shape")
+        if icm:
+            residual = residual.buf
+        N.require_gpu(residual)
+        if not icm:
+            residual = residual.contiguous() if linear else _nhwc(residual)
+    q = _quantiser(emit, alloc, codes, True, "conv2d_i8")
+    nbytes = codes.numel() + wq.numel() + out_elems * (4 * (out is not None) + 4 * (residual is not None) + (emit is not None))
+    flags = (N.FORCE_TILED if force_tiled else 0) | (N.PIPELINED if pipelined else 0)
+    # the entry point: head, [w_offset], geometry, the epilogue, [what only this entry point takes]
+    w_off, trailer, observing = (), (), False
+    if in_offset is not None or w_offset is not None:
+        w_offset = _flat(w_offset, codes)
+        w_off = (N.ptr(w_offset),)
+    if in_offset is not None:
+        fn = N.lib.dlmcq_conv2d_i8_nhwc_xoff
+        in_offset, tap_sums = _flat(in_offset, codes), _flat(tap_sums, codes)
+        trailer = (N.ptr(in_offset), N.ptr(tap_sums))
+    elif w_offset is not None:
+        fn = N.lib.dlmcq_conv2d_i8_nhwc_asym
+    elif observe and out is not None:
+        fn, observing = N.lib.dlmcq_conv2d_i8_nhwc_fused_observed, True
+        cap = int(N.lib.dlmcq_conv2d_i8_observed_partials(out_elems // K, K))
+        partials = torch.empty(3 * cap, dtype=torch.float32, device=codes.device)
+        count = ctypes.c_int64(0)
+        trailer = (N.ptr(partials), 3 * cap, ctypes.byref(count))
+    else:
+        fn = N.lib.dlmcq_conv2d_i8_nhwc_fused
+
+    def call(extra=0):      # (`residual` as it is when the call is made: a ChunkMajor one may be converted below)
+        return fn(*head, *w_off, *geo, N.ptr(residual), act, *_q_args(q, flags | extra), *trailer, N.stream_ptr())
+    cm_bits = 0
+    if icm or ocm:
+        # chunk-major block tensors: only where the block-end kernel takes the call, with one layout for its fp32 tensors (the
+        # library's own dispatch answers: DLMCQ_ROUTE_ONLY).  Otherwise: the ordinary layout, the residual converted
+        if (not w_off and not observing and (residual is None or out is None or icm == ocm)
+                and N.route(call(N.ROUTE_ONLY)) == N.ROUTE_PWR):
+            cm_bits = (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
+        else:
+            if icm:
+                residual = ChunkMajor(residual, shape).to_nhwc()
+            ocm = False
     # (the profile tag - which kernel of the library takes the launch - is asked of the library itself: the same call with
     #  DLMCQ_ROUTE_ONLY runs the dispatch code and launches nothing; only when bench.py's per-kernel events are on)
-    if fused:
-        out_codes = q_scale = q_zp = None
-        lo = hi = form = 0
-        g = 0.0
-        icm = isinstance(residual, ChunkMajor)
-        ocm = bool(out_chunk_major) and out is not None and not linear
-        if residual is not None:
-            if tuple(residual.shape) != ((n, K) if linear else (n, K, P, Q)) or residual.dtype != torch.float32:
-                raise ValueError("conv2d_i8: residual must be fp32 of the output's shape")
-            if icm:
-                residual = residual.buf
-            N.require_gpu(residual)
-            if icm:
-                pass
-            elif linear:
-                residual = residual.contiguous()
-            elif not residual.is_contiguous(memory_format=torch.channels_last):
-                residual = residual.contiguous(memory_format=torch.channels_last)
-        if emit is not None:
-            out_codes = alloc(emit.dtype)
-            q_scale = _f32c(emit.scale.detach(), ref).reshape(-1)
-            q_zp = None if emit.zero_point is None else _f32c(emit.zero_point, ref).reshape(-1)
-            lo, hi, form, g = emit.lo, emit.hi, emit.form_arg, emit.g
-        nbytes = codes.numel() + wq.numel() + out_elems * (4 * (out is not None) + 4 * (residual is not None) + (emit is not None))
-        form |= (N.FORCE_TILED if force_tiled else 0) | (N.PIPELINED if pipelined else 0)
-        if in_offset is not None:
-            in_offset = _f32c(in_offset, ref).reshape(-1)
-            tap_sums = _f32c(tap_sums.detach(), ref).contiguous()
-
-            def call(extra=0):
-                return N.lib.dlmcq_conv2d_i8_nhwc_xoff(
-                    *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
-                    lo, hi, form | extra, g, N.ptr(in_offset), N.ptr(tap_sums), N.stream_ptr())
-        elif w_offset is not None:
-            def call(extra=0):
-                return N.lib.dlmcq_conv2d_i8_nhwc_asym(
-                    *args[:8], N.ptr(w_offset), *args[8:], N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp),
-                    lo, hi, form | extra, g, N.stream_ptr())
-        elif observe and out is not None:
-            cap = int(N.lib.dlmcq_conv2d_i8_observed_partials(n * P * Q, K))
-            partials = torch.empty(3 * cap, dtype=torch.float32, device=codes.device)
-            count = ctypes.c_int64(0)
-
-            def call(extra=0):
-                return N.lib.dlmcq_conv2d_i8_nhwc_fused_observed(
-                    *args, N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
-                    N.ptr(partials), 3 * cap, ctypes.byref(count), N.stream_ptr())
-        else:
-            def call(extra=0):
-                return N.lib.dlmcq_conv2d_i8_nhwc_fused(
-                    *args, N.ptr(residual), act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g,
-                    N.stream_ptr())
-        cm_bits = 0
-        if icm or ocm:
-            # chunk-major block tensors: only where the block-end kernel takes the call, with one layout for its fp32 tensors (the
-            # library's own dispatch answers: DLMCQ_ROUTE_ONLY).  Otherwise: the ordinary layout, the residual converted
-            if (w_offset is None and in_offset is None and not (observe and out is not None) and (residual is None or out is None or icm == ocm)
-                    and N.route(call(N.ROUTE_ONLY)) == N.ROUTE_PWR):
-                cm_bits = (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
-            else:
-                if icm:
-                    residual = ChunkMajor(residual, (n, K, P, Q)).to_nhwc()
-                ocm = False
-        tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_i8"
-        PROFILE.launch(tag, nbytes, lambda: N.check(call(cm_bits)), ops)
-        if observe and out is not None and w_offset is None and count.value > 0:
-            out._dlmcq_mm = (partials, int(count.value), out._version)      # (an in-place write to `out` later invalidates it: the version is checked)
-        if ocm:     # (the same memory, read as [K / 64][M][64])
-            out = ChunkMajor(out.permute(0, 2, 3, 1).reshape(K // 64, n * P * Q, 64), (n, K, P, Q))
-        return (out, out_codes) if emit is not None else out
-    if force_tiled:
-        raise ValueError("conv2d_i8: force_tiled needs an epilogue (the plain fp32 entry point always runs the tiled kernel)")
-    args = args + (N.stream_ptr(),)
-    PROFILE.launch("conv_i8", codes.numel() + out_elems * 4 + wq.numel(), lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_f32(*args)), ops)
-    return out
+    tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_i8"
+    PROFILE.launch(tag, nbytes, lambda: N.check(call(cm_bits)), ops)
+    if observing and count.value > 0:
+        out._dlmcq_mm = (partials, int(count.value), out._version)      # (an in-place write to `out` later invalidates it: the version is checked)
+    if ocm:
+        out = _as_chunk_major(out)
+    return (out, q[0]) if emit is not None else out
 
 
 def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, stride=1, padding=0, relu=False, emit=None, want_out=True,
                  force_tiled=False, act=None, in_offset=None, tap_sums=None):
     """Depthwise convolution on activation codes (dlmcq_conv2d_dw_i8_nhwc).  codes: (N, C, H, W) uint8/int8 channels_last,
-    C % 4 == 0; wq: int8 [R, S, C] (tap-major); per-channel w_scale / w_offset / bias [C].  Returns fp32 (N, C, P, Q)
+    C % 4 == 0; wq: int8 [R, S, C] (tap-major); per-channel w_scale / w_offset / bias [C] (passed as given: no broadcast).  Returns fp32 (N, C, P, Q)
     channels_last, or `(out, codes)` with `emit`.  `relu` / `act` as in conv2d_i8.  `in_offset` / `tap_sums` ([R * S, C]): a float
     activation offset, as in conv2d_i8 (dlmcq_conv2d_dw_i8_nhwc_xoff: 3 x 3 layers, C % 16 == 0)."""
     if (in_offset is None) != (tap_sums is None):
         raise ValueError("conv2d_dw_i8: in_offset and tap_sums go together")
-    _no_shift(emit, "conv2d_dw_i8")
     N.require_gpu(codes, wq)
     n, c, h, w_ = codes.shape
-    if not codes.is_contiguous(memory_format=torch.channels_last):
-        codes = codes.contiguous(memory_format=torch.channels_last)
+    codes = _nhwc(codes)
     R, S, _ = wq.shape
-    P, Q = (h + 2 * padding - R) // stride + 1, (w_ + 2 * padding - S) // stride + 1
+    P, Q = _out_hw(h, w_, R, S, stride, padding)
     if not want_out and emit is None:
         raise ValueError("conv2d_dw_i8: nothing to produce (want_out=False without emit)")
 
     def alloc(dtype):
         return torch.empty((n, c, P, Q), dtype=dtype, device=codes.device, memory_format=torch.channels_last)
+    q = _quantiser(emit, alloc, codes, False, "conv2d_dw_i8")
     out = alloc(torch.float32) if want_out else None
-    w_scale = _f32c(w_scale.detach(), codes).reshape(-1)
-    w_offset = None if w_offset is None else _f32c(w_offset.detach(), codes).reshape(-1)
-    in_scale = _f32c(in_scale.detach(), codes).reshape(-1)
-    in_zp = None if in_zp is None else _f32c(in_zp, codes).reshape(-1)
-    bias = None if bias is None else bias.detach().contiguous()
-    out_codes = q_scale = q_zp = None
-    lo = hi = form = 0
-    g = 0.0
-    if emit is not None:
-        out_codes = alloc(emit.dtype)
-        q_scale = _f32c(emit.scale.detach(), codes).reshape(-1)
-        q_zp = None if emit.zero_point is None else _f32c(emit.zero_point, codes).reshape(-1)
-        lo, hi, form, g = emit.lo, emit.hi, emit.form, emit.g
-    oe = n * c * P * Q
-    form |= N.FORCE_TILED if force_tiled else 0
-
+    small = (_bias_c(bias), _flat(in_scale, codes), _flat(in_zp, codes), _flat(w_scale, codes), _flat(w_offset, codes))
+    fn, trailer = N.lib.dlmcq_conv2d_dw_i8_nhwc, ()
     if in_offset is not None:
-        in_offset = _f32c(in_offset, codes).reshape(-1)
-        tap_sums = _f32c(tap_sums.detach(), codes).contiguous()
+        in_offset, tap_sums = _flat(in_offset, codes), _flat(tap_sums, codes)
+        fn, trailer = N.lib.dlmcq_conv2d_dw_i8_nhwc_xoff, (N.ptr(in_offset), N.ptr(tap_sums))
+    args = (N.ptr(codes), N.ptr(wq), N.ptr(out), *map(N.ptr, small), n, h, w_, c, R, S, int(stride), int(padding),
+            int(codes.dtype == torch.uint8), _act(relu, act))
+    flags = N.FORCE_TILED if force_tiled else 0
 
-        def call(extra=0):
-            return N.lib.dlmcq_conv2d_dw_i8_nhwc_xoff(
-                N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
-                n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
-                N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.ptr(in_offset), N.ptr(tap_sums), N.stream_ptr())
-    else:
-        def call(extra=0):
-            return N.lib.dlmcq_conv2d_dw_i8_nhwc(
-                N.ptr(codes), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), N.ptr(w_offset),
-                n, h, w_, c, R, S, int(stride), int(padding), int(codes.dtype == torch.uint8), _act(relu, act), N.ptr(out_codes),
-                N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.stream_ptr())
+    def call(extra=0):
+        return fn(*args, *_q_args(q, flags | extra), *trailer, N.stream_ptr())
+    oe = n * c * P * Q
     # (the profile tag - conv_dw: the vector kernels, conv_dwm: the matrix-core kernel - from the library's own dispatch, DLMCQ_ROUTE_ONLY)
     tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_dw"
     PROFILE.launch(tag, codes.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)), lambda: N.check(call()), 2 * oe * R * S)
-    return (out, out_codes) if emit is not None else out
+    return (out, q[0]) if emit is not None else out
 
 
 DWPW_WIDTHS = (128, 192, 512)      # pointwise output widths dlmcq_conv2d_dwpw_i8_nhwc is built for
@@ -649,13 +672,8 @@ def dwpw_table(wq, bias, in_scale, in_zp, w_scale, w_offset, x_unsigned=True):
     if (r, s_) != (3, 3) or c % 64:
         raise ValueError("dwpw_table: 3 x 3 weights [3, 3, C], C % 64 == 0")
     table = torch.empty((c // 64, 64, 8), dtype=torch.int32, device=wq.device)
-    ws = _f32c(w_scale.detach(), wq).reshape(-1)
-    wo = None if w_offset is None else _f32c(w_offset.detach(), wq).reshape(-1)
-    si = _f32c(in_scale.detach(), wq).reshape(-1)
-    zp = None if in_zp is None else _f32c(in_zp, wq).reshape(-1)
-    b = None if bias is None else bias.detach().contiguous()
-    N.check(N.lib.dlmcq_dwpw_pack_table(N.ptr(wq), N.ptr(b), N.ptr(si), N.ptr(zp), N.ptr(ws), N.ptr(wo), c, int(bool(x_unsigned)),
-                                        N.ptr(table), N.stream_ptr()))
+    small = (_bias_c(bias), _flat(in_scale, wq), _flat(in_zp, wq), _flat(w_scale, wq), _flat(w_offset, wq))
+    N.check(N.lib.dlmcq_dwpw_pack_table(N.ptr(wq), *map(N.ptr, small), c, int(bool(x_unsigned)), N.ptr(table), N.stream_ptr()))
     return table
 
 
@@ -664,97 +682,63 @@ def conv2d_dwpw_i8(codes, table, dw_asym, dw_bias, dw_relu, in_zp, emit, pw, rel
     quantiser `emit2`) in one kernel (dlmcq_conv2d_dwpw_i8_nhwc).  codes: (N, C, H, W) uint8 / int8 channels_last; table:
     dwpw_table(...) of the depthwise layer; pw: dict with wq [K, 1, 1, C], wsum, bias, w_scale, optional w_offset and in_scale (the
     scale the pointwise layer dequantises its input with).  Returns the codes (N, K, H, W)."""
-    _no_shift(emit, "conv2d_dwpw_i8")
-    _no_shift(emit2, "conv2d_dwpw_i8")
     N.require_gpu(codes, table, pw["wq"])
-    if not codes.is_contiguous(memory_format=torch.channels_last):
-        codes = codes.contiguous(memory_format=torch.channels_last)
+    codes = _nhwc(codes)
     n, c, h, w_ = codes.shape
     k = pw["wq"].shape[0]
     if tuple(pw["wq"].shape[1:]) != (1, 1, c) or emit is None or emit2 is None or tuple(table.shape) != (c // 64, 64, 8):
         raise ValueError("conv2d_dwpw_i8: a pointwise layer [K, 1, 1, C] on the depthwise layer's codes, both quantisers given")
-    out = torch.empty((n, k, h, w_), dtype=emit2.dtype, device=codes.device, memory_format=torch.channels_last)
-
-    def small(t):
-        return None if t is None else _f32c(t.detach() if hasattr(t, "detach") else t, codes).reshape(-1)
-
-    def vec(t):
-        t = _f32c(t.detach(), codes).reshape(-1)
-        return t.expand(k).contiguous() if t.numel() == 1 else t
-    zx, qs, qz, q2s, q2z = small(in_zp), small(emit.scale), small(emit.zero_point), small(emit2.scale), small(emit2.zero_point)
-    ws, wo, si = vec(pw["w_scale"]), (None if pw.get("w_offset") is None else vec(pw["w_offset"])), small(pw["in_scale"])
-    b = None if pw["bias"] is None else pw["bias"].detach().contiguous()
+    q1 = _quantiser(emit, lambda dtype: None, codes, False, "conv2d_dwpw_i8")      # (the depthwise layer's codes stay in LDS)
+    q2 = _quantiser(emit2, lambda dtype: torch.empty((n, k, h, w_), dtype=dtype, device=codes.device, memory_format=torch.channels_last),
+                    codes, False, "conv2d_dwpw_i8")
+    zx, b = _flat(in_zp, codes), _bias_c(pw["bias"])
+    scales = (_flat(pw["in_scale"], codes), _flat(pw["w_scale"], codes, k), _flat(pw.get("w_offset"), codes, k))
     m = n * h * w_
     nbytes = codes.numel() + table.numel() * 4 + pw["wq"].numel() + m * k
     PROFILE.launch("conv_dwpw", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_dwpw_i8_nhwc(
         N.ptr(codes), N.ptr(table), int(bool(dw_asym)), int(bool(dw_bias)), int(bool(dw_relu)), N.ptr(zx), n, h, w_, c,
-        int(codes.dtype == torch.uint8), N.ptr(qs), N.ptr(qz), emit.lo, emit.hi, emit.form, emit.g, N.ptr(pw["wq"]), N.ptr(b),
-        N.ptr(pw["wsum"]), N.ptr(si), N.ptr(ws), N.ptr(wo), k, int(bool(relu)), N.ptr(out), N.ptr(q2s), N.ptr(q2z), emit2.lo, emit2.hi,
-        emit2.form, emit2.g, N.stream_ptr())), 2 * m * c * (9 + k))
-    return out
+        int(codes.dtype == torch.uint8), *_q_args(q1)[1:], N.ptr(pw["wq"]), N.ptr(b), N.ptr(pw["wsum"]), *map(N.ptr, scales), k,
+        int(bool(relu)), *_q_args(q2), N.stream_ptr())), 2 * m * c * (9 + k))
+    return q2[0]
 
 
 def conv2d_i8_dual(a, b, relu=False, emit=None, want_out=True, force_tiled=False, out_chunk_major=False):
     """conv(a) + conv(b) in one kernel (dlmcq_conv2d_i8_nhwc_dual).  `a`, `b`: dicts with codes, wq, wsum, bias,
-    in_scale, in_zp, w_scale and optional stride / padding / dilation; both must produce the same output shape.
+    in_scale, in_zp, w_scale and optional stride / padding / dilation (`_operand`); both must produce the same output shape.
     Returns fp32 (N, K, P, Q) channels_last, or `(out, codes)` with `emit` (see conv2d_i8; `force_tiled`, `out_chunk_major` as there)."""
-    def prep(t):
-        c = t["codes"]
-        N.require_gpu(c, t["wq"])
-        if c.dim() != 4:
+    for t in (a, b):
+        if t["codes"].dim() != 4:
             raise ValueError("conv2d_i8_dual takes 4-D activation codes")
-        if not c.is_contiguous(memory_format=torch.channels_last):
-            c = c.contiguous(memory_format=torch.channels_last)
-        n, ch, h, w_ = c.shape
-        K_, R, S, _ = t["wq"].shape
-        st, pd, dl = int(t.get("stride", 1)), int(t.get("padding", 0)), int(t.get("dilation", 1))
-        P, Q = (h + 2 * pd - dl * (R - 1) - 1) // st + 1, (w_ + 2 * pd - dl * (S - 1) - 1) // st + 1
-        ws = _f32c(t["w_scale"].detach(), c).reshape(-1)
-        if ws.numel() == 1:
-            ws = ws.expand(K_).contiguous()
-        keep = (c, ws, _f32c(t["in_scale"].detach(), c).reshape(-1), None if t["in_zp"] is None else _f32c(t["in_zp"], c).reshape(-1),
-                None if t["bias"] is None else t["bias"].detach().contiguous())
-        return keep, (n, K_, P, Q), (h, w_, ch, R, S, st, pd, dl, int(c.dtype == torch.uint8))
-    (ca, wsa, sia, zpa, ba), shape_a, ga = prep(a)
-    (cb, wsb, sib, zpb, bb), shape_b, gb = prep(b)
-    if shape_a != shape_b:
-        raise ValueError(f"conv2d_i8_dual: the two convolutions give {shape_a} and {shape_b}")
+    oa, ob = _operand(a), _operand(b)
+    if oa.shape != ob.shape:
+        raise ValueError(f"conv2d_i8_dual: the two convolutions give {oa.shape} and {ob.shape}")
     if not want_out and emit is None:
         raise ValueError("conv2d_i8_dual: nothing to produce (want_out=False without emit)")
-    n, K_, P, Q = shape_a
+    shape = oa.shape
+    n, K_ = shape[:2]
 
     def alloc(dtype):
-        return torch.empty(shape_a, dtype=dtype, device=ca.device, memory_format=torch.channels_last)
+        return torch.empty(shape, dtype=dtype, device=oa.codes.device, memory_format=torch.channels_last)
     out = alloc(torch.float32) if want_out else None
-    out_codes = q_scale = q_zp = None
-    lo = hi = form = 0
-    g = 0.0
-    if emit is not None:
-        out_codes = alloc(emit.dtype)
-        q_scale = _f32c(emit.scale.detach(), ca).reshape(-1)
-        q_zp = None if emit.zero_point is None else _f32c(emit.zero_point, ca).reshape(-1)
-        lo, hi, form, g = emit.lo, emit.hi, emit.form_arg, emit.g
-    h, w_, ch, R, S, st, pd, dl, uns = ga
-    h2, w2, ch2, R2, S2, st2, pd2, dl2, uns2 = gb
-    oe = n * K_ * P * Q
+    q = _quantiser(emit, alloc, oa.codes, True, "conv2d_i8_dual")
+    h, w_, ch, R, S, st, pd, dl, uns = oa.geom
+    _, _, ch2, R2, S2, st2, _, _, _ = ob.geom
+    oe = math.prod(shape)
     def touched(c, r, s_, stride):     # a strided 1x1 convolution reads only the pixels it samples
         return c.numel() // (stride * stride) if r == 1 and s_ == 1 else c.numel()
-    nbytes = touched(ca, R, S, st) + touched(cb, R2, S2, st2) + a["wq"].numel() + b["wq"].numel() + oe * (4 * want_out + (emit is not None))
-    form |= N.FORCE_TILED if force_tiled else 0
+    nbytes = touched(oa.codes, R, S, st) + touched(ob.codes, R2, S2, st2) + a["wq"].numel() + b["wq"].numel() + oe * (4 * want_out + (emit is not None))
+    args = (*_head(oa, out), n, h, w_, ch, K_, R, S, st, pd, dl, uns, *ob.ptrs, *ob.geom, int(bool(relu)))
+    flags = N.FORCE_TILED if force_tiled else 0
 
     def call(extra=0):
-        return N.lib.dlmcq_conv2d_i8_nhwc_dual(
-            N.ptr(ca), N.ptr(a["wq"]), N.ptr(out), N.ptr(ba), N.ptr(a["wsum"]), N.ptr(sia), N.ptr(zpa), N.ptr(wsa),
-            n, h, w_, ch, K_, R, S, st, pd, dl, uns,
-            N.ptr(cb), N.ptr(b["wq"]), N.ptr(bb), N.ptr(b["wsum"]), N.ptr(sib), N.ptr(zpb), N.ptr(wsb), h2, w2, ch2, R2, S2, st2, pd2, dl2,
-            uns2, int(bool(relu)), N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | extra, g, N.stream_ptr())
+        return N.lib.dlmcq_conv2d_i8_nhwc_dual(*args, *_q_args(q, flags | extra), N.stream_ptr())
     # (the profile tag from the library's own dispatch: conv_pwr = csrc/conv_pwr_i8.hip's dual form, conv_i8 = the tiled dual kernel)
     ocm = bool(out_chunk_major) and out is not None and N.route(call(N.ROUTE_ONLY)) == N.ROUTE_PWR
     tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_i8"
     PROFILE.launch(tag, nbytes, lambda: N.check(call(N.FP32_OUT_CHUNK_MAJOR if ocm else 0)), 2 * oe * (ch * R * S + ch2 * R2 * S2))
-    if ocm:         # (the same memory, read as [K / 64][M][64])
-        out = ChunkMajor(out.permute(0, 2, 3, 1).reshape(K_ // 64, n * P * Q, 64), shape_a)
-    return (out, out_codes) if emit is not None else out
+    if ocm:
+        out = _as_chunk_major(out)
+    return (out, q[0]) if emit is not None else out
 
 
 CHAIN_SHAPES = {(64, 64), (64, 128), (128, 128), (128, 256), (256, 256)}   # (C, K2) pairs dlmcq_conv2d_i8_nhwc_chain is built for
@@ -840,54 +824,39 @@ def conv2d_i8_chain(a, b, residual, relu=True, emit=None, want_out=True, want_co
     input quantiser is `emit`).  Returns (out or None, codes or None, codes2).  `residual` may be a ChunkMajor; `out_chunk_major`
     asks for the fp32 output as one (the 128 -> K -> 128 instantiation keeps both fp32 tensors of a call in ONE layout: there a
     residual in the other layout is converted first - a copy; plans avoid it)."""
-    _no_shift(emit, "conv2d_i8_chain")
     c = a["codes"]
     icm, ocm = isinstance(residual, ChunkMajor), bool(out_chunk_major) and want_out
     if want_out and icm != ocm and (c.shape[1], b["wq"].shape[0]) in CHAIN_ONE_LAYOUT:
         residual = residual.to_nhwc() if icm else ChunkMajor.from_nhwc(residual)
         icm = ocm
     res_cm, residual = (residual, residual.buf) if icm else (None, residual)
-    N.require_gpu(c, a["wq"], b["wq"], residual)
-    if not c.is_contiguous(memory_format=torch.channels_last):
-        c = c.contiguous(memory_format=torch.channels_last)
-    n, ch, h, w_ = c.shape
-    K_, R, S, _ = a["wq"].shape
+    N.require_gpu(b["wq"], residual)
+    o = _operand(a)
+    c = o.codes
+    (n, K_), (h, w_, ch, R, S, _, _, _, uns) = o.shape[:2], o.geom
     K2, R2, S2, C2 = b["wq"].shape
     if (R, S, R2, S2) != (1, 1, 1, 1) or C2 != K_ or emit is None or emit2 is None:
         raise ValueError("conv2d_i8_chain: two 1x1 convolutions, the second reading the first's codes")
     if tuple(res_cm.shape if icm else residual.shape) != (n, K_, h, w_) or residual.dtype != torch.float32:
         raise ValueError("conv2d_i8_chain: residual must be fp32 of the first output's shape")
-    if not icm and not residual.is_contiguous(memory_format=torch.channels_last):
-        residual = residual.contiguous(memory_format=torch.channels_last)
+    if not icm:
+        residual = _nhwc(residual)
     m = n * h * w_
 
     def alloc(k, dtype):
         return torch.empty((n, k, h, w_), dtype=dtype, device=c.device, memory_format=torch.channels_last)
     out = (ChunkMajor.empty(n, K_, h, w_, c.device) if ocm else alloc(K_, torch.float32)) if want_out else None
-    out_t = out.buf if ocm else out
-    codes = alloc(K_, emit.dtype) if want_codes else None
-    codes2 = alloc(K2, emit2.dtype)
-
-    def vec(t, k):
-        t = _f32c(t.detach(), c).reshape(-1)
-        return t.expand(k).contiguous() if t.numel() == 1 else t
-    ws1, ws2 = vec(a["w_scale"], K_), vec(b["w_scale"], K2)
-    si = _f32c(a["in_scale"].detach(), c).reshape(-1)
-    zp = None if a["in_zp"] is None else _f32c(a["in_zp"], c).reshape(-1)
-    b1 = None if a["bias"] is None else a["bias"].detach().contiguous()
-    b2 = None if b["bias"] is None else b["bias"].detach().contiguous()
-    qs, qz = _f32c(emit.scale.detach(), c).reshape(-1), None if emit.zero_point is None else _f32c(emit.zero_point, c).reshape(-1)
-    qs2, qz2 = _f32c(emit2.scale.detach(), c).reshape(-1), None if emit2.zero_point is None else _f32c(emit2.zero_point, c).reshape(-1)
+    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, c, False, "conv2d_i8_chain")
+    q2 = _quantiser(emit2, lambda dtype: alloc(K2, dtype), c, True, "conv2d_i8_chain")
+    b2, ws2 = _bias_c(b["bias"]), _flat(b["w_scale"], c, K2)
     nbytes = c.numel() + a["wq"].numel() + b["wq"].numel() + m * K_ * (4 + 4 * want_out + want_codes) + m * K2
     w2t, w2flag = _second_weights(b)
+    flags = w2flag | (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
     PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_chain(
-        N.ptr(c), N.ptr(a["wq"]), N.ptr(out_t), N.ptr(b1), N.ptr(a["wsum"]), N.ptr(si), N.ptr(zp), N.ptr(ws1), m, ch, K_,
-        int(c.dtype == torch.uint8), N.ptr(residual), int(bool(relu)), N.ptr(codes), N.ptr(qs), N.ptr(qz), emit.lo, emit.hi,
-        emit.form, emit.g, N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2, int(bool(relu2)), N.ptr(codes2),
-        N.ptr(qs2), N.ptr(qz2), emit2.lo, emit2.hi, emit2.form_arg | w2flag | (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0), emit2.g,
-        int(rows_per_tile), N.stream_ptr())),
+        *_head(o, out.buf if ocm else out), m, ch, K_, uns, N.ptr(residual), int(bool(relu)), *_q_args(q),
+        N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2, int(bool(relu2)), *_q_args(q2, flags), int(rows_per_tile), N.stream_ptr())),
         2 * m * K_ * (ch + K2))
-    return out, codes, codes2
+    return out, q[0], q2[0]
 
 
 DUAL_CHAIN_SHAPES = {(64, 64, 64), (128, 256, 128)}   # (C, C2, K3) triples dlmcq_conv2d_i8_nhwc_dual_chain is built for
@@ -902,55 +871,32 @@ def conv2d_i8_dual_chain(a, b, c3, relu=True, emit=None, want_out=True, want_cod
     """conv1x1(a) + conv1x1(b, strided) (+ ReLU, the consumer's quantiser `emit`) and the next 1x1 convolution `c3` on the
     codes, in one kernel (dlmcq_conv2d_i8_nhwc_dual_chain).  `a`, `b`: operand dicts as for conv2d_i8_dual (`b` may carry a
     stride); `c3`: wq, wsum, bias, w_scale.  Returns (out or None, codes or None, codes3)."""
-    _no_shift(emit, "conv2d_i8_dual_chain")
-    ca, cb = a["codes"], b["codes"]
-    N.require_gpu(ca, cb, a["wq"], b["wq"], c3["wq"])
-    if not ca.is_contiguous(memory_format=torch.channels_last):
-        ca = ca.contiguous(memory_format=torch.channels_last)
-    if not cb.is_contiguous(memory_format=torch.channels_last):
-        cb = cb.contiguous(memory_format=torch.channels_last)
-    n, ch, h, w_ = ca.shape
-    _, ch2, h2, w2 = cb.shape
-    K_, K3 = a["wq"].shape[0], c3["wq"].shape[0]
-    st2 = int(b.get("stride", 1))
-    if (tuple(a["wq"].shape[1:3]), tuple(b["wq"].shape[1:3]), tuple(c3["wq"].shape[1:3])) != ((1, 1),) * 3 or int(a.get("stride", 1)) != 1 \
-            or int(a.get("padding", 0)) or int(b.get("padding", 0)) or b["wq"].shape[0] != K_ or c3["wq"].shape[3] != K_ or emit is None \
-            or emit3 is None:
+    N.require_gpu(c3["wq"])
+    oa, ob = _operand(a), _operand(b)
+    (n, K_), (h, w_, ch, _, _, st, pd, _, uns) = oa.shape[:2], oa.geom
+    h2, w2, ch2, _, _, st2, pd2, _, uns2 = ob.geom
+    K3 = c3["wq"].shape[0]
+    if (tuple(a["wq"].shape[1:3]), tuple(b["wq"].shape[1:3]), tuple(c3["wq"].shape[1:3])) != ((1, 1),) * 3 or st != 1 or pd or pd2 \
+            or b["wq"].shape[0] != K_ or c3["wq"].shape[3] != K_ or emit is None or emit3 is None:
         raise ValueError("conv2d_i8_dual_chain: three unpadded 1x1 convolutions, the third reading the codes of the sum of the first two")
 
     def alloc(k, dtype):
-        return torch.empty((n, k, h, w_), dtype=dtype, device=ca.device, memory_format=torch.channels_last)
+        return torch.empty((n, k, h, w_), dtype=dtype, device=oa.codes.device, memory_format=torch.channels_last)
     fcm = bool(out_chunk_major) and want_out
-    out = (ChunkMajor.empty(n, K_, h, w_, ca.device) if fcm else alloc(K_, torch.float32)) if want_out else None
-    out_t = out.buf if fcm else out
-    codes = alloc(K_, emit.dtype) if want_codes else None
-    codes3 = alloc(K3, emit3.dtype)
-
-    def vec(t, k):
-        t = _f32c(t.detach(), ca).reshape(-1)
-        return t.expand(k).contiguous() if t.numel() == 1 else t
-
-    def small(t):
-        return None if t is None else _f32c(t.detach() if hasattr(t, "detach") else t, ca).reshape(-1)
-
-    def bias_of(t):
-        return None if t["bias"] is None else t["bias"].detach().contiguous()
-    wsa, wsb, ws3 = vec(a["w_scale"], K_), vec(b["w_scale"], K_), vec(c3["w_scale"], K3)
-    sia, zpa, sib, zpb = small(a["in_scale"]), small(a["in_zp"]), small(b["in_scale"]), small(b["in_zp"])
-    ba, bb, b3 = bias_of(a), bias_of(b), bias_of(c3)
-    qs, qz, qs3, qz3 = small(emit.scale), small(emit.zero_point), small(emit3.scale), small(emit3.zero_point)
+    out = (ChunkMajor.empty(n, K_, h, w_, oa.codes.device) if fcm else alloc(K_, torch.float32)) if want_out else None
+    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, oa.codes, False, "conv2d_i8_dual_chain")
+    q3 = _quantiser(emit3, lambda dtype: alloc(K3, dtype), oa.codes, True, "conv2d_i8_dual_chain")
+    b3, ws3 = _bias_c(c3["bias"]), _flat(c3["w_scale"], oa.codes, K3)
     m = n * h * w_
-    nbytes = ca.numel() + cb.numel() // (st2 * st2) + a["wq"].numel() + b["wq"].numel() + c3["wq"].numel() + \
+    nbytes = oa.codes.numel() + ob.codes.numel() // (st2 * st2) + a["wq"].numel() + b["wq"].numel() + c3["wq"].numel() + \
         m * K_ * (4 * want_out + want_codes) + m * K3
     w3t, w3flag = _second_weights(c3)
     PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_dual_chain(
-        N.ptr(ca), N.ptr(a["wq"]), N.ptr(out_t), N.ptr(ba), N.ptr(a["wsum"]), N.ptr(sia), N.ptr(zpa), N.ptr(wsa), n, h, w_, ch, K_,
-        int(ca.dtype == torch.uint8), N.ptr(cb), N.ptr(b["wq"]), N.ptr(bb), N.ptr(b["wsum"]), N.ptr(sib), N.ptr(zpb), N.ptr(wsb), h2, w2,
-        ch2, st2, int(cb.dtype == torch.uint8), int(bool(relu)), N.ptr(codes), N.ptr(qs), N.ptr(qz), emit.lo, emit.hi, emit.form, emit.g,
-        N.ptr(w3t), N.ptr(b3), N.ptr(c3["wsum"]), N.ptr(ws3), K3, int(bool(relu3)), N.ptr(codes3), N.ptr(qs3), N.ptr(qz3), emit3.lo,
-        emit3.hi, emit3.form_arg | w3flag | (N.FP32_OUT_CHUNK_MAJOR if fcm else 0), emit3.g, int(rows_per_tile), N.stream_ptr())),
+        *_head(oa, out.buf if fcm else out), n, h, w_, ch, K_, uns, *ob.ptrs, h2, w2, ch2, st2, uns2, int(bool(relu)), *_q_args(q),
+        N.ptr(w3t), N.ptr(b3), N.ptr(c3["wsum"]), N.ptr(ws3), K3, int(bool(relu3)),
+        *_q_args(q3, w3flag | (N.FP32_OUT_CHUNK_MAJOR if fcm else 0)), int(rows_per_tile), N.stream_ptr())),
         2 * m * K_ * (ch + ch2 + K3))
-    return out, codes, codes3
+    return out, q[0], q3[0]
 
 
 def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=False, pad_code0=False):
@@ -998,69 +944,42 @@ def conv2d_i8_stem(xpad, wq, wsum, bias, in_scale, in_zp, w_scale, S, stride=1, 
     channel count `channels`): asymmetric per-channel weights (dlmcq_conv2d_i8_stem_asym; not with `pool`).  `relu` / `act` as in
     conv2d_i8 (the pooling kernel: ReLU only).  `in_offset` / `tap_sums` ([R * S, K]) with `pad` (the buffer's padding, filled with
     code 0: quantize_pad_nhwc4(pad_code0=True)): a float activation offset, as in conv2d_i8 (dlmcq_conv2d_i8_stem_xoff; R = 3 or 7)."""
-    _no_shift(emit, "conv2d_i8_stem")
     if (in_offset is None) != (tap_sums is None) or (in_offset is not None and pool):
         raise ValueError("conv2d_i8_stem: in_offset needs tap_sums and no pool")
     act = _act(relu, act)
     N.require_gpu(xpad, wq)
     n, hp, wp, _ = xpad.shape
     K_, R = wq.shape[0], wq.shape[1]
-    P, Q = (hp - R) // stride + 1, (wp - S) // stride + 1
+    P0, Q0 = P, Q = _out_hw(hp, wp, R, S, stride)       # the convolution's own output: what the operation count is of
     if pool:
         if K_ > 64:
             raise ValueError("conv2d_i8_stem(pool=True) handles at most 64 output channels")
-        P, Q = (P + 2 - 3) // 2 + 1, (Q + 2 - 3) // 2 + 1
+        P, Q = _out_hw(P, Q, 3, 3, 2, 1)
     if not want_out and emit is None:
         raise ValueError("conv2d_i8_stem: nothing to produce (want_out=False without emit)")
 
     def alloc(dtype):
         return torch.empty((n, K_, P, Q), dtype=dtype, device=xpad.device, memory_format=torch.channels_last)
+    q = _quantiser(emit, alloc, xpad, False, "conv2d_i8_stem")
     out = alloc(torch.float32) if want_out else None
-    w_scale = _f32c(w_scale.detach(), xpad).reshape(-1)
-    if w_scale.numel() == 1:
-        w_scale = w_scale.expand(K_).contiguous()
-    in_scale = _f32c(in_scale.detach(), xpad).reshape(-1)
-    in_zp = None if in_zp is None else _f32c(in_zp, xpad).reshape(-1)
-    bias = None if bias is None else bias.detach().contiguous()
-    out_codes = q_scale = q_zp = None
-    lo = hi = form = 0
-    g = 0.0
-    if emit is not None:
-        out_codes = alloc(emit.dtype)
-        q_scale = _f32c(emit.scale.detach(), xpad).reshape(-1)
-        q_zp = None if emit.zero_point is None else _f32c(emit.zero_point, xpad).reshape(-1)
-        lo, hi, form, g = emit.lo, emit.hi, emit.form, emit.g
-    oe = n * K_ * P * Q
+    bias, in_scale, in_zp, w_scale = _bias_c(bias), _flat(in_scale, xpad), _flat(in_zp, xpad), _flat(w_scale, xpad, K_)
+    w_offset, in_offset, tap_sums = _flat(w_offset, xpad), _flat(in_offset, xpad), _flat(tap_sums, xpad)
+    # the entry point by (in_offset, w_offset, pool), with what it takes beyond the plain one: [w_offset, C] before the geometry, [pad]
+    # inside it, [in_offset, tap_sums] at the end.  (The plain kernels' operation count is of the 3 channels of an image.)
+    w_off, pad_arg, trailer, cin = (N.ptr(w_offset), int(channels)), (), (), int(channels)
     if in_offset is not None:
-        w_offset = None if w_offset is None else _f32c(w_offset.detach(), xpad).reshape(-1)
-        in_offset = _f32c(in_offset, xpad).reshape(-1)
-        tap_sums = _f32c(tap_sums.detach(), xpad).contiguous()
-        PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
-                       lambda: N.check(N.lib.dlmcq_conv2d_i8_stem_xoff(
-                           N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
-                           N.ptr(w_offset), int(channels), n, hp, wp, K_, R, int(S), int(stride), int(pad), int(xpad.dtype == torch.uint8),
-                           act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.ptr(in_offset), N.ptr(tap_sums),
-                           N.stream_ptr())),
-                       2 * n * K_ * P * Q * R * S * int(channels))
-        return (out, out_codes) if emit is not None else out
-    if w_offset is not None:
+        fn, pad_arg, trailer = N.lib.dlmcq_conv2d_i8_stem_xoff, (int(pad),), (N.ptr(in_offset), N.ptr(tap_sums))
+    elif w_offset is not None:
         if pool:
             raise ValueError("conv2d_i8_stem: the pooling kernel has no weight-offset term")
-        w_offset = _f32c(w_offset.detach(), xpad).reshape(-1)
-        PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
-                       lambda: N.check(N.lib.dlmcq_conv2d_i8_stem_asym(
-                           N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
-                           N.ptr(w_offset), int(channels), n, hp, wp, K_, R, int(S), int(stride), int(xpad.dtype == torch.uint8),
-                           act, N.ptr(out_codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.stream_ptr())),
-                       2 * n * K_ * ((hp - R) // stride + 1) * ((wp - S) // stride + 1) * R * S * int(channels))
-        return (out, out_codes) if emit is not None else out
-    PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
-                   lambda: N.check((N.lib.dlmcq_conv2d_i8_stem_pool_fused if pool else N.lib.dlmcq_conv2d_i8_stem_fused)(
-                       N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale),
-                       n, hp, wp, K_, R, int(S), int(stride), int(xpad.dtype == torch.uint8), act, N.ptr(out_codes),
-                       N.ptr(q_scale), N.ptr(q_zp), lo, hi, form, g, N.stream_ptr())),
-                   2 * n * K_ * ((hp - R) // stride + 1) * ((wp - S) // stride + 1) * R * S * 3)
-    return (out, out_codes) if emit is not None else out
+        fn = N.lib.dlmcq_conv2d_i8_stem_asym
+    else:
+        fn, w_off, cin = (N.lib.dlmcq_conv2d_i8_stem_pool_fused if pool else N.lib.dlmcq_conv2d_i8_stem_fused), (), 3
+    args = (N.ptr(xpad), N.ptr(wq), N.ptr(out), N.ptr(bias), N.ptr(wsum), N.ptr(in_scale), N.ptr(in_zp), N.ptr(w_scale), *w_off,
+            n, hp, wp, K_, R, int(S), int(stride), *pad_arg, int(xpad.dtype == torch.uint8), act, *_q_args(q), *trailer)
+    PROFILE.launch("conv_stem", xpad.numel() + wq.numel() + n * K_ * P * Q * (4 * want_out + (emit is not None)),
+                   lambda: N.check(fn(*args, N.stream_ptr())), 2 * n * K_ * P0 * Q0 * R * S * cin)
+    return (out, q[0]) if emit is not None else out
 
 
 def maxpool_codes(codes, kernel, stride, padding):

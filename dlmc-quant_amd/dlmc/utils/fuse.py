@@ -357,9 +357,9 @@ class Int8Layer(_PlanLayer):
         r, s = lay.weight.shape[2], lay.weight.shape[3]
         return (codes.shape[2] + 2 * pd - dl * (r - 1) - 1) // st + 1, (codes.shape[3] + 2 * pd - dl * (s - 1) - 1) // st + 1
 
-    def operand(self, x):
-        """This layer as one addend of conv2d_i8_dual."""
-        codes = self._codes(x)
+    def operand(self, x, codes=None):
+        """This layer as an operand dict of the kernel wrappers (conv2d_i8_dual / _chain / _dual_chain); `codes`: _codes(x), when made already."""
+        codes = self._codes(x) if codes is None else codes
         return dict(codes=codes, wq=self.wq, wsum=self.wsum, bias=self._bias(), in_scale=self._in_scale(self._real_numel(codes)),
                     in_zp=self._zp(codes), w_scale=self.w_scale, **self._conv_kw())
 
@@ -476,9 +476,7 @@ class ChainInt8Layer(nn.Module):
                     y = y.to_nhwc()
                 out, mid = a(x, y)
                 return out, (mid if self.want_codes else None), b(mid)[1]
-            oa = dict(codes=codes, wq=a.wq, wsum=a.wsum, bias=a._bias(), in_scale=a._in_scale(a._real_numel(codes)), in_zp=a._zp(codes),
-                      w_scale=a.w_scale)
-            return K.conv2d_i8_chain(oa, nxt, y, relu2=b.relu, **kw)
+            return K.conv2d_i8_chain(a.operand(x, codes), nxt, y, relu2=b.relu, **kw)
         if not K.dual_chain_supported(c, sc.c, a.k, b.k, n * h * w):
             out, mid = DualInt8Layer(a, sc if mn is a else mn)(*((x, y) if mn is a else (y, x)))
             return out, (mid if self.want_codes else None), b(mid)[1]      # (row-major: every reader takes that)

@@ -325,3 +325,33 @@ def test_chunk_major_block_tensor_round_trip_on_the_host():
         K.ChunkMajor.from_nhwc(torch.zeros(1, 96, 2, 2))          # K % 64 != 0
     with pytest.raises(ValueError):
         K.ChunkMajor.from_nhwc(torch.zeros(1, 64, 2, 2, dtype=torch.float16))
+
+
+def test_wrapper_marshalling_helpers_on_the_host():
+    """The pure helpers the int8 convolution wrappers marshal their operands with (kernels._flat, _out_hw, _as_chunk_major)."""
+    import torch.nn.functional as F
+    from dlmc.quantization.scalar import kernels as K
+    like = torch.zeros(1)
+    assert K._flat(None, like) is None and K._flat(None, like, 5) is None
+    one = K._flat(0.25, like)
+    assert one.dtype == torch.float32 and tuple(one.shape) == (1,) and float(one) == 0.25
+    wide = K._flat(torch.tensor([[1.5]]), like, 5)
+    assert tuple(wide.shape) == (5,) and wide.is_contiguous() and wide.stride() == (1,) and bool((wide == 1.5).all())
+    assert tuple(K._flat(torch.tensor(1.5), like).shape) == (1,)                       # 0-d -> [1]; not broadcast without k
+    five = torch.arange(5, dtype=torch.float32)
+    for got in (K._flat(five, like), K._flat(five, like, 5), K._flat(five.reshape(1, 5, 1, 1), like, 5)):
+        assert got.data_ptr() == five.data_ptr() and tuple(got.shape) == (5,)       # no copy
+    assert torch.equal(K._flat(torch.arange(5, dtype=torch.float64), like, 5), five)  # other dtypes are converted
+    for k in (None, 5):                                                                 # requires_grad does not leak
+        assert not K._flat(torch.ones(1, requires_grad=True), like, k).requires_grad
+        assert not K._flat(torch.ones(5, requires_grad=True), like, k).requires_grad
+    for h, w, r, s, stride, pad, dil in ((5, 5, 3, 3, 1, 1, 1), (7, 9, 1, 1, 1, 0, 1), (10, 10, 1, 1, 2, 0, 1), (24, 24, 7, 7, 2, 0, 1),
+                                         (9, 8, 3, 3, 2, 1, 1), (11, 13, 3, 3, 1, 2, 2), (12, 7, 3, 5, 3, 2, 2), (3, 3, 3, 3, 1, 0, 1)):
+        want = F.conv2d(torch.zeros(1, 1, h, w), torch.zeros(1, 1, r, s), stride=stride, padding=pad, dilation=dil).shape[2:]
+        assert K._out_hw(h, w, r, s, stride, pad, dil) == tuple(want), (h, w, r, s, stride, pad, dil)
+    assert K._out_hw(9, 9, 3, 3, 2, 1) == tuple(F.max_pool2d(torch.zeros(1, 1, 9, 9), 3, 2, 1).shape[2:])
+    # a channels_last tensor whose MEMORY holds chunk-major planes, re-read as the ChunkMajor it is
+    t = torch.randn(2, 128, 3, 5, generator=torch.Generator().manual_seed(5)).contiguous(memory_format=torch.channels_last)
+    cm = K._as_chunk_major(t)
+    assert cm.shape == (2, 128, 3, 5) and tuple(cm.buf.shape) == (2, 30, 64) and cm.buf.data_ptr() == t.data_ptr()
+    assert torch.equal(cm.buf.reshape(-1), t.permute(0, 2, 3, 1).reshape(-1))
