@@ -33,9 +33,9 @@ FP32_IN_CHUNK_MAJOR = 0x2000   # DLMCQ_FP32_IN_CHUNK_MAJOR: a chain call's fp32 
 FP32_OUT_CHUNK_MAJOR = 0x4000  # DLMCQ_FP32_OUT_CHUNK_MAJOR: ... and / or its fp32 block output
 PAD_CODE0 = 0x8000       # DLMCQ_PAD_CODE0: quantize_pad_nhwc4's border holds code 0 (a float-offset quantiser's padding)
 PIPELINED = 0x1000       # DLMCQ_PIPELINED (opt-in): the persistent, software-pipelined halo-tile 3x3 kernel where it applies
-ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE = 1, 2, 3, 4, 5, 6, 7
+ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE, ROUTE_GAP = 1, 2, 3, 4, 5, 6, 7, 8
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
-             ROUTE_DWM: "conv_dwm", ROUTE_HALO3X3_PIPE: "conv3x3_pipe"}     # the profile tag (bench.py's kernel families) of each route
+             ROUTE_DWM: "conv_dwm", ROUTE_HALO3X3_PIPE: "conv3x3_pipe", ROUTE_GAP: "conv_gap"}     # the profile tag (bench.py's kernel families) of each route
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2   # DLMCQ_ACT_*: the `relu` argument of the fused convolution entry points
 Y_DEQUANT, Y_CODES = 0, 1
 CODES_NONE, CODES_I8, CODES_P4 = 0, 1, 2
@@ -118,6 +118,9 @@ SIGNATURES = {
     "dlmcq_conv2d_i8_stem_pool_fused": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
                                                       _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_maxpool_codes_nhwc": (ctypes.c_int, [_p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _p]),
+    "dlmcq_gap_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_conv2d_i8_nhwc_gap": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p,
+                                               _i32, _i32, _i32, _f32, _p]),
     "dlmcq_fold_bn_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p]),
     "dlmcq_repvgg_fuse_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _f32, _f32, _f32, _i64, _i64, _p]),
 }

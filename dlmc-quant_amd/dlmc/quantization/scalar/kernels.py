@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "pack_int4", "unpack_int4", "fake_quant_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -994,6 +994,85 @@ def maxpool_codes(codes, kernel, stride, padding):
         N.ptr(codes), N.ptr(y), n, h, w, c, int(kernel), int(stride), int(padding), int(codes.dtype == torch.uint8),
         N.stream_ptr())))
     return y
+
+
+GAP_HEAD_MAX_HW, GAP_HEAD_MAX_C = 64, 2048    # dlmcq_conv2d_i8_nhwc_gap: the image fits one 64-row tile, the slice's weights stay in LDS (DLMCQ_GAP_MAX_C)
+
+
+def gap_head_supported(c, k, h, w, ksize=1, stride=1, padding=0, asym=False):
+    """Whether dlmcq_conv2d_i8_nhwc_gap takes a layer of c -> k channels (ksize x ksize, stride, padding; `asym`: per-channel weight
+    offsets) on an h x w map followed by a global average pool."""
+    return (ksize == 1 and stride == 1 and padding == 0 and not asym and c >= 64 and c % 64 == 0 and c <= GAP_HEAD_MAX_C and k >= 64 and
+            k % 64 == 0 and h >= 1 and w >= 1 and h * w <= GAP_HEAD_MAX_HW)
+
+
+# (C, K) of the layers on which the fused head was MEASURED slower than the layer's ordinary launch + the pool kernel (7 x 7 maps, batch
+# 512 / 1024: ResNet-50 233 against 98 + 35 us, MobileNetV2 178 against 92 + 45, MobileOne-S1 213 against 105 + 41; DESIGN.md 5.14,
+# profiles/gap_head_ab.json).  fuse_inference(gap_head=True) runs these as two launches; the kernel stays reachable through
+# conv2d_i8_gap and gap_head="fused"
+GAP_HEAD_MEASURED_SLOWER = {(512, 2048), (320, 1280), (512, 1280)}
+
+
+def gap_head_profitable(c, k):
+    """Whether fuse_inference(gap_head=True) routes a gap_head_supported layer of c -> k channels to the fused head: not where it was
+    measured slower than the two launches it replaces (GAP_HEAD_MEASURED_SLOWER)."""
+    return (c, k) not in GAP_HEAD_MEASURED_SLOWER
+
+
+def global_avgpool(x, emit=None, want_out=True):
+    """Global average pool of an fp32 (N, C, H, W) map in channels_last memory (copied when it is not), C % 4 == 0, by
+    dlmcq_gap_nhwc_f32: a sequential fp32 sum over the pixels in row order and a true division (include/dlmcq.h: NOT torch.mean's
+    summation order).  Returns fp32 (N, C); with `emit=EmitCodes(...)` `(pooled, codes)` - the consumer's activation codes (N, C) of
+    the pooled values - `pooled` being None when `want_out=False`."""
+    N.require_gpu(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("global_avgpool: an fp32 (N, C, H, W) tensor")
+    if not want_out and emit is None:
+        raise ValueError("global_avgpool: nothing to produce (want_out=False without emit)")
+    x = _nhwc(x)
+    n, c, h, w_ = x.shape
+
+    def alloc(dtype):
+        return torch.empty((n, c), dtype=dtype, device=x.device)
+    out = alloc(torch.float32) if want_out else None
+    q = _quantiser(emit, alloc, x, True, "global_avgpool")
+    PROFILE.launch("gap", x.numel() * 4 + n * c * (4 * want_out + (emit is not None)), lambda: N.check(N.lib.dlmcq_gap_nhwc_f32(
+        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h * w_, c, *_q_args(q)[1:], N.stream_ptr())))
+    return (out, q[0]) if emit is not None else out
+
+
+def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):
+    """A 1 x 1 / stride 1 / unpadded int8 convolution (+ fp32 `residual` of its output's shape) (+ `act`: N.ACT_NONE / ACT_RELU /
+    ACT_RELU6) and the global average pool of the result in ONE launch (dlmcq_conv2d_i8_nhwc_gap): the (N, K, H, W) map is never
+    written.  Operands as conv2d_i8 takes them (codes (N, C, H, W), wq [K, 1, 1, C]); `gap_head_supported` says which shapes the
+    kernel is built for.  Returns fp32 (N, K) - conv2d_i8(..., want_out=True) followed by global_avgpool, bit for bit - or
+    `(pooled or None, codes)` with `emit`."""
+    o = _operand(dict(codes=codes, wq=wq, wsum=wsum, bias=bias, in_scale=in_scale, in_zp=in_zp, w_scale=w_scale))
+    codes = o.codes
+    if codes.dim() != 4 or tuple(wq.shape[1:3]) != (1, 1):
+        raise ValueError("conv2d_i8_gap: 4-D activation codes and a 1 x 1 layer [K, 1, 1, C]")
+    if not want_out and emit is None:
+        raise ValueError("conv2d_i8_gap: nothing to produce (want_out=False without emit)")
+    (n, K_), (h, w_, c, _, _, _, _, _, uns) = o.shape[:2], o.geom
+    if residual is not None:
+        if tuple(residual.shape) != tuple(o.shape) or residual.dtype != torch.float32:
+            raise ValueError("conv2d_i8_gap: residual must be fp32 of the convolution output's shape")
+        N.require_gpu(residual)
+        residual = _nhwc(residual)
+
+    def alloc(dtype):
+        return torch.empty((n, K_), dtype=dtype, device=codes.device)
+    out = alloc(torch.float32) if want_out else None
+    q = _quantiser(emit, alloc, codes, True, "conv2d_i8_gap")
+    m = n * h * w_
+    nbytes = codes.numel() + wq.numel() + m * K_ * 4 * (residual is not None) + n * K_ * (4 * want_out + (emit is not None))
+
+    def call(extra=0):
+        return N.lib.dlmcq_conv2d_i8_nhwc_gap(*_head(o, out), n, h, w_, c, K_, uns, N.ptr(residual), _act(False, act), *_q_args(q, extra),
+                                              N.stream_ptr())
+    tag = N.ROUTE_TAG[N.route(call(N.ROUTE_ONLY))] if PROFILE.enabled else "conv_gap"
+    PROFILE.launch(tag, nbytes, lambda: N.check(call()), 2 * m * K_ * c)
+    return (out, q[0]) if emit is not None else out
 
 
 def pack_int4(codes):

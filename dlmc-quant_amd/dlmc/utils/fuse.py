@@ -32,7 +32,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -714,6 +714,195 @@ def _block_layout_pass(gm, report):
     report.chunk_major = count
 
 
+class GapLayer(nn.Module):
+    """Global average pool of an fp32 map (csrc/gap.hip) straight to the classifier's activation codes [N, C] (and / or fp32): the
+    pool, the flatten and the consumer's quantise pass as one read of the map.  Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, emit, want_out):
+        super().__init__()
+        self.emit, self.want_out = emit, bool(want_out)
+
+    def forward(self, x):
+        n, c = x.shape[0], x.shape[1]
+        return K.global_avgpool(x, emit=self.emit.emit(n * c), want_out=self.want_out)
+
+
+class GapHeadLayer(nn.Module):
+    """The network's head as ONE kernel (csrc/conv_gap_i8.hip): the last 1x1 convolution (+ fp32 shortcut) (+ ReLU / ReLU6), pooled
+    over its <= 64 pixels into the classifier's codes - its fp32 map is never written.  `a`: the convolution's plan node (it carries
+    the activation); maps the kernel is not built for (more than 64 pixels) run the plan node and the pool kernel one after the other.
+    Returns `(fp32 [N, K] or None, codes [N, K])` - the same bits either way."""
+
+    def __init__(self, a, emit, want_out):
+        super().__init__()
+        self.a, self.emit, self.want_out = a, emit, bool(want_out)
+
+    def forward(self, x, residual=None):
+        a = self.a
+        codes = a._codes(x)
+        n, c, h, w = codes.shape
+        emit = self.emit.emit(n * a.k)
+        if not K.gap_head_supported(c, a.k, h, w):
+            return K.global_avgpool(a(codes, residual)[0], emit=emit, want_out=self.want_out)
+        return K.conv2d_i8_gap(codes, a.wq, a.wsum, a._bias(), a._in_scale(a._real_numel(codes)), a._zp(codes), a.w_scale,
+                               residual=residual, act=a._act_arg(), emit=emit, want_out=self.want_out)
+
+
+def _pool_dims(node, modules):
+    """Rank of the result (4: keeps [N, C, 1, 1]; 2: [N, C]) if `node` is a global average pool in a spelling the plan folds -
+    nn.AdaptiveAvgPool2d(1 | (1, 1)), F.adaptive_avg_pool2d(x, 1 | (1, 1)), x.mean((2, 3)) / torch.mean(x, (2, 3)) / [2, 3] / dim=,
+    keepdim either way - else None."""
+    one = lambda v: v == 1 or (isinstance(v, (tuple, list)) and tuple(v) == (1, 1))  # noqa: E731
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        return 4 if type(m) is nn.AdaptiveAvgPool2d and one(m.output_size) and len(node.args) == 1 and not node.kwargs else None
+    if node.op == "call_function" and node.target is F.adaptive_avg_pool2d:
+        given = dict(zip(("input", "output_size"), node.args), **node.kwargs)
+        return 4 if set(given) == {"input", "output_size"} and isinstance(given["input"], fx.Node) and one(given["output_size"]) else None
+    if (node.op == "call_method" and node.target == "mean") or (node.op == "call_function" and node.target is torch.mean):
+        given = dict(zip(("input", "dim", "keepdim"), node.args), **node.kwargs)
+        if not set(given) <= {"input", "dim", "keepdim"} or not isinstance(given.get("input"), fx.Node):
+            return None
+        dim, keep = given.get("dim"), given.get("keepdim", False)
+        if not (isinstance(dim, (tuple, list)) and sorted(dim) in ([2, 3], [-2, -1]) and isinstance(keep, bool)):
+            return None
+        return 4 if keep else 2
+    return None
+
+
+def _batch_size_of(node):
+    """Whether `node` is `t.size(0)` / `t.shape[0]` of some tensor `t` (the first argument of a `.view(N, -1)`)."""
+    if not isinstance(node, fx.Node):
+        return False
+    if node.op == "call_method" and node.target == "size":
+        return len(node.args) == 2 and node.args[1] == 0 and not node.kwargs
+    if node.op == "call_function" and node.target is operator.getitem and node.args[1] == 0:
+        src = node.args[0]
+        return (isinstance(src, fx.Node) and ((src.op == "call_function" and src.target is getattr and src.args[1] == "shape") or
+                                              (src.op == "call_method" and src.target == "size" and len(src.args) == 1)))
+    return False
+
+
+def _flatten_rank(node, src, rank):
+    """Rank after `node` if it is one of the reshapes that follow a global pool - torch.flatten(x, 1) / x.flatten(1), x.view(N, -1) /
+    x.reshape(N, -1) with N = t.size(0) / t.shape[0] (not an int literal), x.squeeze() / x.squeeze(d) over a pooled axis - applied to `src`; else None."""
+    fn, meth = node.op == "call_function", node.op == "call_method"
+    if not (fn or meth) or not node.args or node.args[0] is not src:
+        return None
+    if (fn and node.target is torch.flatten) or (meth and node.target == "flatten"):
+        given = dict(zip(("input", "start_dim", "end_dim"), node.args), **node.kwargs)
+        return 2 if given.get("start_dim") == 1 and given.get("end_dim", -1) in (-1, rank - 1) and set(given) <= {"input", "start_dim", "end_dim"} else None
+    if meth and node.target in ("view", "reshape") and not node.kwargs:
+        shape = node.args[1:]
+        if len(shape) == 1 and isinstance(shape[0], (tuple, list)):
+            shape = tuple(shape[0])
+        return 2 if len(shape) == 2 and shape[1] == -1 and _batch_size_of(shape[0]) else None     # (an int literal is [N, C] only at that batch size)
+    if (fn and node.target is torch.squeeze) or (meth and node.target == "squeeze"):
+        given = dict(zip(("input", "dim"), node.args), **node.kwargs)
+        if set(given) == {"input"}:
+            return 2
+        d = given.get("dim")
+        if set(given) != {"input", "dim"} or not isinstance(d, int) or isinstance(d, bool):
+            return None
+        d = d if d >= 0 else rank + d
+        return rank - 1 if 2 <= d < rank else None
+    return None
+
+
+def _gap_pass(gm, report, mode, planned, dry_run):
+    """Global-average-pool heads (fuse_inference(gap_head=...)): `pool -> flatten -> quantised Linear` becomes a node that hands the
+    Linear its activation codes [N, C].  `planned`: plan node -> what the main pass decided for it."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+
+    def aux(n, inside):      # a batch-size read (x.size(0), x.shape[0] and their pieces) used by the chain's nodes only
+        if not ((n.op == "call_method" and n.target == "size") or (n.op == "call_function" and n.target in (getattr, operator.getitem))):
+            return False
+        return bool(n.users) and all(u in inside or aux(u, inside) for u in n.users)
+
+    def real_users(n, inside):
+        return [u for u in n.users if not aux(u, inside)]
+
+    for pool in list(graph.nodes):
+        rank = _pool_dims(pool, modules)
+        if rank is None:
+            continue
+        x = pool.args[0] if pool.args else pool.kwargs["input"]
+        # ---- pool -> reshapes -> [N, C], each link the only reader of the one before ----
+        chain, last = [pool], pool
+        while True:
+            nxt = [u for u in last.users if _flatten_rank(u, last, rank) is not None]
+            if len(nxt) != 1 or len(real_users(last, set(chain) | set(nxt))) != 1:
+                break
+            rank = _flatten_rank(nxt[0], last, rank)
+            chain.append(nxt[0])
+            last = nxt[0]
+        if rank != 2:
+            continue
+        inside = set(chain)
+        if any(real_users(n, inside) != [c] for n, c in zip(chain[:-1], chain[1:])):
+            continue
+        # ---- the readers: plan-eligible linear layers, through their activation argument, take codes ----
+        def linear_act(u):
+            info = planned.get(u)
+            if info is None or info["dual"] or info["kind"] != "gemm" or u.args[0] is not last or last in u.args[1:]:
+                return None
+            w = info["mod"].weight
+            return info["spec"][0] if w.dim() == 2 and w.shape[1] % 64 == 0 else None
+        users = real_users(last, inside)
+        acts = {u: linear_act(u) for u in users}
+        keys = [a.key for a in acts.values() if a is not None]
+        if not keys:
+            continue
+        key = max(set(keys), key=keys.count)
+        takers = [u for u, a in acts.items() if a is not None and a.key == key]
+        emit = acts[takers[0]]
+        want_out = len(takers) != len(users)
+        # ---- the producer: a plan convolution read by the pool alone becomes the fused head (True: where profitable; "fused": always) ----
+        prod = x.args[0] if x.op == "call_function" and x.target is operator.getitem and x.args[1] == 0 else None
+        info = planned.get(prod)
+        fused = False
+        if mode in (True, "fused") and info is not None and real_users(x, inside) == [pool]:
+            w = info["mod"].weight
+            gets = [u for u in prod.users if u.op == "call_function" and u.target is operator.getitem]
+            fused = (info["kind"] == "gemm" and not info["dual"] and info["pool"] is None and info["emit"] is None and w.dim() == 4 and
+                     len(gets) == len(prod.users) and all(g is x or not real_users(g, inside) for g in gets) and info["spec"][5] is None and
+                     K.gap_head_supported(_ceil64(w.shape[1]), w.shape[0], 1, 1, w.shape[2], info["mod"].stride[0], info["mod"].padding[0]) and
+                     w.shape[2] == w.shape[3] and (mode == "fused" or K.gap_head_profitable(_ceil64(w.shape[1]), w.shape[0])))
+        name = f"_int8_gap_{count}"
+        count += 1
+        if dry_run:
+            gm.add_module(name, _DryNode())
+        elif fused:
+            gm.add_module(name, GapHeadLayer(modules[prod.target], emit, want_out))
+        else:
+            gm.add_module(name, GapLayer(emit, want_out))
+        with graph.inserting_after(last):
+            node = graph.call_module(name, args=tuple(prod.args) if fused else (x,))
+        with graph.inserting_after(node):
+            out = graph.call_function(operator.getitem, (node, 0))
+            codes = graph.call_function(operator.getitem, (node, 1))
+        for u in users:
+            u.replace_input_with(last, codes if u in takers else out)
+        def erase_tree(n):     # `n` and what hangs on it: by now the chain's reshapes and their batch-size reads only
+            for u in list(n.users):
+                erase_tree(u)
+            if n in live:
+                live.discard(n)
+                graph.erase_node(n)
+        live = set(graph.nodes)
+        erase_tree(pool)
+        if fused:
+            erase_tree(prod)
+            report.fp32_outputs -= 1
+        report.gap_heads.append((name, "fused" if fused else "separate"))
+    if count:
+        graph.eliminate_dead_code()
+        graph.lint()
+        gm.recompile()
+
+
 class StemLayer(_PlanLayer):
     """The network's first convolution (<= 4 input channels) of the frozen plan: the image is quantised into a
     zero-point-padded NHWC4 code buffer and convolved on the matrix cores (csrc/conv_stem_i8.hip)."""
@@ -773,13 +962,14 @@ class FusionReport:
         self.chunk_major = 0  # fp32 block outputs kept chunk-major between two kernels that walk them chunk by chunk (_block_layout_pass)
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
         self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
+        self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
     def __repr__(self):
         return (f"FusionReport(int8 layers={self.layers}, relu fused={self.relu}, relu6 fused={self.relu6}, residual fused={self.residual}, "
                 f"code-emitting={self.emit}, fp32 outputs kept={self.fp32_outputs}, stem layers={self.stem}, "
                 f"pools on codes={self.pooled}, dual (conv + shortcut conv) kernels={self.dual}, chained pairs={self.chained} (fp32 outputs chunk-major: {self.chunk_major}), "
-                f"depthwise + pointwise units={self.dwpw}, "
+                f"depthwise + pointwise units={self.dwpw}, " + (f"gap heads={self.gap_heads}, " if self.gap_heads else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1047,7 +1237,7 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True, act_offsets=False):
+                   relu6=True, act_offsets=False, gap_head=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1068,7 +1258,24 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     `act_offsets=True` also plans QBase layers whose activation quantiser has a per-tensor FLOAT offset (x^ = q * s^ + o: the
     unsigned min/max quantiser of any tensor that can go negative - shortcut sums, normalised images): producers emit their codes
     with that offset, the offset times the weight sums goes into the bias, and padded layers run the border term of the *_xoff
-    entry points.  Off by default: the plan without it is the plan as it was."""
+    entry points.  Off by default: the plan without it is the plan as it was.
+    `gap_head`: the tail `global average pool -> flatten -> quantised Linear` on the plan.  The pool
+    (nn.AdaptiveAvgPool2d(1), F.adaptive_avg_pool2d(x, 1), x.mean((2, 3)) / torch.mean, keepdim either way) and the reshape behind it
+    (flatten(1), view / reshape(x.size(0), -1), squeeze) become one node that hands a plan-eligible Linear its activation codes [N, C].
+    True: where the pool's producer is a 1x1 / stride 1 plan convolution (+ shortcut, ReLU / ReLU6) read by nothing else, the kernel
+    is built for it (K.gap_head_supported) AND it was not measured slower there (K.gap_head_profitable), the two run as ONE kernel that
+    never writes the fp32 map (csrc/conv_gap_i8.hip); else the pool kernel (csrc/gap.hip) follows the producer's ordinary launch.  On
+    the last layers of ResNet-50, MobileNetV2 and MobileOne-S1 the fused head is slower than those two launches at batch 512 / 1024
+    (DESIGN.md 5.14), so True runs them as two.  "separate": always the pool kernel; "fused": the fused head wherever it is built,
+    profitable or not (both: A/B and tests).  All settings agree bit for bit.  The pooled sum is sequential fp32 in pixel order - not
+    torch.mean's order - so against the plan WITHOUT heads a pooled value can differ in its last bit, which now and then flips a
+    pooled activation code by one; the classifier amplifies such a flip (ResNet-50 b512: logits differ by up to 1.6 where they reach 3.7e3).
+    A pool whose reader is not plan-eligible (RootQ, a disabled quantiser, a non-integer zero point, in-features % 64 != 0), any other
+    output size, and F.avg_pool2d(x, x.size(3)) (a kernel size read from the tensor) are left as they are.  One spelling is folded
+    although it differs from the model at batch 1: a bare x.squeeze() gives [C] there, the plan's node [1, C].  Off by default: the
+    plan without it is the plan as it was."""
+    if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
+        raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
         raise RuntimeError("fuse_inference: the plan is for inference - call model.eval() first")
     report = report if report is not None else FusionReport()
@@ -1108,6 +1315,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         return s[0] if s is not None and s[4] in ("gemm", "dw") else None
 
     count = 0
+    planned = {}       # plan node -> what was decided for it (the gap-head pass reads it; under dry_run the modules are placeholders)
     live = set(graph.nodes)
     for node in list(graph.nodes):
         if node not in live:            # absorbed into a dual kernel earlier in this loop
@@ -1210,6 +1418,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             args = (node.args[0],) if residual is None else (node.args[0], residual)
         with graph.inserting_after(last):
             fused = graph.call_module(name, args=args)
+        planned[fused] = dict(spec=spec, kind=spec[4], mod=modules[node.target], dual=bool(dual), pool=pool, emit=emit)
         if dual:
             dual_inputs[fused] = (spec[0], other[0])
             chain.insert(0, residual)       # erased last (its only user, the add, goes first)
@@ -1240,6 +1449,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     graph.eliminate_dead_code()
     graph.lint()
     gm.recompile()
+    if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
+        _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and not dry_run:
         _chain_pass(gm, report)
         if block_layout:

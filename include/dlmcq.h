@@ -119,6 +119,7 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
 #define DLMCQ_ROUTE_DW 5      /* conv_dw_i8_kernel / conv_dw3_i8_kernel / conv_dw3p2_i8_kernel (csrc/conv_dw_i8.hip) */
 #define DLMCQ_ROUTE_DWM 6     /* conv_dwm_i8_kernel (csrc/conv_dwm_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3_PIPE 7 /* conv3x3_pipe_i8_kernel (csrc/conv3x3_pipe_i8.hip) */
+#define DLMCQ_ROUTE_GAP 8     /* conv_gap_i8_kernel (csrc/conv_gap_i8.hip): the answer of dlmcq_conv2d_i8_nhwc_gap */
 
 /* ---- the activation of a fused epilogue: the `relu` / `relu2` / `relu3` / `dw_relu` arguments of the convolution entry points ----
  * DLMCQ_ACT_RELU6 is  v = v < 0 ? 0 : (v > 6 ? 6 : v)  (torch.nn.functional.relu6; NaN stays NaN, -0 stays -0), applied in fp32
@@ -645,6 +646,34 @@ int dlmcq_conv2d_i8_stem_xoff(const void* xpad, const int8_t* w, float* out, con
                               int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
                               const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                               const float* in_offset, const float* tap_sums, dlmcq_stream_t stream);
+
+/* ---- global-average-pool heads: the pooled output as fp32 and / or the classifier's activation codes ----
+ * One arithmetic for both entry points.  For image n and channel k, over the HW pixels p = 0 .. HW - 1 in NHWC row order:
+ *     s = v[n,0,k];  for p = 1 .. HW - 1: s = fl32(s + v[n,p,k]);  pooled[n,k] = fl32(s / fl32(HW))  (true IEEE division)
+ *     code[n,k] = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused; DLMCQ_EMIT_SHIFT128 accepted) of pooled[n,k] -
+ *                 the code dlmcq_fake_quant_f32 gives for it
+ * A sequential fp32 sum, no atomics: the result depends neither on the launch geometry nor on the run.  (torch.mean sums in another
+ * order: equal to it only within HW * 2^-24 * mean|v|.)  `pooled` (fp32 [N, C]) and `codes` ([N, C] bytes) are optional, at least one
+ * is required; `codes` needs q_scale.
+ *
+ * dlmcq_gap_nhwc_f32: x fp32 [N, HW, C] row-major NHWC (16-byte aligned), C % 4 == 0, HW >= 1.  One read of the map, no scratch.
+ * Every control / layout bit in q_form (a chunk-major input, DLMCQ_ROUTE_ONLY, ...) is DLMCQ_EINVAL.
+ *
+ * dlmcq_conv2d_i8_nhwc_gap: v is the output of the 1 x 1 / stride 1 / unpadded convolution of dlmcq_conv2d_i8_nhwc_fused (same
+ * operands: codes x [N, H, W, C], weights [K, C], symmetric; in_zero_point as there - also the `zp - 128` of shifted codes passed as
+ * signed; a float activation offset is folded into `bias` by the caller, an unpadded layer has no border term) + `residual` (fp32
+ * [N, H, W, K] row-major or NULL) + `act` (DLMCQ_ACT_NONE / RELU / RELU6), bit for bit the value that call stores - but the
+ * [N, H, W, K] map is never written: one launch produces pooled / codes.  Supported: C % 64 == 0, C <= DLMCQ_GAP_MAX_C (the slice's
+ * weights stay in LDS), K % 64 == 0, H * W <= 64; anything else DLMCQ_EINVAL.  DLMCQ_ROUTE_ONLY in q_form: validates, launches
+ * nothing, returns DLMCQ_ROUTE_GAP; every other control / layout bit is DLMCQ_EINVAL (refused, not stripped). */
+#define DLMCQ_GAP_MAX_C 2048
+int dlmcq_gap_nhwc_f32(const float* x, float* pooled, void* codes, int64_t N, int64_t HW, int64_t C, const float* q_scale,
+                       const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+int dlmcq_conv2d_i8_nhwc_gap(const void* x, const int8_t* w, float* pooled, const float* bias, const int32_t* wsum,
+                             const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N, int64_t H,
+                             int64_t W, int64_t C, int64_t K, int32_t x_is_unsigned, const float* residual, int32_t act,
+                             void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                             int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
 #ifdef __cplusplus
 }

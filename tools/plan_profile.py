@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Per-layer timing of the fused plan (HIP events around every plan node).  python tools/plan_profile.py [model] [batch] [qbase] [act_offsets]
+"""Per-layer timing of the fused plan (HIP events around every plan node).
+python tools/plan_profile.py [model] [batch] [qbase] [act_offsets] [gap_head | gap_separate | gap_fused] [zp0]
 (model mobileone_s1 is profiled as BASELINE config 5: QBase W4A8, asymmetric per-channel weights; `qbase` profiles any other model under that
-quantiser too, `act_offsets` builds the plan with fuse_inference(act_offsets=True))"""
+quantiser too, `act_offsets` builds the plan with fuse_inference(act_offsets=True), `gap_head` / `gap_separate` / `gap_fused` with gap_head=True / "separate" / "fused" -
+FSPTQ's zero points are then set to 0 after calibration, as tools/gap_head_ab.py does, so that the classifier is a plan node; `zp0` does
+the same without a gap flag: the plan those are to be compared with)"""
 import json
 import os
 import sys
@@ -12,7 +15,7 @@ import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
 from bench import QCFG  # noqa: E402
-from dlmc.utils.fuse import ChainInt8Layer, DualInt8Layer, DwPwInt8Layer, _PlanLayer as Int8Layer, fuse_inference  # noqa: E402
+from dlmc.utils.fuse import ChainInt8Layer, DualInt8Layer, DwPwInt8Layer, GapHeadLayer, GapLayer, _PlanLayer as Int8Layer, fuse_inference  # noqa: E402
 from dlmc.utils.merge_bn import merge_bn  # noqa: E402
 from dlmc.utils.quantize import quantize_model  # noqa: E402
 
@@ -22,6 +25,8 @@ dev = "cuda:0"
 torch.manual_seed(2333)
 qbase = name == "mobileone_s1" or "qbase" in sys.argv[3:]
 act_offsets = "act_offsets" in sys.argv[3:]
+gap_head = True if "gap_head" in sys.argv[3:] else next((v for v in ("separate", "fused") if "gap_" + v in sys.argv[3:]), False)
+zp0 = bool(gap_head) or "zp0" in sys.argv[3:]
 if qbase:
     model = W.MODELS[name]().to(dev).eval()
     if name != "mobileone_s1":
@@ -37,7 +42,12 @@ else:
 recs = []
 with torch.no_grad():
     model(x)
-    plan = fuse_inference(model, act_offsets=act_offsets)
+    if zp0 and not qbase:
+        for m in model.modules():
+            if hasattr(m, "_zp_is_int"):
+                m.in_offset.zero_()
+                m._zp_is_int = None
+    plan = fuse_inference(model, act_offsets=act_offsets, gap_head=gap_head)
     for _ in range(2):
         plan(x)
 
@@ -59,8 +69,11 @@ with torch.no_grad():
     for p_ in plan.modules():
         if isinstance(p_, DwPwInt8Layer):
             inner |= {id(p_.dw), id(p_.pw)}
+    for p_ in plan.modules():
+        if isinstance(p_, GapHeadLayer):
+            inner.add(id(p_.a))
     for m in plan.modules():
-        if isinstance(m, (DualInt8Layer, ChainInt8Layer, DwPwInt8Layer)) or (isinstance(m, Int8Layer) and id(m) not in inner):
+        if isinstance(m, (DualInt8Layer, ChainInt8Layer, DwPwInt8Layer, GapHeadLayer, GapLayer)) or (isinstance(m, Int8Layer) and id(m) not in inner):
             m.register_forward_pre_hook(pre)
             m.register_forward_hook(post)
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -73,6 +86,20 @@ tot = 0.0
 for mod, args, out, s, e in recs:
     us = s.elapsed_time(e) * 1e3
     tot += us
+    if isinstance(mod, (GapHeadLayer, GapLayer)):      # algorithmic bytes: the map (or the head's codes, weights and shortcut) in, [N, K] out
+        xin, o = args[0], out[1]
+        nb = o.numel() * (1 + 4 * (out[0] is not None))
+        if isinstance(mod, GapLayer):
+            nb += xin.numel() * 4
+            print(f"{us:8.1f} us  GAP  in {str(tuple(xin.shape)):22s} float32  -> {str(tuple(o.shape)):14s} {'out ' if out[0] is not None else '    '}codes  "
+                  f"{nb / us / 1e3:6.0f} GB/s")
+        else:
+            w = mod.a.layer.weight
+            macs = xin.numel() // xin.shape[1] * w.numel()
+            nb += xin.numel() + w.numel() + (args[1].numel() * 4 if len(args) > 1 else 0)
+            print(f"{us:8.1f} us  GAPHEAD in {str(tuple(xin.shape)):20s} x {str(tuple(w.shape)):18s} {'res ' if len(args) > 1 else '    '}"
+                  f"-> {str(tuple(o.shape)):14s} {'out ' if out[0] is not None else '    '}codes  {2 * macs / us / 1e6:6.0f} TOP/s {nb / us / 1e3:6.0f} GB/s")
+        continue
     if isinstance(mod, DwPwInt8Layer):
         xin, o = args[0], out[1]
         wd, wp = mod.dw.layer.weight, mod.pw.layer.weight
