@@ -15,21 +15,9 @@
 //   * streaming (non-temporal) stores: the output is not re-read by this kernel.
 // Bit-exactness: true IEEE division, rintf (half-to-even), the reference's own operation order and its
 // STE identities (ste_round / ste_scale), no FMA contraction (-ffp-contract=off), fp32 denormals kept.
-#include "dlmcq_internal.h"
+#include "fq_bodies.h"   // fq4 (shared with fake_quant_multi.hip)
 
 namespace dlmcq {
-
-// Four elements sharing one channel.
-template <int FORM>
-__device__ __forceinline__ void fq4(const f32x4& v, const ChanConst<FORM>& c, float lo, float hi, f32x4& q, f32x4& y) {
-  float q0, q1, q2, q3, y0, y1, y2, y3;
-  fq_one<FORM>(v.x, c, lo, hi, q0, y0);
-  fq_one<FORM>(v.y, c, lo, hi, q1, y1);
-  fq_one<FORM>(v.z, c, lo, hi, q2, y2);
-  fq_one<FORM>(v.w, c, lo, hi, q3, y3);
-  q = f32x4{q0, q1, q2, q3};
-  y = f32x4{y0, y1, y2, y3};
-}
 
 struct FqOut {
   float* y;
@@ -54,8 +42,6 @@ __device__ __forceinline__ void store4(const FqOut& o, int64_t gidx, const f32x4
     __builtin_nontemporal_store(w, reinterpret_cast<uint16_t*>(o.codes + (gidx >> 1)));
   }
 }
-
-constexpr int FQ_BLOCK = DLMCQ_WAVE;  // one-wave workgroups (see the header comment)
 
 // ------------------------------------------------------------------ per-tensor, 128-bit path
 // Grid-stride over chunks of 256*U float4.  n4 = numel/4; the 0-3 tail elements are finished by

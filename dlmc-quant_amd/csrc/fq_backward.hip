@@ -6,74 +6,9 @@
 // modules/function.py:37-49); with v = (x - o)/s^ and inside = [lo <= v <= hi]:
 //   gx    = inside ? (gy * s^) / s^ : +0          (two roundings - identical to autograd's mul, div)
 //   gs[c] = g * sum( gy*(q - inside*v) ),               q = ste_round(clamp(v))      (= LSQ's closed form)
-#include "dlmcq_internal.h"
+#include "fq_bodies.h"   // BwdConst, bwd_one and the per-workgroup bodies (shared with fake_quant_multi.hip)
 
 namespace dlmcq {
-
-struct BwdConst {
-  float sh;  // the divisor: s^ (QBASE) or s
-  float of;  // QBASE: the offset subtracted before the division;  ZEROPOINT: the zero point added after the rounding;
-             // ROOTQ_ACT: the upper clip s*(hi - lo)
-  float span;  // ROOTQ_ACT: hi - lo
-  int form;
-  __device__ __forceinline__ BwdConst(float s, float o, float g, int f, float lo, float hi)
-      : sh(f == DLMCQ_FORM_QBASE ? ste_scale(s, g) : s),
-        of(f == DLMCQ_FORM_SYMMETRIC ? 0.0f : (f == DLMCQ_FORM_ROOTQ_ACT ? s * (hi - lo) : o)), span(hi - lo), form(f) {}
-};
-
-// QBASE:      v = (x - o)/s^,  inside = [lo <= v <= hi],              q = R(clamp(v)),  gs += gy*(q - inside*v)
-// ZEROPOINT:  u = x/s, a = R(u) + zp, inside = [lo <= a <= hi], t = clamp(a) - zp,       gs += gy*(t - inside*u)
-// SYMMETRIC:  ZEROPOINT with zp = 0     (FSPTQuant/base.py:108-109, 149-152 as autograd runs them: the rounding is a
-//             straight-through identity, torch.clamp passes the gradient on the closed interval, x/s gives gx = g/s)
-// gx = inside ? (gy*s)/s : +0 in all three - the two roundings autograd performs.
-__device__ __forceinline__ void bwd_one(float x, float gy, const BwdConst& c, float lo, float hi, float& gx,
-                                        float& contrib) {
-  float v, q;
-  bool inside;
-  if (c.form == DLMCQ_FORM_ROOTQ_ACT) {
-    // RootQ/base.py:106-111 + function.py:15-20 as autograd runs them: t1 = x + relu(0 - x), t = t1 - relu(t1 - up),
-    // u = t/s, y = R(u)*s.  A clipped element passes no gradient to x (gt - gt = +0); the scale collects gy*R(u) from the
-    // product, -gy*u from the division and, through up = s*(hi - lo), gy*(hi - lo) from every element clipped above.
-    const float t1 = x + relu_nan(0.0f - x);
-    const bool below = (0.0f - x) > 0.0f, above = (t1 - c.of) > 0.0f;
-    const float t = t1 - relu_nan(t1 - c.of);
-    v = t / c.sh;
-    q = ste_round(v);
-    const float gv = (below || above) ? 0.0f : gy * c.sh;
-    gx = gv / c.sh;
-    contrib = gy * (q - v) + (above ? gy * c.span : 0.0f);
-    return;
-  }
-  if (c.form == DLMCQ_FORM_QBASE) {
-    v = (x - c.of) / c.sh;
-    q = ste_round(clamp_nan(v, lo, hi));
-    inside = (v >= lo) && (v <= hi);
-  } else {
-    v = x / c.sh;
-    const float a = ste_round(v) + c.of;
-    inside = (a >= lo) && (a <= hi);
-    q = clamp_nan(a, lo, hi) - c.of;
-  }
-  const float gv = inside ? gy * c.sh : 0.0f;
-  gx = gv / c.sh;                               // bit-exact with autograd's mul-then-div
-  // autograd accumulates gy*q and -gv*(v/s) separately; gv*(v/s) == gy*v up to rounding and the scale
-  // gradient is an order-dependent sum anyway, so the third division is not spent: gy*(q - [inside]*v)
-  contrib = gy * (q - (inside ? v : 0.0f));
-}
-
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int off = DLMCQ_WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, DLMCQ_WAVE);
-  return s;
-}
-
-__device__ __forceinline__ float block_sum(float s) {
-  __shared__ float part[DLMCQ_BLOCK / DLMCQ_WAVE];
-  s = wave_sum(s);
-  if ((threadIdx.x & (DLMCQ_WAVE - 1)) == 0) part[threadIdx.x / DLMCQ_WAVE] = s;
-  __syncthreads();
-  return part[0] + part[1] + part[2] + part[3];
-}
 
 // Per tensor.  VEC: all pointers 16-byte aligned.
 template <int U, bool VEC>
@@ -87,41 +22,9 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void fq_bwd_tensor_kernel(const float*
   if (VEC) {
     const int64_t n4 = n >> 2;
     const int64_t nchunks = (n4 + DLMCQ_BLOCK * U - 1) / (DLMCQ_BLOCK * U);
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(gy);
-    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-      const int64_t i0 = chunk * (DLMCQ_BLOCK * U) + threadIdx.x;
-      f32x4 xv[U], gv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = i0 + u * DLMCQ_BLOCK;
-        if (i < n4) {
-          xv[u] = __builtin_nontemporal_load(x4 + i);
-          gv[u] = __builtin_nontemporal_load(g4 + i);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t i = i0 + u * DLMCQ_BLOCK;
-        if (i < n4) {
-          float o0, o1, o2, o3, e0, e1, e2, e3;
-          bwd_one(xv[u].x, gv[u].x, c, lo, hi, o0, e0);
-          bwd_one(xv[u].y, gv[u].y, c, lo, hi, o1, e1);
-          bwd_one(xv[u].z, gv[u].z, c, lo, hi, o2, e2);
-          bwd_one(xv[u].w, gv[u].w, c, lo, hi, o3, e3);
-          const f32x4 o = {o0, o1, o2, o3};
-          acc += (e0 + e1) + (e2 + e3);
-          if (gx) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(gx) + i);
-        }
-      }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-      const int64_t i = (n4 << 2) + threadIdx.x;
-      float o, e;
-      bwd_one(x[i], gy[i], c, lo, hi, o, e);
-      acc += e;
-      if (gx) gx[i] = o;
-    }
+    for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x)
+      bwd_tensor_chunk<U>(x, gy, gx, chunk, n4, c, lo, hi, acc);
+    if (blockIdx.x == 0) bwd_tensor_tail(x, gy, gx, n, c, lo, hi, acc);
   } else {
     for (int64_t i = (int64_t)blockIdx.x * DLMCQ_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * DLMCQ_BLOCK) {
       float o, e;
@@ -149,28 +52,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void fq_bwd_rows_kernel(const float* x
   float acc = 0.0f;
   for (int64_t n = n_lo; n < n_hi; ++n) {
     const int64_t base = (n * channels + c) * inner;
-    if (VEC) {
-      const int64_t i4 = inner >> 2;
-      for (int64_t i = threadIdx.x; i < i4; i += DLMCQ_BLOCK) {
-        const f32x4 xv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + base) + i);
-        const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gy + base) + i);
-        float o0, o1, o2, o3, e0, e1, e2, e3;
-        bwd_one(xv.x, gv.x, k, lo, hi, o0, e0);
-        bwd_one(xv.y, gv.y, k, lo, hi, o1, e1);
-        bwd_one(xv.z, gv.z, k, lo, hi, o2, e2);
-        bwd_one(xv.w, gv.w, k, lo, hi, o3, e3);
-        const f32x4 o = {o0, o1, o2, o3};
-        acc += (e0 + e1) + (e2 + e3);
-        if (gx) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(gx + base) + i);
-      }
-    } else {
-      for (int64_t i = threadIdx.x; i < inner; i += DLMCQ_BLOCK) {
-        float o, e;
-        bwd_one(x[base + i], gy[base + i], k, lo, hi, o, e);
-        acc += e;
-        if (gx) gx[base + i] = o;
-      }
-    }
+    bwd_row_walk<VEC>(x, gy, gx, base, inner, k, lo, hi, acc);
   }
   const float s = block_sum(acc);
   if (threadIdx.x == 0) partials[sg * channels + c] = s;
@@ -182,28 +64,15 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void fq_bwd_finalize_kernel(const floa
                                                                      float* __restrict__ gscale) {
   const int64_t c = (int64_t)blockIdx.x * DLMCQ_BLOCK + threadIdx.x;
   if (c >= channels) return;
-  double s = 0.0;
-  for (int64_t k = 0; k < nseg; ++k) s += (double)partials[k * channels + c];
-  gscale[c] = (float)s * g;
+  gscale[c] = fold_channel(partials, nseg, channels, c, g);
 }
 
 // Per tensor: one block folds all workgroup partials (strided fp64 sums, then a tree through LDS).
 __global__ __launch_bounds__(DLMCQ_BLOCK) void fq_bwd_finalize_tensor_kernel(const float* __restrict__ partials, int64_t n,
                                                                             float g, float* __restrict__ gscale) {
-  __shared__ double red[DLMCQ_BLOCK];
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += DLMCQ_BLOCK) s += (double)partials[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = DLMCQ_BLOCK / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) gscale[0] = (float)red[0] * g;
+  const float v = fold_tensor(partials, n, g);
+  if (threadIdx.x == 0) gscale[0] = v;
 }
-
-constexpr int BWD_U = 1;                      // one float4 of x and of gy per lane, one chunk per workgroup
-constexpr int BWD_TENSOR_BLOCKS = 8192;       // persistent grid: one partial sum per workgroup for the finalize to fold
 
 struct BwdPlan {
   int64_t nseg;   // partial rows

@@ -68,6 +68,10 @@ SIGNATURES = {
     "dlmcq_rootq_bwd_scratch_bytes": (ctypes.c_size_t, [_i64]),
     "dlmcq_rootq_weight_bwd_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p, _sz, _p]),
     "dlmcq_fake_quant_bwd_form_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _p, _sz, _p]),
+    "dlmcq_fq_segment_bytes": (_sz, []),
+    "dlmcq_fq_multi_prepare": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p]),
+    "dlmcq_fake_quant_multi_f32": (ctypes.c_int, [_p, _i64, _i64, _p]),
+    "dlmcq_fake_quant_multi_bwd_f32": (ctypes.c_int, [_p, _i64, _i64, _i64, _p, _sz, _p]),
     "dlmcq_rootq_weight_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i32, _p]),
     "dlmcq_l2norm_scratch_bytes": (_sz, [_i64, _i64, _i64]),
     "dlmcq_l2norm_step_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _sz, _p]),
@@ -126,6 +130,16 @@ SIGNATURES = {
 }
 
 
+class FqSegment(ctypes.Structure):
+    """dlmcq_fq_segment of include/dlmcq.h: 17 fields of 8 bytes (checked against dlmcq_fq_segment_bytes() on load)."""
+    _fields_ = [("x", _p), ("y", _p), ("gy", _p), ("gx", _p), ("scale", _p), ("offset", _p), ("gscale", _p),
+                ("n", _i64), ("channels", _i64), ("inner", _i64), ("lo", _i64), ("hi", _i64), ("ste_g", ctypes.c_double),
+                ("form", _i64), ("fwd_chunk0", _i64), ("bwd_wg0", _i64), ("part0", _i64)]
+
+
+FQ_MULTI_MAX_ELEMENTS = 8192 * 1024      # a segment's cap: 8192 backward chunks of 1024 elements (include/dlmcq.h)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -145,6 +159,8 @@ def _load():
                 continue
             raise
         fn.restype, fn.argtypes = res, args
+    if hasattr(lib, "dlmcq_fq_segment_bytes") and lib.dlmcq_fq_segment_bytes() != ctypes.sizeof(FqSegment):
+        raise ImportError(f"{LIB_PATH}: dlmcq_fq_segment is {lib.dlmcq_fq_segment_bytes()} bytes, the ctypes mirror {ctypes.sizeof(FqSegment)}")
     return lib
 
 

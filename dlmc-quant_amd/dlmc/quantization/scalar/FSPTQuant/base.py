@@ -18,7 +18,7 @@ from torch.nn import Module
 from .... import _native as N
 from .. import kernels as K
 from .. import ops
-from .._wrapper import InitState, ZeroPointSpeculation, fake_quant, fusable_epilogue, int8_forward, int8_gemm_default, int8_kind, set_scale
+from .._wrapper import InitState, ZeroPointSpeculation, batched_weight, fake_quant, fusable_epilogue, int8_forward, int8_gemm_default, int8_kind, set_scale
 from ..utils import get_qrange
 
 
@@ -202,6 +202,8 @@ class FSPTQBase(Module):
             raise NotImplementedError("recon_type 'dist_recon' is unfinished in the reference "
                                       "(FSPTQuant/base.py:133,143 call undefined code)")
         else:
-            weight = fake_quant(self.weight, self.wt_scale, None, self.wt_min_val, self.wt_max_val,
-                                N.FORM_SYMMETRIC)
+            weight = batched_weight(self)      # inside a WeightQuantBatch step: this layer's share of the one launch
+            if weight is None:
+                weight = fake_quant(self.weight, self.wt_scale, None, self.wt_min_val, self.wt_max_val,
+                                    N.FORM_SYMMETRIC)
         return self._forward_func(q_input, weight)

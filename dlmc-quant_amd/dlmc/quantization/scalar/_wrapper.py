@@ -97,6 +97,42 @@ class FakeQuantFn(torch.autograd.Function):
         return gx, gs, None, None, None, None, None
 
 
+class MultiFakeQuantFn(torch.autograd.Function):
+    """All of a model's weight quantisers as one node: `apply(plan, *weights, *scales)` -> the fake-quantised weights.
+    Forward: one launch (K.FqMultiPlan.forward).  Backward: one launch plus one finalize; an output nobody used gets zero
+    gradients and no workgroups, and `needs_input_grad` is honoured per tensor, as in FakeQuantFn."""
+
+    @staticmethod
+    def forward(ctx, plan, *tensors):
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*tensors)      # (the plan reads them where they lie; saving them makes autograd check their versions)
+        return tuple(plan.forward())
+
+    @staticmethod
+    def backward(ctx, *gys):
+        plan, n = ctx.plan, ctx.plan.nseg
+        tensors = ctx.saved_tensors
+        need_x, need_s = ctx.needs_input_grad[1:1 + n], ctx.needs_input_grad[1 + n:1 + 2 * n]
+        gxs, gss = plan.backward(list(gys), want_gx=list(need_x), want_gscale=list(need_s))
+        for i in range(n):
+            if need_x[i] and gxs[i] is None:
+                gxs[i] = torch.zeros_like(tensors[i])
+            if need_s[i]:
+                gss[i] = torch.zeros_like(tensors[n + i]) if gss[i] is None else gss[i].reshape(tensors[n + i].shape)
+        return (None, *gxs, *gss)
+
+
+# The weight batch whose step is open (dlmc.utils.quantize.WeightQuantBatch.step), or None: outside a step nothing changes.
+ACTIVE_WEIGHT_BATCH = None
+
+
+def batched_weight(mod):
+    """The fake-quantised weight the open WeightQuantBatch step computed for `mod` in its one launch, or None: no step is
+    open, the layer is not a member, or its weight or scale was written to since that launch."""
+    return None if ACTIVE_WEIGHT_BATCH is None else ACTIVE_WEIGHT_BATCH.take(mod)
+
+
 def fake_quant(x, scale, offset, lo, hi, form, g=0.0):
     """Fake-quantise with autograd when (and only when) something upstream wants gradients."""
     if offset is None:
@@ -305,6 +341,7 @@ class InitState:
 
     def __init__(self):
         self._known = {}
+        self.marks = 0      # bumped by every (re-)calibration or reset: a WeightQuantBatch step notices one that happens inside it
 
     def ready(self, mod, name):
         v = self._known.get(name)
@@ -316,6 +353,7 @@ class InitState:
     def mark(self, mod, name, value=True):
         getattr(mod, name).fill_(1 if value else 0)
         self._known[name] = bool(value)
+        self.marks += 1
 
     def invalidate(self):
         self._known = {}

@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1118,6 +1118,176 @@ def fake_quant_backward(x, gy, scale, offset, lo, hi, g, ch_axis=None, want_gx=T
         N.ptr(x), N.ptr(gy), N.ptr(gx), N.ptr(gs), N.ptr(scale), N.ptr(offset), outer, ch, inner, int(lo), int(hi),
         int(N.FORM_QBASE if form is None else form), float(g), N.ptr(sc), sc.numel() * 4, N.stream_ptr())))
     return gx, gs
+
+
+# ------------------------------------------------------ many tensors, one launch (csrc/fake_quant_multi.hip)
+_MULTI_FORMS = (FORM_QBASE, FORM_ZEROPOINT, FORM_SYMMETRIC)
+
+
+class Segment:
+    """One tensor with its quantiser, as `fake_quant_multi` takes it: per tensor (a one-element scale) or per channel on axis 0.
+    Nothing is copied - the launches read `x` and `scale` where they lie - so `x` must be fp32 and contiguous already."""
+    __slots__ = ("x", "scale", "offset", "lo", "hi", "form", "g", "channels", "inner")
+
+    def __init__(self, x, scale, offset, lo, hi, form, g=0.0):
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("fake_quant_multi: a segment is fp32 and contiguous")
+        if int(form) not in _MULTI_FORMS:
+            raise ValueError("fake_quant_multi: forms QBASE, ZEROPOINT and SYMMETRIC only")
+        scale, offset = _f32c(scale.detach(), x), _f32c(offset, x)
+        outer, ch, inner = geometry(x, scale)
+        if ch > 1 and outer != 1:
+            raise ValueError("fake_quant_multi: per-channel segments have their channel on axis 0")
+        if offset is not None and offset.numel() != scale.numel():
+            if offset.numel() != 1:
+                raise ValueError("offset must have one entry per scale entry")
+            offset = offset.reshape(1).expand(scale.numel()).contiguous()
+        self.x, self.scale, self.offset = x.detach(), scale, None if form == FORM_SYMMETRIC else offset
+        self.lo, self.hi, self.form, self.g = int(lo), int(hi), int(form), float(g)
+        self.channels, self.inner = ch, (inner if ch > 1 else x.numel())
+
+    def fill(self, rec):
+        """The caller's fields of one dlmcq_fq_segment (the pointers of the outputs stay 0)."""
+        rec.x, rec.scale = self.x.data_ptr(), self.scale.data_ptr()
+        rec.offset = 0 if self.offset is None else self.offset.data_ptr()
+        rec.y = rec.gy = rec.gx = rec.gscale = 0
+        rec.n, rec.channels, rec.inner = self.x.numel(), self.channels, self.inner
+        rec.lo, rec.hi, rec.ste_g, rec.form = self.lo, self.hi, self.g, self.form
+
+
+def _prepare(table, nseg):
+    f, b, z, sc = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_size_t(0)
+    rc = N.lib.dlmcq_fq_multi_prepare(ctypes.byref(table), nseg, ctypes.byref(f), ctypes.byref(b), ctypes.byref(z), ctypes.byref(sc))
+    return rc, f.value, b.value, z.value, sc.value
+
+
+def segment_refusal(seg):
+    """None when the library takes `seg` in a segment table, else why not (dlmcq_fq_multi_prepare's verdict; host only)."""
+    table = (N.FqSegment * 1)()
+    seg.fill(table[0])
+    rc = _prepare(table, 1)[0]
+    return None if rc == 0 else N.lib.dlmcq_strerror(rc).decode()
+
+
+def _carve(sizes, device, pad=4):
+    """One fp32 arena and a view of sizes[i] elements per entry, each starting on a 16-byte boundary."""
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += (n + pad - 1) // pad * pad
+    arena = torch.empty(max(total, pad), dtype=torch.float32, device=device)
+    return arena, [arena[o:o + n] for o, n in zip(offs, sizes)]
+
+
+def _aligned(t):
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class FqMultiPlan:
+    """A list of segments as device tables: the forward table is built and uploaded once (weights, scales and the outputs - an
+    arena this object owns unless `out` names them - keep their addresses across steps), the backward's per call (gy and gx are
+    new tensors every step)."""
+
+    def __init__(self, segments, out=None, forward=True):
+        self.segments = list(segments)
+        self.nseg = len(self.segments)
+        N.require_gpu(*[s.x for s in self.segments])
+        self.device = self.segments[0].x.device if self.segments else torch.device("cuda")
+        self.numel = sum(s.x.numel() for s in self.segments)
+        self._host = (N.FqSegment * max(self.nseg, 1))()
+        for s, rec in zip(self.segments, self._host):
+            s.fill(rec)
+        self.arena, self.ys, self._fwd_table, self._bwd_table, self.fwd_workgroups = None, None, None, None, 0
+        if not forward:
+            return
+        if out is None:
+            self.arena, flat = _carve([s.x.numel() for s in self.segments], self.device)
+            self.ys = [y.view(s.x.shape) for y, s in zip(flat, self.segments)]
+        else:
+            self.ys = list(out)
+            for y, s in zip(self.ys, self.segments):
+                if not (y.dtype == torch.float32 and y.shape == s.x.shape and y.is_contiguous() and y.device == s.x.device):
+                    raise ValueError("out must hold contiguous fp32 tensors of the segments' shapes")
+        for y, rec in zip(self.ys, self._host):
+            rec.y = y.data_ptr()
+        rc, self.fwd_workgroups = _prepare(self._host, self.nseg)[:2]
+        N.check(rc)
+        self._fwd_table = self._upload(self._host)
+
+    def _upload(self, table):
+        """The table on the device, through a pinned staging buffer: a copy from pageable memory would make the host wait for
+        everything queued on the stream - in the middle of a backward pass.  (The pinned allocator keeps the buffer until the
+        copy has run.)"""
+        host = torch.empty(ctypes.sizeof(table) // 8, dtype=torch.int64, pin_memory=True)
+        ctypes.memmove(host.data_ptr(), table, ctypes.sizeof(table))
+        return host.to(self.device, non_blocking=True)
+
+    def forward(self):
+        """One launch; returns the outputs (the same storage every call)."""
+        if self.arena is not None:
+            torch.autograd.graph.increment_version(self.arena)   # a graph that still holds last step's outputs must say so
+        if self.fwd_workgroups:
+            PROFILE.launch("fq_multi", 8 * self.numel, lambda: N.check(N.lib.dlmcq_fake_quant_multi_f32(
+                N.ptr(self._fwd_table), self.nseg, self.fwd_workgroups, N.stream_ptr())))
+        return [y.detach() for y in self.ys]
+
+    def backward(self, gys, want_gx=True, want_gscale=True, gx_out=None, gscale_out=None, scratch=None):
+        """One backward launch and one finalize.  `gys[i]` None: segment i takes no part.  Returns (gxs, gscales), with None
+        where nothing was wanted or computed; gscales are [channels]."""
+        wx = list(want_gx) if isinstance(want_gx, (list, tuple)) else [bool(want_gx)] * self.nseg
+        ws = list(want_gscale) if isinstance(want_gscale, (list, tuple)) else [bool(want_gscale)] * self.nseg
+        live = [g is not None and (a or b) for g, a, b in zip(gys, wx, ws)]
+        gys = [_aligned(g) if l else None for g, l in zip(gys, live)]
+        for g, s, l in zip(gys, self.segments, live):
+            if l and (g.dtype != torch.float32 or g.shape != s.x.shape):
+                raise ValueError("fake_quant_multi_backward: gy must be fp32 with the segment's shape")
+        gxs, gss = [None] * self.nseg, [None] * self.nseg
+        if gx_out is None:
+            idx = [i for i in range(self.nseg) if live[i] and wx[i]]
+            flat = _carve([self.segments[i].x.numel() for i in idx], self.device)[1]
+            for i, t in zip(idx, flat):
+                gxs[i] = t.view(self.segments[i].x.shape)
+        else:
+            gxs = [t if (l and w) else None for t, l, w in zip(gx_out, live, wx)]
+        if gscale_out is None:
+            idx = [i for i in range(self.nseg) if live[i] and ws[i]]
+            flat = _carve([self.segments[i].channels for i in idx], self.device, pad=1)[1]
+            for i, t in zip(idx, flat):
+                gss[i] = t
+        else:
+            gss = [t if (l and w) else None for t, l, w in zip(gscale_out, live, ws)]
+        table = (N.FqSegment * max(self.nseg, 1))()
+        ctypes.memmove(table, self._host, ctypes.sizeof(table))
+        nbytes = 0
+        for rec, g, gx, gs, s in zip(table, gys, gxs, gss, self.segments):
+            rec.y = 0
+            rec.gy = 0 if g is None else g.data_ptr()
+            rec.gx = 0 if gx is None else gx.data_ptr()
+            rec.gscale = 0 if gs is None else gs.data_ptr()
+            if g is not None:
+                nbytes += s.x.numel() * (12 if gx is not None else 8)
+        rc, _, bwd, fin, need = _prepare(table, self.nseg)
+        N.check(rc)
+        if bwd or fin:
+            sc = scratch if scratch is not None else _scratch(need, self.device)
+            raw = bytes(table)      # in the steady state the allocator hands out last step's addresses: the same table
+            if self._bwd_table is None or self._bwd_table[0] != raw:
+                self._bwd_table = (raw, self._upload(table))
+            dev = self._bwd_table[1]
+            PROFILE.launch("fq_multi_bwd", nbytes, lambda: N.check(N.lib.dlmcq_fake_quant_multi_bwd_f32(
+                N.ptr(dev), self.nseg, bwd, fin, N.ptr(sc), sc.numel() * 4, N.stream_ptr())))
+        return gxs, gss
+
+
+def fake_quant_multi(segments, out=None):
+    """Fake-quantise every tensor of `segments` in ONE launch; the outputs (dequantised fp32) are the bits of `fake_quant` on each."""
+    return FqMultiPlan(segments, out=out).forward()
+
+
+def fake_quant_multi_backward(segments, gys, want_gx=True, want_gscale=True, gx_out=None, gscale_out=None, scratch=None):
+    """The backward of every segment in one launch plus one finalize: ([gx], [gscale]), the bits of `fake_quant_backward` on each."""
+    return FqMultiPlan(segments, forward=False).backward(gys, want_gx, want_gscale, gx_out, gscale_out, scratch)
 
 
 def rootq_weight(w, upper, lower, lo, hi):

@@ -23,7 +23,7 @@ from torch.nn import Module
 from .... import _native as N
 from .. import kernels as K
 from .. import ops
-from .._wrapper import (InitState, fake_quant, fusable_epilogue, int8_forward, int8_gemm_default, int8_kind, set_scale,
+from .._wrapper import (InitState, batched_weight, fake_quant, fusable_epilogue, int8_forward, int8_gemm_default, int8_kind, set_scale,
                         ste_scale_value)
 from ..utils import get_qrange
 
@@ -173,6 +173,8 @@ class QBase(Module):
             if not self._init.ready(self, "wt_init_state"):
                 self._calibrate_weight(input)
             g_w = 1 / math.sqrt(self.weight.numel() * self.wt_max_val)
-            weight = fake_quant(self.weight, self.wt_scale, self.wt_offset, self.wt_min_val, self.wt_max_val,
-                                N.FORM_QBASE, g_w)
+            weight = batched_weight(self)      # inside a WeightQuantBatch step: this layer's share of the one launch
+            if weight is None:
+                weight = fake_quant(self.weight, self.wt_scale, self.wt_offset, self.wt_min_val, self.wt_max_val,
+                                    N.FORM_QBASE, g_w)
         return self._forward_func(input, weight)

@@ -266,6 +266,68 @@ int dlmcq_fake_quant_bwd_form_f32(const float* x, const float* gy, float* gx, fl
                                   dlmcq_stream_t stream);
 
 /*
+ * ---- fake-quant of MANY weight tensors in one launch, forward and backward (csrc/fake_quant_multi.hip) ----
+ * A segment is one tensor with its quantiser; a device-resident table of segments drives one forward launch
+ * (dlmcq_fake_quant_multi_f32) and one backward launch plus one finalize (dlmcq_fake_quant_multi_bwd_f32).  For every
+ * segment y, gx and gscale are bit-identical to dlmcq_fake_quant_f32 (y_kind = DLMCQ_Y_DEQUANT, no codes) and
+ * dlmcq_fake_quant_bwd_form_f32 on that tensor alone: both families run the same per-workgroup bodies (csrc/fq_bodies.h).
+ *
+ * Layout: 17 fields of 8 bytes, no padding (sizeof = dlmcq_fq_segment_bytes() = 136).  The caller fills the first 14
+ * on the host, dlmcq_fq_multi_prepare fills the last three, and the caller copies the table to the device.
+ *
+ * Eligibility (everything else keeps its own launches):
+ *   - fp32, contiguous; x, y, gy and gx 16-byte aligned (DLMCQ_EALIGN otherwise);
+ *   - form is DLMCQ_FORM_QBASE, DLMCQ_FORM_ZEROPOINT or DLMCQ_FORM_SYMMETRIC (DLMCQ_EINVAL otherwise);
+ *   - per tensor (channels == 1; inner is ignored) or per channel on axis 0 (n == channels * inner, rows of `inner`
+ *     elements; DLMCQ_EINVAL otherwise);
+ *   - at most 8192 backward chunks of 1024 elements, n <= 8 388 608 (DLMCQ_ERANGE otherwise): above that the one-tensor
+ *     backward grid-strides and one chunk per workgroup cannot reproduce its summation order;
+ *   - lo <= hi (DLMCQ_EINVAL), both within int32 (DLMCQ_ERANGE); n, channels >= 0 ... see dlmcq_fq_multi_prepare.
+ */
+typedef struct dlmcq_fq_segment {
+  const float* x;       /* input, n elements */
+  float* y;             /* forward output (dequantised fp32); NULL: the segment takes no part in the forward */
+  const float* gy;      /* backward: gradient of y; NULL (n > 0): the segment takes no part in the backward */
+  float* gx;            /* backward: gradient of x, or NULL (not wanted); may alias gy */
+  const float* scale;   /* [channels] */
+  const float* offset;  /* [channels] or NULL (= 0): QBASE offset / ZEROPOINT zero point; SYMMETRIC ignores it */
+  float* gscale;        /* backward: [channels] gradient of scale, or NULL (not wanted) */
+  int64_t n;            /* elements; 0 is legal: no workgroups (the backward zero-fills gscale, as the one-tensor call does) */
+  int64_t channels;     /* 1: per tensor;  > 1: per channel on axis 0 */
+  int64_t inner;        /* elements per channel row (channels > 1) */
+  int64_t lo, hi;       /* integer code range */
+  double ste_g;         /* DLMCQ_FORM_QBASE only: the `g` of grad_scale (rounded to fp32, as the one-tensor calls take it) */
+  int64_t form;         /* DLMCQ_FORM_QBASE / _ZEROPOINT / _SYMMETRIC */
+  /* filled in by dlmcq_fq_multi_prepare: */
+  int64_t fwd_chunk0;   /* first forward workgroup (one 256-element chunk each) */
+  int64_t bwd_wg0;      /* first backward workgroup (per tensor: one 1024-element chunk each; per channel: one row each) */
+  int64_t part0;        /* first of this segment's fp32 partial sums in the scratch (one per backward workgroup) */
+} dlmcq_fq_segment;
+
+size_t dlmcq_fq_segment_bytes(void);
+/*
+ * Host only (no HIP call): validates every segment of the HOST table `segs` (the codes above; nseg < 0 or a NULL output pointer:
+ * DLMCQ_EINVAL; n > 0 with x or scale NULL: DLMCQ_EINVAL), fills fwd_chunk0 / bwd_wg0 / part0 and returns the grids:
+ *   *fwd_workgroups      sum over segments with y != NULL of max(1, ceil((n / 4) / 64))      (n > 0)
+ *   *bwd_workgroups      sum over segments with gy != NULL and (gx or gscale) of: channels == 1 ? max(1, ceil((n / 4) / 256))
+ *                        : channels                                                          (n > 0)
+ *   *finalize_workgroups nseg when any segment has a gscale, else 0: the finalize is indexed by segment, and the workgroup
+ *                        of a segment with nothing to fold returns at once
+ *   *scratch_bytes       4 bytes per backward workgroup when any segment has a gscale, else 0
+ * Empty segments get no forward or backward workgroups.
+ */
+int dlmcq_fq_multi_prepare(dlmcq_fq_segment* segs, int64_t nseg, int64_t* fwd_workgroups, int64_t* bwd_workgroups,
+                           int64_t* finalize_workgroups, size_t* scratch_bytes);
+/* One launch for every segment with y != NULL.  `table` is the prepared table in DEVICE memory (8-byte aligned). */
+int dlmcq_fake_quant_multi_f32(const dlmcq_fq_segment* table, int64_t nseg, int64_t fwd_workgroups,
+                               dlmcq_stream_t stream);
+/* One backward launch and (finalize_workgroups > 0) one finalize launch.  scratch_bytes below what prepare returned
+ * (or a NULL scratch when it returned more than 0): DLMCQ_ESCRATCH.  Buffers of segments that take no part, and a NULL gx / gscale, are not touched. */
+int dlmcq_fake_quant_multi_bwd_f32(const dlmcq_fq_segment* table, int64_t nseg, int64_t bwd_workgroups,
+                                   int64_t finalize_workgroups, void* scratch, size_t scratch_bytes,
+                                   dlmcq_stream_t stream);
+
+/*
  * RootQ weight forward (RootQ/base.py:146-155 + RootQ/function.py:15-32,58-67), per tensor.
  * `bounds` is a device array {upper, lower}.  The forward value does not depend on alpha (it only
  * shapes the gradient), so alpha is not an input.  y = ((sgn+1)/2 + interval)*delta + lower.

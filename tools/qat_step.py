@@ -2,11 +2,12 @@
 """Training-step time (forward + backward + SGD) of the three wrapper families - the reference's QAT use of the path
 (trainer/quantization_aware_training_trainer.py:51-75: output = model(data); loss.backward(); optimizer.step()).
 
-    python tools/qat_step.py [model] [batch] [--json FILE]
+    python tools/qat_step.py [model] [batch] [--json FILE] [--batched-weights]
 
 Prints ms per step and images/s per family and - round 5 - the fake-quant kernels' own rates inside one more, instrumented step
 (HIP events per launch: forward fq_tensor / fq_channel at 8 algorithmic bytes per element, the one-pass backward `fq_bwd` at 12);
---json writes the whole record (profiles/r05_qat_step_<model>.json)."""
+--json writes the whole record (profiles/r05_qat_step_<model>.json).  --batched-weights runs the QBase and FSPTQ steps under
+dlmc.utils.quantize.WeightQuantBatch: all weight fake-quants as one `fq_multi` launch, all their backward passes as one `fq_multi_bwd`."""
 import json
 import os
 import sys
@@ -17,7 +18,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd")]
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
+from dlmc.utils.quantize import WeightQuantBatch, quantize_model  # noqa: E402
 
 argv = [a for a in sys.argv[1:]]
 json_path = None
@@ -25,6 +26,9 @@ if "--json" in argv:
     i = argv.index("--json")
     json_path = argv[i + 1]
     del argv[i:i + 2]
+batched = "--batched-weights" in argv
+if batched:
+    argv.remove("--batched-weights")
 name = argv[0] if len(argv) > 0 else "resnet18"
 batch = int(argv[1]) if len(argv) > 1 else 128
 from dlmc.quantization.scalar import kernels as K  # noqa: E402
@@ -43,9 +47,20 @@ for family, wtype, asigned in (("QBase (LSQ-style)", "minmax_tensor", True), ("R
     x = torch.randn(batch, 3, 224, 224, device=dev)
     y = torch.randint(0, 1000, (batch,), device=dev)
 
+    wqb = None
+    if batched and family in ("QBase (LSQ-style)", "FSPTQ"):
+        with torch.no_grad():
+            net(x)                        # calibrate, then collect the weight quantisers
+        wqb = WeightQuantBatch(net)
+
     def step():
         opt.zero_grad(set_to_none=True)
-        torch.nn.functional.cross_entropy(net(x), y).backward()
+        if wqb is None:
+            loss = torch.nn.functional.cross_entropy(net(x), y)
+        else:
+            with wqb.step():
+                loss = torch.nn.functional.cross_entropy(net(x), y)
+        loss.backward()
         opt.step()
     for _ in range(3):
         step()
@@ -56,6 +71,8 @@ for family, wtype, asigned in (("QBase (LSQ-style)", "minmax_tensor", True), ("R
     torch.cuda.synchronize()
     ms = round((time.perf_counter() - t0) / 10 * 1e3, 2)
     rec = {"ms_per_step": ms, "images_per_s": round(batch / ms * 1e3, 1)}
+    if wqb is not None:
+        rec["batched_weights"] = {"members": len(wqb.members), "skipped": len(wqb.skipped)}
     if wtype is not None:       # one more step with HIP events on every launch of this project's kernels
         K.PROFILE.reset()
         K.PROFILE.enabled = True
