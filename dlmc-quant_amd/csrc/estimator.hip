@@ -362,6 +362,10 @@ using namespace dlmcq;
 
 extern "C" size_t dlmcq_l2norm_scratch_bytes(int64_t outer, int64_t channels, int64_t inner) {
   if (outer < 1 || channels < 1 || inner < 1) return 0;
+  if (channels == 1 && outer > 1) {  // the entry points flatten this case and plan for the flat row: size for that plan
+    inner *= outer;
+    outer = 1;
+  }
   const L2Plan p = l2_plan(outer, channels, inner);
   return (size_t)(p.nseg * channels * 2) * sizeof(float);
 }

@@ -205,8 +205,8 @@ def quantize_codes(x, scale, offset, lo, hi):
     return ((x - offset) / (scale + 1e-7)).round().clamp(lo, hi)
 
 
-def l2norm_tensor(x, n_bits, signed, max_iter=100000):
-    """ops.py:71-83."""
+def l2norm_tensor(x, n_bits, signed, max_iter=100000, return_iters=False):
+    """ops.py:71-83.  `return_iters` appends the number of iterations the loop ran."""
     scale, offset = minmax_tensor(x, n_bits, signed)
     lo, hi = qrange(signed, n_bits)
     diff = float("inf")
@@ -217,11 +217,13 @@ def l2norm_tensor(x, n_bits, signed, max_iter=100000):
         diff = float((new - scale).abs() / scale)
         scale = new
         it += 1
+    if return_iters:
+        return scale, offset, it
     return scale, offset
 
 
-def l2norm_channel(x, n_bits, signed, ch_axis=0, max_iter=100000):
-    """ops.py:198-215."""
+def l2norm_channel(x, n_bits, signed, ch_axis=0, max_iter=100000, return_iters=False):
+    """ops.py:198-215.  `return_iters` appends the number of iterations the loop ran."""
     shape = [1] * x.dim()
     shape[ch_axis] = -1
     rows = x.transpose(0, ch_axis).reshape(x.shape[ch_axis], -1)
@@ -235,6 +237,8 @@ def l2norm_channel(x, n_bits, signed, ch_axis=0, max_iter=100000):
         diff = float(((new - scale) ** 2).sum().sqrt() / (scale ** 2).sum().sqrt())
         scale = new
         it += 1
+    if return_iters:
+        return scale.reshape(shape), offset.reshape(shape), it
     return scale.reshape(shape), offset.reshape(shape)
 
 
@@ -374,14 +378,21 @@ def fsptq_layer_forward(layer, x, in_scale, in_zp, wt_scale, in_rng, wt_rng):
 
 
 # ------------------------------------------------- weight transforms that precede the path
+def _sqrt(v):
+    """IEEE square root of an fp32 tensor.  `v.sqrt()` is that wherever ATen computes it itself; a build that hands unary
+    functions to a vector maths library gets that library's accuracy (below one ulp, not correct rounding).  The square root
+    in float64 rounded to fp32 is correctly rounded either way (53 bits are more than 2*24 + 2)."""
+    return v.double().sqrt().float()
+
+
 def fold_bn(weight, bias, gamma, beta, mean, var):
     """dlmc/utils/merge_bn.py:85-101: note var + 1e-7 (not bn.eps).  Returns (weight', bias')."""
     v = var + 1e-7
     cout = weight.shape[0]
     if bias is None or bias.numel() == 0:
         bias = torch.zeros(cout)
-    b = gamma * (bias - mean) / v.sqrt() + beta
-    w = (weight.reshape(cout, -1) * gamma.reshape(-1, 1) / v.sqrt().reshape(-1, 1)).reshape(weight.shape)
+    b = gamma * (bias - mean) / _sqrt(v) + beta
+    w = (weight.reshape(cout, -1) * gamma.reshape(-1, 1) / _sqrt(v).reshape(-1, 1)).reshape(weight.shape)
     return w, b
 
 
@@ -389,7 +400,7 @@ def repvgg_fuse(k3, bn3, k1, bn1, bnid, groups=1):
     """model/classification/repvgg.py:92-130.  bn* = (gamma, beta, mean, var, eps); bnid may be None."""
     def branch(kernel, bn):
         gamma, beta, mean, var, eps = bn
-        std = (var + eps).sqrt()
+        std = _sqrt(var + eps)
         return kernel * (gamma / std).reshape(-1, 1, 1, 1), beta - mean * gamma / std
     ka, ba = branch(k3, bn3)
     kb, bb = branch(k1, bn1)
@@ -420,5 +431,29 @@ def l2norm_output(layer, x, weight, n_bits, signed, patience=1000):
         scale = new
         if mse < best_mse:
             best_mse, best_scale = mse, scale
+        count += 1
+    return best_scale, offset
+
+
+def l2norm_output_channel(layer, x, weight, n_bits, signed, ch_axis=0, patience=1000):
+    """ops.py:252-292: refine the per-channel weight scale against the layer output, viewed as [batch, channel, rest].
+    The new scale of a channel is SUM out*out_q / SUM (out_q*out_q + 1e-7) over axes (0, 2); the stopping norm is taken
+    over all channels.  Unlike `l2norm_output`, the best scale is the one the iteration STARTED with (:279-283: the
+    bookkeeping runs before `scale = new_scale`), so `patience=1` returns the min/max scale."""
+    out = conv_or_linear(layer, x, weight)
+    batch, channel = out.shape[0], out.shape[1]
+    out = out.reshape(batch, channel, -1)
+    scale, offset = minmax_channel(weight, n_bits, signed, ch_axis=ch_axis)
+    lo, hi = qrange(signed, n_bits)
+    diff, best_mse, best_scale, count = float("inf"), float("inf"), scale, 0
+    while diff > 1e-5 and count != patience:
+        wq = quantize_codes(weight, scale, offset, lo, hi)
+        oq = conv_or_linear(layer, x, wq).reshape(batch, channel, -1)
+        new = ((out * oq).sum(axis=(0, 2)) / (oq * oq + 1e-7).sum(axis=(0, 2))).reshape(scale.shape)
+        mse = l2_loss(out, oq)
+        diff = float(((new - scale) ** 2).sum().sqrt() / (scale ** 2).sum().sqrt())
+        if mse < best_mse:
+            best_mse, best_scale = mse, scale
+        scale = new
         count += 1
     return best_scale, offset

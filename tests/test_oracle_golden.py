@@ -341,3 +341,47 @@ def test_minmax_pixel(golden):
             s, o = O.minmax_pixel(x, c["n_bits"], c["signed"], allow_offset=False)
             assert_bits_equal(s, golden.get(c, "scale_nooff"))
             assert_bits_equal(o, golden.get(c, "offset_nooff"))
+
+
+def test_output_aware_channel_estimator_two_iterations_by_hand():
+    """`l2norm_output_channel` (ops.py:252-292) on a tiny conv - x (4, 3, 12, 12), w (8, 3, 3, 3), 4 bit signed - against the
+    first two iterations written out: the best scale is the one an iteration STARTED with, so one iteration returns the
+    min/max scale and two return either that or the first refined scale, whichever had the smaller output error."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(2333)
+    x = torch.randn(4, 3, 12, 12, generator=g)
+    w = torch.randn(8, 3, 3, 3, generator=g) * 0.2
+    conv = torch.nn.Conv2d(3, 8, 3, padding=1, bias=False)
+    lo, hi = -7, 7
+    out = F.conv2d(x, w, None, 1, 1).reshape(4, 8, -1)
+    s0 = (w.reshape(8, -1).abs().max(dim=1)[0] / 7).reshape(8, 1, 1, 1)
+    q0 = (w / (s0 + 1e-7)).round().clamp(lo, hi)
+    oq0 = F.conv2d(x, q0, None, 1, 1).reshape(4, 8, -1)
+    mse0 = ((out - oq0) ** 2).sum(axis=1).mean()
+    s1 = ((out * oq0).sum(axis=(0, 2)) / (oq0 * oq0 + 1e-7).sum(axis=(0, 2))).reshape(8, 1, 1, 1)
+    q1 = (w / (s1 + 1e-7)).round().clamp(lo, hi)
+    oq1 = F.conv2d(x, q1, None, 1, 1).reshape(4, 8, -1)
+    mse1 = ((out - oq1) ** 2).sum(axis=1).mean()
+    # the refined scale, channel by channel in float64
+    for c in range(8):
+        a = (out[:, c].double() * oq0[:, c].double()).sum()
+        b = (oq0[:, c] * oq0[:, c] + 1e-7).double().sum()
+        assert abs(float(s1[c]) - float(a / b)) <= 1e-5 * float(a / b)
+    assert abs(float(mse1) - float(mse0)) > 0.01 * float(mse0), "the two errors must not be a near tie"
+    s, o = O.l2norm_output_channel(conv, x, w, 4, True, patience=1)
+    assert_bits_equal(s, s0, "one iteration: the min/max scale")
+    assert_bits_equal(o, torch.zeros(8, 1, 1, 1))
+    s, _ = O.l2norm_output_channel(conv, x, w, 4, True, patience=2)
+    assert s.shape == (8, 1, 1, 1)
+    assert_bits_equal(s, s1 if bool(mse1 < mse0) else s0, "two iterations")
+    # three iterations: the scale with the smallest error among those an iteration started with, the earliest on a tie
+    s2 = ((out * oq1).sum(axis=(0, 2)) / (oq1 * oq1 + 1e-7).sum(axis=(0, 2))).reshape(8, 1, 1, 1)
+    q2 = (w / (s2 + 1e-7)).round().clamp(lo, hi)
+    oq2 = F.conv2d(x, q2, None, 1, 1).reshape(4, 8, -1)
+    mse2 = ((out - oq2) ** 2).sum(axis=1).mean()
+    best, best_mse = s0, mse0
+    for cand, mse in ((s1, mse1), (s2, mse2)):
+        if bool(mse < best_mse):
+            best, best_mse = cand, mse
+    s, _ = O.l2norm_output_channel(conv, x, w, 4, True, patience=3)
+    assert_bits_equal(s, best, "three iterations")
