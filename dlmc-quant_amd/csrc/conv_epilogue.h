@@ -32,6 +32,11 @@ struct ConvEpi {
   // tensor: modules/base.py:82-94 -> ops.py:20-34) comes out of the launch that produces the tensor.
   float* mm;
   int mm_np;
+  // narrow fp32 rows (dlmcq_conv2d_i8_nhwc_narrow; the NARROW instantiations of conv_i8_mfma_kernel): `out` and `residual` are [M][kf]
+  // with K - 64 < kf <= K, kf % 4 == 0, while the codes keep rows of K (the layer's channel count zero-padded to the K step of its
+  // consumer); 0 everywhere else.  (It sits in what was padding in front of the next pointer: the struct's size and the offsets of
+  // every other field are what they were.)
+  int kf;
   // float activation offset (the *_xoff entry points; the XOFF instantiations): x^ = q * s^ + o with a per-tensor float o (`x_off`, a
   // device scalar) that no integer zero point represents.  The caller folds o * SUM_{all taps} tap[k] into the bias; the epilogue of a
   // BORDER pixel subtracts o * SUM_{out-of-bounds taps} tap[k][r][s] (`x_tap`: fp32 [R * S][K], the per-tap sums of the dequantised

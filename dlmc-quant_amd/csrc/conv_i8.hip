@@ -52,7 +52,11 @@ namespace dlmcq {
 // or quantised (conv_epilogue.h); single-layer instantiations only (the dual entry point refuses it)
 // XOFF: a float activation offset (dlmcq_conv2d_i8_nhwc_xoff; ep.x_off / ep.x_tap): a border pixel's value loses o * (its out-of-bounds taps'
 // weight sums), conv_epilogue.h xoff_border4; the unswapped single-pair A-direct instantiations only
-template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false, bool XOFF = false>
+// NARROW: narrow fp32 rows (dlmcq_conv2d_i8_nhwc_narrow; ep.kf) - a layer whose K is its real channel count kf zero-padded to a multiple of
+// 64 reads its fp32 shortcut and writes its fp32 output as [M][kf], guarded by col < kf, while its codes keep rows of K (every column
+// written: the padded ones hold the consumer's code of what the zero weights and bias give).  The unswapped 64-wide single-pair
+// A-direct epilogue only; no observing, XOFF or K % 4 != 0 form
+template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false, bool XOFF = false, bool NARROW = false>
 __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : (SWAP && BN == 64 && ADIR && !ASYM ? 5 : SWAP && BN == 128 && ADIR && !ASYM ? 3 : ADIR || BN == 64 ? (ASYM ? 3 : 4) : 3))) void conv_i8_mfma_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w, float* __restrict__ out, const float* __restrict__ bias,
     const int32_t* __restrict__ wsum, const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -90,6 +94,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   static_assert(!(ASYM && DUAL), "asymmetric weights: single pair only");
   static_assert(!(SWAP && DUAL), "SWAP: codes-only layers with one operand pair");
   static_assert(!(XOFF && (SWAP || DUAL || !ADIR)), "XOFF: the unswapped single-pair A-direct epilogue");
+  static_assert(!(NARROW && (BN != 64 || SWAP || DUAL || !ADIR || XOFF || LAB != 0)), "NARROW: the unswapped 64-wide single-pair A-direct epilogue");
   __shared__ __attribute__((aligned(1024))) int8_t lds[LDS_BYTES + PAR_BYTES + (ASYM ? 4 * 32 * 4 : 0)];
 
   // XCD-aware tile order: the workgroups that share an activation tile (same row block, different column blocks) are
@@ -133,16 +138,17 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   auto par_i = [&](int a, int j) { return *reinterpret_cast<const int*>(lds + LDS_BYTES + (a * BN + j * 32 + l31) * 4); };
   const int er = lane >> 4, ec = (lane & 15) * 4;   // row-major layout of the staged tile: 4 rows x 64 channels per wave-instruction
   f32x4 idt[8];
+  const int kf = NARROW ? ep.kf : g.K;              // row width of the fp32 tensors (`out`, `residual`); the codes' is g.K
   auto load_residual = [&](int h) {
     const int colr = n0 + h * 64 + ec;
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int64_t row = m0 + wrow0 + it * 4 + er;
-      idt[it] = (row < g.M && colr < g.K) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ep.residual + row * g.K + colr))
+      idt[it] = (row < g.M && colr < kf) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ep.residual + row * kf + colr))
                                           : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
   };
-  if (EARLY_RES && !DUAL && ep.residual && (g.K & 3) == 0) load_residual(0);
+  if (EARLY_RES && !DUAL && ep.residual && (NARROW || (g.K & 3) == 0)) load_residual(0);
 
   // ---- DMA assignment: wave-instruction i of this wave covers tile rows (i*4 + wave)*16 .. +15 ----
   const int lrow = lane >> 2, pslot = lane & 3;
@@ -524,7 +530,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
       reinterpret_cast<uint32_t*>(ep.mm)[2 * ep.mm_np + blockIdx.x] = ab;
     }
   };
-  if ((g.K & 3) == 0) {
+  if (NARROW || (g.K & 3) == 0) {
     // through LDS: accumulator layout (lane = channel, register = row) -> row-major, so that each lane stores 16 B and
     // each wave-instruction writes 4 rows x 256 contiguous bytes (the 1x1 layers are bound by this output stream).
     asm volatile("s_barrier" ::: "memory");         // every wave is done reading the operand buffers
@@ -572,10 +578,13 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
             if (xoff_is_border(xh0, xw0, g.R, g.S, g.dil, g.H, g.W))
               v = xoff_sub4(v, xo, xoff_border4(ep.x_tap, g.K, col, xh0, xw0, g.R, g.S, g.dil, g.H, g.W));
           }
-          if (ep.residual) v = f32x4{v.x + idt[it].x, v.y + idt[it].y, v.z + idt[it].z, v.w + idt[it].w};
+          // (NARROW: a column in kf .. K - 1 has no shortcut - load_residual left its quad at +0 - and is not stored as fp32)
+          if (ep.residual && (!NARROW || col < kf)) v = f32x4{v.x + idt[it].x, v.y + idt[it].y, v.z + idt[it].z, v.w + idt[it].w};
           if (ep.relu) v = f32x4{relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)};
           if constexpr (R6) v = cap6_nan4(v);
-          if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
+          if constexpr (NARROW) {
+            if (out && col < kf) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + row * kf + col));
+          } else if (out) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out + at));
           if (ep.mm) { mm_add(v.x); mm_add(v.y); mm_add(v.z); mm_add(v.w); }
           if (ep.codes) {
             const uint32_t c = eq.code4(v);
@@ -775,7 +784,17 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
     plan.adir = true;
     if (plan.bn != 64) plan.bn = 128;
   }
-  const bool special = plan.halo && !(ep.ctl & DLMCQ_FORCE_TILED) && !xoff, route_only = (ep.ctl & DLMCQ_ROUTE_ONLY) != 0;
+  // narrow fp32 rows (ep.kf; dlmcq_conv2d_i8_nhwc_narrow) likewise: the NARROW instantiations of this file's kernel only - unswapped,
+  // A-direct, 64-wide tiles (the fp32 tile of the last column block is the only partial one) - and no specialised kernel
+  const bool narrow = ep.kf != 0;
+  if (narrow) {
+    if (seg2 || forced || xoff || (ep.ctl & DLMCQ_PIPELINED)) return DLMCQ_EINVAL;
+    if (ep.codes && !aligned16(ep.codes)) return DLMCQ_EALIGN;
+    plan.swap = false;
+    plan.adir = true;
+    plan.bn = 64;
+  }
+  const bool special = plan.halo && !(ep.ctl & DLMCQ_FORCE_TILED) && !xoff && !narrow, route_only = (ep.ctl & DLMCQ_ROUTE_ONLY) != 0;
   float* const mm_req = ep.mm;
   ep.mm = nullptr;                    // (the specialised kernels below do not write partials)
   // (only the block-end kernel knows the chunk-major form of the fp32 block tensors: a call that carries the bits and would land
@@ -829,7 +848,10 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound (the dual entry point refuses it)
   auto launch = [&](auto r6) {
     constexpr bool R6 = decltype(r6)::value;
-    if (xoff) {
+    if (narrow) {
+      if (ep.w_off) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
+    } else if (xoff) {
       if (ep.w_off) {
         if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
         else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
@@ -963,6 +985,22 @@ extern "C" int dlmcq_conv2d_i8_nhwc_xoff(const void* x, const int8_t* w, float* 
     ep.x_off = in_offset;
     ep.x_tap = tap_sums;
   }
+  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
+                     x_is_unsigned, stream, ep);
+}
+
+extern "C" int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                           const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                           const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R,
+                                           int64_t S, int32_t stride, int32_t pad, int32_t dilation, int32_t x_is_unsigned,
+                                           const float* residual, int32_t relu, void* codes, const float* q_scale,
+                                           const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                                           int64_t Kf, dlmcq_stream_t stream) {
+  // fp32 rows of Kf floats beside code rows of K bytes: K the padded width, Kf the real one, inside K's last block of 64
+  if (K < 64 || K % 64 != 0 || Kf % 4 != 0 || Kf > K || Kf <= K - 64) return DLMCQ_EINVAL;
+  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  ep.w_off = w_offset;
+  ep.kf = (int)Kf;
   return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
                      x_is_unsigned, stream, ep);
 }

@@ -512,7 +512,7 @@ def _head(o, out):
 
 def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding=0, dilation=1,
               residual=None, relu=False, emit=None, want_out=True, w_offset=None, force_tiled=False, pipelined=False, observe=False,
-              out_chunk_major=False, act=None, in_offset=None, tap_sums=None):
+              out_chunk_major=False, act=None, in_offset=None, tap_sums=None, out_channels=None):
     """Fused int8 conv / linear on the matrix cores.  `codes`: uint8/int8 activation codes, logically
     (N, C, H, W) in channels_last memory, or (N, C) for a linear layer.  Returns fp32 (N, K, P, Q) in
     channels_last memory (or (N, K)).  The operands are marshalled by `_operand`: scales and zero point as `_flat` takes them, a
@@ -531,29 +531,41 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
     block-end kernel (csrc/conv_pwr_i8.hip) takes them so; where the library's dispatch hands the call to another kernel a ChunkMajor
     residual is converted first (a copy) and the output comes back as an ordinary tensor.
     `in_offset` (fp32 device scalar o) with `tap_sums` (fp32 [R * S, K]): a float activation offset (dlmcq_conv2d_i8_nhwc_xoff) - `bias`
-    must already hold o * tap_sums.sum(0); border pixels lose o * (their out-of-bounds taps' sums).  Not with `observe`."""
+    must already hold o * tap_sums.sum(0); border pixels lose o * (their out-of-bounds taps' sums).  Not with `observe`.
+    `out_channels=k` (dlmcq_conv2d_i8_nhwc_narrow; convolutions only): the weights' K rows are a layer's k real output channels zero-padded
+    to a multiple of 64 (K - 64 < k <= K, k % 4 == 0).  The fp32 output is then (N, k, P, Q), dense channels_last, and `residual` has that
+    shape, while the emitted codes stay (N, K, P, Q) - what a consumer's K step wants.  Always the tiled kernel.  Not with `observe`,
+    `in_offset`, `out_chunk_major`, a ChunkMajor residual or `pipelined`."""
     if (in_offset is None) != (tap_sums is None):
         raise ValueError("conv2d_i8: in_offset and tap_sums go together")
+    narrow = out_channels is not None
+    if narrow and (observe or in_offset is not None or out_chunk_major or pipelined or isinstance(residual, ChunkMajor)):
+        raise ValueError("conv2d_i8: out_channels (narrow fp32 rows) goes with none of observe, in_offset, out_chunk_major, a ChunkMajor "
+                         "residual and pipelined")
     o = _operand(dict(codes=codes, wq=wq, wsum=wsum, bias=bias, in_scale=in_scale, in_zp=in_zp, w_scale=w_scale, stride=stride,
                       padding=padding, dilation=dilation))
     codes, shape = o.codes, o.shape      # (codes: the device / dtype anchor for the small parameter tensors)
     linear = codes.dim() == 2
     (n, K), (h, w_, c, R, S, st, pd, dl, uns) = shape[:2], o.geom
     geo = (n, h, w_, c, K, R, S, st, pd, dl, uns)
+    if narrow and linear:
+        raise ValueError("conv2d_i8: out_channels is for convolutions (4-D codes)")
+    fshape = (n, int(out_channels)) + tuple(shape[2:]) if narrow else shape      # the fp32 tensors' shape (`out`, `residual`)
 
-    def alloc(dtype):
+    def alloc(dtype, shape=shape):
         if linear:
             return torch.empty(shape, dtype=dtype, device=codes.device)
         return torch.empty(shape, dtype=dtype, device=codes.device, memory_format=torch.channels_last)
     act = _act(relu, act)
-    fused = residual is not None or act or emit is not None or w_offset is not None or (observe and want_out) or in_offset is not None
+    fused = (residual is not None or act or emit is not None or w_offset is not None or (observe and want_out) or in_offset is not None
+             or narrow)
     if in_offset is not None and observe:
         raise ValueError("conv2d_i8: the offset entry point has no observing form")
     if not want_out and emit is None:
         raise ValueError("conv2d_i8: nothing to produce (want_out=False without emit)")
-    out = alloc(torch.float32) if want_out else None
+    out = alloc(torch.float32, fshape) if want_out else None
     head = _head(o, out)
-    out_elems = math.prod(shape)
+    out_elems, f_elems = math.prod(shape), math.prod(fshape)
     ops = 2 * out_elems * c * R * S
     if not fused:
         if force_tiled:
@@ -564,7 +576,7 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
     icm = isinstance(residual, ChunkMajor)
     ocm = bool(out_chunk_major) and out is not None and not linear
     if residual is not None:
-        if tuple(residual.shape) != shape or residual.dtype != torch.float32:
+        if tuple(residual.shape) != fshape or residual.dtype != torch.float32:
             raise ValueError("conv2d_i8: residual must be fp32 of the output's shape")
         if icm:
             residual = residual.buf
@@ -572,14 +584,16 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         if not icm:
             residual = residual.contiguous() if linear else _nhwc(residual)
     q = _quantiser(emit, alloc, codes, True, "conv2d_i8")
-    nbytes = codes.numel() + wq.numel() + out_elems * (4 * (out is not None) + 4 * (residual is not None) + (emit is not None))
+    nbytes = codes.numel() + wq.numel() + f_elems * (4 * (out is not None) + 4 * (residual is not None)) + out_elems * (emit is not None)
     flags = (N.FORCE_TILED if force_tiled else 0) | (N.PIPELINED if pipelined else 0)
     # the entry point: head, [w_offset], geometry, the epilogue, [what only this entry point takes]
     w_off, trailer, observing = (), (), False
-    if in_offset is not None or w_offset is not None:
+    if in_offset is not None or w_offset is not None or narrow:
         w_offset = _flat(w_offset, codes)
         w_off = (N.ptr(w_offset),)
-    if in_offset is not None:
+    if narrow:
+        fn, trailer = N.lib.dlmcq_conv2d_i8_nhwc_narrow, (int(out_channels),)
+    elif in_offset is not None:
         fn = N.lib.dlmcq_conv2d_i8_nhwc_xoff
         in_offset, tap_sums = _flat(in_offset, codes), _flat(tap_sums, codes)
         trailer = (N.ptr(in_offset), N.ptr(tap_sums))

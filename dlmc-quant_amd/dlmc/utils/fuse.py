@@ -204,6 +204,9 @@ class _PlanLayer(nn.Module):
         for name in ("bias_fold", "x_off", "tap_sums"):
             self.register_buffer(name, None, persistent=False)
         self.xoff_padded = False     # the border term runs in the kernel (the *_xoff entry points)
+        # narrow fp32 rows (fuse_inference(narrow_rows=True); Int8Layer only): a channel-padded layer reads its fp32 shortcut and writes its
+        # fp32 output k wide - dense, no slice on the way out - while its codes stay k_pad wide (dlmcq_conv2d_i8_nhwc_narrow)
+        self.narrow = False
 
     def _fold_offset(self, tap):
         """A float activation offset o (act.xoff): `tap` [k_pad, R, S] (float64, on the device) = per output channel and tap the sum of the
@@ -264,7 +267,7 @@ class _PlanLayer(nn.Module):
     def _finish(self, out, codes):
         if self.pool is not None:
             codes = K.maxpool_codes(codes, *self.pool)
-        if out is not None and self.k_pad != self.k:
+        if out is not None and self.k_pad != self.k and not self.narrow:
             out = out[:, :self.k]          # fp32 leaves the plan: drop the padding channels (codes stay padded for plan consumers)
         return out, codes
 
@@ -379,6 +382,8 @@ class Int8Layer(_PlanLayer):
         if self.w_off is not None:
             kw["w_offset"] = self.w_off
         kw.update(self._xoff_kw())
+        if self.narrow:
+            kw["out_channels"] = self.k
         if self.relu or self.relu6 or residual is not None or emit is not None or self.w_off is not None or self.xoff_padded:
             res = K.conv2d_i8(codes, self.wq, self.wsum, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale,
                               residual=residual, act=self._act_arg(), emit=emit, want_out=self.want_out,
@@ -962,6 +967,7 @@ class FusionReport:
         self.chunk_major = 0  # fp32 block outputs kept chunk-major between two kernels that walk them chunk by chunk (_block_layout_pass)
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
         self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
+        self.narrow = 0       # channel-padded layers reading / writing their fp32 tensors at the real width (fuse_inference(narrow_rows=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -970,6 +976,7 @@ class FusionReport:
                 f"code-emitting={self.emit}, fp32 outputs kept={self.fp32_outputs}, stem layers={self.stem}, "
                 f"pools on codes={self.pooled}, dual (conv + shortcut conv) kernels={self.dual}, chained pairs={self.chained} (fp32 outputs chunk-major: {self.chunk_major}), "
                 f"depthwise + pointwise units={self.dwpw}, " + (f"gap heads={self.gap_heads}, " if self.gap_heads else "") +
+                (f"narrow fp32 rows={self.narrow}, " if self.narrow else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1237,7 +1244,7 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True, act_offsets=False, gap_head=False):
+                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1273,7 +1280,17 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     A pool whose reader is not plan-eligible (RootQ, a disabled quantiser, a non-integer zero point, in-features % 64 != 0), any other
     output size, and F.avg_pool2d(x, x.size(3)) (a kernel size read from the tensor) are left as they are.  One spelling is folded
     although it differs from the model at batch 1: a bare x.squeeze() gives [C] there, the plan's node [1, C].  Off by default: the
-    plan without it is the plan as it was."""
+    plan without it is the plan as it was.
+    `narrow_rows=True`: a convolution whose output channels are zero-padded to a multiple of 64 (MobileNetV2's 24 / 32 /
+    96 / 160-channel projections, CIFAR ResNets' 16 / 32) and a multiple of 4 reads and writes its fp32 tensors at the REAL width while
+    its codes stay padded (dlmcq_conv2d_i8_nhwc_narrow; the tiled kernel, 64-wide tiles).  The shortcut add behind such a layer is then
+    folded into its epilogue like any other (with the ReLU / ReLU6, pool and emit rules behind it), its fp32 output is dense - the next
+    block reads it as its shortcut without a copy - and every such layer that writes fp32 at all writes it that way
+    (`fusion_report.narrow` counts them).  Such a layer is never half of a dual kernel: a convolution on its shortcut runs as its own
+    node; the chain, block-layout and fused-head passes keep requiring unpadded channels.  A padded layer with the border term of a
+    float activation offset (the *_xoff kernels have no narrow form) or with k % 4 != 0 keeps its add outside.  Bit-identical to the
+    plan without it (IEEE addition commutes; the codes are those of the stored value either way).  Off by default: the plan without it
+    is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -1331,7 +1348,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         #  fit it, so the add stays outside the kernel)
         wn = modules[node.target].weight
         unpadded = wn.dim() != 4 or wn.shape[0] % 64 == 0
-        if spec[4] == "gemm" and unpadded and len(users) == 1 and _is_add(users[0]) and users[0].args[0] is not users[0].args[1]:
+        # ... unless the layer runs with narrow fp32 rows (narrow_rows): a padded "gemm" convolution of k % 4 == 0 channels without the
+        # border term of a float activation offset (the *_xoff kernels have no narrow form)
+        can_narrow = (narrow_rows and spec[4] == "gemm" and not unpadded and wn.shape[0] % 4 == 0 and
+                      not (spec[0].xoff and int(modules[node.target].padding[0]) > 0))
+        if spec[4] == "gemm" and (unpadded or can_narrow) and len(users) == 1 and _is_add(users[0]) and users[0].args[0] is not users[0].args[1]:
             add = users[0]
             residual = add.args[1] if add.args[0] is last else add.args[0]
             chain.append(add)
@@ -1384,9 +1405,12 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         cls = {"gemm": Int8Layer, "dw": DwInt8Layer}.get(spec[4], StemLayer)
         # the shortcut is itself a not-yet-planned int8 convolution read by nobody else: one dual kernel
         other = spec_of(residual) if residual is not None and residual.op == "call_module" else None
-        dual = (other is not None and other[4] == "gemm" and spec[5] is None and other[5] is None and list(residual.users) == [chain[1]] and
+        # (a narrow layer is never a dual operand: the convolution on its shortcut runs as its own node)
+        dual = (other is not None and unpadded and other[4] == "gemm" and spec[5] is None and other[5] is None and list(residual.users) == [chain[1]] and
                 modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4 and not act6 and   # (dual kernel: ReLU alone)
                 not any(sp[0].xoff and int(modules[t].padding[0]) > 0 for sp, t in ((spec, node.target), (other, residual.target))))
+        # every such layer that writes fp32 (or reads a shortcut) does so at the real width
+        narrow = bool(can_narrow and (fp32_needed or emit is None or residual is not None))
         if dry_run:       # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
             gm.add_module(name, _DryNode())
         else:
@@ -1398,6 +1422,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             if other is not None and dual:
                 other = from_blob(residual.target, other)
             plan = cls(modules[node.target], spec, relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
+            plan.narrow = narrow
             # codes of an unsigned-byte quantiser read only by matrix-core layers (no channel padding, no pooling on the way)
             # travel re-centred (see _PlanLayer.__init__); the consumers recognise them by dtype
             def takes_shifted(u):
@@ -1444,6 +1469,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         report.relu6 += act6
         report.act_offset += spec[0].xoff + (dual and other[0].xoff)
         report.residual += residual is not None
+        report.narrow += narrow
         report.emit += emit is not None
         report.fp32_outputs += bool(fp32_needed or emit is None)
     graph.eliminate_dead_code()

@@ -229,6 +229,31 @@ class MobileNetV2(nn.Module):
         return self.classifier(torch.flatten(self.pool(self.features(x)), 1))
 
 
+class CifarResNet(nn.Module):
+    """The CIFAR ResNet of He et al. 2016, section 4.2 (public architecture): a 3x3 first layer of 16 channels on the 32 x 32 image, three
+    stages of `depth` BasicBlocks at 16 / 32 / 64 channels (stride 2 into the second and third), global average pool, linear head.  Where
+    the shape changes the shortcut is a 1x1 convolution + BN (BasicBlock's `downsample`; "option B")."""
+
+    def __init__(self, depth, num_classes=10):
+        super().__init__()
+        self.conv1 = _conv(3, 16, 3)
+        self.bn1 = nn.BatchNorm2d(16)
+        self.relu = nn.ReLU(inplace=True)
+        cin, stages = 16, []
+        for i, width in enumerate((16, 32, 64)):
+            stages.append(nn.Sequential(*[BasicBlock(cin if j == 0 else width, width, 2 if (j == 0 and i > 0) else 1) for j in range(depth)]))
+            cin = width
+        self.layer1, self.layer2, self.layer3 = stages
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.fc = nn.Linear(cin, num_classes)
+        _init(self)
+
+    def forward(self, x):
+        x = self.relu(self.bn1(self.conv1(x)))
+        x = self.layer3(self.layer2(self.layer1(x)))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+
 def _init(model):
     for m in model.modules():
         if isinstance(m, nn.Conv2d):
@@ -259,6 +284,11 @@ def mobileone_s1_deploy(num_classes=1000):
 
 def mobilenet_v2(num_classes=1000):
     return MobileNetV2(num_classes=num_classes)
+
+
+def cifar_resnet20(num_classes=10):
+    """ResNet-20 for CIFAR: 6 * 3 + 2 layers, widths 16 / 32 / 64 - every block of its first two stages has channel-padded outputs."""
+    return CifarResNet(3, num_classes)
 
 
 MODELS = {"resnet18": resnet18, "resnet50": resnet50, "repvgg_a1": repvgg_a1_deploy, "mobileone_s1": mobileone_s1_deploy,

@@ -511,6 +511,25 @@ int dlmcq_conv2d_i8_nhwc_asym(const void* x, const int8_t* w, float* out, const 
                               void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                               int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* Narrow fp32 rows: dlmcq_conv2d_i8_nhwc_fused (w_offset == NULL) / dlmcq_conv2d_i8_nhwc_asym (w_offset != NULL) for a layer whose
+ * K is its real channel count Kf zero-padded to the K step of its consumer (K % 64 == 0, Kf % 4 == 0, K - 64 < Kf <= K; anything
+ * else DLMCQ_EINVAL): the two fp32 tensors have rows of the REAL width, the codes rows of the padded one.
+ *   residual  fp32 [N, P, Q, Kf] or NULL, out  fp32 [N, P, Q, Kf] or NULL: columns Kf .. K - 1 are neither read nor written
+ *   codes     [N, P, Q, K] or NULL: every column is written; for a column in Kf .. K - 1 no shortcut is added - the code is the
+ *             consumer's code of what the (zero) padded weights, bias and weight offset give
+ *   w, wsum, w_scale, bias, w_offset: [K] entries / rows, the padded ones included
+ * Per element the order of dlmcq_conv2d_i8_nhwc_fused: dequantise, weight-offset term, shortcut, ReLU / ReLU6, store, quantiser; with
+ * Kf == K the call gives, bit for bit, what _fused / _asym gives.  out, residual AND codes 16-byte aligned (DLMCQ_EALIGN otherwise).
+ * Always conv_i8_mfma_kernel (64-wide tiles, unswapped epilogue): the halo-tile, pointwise and block-end kernels are never chosen, so
+ * DLMCQ_FORCE_TILED changes nothing and DLMCQ_ROUTE_ONLY answers DLMCQ_ROUTE_TILED; DLMCQ_EMIT_SHIFT128 as in _fused; DLMCQ_PIPELINED and
+ * the two DLMCQ_FP32_*_CHUNK_MAJOR bits are DLMCQ_EINVAL.  No dual, observing or float-offset (_xoff) form. */
+int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                const float* in_scale, const float* in_zero_point, const float* w_scale, const float* w_offset,
+                                int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride,
+                                int32_t pad, int32_t dilation, int32_t x_is_unsigned, const float* residual, int32_t relu,
+                                void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                                int32_t q_form, float q_ste_g, int64_t Kf, dlmcq_stream_t stream);
+
 /* Depthwise 3x3 convolution (groups = channels; the MobileOne / MobileNet unit, modules/conv.py:13-19 with `groups`) on
  * activation codes, HBM-bound (1 byte in, 1 byte out): plain vector arithmetic, no matrix cores.  x: NHWC codes (uint8 if
  * x_is_unsigned), C % 4 == 0; w: int8 codes [R*S][C] (tap-major); per-channel w_scale and optional w_offset (asymmetric

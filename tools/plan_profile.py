@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Per-layer timing of the fused plan (HIP events around every plan node).
-python tools/plan_profile.py [model] [batch] [qbase] [act_offsets] [gap_head | gap_separate | gap_fused] [zp0]
+python tools/plan_profile.py [model] [batch] [qbase] [act_offsets] [gap_head | gap_separate | gap_fused] [zp0] [narrow_rows]
 (model mobileone_s1 is profiled as BASELINE config 5: QBase W4A8, asymmetric per-channel weights; `qbase` profiles any other model under that
 quantiser too, `act_offsets` builds the plan with fuse_inference(act_offsets=True), `gap_head` / `gap_separate` / `gap_fused` with gap_head=True / "separate" / "fused" -
 FSPTQ's zero points are then set to 0 after calibration, as tools/gap_head_ab.py does, so that the classifier is a plan node; `zp0` does
-the same without a gap flag: the plan those are to be compared with)"""
+the same without a gap flag: the plan those are to be compared with; `narrow_rows` builds the plan with fuse_inference(narrow_rows=True) and
+marks the nodes launched that way `nrw`)"""
 import json
 import os
 import sys
@@ -25,6 +26,7 @@ dev = "cuda:0"
 torch.manual_seed(2333)
 qbase = name == "mobileone_s1" or "qbase" in sys.argv[3:]
 act_offsets = "act_offsets" in sys.argv[3:]
+narrow_rows = "narrow_rows" in sys.argv[3:]
 gap_head = True if "gap_head" in sys.argv[3:] else next((v for v in ("separate", "fused") if "gap_" + v in sys.argv[3:]), False)
 zp0 = bool(gap_head) or "zp0" in sys.argv[3:]
 if qbase:
@@ -47,7 +49,7 @@ with torch.no_grad():
             if hasattr(m, "_zp_is_int"):
                 m.in_offset.zero_()
                 m._zp_is_int = None
-    plan = fuse_inference(model, act_offsets=act_offsets, gap_head=gap_head)
+    plan = fuse_inference(model, act_offsets=act_offsets, gap_head=gap_head, narrow_rows=narrow_rows)
     for _ in range(2):
         plan(x)
 
@@ -146,5 +148,5 @@ for mod, args, out, s, e in recs:
         4 * (out[0] is not None) + (out[1] is not None) + 4 * (len(args) > 1))
     print(f"{us:8.1f} us  in {str(tuple(xin.shape)):22s} {str(xin.dtype)[6:]:8s} w {str(tuple(w.shape)):20s} "
           f"{'res ' if len(args) > 1 else '    '}{'relu ' if mod.relu else '     '}{'out ' if out[0] is not None else '    '}"
-          f"{'codes' if out[1] is not None else '     '}  {2 * macs / us / 1e6:6.0f} TOP/s {nbytes / us / 1e3:6.0f} GB/s")
+          f"{'codes' if out[1] is not None else '     '}{' nrw' if getattr(mod, 'narrow', False) else ''}  {2 * macs / us / 1e6:6.0f} TOP/s {nbytes / us / 1e3:6.0f} GB/s")
 print(f"plan nodes {tot / 1e3:.2f} ms")
