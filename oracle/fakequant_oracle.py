@@ -349,6 +349,126 @@ def fsptq_weight_backward(w, scale, gy, lo, hi):
     return gw, gs
 
 
+# ------------------------------------------- float64 anchors of the backward kernels' sums
+def _relu_nan(v):
+    """csrc/dlmcq_internal.h `relu_nan`: v < 0 ? 0 : v (NaN stays NaN, -0 stays -0)."""
+    return torch.where(v < 0, torch.zeros((), dtype=v.dtype), v)
+
+
+def fq_backward_f64(form, x, gy, scale, offset, lo, hi, g=0.0):
+    """The one-pass backward of a fake-quant form (csrc/fq_bodies.h `bwd_one`) with its scale gradient in float64.
+    `form` is "qbase", "zeropoint", "symmetric" or "rootq_act"; `x`, `gy` are fp32 [outer, channels, inner]; `scale` and
+    `offset` (None: zero) are fp32 [channels].
+
+    Every DECISION is taken in fp32 in the kernel's op order - v, the clamp, `inside`, ste_round, `below` / `above` - so
+    gx = (gy*s)/s is the kernel's bit for bit.  Each element's contribution to the scale gradient is then computed in
+    float64 FROM the fp32 v and q, and summed in float64 per channel:
+      qbase      v = (x - o)/s^, inside = [lo <= v <= hi], q = R(clamp(v)),              contrib = gy*(q - inside*v)
+      zeropoint  v = x/s, a = R(v) + zp, inside = [lo <= a <= hi], q = clamp(a) - zp,    contrib = gy*(q - inside*v)
+      symmetric  zeropoint with zp = 0
+      rootq_act  t = clip(x, 0, s*(hi - lo)) (additive), v = t/s, q = R(v),             contrib = gy*(q - v) + above*gy*(hi - lo)
+    Returns (gx fp32, value float64 [channels], abs_sum float64 [channels], contrib float64 like x) with
+    value = g32 * sum(contrib) for qbase (g32 = g rounded to fp32, the kernel's argument) and sum(contrib) otherwise."""
+    f32 = torch.float32
+    assert x.dtype == f32 and gy.dtype == f32 and x.dim() == 3 and gy.shape == x.shape
+    s = scale.to(f32).reshape(1, -1, 1)
+    o = torch.zeros_like(s) if offset is None or form == "symmetric" else offset.to(f32).reshape(1, -1, 1)
+    flo, fhi = torch.tensor(float(lo), dtype=f32), torch.tensor(float(hi), dtype=f32)
+    g32 = torch.tensor(float(g), dtype=f32)
+    zero = torch.zeros((), dtype=f32)
+    if form == "rootq_act":
+        span = fhi - flo
+        up = s * span
+        t1 = x + _relu_nan(zero - x)
+        below, above = (zero - x) > 0, (t1 - up) > 0
+        t = t1 - _relu_nan(t1 - up)
+        v = t / s
+        q = ste_round(v)
+        gx = torch.where(below | above, zero, gy * s) / s
+        contrib = gy.double() * (q.double() - v.double()) + torch.where(above, gy.double() * float(span), torch.zeros((), dtype=torch.float64))
+    else:
+        if form == "qbase":
+            s = ste_scale(s, g32)
+            v = (x - o) / s
+            q = ste_round(v.clamp(flo, fhi))
+            inside = (v >= flo) & (v <= fhi)
+        elif form in ("zeropoint", "symmetric"):
+            v = x / s
+            a = ste_round(v) + o
+            inside = (a >= flo) & (a <= fhi)
+            q = a.clamp(flo, fhi) - o
+        else:
+            raise ValueError(form)
+        gx = torch.where(inside, gy * s, zero) / s
+        contrib = gy.double() * (q.double() - torch.where(inside, v, zero).double())
+    total = contrib.sum(dim=(0, 2))
+    value = total * g32.double() if form == "qbase" else total
+    return gx, value, contrib.abs().sum(dim=(0, 2)), contrib
+
+
+def rootq_weight_backward_f64(w, gy, upper, lower, alpha, lo, hi):
+    """Backward of `fq_rootq_weight` as csrc/rootq.hip `rootq_weight_bwd_kernel` computes it, anchored in float64: the clip
+    masks, the floor and the signs are the kernel's fp32 decisions (wc, delta, v, floor_pass(v), mi, e and sgn are fp32, op for
+    op); the smooth part - pow, log, every division after e - is float64 of those fp32 values.
+    Returns (gw float64, (g_upper, g_lower, g_alpha) float64, abs_sums) where abs_sums maps "d", "l", "u", "a" to the sum of
+    |addend| over the addends of the kernel's four sums, counted as its fp32 expression rounds them:
+      d: g*((sphi + 1)/2 + I),  -g_v*(v/delta),  g_k*(-2/delta^2)      (three per element)
+      l: g,  -g_v/delta,  and g_t1 where the element is clipped below
+      u: g_wc where the element is clipped above
+      a: g_P * P * log(B)
+    and g_upper = u + d/range, g_lower = l - d/range, g_alpha = a where alpha was not clipped, else 0."""
+    f32, f64 = torch.float32, torch.float64
+    w, g32 = w.to(f32).reshape(-1), gy.to(f32).reshape(-1)
+    up, lw = torch.as_tensor(upper, dtype=f32).reshape(()), torch.as_tensor(lower, dtype=f32).reshape(())
+    a0 = torch.as_tensor(alpha, dtype=f32).reshape(())
+    rng = torch.tensor(float(hi - lo), dtype=f32)
+    delta = (up - lw) / rng
+    c_lo, c_hi, eps, half = (torch.tensor(v, dtype=f32) for v in (1e-4, 1.0, 1e-5, 0.5))
+    a1 = a0 + _relu_nan(c_lo - a0)
+    a = a1 - _relu_nan(a1 - c_hi)
+    passes = not bool((a1 - c_hi) > 0) and not bool((c_lo - a0) > 0)
+    m_lo = (lw - w) > 0
+    t1 = w + _relu_nan(lw - w)
+    m_up = (t1 - up) > 0
+    wc = t1 - _relu_nan(t1 - up)
+    v = (wc - lw) / delta
+    iv = ste_floor(v)
+    mi = (iv + half) * delta + lw
+    e = wc - mi
+    sg = e.sgn()
+    k32 = torch.tensor(2.0, dtype=f32) / delta
+    phi32 = torch.pow(k32 * e.abs() + eps, a) * (e / (e.abs() + eps))
+    sphi = phi32.sgn().double()
+    # float64 from here on
+    g, d, vd, ivd, ed, sgd, ad = g32.double(), delta.double(), v.double(), iv.double(), e.double(), sg.double(), a.double()
+    aed = ed.abs()
+    den = aed + eps.double()
+    sign = ed / den
+    k = 2.0 / d
+    B = k * aed + eps.double()
+    P = torch.pow(B, ad)
+    g_phi, g_v = g * d * 0.5, g * d
+    d1, d2 = g * ((sphi + 1.0) * 0.5 + ivd), -g_v * (vd / d)
+    l1, l2 = g, -g_v / d
+    g_P, g_sign = g_phi * sign, g_phi * P
+    g_B = g_P * ad * torch.pow(B, ad - 1.0)
+    a_add = g_P * P * torch.log(B)
+    d3 = g_B * aed * (-2.0 / (d * d))
+    g_e = g_B * k * sgd + g_sign / den - (g_sign * ed / (den * den)) * sgd
+    g_wc = g_v / d + g_e
+    zero = torch.zeros((), dtype=f64)
+    g_t1 = torch.where(m_up, zero, g_wc)
+    u_add = torch.where(m_up, g_wc, zero)
+    l3 = torch.where(m_lo, g_t1, zero)
+    gw = torch.where(m_lo, zero, g_t1)
+    s_d, s_l, s_u, s_a = (d1 + d2 + d3).sum(), (l1 + l2 + l3).sum(), u_add.sum(), a_add.sum()
+    r = float(rng)
+    scalars = (s_u + s_d / r, s_l - s_d / r, s_a if passes else zero)
+    abs_sums = {"d": (d1.abs() + d2.abs() + d3.abs()).sum(), "l": (l1.abs() + l2.abs() + l3.abs()).sum(),
+                "u": u_add.abs().sum(), "a": a_add.abs().sum() if passes else zero}
+    return gw, scalars, abs_sums
+
+
 # --------------------------------------------------------------------------- layer forwards
 def conv_or_linear(layer, x_q, w_q):
     """modules/conv.py:13-19, modules/linear.py:12-13 (and the FSPTQuant/RootQ copies)."""
