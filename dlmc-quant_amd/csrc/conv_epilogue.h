@@ -17,7 +17,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct ConvEpi {
   const float* w_off;      // asymmetric per-channel weights w' = qw * s_w[k] + w_off[k] (ops.py:129-136): the extra term
                            // w_off[k] * SUM x' of the convolution, from a per-pixel sum of the activation codes (conv_i8.hip)
-  const float* residual;
+  const float* residual;   // fp32, the output's shape - or, in the PADRES instantiations of conv_i8_mfma_kernel, the SOURCE of a subsampled, zero-padded
+                           // shortcut, its geometry in the kernel's otherwise unused second-pair argument (conv_i8.hip)
   uint8_t* codes;
   const float* q_scale;
   const float* q_zp;

@@ -56,7 +56,14 @@ namespace dlmcq {
 // 64 reads its fp32 shortcut and writes its fp32 output as [M][kf], guarded by col < kf, while its codes keep rows of K (every column
 // written: the padded ones hold the consumer's code of what the zero weights and bias give).  The unswapped 64-wide single-pair
 // A-direct epilogue only; no observing, XOFF or K % 4 != 0 form
-template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false, bool XOFF = false, bool NARROW = false>
+// PADRES: a parameter-free shortcut folded into the NARROW epilogue (dlmcq_conv2d_i8_nhwc_padres) - ep.residual is not a tensor of the
+// output's shape but the SOURCE x of `pad(x[:, ::rs, ::rs, :])`, a dense fp32 NHWC tensor [N][Hs][Ws][Cs]: output row (n, p, q), fp32 column
+// col reads x[n][p * rs][q * rs][col - clo] where clo <= col < clo + Cs and adds +0 elsewhere (the addition is performed: -0 + +0 = +0,
+// as the materialised zero padding gives it).  Cs and clo are multiples of 4, so a quad is wholly inside the source or wholly zero.  The
+// five scalars ride in the second pair's geometry, which a single-pair kernel does not otherwise read (sg.g.H / W / C = Hs / Ws / Cs,
+// sg.g.stride = rs, sg.g.pad = clo): no other instantiation's arguments change
+template <int BN, bool DUAL, bool ADIR, bool ASYM = false, int LAB = 0, bool SWAP = false, bool R6 = false, bool XOFF = false, bool NARROW = false,
+          bool PADRES = false>
 __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : (SWAP && BN == 64 && ADIR && !ASYM ? 5 : SWAP && BN == 128 && ADIR && !ASYM ? 3 : ADIR || BN == 64 ? (ASYM ? 3 : 4) : 3))) void conv_i8_mfma_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w, float* __restrict__ out, const float* __restrict__ bias,
     const int32_t* __restrict__ wsum, const float* __restrict__ s_in, const float* __restrict__ zp_in,
@@ -95,6 +102,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   static_assert(!(SWAP && DUAL), "SWAP: codes-only layers with one operand pair");
   static_assert(!(XOFF && (SWAP || DUAL || !ADIR)), "XOFF: the unswapped single-pair A-direct epilogue");
   static_assert(!(NARROW && (BN != 64 || SWAP || DUAL || !ADIR || XOFF || LAB != 0)), "NARROW: the unswapped 64-wide single-pair A-direct epilogue");
+  static_assert(!PADRES || NARROW, "PADRES: an addressing mode of the NARROW epilogue's shortcut");
   __shared__ __attribute__((aligned(1024))) int8_t lds[LDS_BYTES + PAR_BYTES + (ASYM ? 4 * 32 * 4 : 0)];
 
   // XCD-aware tile order: the workgroups that share an activation tile (same row block, different column blocks) are
@@ -141,6 +149,23 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
   const int kf = NARROW ? ep.kf : g.K;              // row width of the fp32 tensors (`out`, `residual`); the codes' is g.K
   auto load_residual = [&](int h) {
     const int colr = n0 + h * 64 + ec;
+    if constexpr (PADRES) {
+      const int cs = colr - sg.g.pad;                 // the quad's first source channel (clo, Cs, colr: multiples of 4)
+      const bool inside = cs >= 0 && cs < sg.g.C;
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const int64_t row = m0 + wrow0 + it * 4 + er;
+        idt[it] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (row < g.M && inside) {
+          int rn, rp, rq;
+          row_npq(g, (uint32_t)row, rn, rp, rq);
+          // P = ceil(Hs / rs), Q = ceil(Ws / rs) (checked by the entry point): p * rs < Hs and q * rs < Ws for every output pixel
+          const int64_t at = (((int64_t)rn * sg.g.H + (int64_t)rp * sg.g.stride) * sg.g.W + (int64_t)rq * sg.g.stride) * sg.g.C + cs;
+          idt[it] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ep.residual + at));
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int64_t row = m0 + wrow0 + it * 4 + er;
@@ -733,11 +758,18 @@ static ConvPlan conv_plan(int64_t C, int64_t K, int64_t R, int64_t S, bool dual)
   return p;
 }
 
+// A pad shortcut (the PADRES instantiations; dlmcq_conv2d_i8_nhwc_padres): ep.residual is the dense fp32 NHWC source [N][h][w][c] of
+// pad(x[:, ::stride, ::stride, :]) with `clo` zero channels in front
+struct PadRes {
+  int h, w, c, stride, clo;
+};
+
 static int conv_launch(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
                        const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N, int64_t H,
                        int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
                        int32_t dilation, int32_t x_is_unsigned, dlmcq_stream_t stream, const ConvEpi& ep_in = ConvEpi{},
-                       const ConvSeg2* seg2 = nullptr, const ConvPlan* forced = nullptr, int64_t* mm_count = nullptr) {
+                       const ConvSeg2* seg2 = nullptr, const ConvPlan* forced = nullptr, int64_t* mm_count = nullptr,
+                       const PadRes* padres = nullptr) {
   // (observer partials - ep.mm - come from the tiled kernel's fp32 epilogue only: a call another kernel takes reports 0 partials)
   ConvEpi ep = ep_in;
   if (mm_count) *mm_count = 0;
@@ -794,6 +826,15 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
     plan.adir = true;
     plan.bn = 64;
   }
+  // a pad shortcut is an addressing mode of the narrow epilogue's shortcut; the output pixels must be exactly the source's subsampled
+  // ones (P = ceil(h / stride), Q = ceil(w / stride): no output pixel then reads outside the source)
+  if (padres) {
+    const PadRes& pr = *padres;
+    if (!narrow || !ep.residual || pr.h < 1 || pr.w < 1 || pr.stride < 1 || pr.c < 4 || pr.c % 4 != 0 || pr.clo < 0 || pr.clo % 4 != 0 ||
+        (int64_t)pr.clo + pr.c > ep.kf || P != ((int64_t)pr.h + pr.stride - 1) / pr.stride || Q != ((int64_t)pr.w + pr.stride - 1) / pr.stride)
+      return DLMCQ_EINVAL;
+    if (N * pr.h * pr.w * pr.c >= (1ll << 40)) return DLMCQ_ERANGE;
+  }
   const bool special = plan.halo && !(ep.ctl & DLMCQ_FORCE_TILED) && !xoff && !narrow, route_only = (ep.ctl & DLMCQ_ROUTE_ONLY) != 0;
   float* const mm_req = ep.mm;
   ep.mm = nullptr;                    // (the specialised kernels below do not write partials)
@@ -838,6 +879,9 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
     s2.g.nblk_n = g.nblk_n;
     if (s2.g.M != g.M || s2.g.K != g.K || s2.g.P != g.P || s2.g.Q != g.Q || ep.w_off) return DLMCQ_EINVAL;
   }
+  if (padres) {       // (no second pair: its geometry carries the shortcut's - see the kernel)
+    s2.g.H = padres->h; s2.g.W = padres->w; s2.g.C = padres->c; s2.g.stride = padres->stride; s2.g.pad = padres->clo;
+  }
   if (route_only) return DLMCQ_ROUTE_TILED;
   if (mm_req && out) {                             // one partial per workgroup of this launch
     ep.mm = mm_req;
@@ -848,7 +892,10 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound (the dual entry point refuses it)
   auto launch = [&](auto r6) {
     constexpr bool R6 = decltype(r6)::value;
-    if (narrow) {
+    if (padres) {
+      if (ep.w_off) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, false, true, true>), DLMCQ_CONV_ARGS);
+      else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, false, true, true>), DLMCQ_CONV_ARGS);
+    } else if (narrow) {
       if (ep.w_off) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
       else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
     } else if (xoff) {
@@ -1003,6 +1050,27 @@ extern "C" int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float
   ep.kf = (int)Kf;
   return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
                      x_is_unsigned, stream, ep);
+}
+
+extern "C" int dlmcq_conv2d_i8_nhwc_padres(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                           const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                           const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R,
+                                           int64_t S, int32_t stride, int32_t pad, int32_t dilation, int32_t x_is_unsigned,
+                                           const float* res_src, int64_t res_h, int64_t res_w, int64_t res_c, int32_t res_stride,
+                                           int64_t res_clo, int32_t relu, void* codes, const float* q_scale,
+                                           const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                                           int64_t Kf, dlmcq_stream_t stream) {
+  if (K < 64 || K % 64 != 0 || Kf % 4 != 0 || Kf > K || Kf <= K - 64) return DLMCQ_EINVAL;      // (the narrow entry point's rule)
+  constexpr int64_t BIG = 1ll << 30;
+  if (!res_src || res_h < 1 || res_w < 1 || res_c < 4 || res_stride < 1 || res_clo < 0 || res_h >= BIG || res_w >= BIG || res_c >= BIG ||
+      res_clo >= BIG)
+    return DLMCQ_EINVAL;
+  ConvEpi ep = make_epi(res_src, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  ep.w_off = w_offset;
+  ep.kf = (int)Kf;
+  const PadRes pr{(int)res_h, (int)res_w, (int)res_c, res_stride, (int)res_clo};
+  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
+                     x_is_unsigned, stream, ep, nullptr, nullptr, nullptr, &pr);
 }
 
 static int make_seg2(ConvSeg2& s2, int64_t N, int64_t K, const void* x2, const int8_t* w2, const float* bias2,

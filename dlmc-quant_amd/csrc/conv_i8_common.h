@@ -30,6 +30,15 @@ __device__ __forceinline__ void row_origin(const ConvGeom& g, uint32_t m, int& n
   w0 = q * g.stride - g.pad;
 }
 
+// output row m -> image n and output pixel (p, q): what a shortcut read at a pixel stride needs (the PADRES epilogue of conv_i8.hip)
+__device__ __forceinline__ void row_npq(const ConvGeom& g, uint32_t m, int& n, int& p, int& q) {
+  const uint32_t t = fdiv(m, g.qdiv);
+  q = (int)(m - t * (uint32_t)g.Q);
+  const uint32_t nn = fdiv(t, g.pdiv);
+  p = (int)(t - nn * (uint32_t)g.P);
+  n = (int)nn;
+}
+
 struct PadTable {   // 64 bytes of every byte value: a padded tap reads its K chunks at offsets 0 / 32 of one line
   int8_t b[256 * 64];
   constexpr PadTable() : b() {

@@ -92,6 +92,9 @@ SIGNATURES = {
                                                 _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_conv2d_i8_nhwc_narrow": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                                   _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _i64, _p]),
+    "dlmcq_conv2d_i8_nhwc_padres": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                                  _i32, _i32, _i32, _i32, _p, _i64, _i64, _i64, _i32, _i64, _i32, _p, _p, _p, _i32, _i32, _i32,
+                                                  _f32, _i64, _p]),
     "dlmcq_conv2d_dw_i8_nhwc": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
                                               _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_conv2d_i8_nhwc_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,

@@ -539,6 +539,9 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
     if (in_offset is None) != (tap_sums is None):
         raise ValueError("conv2d_i8: in_offset and tap_sums go together")
     narrow = out_channels is not None
+    padres = isinstance(residual, PadShortcut)
+    if padres and not narrow:
+        raise ValueError("conv2d_i8: a PadShortcut residual goes with the narrow path only - pass out_channels (K for an unpadded layer)")
     if narrow and (observe or in_offset is not None or out_chunk_major or pipelined or isinstance(residual, ChunkMajor)):
         raise ValueError("conv2d_i8: out_channels (narrow fp32 rows) goes with none of observe, in_offset, out_chunk_major, a ChunkMajor "
                          "residual and pipelined")
@@ -575,7 +578,15 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         return out
     icm = isinstance(residual, ChunkMajor)
     ocm = bool(out_chunk_major) and out is not None and not linear
-    if residual is not None:
+    pad_args = None
+    if padres:
+        src = residual.src
+        N.require_gpu(src)
+        if residual.shape_for(int(out_channels)) != fshape:
+            raise ValueError(f"conv2d_i8: the pad shortcut gives {residual.shape_for(int(out_channels))}, the layer's fp32 output is {fshape}")
+        pad_args = (N.ptr(src), src.shape[2], src.shape[3], src.shape[1], residual.stride, residual.lo)
+        residual_elems = f_elems // int(out_channels) * src.shape[1]     # (what the kernel reads of it)
+    elif residual is not None:
         if tuple(residual.shape) != fshape or residual.dtype != torch.float32:
             raise ValueError("conv2d_i8: residual must be fp32 of the output's shape")
         if icm:
@@ -584,14 +595,17 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         if not icm:
             residual = residual.contiguous() if linear else _nhwc(residual)
     q = _quantiser(emit, alloc, codes, True, "conv2d_i8")
-    nbytes = codes.numel() + wq.numel() + f_elems * (4 * (out is not None) + 4 * (residual is not None)) + out_elems * (emit is not None)
+    nbytes = (codes.numel() + wq.numel() + f_elems * 4 * (out is not None) + out_elems * (emit is not None) +
+              4 * (residual_elems if padres else f_elems * (residual is not None)))
     flags = (N.FORCE_TILED if force_tiled else 0) | (N.PIPELINED if pipelined else 0)
     # the entry point: head, [w_offset], geometry, the epilogue, [what only this entry point takes]
     w_off, trailer, observing = (), (), False
     if in_offset is not None or w_offset is not None or narrow:
         w_offset = _flat(w_offset, codes)
         w_off = (N.ptr(w_offset),)
-    if narrow:
+    if padres:
+        fn, trailer = N.lib.dlmcq_conv2d_i8_nhwc_padres, (int(out_channels),)
+    elif narrow:
         fn, trailer = N.lib.dlmcq_conv2d_i8_nhwc_narrow, (int(out_channels),)
     elif in_offset is not None:
         fn = N.lib.dlmcq_conv2d_i8_nhwc_xoff
@@ -609,7 +623,8 @@ def conv2d_i8(codes, wq, wsum, bias, in_scale, in_zp, w_scale, stride=1, padding
         fn = N.lib.dlmcq_conv2d_i8_nhwc_fused
 
     def call(extra=0):      # (`residual` as it is when the call is made: a ChunkMajor one may be converted below)
-        return fn(*head, *w_off, *geo, N.ptr(residual), act, *_q_args(q, flags | extra), *trailer, N.stream_ptr())
+        res_args = pad_args if padres else (N.ptr(residual),)
+        return fn(*head, *w_off, *geo, *res_args, act, *_q_args(q, flags | extra), *trailer, N.stream_ptr())
     cm_bits = 0
     if icm or ocm:
         # chunk-major block tensors: only where the block-end kernel takes the call, with one layout for its fp32 tensors (the
@@ -817,6 +832,38 @@ class ChunkMajor:
 
     def record_stream(self, s):
         self.buf.record_stream(s)
+
+
+class PadShortcut:
+    """The parameter-free "option A" shortcut of He et al. 2016, section 4.2 - `F.pad(src[:, :, ::stride, ::stride], (0, 0, 0, 0, lo, hi))`,
+    subsample and zero-pad the channels - as the SOURCE tensor and two numbers instead of the padded tensor: `conv2d_i8(residual=
+    PadShortcut(src, stride, lo), out_channels=k)` reads `src` in place (dlmcq_conv2d_i8_nhwc_padres), `hi` being whatever is left of k.
+    `src`: fp32 (N, Cs, Hs, Ws), dense in channels_last memory (rows of Cs floats, no gaps), Cs % 4 == 0, lo % 4 == 0.  Deliberately NOT a
+    tensor (as ChunkMajor is not): only conv2d_i8's narrow path takes it, anything else fails loudly; `.materialise(k)` gives the tensor."""
+
+    def __init__(self, src, stride=1, lo=0):
+        if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.dtype != torch.float32:
+            raise ValueError("PadShortcut: the source is an fp32 (N, C, H, W) tensor")
+        if not src.permute(0, 2, 3, 1).is_contiguous():
+            raise ValueError("PadShortcut: the source must be dense in channels_last memory (a slice or a view with gaps is not)")
+        self.src, self.stride, self.lo = src, int(stride), int(lo)
+        if self.stride < 1 or self.lo < 0 or self.lo % 4 or src.shape[1] % 4 or src.shape[1] < 4:
+            raise ValueError("PadShortcut: stride >= 1, lo >= 0, lo % 4 == 0 and source channels % 4 == 0")
+        self.dtype, self.device = src.dtype, src.device
+
+    def shape_for(self, k):
+        """Shape of the padded shortcut at `k` channels, or None when source and leading pad do not fit into k."""
+        n, c, h, w = self.src.shape
+        s = self.stride
+        return (n, k, (h + s - 1) // s, (w + s - 1) // s) if self.lo + c <= k else None
+
+    def materialise(self, k):
+        """The shortcut as the tensor the model's own `F.pad(x[:, :, ::s, ::s], ...)` builds: fp32 (N, k, P, Q), channels_last."""
+        sub = self.src[:, :, ::self.stride, ::self.stride]
+        return torch.nn.functional.pad(sub, (0, 0, 0, 0, self.lo, k - self.lo - sub.shape[1])).contiguous(memory_format=torch.channels_last)
+
+    def record_stream(self, s):
+        self.src.record_stream(s)
 
 
 def _second_weights(b):

@@ -207,6 +207,10 @@ class _PlanLayer(nn.Module):
         # narrow fp32 rows (fuse_inference(narrow_rows=True); Int8Layer only): a channel-padded layer reads its fp32 shortcut and writes its
         # fp32 output k wide - dense, no slice on the way out - while its codes stay k_pad wide (dlmcq_conv2d_i8_nhwc_narrow)
         self.narrow = False
+        # a pad shortcut (fuse_inference(pad_shortcuts=True); Int8Layer only): (stride, leading zero channels) of an option-A shortcut
+        # `F.pad(x[:, :, ::s, ::s], (0, 0, 0, 0, lo, hi))` - the node's second argument is then the SOURCE x, read in place by the
+        # epilogue (K.PadShortcut, dlmcq_conv2d_i8_nhwc_padres: the narrow path, at k == k_pad too)
+        self.pad_shortcut = None
 
     def _fold_offset(self, tap):
         """A float activation offset o (act.xoff): `tap` [k_pad, R, S] (float64, on the device) = per output channel and tap the sum of the
@@ -382,8 +386,11 @@ class Int8Layer(_PlanLayer):
         if self.w_off is not None:
             kw["w_offset"] = self.w_off
         kw.update(self._xoff_kw())
-        if self.narrow:
+        if self.narrow or self.pad_shortcut is not None:
             kw["out_channels"] = self.k
+        if self.pad_shortcut is not None:
+            # (a plan node's output is dense channels_last already: no copy; only an NCHW-contiguous network input is converted)
+            residual = K.PadShortcut(K._nhwc(residual), *self.pad_shortcut)
         if self.relu or self.relu6 or residual is not None or emit is not None or self.w_off is not None or self.xoff_padded:
             res = K.conv2d_i8(codes, self.wq, self.wsum, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale,
                               residual=residual, act=self._act_arg(), emit=emit, want_out=self.want_out,
@@ -578,7 +585,8 @@ def _pointwise(plan):
     lay = plan.layer
     return (type(plan) is Int8Layer and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and lay.stride[0] == 1 and
             lay.padding[0] == 0 and plan.w_off is None and plan.pool is None and plan.k_pad == plan.k and plan.c_pad == plan.c and
-            not plan.act.needs_g and not plan.relu6)          # (the chain kernel: ReLU only)
+            not plan.act.needs_g and not plan.relu6 and          # (the chain kernel: ReLU only)
+            plan.pad_shortcut is None)                           # (a pad shortcut: the tiled kernel's PADRES epilogue alone reads one)
 
 
 def _chain_pass(gm, report):
@@ -872,6 +880,7 @@ def _gap_pass(gm, report, mode, planned, dry_run):
             w = info["mod"].weight
             gets = [u for u in prod.users if u.op == "call_function" and u.target is operator.getitem]
             fused = (info["kind"] == "gemm" and not info["dual"] and info["pool"] is None and info["emit"] is None and w.dim() == 4 and
+                     info.get("pad_shortcut") is None and
                      len(gets) == len(prod.users) and all(g is x or not real_users(g, inside) for g in gets) and info["spec"][5] is None and
                      K.gap_head_supported(_ceil64(w.shape[1]), w.shape[0], 1, 1, w.shape[2], info["mod"].stride[0], info["mod"].padding[0]) and
                      w.shape[2] == w.shape[3] and (mode == "fused" or K.gap_head_profitable(_ceil64(w.shape[1]), w.shape[0])))
@@ -968,6 +977,7 @@ class FusionReport:
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
         self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
         self.narrow = 0       # channel-padded layers reading / writing their fp32 tensors at the real width (fuse_inference(narrow_rows=True))
+        self.pad_shortcuts = 0   # option-A shortcuts (subsample + zero-pad) read in place by the layer's epilogue (fuse_inference(pad_shortcuts=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -977,6 +987,7 @@ class FusionReport:
                 f"pools on codes={self.pooled}, dual (conv + shortcut conv) kernels={self.dual}, chained pairs={self.chained} (fp32 outputs chunk-major: {self.chunk_major}), "
                 f"depthwise + pointwise units={self.dwpw}, " + (f"gap heads={self.gap_heads}, " if self.gap_heads else "") +
                 (f"narrow fp32 rows={self.narrow}, " if self.narrow else "") +
+                (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1030,6 +1041,41 @@ def _is_relu6(node, modules):
         return (isinstance(lo, (int, float)) and isinstance(hi, (int, float)) and not isinstance(lo, bool) and not isinstance(hi, bool)
                 and float(lo) == 0.0 and float(hi) == 6.0)
     return False
+
+
+_PAD_FNS = tuple({F.pad, torch._C._nn.pad})
+
+
+def _pad_shortcut(node):
+    """`node` as an option-A shortcut (He et al. 2016, section 4.2: subsample, zero-pad the channels) - `F.pad(t, (0, 0, 0, 0, lo, hi))`,
+    constant mode, value 0, of `t = x[:, :, ::s, ::s]` or of x itself - as (x, s, lo, hi, the nodes to erase), each node the only reader
+    of the one before; None for anything else."""
+    if node.op != "call_function" or node.target not in _PAD_FNS or len(node.users) != 1:
+        return None
+    names = ("input", "pad", "mode", "value")
+    if len(node.args) > len(names) or not set(node.kwargs) <= set(names[len(node.args):]):
+        return None
+    given = dict(zip(names, node.args), **node.kwargs)
+    t, pad, mode, value = given.get("input"), given.get("pad"), given.get("mode", "constant"), given.get("value", None)
+    if not isinstance(t, fx.Node) or not isinstance(pad, (tuple, list)) or len(pad) != 6 or mode != "constant":
+        return None
+    if not all(isinstance(v, int) and not isinstance(v, bool) for v in pad) or tuple(pad[:4]) != (0, 0, 0, 0) or pad[4] < 0 or pad[5] < 0:
+        return None
+    if not (value is None or (isinstance(value, (int, float)) and not isinstance(value, bool) and float(value) == 0.0)):
+        return None
+    # (`t[i]` with an integer i is a plan node's output, not a subscript of a tensor)
+    if not (t.op == "call_function" and t.target is operator.getitem and len(t.args) == 2 and not isinstance(t.args[1], int)):
+        return t, 1, int(pad[4]), int(pad[5]), [node]          # F.pad alone: stride 1
+    if len(t.users) != 1 or t.kwargs or not isinstance(t.args[0], fx.Node) or not isinstance(t.args[1], tuple):
+        return None
+    idx = t.args[1]
+    full = slice(None, None, None)
+    if len(idx) != 4 or idx[0] != full or idx[1] != full or not all(isinstance(i, slice) for i in idx):
+        return None
+    s = idx[2].step
+    if (idx[2].start, idx[2].stop, idx[3].start, idx[3].stop) != (None,) * 4 or not isinstance(s, int) or isinstance(s, bool) or s < 1 or idx[3].step != s:
+        return None
+    return t.args[0], s, int(pad[4]), int(pad[5]), [node, t]
 
 
 def _pool_params(node, modules):
@@ -1244,7 +1290,7 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False):
+                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1290,7 +1336,18 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     node; the chain, block-layout and fused-head passes keep requiring unpadded channels.  A padded layer with the border term of a
     float activation offset (the *_xoff kernels have no narrow form) or with k % 4 != 0 keeps its add outside.  Bit-identical to the
     plan without it (IEEE addition commutes; the codes are those of the stored value either way).  Off by default: the plan without it
-    is the plan as it was."""
+    is the plan as it was.
+    `pad_shortcuts=True`: where a foldable add's shortcut is the parameter-free "option A" one of the CIFAR ResNets -
+    `F.pad(x[:, :, ::s, ::s], (0, 0, 0, 0, lo, hi))`, constant mode, value 0 (or F.pad alone: s = 1), each node read by the next alone -
+    the layer's epilogue reads x itself at the pixel stride and the channel offset and adds +0 elsewhere (K.PadShortcut,
+    dlmcq_conv2d_i8_nhwc_padres); the slice and the pad leave the graph (`fusion_report.pad_shortcuts` counts them).  Taken for a "gemm"
+    convolution whose add folds anyway (unpadded, or narrow under `narrow_rows`), with lo % 4 == 0, x's channels % 4 == 0, lo + channels
+    + hi == the layer's channels, and x known to be dense channels_last at its real width: the fp32 output of a plan node that is
+    unpadded or narrow, or the network input (>= 4 channels; read in place when it is channels_last, else copied to channels_last
+    once per call).  Not for a layer with the border term of a float activation offset (`act_offsets`: the *_xoff kernels have no
+    narrow form).  Such a node always runs the tiled kernel's narrow epilogue and is never
+    half of a chain, chunk-major or a fused head.  Anything else keeps today's graph.  Bit-identical to the plan without it.  Off by
+    default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -1330,6 +1387,24 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             return next(iter(acts.values())) if len(acts) == 1 else None
         s = spec_of(u) if u.args and u.args[0] is t else None
         return s[0] if s is not None and s[4] in ("gemm", "dw") else None
+
+    def source_channels(src):
+        """Channels of `src` if its fp32 value is known to be dense channels_last at its real width - the fp32 output of a plan node
+        that is unpadded or narrow, or the network input as a planned convolution reads it - else None."""
+        if src.op == "call_function" and src.target is operator.getitem and src.args[1] == 0 and src.args[0] in planned:
+            info = planned[src.args[0]]
+            w = info["mod"].weight
+            ok = w.dim() == 4 and info["kind"] in ("gemm", "dw") and info["pool"] is None and (w.shape[0] % 64 == 0 or info["narrow"])
+            return int(w.shape[0]) if ok else None
+        # the network input: its width is read off a planned (ungrouped) convolution that takes it as its activation; with no such
+        # reader yet (or only readers planned later) the answer is None and nothing folds.  Dense only once it is channels_last: an
+        # NCHW-contiguous input is converted per call by Int8Layer.forward (one copy of the input, in place of the slice and the pad)
+        if src.op == "placeholder":
+            for u in src.users:
+                info = planned.get(u)
+                if info is not None and u.args[0] is src and info["mod"].weight.dim() == 4 and info["mod"].groups == 1:
+                    return int(info["mod"].weight.shape[1])
+        return None
 
     count = 0
     planned = {}       # plan node -> what was decided for it (the gap-head pass reads it; under dry_run the modules are placeholders)
@@ -1381,6 +1456,16 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
                 pool = _pool_params(mp, modules)
                 chain.append(mp)
                 last = mp
+        # ---- an option-A shortcut (pad_shortcuts): the epilogue reads its source in place ----
+        # (not for a layer with the border term of a float activation offset: it runs on the *_xoff kernels, which have no narrow form -
+        #  the exclusion `can_narrow` and `dual` carry; its add keeps folding with the materialised tensor)
+        pad_sc = None
+        if (pad_shortcuts and residual is not None and residual.op == "call_function" and
+                not (spec[0].xoff and int(modules[node.target].padding[0]) > 0)):
+            m = _pad_shortcut(residual)
+            cs = source_channels(m[0]) if m is not None else None
+            if cs is not None and m[2] % 4 == 0 and cs % 4 == 0 and cs >= 4 and m[2] + cs + m[3] == wn.shape[0]:
+                pad_sc = m
         # ---- who reads the result: int8 layers fed ONLY through their activation argument take codes ----
         consumers = {}
         fp32_needed = False
@@ -1423,6 +1508,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
                 other = from_blob(residual.target, other)
             plan = cls(modules[node.target], spec, relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
             plan.narrow = narrow
+            if pad_sc is not None:
+                plan.pad_shortcut = (pad_sc[1], pad_sc[2])
             # codes of an unsigned-byte quantiser read only by matrix-core layers (no channel padding, no pooling on the way)
             # travel re-centred (see _PlanLayer.__init__); the consumers recognise them by dtype
             def takes_shifted(u):
@@ -1440,10 +1527,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         if dual:
             args = (node.args[0], residual.args[0])
         else:
-            args = (node.args[0],) if residual is None else (node.args[0], residual)
+            args = (node.args[0],) if residual is None else (node.args[0], residual if pad_sc is None else pad_sc[0])
         with graph.inserting_after(last):
             fused = graph.call_module(name, args=args)
-        planned[fused] = dict(spec=spec, kind=spec[4], mod=modules[node.target], dual=bool(dual), pool=pool, emit=emit)
+        planned[fused] = dict(spec=spec, kind=spec[4], mod=modules[node.target], dual=bool(dual), pool=pool, emit=emit, narrow=narrow,
+                              pad_shortcut=pad_sc)
         if dual:
             dual_inputs[fused] = (spec[0], other[0])
             chain.insert(0, residual)       # erased last (its only user, the add, goes first)
@@ -1462,6 +1550,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         if dual:
             graph.erase_node(residual)
             live.discard(residual)
+        if pad_sc is not None:              # the pad, then the slice: their only readers are gone
+            for n in pad_sc[4]:
+                graph.erase_node(n)
+                live.discard(n)
+        report.pad_shortcuts += pad_sc is not None
         report.layers += 1
         report.stem += spec[4] == "stem"
         report.pooled += pool is not None

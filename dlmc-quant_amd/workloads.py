@@ -13,6 +13,7 @@ counts; tests pin the totals to SURVEY.md section 8(d):
     MobileNetV2: 53 layers, 6 767 200 input elems/img, 3 469 760 weight elems (300 774 272 MAC/img)
 """
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 
@@ -23,19 +24,32 @@ def _conv(cin, cout, k, stride=1, groups=1):
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin, width, stride):
+    def __init__(self, cin, width, stride, option="B"):
         super().__init__()
+        if option not in ("A", "B"):
+            raise ValueError(f"BasicBlock: shortcut option 'A' or 'B', not {option!r}")
         self.conv1 = _conv(cin, width, 3, stride)
         self.bn1 = nn.BatchNorm2d(width)
         self.conv2 = _conv(width, width, 3)
         self.bn2 = nn.BatchNorm2d(width)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = None
-        if stride != 1 or cin != width:
+        # where the shape changes: a 1x1 convolution + BN on the shortcut ("option B"), or no parameters at all ("option A", He et al.
+        # 2016, section 4.2): every stride-th pixel of x, the new channels zero, half of them in front and half behind
+        self.subsample = None
+        if (stride != 1 or cin != width) and option == "A":
+            if width < cin or (width - cin) % 2:
+                raise ValueError("BasicBlock: option A pads (width - cin) / 2 zero channels on either side")
+            self.subsample = (stride, (width - cin) // 2)
+        elif stride != 1 or cin != width:
             self.downsample = nn.Sequential(_conv(cin, width, 1, stride), nn.BatchNorm2d(width))
 
     def forward(self, x):
-        idt = x if self.downsample is None else self.downsample(x)
+        if self.subsample is not None:
+            s, pad = self.subsample
+            idt = F.pad(x[:, :, ::s, ::s], (0, 0, 0, 0, pad, pad), "constant", 0)
+        else:
+            idt = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + idt)
@@ -232,16 +246,18 @@ class MobileNetV2(nn.Module):
 class CifarResNet(nn.Module):
     """The CIFAR ResNet of He et al. 2016, section 4.2 (public architecture): a 3x3 first layer of 16 channels on the 32 x 32 image, three
     stages of `depth` BasicBlocks at 16 / 32 / 64 channels (stride 2 into the second and third), global average pool, linear head.  Where
-    the shape changes the shortcut is a 1x1 convolution + BN (BasicBlock's `downsample`; "option B")."""
+    the shape changes the shortcut is a 1x1 convolution + BN (BasicBlock's `downsample`; "option B") or, with `option="A"`, the paper's
+    parameter-free one: x subsampled at the stride, its channels zero-padded on both sides (what its CIFAR experiments use)."""
 
-    def __init__(self, depth, num_classes=10):
+    def __init__(self, depth, num_classes=10, option="B"):
         super().__init__()
         self.conv1 = _conv(3, 16, 3)
         self.bn1 = nn.BatchNorm2d(16)
         self.relu = nn.ReLU(inplace=True)
         cin, stages = 16, []
         for i, width in enumerate((16, 32, 64)):
-            stages.append(nn.Sequential(*[BasicBlock(cin if j == 0 else width, width, 2 if (j == 0 and i > 0) else 1) for j in range(depth)]))
+            stages.append(nn.Sequential(*[BasicBlock(cin if j == 0 else width, width, 2 if (j == 0 and i > 0) else 1, option)
+                                          for j in range(depth)]))
             cin = width
         self.layer1, self.layer2, self.layer3 = stages
         self.avgpool = nn.AdaptiveAvgPool2d(1)
@@ -286,9 +302,15 @@ def mobilenet_v2(num_classes=1000):
     return MobileNetV2(num_classes=num_classes)
 
 
-def cifar_resnet20(num_classes=10):
-    """ResNet-20 for CIFAR: 6 * 3 + 2 layers, widths 16 / 32 / 64 - every block of its first two stages has channel-padded outputs."""
-    return CifarResNet(3, num_classes)
+def cifar_resnet20(num_classes=10, option="B"):
+    """ResNet-20 for CIFAR: 6 * 3 + 2 layers, widths 16 / 32 / 64 - every block of its first two stages has channel-padded outputs.
+    `option="A"`: parameter-free shortcuts (20 layers: no shortcut convolutions)."""
+    return CifarResNet(3, num_classes, option)
+
+
+def cifar_resnet56(num_classes=10, option="B"):
+    """ResNet-56 for CIFAR: 6 * 9 + 2 layers."""
+    return CifarResNet(9, num_classes, option)
 
 
 MODELS = {"resnet18": resnet18, "resnet50": resnet50, "repvgg_a1": repvgg_a1_deploy, "mobileone_s1": mobileone_s1_deploy,

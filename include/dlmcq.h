@@ -530,6 +530,29 @@ int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float* out, cons
                                 void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                 int32_t q_form, float q_ste_g, int64_t Kf, dlmcq_stream_t stream);
 
+/* Pad shortcut: dlmcq_conv2d_i8_nhwc_narrow whose shortcut is not a tensor of the output's shape but the SOURCE of a parameter-free
+ * "option A" shortcut (He et al. 2016, section 4.2: subsample, zero-pad the channels)
+ *     shortcut = pad(res_src[:, ::res_stride, ::res_stride, :], res_clo zero channels in front, Kf - res_clo - res_c behind)
+ * read in place by the epilogue - the padded tensor is never written or read back.
+ *   res_src   fp32 [N, res_h, res_w, res_c], DENSE (rows of res_c floats, no gaps), 16-byte aligned (DLMCQ_EALIGN otherwise), not NULL
+ *   output row (n, p, q), fp32 column col < Kf:   r = res_src[n, p * res_stride, q * res_stride, col - res_clo]
+ *             where res_clo <= col < res_clo + res_c, and r = +0.0f elsewhere.  The addition v + r IS performed for the zero columns as
+ *             well (-0 + +0 = +0, exactly what adding the materialised padding gives); columns Kf .. K - 1 get no addition and no
+ *             fp32 store, as in _narrow.  Everything behind the addition is _narrow's order: ReLU / ReLU6, store, quantiser.
+ * DLMCQ_EINVAL for anything _narrow refuses and for: res_src == NULL; res_stride < 1; res_h or res_w < 1; P != ceil(res_h / res_stride)
+ * or Q != ceil(res_w / res_stride) (the condition under which no output pixel reads outside the source); res_c < 4; res_c % 4 != 0;
+ * res_clo % 4 != 0; res_clo < 0; res_clo + res_c > Kf (multiples of 4 keep every shortcut access a 16-byte one: a quad is wholly inside
+ * the source or wholly zero); DLMCQ_PIPELINED or either DLMCQ_FP32_*_CHUNK_MAJOR bit.  w_offset == NULL selects symmetric weights.
+ * Always conv_i8_mfma_kernel (its PADRES instantiations): DLMCQ_ROUTE_ONLY answers DLMCQ_ROUTE_TILED and launches nothing,
+ * DLMCQ_FORCE_TILED changes nothing, DLMCQ_EMIT_SHIFT128 as in _fused.  Bit for bit what _narrow gives on the materialised shortcut. */
+int dlmcq_conv2d_i8_nhwc_padres(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                const float* in_scale, const float* in_zero_point, const float* w_scale, const float* w_offset,
+                                int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride,
+                                int32_t pad, int32_t dilation, int32_t x_is_unsigned, const float* res_src, int64_t res_h,
+                                int64_t res_w, int64_t res_c, int32_t res_stride, int64_t res_clo, int32_t relu, void* codes,
+                                const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                                float q_ste_g, int64_t Kf, dlmcq_stream_t stream);
+
 /* Depthwise 3x3 convolution (groups = channels; the MobileOne / MobileNet unit, modules/conv.py:13-19 with `groups`) on
  * activation codes, HBM-bound (1 byte in, 1 byte out): plain vector arithmetic, no matrix cores.  x: NHWC codes (uint8 if
  * x_is_unsigned), C % 4 == 0; w: int8 codes [R*S][C] (tap-major); per-channel w_scale and optional w_offset (asymmetric
