@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1100,6 +1100,50 @@ def global_avgpool(x, emit=None, want_out=True):
     PROFILE.launch("gap", x.numel() * 4 + n * c * (4 * want_out + (emit is not None)), lambda: N.check(N.lib.dlmcq_gap_nhwc_f32(
         N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h * w_, c, *_q_args(q)[1:], N.stream_ptr())))
     return (out, q[0]) if emit is not None else out
+
+
+def _nhwc_rows(x):
+    """Floats per pixel if 4-D `x` can be read in place as NHWC rows - channels_last memory, or a channel slice `t[:, :c]` of a
+    channels_last tensor (rows wider than the data, a multiple of 4 floats, 16-byte aligned) - else None."""
+    n, c, h, w = x.shape
+    xs = x.stride(3)
+    ok = (h > 1 and w > 1 and x.stride(1) == 1 and xs >= c and xs % 4 == 0 and x.stride(2) == w * xs and
+          (n == 1 or x.stride(0) == h * w * xs) and x.data_ptr() % 16 == 0)
+    return xs if ok else None
+
+
+def avgpool_quant(x, window, emit=None, want_out=True, c_pad=None, pad_code=0):
+    """nn.AvgPool2d(window, window) (no padding, floor) of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_avgpool_nhwc_f32: a
+    sequential fp32 sum from +0 in row-major window order and a true division (torch's own loop: the pooled values are bit-identical to
+    F.avg_pool2d(x, window)).  `x` is read in place when it is channels_last or a channel slice of a channels_last tensor, else copied to
+    channels_last.  Returns `(pooled or None, codes or None)`, both channels_last: fp32 (N, C, H // window, W // window) unless
+    `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the pooled values, `c_pad` channels wide
+    (default C), channels C .. c_pad - 1 holding the byte `pad_code` (the consumer's zero point; code 0 under a float activation
+    offset; either minus 128 with `emit.shift128`)."""
+    N.require_gpu(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("avgpool_quant: an fp32 (N, C, H, W) tensor")
+    if not want_out and emit is None:
+        raise ValueError("avgpool_quant: nothing to produce (want_out=False without emit)")
+    n, c, h, w_ = x.shape
+    c_pad = c if c_pad is None else int(c_pad)
+    if c_pad != c and emit is None:
+        raise ValueError("avgpool_quant: c_pad pads the code rows (emit=None writes none)")
+    s = int(window)
+    xs = _nhwc_rows(x)
+    if xs is None:
+        x = _nhwc(x)
+        xs = c
+    p, q_ = (h // s, w_ // s) if s > 0 else (0, 0)
+
+    def alloc(dtype, ch=c_pad):
+        return torch.empty((n, ch, p, q_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
+    out = alloc(torch.float32, c) if want_out else None
+    q = _quantiser(emit, alloc, x, True, "avgpool_quant")
+    m = n * p * q_
+    PROFILE.launch("avgpool", m * (c * (4 * s * s + 4 * want_out) + c_pad * (emit is not None)), lambda: N.check(N.lib.dlmcq_avgpool_nhwc_f32(
+        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, s, c_pad, int(pad_code), *_q_args(q)[1:], N.stream_ptr())))
+    return out, q[0]
 
 
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):

@@ -32,7 +32,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -761,6 +761,122 @@ class GapHeadLayer(nn.Module):
                                residual=residual, act=a._act_arg(), emit=emit, want_out=self.want_out)
 
 
+class AvgPoolLayer(nn.Module):
+    """A windowed average pool (nn.AvgPool2d(s, s) / F.avg_pool2d(x, s): window = stride, no padding, floor) of an fp32 map straight to
+    the activation codes of the plan layers that read it (csrc/avgpool.hip) - the shortcut of a ResNet-C / -D block: the pool, the pooled
+    fp32 tensor and the consumer's quantise pass as one read of the map.  `emit`: the readers' activation quantiser (_ActSpec); the code
+    rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32 tensor.
+    Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, window, emit, want_out, c, c_pad, pad_code, shift=False):
+        super().__init__()
+        self.window, self.emit, self.want_out = int(window), emit, bool(want_out)
+        self.c, self.c_pad, self.pad_code, self.emit_shift = int(c), int(c_pad), int(pad_code), bool(shift)
+
+    def forward(self, x):
+        n, c, h, w = x.shape
+        s = self.window
+        e = self.emit.emit(n * c * (h // s) * (w // s))       # (a QBase consumer's g: over its real input, the pooled tensor)
+        e.shift128 = self.emit_shift
+        return K.avgpool_quant(x, s, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+
+
+_AVGPOOL_NAMES = ("input", "kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override")
+
+
+def _avgpool_window(node, modules):
+    """(input node, s) if `node` is an average pool the plan runs - nn.AvgPool2d or F.avg_pool2d in any argument spelling, the kernel a
+    Python int or an equal pair in 2 .. 8, the stride None or equal to the kernel, padding 0, ceil_mode False, divisor_override None -
+    else None (a kernel size read from the tensor, as in F.avg_pool2d(x, x.size(3)), is a graph node, not an int)."""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        if type(m) is not nn.AvgPool2d or len(node.args) != 1 or node.kwargs:
+            return None
+        given = dict(input=node.args[0], kernel_size=m.kernel_size, stride=m.stride, padding=m.padding, ceil_mode=m.ceil_mode,
+                     divisor_override=m.divisor_override)
+    elif node.op == "call_function" and node.target in (F.avg_pool2d, torch._C._nn.avg_pool2d):
+        if len(node.args) > len(_AVGPOOL_NAMES) or not set(node.kwargs) <= set(_AVGPOOL_NAMES[len(node.args):]):
+            return None
+        given = dict(zip(_AVGPOOL_NAMES, node.args), **node.kwargs)
+    else:
+        return None
+
+    def one(v):      # an int, or a pair of equal ints
+        if isinstance(v, (tuple, list)) and len(v) in (1, 2) and len(set(v)) == 1:
+            v = v[0]
+        return v if isinstance(v, int) and not isinstance(v, bool) else None
+    x, k = given.get("input"), one(given.get("kernel_size"))
+    stride, pad = given.get("stride"), given.get("padding", 0)
+    if not isinstance(x, fx.Node) or k is None or not 2 <= k <= 8:
+        return None
+    if not (stride is None or (isinstance(stride, (tuple, list)) and len(stride) == 0) or one(stride) == k):
+        return None
+    if one(pad) != 0 or given.get("ceil_mode", False) is not False or given.get("divisor_override") is not None:
+        return None
+    return x, k
+
+
+def _avgpool_pass(gm, report, planned, dry_run):
+    """Windowed average pools (fuse_inference(avg_pools=True)): `AvgPool2d(s, s) -> plan convolution` becomes a node that hands the
+    convolution its activation codes (AvgPoolLayer).  `planned`: plan node -> what the main pass decided for it; whatever that is for
+    the convolution behind the pool (dual operand, own node, narrow, chain) stays - only its input changes, from fp32 to codes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+
+    def reader(u, pool):
+        """(activation spec, convolution) with which plan node `u` reads `pool` as codes, else None."""
+        info = planned.get(u)
+        if info is None or info["kind"] != "gemm":
+            return None
+        if info["dual"]:
+            ops = [(info["dual_inputs"][i], (info["mod"], info["dual_mod"])[i]) for i in (0, 1) if u.args[i] is pool]
+            if not ops or len({a.key for a, _ in ops}) != 1:
+                return None
+        elif u.args[0] is pool and pool not in u.args[1:]:
+            ops = [(info["spec"][0], info["mod"])]
+        else:
+            return None
+        a, m = ops[0]
+        return (a, m) if m.weight.dim() == 4 and m.groups == 1 and all(mm.weight.shape[1] == m.weight.shape[1] for _, mm in ops) else None
+
+    for pool in list(graph.nodes):
+        win = _avgpool_window(pool, modules)
+        if win is None:
+            continue
+        x, s = win
+        readers = {u: reader(u, pool) for u in pool.users}
+        takers = [u for u, r in readers.items() if r is not None]
+        if not takers or len({readers[u][0].key for u in takers}) != 1:      # (the max-pool rule: one quantiser for all code readers)
+            continue
+        emit, conv = readers[takers[0]]
+        c = int(conv.weight.shape[1])
+        if c % 4 or c < 4 or any(int(readers[u][1].weight.shape[1]) != c for u in takers):
+            continue
+        c_pad = _ceil64(c)
+        # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (the main
+        # pass's takes_shifted: no channel padding; a dual node is never handed shifted codes there either)
+        shift = bool(0 <= emit.lo and emit.hi <= 255 and c_pad == c and not any(planned[u]["dual"] for u in takers))
+        zp_fill = 0 if (emit.xoff or emit.zp is None) else int(float(emit.zp.reshape(-1)[0]))      # Int8Layer's _zp_fill (read once)
+        want_out = len(takers) != len(readers)
+        name = f"_int8_avgpool_{count}"
+        count += 1
+        gm.add_module(name, _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, zp_fill - (128 if shift else 0), shift))
+        with graph.inserting_after(pool):
+            node = graph.call_module(name, args=(x,))
+        with graph.inserting_after(node):
+            out = graph.call_function(operator.getitem, (node, 0))
+            codes = graph.call_function(operator.getitem, (node, 1))
+        for u in list(pool.users):
+            u.replace_input_with(pool, codes if u in takers else out)
+        graph.erase_node(pool)
+    report.avg_pools = count
+    if count:
+        graph.eliminate_dead_code()
+        graph.lint()
+        gm.recompile()
+
+
 def _pool_dims(node, modules):
     """Rank of the result (4: keeps [N, C, 1, 1]; 2: [N, C]) if `node` is a global average pool in a spelling the plan folds -
     nn.AdaptiveAvgPool2d(1 | (1, 1)), F.adaptive_avg_pool2d(x, 1 | (1, 1)), x.mean((2, 3)) / torch.mean(x, (2, 3)) / [2, 3] / dim=,
@@ -978,6 +1094,7 @@ class FusionReport:
         self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
         self.narrow = 0       # channel-padded layers reading / writing their fp32 tensors at the real width (fuse_inference(narrow_rows=True))
         self.pad_shortcuts = 0   # option-A shortcuts (subsample + zero-pad) read in place by the layer's epilogue (fuse_inference(pad_shortcuts=True))
+        self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -988,6 +1105,7 @@ class FusionReport:
                 f"depthwise + pointwise units={self.dwpw}, " + (f"gap heads={self.gap_heads}, " if self.gap_heads else "") +
                 (f"narrow fp32 rows={self.narrow}, " if self.narrow else "") +
                 (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
+                (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1290,7 +1408,7 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False):
+                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1347,7 +1465,25 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     once per call).  Not for a layer with the border term of a float activation offset (`act_offsets`: the *_xoff kernels have no
     narrow form).  Such a node always runs the tiled kernel's narrow epilogue and is never
     half of a chain, chunk-major or a fused head.  Anything else keeps today's graph.  Bit-identical to the plan without it.  Off by
-    default: the plan without it is the plan as it was."""
+    default: the plan without it is the plan as it was.
+    `avg_pools=True`: a windowed average pool in front of plan convolutions - the shortcut of a ResNet-C / -D block
+    (`workloads.CifarResNet(3, option="C")`), a DenseNet transition, an "anti-aliased" downsample - becomes a plan node (AvgPoolLayer,
+    csrc/avgpool.hip) that hands those convolutions their activation codes; the pooled fp32 tensor and the consumer's quantise pass
+    leave the step (`fusion_report.avg_pools` counts the nodes).  Taken: nn.AvgPool2d / F.avg_pool2d in any argument spelling with the
+    kernel a Python int or an equal pair in 2 .. 8, stride None or equal to the kernel, padding 0, ceil_mode False, divisor_override
+    None, read by at least one "gemm" plan convolution through its activation argument (as its own node or as either operand of a dual
+    node) whose input channels are a multiple of 4, all such readers sharing one activation quantiser (the max-pool rule).  The codes
+    are as wide as the readers take them (padded to 64 with their zero point, or code 0 under a float activation offset), shifted
+    where every reader takes shifted codes, a QBase reader's g taken over the pooled tensor; other readers of the pool get the pooled
+    fp32 tensor from the same launch.  Whatever the main pass decided for the convolution behind the pool - dual operand, own node,
+    narrow, chain - stays; only its input changes.  Left as they are: a pool with no plan-eligible reader or with readers of different
+    quantisers, a kernel size read from the tensor (F.avg_pool2d(x, x.size(3))), ceil_mode=True, any padding, stride != kernel,
+    divisor_override, pools in front of depthwise or first-layer kernels.  The kernel sums each window sequentially from +0 in
+    row-major order and divides once - torch's own loop - so the plan is bit-identical to the plan without the flag
+    (tests/test_gpu_avgpool.py: torch.equal against F.avg_pool2d on the device and between the two plans' logits).  Measured (tools/avgpool_shortcut_ab.py,
+    profiles/avgpool_shortcut_ab.json; ResNet-20 / -56, options C / D, FSPTQ and QBase, batch 512 at 32^2, interleaved): flag off / flag on =
+    0.976 ... 1.103 in ms per step, no case slower beyond the run-to-run spread.
+    Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -1534,6 +1670,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
                               pad_shortcut=pad_sc)
         if dual:
             dual_inputs[fused] = (spec[0], other[0])
+            planned[fused].update(dual_inputs=dual_inputs[fused], dual_mod=modules[residual.target])
             chain.insert(0, residual)       # erased last (its only user, the add, goes first)
             specs[residual.target] = None   # never planned on its own
             report.layers += 1
@@ -1568,6 +1705,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     graph.eliminate_dead_code()
     graph.lint()
     gm.recompile()
+    if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
+        _avgpool_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and not dry_run:

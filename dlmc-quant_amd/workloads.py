@@ -26,8 +26,8 @@ class BasicBlock(nn.Module):
 
     def __init__(self, cin, width, stride, option="B"):
         super().__init__()
-        if option not in ("A", "B"):
-            raise ValueError(f"BasicBlock: shortcut option 'A' or 'B', not {option!r}")
+        if option not in ("A", "B", "C", "D"):
+            raise ValueError(f"BasicBlock: shortcut option 'A', 'B', 'C' or 'D', not {option!r}")
         self.conv1 = _conv(cin, width, 3, stride)
         self.bn1 = nn.BatchNorm2d(width)
         self.conv2 = _conv(width, width, 3)
@@ -41,6 +41,12 @@ class BasicBlock(nn.Module):
             if width < cin or (width - cin) % 2:
                 raise ValueError("BasicBlock: option A pads (width - cin) / 2 zero channels on either side")
             self.subsample = (stride, (width - cin) // 2)
+        elif option == "D" or ((stride != 1 or cin != width) and option == "C"):
+            # "option C": the stride moves from the 1x1 convolution into an average pool in front of it (nn.AvgPool2d(stride, stride), the
+            # ResNet-D / "anti-aliased" downsample); "option D": the same, and a 1x1 convolution + BN on every stride-1 shortcut as well
+            # (cifarresnet.py:57-87)
+            pool = [nn.AvgPool2d(kernel_size=stride, stride=stride)] if stride != 1 else []
+            self.downsample = nn.Sequential(*pool, _conv(cin, width, 1), nn.BatchNorm2d(width))
         elif stride != 1 or cin != width:
             self.downsample = nn.Sequential(_conv(cin, width, 1, stride), nn.BatchNorm2d(width))
 
@@ -247,7 +253,9 @@ class CifarResNet(nn.Module):
     """The CIFAR ResNet of He et al. 2016, section 4.2 (public architecture): a 3x3 first layer of 16 channels on the 32 x 32 image, three
     stages of `depth` BasicBlocks at 16 / 32 / 64 channels (stride 2 into the second and third), global average pool, linear head.  Where
     the shape changes the shortcut is a 1x1 convolution + BN (BasicBlock's `downsample`; "option B") or, with `option="A"`, the paper's
-    parameter-free one: x subsampled at the stride, its channels zero-padded on both sides (what its CIFAR experiments use)."""
+    parameter-free one: x subsampled at the stride, its channels zero-padded on both sides (what its CIFAR experiments use).  `option="C"`:
+    an average pool at the stride, then a 1x1 / stride 1 convolution + BN; `option="D"`: C, and a 1x1 convolution + BN on every stride-1
+    shortcut too (cifarresnet.py:57-87)."""
 
     def __init__(self, depth, num_classes=10, option="B"):
         super().__init__()
@@ -302,15 +310,24 @@ def mobilenet_v2(num_classes=1000):
     return MobileNetV2(num_classes=num_classes)
 
 
+def _named_option(option):
+    # the named CIFAR networks are the ones they were: options "A" and "B" (tests/test_pad_shortcut_host.py pins that anything else is
+    # refused here); the average-pooled shortcuts "C" / "D" are built with CifarResNet(depth, option=...) itself
+    if option not in ("A", "B"):
+        raise ValueError(f"cifar_resnet20 / cifar_resnet56: shortcut option 'A' or 'B', not {option!r} (CifarResNet(depth, option=...) takes 'C' and 'D')")
+    return option
+
+
 def cifar_resnet20(num_classes=10, option="B"):
     """ResNet-20 for CIFAR: 6 * 3 + 2 layers, widths 16 / 32 / 64 - every block of its first two stages has channel-padded outputs.
-    `option="A"`: parameter-free shortcuts (20 layers: no shortcut convolutions)."""
-    return CifarResNet(3, num_classes, option)
+    `option="A"`: parameter-free shortcuts (20 layers: no shortcut convolutions).  (Average-pooled shortcuts: CifarResNet(3, option="C" / "D"),
+    22 / 29 layers.)"""
+    return CifarResNet(3, num_classes, _named_option(option))
 
 
 def cifar_resnet56(num_classes=10, option="B"):
     """ResNet-56 for CIFAR: 6 * 9 + 2 layers."""
-    return CifarResNet(9, num_classes, option)
+    return CifarResNet(9, num_classes, _named_option(option))
 
 
 MODELS = {"resnet18": resnet18, "resnet50": resnet50, "repvgg_a1": repvgg_a1_deploy, "mobileone_s1": mobileone_s1_deploy,

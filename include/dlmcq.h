@@ -779,6 +779,27 @@ int dlmcq_conv2d_i8_nhwc_gap(const void* x, const int8_t* w, float* pooled, cons
                              void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                              int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- windowed average pool (nn.AvgPool2d(s, s): window = stride, no padding, floor): fp32 and / or the consumer's activation codes ----
+ * For image n, output pixel (p, q), channel c, with s = window, P = H / s, Q = W / s (floor: trailing rows / columns are dropped):
+ *     a = +0.0f;  for dy = 0 .. s-1: for dx = 0 .. s-1: a = fl32(a + x[n, p*s + dy, q*s + dx, c]);  pooled = fl32(a / fl32(s*s))
+ *     code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused; DLMCQ_EMIT_SHIFT128 accepted) of pooled - the code
+ *            dlmcq_fake_quant_f32 gives for it
+ * A sequential fp32 sum from +0 in row-major window order and a true IEEE division - the loop of torch's avg_pool2d, bit for bit; no
+ * atomics, no scratch: the result depends neither on the launch geometry nor on the run.
+ *   x        fp32 [N, H, W, x_stride] row-major, of which channels 0 .. C - 1 are read (x_stride >= C, x_stride % 4 == 0: the channel
+ *            slice of a wider NHWC tensor is read in place), 16-byte aligned
+ *   pooled   fp32 [N, P, Q, C] dense, 16-byte aligned, or NULL
+ *   codes    bytes [N, P, Q, c_pad], 4-byte aligned, or NULL (needs q_scale); c_pad >= C, c_pad % 4 == 0; channels C .. c_pad - 1 receive
+ *            the byte `pad_code` (-128 .. 255, its low 8 bits are stored as given: the caller passes the consumer's zero point, code 0
+ *            under a float activation offset, or either minus 128 beside DLMCQ_EMIT_SHIFT128)
+ * DLMCQ_EINVAL: window < 2, window > 8, H < window, W < window, C < 4, C % 4, x_stride < C, x_stride % 4, c_pad < C, c_pad % 4, pad_code
+ * outside -128 .. 255, both outputs NULL, c_pad != C without codes, an invalid quantiser, any control or layout bit in q_form (refused,
+ * not stripped).  DLMCQ_EALIGN: x / pooled not 16-byte aligned, codes not 4-byte aligned.  DLMCQ_ERANGE: N * P * Q * c_pad / 4 or H * W
+ * reaches 2^31.  N == 0: DLMCQ_OK, nothing launched. */
+int dlmcq_avgpool_nhwc_f32(const float* x, float* pooled, void* codes, int64_t N, int64_t H, int64_t W, int64_t C, int64_t x_stride,
+                           int64_t window, int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point,
+                           int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
