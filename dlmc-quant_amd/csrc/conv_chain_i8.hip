@@ -44,6 +44,17 @@ struct ChainArgs {
   const float* zp_in2;
   int shift2, P, Q, H2, W2, stride2;
   FastDiv qdiv, pdiv;
+  // the shortcut RECOMPUTED (CA > 0; the second block of a stage): it is the output relu?(conv1x1(xa, wa) + conv1x1(xb sampled, wb)) of the
+  // stage's first, convolution-shortcut block, whose operands are handed over instead of its fp32 tensor.  The sampled operand (xb, wb, ...)
+  // travels in the x2 / w2 / ... fields above, the unit-stride one here: xa codes [M][CA], wa [KD][CA]
+  const int8_t* xa;
+  const int8_t* wa;
+  const float* s_wa;
+  const int32_t* wsuma;
+  const float* biasa;
+  const float* s_ina;
+  const float* zp_ina;
+  int shifta, relu_sc;
   float* out;              // fp32 [M][KD] or null
   uint8_t* codes;          // [M][KD] or null
   // GEMM 2: the next 1x1 reduction.  w3 [KB][KD] int8; its input quantiser is ep1's (scale, zero point)
@@ -84,16 +95,23 @@ constexpr int CH_BIG = 0x7fff0000;   // a byte offset beyond every buffer this k
 // from the arguments at run time (the general form; the plan's launches are all ReLU ones).  A run-time flag is a uniform branch per
 // group of 4 values - five per group with the quantiser's, each a bubble in a wave's issue and a basic-block boundary the scheduler
 // cannot move work across.
-template <int C1, int KB, int C2 = 0, int FL = -1>
-__global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_kernel(ChainArgs a, ConvEpi ep1, ConvEpi ep2) {
+// CA, CB (round 6): the shortcut is neither loaded nor a convolution of this block but the PREVIOUS block's output, recomputed per chunk from
+// that block's two code operands (CA, CB channels; C2 = 0) with the convolution-shortcut form's own instructions in its own order - the
+// same fp32 values bit for bit, for 2 x 64 B of codes per pixel instead of 1 KB of fp32 (LABNOTES 17)
+template <int C1, int KB, int C2 = 0, int FL = -1, int CA = 0, int CB = 0>
+__global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_chain_i8_kernel(ChainArgs a, ConvEpi ep1, ConvEpi ep2) {
   constexpr bool DUALH = C2 > 0;         // the shortcut is a second convolution (no fp32 shortcut tensor)
+  constexpr bool RC = CA > 0;            // the shortcut is recomputed from the previous block's operands (no fp32 shortcut tensor)
+  static_assert(!RC || (C2 == 0 && CB > 0 && FL >= 0), "the recomputing form: two operands, no convolution shortcut of its own, flags known");
+  constexpr int SA = CA / 64, SB = CB / 64;   // K steps of the two recomputed reductions
+  constexpr int W3U = C1 / 64 + C2 / 64 + SA + SB;   // the 4 KB unit of a chunk's weights at which W3's piece starts
   const bool relu1 = FL < 0 ? ep1.relu != 0 : (FL & 1) != 0;
   const bool out1 = FL < 0 ? a.out != nullptr : (FL & 2) != 0;
   constexpr int S1 = C1 / 64;            // K steps of GEMM 1
   constexpr int S2 = C2 / 64;            // K steps of the shortcut convolution
   constexpr int U3 = KB / 64;            // 64-row units of a W3 chunk = accumulator slabs of GEMM 2 per wave (KB/2 columns)
-  constexpr int WCH = (S1 + S2 + U3) * 4096;  // bytes of one chunk's weights
-  constexpr int NPD = DUALH ? 2 : 1;     // constant-table DMAs per wave per chunk
+  constexpr int WCH = (W3U + U3) * 4096;  // bytes of one chunk's weights: W1 | W2 | Wa | Wb | W3
+  constexpr int NPD = DUALH ? 2 : RC ? 3 : 1;     // constant-table DMAs per wave per chunk
   constexpr int PAR = NPD * 4 * 256;     // per-channel constants of one chunk ((scale, code sum, bias) per pair) x 64 columns
   // How the accumulator layout (lane = channel, register = row) becomes rows of 4 consecutive channels per lane (TF):
   //   0  two DPP exchange rounds inside each quad (8 v_mov_dpp + 8 v_cndmask per 4 values).  The quad structure then dictates which
@@ -183,6 +201,19 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
       for (int s = 0; s < S2; ++s)
         __builtin_amdgcn_global_load_lds((gptr_t)(xp2 + s * 64), (lptr_t)(lds + WCH + (S1 + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
     }
+    if constexpr (RC) {      // the previous block's operands: xa row for row like x, xb sampled like the convolution shortcut's x2
+      const int8_t* xpa = a.xa + (row0 + (lrw < rows_here ? lrw : rows_here - 1)) * CA + sgw;
+#pragma unroll
+      for (int s = 0; s < SA; ++s)
+        __builtin_amdgcn_global_load_lds((gptr_t)(xpa + s * 64), (lptr_t)(lds + WCH + (S1 + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
+      const uint32_t m = (uint32_t)(row0 + (lrw < rows_here ? lrw : rows_here - 1));
+      const uint32_t t = fdiv(m, a.qdiv), nn = fdiv(t, a.pdiv);
+      const int q = (int)(m - t * (uint32_t)a.Q), pp = (int)(t - nn * (uint32_t)a.P);
+      const int8_t* xpb = a.x2 + (((int64_t)nn * a.H2 + pp * a.stride2) * a.W2 + q * a.stride2) * CB + sgw;
+#pragma unroll
+      for (int s = 0; s < SB; ++s)
+        __builtin_amdgcn_global_load_lds((gptr_t)(xpb + s * 64), (lptr_t)(lds + WCH + (S1 + SA + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
+    }
   }
   // GEMM 2's epilogue constants, once per workgroup (its accumulator is kept with the operands swapped - weights as A, the
   // code tile as B - so a lane owns 16 consecutive channels of one pixel and reads their constants as broadcast ds_read_b128)
@@ -198,6 +229,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
   i32x4 af[S1][2];
   i32x4 af2[DUALH ? S2 : 1][2];
+  i32x4 afa[RC ? SA : 1][2], afb[RC ? SB : 1][2];   // the recomputed reductions' A fragments: once per tile, like af2
   {
     const int r = wr * 32 + l31;
     const int8_t* ab = lds + WCH + r * 64;
@@ -217,6 +249,23 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
         for (int ks = 0; ks < 2; ++ks) {
           const i32x4 t = *reinterpret_cast<const i32x4*>(ab + (S1 + s) * 4096 + (((ks * 2 + hsel) ^ ((r >> 2) & 3)) << 4));
           af2[s][ks] = i32x4{(int)(t.x ^ xw2), (int)(t.y ^ xw2), (int)(t.z ^ xw2), (int)(t.w ^ xw2)};
+        }
+    }
+    if constexpr (RC) {
+      const uint32_t xwa = a.shifta ? 0x80808080u : 0u, xwb = a.shift2 ? 0x80808080u : 0u;
+#pragma unroll
+      for (int s = 0; s < SA; ++s)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const i32x4 t = *reinterpret_cast<const i32x4*>(ab + (S1 + s) * 4096 + (((ks * 2 + hsel) ^ ((r >> 2) & 3)) << 4));
+          afa[s][ks] = i32x4{(int)(t.x ^ xwa), (int)(t.y ^ xwa), (int)(t.z ^ xwa), (int)(t.w ^ xwa)};
+        }
+#pragma unroll
+      for (int s = 0; s < SB; ++s)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const i32x4 t = *reinterpret_cast<const i32x4*>(ab + (S1 + SA + s) * 4096 + (((ks * 2 + hsel) ^ ((r >> 2) & 3)) << 4));
+          afb[s][ks] = i32x4{(int)(t.x ^ xwb), (int)(t.y ^ xwb), (int)(t.z ^ xwb), (int)(t.w ^ xwb)};
         }
     }
   }
@@ -259,7 +308,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
   // the output's offsets: the shortcut's, unless the two tensors differ in layout (one row-major, one chunk-major: a chain between a
   // kernel that does not know the chunk-major form and one that does).  The instantiation that sits at its register limit has no room
   // for a second set: chain_launch refuses mixed layouts for it.
-  constexpr bool MIXED_OK = !DUALH && !(C1 == 128 && KB == 128);
+  constexpr bool MIXED_OK = !DUALH && !RC && !(C1 == 128 && KB == 128);
   int fo2[MIXED_OK ? 4 : 1];
   const int cstep2 = a.o_cstep;
   if constexpr (MIXED_OK) {
@@ -298,6 +347,11 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
   const int8_t* w2p = DUALH ? a.w2 + (int64_t)drow * C2 + dseg : nullptr;
   const void* const pars2[4] = {a.s_w2, a.wsum2, a.bias2 ? (const void*)a.bias2 : (const void*)a.s_w2, a.s_w2};
   const int32_t* parp2 = static_cast<const int32_t*>(wave == 0 ? pars2[0] : wave == 1 ? pars2[1] : wave == 2 ? pars2[2] : pars2[3]) + lane;
+  // the recomputed shortcut's weights and tables: Wa in units S1.., Wb behind it; tables 1 (a) and 2 (b) of the chunk's NPD = 3
+  const int8_t* wap = RC ? a.wa + (int64_t)drow * CA + dseg : nullptr;
+  const int8_t* wbp = RC ? a.w2 + (int64_t)drow * CB + dseg : nullptr;
+  const void* const parsa[4] = {a.s_wa, a.wsuma, a.biasa ? (const void*)a.biasa : (const void*)a.s_wa, a.s_wa};
+  const int32_t* parpa = static_cast<const int32_t*>(wave == 0 ? parsa[0] : wave == 1 ? parsa[1] : wave == 2 ? parsa[2] : parsa[3]) + lane;
 
   f32x4 res[2][4];
 #ifdef DLMCQ_LAB
@@ -321,7 +375,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
     for (int u = 0; u < U3; ++u)
       if (wdma) {
         const int8_t* src = w3p + (int64_t)u * 64 * a.w3_row + (int64_t)n * a.w3_chunk;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wb + (S1 + S2 + u) * 4096 + wave * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wb + (W3U + u) * 4096 + wave * 1024), 16, 0, 0);
       }
     __builtin_amdgcn_global_load_lds((gptr_t)(parp + n * 64), (lptr_t)(par0 + P * PAR + wave * 256), 4, 0, 0);
     if constexpr (DUALH) {
@@ -329,6 +383,17 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
       for (int s = 0; s < S2; ++s)
         if (wdma) __builtin_amdgcn_global_load_lds((gptr_t)(w2p + (int64_t)n * 64 * C2 + s * 64), (lptr_t)(wb + (S1 + s) * 4096 + wave * 1024), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((gptr_t)(parp2 + n * 64), (lptr_t)(par0 + P * PAR + 1024 + wave * 256), 4, 0, 0);
+      return;      // no fp32 shortcut tile
+    }
+    if constexpr (RC) {
+#pragma unroll
+      for (int s = 0; s < SA; ++s)
+        if (wdma) __builtin_amdgcn_global_load_lds((gptr_t)(wap + (int64_t)n * 64 * CA + s * 64), (lptr_t)(wb + (S1 + s) * 4096 + wave * 1024), 16, 0, 0);
+#pragma unroll
+      for (int s = 0; s < SB; ++s)
+        if (wdma) __builtin_amdgcn_global_load_lds((gptr_t)(wbp + (int64_t)n * 64 * CB + s * 64), (lptr_t)(wb + (S1 + SA + s) * 4096 + wave * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(parpa + n * 64), (lptr_t)(par0 + P * PAR + 1024 + wave * 256), 4, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(parp2 + n * 64), (lptr_t)(par0 + P * PAR + 2048 + wave * 256), 4, 0, 0);
       return;      // no fp32 shortcut tile
     }
 #pragma unroll
@@ -355,8 +420,10 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
   const float sin1 = a.s_in1[0];
   const float zpf1 = a.zp_in1 ? a.zp_in1[0] : 0.0f;
   const int dz1 = a.shift1 - (int)__builtin_rintf(zpf1);
-  const float sin1b = DUALH ? a.s_in2[0] : 0.0f;
-  const int dz1b = DUALH ? a.shift2 - (int)__builtin_rintf(a.zp_in2 ? a.zp_in2[0] : 0.0f) : 0;
+  const float sin1b = (DUALH || RC) ? a.s_in2[0] : 0.0f;
+  const int dz1b = (DUALH || RC) ? a.shift2 - (int)__builtin_rintf(a.zp_in2 ? a.zp_in2[0] : 0.0f) : 0;
+  const float sin1a = RC ? a.s_ina[0] : 0.0f;
+  const int dz1a = RC ? a.shifta - (int)__builtin_rintf(a.zp_ina ? a.zp_ina[0] : 0.0f) : 0;
   ConvEpi e1 = ep1;
   e1.codes = reinterpret_cast<uint8_t*>(uintptr_t(1));   // the quantiser is always needed (GEMM 2 reads its codes)
   // FL >= 0 also says: both quantisers are the plain unsigned-byte one (epi_plain_q; the launcher checks) - code4n_plain, whose
@@ -383,7 +450,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
     else if (nst == 5) asm volatile("s_waitcnt vmcnt(5)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(1)\n\ts_barrier" ::: "memory");
     CHAIN_STAMP();   // 2 + 3n: chunk n's operands are there
-    if constexpr (!DUALH) asm volatile("" : "+v"(res[P][0]), "+v"(res[P][1]), "+v"(res[P][2]), "+v"(res[P][3]));
+    if constexpr (!DUALH && !RC) asm volatile("" : "+v"(res[P][0]), "+v"(res[P][1]), "+v"(res[P][2]), "+v"(res[P][3]));
     if (nseq + 1 < NC) request(nseq + 1, std::integral_constant<int, 1 - P>{});
 
     const int8_t* wb = lds + P * WCH;
@@ -411,6 +478,59 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
       const f32x2 c2{corr2f, corr2f}, m2{mult2, mult2}, b2{bv2, bv2};
 #pragma unroll
       for (int i = 0; i < 8; ++i) extra2[i] = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
+    }
+    // the recomputed shortcut: the previous block's `deq(Wa . xa) + deq(Wb . xb)`, ReLU - the convolution-shortcut form's statements above
+    // and in epilogue 1 below (sampled operand first, the same pk_fma, the same sum, relu4_nan), on the same accumulator layout: the value that
+    // block stored.  It waits in registers, accumulator layout, where the fp32 form's `res` waits in the transposed one
+    f32x2 sc2[RC ? 8 : 1];
+    if constexpr (RC) {
+      f32x2 eb[8];
+      const int r = wc * 32 + l31;
+      {
+        const float corrbf = (float)(dz1b * *reinterpret_cast<const int*>(pp + 2048 + 256));
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0;
+#pragma unroll
+        for (int s = 0; s < SB; ++s)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            const i32x4 bf = *reinterpret_cast<const i32x4*>(wb + (S1 + SA + s) * 4096 + r * 64 + (((ks * 2 + hsel) ^ ((r >> 2) & 3)) << 4));
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afb[s][ks], bf, acc, 0, 0, 0);
+          }
+        const float multb = sin1b * *reinterpret_cast<const float*>(pp + 2048);
+        const float bvb = a.bias2 ? *reinterpret_cast<const float*>(pp + 2048 + 512) : 0.0f;
+        const f32x2 c2{corrbf, corrbf}, m2{multb, multb}, b2{bvb, bvb};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) eb[i] = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
+      }
+      {
+        const float corraf = (float)(dz1a * *reinterpret_cast<const int*>(pp + 1024 + 256));
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0;
+#pragma unroll
+        for (int s = 0; s < SA; ++s)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            const i32x4 bf = *reinterpret_cast<const i32x4*>(wb + (S1 + s) * 4096 + r * 64 + (((ks * 2 + hsel) ^ ((r >> 2) & 3)) << 4));
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afa[s][ks], bf, acc, 0, 0, 0);
+          }
+        const float multa = sin1a * *reinterpret_cast<const float*>(pp + 1024);
+        const float bva = a.biasa ? *reinterpret_cast<const float*>(pp + 1024 + 512) : 0.0f;
+        const f32x2 c2{corraf, corraf}, m2{multa, multa}, b2{bva, bva};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          f32x2 f = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
+          sc2[i] = f + eb[i];
+        }
+      }
+      if (a.relu_sc) {
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+          const f32x4 t = relu4_nan(f32x4{sc2[i].x, sc2[i].y, sc2[i + 1].x, sc2[i + 1].y});
+          sc2[i] = f32x2{t.x, t.y};
+          sc2[i + 1] = f32x2{t.z, t.w};
+        }
+      }
     }
     // ---- GEMM 1: rows wr*32.., columns n*64 + wc*32.. ----
     const float corrf = (float)(dz1 * *reinterpret_cast<const int*>(pp + 256));
@@ -440,6 +560,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
       for (int i = 0; i < 8; ++i) {
         f32x2 f = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
         if constexpr (DUALH) f = f + extra2[DUALH ? i : 0];     // `out += identity`, the identity being a convolution
+        if constexpr (RC) f = f + sc2[RC ? i : 0];              // ... the identity being the previous block's output (what the fp32 form adds as `res`)
         v[2 * i] = f.x;
         v[2 * i + 1] = f.y;
       }
@@ -470,7 +591,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
           quad_transpose(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3], b0, b1);
           y[k] = f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
         }
-        if constexpr (!DUALH) y[k] = y[k] + res[P][g];
+        if constexpr (!DUALH && !RC) y[k] = y[k] + res[P][g];
         if (relu1 && (FL < 0 || out1)) y[k] = relu4_nan(y[k]);      // (plain quantiser: only the fp32 output needs the rectified value)
 #ifdef DLMCQ_LAB
         // timing only (round 5): 0x1000 - the fp32 stores land in a 64 KB window of the output (they stay in L2: what do the STORE INSTRUCTIONS cost
@@ -511,7 +632,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2, KB)) void conv_chain_i8_ker
 #pragma unroll
         for (int j = 0; j < U3; ++j) {
           const int kb = wc * (KB / 2) + j * 32 + l31;
-          const i32x4 bf = *reinterpret_cast<const i32x4*>(wb + (S1 + S2) * 4096 + kb * 64 + (((ks * 2 + hsel) ^ ((kb >> 2) & 3)) << 4));
+          const i32x4 bf = *reinterpret_cast<const i32x4*>(wb + W3U * 4096 + kb * 64 + (((ks * 2 + hsel) ^ ((kb >> 2) & 3)) << 4));
           acc2[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(bf, a2, acc2[j], 0, 0, 0);
         }
       }
@@ -573,7 +694,7 @@ extern "C" void dlmcq_x_chain_lab(int flags) { g_chain_lab = flags; }
 static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C2, int64_t K2, int32_t relu, void* codes,
                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                         int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi,
-                        int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
+                        int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream, int64_t CA = 0, int64_t CB = 0) {
   if (relu == DLMCQ_ACT_RELU6 || relu2 == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only: the flags below read any non-zero value as ReLU)
   if (q_lo != 0 || q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
   if (q2_form & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED)) return DLMCQ_EINVAL;   // (no other kernel, no route query here)
@@ -605,7 +726,7 @@ static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C
   // 512 slots of the two-workgroup instantiations, 3.06 rounds - run 3.5 rounds of 56-row tiles 8 % faster.  The rule: few rounds, the last
   // one less than an eighth full.
   if (rows_per_tile <= 0) {
-    const int64_t t64 = (M + 63) / 64, slots = 256 * CHAIN_WGS((int)(C + C2), (int)K2);
+    const int64_t t64 = (M + 63) / 64, slots = 256 * CHAIN_WGS((int)(C + C2 + CA + CB), (int)K2);
     const int64_t full = t64 / slots, left = t64 % slots;
     rows_per_tile = (full >= 2 && full <= 4 && left > 0 && left * 8 < slots) ? 56 : 64;
   }
@@ -631,7 +752,12 @@ static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C
     else if (fl == 1) hipLaunchKernelGGL((conv_chain_i8_kernel<__VA_ARGS__, 1>), grid, block, dyn, st, a, ep1, ep2);  \
     else hipLaunchKernelGGL((conv_chain_i8_kernel<__VA_ARGS__, -1>), grid, block, dyn, st, a, ep1, ep2);              \
   } while (0)
-  if (C2 == 0) {
+  if (CA > 0) {
+    // the recomputing form is built for the plan's launch alone: stage 1's second block, ReLU, plain quantisers (no run-time-flag form)
+    if (!(C == 64 && K2 == 64 && CA == 64 && CB == 64) || fl < 0) return DLMCQ_EINVAL;
+    if (fl == 3) hipLaunchKernelGGL((conv_chain_i8_kernel<64, 64, 0, 3, 64, 64>), grid, block, dyn, st, a, ep1, ep2);
+    else hipLaunchKernelGGL((conv_chain_i8_kernel<64, 64, 0, 1, 64, 64>), grid, block, dyn, st, a, ep1, ep2);
+  } else if (C2 == 0) {
     if (C == 64 && K2 == 64) DLMCQ_CHAIN_GO(64, 64, 0);
     else if (C == 64 && K2 == 128) DLMCQ_CHAIN_GO(64, 128, 0);
     else if (C == 128 && K2 == 128) DLMCQ_CHAIN_GO(128, 128, 0);
@@ -706,4 +832,43 @@ extern "C" int dlmcq_conv2d_i8_nhwc_dual_chain(const void* x, const int8_t* w, f
   a.w3 = w3; a.s_w3 = w_scale3; a.wsum3 = wsum3; a.bias3 = bias3; a.codes2 = static_cast<uint8_t*>(codes3);
   return chain_launch(a, M, C, K, C2, K3, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, relu3, codes3, q3_scale,
                       q3_zero_point, q3_lo, q3_hi, q3_form, q3_ste_g, rows_per_tile, stream);
+}
+
+extern "C" int dlmcq_conv2d_i8_nhwc_recompute_chain(
+    const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale, const float* in_zero_point,
+    const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t x_is_unsigned, const void* xa, const int8_t* wa,
+    const float* biasa, const int32_t* wsuma, const float* in_scalea, const float* in_zero_pointa, const float* w_scalea, int64_t Ca,
+    int32_t xa_is_unsigned, const void* xb, const int8_t* wb, const float* biasb, const int32_t* wsumb, const float* in_scaleb,
+    const float* in_zero_pointb, const float* w_scaleb, int64_t Hb, int64_t Wb, int64_t Cb, int32_t strideb, int32_t xb_is_unsigned,
+    int32_t relu_shortcut, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+    int32_t q_form, float q_ste_g, const int8_t* w2, const float* bias2, const int32_t* wsum2, const float* w_scale2, int64_t K2,
+    int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi, int32_t q2_form,
+    float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
+  if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || K2 < 1 || K % 64 != 0 || Ca < 1 || Hb < 1 || Wb < 1 || Cb < 1 || strideb < 1)
+    return DLMCQ_EINVAL;
+  if ((Hb - 1) / strideb + 1 != H || (Wb - 1) / strideb + 1 != W) return DLMCQ_EINVAL;   // the recomputed block gives [N, H, W, K] too
+  if (relu_shortcut == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;
+  const int64_t M = N * H * W;
+  if (M == 0) return DLMCQ_OK;
+  if (!x || !w || !wsum || !in_scale || !w_scale || !xa || !wa || !wsuma || !in_scalea || !w_scalea || !xb || !wb || !wsumb ||
+      !in_scaleb || !w_scaleb || !w2 || !wsum2 || !w_scale2 || !codes2 || !q_scale || !q2_scale)
+    return DLMCQ_EINVAL;
+  if (!aligned16(x) || !aligned16(w) || !aligned16(xa) || !aligned16(wa) || !aligned16(xb) || !aligned16(wb) || !aligned16(w2) ||
+      (out && !aligned16(out)) || (codes && !aligned16(codes)) || !aligned16(codes2))
+    return DLMCQ_EALIGN;
+  if (M >= (1ll << 31) || N * Hb * Wb * Cb >= (1ll << 40)) return DLMCQ_ERANGE;
+  ChainArgs a{};
+  a.x = static_cast<const int8_t*>(x); a.w1 = w; a.s_w1 = w_scale; a.wsum1 = wsum; a.bias1 = bias;
+  a.s_in1 = in_scale; a.zp_in1 = in_zero_point; a.shift1 = x_is_unsigned ? 128 : 0;
+  a.xa = static_cast<const int8_t*>(xa); a.wa = wa; a.s_wa = w_scalea; a.wsuma = wsuma; a.biasa = biasa;
+  a.s_ina = in_scalea; a.zp_ina = in_zero_pointa; a.shifta = xa_is_unsigned ? 128 : 0; a.relu_sc = relu_shortcut != 0;
+  a.x2 = static_cast<const int8_t*>(xb); a.w2 = wb; a.s_w2 = w_scaleb; a.wsum2 = wsumb; a.bias2 = biasb;
+  a.s_in2 = in_scaleb; a.zp_in2 = in_zero_pointb; a.shift2 = xb_is_unsigned ? 128 : 0;
+  a.P = (int)H; a.Q = (int)W; a.H2 = (int)Hb; a.W2 = (int)Wb; a.stride2 = strideb;
+  a.qdiv = make_fastdiv((uint32_t)W);
+  a.pdiv = make_fastdiv((uint32_t)H);
+  a.residual = nullptr; a.out = out; a.codes = static_cast<uint8_t*>(codes);
+  a.w3 = w2; a.s_w3 = w_scale2; a.wsum3 = wsum2; a.bias3 = bias2; a.codes2 = static_cast<uint8_t*>(codes2);
+  return chain_launch(a, M, C, K, 0, K2, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, relu2, codes2, q2_scale,
+                      q2_zero_point, q2_lo, q2_hi, q2_form, q2_ste_g, rows_per_tile, stream, Ca, Cb);
 }

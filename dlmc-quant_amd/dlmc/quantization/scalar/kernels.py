@@ -834,6 +834,31 @@ class ChunkMajor:
         self.buf.record_stream(s)
 
 
+class DeferredBlock(ChunkMajor):
+    """An fp32 block tensor [N, K, H, W] that is NOT stored: the output relu?(conv1x1(pa) + conv1x1(pb)) of a convolution-shortcut block,
+    carried as the two operand dicts it is made of (as conv2d_i8_dual takes them; `pb` may carry a stride).  A reader that can make
+    the values itself takes the operands (conv2d_i8_recompute_chain, via fuse.ChainInt8Layer); for anyone else it is a ChunkMajor whose
+    `buf` appears on first use - one conv2d_i8_dual launch, the bits the block's own kernel would have stored - and is kept."""
+
+    def __init__(self, pa, pb, relu, shape):
+        self.pa, self.pb, self.relu, self.shape = pa, pb, bool(relu), tuple(shape)
+        self.dtype, self.device, self._buf = torch.float32, pa["codes"].device, None
+
+    @property
+    def buf(self):
+        if self._buf is None:
+            self._buf = ChunkMajor.from_nhwc(conv2d_i8_dual(self.pa, self.pb, relu=self.relu, emit=None, want_out=True)).buf
+        return self._buf
+
+    def numel(self):
+        return math.prod(self.shape)
+
+    def record_stream(self, s):
+        for t in (self.pa["codes"], self.pb["codes"], self._buf):
+            if t is not None:
+                t.record_stream(s)
+
+
 class PadShortcut:
     """The parameter-free "option A" shortcut of He et al. 2016, section 4.2 - `F.pad(src[:, :, ::stride, ::stride], (0, 0, 0, 0, lo, hi))`,
     subsample and zero-pad the channels - as the SOURCE tensor and two numbers instead of the padded tensor: `conv2d_i8(residual=
@@ -958,6 +983,52 @@ def conv2d_i8_dual_chain(a, b, c3, relu=True, emit=None, want_out=True, want_cod
         *_q_args(q3, w3flag | (N.FP32_OUT_CHUNK_MAJOR if fcm else 0)), int(rows_per_tile), N.stream_ptr())),
         2 * m * K_ * (ch + ch2 + K3))
     return out, q[0], q3[0]
+
+
+RECOMPUTE_CHAIN_SHAPES = {(64, 64, 64, 64)}   # (C, Ca, Cb, K2) dlmcq_conv2d_i8_nhwc_recompute_chain is built for: ResNet-50's stage 1
+
+
+def recompute_chain_supported(c, ca, cb, k, k2, m):
+    return (c, ca, cb, k2) in RECOMPUTE_CHAIN_SHAPES and k % 64 == 0 and m * k * 4 <= 0x7fff0000
+
+
+def conv2d_i8_recompute_chain(a, b, pa, pb, relu_shortcut=True, relu=True, emit=None, want_out=True, want_codes=False, relu2=True,
+                              emit2=None, rows_per_tile=0, out_chunk_major=False):
+    """conv2d_i8_chain whose shortcut is not an fp32 tensor but the PREVIOUS block's two operands `pa` (unit stride) and `pb` (may carry a
+    stride) - operand dicts as conv2d_i8_dual_chain takes them as `a` and `b`: the shortcut relu?(conv1x1(pa) + conv1x1(pb)) is
+    recomputed chunk by chunk, bit for bit what conv2d_i8_dual_chain(pa, pb, ..., want_out=True) stores
+    (dlmcq_conv2d_i8_nhwc_recompute_chain).  `a`, `b` and the rest as in conv2d_i8_chain.  Returns (out or None, codes or None, codes2)."""
+    N.require_gpu(b["wq"])
+    o, oa, ob = _operand(a), _operand(pa), _operand(pb)
+    c = o.codes
+    (n, K_), (h, w_, ch, R, S, st, pd, _, uns) = o.shape[:2], o.geom
+    _, _, cha, Ra, Sa, sta, pda, _, unsa = oa.geom
+    hb, wb_, chb, Rb, Sb, stb, pdb, _, unsb = ob.geom
+    K2, R2, S2, C2 = b["wq"].shape
+    if (R, S, R2, S2, Ra, Sa, Rb, Sb) != (1,) * 8 or (st, sta) != (1, 1) or pd or pda or pdb or C2 != K_ or emit is None or emit2 is None:
+        raise ValueError("conv2d_i8_recompute_chain: unpadded 1x1 convolutions, the second reading the first's codes")
+    if oa.shape != o.shape or ob.shape != o.shape:
+        raise ValueError(f"conv2d_i8_recompute_chain: the block gives {o.shape}, its recomputed shortcut {oa.shape} and {ob.shape}")
+    m = n * h * w_
+
+    def alloc(k, dtype):
+        return torch.empty((n, k, h, w_), dtype=dtype, device=c.device, memory_format=torch.channels_last)
+    ocm = bool(out_chunk_major) and want_out
+    out = (ChunkMajor.empty(n, K_, h, w_, c.device) if ocm else alloc(K_, torch.float32)) if want_out else None
+    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, c, False, "conv2d_i8_recompute_chain")
+    q2 = _quantiser(emit2, lambda dtype: alloc(K2, dtype), c, True, "conv2d_i8_recompute_chain")
+    b2, ws2 = _bias_c(b["bias"]), _flat(b["w_scale"], c, K2)
+    # algorithmic bytes: the launch's real operands - three code tensors (the strided one where it is sampled) and four weight tensors in,
+    # no fp32 in; ops: the MACs it executes, the two recomputed reductions included
+    nbytes = c.numel() + oa.codes.numel() + ob.codes.numel() // (stb * stb) + a["wq"].numel() + pa["wq"].numel() + pb["wq"].numel() + \
+        b["wq"].numel() + m * K_ * (4 * want_out + want_codes) + m * K2
+    w2t, w2flag = _second_weights(b)
+    PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_recompute_chain(
+        *_head(o, out.buf if ocm else out), n, h, w_, ch, K_, uns, *oa.ptrs, cha, unsa, *ob.ptrs, hb, wb_, chb, stb, unsb,
+        int(bool(relu_shortcut)), int(bool(relu)), *_q_args(q), N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2, int(bool(relu2)),
+        *_q_args(q2, w2flag | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)), int(rows_per_tile), N.stream_ptr())),
+        2 * m * K_ * (ch + cha + chb + K2))
+    return out, q[0], q2[0]
 
 
 def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=False, pad_code0=False):

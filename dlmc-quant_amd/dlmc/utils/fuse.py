@@ -18,6 +18,7 @@ explicit HIP launches of the plan, and the result can be captured with `dlmc.uti
 The plan snapshots weights and scales: re-fuse after changing them.
 """
 import math
+import os
 import operator
 
 import torch
@@ -468,6 +469,12 @@ class ChainInt8Layer(nn.Module):
         self.swapped = short is not None and self.main is not a       # main reads the plan node's SECOND input
         self._w2cm = None      # the second layer's weight codes chunk-major (K.chunk_major), made at the first forward
         self.out_cm = False    # the fp32 block output as a K.ChunkMajor (set by _block_layout_pass where only chain kernels read it)
+        # _recompute_pass.  `defer_out` (a convolution-shortcut chain): the fp32 block output is not stored but handed on as a
+        # K.DeferredBlock - the two operands it is made of; `recompute` (the chain that alone reads it, as its shortcut): given such a
+        # value, the kernel recomputes it chunk by chunk (K.conv2d_i8_recompute_chain).  Any other reader of a DeferredBlock gets the
+        # tensor, materialised by one dual launch: same bits
+        self.defer_out = False
+        self.recompute = False
 
     def forward(self, x, y):
         a, b, sc, mn = self.a, self.b, self.short, self.main
@@ -483,6 +490,9 @@ class ChainInt8Layer(nn.Module):
         kw = dict(relu=a.relu, emit=a._emit_for(n, a.k, h, w), want_out=a.want_out, want_codes=self.want_codes, emit2=b._emit_for(n, b.k, h, w),
                   out_chunk_major=self.out_cm)
         if sc is None:
+            if (self.recompute and isinstance(y, K.DeferredBlock) and y._buf is None and
+                    K.recompute_chain_supported(c, y.pa["codes"].shape[1], y.pb["codes"].shape[1], a.k, b.k, n * h * w)):
+                return K.conv2d_i8_recompute_chain(a.operand(x, codes), nxt, y.pa, y.pb, relu_shortcut=y.relu, relu2=b.relu, **kw)
             if not K.chain_supported(c, a.k, b.k, n * h * w):
                 if isinstance(y, K.ChunkMajor):      # (the plan nodes one after the other know row-major tensors only)
                     y = y.to_nhwc()
@@ -493,7 +503,11 @@ class ChainInt8Layer(nn.Module):
             out, mid = DualInt8Layer(a, sc if mn is a else mn)(*((x, y) if mn is a else (y, x)))
             return out, (mid if self.want_codes else None), b(mid)[1]      # (row-major: every reader takes that)
         kw["emit3"] = kw.pop("emit2")
-        return K.conv2d_i8_dual_chain(mn.operand(x), sc.operand(y), nxt, relu3=b.relu, **kw)
+        oa, ob = mn.operand(x), sc.operand(y)
+        if self.defer_out and a.want_out:
+            _, mid, codes3 = K.conv2d_i8_dual_chain(oa, ob, nxt, relu3=b.relu, **dict(kw, want_out=False))
+            return K.DeferredBlock(oa, ob, a.relu, (n, a.k, h, w)), mid, codes3
+        return K.conv2d_i8_dual_chain(oa, ob, nxt, relu3=b.relu, **kw)
 
 
 class DwPwInt8Layer(nn.Module):
@@ -583,7 +597,7 @@ def _dwpw_pass(gm, report):
 def _pointwise(plan):
     """A plan node the chain kernel can take as either half: a plain 1x1 / stride 1 / unpadded int8 convolution."""
     lay = plan.layer
-    return (type(plan) is Int8Layer and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and lay.stride[0] == 1 and
+    return (_is_int8(plan) and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and lay.stride[0] == 1 and
             lay.padding[0] == 0 and plan.w_off is None and plan.pool is None and plan.k_pad == plan.k and plan.c_pad == plan.c and
             not plan.act.needs_g and not plan.relu6 and          # (the chain kernel: ReLU only)
             plan.pad_shortcut is None)                           # (a pad shortcut: the tiled kernel's PADRES epilogue alone reads one)
@@ -603,7 +617,7 @@ def _chain_pass(gm, report):
             a, other = a.a, a.b
             main, short = (a, other) if _pointwise(a) else (other, a)
             lay = short.layer
-            if not (_pointwise(main) and type(short) is Int8Layer and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and
+            if not (_pointwise(main) and _is_int8(short) and lay.weight.dim() == 4 and tuple(lay.weight.shape[2:]) == (1, 1) and
                     lay.padding[0] == 0 and short.w_off is None and short.pool is None and short.k_pad == short.k and
                     short.c_pad == short.c and not short.act.needs_g and a.pool is None and a.w_off is None):
                 continue
@@ -651,11 +665,54 @@ def _chain_pass(gm, report):
         gm.recompile()
 
 
+# (C, Ca, Cb, K2) of the pairs _recompute_pass rewrites: the shapes whose pair won when measured (LABNOTES 17), among those the kernel is
+# built for (K.RECOMPUTE_CHAIN_SHAPES)
+RECOMPUTE_ENABLED = {(64, 64, 64, 64)}
+# fuse_inference(recompute_shortcuts=None) takes its default from the environment, so that one tree runs an unchanged benchmark both ways
+RECOMPUTE_DEFAULT = os.environ.get("DLMCQ_RECOMPUTE_SHORTCUTS", "1") not in ("0", "", "off", "false")
+
+
+def _plain_emit(e):
+    """The quantiser the chain kernels' compile-time-flag forms know: unsigned byte, zero point 0, no g."""
+    return e is not None and (e.lo, e.hi) == (0, 255) and not e.needs_g and e.zp_emit is None
+
+
+def _recompute_pass(gm, report, enabled):
+    """The fp32 output of a stage's first block (a convolution-shortcut chain) read by nothing but the next chain, as its shortcut, exists
+    only for transport - 1 KB per pixel written and read back at K = 256, computed from 128 B of codes.  Where the shape is enabled the
+    first launch hands on a K.DeferredBlock - its two operands - instead of the tensor, and the second recomputes the tensor chunk
+    by chunk from them (csrc/conv_chain_i8.hip, the CA / CB form): bit-identical.  The graph keeps its edges: only the two modules are marked.  Anything else - another reader of the tensor, a quantiser the kernel's
+    compile-time forms do not know, a second layer without ReLU, a shape outside `enabled` - keeps the graph as it is."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+    for n0 in list(graph.nodes):
+        m0 = modules.get(n0.target) if n0.op == "call_module" else None
+        if not isinstance(m0, ChainInt8Layer) or m0.short is None or m0.defer_out or len(n0.args) != 2:
+            continue
+        outs = [u for u in n0.users if u.op == "call_function" and u.target is operator.getitem and u.args[1] == 0]
+        if len(outs) != 1 or len(outs[0].users) != 1:
+            continue
+        o = outs[0]
+        n1 = next(iter(o.users))
+        m1 = modules.get(n1.target) if n1.op == "call_module" else None
+        if not (isinstance(m1, ChainInt8Layer) and m1.short is None and not m1.recompute and len(n1.args) == 2 and not n1.kwargs and
+                n1.args[1] is o and n1.args[0] is not o):
+            continue
+        if (m1.main.c, m0.main.c, m0.short.c, m1.b.k) not in enabled or m0.a.k != m1.a.k:
+            continue
+        if not (m1.a.relu and _plain_emit(m1.a.emit) and _plain_emit(m1.b.emit) and m0.a.pool is None and m1.a.pool is None):
+            continue
+        m0.defer_out = m1.recompute = True
+        count += 1
+    report.recomputed = count
+
+
 def _block_end_like(m):
     """A plan layer the library's block-end kernel (csrc/conv_pwr_i8.hip) can take: the only kernel besides the chain kernels that
     knows chunk-major block tensors.  (Whether it DOES take a call is the library's decision per call - K.conv2d_i8 asks and falls
     back to the ordinary layout.)"""
-    return (type(m) is Int8Layer and _pointwise(m) and m.c in (256, 512) and m.k % 128 == 0 and m.k_pad == m.k and m.c_pad == m.c and m.relu
+    return (_is_int8(m) and _pointwise(m) and m.c in (256, 512) and m.k % 128 == 0 and m.k_pad == m.k and m.c_pad == m.c and m.relu
             and m.w_off is None and m.pool is None and m.layer.stride[0] == 1 and not m.act.needs_g and
             (m.emit is None or ((m.emit.lo, m.emit.hi) == (0, 255) and not m.emit.needs_g)))
 
@@ -676,7 +733,7 @@ def _block_layout_pass(gm, report):
         if isinstance(m, ChainInt8Layer):
             return m.a.k % 64 == 0
         if isinstance(m, DualInt8Layer):     # (the 256-deep addend read row by row, the 512-deep one sampled: conv_pwr_applies)
-            one = lambda t: type(t) is Int8Layer and t.layer.weight.dim() == 4 and tuple(t.layer.weight.shape[2:]) == (1, 1)
+            one = lambda t: _is_int8(t) and t.layer.weight.dim() == 4 and tuple(t.layer.weight.shape[2:]) == (1, 1)
             dense, other = (m.a, m.b) if m.a.c == 256 else (m.b, m.a)
             return (one(m.a) and one(m.b) and (dense.c, other.c) == (256, 512) and dense.layer.stride[0] == 1 and m.a.relu and m.a.k % 128 == 0
                     and m.a.k_pad == m.a.k and m.a.w_off is None and m.b.w_off is None and m.a.pool is None and m.a.emit is not None)
@@ -1082,6 +1139,28 @@ class _DryNode(nn.Module):
         raise RuntimeError("fuse_inference(dry_run=True) builds the plan's structure only")
 
 
+class _DryInt8Layer(Int8Layer):
+    """fuse_inference(dry_run="chains"): an Int8Layer's structure - what the chain-level passes decide on - without its weight codes
+    (quantising them needs the GPU).  It cannot be run."""
+
+    def __init__(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False):
+        nn.Module.__init__(self)
+        self.layer, self.act, self.kind, self.w_off = layer, spec[0], spec[4], spec[5]
+        self.relu, self.emit, self.want_out, self.pool, self.relu6 = bool(relu), emit, bool(want_out), pool, bool(relu6)
+        w = layer.weight
+        self.k, self.c = int(w.shape[0]), int(w.shape[1])
+        self.k_pad, self.c_pad = (_ceil64(self.k), _ceil64(self.c)) if w.dim() == 4 else (self.k, self.c)
+        self.narrow, self.pad_shortcut, self.emit_shift = False, None, False
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+def _is_int8(m):
+    """A plain Int8Layer plan node (no subclass with a kernel family of its own), or its dry-run stand-in."""
+    return type(m) in (Int8Layer, _DryInt8Layer)
+
+
 class FusionReport:
     """What the pass did, for logs and tests."""
 
@@ -1089,6 +1168,7 @@ class FusionReport:
         self.layers = self.relu = self.residual = self.emit = self.fp32_outputs = self.stem = self.pooled = self.dual = 0
         self.relu6 = 0        # ReLU6 (nn.ReLU6, nn.Hardtanh(0, 6), F.relu6, F.hardtanh(x, 0, 6)) fused; `relu` counts ReLU alone
         self.chained = 0      # block end + next block's 1x1 pairs running as one kernel
+        self.recomputed = 0   # projection-block fp32 outputs dropped, their reader recomputing them from the block's operands (_recompute_pass)
         self.chunk_major = 0  # fp32 block outputs kept chunk-major between two kernels that walk them chunk by chunk (_block_layout_pass)
         self.dwpw = 0         # depthwise 3x3 + pointwise 1x1 units running as one kernel
         self.act_offset = 0   # planned layers whose input quantiser has a float offset (fuse_inference(act_offsets=True))
@@ -1103,6 +1183,7 @@ class FusionReport:
                 f"code-emitting={self.emit}, fp32 outputs kept={self.fp32_outputs}, stem layers={self.stem}, "
                 f"pools on codes={self.pooled}, dual (conv + shortcut conv) kernels={self.dual}, chained pairs={self.chained} (fp32 outputs chunk-major: {self.chunk_major}), "
                 f"depthwise + pointwise units={self.dwpw}, " + (f"gap heads={self.gap_heads}, " if self.gap_heads else "") +
+                (f"recomputed shortcuts={self.recomputed}, " if self.recomputed else "") +
                 (f"narrow fp32 rows={self.narrow}, " if self.narrow else "") +
                 (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
@@ -1408,14 +1489,19 @@ def _codes_from_blob(mod_name, blob, layer):
 
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
-                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False):
+                   relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
+                   recompute_shortcuts=None):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
     layers' weight codes from it (expanded on the device) instead of quantising the fp32 weights again.
     Layers that are not eligible (grouped / 3-channel convs, non-integer zero points, RootQ, ...) keep running
     their own wrapper.  `model` must be on the GPU, in eval mode, already calibrated.  `dry_run=True` only takes the
-    fusion decisions (graph + `fusion_report`, placeholder nodes): it needs no GPU and the result cannot be run.
+    fusion decisions (graph + `fusion_report`, placeholder nodes): it needs no GPU and the result cannot be run.  `dry_run="chains"`
+    also takes the chain-level decisions (chain pairs, block layout, recomputed shortcuts) on structural stand-ins of the plan layers.
+    `recompute_shortcuts`: a stage's first block hands on its fp32 output unstored (K.DeferredBlock) where the next chain
+    alone reads it, and that chain recomputes it from the block's two code operands (_recompute_pass; RECOMPUTE_ENABLED shapes: ResNet-50's stage 1).
+    Bit-identical.  None: the environment's DLMCQ_RECOMPUTE_SHORTCUTS (0 / 1), on when unset; False: the plan as it was.
     `chain_pairs=False` keeps every block end and the 1x1 convolution behind it as two launches (A/B and tests).
     `dwpw=True` runs every depthwise 3x3 / stride 1 + pointwise 1x1 unit (MobileOne, MobileNet) as ONE launch
     (csrc/conv_dwpw_i8.hip: the code tensor between the two layers stays in LDS; bit-identical).  Off by default: at MobileOne-S1
@@ -1632,7 +1718,11 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
                 not any(sp[0].xoff and int(modules[t].padding[0]) > 0 for sp, t in ((spec, node.target), (other, residual.target))))
         # every such layer that writes fp32 (or reads a shortcut) does so at the real width
         narrow = bool(can_narrow and (fp32_needed or emit is None or residual is not None))
-        if dry_run:       # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
+        if dry_run == "chains" and cls is Int8Layer:    # ... a structural stand-in the chain-level passes can read
+            opts = dict(relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
+            plan = _DryInt8Layer(modules[node.target], spec, **opts)
+            gm.add_module(name, DualInt8Layer(plan, _DryInt8Layer(modules[residual.target], other)) if dual else plan)
+        elif dry_run:     # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
             gm.add_module(name, _DryNode())
         else:
             def from_blob(name, sp):       # the layer's weight codes come from the integer checkpoint, expanded on the device
@@ -1709,10 +1799,12 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _avgpool_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
-    if chain_pairs and not dry_run:
+    if chain_pairs and (not dry_run or dry_run == "chains"):
         _chain_pass(gm, report)
         if block_layout:
             _block_layout_pass(gm, report)
+        if RECOMPUTE_DEFAULT if recompute_shortcuts is None else recompute_shortcuts:
+            _recompute_pass(gm, report, RECOMPUTE_ENABLED)
         if dwpw:      # (off by default: measured no faster than the two launches - both halves of a MobileOne unit are bound by their
             #            own vector arithmetic, not by the code tensor between them: LABNOTES round 4)
             _dwpw_pass(gm, report)

@@ -653,6 +653,33 @@ int dlmcq_conv2d_i8_nhwc_dual_chain(const void* x, const int8_t* w, float* out, 
                                     int32_t q3_lo, int32_t q3_hi, int32_t q3_form, float q3_ste_g, int32_t rows_per_tile,
                                     dlmcq_stream_t stream);
 
+/*
+ * dlmcq_conv2d_i8_nhwc_chain whose fp32 shortcut is not read but RECOMPUTED: the shortcut is the output of a block of the
+ * dlmcq_conv2d_i8_nhwc_dual_chain kind (the first block of a stage), handed over as that block's operands,
+ *     r      = conv1x1(xa, wa) + biasa  +  conv1x1(xb sampled at strideb, wb) + biasb;  ReLU (if relu_shortcut)
+ *     v      = conv1x1(x, w) + bias + r;  ReLU (if relu);  out = v (optional);  codes = Q(v) (optional)
+ *     codes2 = Q2( ReLU?( conv1x1( Q(v), w2 ) + bias2 ) )
+ * r is computed per 64-channel chunk by the instructions dlmcq_conv2d_i8_nhwc_dual_chain computes its fp32 output with, in their order,
+ * so the call is bit-identical to dlmcq_conv2d_i8_nhwc_chain reading that call's `out` as `residual` - for Ca + Cb bytes of codes per pixel
+ * instead of 4 K bytes of fp32, and the first call then needs no fp32 output.  x: [N][H][W][C] codes; xa: [N][H][W][Ca]; xb: [N][Hb][Wb][Cb]
+ * with (Hb - 1) / strideb + 1 == H (likewise Wb); w: [K][C]; wa: [K][Ca]; wb: [K][Cb]; w2: [K2][K].  out is chunk-major under
+ * DLMCQ_FP32_OUT_CHUNK_MAJOR in q2_form (DLMCQ_W2_CHUNK_MAJOR as in the other chain calls).
+ * Supported: (C, Ca, Cb, K2) = (64, 64, 64, 64) (ResNet-50's stage 1), K % 64 == 0, N*H*W*K*4 < 2^31 - 64 Ki, relu != 0, and both quantisers
+ * plain ones (forms ZEROPOINT / SYMMETRIC with an integer zero point, as the plan's are; there is no run-time-flag form of this kernel) -
+ * anything else: DLMCQ_EINVAL / DLMCQ_ERANGE, and callers run dlmcq_conv2d_i8_nhwc_chain on the stored tensor.  relu_shortcut, relu or
+ * relu2 = DLMCQ_ACT_RELU6: DLMCQ_EINVAL.  Pointer and alignment rules as for the other two chain calls.
+ */
+int dlmcq_conv2d_i8_nhwc_recompute_chain(
+    const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale, const float* in_zero_point,
+    const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t x_is_unsigned, const void* xa, const int8_t* wa,
+    const float* biasa, const int32_t* wsuma, const float* in_scalea, const float* in_zero_pointa, const float* w_scalea, int64_t Ca,
+    int32_t xa_is_unsigned, const void* xb, const int8_t* wb, const float* biasb, const int32_t* wsumb, const float* in_scaleb,
+    const float* in_zero_pointb, const float* w_scaleb, int64_t Hb, int64_t Wb, int64_t Cb, int32_t strideb, int32_t xb_is_unsigned,
+    int32_t relu_shortcut, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+    int32_t q_form, float q_ste_g, const int8_t* w2, const float* bias2, const int32_t* wsum2, const float* w_scale2, int64_t K2,
+    int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi, int32_t q2_form,
+    float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream);
+
 /* ---- the 3-channel first layer and its max-pool, in the integer-code domain (csrc/conv_stem_i8.hip) ---- */
 
 /*

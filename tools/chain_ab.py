@@ -7,7 +7,13 @@ quantisers: null zero point, unsigned byte range, chunk-major second weights), u
 Prints per shape the median launch time, the algorithmic bytes, TB/s, the fraction of 8 TB/s and a checksum of the outputs
 (equal checksums across builds = the same bytes), then the sum over the plan's 11 launches.  `--lab` flags are the lab library's
 timing-only ablations (dlmcq_x_chain_lab; 1 = no shortcut loads, 32 = no weight DMA, 33 = neither; a lab build is needed).
-Round 5: the tool the A/B runs of the chain variants under csrc/lab/ go through (one process per build, alternated by the caller)."""
+Round 5: the tool the A/B runs of the chain variants under csrc/lab/ go through (one process per build, alternated by the caller).
+
+    python tools/chain_ab.py --pair [--batch 512] [--iters 9] [--runs 2]
+
+Round 6: stage 1's first two chain launches as the plan launches them (fp32 block tensors chunk-major), alternated in this process:
+OLD = the convolution-shortcut chain writing its fp32 output + the chain reading it, NEW = the same first launch without that output +
+the chain that recomputes it (dlmcq_conv2d_i8_nhwc_recompute_chain).  Median us per launch and output checksums, which must match."""
 import argparse
 import os
 import sys
@@ -23,6 +29,8 @@ ap.add_argument("--iters", type=int, default=7)
 ap.add_argument("--rows", type=int, default=0)
 ap.add_argument("--cm", action="store_true", help="the fp32 tensors chunk-major (DLMCQ_FP32_CHUNK_MAJOR; same checksums: same values)")
 ap.add_argument("--abcm", action="store_true", help="time row-major and chunk-major fp32 tensors alternately, launch by launch, in this process")
+ap.add_argument("--pair", action="store_true", help="stage 1's first two launches: stored against recomputed shortcut, alternated")
+ap.add_argument("--runs", type=int, default=2, help="--pair: independent repetitions of the alternation")
 ap.add_argument("--noout", action="store_true", help="also time every case without its fp32 / code stores (lab-free ablation)")
 args = ap.parse_args()
 if args.lib:
@@ -66,6 +74,75 @@ def csum(t):
         t = t.buf
     return int(t.view(torch.uint8).to(torch.int64).sum().item()) if t.dtype != torch.float32 else int(t.view(torch.int32).to(torch.int64).sum().item())
 
+
+
+
+def pair_ab():
+    c, h, k, k2, n = 64, 56, 256, 64, args.batch
+    m = n * h * h
+    emits = [K.EmitCodes(torch.full((1,), s_, device=dev), None, 0, 255, N.FORM_ZEROPOINT) for s_ in (0.05, 0.11, 0.07, 0.13)]
+    pa = dict(layer(k, c), in_scale=torch.full((1,), 0.02, device=dev), in_zp=None)
+    pb = dict(layer(k, c), in_scale=torch.full((1,), 0.03, device=dev), in_zp=None, stride=1)
+    a = dict(layer(k, c), in_scale=torch.full((1,), 0.02, device=dev), in_zp=None)
+    c3, b = layer(k2, k), layer(k2, k)
+    c3["wq_chunk"], b["wq_chunk"] = K.chunk_major(c3["wq"]), K.chunk_major(b["wq"])
+    nset = max(2, int(400e6 // (3 * m * c + 2 * m * k * 4)) + 1)
+    codes = [[torch.randint(0, 256, (n, c, h, h), generator=g, device=dev, dtype=torch.uint8).contiguous(memory_format=torch.channels_last)
+              for _ in range(3)] for _ in range(nset)]
+
+    def first(i, wo):
+        return K.conv2d_i8_dual_chain(dict(pa, codes=codes[i][0]), dict(pb, codes=codes[i][1]), c3, relu=True, emit=emits[0], want_out=wo,
+                                      relu3=True, emit3=emits[1], rows_per_tile=args.rows, out_chunk_major=True)
+
+    def old(i, y0):
+        return K.conv2d_i8_chain(dict(a, codes=codes[i][2]), b, y0, relu=True, emit=emits[2], want_out=True, relu2=True, emit2=emits[3],
+                                 rows_per_tile=args.rows, out_chunk_major=True)
+
+    def new(i):
+        return K.conv2d_i8_recompute_chain(dict(a, codes=codes[i][2]), b, dict(pa, codes=codes[i][0]), dict(pb, codes=codes[i][1]),
+                                           relu_shortcut=True, relu=True, emit=emits[2], want_out=True, relu2=True, emit2=emits[3],
+                                           rows_per_tile=args.rows, out_chunk_major=True)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return r, e0.elapsed_time(e1) * 1e3
+    y0, _, f_old = first(0, True)
+    _, _, f_new = first(0, False)
+    r_old, r_new = old(0, y0), new(0)
+    torch.cuda.synchronize()
+    sums = {"old": [csum(f_old), csum(r_old[0]), csum(r_old[2])], "new": [csum(f_new), csum(r_new[0]), csum(r_new[2])]}
+    same = sums["old"] == sums["new"] and torch.equal(r_old[0].buf.view(torch.int32), r_new[0].buf.view(torch.int32)) and torch.equal(r_old[2], r_new[2])
+    print(f"stage 1 pair, batch {n} ({m} pixels), 64 | 64, 64 -> 256 -> 64 at 56^2, fp32 chunk-major; checksums (first launch's codes, y1 fp32, "
+          f"second launch's codes): old {'/'.join(f'{v & 0xffffffff:08x}' for v in sums['old'])}  new "
+          f"{'/'.join(f'{v & 0xffffffff:08x}' for v in sums['new'])}  {'MATCH' if same else 'DIFFER'}", flush=True)
+    del y0, r_old, r_new
+    for run_ in range(args.runs):
+        t = {k_: [] for k_ in ("first+fp32", "chain(fp32 shortcut)", "first", "chain(recomputed)")}
+        for it in range(args.iters + 1):
+            i = it % nset
+            (y0, _, _), t0 = timed(lambda: first(i, True))
+            _, t1 = timed(lambda: old(i, y0))
+            del y0
+            _, t2 = timed(lambda: first(i, False))
+            _, t3 = timed(lambda: new(i))
+            if it:      # (the first round warms up)
+                for k_, v in zip(t, (t0, t1, t2, t3)):
+                    t[k_].append(v)
+        med = {k_: sorted(v)[len(v) // 2] for k_, v in t.items()}
+        o, nw = med["first+fp32"] + med["chain(fp32 shortcut)"], med["first"] + med["chain(recomputed)"]
+        print(f"run {run_}: " + "  ".join(f"{k_} {v:6.1f} us" for k_, v in med.items()) + f"  | pair old {o:6.1f} us  new {nw:6.1f} us  ({(nw / o - 1) * 100:+.1f} %)",
+              flush=True)
+    if not same:
+        sys.exit("chain_ab --pair: the outputs differ")
+
+
+if args.pair:
+    pair_ab()
+    sys.exit(0)
 
 for name in args.cases.split(","):
     c, h, k, k2, want_out, want_codes, c2, h2, st2, count = CASES[name]
