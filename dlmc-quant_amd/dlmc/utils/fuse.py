@@ -17,6 +17,7 @@ every downstream value - are bit-identical to the unfused wrappers; only the mem
 explicit HIP launches of the plan, and the result can be captured with `dlmc.utils.graph.GraphedForward`.
 The plan snapshots weights and scales: re-fuse after changing them.
 """
+import collections
 import math
 import os
 import operator
@@ -87,20 +88,58 @@ def plan_kind(mod):
     return None
 
 
+class _LayerSpec(collections.namedtuple("_LayerSpec", "act w_scale w_lo w_hi kind w_off w_codes", defaults=(None, None))):
+    """The frozen quantisers of one layer that can run on an int8 kernel: `act` (_ActSpec), the weight scale and code range, `kind`
+    (plan_kind).  `w_off`, `w_codes`: None for symmetric per-tensor / per-channel weights quantised by quantize_weight_krsc; asymmetric
+    (offset = channel minimum, ops.py:129-136) or QBase per-channel weights carry their float offsets [K] and a function returning the
+    module's own integer codes [K, C, R, S]."""
+
+    @property
+    def symmetric(self):
+        """Symmetric weights: no offset term (the dual, pooling first-layer and fused-head kernels have none)."""
+        return self.w_off is None
+
+    def with_codes(self, fn):
+        """The same quantisers, the weight codes coming from `fn()` (an integer checkpoint) instead of the fp32 weights."""
+        return self._replace(w_codes=fn)
+
+
+def _border_term(act, mod):
+    """A float activation offset in front of a padded convolution: the layer needs the border term of the *_xoff entry points (which
+    have no narrow, dual or pad-shortcut form)."""
+    return bool(act.xoff and mod.weight.dim() == 4 and int(mod.padding[0]) > 0)
+
+
+def _zp_fill(act):
+    """The code that pads an activation's channels for the kernels: its zero point; a float offset has none and pads with code 0."""
+    return 0 if (act.xoff or act.zp is None) else int(float(act.zp.reshape(-1)[0]))
+
+
+def _takes_shifted(spec, mod, dwpw=False):
+    """Whether plan convolution `mod` (its spec; None: not a plan layer of its own) reads an unsigned-byte quantiser's codes re-centred
+    (`code - 128`, see _PlanLayer.__init__) as they are: a matrix-core layer without channel padding."""
+    if spec is None or mod is None or mod.weight.dim() != 4:
+        return False
+    if spec.kind == "dw":      # the matrix-core depthwise kernel (csrc/conv_dwm_i8.hip) multiplies signed bytes: no re-centring of its fragments
+        # (not with `dwpw`: the fused unit's kernel emits plain codes only)
+        return not dwpw and mod.kernel_size == (3, 3) and mod.stride == (1, 1) and mod.padding == (1, 1) and mod.weight.shape[0] % 64 == 0
+    return spec.kind == "gemm" and mod.groups == 1 and mod.weight.shape[1] % 64 == 0
+
+
+def _emits_shifted(emit, readers, dwpw=False):
+    """Whether a producer hands quantiser `emit`'s codes over re-centred: an unsigned-byte quantiser whose every reader - (spec, module),
+    (None, None) for an operand of a dual node - takes them so."""
+    return bool(emit is not None and 0 <= emit.lo and emit.hi <= 255 and readers and all(_takes_shifted(s, m, dwpw) for s, m in readers))
+
+
 def _frozen_spec(mod, act_offsets=False):
-    """(_ActSpec, weight scale, weight lo, weight hi, kind, weight offset, weight-code function) if `mod` can run on an
-    int8 kernel with frozen scales.  The last two are None for symmetric per-tensor / per-channel weights quantised by
-    quantize_weight_krsc; asymmetric (offset = channel minimum, ops.py:129-136) or QBase per-channel weights carry their
-    float offsets [K] and a function returning the module's own integer codes [K, C, R, S]."""
+    """The _LayerSpec of `mod` if it can run on an int8 kernel with frozen scales, else None."""
     kind = plan_kind(mod)
     if kind is None:
         return None
-    spec = _frozen_spec_(mod, kind, act_offsets)
-    if spec is None:
-        return None
-    if len(spec) == 4:
-        spec = spec + (None, None)
-    return spec[:4] + (kind,) + spec[4:]
+    if isinstance(mod, FSPTQBase):
+        return _fsptq_spec(mod, kind)
+    return _qbase_spec(mod, kind, act_offsets) if isinstance(mod, QBase) else None
 
 
 def _xoff_kernel_exists(mod, kind):
@@ -115,88 +154,75 @@ def _xoff_kernel_exists(mod, kind):
     return w.shape[2] in (3, 7)          # "stem"
 
 
-def _frozen_spec_(mod, kind, act_offsets=False):
-    if isinstance(mod, FSPTQBase):
-        if not (mod.act_quant and mod.wt_quant) or mod.in_scale.numel() != 1:
-            return None
-        if mod.qconfig["weight"].get("recon_type") in ("adaround", "dist_recon"):
-            return None
-        if not (mod._init.ready(mod, "in_init_state") and mod._init.ready(mod, "wt_init_state")):
-            raise RuntimeError("fuse_inference: run a calibration forward first (scales are not initialised)")
-        if not (_byte_range(mod.in_min_val, mod.in_max_val) and -128 <= mod.wt_min_val and mod.wt_max_val <= 127):
-            return None
-        zp = mod.in_offset.detach().to(torch.float32).reshape(-1)[:1].clone()
-        z = float(zp[0])
-        if z != round(z) or not (mod.in_min_val <= z <= mod.in_max_val):
-            return None
-        act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(), zp, mod.in_min_val, mod.in_max_val,
-                       N.FORM_ZEROPOINT, False)
-        return act, mod.wt_scale.detach().clone(), mod.wt_min_val, mod.wt_max_val
-    if isinstance(mod, QBase):
-        cfg = mod.qconfig
-        if not (cfg["input"]["enable"] and cfg["weight"]["enable"]):
-            return None
-        k = mod.weight.shape[0]
-        per_channel = mod.wt_scale.numel() != 1
-        if mod.in_scale.numel() != 1 or (per_channel and (mod.wt_scale.numel() != k or mod.wt_scale.shape[0] != k)):
-            return None
-        if not (mod._init.ready(mod, "in_init_state") and mod._init.ready(mod, "wt_init_state")):
-            raise RuntimeError("fuse_inference: run a calibration forward first (scales are not initialised)")
-        lo, hi = mod.wt_min_val, mod.wt_max_val
-        if not (_byte_range(mod.in_min_val, mod.in_max_val) and _byte_range(lo, hi)):
-            return None
-        xoff = float(mod.in_offset.abs().max()) != 0
-        if xoff and not (act_offsets and mod.in_offset.numel() == 1 and _xoff_kernel_exists(mod, kind)):
-            return None                  # a float activation offset has no integer zero point (padding must be a code): act_offsets=True
-        asym = mod.wt_offset is not None and float(mod.wt_offset.abs().max()) != 0
-        act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(),
-                       mod.in_offset.detach().to(torch.float32).reshape(-1)[:1].clone() if xoff else None, mod.in_min_val, mod.in_max_val,
-                       N.FORM_QBASE, True, xoff=xoff)
-        g_w = 1 / math.sqrt(mod.weight.numel() * hi)
-        s_hat = ste_scale_value(mod.wt_scale, g_w).clone()
-        if not (per_channel or asym or hi > 127 or kind == "dw"):
-            return act, s_hat, lo, hi
-        w_off = mod.wt_offset.detach().to(torch.float32).reshape(-1).clone() if asym else None
+def _fsptq_spec(mod, kind):
+    if not (mod.act_quant and mod.wt_quant) or mod.in_scale.numel() != 1:
+        return None
+    if mod.qconfig["weight"].get("recon_type") in ("adaround", "dist_recon"):
+        return None
+    if not (mod._init.ready(mod, "in_init_state") and mod._init.ready(mod, "wt_init_state")):
+        raise RuntimeError("fuse_inference: run a calibration forward first (scales are not initialised)")
+    if not (_byte_range(mod.in_min_val, mod.in_max_val) and -128 <= mod.wt_min_val and mod.wt_max_val <= 127):
+        return None
+    zp = mod.in_offset.detach().to(torch.float32).reshape(-1)[:1].clone()
+    z = float(zp[0])
+    if z != round(z) or not (mod.in_min_val <= z <= mod.in_max_val):
+        return None
+    act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(), zp, mod.in_min_val, mod.in_max_val, N.FORM_ZEROPOINT, False)
+    return _LayerSpec(act, mod.wt_scale.detach().clone(), mod.wt_min_val, mod.wt_max_val, kind)
 
-        def codes(mod=mod, g_w=g_w, lo=lo, hi=hi):      # the module's own weight quantiser (form QBASE), as integers
-            off = mod.wt_offset if mod.wt_offset is not None else None
-            return K.fake_quant(mod.weight.detach(), mod.wt_scale.detach(), off, lo, hi, N.FORM_QBASE, g=g_w, codes="i8",
-                                want_y=False)[1]
-        return act, s_hat, lo, hi, w_off, codes
-    return None
+
+def _qbase_spec(mod, kind, act_offsets):
+    cfg = mod.qconfig
+    if not (cfg["input"]["enable"] and cfg["weight"]["enable"]):
+        return None
+    k = mod.weight.shape[0]
+    per_channel = mod.wt_scale.numel() != 1
+    if mod.in_scale.numel() != 1 or (per_channel and (mod.wt_scale.numel() != k or mod.wt_scale.shape[0] != k)):
+        return None
+    if not (mod._init.ready(mod, "in_init_state") and mod._init.ready(mod, "wt_init_state")):
+        raise RuntimeError("fuse_inference: run a calibration forward first (scales are not initialised)")
+    lo, hi = mod.wt_min_val, mod.wt_max_val
+    if not (_byte_range(mod.in_min_val, mod.in_max_val) and _byte_range(lo, hi)):
+        return None
+    xoff = float(mod.in_offset.abs().max()) != 0
+    if xoff and not (act_offsets and mod.in_offset.numel() == 1 and _xoff_kernel_exists(mod, kind)):
+        return None                  # a float activation offset has no integer zero point (padding must be a code): act_offsets=True
+    asym = mod.wt_offset is not None and float(mod.wt_offset.abs().max()) != 0
+    act = _ActSpec(mod.in_scale.detach().reshape(-1)[:1].clone(),
+                   mod.in_offset.detach().to(torch.float32).reshape(-1)[:1].clone() if xoff else None, mod.in_min_val, mod.in_max_val,
+                   N.FORM_QBASE, True, xoff=xoff)
+    g_w = 1 / math.sqrt(mod.weight.numel() * hi)
+    s_hat = ste_scale_value(mod.wt_scale, g_w).clone()
+    if not (per_channel or asym or hi > 127 or kind == "dw"):
+        return _LayerSpec(act, s_hat, lo, hi, kind)
+    w_off = mod.wt_offset.detach().to(torch.float32).reshape(-1).clone() if asym else None
+
+    def codes(mod=mod, g_w=g_w, lo=lo, hi=hi):      # the module's own weight quantiser (form QBASE), as integers
+        off = mod.wt_offset if mod.wt_offset is not None else None
+        return K.fake_quant(mod.weight.detach(), mod.wt_scale.detach(), off, lo, hi, N.FORM_QBASE, g=g_w, codes="i8",
+                            want_y=False)[1]
+    return _LayerSpec(act, s_hat, lo, hi, kind, w_off, codes)
 
 
 # -------------------------------------------------------------------------------------------- plan nodes
 class _PlanLayer(nn.Module):
     """Common part of the plan nodes: frozen quantiser constants, the consumer's emit spec, pooling on codes."""
 
-    def __init__(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False):
+    def __init__(self, layer, spec, **decided):
         super().__init__()
-        self.layer = layer
-        self.act, w_scale, self.w_lo, self.w_hi, self.kind, w_off, self._w_codes = spec
-        self.relu, self.emit, self.want_out, self.pool = bool(relu), emit, bool(want_out), pool
-        # ReLU6 fused into the epilogue (DLMCQ_ACT_RELU6).  `relu` keeps meaning ReLU alone: the chain / dual / block-end decisions and
-        # the kernels that know no upper bound read it, and they leave ReLU6 layers alone
-        self.relu6 = bool(relu6)
-        k = layer.weight.shape[0]
-        # channel counts that are no multiple of 64 (the K step of the matrix-core kernel) are zero-padded: padded output
-        # channels have zero weights and bias, so their value is 0 and their code is the consumer's code of 0
-        self.k, self.k_pad = k, (_ceil64(k) if self.kind in ("gemm", "dw") and layer.weight.dim() == 4 else k)
-        w_scale = w_scale.detach().to(torch.float32).reshape(-1)
-        w_scale = w_scale.expand(k) if w_scale.numel() == 1 else w_scale
+        self._structure(layer, spec, **decided)
+        self.w_lo, self.w_hi, self._w_codes = spec.w_lo, spec.w_hi, spec.w_codes
+        w_scale = spec.w_scale.detach().to(torch.float32).reshape(-1)
+        w_scale = w_scale.expand(self.k) if w_scale.numel() == 1 else w_scale
         self.register_buffer("w_scale", self._padk(w_scale, 1.0), persistent=False)
-        if w_off is not None:
-            w_off = w_off.expand(k) if w_off.numel() == 1 else w_off
-        self.register_buffer("w_off", None if w_off is None else self._padk(w_off.to(w_scale.device), 0.0), persistent=False)
-        self.register_buffer("bias_pad", None if layer.bias is None or self.k_pad == k else self._padk(layer.bias.detach().float(), 0.0),
+        self.register_buffer("bias_pad", None if layer.bias is None or self.k_pad == self.k else self._padk(layer.bias.detach().float(), 0.0),
                              persistent=False)
         # the zero point the KERNELS see: a float offset (act.xoff) is none - its codes pad with code 0 and its term is in the bias / border
         self._kzp = None if self.act.xoff else self.act.zp
-        self._zp_fill = int(0 if self._kzp is None else float(self._kzp.reshape(-1)[0]))   # (read once: no host sync in forward)
+        self._zp_fill = _zp_fill(self.act)   # (read once: no host sync in forward)
         # A producer may hand an unsigned-byte quantiser's codes over as int8 `code - 128` (EmitCodes.shift128: what the matrix
         # cores multiply anyway, so the consumer's kernel need not re-centre every operand byte it reads); this node then runs
         # with the zero point `zp - 128` - the same integers.  `emit_shift`: this node emits ITS consumers' codes that way.
-        self.emit_shift = False
         zs = None
         if self.act.lo >= 0:
             zs = (torch.zeros(1, device=w_scale.device) if self._kzp is None else self._kzp.detach().float().reshape(-1)[:1]) - 128.0
@@ -205,13 +231,36 @@ class _PlanLayer(nn.Module):
         for name in ("bias_fold", "x_off", "tap_sums"):
             self.register_buffer(name, None, persistent=False)
         self.xoff_padded = False     # the border term runs in the kernel (the *_xoff entry points)
+
+    def _structure(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False, narrow=False, pad_shortcut=None,
+                   emit_shift=False):
+        """What the plan's passes read off a node - the layer's shape and quantisers, and what the main pass decided for it
+        (_Decision.options).  The whole of a `dry_run="chains"` stand-in; needs no GPU."""
+        self.layer, self.act, self.kind = layer, spec.act, spec.kind
+        self.relu, self.emit, self.want_out, self.pool = bool(relu), emit, bool(want_out), pool
+        # ReLU6 fused into the epilogue (DLMCQ_ACT_RELU6).  `relu` keeps meaning ReLU alone: the chain / dual / block-end decisions and
+        # the kernels that know no upper bound read it, and they leave ReLU6 layers alone
+        self.relu6 = bool(relu6)
+        w = layer.weight
+        conv, k = w.dim() == 4, w.shape[0]
+        # channel counts that are no multiple of 64 (the K step of the matrix-core kernel) are zero-padded: padded output
+        # channels have zero weights and bias, so their value is 0 and their code is the consumer's code of 0
+        self.k, self.k_pad = k, (_ceil64(k) if self.kind in ("gemm", "dw") and conv else k)
+        self.c = k if self.kind == "dw" else w.shape[1]       # (depthwise: one input channel per output channel)
+        if self.kind != "stem":
+            self.c_pad = _ceil64(self.c) if conv else self.c
+        w_off = spec.w_off
+        if w_off is not None:
+            w_off = self._padk((w_off.expand(k) if w_off.numel() == 1 else w_off).to(spec.w_scale.device), 0.0)
+        self.register_buffer("w_off", w_off, persistent=False)
         # narrow fp32 rows (fuse_inference(narrow_rows=True); Int8Layer only): a channel-padded layer reads its fp32 shortcut and writes its
         # fp32 output k wide - dense, no slice on the way out - while its codes stay k_pad wide (dlmcq_conv2d_i8_nhwc_narrow)
-        self.narrow = False
+        self.narrow = bool(narrow)
         # a pad shortcut (fuse_inference(pad_shortcuts=True); Int8Layer only): (stride, leading zero channels) of an option-A shortcut
         # `F.pad(x[:, :, ::s, ::s], (0, 0, 0, 0, lo, hi))` - the node's second argument is then the SOURCE x, read in place by the
         # epilogue (K.PadShortcut, dlmcq_conv2d_i8_nhwc_padres: the narrow path, at k == k_pad too)
-        self.pad_shortcut = None
+        self.pad_shortcut = pad_shortcut
+        self.emit_shift = bool(emit_shift)      # (see __init__; stand-ins: False - the chain pass clears it anyway)
 
     def _fold_offset(self, tap):
         """A float activation offset o (act.xoff): `tap` [k_pad, R, S] (float64, on the device) = per output channel and tap the sum of the
@@ -224,7 +273,7 @@ class _PlanLayer(nn.Module):
         self.register_buffer("bias_fold", (b + o * tap.sum(dim=(1, 2))).to(torch.float32).contiguous(), persistent=False)
         self.register_buffer("x_off", self.act.zp.detach().to(torch.float32).reshape(-1)[:1].to(tap.device).contiguous(), persistent=False)
         lay = self.layer
-        self.xoff_padded = lay.weight.dim() == 4 and int(lay.padding[0]) > 0
+        self.xoff_padded = _border_term(self.act, lay)
         if self.xoff_padded:
             self.register_buffer("tap_sums", tap.permute(1, 2, 0).reshape(-1, tap.shape[0]).to(torch.float32).contiguous(), persistent=False)
 
@@ -308,8 +357,7 @@ class Int8Layer(_PlanLayer):
     def __init__(self, layer, spec, **kw):
         super().__init__(layer, spec, **kw)
         w = layer.weight.detach()
-        c = w.shape[1]
-        self.c, self.c_pad = c, (_ceil64(c) if w.dim() == 4 else c)
+        c = self.c
         if self._w_codes is None and self.c_pad == c and self.k_pad == self.k:
             wq, wsum = K.quantize_weight_krsc(w, self.w_scale, self.w_lo, self.w_hi)
         else:
@@ -411,7 +459,6 @@ class DwInt8Layer(Int8Layer):
     def __init__(self, layer, spec, **kw):
         _PlanLayer.__init__(self, layer, spec, **kw)
         w = layer.weight.detach()
-        self.c, self.c_pad = self.k, self.k_pad
         if self._w_codes is not None:
             q = _weight_codes(self)                                                # [C, 1, R, S]
         else:
@@ -541,6 +588,31 @@ class DwPwInt8Layer(nn.Module):
         return pw._finish(None, out)
 
 
+# ------------------------------------------------------------------------- graph surgery of the passes
+def _outputs_read(node):
+    """{i: the `node[i]` getitem} over the readers of plan node `node`; None if anything else reads it (or two read one output)."""
+    gets = {u.args[1]: u for u in node.users if u.op == "call_function" and u.target is operator.getitem}
+    return gets if len(gets) == len(node.users) else None
+
+
+def _call_plan_module(gm, after, name, module, args, outputs=(0, 1)):
+    """Add `module` to the plan as `name`, called with `args` behind node `after`.  Returns the call and {i: its `[i]` getitem}, made
+    in the order of `outputs`."""
+    gm.add_module(name, module)
+    with gm.graph.inserting_after(after):
+        node = gm.graph.call_module(name, args=args)
+    with gm.graph.inserting_after(node):
+        return node, {i: gm.graph.call_function(operator.getitem, (node, i)) for i in outputs}
+
+
+def _settle(gm, changed=True):
+    """The end of a rewriting pass: drop what nothing reads any more, check the graph, regenerate its code."""
+    if changed:
+        gm.graph.eliminate_dead_code()
+        gm.graph.lint()
+        gm.recompile()
+
+
 def _dwpw_pass(gm, report):
     """Depthwise 3x3 -> pointwise 1x1 (a MobileOne / MobileNet unit): replace the two plan nodes by one DwPwInt8Layer where the pointwise
     layer is the only reader of the depthwise layer's codes and both emit codes only."""
@@ -557,8 +629,8 @@ def _dwpw_pass(gm, report):
         if not (tuple(lay.weight.shape[2:]) == (3, 3) and lay.stride[0] == 1 and lay.padding[0] == 1 and lay.dilation[0] == 1 and dw.pool is None and
                 dw.emit is not None and not dw.want_out and (dw.emit.lo, dw.emit.hi) == (0, 255) and not dw.emit_shift and dw.k_pad % 64 == 0):
             continue
-        gets = {u.args[1]: u for u in nd.users if u.op == "call_function" and u.target is operator.getitem}
-        if len(gets) != len(nd.users) or 1 not in gets or (0 in gets and gets[0].users):
+        gets = _outputs_read(nd)
+        if gets is None or 1 not in gets or (0 in gets and gets[0].users):
             continue
         g1 = gets[1]
         if len(g1.users) != 1:
@@ -573,25 +645,17 @@ def _dwpw_pass(gm, report):
         if not (pl.weight.dim() == 4 and tuple(pl.weight.shape[2:]) == (1, 1) and pl.stride[0] == 1 and pl.padding[0] == 0 and pw.pool is None and
                 pw.emit is not None and not pw.want_out and not pw.emit_shift and pw.c_pad == dw.k_pad and pw.k_pad in K.DWPW_WIDTHS):
             continue
-        pgets = {u.args[1]: u for u in npw.users if u.op == "call_function" and u.target is operator.getitem}
-        if len(pgets) != len(npw.users) or (0 in pgets and pgets[0].users):
+        pgets = _outputs_read(npw)
+        if pgets is None or (0 in pgets and pgets[0].users):
             continue
-        name = f"_int8_dwpw_{count}"
+        _, outs = _call_plan_module(gm, npw, f"_int8_dwpw_{count}", DwPwInt8Layer(dw, pw), nd.args, outputs=(1,))
         count += 1
-        gm.add_module(name, DwPwInt8Layer(dw, pw))
-        with graph.inserting_after(npw):
-            nc = graph.call_module(name, args=nd.args)
-        with graph.inserting_after(nc):
-            codes = graph.call_function(operator.getitem, (nc, 1))
         if 1 in pgets:
-            pgets[1].replace_all_uses_with(codes)
+            pgets[1].replace_all_uses_with(outs[1])
         for n in list(pgets.values()) + [npw] + list(gets.values()) + [nd]:
             graph.erase_node(n)
     report.dwpw = count
-    if count:
-        graph.eliminate_dead_code()
-        graph.lint()
-        gm.recompile()
+    _settle(gm, count)
 
 
 def _pointwise(plan):
@@ -626,8 +690,8 @@ def _chain_pass(gm, report):
         if not (a.emit is not None and (a.emit.lo, a.emit.hi) == (0, 255) and not a.emit.needs_g):
             continue
         mc = (main if main is not None else a).c       # channels of the unit-stride operand
-        gets = {u.args[1]: u for u in na.users if u.op == "call_function" and u.target is operator.getitem}
-        if len(gets) != len(na.users) or 1 not in gets:
+        gets = _outputs_read(na)
+        if gets is None or 1 not in gets:
             continue
         g1 = gets[1]
         nb = next((u for u in g1.users if u.op == "call_module" and u.args == (g1,) and isinstance(modules.get(u.target), Int8Layer) and
@@ -638,17 +702,13 @@ def _chain_pass(gm, report):
         if nb is None:
             continue
         b = modules[nb.target]
-        bgets = {u.args[1]: u for u in nb.users if u.op == "call_function" and u.target is operator.getitem}
-        if len(bgets) != len(nb.users) or (0 in bgets and bgets[0].users):
+        bgets = _outputs_read(nb)
+        if bgets is None or (0 in bgets and bgets[0].users):
             continue
-        name = f"_int8_chain_{count}"
-        count += 1
         a.emit_shift = False        # the chain kernel's second GEMM reads those codes in place, as unsigned bytes
-        gm.add_module(name, ChainInt8Layer(a, b, want_codes=len(g1.users) > 1, short=short, main=main))
-        with graph.inserting_after(na):
-            nc = graph.call_module(name, args=na.args)
-        with graph.inserting_after(nc):
-            outs = [graph.call_function(operator.getitem, (nc, i)) for i in (2, 1, 0)][::-1]
+        _, outs = _call_plan_module(gm, na, f"_int8_chain_{count}", ChainInt8Layer(a, b, want_codes=len(g1.users) > 1, short=short, main=main),
+                                    na.args, outputs=(2, 1, 0))
+        count += 1
         if 0 in gets:
             gets[0].replace_all_uses_with(outs[0])
         for u in list(g1.users):
@@ -659,10 +719,7 @@ def _chain_pass(gm, report):
         for n in list(bgets.values()) + [nb] + list(gets.values()) + [na]:
             graph.erase_node(n)
     report.chained = count
-    if count:
-        graph.eliminate_dead_code()
-        graph.lint()
-        gm.recompile()
+    _settle(gm, count)
 
 
 # (C, Ca, Cb, K2) of the pairs _recompute_pass rewrites: the shapes whose pair won when measured (LABNOTES 17), among those the kernel is
@@ -875,7 +932,7 @@ def _avgpool_window(node, modules):
 
 def _avgpool_pass(gm, report, planned, dry_run):
     """Windowed average pools (fuse_inference(avg_pools=True)): `AvgPool2d(s, s) -> plan convolution` becomes a node that hands the
-    convolution its activation codes (AvgPoolLayer).  `planned`: plan node -> what the main pass decided for it; whatever that is for
+    convolution its activation codes (AvgPoolLayer).  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for
     the convolution behind the pool (dual operand, own node, narrow, chain) stays - only its input changes, from fp32 to codes."""
     graph = gm.graph
     modules = dict(gm.named_modules())
@@ -883,15 +940,15 @@ def _avgpool_pass(gm, report, planned, dry_run):
 
     def reader(u, pool):
         """(activation spec, convolution) with which plan node `u` reads `pool` as codes, else None."""
-        info = planned.get(u)
-        if info is None or info["kind"] != "gemm":
+        d = planned.get(u)
+        if d is None or d.spec.kind != "gemm":
             return None
-        if info["dual"]:
-            ops = [(info["dual_inputs"][i], (info["mod"], info["dual_mod"])[i]) for i in (0, 1) if u.args[i] is pool]
+        if d.dual:
+            ops = [(d.dual_inputs[i], (d.mod, d.dual_mod)[i]) for i in (0, 1) if u.args[i] is pool]
             if not ops or len({a.key for a, _ in ops}) != 1:
                 return None
         elif u.args[0] is pool and pool not in u.args[1:]:
-            ops = [(info["spec"][0], info["mod"])]
+            ops = [(d.spec.act, d.mod)]
         else:
             return None
         a, m = ops[0]
@@ -911,27 +968,18 @@ def _avgpool_pass(gm, report, planned, dry_run):
         if c % 4 or c < 4 or any(int(readers[u][1].weight.shape[1]) != c for u in takers):
             continue
         c_pad = _ceil64(c)
-        # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (the main
-        # pass's takes_shifted: no channel padding; a dual node is never handed shifted codes there either)
-        shift = bool(0 <= emit.lo and emit.hi <= 255 and c_pad == c and not any(planned[u]["dual"] for u in takers))
-        zp_fill = 0 if (emit.xoff or emit.zp is None) else int(float(emit.zp.reshape(-1)[0]))      # Int8Layer's _zp_fill (read once)
+        # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (a dual node
+        # is never handed shifted codes by the main pass either)
+        shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers])
         want_out = len(takers) != len(readers)
-        name = f"_int8_avgpool_{count}"
+        module = _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, _zp_fill(emit) - (128 if shift else 0), shift)
+        _, outs = _call_plan_module(gm, pool, f"_int8_avgpool_{count}", module, (x,))
         count += 1
-        gm.add_module(name, _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, zp_fill - (128 if shift else 0), shift))
-        with graph.inserting_after(pool):
-            node = graph.call_module(name, args=(x,))
-        with graph.inserting_after(node):
-            out = graph.call_function(operator.getitem, (node, 0))
-            codes = graph.call_function(operator.getitem, (node, 1))
         for u in list(pool.users):
-            u.replace_input_with(pool, codes if u in takers else out)
+            u.replace_input_with(pool, outs[1] if u in takers else outs[0])
         graph.erase_node(pool)
     report.avg_pools = count
-    if count:
-        graph.eliminate_dead_code()
-        graph.lint()
-        gm.recompile()
+    _settle(gm, count)
 
 
 def _pool_dims(node, modules):
@@ -997,7 +1045,7 @@ def _flatten_rank(node, src, rank):
 
 def _gap_pass(gm, report, mode, planned, dry_run):
     """Global-average-pool heads (fuse_inference(gap_head=...)): `pool -> flatten -> quantised Linear` becomes a node that hands the
-    Linear its activation codes [N, C].  `planned`: plan node -> what the main pass decided for it."""
+    Linear its activation codes [N, C].  `planned`: plan node -> what the main pass decided for it (_Decision)."""
     graph = gm.graph
     modules = dict(gm.named_modules())
     count = 0
@@ -1031,11 +1079,11 @@ def _gap_pass(gm, report, mode, planned, dry_run):
             continue
         # ---- the readers: plan-eligible linear layers, through their activation argument, take codes ----
         def linear_act(u):
-            info = planned.get(u)
-            if info is None or info["dual"] or info["kind"] != "gemm" or u.args[0] is not last or last in u.args[1:]:
+            d = planned.get(u)
+            if d is None or d.dual or d.spec.kind != "gemm" or u.args[0] is not last or last in u.args[1:]:
                 return None
-            w = info["mod"].weight
-            return info["spec"][0] if w.dim() == 2 and w.shape[1] % 64 == 0 else None
+            w = d.mod.weight
+            return d.spec.act if w.dim() == 2 and w.shape[1] % 64 == 0 else None
         users = real_users(last, inside)
         acts = {u: linear_act(u) for u in users}
         keys = [a.key for a in acts.values() if a is not None]
@@ -1047,31 +1095,24 @@ def _gap_pass(gm, report, mode, planned, dry_run):
         want_out = len(takers) != len(users)
         # ---- the producer: a plan convolution read by the pool alone becomes the fused head (True: where profitable; "fused": always) ----
         prod = x.args[0] if x.op == "call_function" and x.target is operator.getitem and x.args[1] == 0 else None
-        info = planned.get(prod)
+        d = planned.get(prod)
         fused = False
-        if mode in (True, "fused") and info is not None and real_users(x, inside) == [pool]:
-            w = info["mod"].weight
-            gets = [u for u in prod.users if u.op == "call_function" and u.target is operator.getitem]
-            fused = (info["kind"] == "gemm" and not info["dual"] and info["pool"] is None and info["emit"] is None and w.dim() == 4 and
-                     info.get("pad_shortcut") is None and
-                     len(gets) == len(prod.users) and all(g is x or not real_users(g, inside) for g in gets) and info["spec"][5] is None and
-                     K.gap_head_supported(_ceil64(w.shape[1]), w.shape[0], 1, 1, w.shape[2], info["mod"].stride[0], info["mod"].padding[0]) and
+        if mode in (True, "fused") and d is not None and real_users(x, inside) == [pool]:
+            w = d.mod.weight
+            gets = _outputs_read(prod)
+            fused = (d.spec.kind == "gemm" and not d.dual and d.pool is None and d.emit is None and w.dim() == 4 and d.pad_shortcut is None and
+                     gets is not None and all(g is x or not real_users(g, inside) for g in gets.values()) and d.spec.symmetric and
+                     K.gap_head_supported(_ceil64(w.shape[1]), w.shape[0], 1, 1, w.shape[2], d.mod.stride[0], d.mod.padding[0]) and
                      w.shape[2] == w.shape[3] and (mode == "fused" or K.gap_head_profitable(_ceil64(w.shape[1]), w.shape[0])))
         name = f"_int8_gap_{count}"
         count += 1
         if dry_run:
-            gm.add_module(name, _DryNode())
-        elif fused:
-            gm.add_module(name, GapHeadLayer(modules[prod.target], emit, want_out))
+            module = _DryNode()
         else:
-            gm.add_module(name, GapLayer(emit, want_out))
-        with graph.inserting_after(last):
-            node = graph.call_module(name, args=tuple(prod.args) if fused else (x,))
-        with graph.inserting_after(node):
-            out = graph.call_function(operator.getitem, (node, 0))
-            codes = graph.call_function(operator.getitem, (node, 1))
+            module = GapHeadLayer(modules[prod.target], emit, want_out) if fused else GapLayer(emit, want_out)
+        _, outs = _call_plan_module(gm, last, name, module, tuple(prod.args) if fused else (x,))
         for u in users:
-            u.replace_input_with(last, codes if u in takers else out)
+            u.replace_input_with(last, outs[1] if u in takers else outs[0])
         def erase_tree(n):     # `n` and what hangs on it: by now the chain's reshapes and their batch-size reads only
             for u in list(n.users):
                 erase_tree(u)
@@ -1084,10 +1125,7 @@ def _gap_pass(gm, report, mode, planned, dry_run):
             erase_tree(prod)
             report.fp32_outputs -= 1
         report.gap_heads.append((name, "fused" if fused else "separate"))
-    if count:
-        graph.eliminate_dead_code()
-        graph.lint()
-        gm.recompile()
+    _settle(gm, count)
 
 
 class StemLayer(_PlanLayer):
@@ -1096,7 +1134,6 @@ class StemLayer(_PlanLayer):
 
     def __init__(self, layer, spec, **kw):
         super().__init__(layer, spec, **kw)
-        self.c = layer.weight.shape[1]
         if self._w_codes is None:
             wq, wsum = K.quantize_weight_stem(layer.weight, self.w_scale, self.w_lo, self.w_hi)
         else:     # the module's own integer codes (asymmetric / per-channel QBase weights) in the stem kernel's [K, R, 8 taps, 4] layout
@@ -1136,24 +1173,18 @@ class StemLayer(_PlanLayer):
 
 class _DryNode(nn.Module):
     def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=True) builds the plan's structure only")
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
 
 
 class _DryInt8Layer(Int8Layer):
     """fuse_inference(dry_run="chains"): an Int8Layer's structure - what the chain-level passes decide on - without its weight codes
     (quantising them needs the GPU).  It cannot be run."""
 
-    def __init__(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False):
+    def __init__(self, layer, spec, **decided):
         nn.Module.__init__(self)
-        self.layer, self.act, self.kind, self.w_off = layer, spec[0], spec[4], spec[5]
-        self.relu, self.emit, self.want_out, self.pool, self.relu6 = bool(relu), emit, bool(want_out), pool, bool(relu6)
-        w = layer.weight
-        self.k, self.c = int(w.shape[0]), int(w.shape[1])
-        self.k_pad, self.c_pad = (_ceil64(self.k), _ceil64(self.c)) if w.dim() == 4 else (self.k, self.c)
-        self.narrow, self.pad_shortcut, self.emit_shift = False, None, False
+        self._structure(layer, spec, **decided)
 
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+    forward = _DryNode.forward
 
 
 def _is_int8(m):
@@ -1177,6 +1208,21 @@ class FusionReport:
         self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
+
+    def count(self, d):
+        """One plan node of the main pass (its _Decision)."""
+        self.layers += 1 + d.dual
+        self.dual += d.dual
+        self.stem += d.spec.kind == "stem"
+        self.pooled += d.pool is not None
+        self.relu += d.relu
+        self.relu6 += d.relu6
+        self.act_offset += d.spec.act.xoff + (d.dual and d.dual_spec.act.xoff)
+        self.residual += d.residual is not None
+        self.narrow += d.narrow
+        self.pad_shortcuts += d.pad_shortcut is not None
+        self.emit += d.emit is not None
+        self.fp32_outputs += d.want_out
 
     def __repr__(self):
         return (f"FusionReport(int8 layers={self.layers}, relu fused={self.relu}, relu6 fused={self.relu6}, residual fused={self.residual}, "
@@ -1243,12 +1289,13 @@ def _is_relu6(node, modules):
 
 
 _PAD_FNS = tuple({F.pad, torch._C._nn.pad})
+_PadShortcut = collections.namedtuple("_PadShortcut", "source stride lo hi nodes")
 
 
 def _pad_shortcut(node):
     """`node` as an option-A shortcut (He et al. 2016, section 4.2: subsample, zero-pad the channels) - `F.pad(t, (0, 0, 0, 0, lo, hi))`,
-    constant mode, value 0, of `t = x[:, :, ::s, ::s]` or of x itself - as (x, s, lo, hi, the nodes to erase), each node the only reader
-    of the one before; None for anything else."""
+    constant mode, value 0, of `t = x[:, :, ::s, ::s]` or of x itself - as _PadShortcut(x, s, lo, hi, the nodes to erase), each node the
+    only reader of the one before; None for anything else."""
     if node.op != "call_function" or node.target not in _PAD_FNS or len(node.users) != 1:
         return None
     names = ("input", "pad", "mode", "value")
@@ -1264,7 +1311,7 @@ def _pad_shortcut(node):
         return None
     # (`t[i]` with an integer i is a plan node's output, not a subscript of a tensor)
     if not (t.op == "call_function" and t.target is operator.getitem and len(t.args) == 2 and not isinstance(t.args[1], int)):
-        return t, 1, int(pad[4]), int(pad[5]), [node]          # F.pad alone: stride 1
+        return _PadShortcut(t, 1, int(pad[4]), int(pad[5]), [node])          # F.pad alone: stride 1
     if len(t.users) != 1 or t.kwargs or not isinstance(t.args[0], fx.Node) or not isinstance(t.args[1], tuple):
         return None
     idx = t.args[1]
@@ -1274,7 +1321,7 @@ def _pad_shortcut(node):
     s = idx[2].step
     if (idx[2].start, idx[2].stop, idx[3].start, idx[3].stop) != (None,) * 4 or not isinstance(s, int) or isinstance(s, bool) or s < 1 or idx[3].step != s:
         return None
-    return t.args[0], s, int(pad[4]), int(pad[5]), [node, t]
+    return _PadShortcut(t.args[0], s, int(pad[4]), int(pad[5]), [node, t])
 
 
 def _pool_params(node, modules):
@@ -1488,6 +1535,240 @@ def _codes_from_blob(mod_name, blob, layer):
     return q.reshape(rec["shape"]).to(torch.int16)
 
 
+class _Decision:
+    """What the main pass decided for one plan node: the wrapper `node` calls (`mod`, its `spec`) and what it absorbs."""
+
+    def __init__(self, node, mod, spec):
+        self.node, self.mod, self.spec = node, mod, spec
+        self.chain = [node]                    # the graph nodes the plan node replaces: the wrapper's, (the add), (the ReLU / ReLU6), (the max-pool)
+        self.residual = None                   # the other addend of the folded add
+        self.relu = self.relu6 = False
+        self.pool = None                       # (kernel, stride, padding) of the max-pool behind it
+        self.pad_shortcut = None               # `residual` is an option-A shortcut (_PadShortcut), read in place at its source
+        self.emit, self.takers = None, ()      # the quantiser (_ActSpec) of the readers that take codes, and those readers
+        self.want_out, self.narrow = True, False       # someone reads the fp32 output; fp32 rows at the real width
+        self.dual_mod = self.dual_spec = None  # the convolution on the shortcut, run by the same (dual) kernel, and its spec
+        self.dual_inputs = None                # a dual node's activation quantisers: of its input 0, of its input 1
+
+    @property
+    def dual(self):
+        return self.dual_inputs is not None
+
+    @property
+    def last(self):
+        """The graph node whose readers become the plan node's."""
+        return self.chain[-1]
+
+    def args(self):
+        """The plan node's inputs: the activation(s), or the activation and the fp32 shortcut (a pad shortcut: its source)."""
+        if self.residual is None:
+            return (self.node.args[0],)
+        if self.dual:
+            return self.node.args[0], self.residual.args[0]
+        return self.node.args[0], (self.residual if self.pad_shortcut is None else self.pad_shortcut.source)
+
+    def options(self):
+        """The decision as _PlanLayer._structure takes it."""
+        return dict(relu=self.relu, relu6=self.relu6, emit=self.emit, want_out=self.want_out, pool=self.pool, narrow=self.narrow,
+                    pad_shortcut=None if self.pad_shortcut is None else (self.pad_shortcut.stride, self.pad_shortcut.lo))
+
+
+def _sole_user(node):
+    return next(iter(node.users)) if len(node.users) == 1 else None
+
+
+class _MainPass:
+    """fuse_inference's main pass: every eligible wrapper becomes a plan node `(fp32 or None, codes or None)` that has absorbed the add,
+    the activation and the max-pool behind it.  Per wrapper, in graph order: decide (reads the graph and the specs, changes nothing),
+    build (the module, by mode), splice (the graph), FusionReport.count.  A new flag is a field of _Decision set in `decide`, handed to
+    the node by `_Decision.options` / `_PlanLayer._structure` and counted in `FusionReport.count`."""
+
+    def __init__(self, gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts):
+        self.gm, self.graph, self.modules = gm, gm.graph, dict(gm.named_modules())
+        self.dry_run, self.weight_blob, self.dwpw = dry_run, weight_blob, dwpw
+        self.relu6, self.act_offsets, self.narrow_rows, self.pad_shortcuts = relu6, act_offsets, narrow_rows, pad_shortcuts
+        self.specs, self.skipped = {}, []      # wrapper -> its _LayerSpec or None, made when first asked for; those without, in that order
+        self.planned = {}                      # plan node -> its _Decision (the average-pool and head passes read it)
+
+    def run(self, report):
+        live = set(self.graph.nodes)
+        for node in list(self.graph.nodes):
+            d = self.decide(node) if node in live else None       # (not live: absorbed into an earlier node)
+            if d is not None:
+                live.difference_update(self.splice(d, self.build(d)))
+                report.count(d)
+        report.skipped += self.skipped
+        _settle(self.gm)
+        return self.planned
+
+    def spec_of(self, node):
+        if node.op != "call_module" or len(node.args) != 1 or node.kwargs:
+            return None
+        if node.target not in self.specs:
+            mod = self.modules.get(node.target)      # (a plan node's module is not in here: no spec)
+            self.specs[node.target] = _frozen_spec(mod, self.act_offsets) if isinstance(mod, (QBase, FSPTQBase)) else None
+            if self.specs[node.target] is None and isinstance(mod, (QBase, FSPTQBase, RootQBase)):
+                self.skipped.append(node.target)
+        return self.specs[node.target]
+
+    def accepts(self, u, t):
+        """The activation quantiser `u` applies to tensor `t`, if `u` can take `t` as codes instead."""
+        d = self.planned.get(u)
+        if d is not None and d.dual:
+            acts = {d.dual_inputs[i].key: d.dual_inputs[i] for i in (0, 1) if u.args[i] is t}
+            return next(iter(acts.values())) if len(acts) == 1 else None
+        s = self.spec_of(u) if u.args and u.args[0] is t else None
+        return s.act if s is not None and s.kind in ("gemm", "dw") else None
+
+    def source_channels(self, src):
+        """Channels of `src` if its fp32 value is known to be dense channels_last at its real width - the fp32 output of a plan node
+        that is unpadded or narrow, or the network input as a planned convolution reads it - else None."""
+        if src.op == "call_function" and src.target is operator.getitem and src.args[1] == 0 and src.args[0] in self.planned:
+            d = self.planned[src.args[0]]
+            w = d.mod.weight
+            ok = w.dim() == 4 and d.spec.kind in ("gemm", "dw") and d.pool is None and (w.shape[0] % 64 == 0 or d.narrow)
+            return int(w.shape[0]) if ok else None
+        # the network input: its width is read off a planned (ungrouped) convolution that takes it as its activation; with no such
+        # reader yet (or only readers planned later) the answer is None and nothing folds.  Dense only once it is channels_last: an
+        # NCHW-contiguous input is converted per call by Int8Layer.forward (one copy of the input, in place of the slice and the pad)
+        if src.op == "placeholder":
+            for u in src.users:
+                d = self.planned.get(u)
+                if d is not None and u.args[0] is src and d.mod.weight.dim() == 4 and d.mod.groups == 1:
+                    return int(d.mod.weight.shape[1])
+        return None
+
+    # ---- decide: add, then ReLU / ReLU6, then max-pool, then pad shortcut, then readers, then dual, then narrow (later ones read earlier ones)
+    def decide(self, node):
+        """The _Decision for the wrapper `node` calls, or None if it has no spec."""
+        spec = self.spec_of(node)
+        if spec is None:
+            return None
+        mod, modules = self.modules[node.target], self.modules
+        d = _Decision(node, mod, spec)
+        # the chain  layer -> (+ shortcut) -> ReLU, each link the sole user of the previous one.  (The stem kernel has no shortcut input;
+        # a layer whose output channels are zero-padded to a multiple of 64 - MobileNetV2's 24 / 96 / 160-channel projections, CIFAR
+        # ResNets' 16 / 32 - computes a k_pad-wide tile: the k-wide fp32 shortcut does not fit it, so the add stays outside the kernel)
+        wn = mod.weight
+        unpadded = wn.dim() != 4 or wn.shape[0] % 64 == 0
+        # ... unless the layer runs with narrow fp32 rows (narrow_rows): a padded "gemm" convolution of k % 4 == 0 channels without the
+        # border term of a float activation offset (the *_xoff kernels have no narrow form)
+        can_narrow = (self.narrow_rows and spec.kind == "gemm" and not unpadded and wn.shape[0] % 4 == 0 and not _border_term(spec.act, mod))
+        add = _sole_user(node)
+        if spec.kind == "gemm" and (unpadded or can_narrow) and add is not None and _is_add(add) and add.args[0] is not add.args[1]:
+            d.residual = add.args[1] if add.args[0] is node else add.args[0]
+            d.chain.append(add)
+        act = _sole_user(d.last)
+        if act is not None and (_is_relu(act, modules) or (self.relu6 and _is_relu6(act, modules))):
+            d.relu = _is_relu(act, modules)
+            d.relu6 = not d.relu
+            d.chain.append(act)
+        self._decide_pool(d)
+        self._decide_pad_shortcut(d)
+        self._decide_readers(d)
+        self._decide_dual(d, unpadded)
+        # every narrow-capable layer that writes fp32 (or reads a shortcut) does so at the real width
+        d.narrow = bool(can_narrow and (d.want_out or d.residual is not None))
+        return d
+
+    def _decide_pool(self, d):
+        """A max-pool read only by int8 layers of one quantiser runs on the codes (monotone quantiser)."""
+        mp = _sole_user(d.last)
+        params = _pool_params(mp, self.modules) if mp is not None else None
+        if params is None or d.mod.weight.shape[0] % 4 != 0:
+            return
+        cons = [self.accepts(u, mp) for u in mp.users]
+        on_codes = cons and all(c is not None for c in cons) and len({c.key for c in cons}) == 1
+        # the first-layer kernel pools in fp32 itself (any consumers); elsewhere the pool runs on the emitted codes
+        # (the pooling first-layer kernel has no weight-offset term, and ReLU alone)
+        in_stem = (d.spec.kind == "stem" and params == (3, 2, 1) and d.mod.weight.shape[0] <= 64 and d.spec.symmetric and not d.relu6 and
+                   not d.spec.act.xoff)
+        if on_codes or in_stem:
+            d.pool = params
+            d.chain.append(mp)
+
+    def _decide_pad_shortcut(self, d):
+        """An option-A shortcut (pad_shortcuts): the epilogue reads its source in place.  (Not for a layer with the border term of a
+        float activation offset: it runs on the *_xoff kernels, which have no narrow form - the exclusion `can_narrow` and the dual
+        decision carry; its add keeps folding with the materialised tensor.)"""
+        res = d.residual
+        if not self.pad_shortcuts or res is None or res.op != "call_function" or _border_term(d.spec.act, d.mod):
+            return
+        m = _pad_shortcut(res)
+        cs = self.source_channels(m.source) if m is not None else None
+        if cs is not None and m.lo % 4 == 0 and cs % 4 == 0 and cs >= 4 and m.lo + cs + m.hi == d.mod.weight.shape[0]:
+            d.pad_shortcut = m
+
+    def _decide_readers(self, d):
+        """Who reads the result: int8 layers fed ONLY through their activation argument take codes (the most common quantiser's)."""
+        consumers, fp32_needed = {}, not d.last.users
+        for u in d.last.users:
+            a = self.accepts(u, d.last)
+            if a is None:
+                fp32_needed = True
+            else:
+                consumers.setdefault(a.key, []).append((u, a))
+        if consumers:
+            key = max(consumers, key=lambda k: len(consumers[k]))
+            d.takers = [u for u, _ in consumers[key]]
+            d.emit = consumers[key][0][1]
+            fp32_needed = fp32_needed or len(consumers) > 1
+        d.want_out = bool(fp32_needed or d.emit is None)
+
+    def _decide_dual(self, d, unpadded):
+        """The shortcut is itself a not-yet-planned int8 convolution read by nobody else: one dual kernel (ReLU alone, symmetric weights,
+        no border term).  (A narrow layer is never a dual operand: the convolution on its shortcut runs as its own node.)"""
+        res = d.residual
+        other = self.spec_of(res) if res is not None and res.op == "call_module" else None
+        omod = self.modules[res.target] if other is not None else None
+        if (other is not None and unpadded and other.kind == "gemm" and list(res.users) == [d.chain[1]] and d.spec.symmetric and other.symmetric and
+                d.mod.weight.dim() == 4 and omod.weight.dim() == 4 and not d.relu6 and
+                not _border_term(d.spec.act, d.mod) and not _border_term(other.act, omod)):
+            d.dual_mod, d.dual_spec, d.dual_inputs = omod, other, (d.spec.act, other.act)
+
+    # ---- build
+    def build(self, d):
+        """The module of the plan node: the plan layer (real), a structural stand-in of an Int8Layer (`dry_run="chains"`) or a placeholder."""
+        cls = {"gemm": Int8Layer, "dw": DwInt8Layer}.get(d.spec.kind, StemLayer)
+        if self.dry_run == "chains" and cls is Int8Layer:    # ... a structural stand-in the chain-level passes can read
+            plan = _DryInt8Layer(d.mod, d.spec, **d.options())
+            return DualInt8Layer(plan, _DryInt8Layer(d.dual_mod, d.dual_spec)) if d.dual else plan
+        if self.dry_run:      # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
+            return _DryNode()
+        # codes of an unsigned-byte quantiser read only by matrix-core layers (no channel padding, no pooling on the way)
+        # travel re-centred (see _PlanLayer.__init__); the consumers recognise them by dtype
+        shift = (cls is Int8Layer and d.pool is None and (d.mod.weight.dim() != 4 or d.mod.weight.shape[0] % 64 == 0) and
+                 _emits_shifted(d.emit, [(self.spec_of(u), self.modules.get(u.target)) for u in d.takers], self.dwpw))
+        plan = cls(d.mod, self._from_blob(d.node.target, d.spec), emit_shift=shift, **d.options())
+        return DualInt8Layer(plan, Int8Layer(d.dual_mod, self._from_blob(d.residual.target, d.dual_spec))) if d.dual else plan
+
+    def _from_blob(self, name, spec):
+        """`spec`, the layer's weight codes coming from the integer checkpoint (expanded on the device) where it holds them."""
+        blob = self.weight_blob
+        if blob is None or name not in blob["layers"]:
+            return spec
+        return spec.with_codes(lambda: _codes_from_blob(name, blob, self.modules[name]))
+
+    # ---- splice
+    def splice(self, d, module):
+        """Put the plan node behind the last node it absorbs, hand its readers the codes or the fp32 output, erase what it replaces.
+        Returns the erased nodes the pass has not visited yet and must not plan."""
+        fused, outs = _call_plan_module(self.gm, d.last, f"_int8_plan_{len(self.planned)}", module, d.args())
+        self.planned[fused] = d
+        for u in list(d.last.users):
+            if u not in outs.values():
+                u.replace_input_with(d.last, outs[1] if u in d.takers else outs[0])
+        for n in reversed(d.chain):
+            self.graph.erase_node(n)
+        if d.dual:
+            self.specs[d.residual.target] = None   # never planned on its own
+        # the convolution on the shortcut; the pad, then the slice: their only readers are gone
+        gone = ([d.residual] if d.dual else []) + (d.pad_shortcut.nodes if d.pad_shortcut is not None else [])
+        for n in gone:
+            self.graph.erase_node(n)
+        return gone
+
+
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
                    recompute_shortcuts=None):
@@ -1581,220 +1862,13 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         raise RuntimeError(f"fuse_inference reads the model's dataflow with torch.fx and could not trace it ({type(e).__name__}: "
                            f"{e}); the module-by-module path (quantize_model(..., int8_gemm=True)) needs no tracing") from e
     gm = fx.GraphModule(model, graph)
-    modules = dict(gm.named_modules())
-    specs = {}
-
-    def spec_of(node):
-        if node.op != "call_module" or len(node.args) != 1 or node.kwargs:
-            return None
-        if node.target not in specs:
-            mod = modules[node.target]
-            specs[node.target] = _frozen_spec(mod, act_offsets) if isinstance(mod, (QBase, FSPTQBase)) else None
-            if specs[node.target] is None and isinstance(mod, (QBase, FSPTQBase, RootQBase)):
-                report.skipped.append(node.target)
-        return specs[node.target]
-
     # folded BatchNorms (merge_bn leaves nn.Identity) and eval-mode Dropout are wires, not operations
+    modules = dict(gm.named_modules())
     for node in list(graph.nodes):
         if node.op == "call_module" and isinstance(modules[node.target], (nn.Identity, nn.Dropout)) and len(node.args) == 1:
             node.replace_all_uses_with(node.args[0])
             graph.erase_node(node)
-
-    dual_inputs = {}   # dual plan node -> (activation spec of input 0, of input 1)
-
-    def accepts(u, t):
-        """The activation quantiser `u` applies to tensor `t`, if `u` can take `t` as codes instead."""
-        if u in dual_inputs:
-            acts = {dual_inputs[u][i].key: dual_inputs[u][i] for i in (0, 1) if u.args[i] is t}
-            return next(iter(acts.values())) if len(acts) == 1 else None
-        s = spec_of(u) if u.args and u.args[0] is t else None
-        return s[0] if s is not None and s[4] in ("gemm", "dw") else None
-
-    def source_channels(src):
-        """Channels of `src` if its fp32 value is known to be dense channels_last at its real width - the fp32 output of a plan node
-        that is unpadded or narrow, or the network input as a planned convolution reads it - else None."""
-        if src.op == "call_function" and src.target is operator.getitem and src.args[1] == 0 and src.args[0] in planned:
-            info = planned[src.args[0]]
-            w = info["mod"].weight
-            ok = w.dim() == 4 and info["kind"] in ("gemm", "dw") and info["pool"] is None and (w.shape[0] % 64 == 0 or info["narrow"])
-            return int(w.shape[0]) if ok else None
-        # the network input: its width is read off a planned (ungrouped) convolution that takes it as its activation; with no such
-        # reader yet (or only readers planned later) the answer is None and nothing folds.  Dense only once it is channels_last: an
-        # NCHW-contiguous input is converted per call by Int8Layer.forward (one copy of the input, in place of the slice and the pad)
-        if src.op == "placeholder":
-            for u in src.users:
-                info = planned.get(u)
-                if info is not None and u.args[0] is src and info["mod"].weight.dim() == 4 and info["mod"].groups == 1:
-                    return int(info["mod"].weight.shape[1])
-        return None
-
-    count = 0
-    planned = {}       # plan node -> what was decided for it (the gap-head pass reads it; under dry_run the modules are placeholders)
-    live = set(graph.nodes)
-    for node in list(graph.nodes):
-        if node not in live:            # absorbed into a dual kernel earlier in this loop
-            continue
-        spec = spec_of(node)
-        if spec is None:
-            continue
-        # ---- the chain  layer -> (+ shortcut) -> ReLU, each link the sole user of the previous one ----
-        chain, last, residual, relu, act6 = [node], node, None, False, False
-        users = list(last.users)
-        # (the stem kernel has no shortcut input; a layer whose output channels are zero-padded to a multiple of 64 - MobileNetV2's
-        #  24 / 96 / 160-channel projections, CIFAR ResNets' 16 / 32 - computes a k_pad-wide tile: the k-wide fp32 shortcut does not
-        #  fit it, so the add stays outside the kernel)
-        wn = modules[node.target].weight
-        unpadded = wn.dim() != 4 or wn.shape[0] % 64 == 0
-        # ... unless the layer runs with narrow fp32 rows (narrow_rows): a padded "gemm" convolution of k % 4 == 0 channels without the
-        # border term of a float activation offset (the *_xoff kernels have no narrow form)
-        can_narrow = (narrow_rows and spec[4] == "gemm" and not unpadded and wn.shape[0] % 4 == 0 and
-                      not (spec[0].xoff and int(modules[node.target].padding[0]) > 0))
-        if spec[4] == "gemm" and (unpadded or can_narrow) and len(users) == 1 and _is_add(users[0]) and users[0].args[0] is not users[0].args[1]:
-            add = users[0]
-            residual = add.args[1] if add.args[0] is last else add.args[0]
-            chain.append(add)
-            last = add
-            users = list(last.users)
-        if len(users) == 1 and _is_relu(users[0], modules):
-            relu = True
-            chain.append(users[0])
-            last = users[0]
-            users = list(last.users)
-        elif relu6 and len(users) == 1 and _is_relu6(users[0], modules):
-            act6 = True
-            chain.append(users[0])
-            last = users[0]
-            users = list(last.users)
-        # ---- a max-pool read only by int8 layers of one quantiser runs on the codes (monotone quantiser) ----
-        pool = None
-        if len(users) == 1 and _pool_params(users[0], modules) is not None and modules[node.target].weight.shape[0] % 4 == 0:
-            mp = users[0]
-            cons = [accepts(u, mp) for u in mp.users]
-            on_codes = cons and all(c is not None for c in cons) and len({c.key for c in cons}) == 1
-            # the first-layer kernel pools in fp32 itself (any consumers); elsewhere the pool runs on the emitted codes
-            in_stem = (spec[4] == "stem" and _pool_params(mp, modules) == (3, 2, 1) and modules[node.target].weight.shape[0] <= 64 and
-                       spec[5] is None and not act6 and not spec[0].xoff)   # (the pooling first-layer kernel has no weight-offset term, and ReLU alone)
-            if on_codes or in_stem:
-                pool = _pool_params(mp, modules)
-                chain.append(mp)
-                last = mp
-        # ---- an option-A shortcut (pad_shortcuts): the epilogue reads its source in place ----
-        # (not for a layer with the border term of a float activation offset: it runs on the *_xoff kernels, which have no narrow form -
-        #  the exclusion `can_narrow` and `dual` carry; its add keeps folding with the materialised tensor)
-        pad_sc = None
-        if (pad_shortcuts and residual is not None and residual.op == "call_function" and
-                not (spec[0].xoff and int(modules[node.target].padding[0]) > 0)):
-            m = _pad_shortcut(residual)
-            cs = source_channels(m[0]) if m is not None else None
-            if cs is not None and m[2] % 4 == 0 and cs % 4 == 0 and cs >= 4 and m[2] + cs + m[3] == wn.shape[0]:
-                pad_sc = m
-        # ---- who reads the result: int8 layers fed ONLY through their activation argument take codes ----
-        consumers = {}
-        fp32_needed = False
-        for u in last.users:
-            a = accepts(u, last)
-            if a is None:
-                fp32_needed = True
-            else:
-                consumers.setdefault(a.key, []).append((u, a))
-        emit, takers = None, []
-        if consumers:
-            key = max(consumers, key=lambda k: len(consumers[k]))
-            takers = [u for u, _ in consumers[key]]
-            emit = consumers[key][0][1]
-            fp32_needed = fp32_needed or len(consumers) > 1
-        if not last.users:
-            fp32_needed = True
-        name = f"_int8_plan_{count}"
-        count += 1
-        specs[name] = None
-        modules[name] = None
-        cls = {"gemm": Int8Layer, "dw": DwInt8Layer}.get(spec[4], StemLayer)
-        # the shortcut is itself a not-yet-planned int8 convolution read by nobody else: one dual kernel
-        other = spec_of(residual) if residual is not None and residual.op == "call_module" else None
-        # (a narrow layer is never a dual operand: the convolution on its shortcut runs as its own node)
-        dual = (other is not None and unpadded and other[4] == "gemm" and spec[5] is None and other[5] is None and list(residual.users) == [chain[1]] and
-                modules[node.target].weight.dim() == 4 and modules[residual.target].weight.dim() == 4 and not act6 and   # (dual kernel: ReLU alone)
-                not any(sp[0].xoff and int(modules[t].padding[0]) > 0 for sp, t in ((spec, node.target), (other, residual.target))))
-        # every such layer that writes fp32 (or reads a shortcut) does so at the real width
-        narrow = bool(can_narrow and (fp32_needed or emit is None or residual is not None))
-        if dry_run == "chains" and cls is Int8Layer:    # ... a structural stand-in the chain-level passes can read
-            opts = dict(relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
-            plan = _DryInt8Layer(modules[node.target], spec, **opts)
-            gm.add_module(name, DualInt8Layer(plan, _DryInt8Layer(modules[residual.target], other)) if dual else plan)
-        elif dry_run:     # decisions only (CPU-side tests): the node is a placeholder, nothing is quantised or launched
-            gm.add_module(name, _DryNode())
-        else:
-            def from_blob(name, sp):       # the layer's weight codes come from the integer checkpoint, expanded on the device
-                if weight_blob is None or name not in weight_blob["layers"]:
-                    return sp
-                return sp[:6] + ((lambda name=name: _codes_from_blob(name, weight_blob, modules[name])),)
-            spec = from_blob(node.target, spec)
-            if other is not None and dual:
-                other = from_blob(residual.target, other)
-            plan = cls(modules[node.target], spec, relu=relu, emit=emit, want_out=fp32_needed or emit is None, pool=pool, relu6=act6)
-            plan.narrow = narrow
-            if pad_sc is not None:
-                plan.pad_shortcut = (pad_sc[1], pad_sc[2])
-            # codes of an unsigned-byte quantiser read only by matrix-core layers (no channel padding, no pooling on the way)
-            # travel re-centred (see _PlanLayer.__init__); the consumers recognise them by dtype
-            def takes_shifted(u):
-                sp = spec_of(u) if u.op == "call_module" else None
-                m = modules.get(u.target) if u.op == "call_module" else None
-                if sp is None or m is None or m.weight.dim() != 4:
-                    return False
-                if sp[4] == "dw":      # the matrix-core depthwise kernel (csrc/conv_dwm_i8.hip) multiplies signed bytes: no re-centring of its fragments
-                    # (not with `dwpw`: the fused unit's kernel emits plain codes only)
-                    return (not dwpw and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.weight.shape[0] % 64 == 0)
-                return sp[4] == "gemm" and m.groups == 1 and m.weight.shape[1] % 64 == 0
-            plan.emit_shift = bool(cls is Int8Layer and emit is not None and 0 <= emit.lo and emit.hi <= 255 and pool is None and
-                                   plan.k_pad == plan.k and takers and all(takes_shifted(u) for u in takers))
-            gm.add_module(name, DualInt8Layer(plan, Int8Layer(modules[residual.target], other)) if dual else plan)
-        if dual:
-            args = (node.args[0], residual.args[0])
-        else:
-            args = (node.args[0],) if residual is None else (node.args[0], residual if pad_sc is None else pad_sc[0])
-        with graph.inserting_after(last):
-            fused = graph.call_module(name, args=args)
-        planned[fused] = dict(spec=spec, kind=spec[4], mod=modules[node.target], dual=bool(dual), pool=pool, emit=emit, narrow=narrow,
-                              pad_shortcut=pad_sc)
-        if dual:
-            dual_inputs[fused] = (spec[0], other[0])
-            planned[fused].update(dual_inputs=dual_inputs[fused], dual_mod=modules[residual.target])
-            chain.insert(0, residual)       # erased last (its only user, the add, goes first)
-            specs[residual.target] = None   # never planned on its own
-            report.layers += 1
-            report.dual += 1
-        with graph.inserting_after(fused):
-            out = graph.call_function(operator.getitem, (fused, 0))
-            codes = graph.call_function(operator.getitem, (fused, 1))
-        for u in list(last.users):
-            if u in (out, codes):
-                continue
-            u.replace_input_with(last, codes if u in takers else out)
-        for n in reversed(chain[1:] if dual else chain):
-            graph.erase_node(n)
-        if dual:
-            graph.erase_node(residual)
-            live.discard(residual)
-        if pad_sc is not None:              # the pad, then the slice: their only readers are gone
-            for n in pad_sc[4]:
-                graph.erase_node(n)
-                live.discard(n)
-        report.pad_shortcuts += pad_sc is not None
-        report.layers += 1
-        report.stem += spec[4] == "stem"
-        report.pooled += pool is not None
-        report.relu += relu
-        report.relu6 += act6
-        report.act_offset += spec[0].xoff + (dual and other[0].xoff)
-        report.residual += residual is not None
-        report.narrow += narrow
-        report.emit += emit is not None
-        report.fp32_outputs += bool(fp32_needed or emit is None)
-    graph.eliminate_dead_code()
-    graph.lint()
-    gm.recompile()
+    planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts).run(report)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
         _avgpool_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
