@@ -444,14 +444,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
 }
 
 // Whether the halo kernel takes this layer (conv_launch asks before it picks a generic tile), and the launch.
-bool conv3x3_halo_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                          int32_t dilation, const ConvEpi& ep, const float* out, bool dual) {
-  if (R != 3 || S != 3 || (stride != 1 && stride != 2) || pad != 1 || dilation != 1 || dual || out || ep.residual || ep.w_off || !ep.codes)
+bool conv3x3_halo_applies(const ConvCall& c) {
+  const ConvEpi& ep = c.ep;
+  const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K;
+  const int32_t stride = c.stride;
+  if (c.R != 3 || c.S != 3 || (stride != 1 && stride != 2) || c.pad != 1 || c.dil != 1 || c.seg2 || c.out || ep.residual || ep.w_off || !ep.codes)
     return false;
   if (C % 64 != 0 || K % 64 != 0 || !aligned16(ep.codes)) return false;
   if (ep.relu == DLMCQ_ACT_RELU6) return false;                       // (ReLU only: ReLU6 layers take the tiled kernel)
   if (stride == 2 && ((H | W) & 1)) return false;                      // (odd sizes: the generic kernel)
-  const int64_t P = H / stride, Q = W / stride;                        // pad 1, 3 x 3: P = H for stride 1, H / 2 for even H at stride 2
+  const int64_t P = c.P, Q = c.Q;                                      // pad 1, 3 x 3: P = H for stride 1, H / 2 for even H at stride 2
   if (stride == 2 && Q + 1 > 62) return false;                         // a phase tile of 256 + Wp + 2 positions in 20 pieces
   // measured (plan profiles, batch 512): 256 -> 256 at 28^2 -> 14^2 110 -> 86 us, 512 -> 512 at 14^2 -> 7^2 88 -> 75, 128 -> 128 at
   // 56^2 -> 28^2 122 -> 115, 64 -> 64 at 112^2 -> 56^2 210 -> 197; a single chunk feeding 128 channels (64 -> 128 at 56^2 -> 28^2) is
@@ -461,15 +463,16 @@ bool conv3x3_halo_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
   return true;
 }
 
-int conv3x3_halo_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                        const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
-                        int32_t stride, int shift, const ConvEpi& ep, hipStream_t st, int lab, void* lab_trace) {
+int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
   constexpr int TM = 256;
+  const ConvEpi& ep = c.ep;
+  const int64_t N = c.N, C = c.C, K = c.K;
+  const int shift = c.shift;
   const int bn = K % 128 == 0 ? 128 : 64;
-  const bool s2 = stride == 2;
+  const bool s2 = c.stride == 2;
   const bool plain = epi_plain(ep);
   HaloGeom g;
-  g.N = (int)N; g.Hin = (int)H; g.Win = (int)W; g.H = (int)(H / stride); g.W = (int)(W / stride); g.C = (int)C; g.K = (int)K;
+  g.N = (int)N; g.Hin = (int)c.H; g.Win = (int)c.W; g.H = (int)c.P; g.W = (int)c.Q; g.C = (int)C; g.K = (int)K;
   g.Wp = g.W + 1;
   g.FS = (g.H + 1) * (g.W + 1);
   g.MQ = (uint32_t)(N * g.FS);
@@ -481,7 +484,7 @@ int conv3x3_halo_launch(const int8_t* x, const int8_t* w, const float* bias, con
   const int64_t nwg = nblk_m * g.nblk_n;
   if (nwg >= (1ll << 31)) return DLMCQ_ERANGE;
   unsigned long long* const trace = static_cast<unsigned long long*>(lab_trace);
-#define DLMCQ_HALO_ARGS(NW) dim3((uint32_t)nwg), dim3(NW * 64), 0, st, x, w, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, trace
+#define DLMCQ_HALO_ARGS(NW) dim3((uint32_t)nwg), dim3(NW * 64), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, shift, ep, trace
 #ifdef DLMCQ_LAB
   if (lab) {     // lab: variant = lab % 100 on the product tiling, + 100 for the 8-wave tiling (100 = its product code); stride 1 only
     const int v = lab % 100;

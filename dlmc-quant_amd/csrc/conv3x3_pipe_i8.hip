@@ -467,13 +467,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_i8_kernel(
 }
 
 template <int NCH>
-static int conv3x3_pipe_go(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                           const float* in_zero_point, const float* w_scale, const PipeGeom& g, int shift, const ConvEpi& ep, hipStream_t st,
-                           uint32_t grid) {
-  if (shift) hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, true>), dim3(grid), dim3(512), 0, st, x, w, bias, wsum, in_scale, in_zero_point,
-                                w_scale, g, shift, ep);
-  else hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, false>), dim3(grid), dim3(512), 0, st, x, w, bias, wsum, in_scale, in_zero_point,
-                          w_scale, g, shift, ep);
+static int conv3x3_pipe_go(const ConvCall& c, const PipeGeom& g, uint32_t grid) {
+  if (c.shift) hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, true>), dim3(grid), dim3(512), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in,
+                                  c.zp_in, c.s_w, g, c.shift, c.ep);
+  else hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, false>), dim3(grid), dim3(512), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in,
+                          c.s_w, g, c.shift, c.ep);
   return launch_status();
 }
 
@@ -487,8 +485,10 @@ extern "C" int dlmcq_x_pipe_wg(unsigned long long* host1024) {
 }
 namespace dlmcq {
 #endif
-bool conv3x3_pipe_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t stride, const ConvEpi& ep, int cus) {
-  if (stride != 1 || !(C == 128 || C == 256 || C == 512) || K % 128 != 0 || K > PIPE_KMAX || !epi_plain(ep)) return false;
+bool conv3x3_pipe_applies(const ConvCall& c, int cus) {
+  const ConvEpi& ep = c.ep;
+  const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K;
+  if (c.stride != 1 || !(C == 128 || C == 256 || C == 512) || K % 128 != 0 || K > PIPE_KMAX || !epi_plain(ep)) return false;
   if (ep.relu == DLMCQ_ACT_RELU6) return false;                                   // (ReLU only: ReLU6 layers take the tiled kernel)
   if (W + 1 > 62) return false;                                                   // six halo pieces per wave
   const int64_t MQ = N * (H + 1) * (W + 1);
@@ -497,11 +497,10 @@ bool conv3x3_pipe_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
   return N * H * W * K < (int64_t)BUF_BIG;                                        // 32-bit buffer offsets of the row stores
 }
 
-int conv3x3_pipe_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                        const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int shift,
-                        const ConvEpi& ep, hipStream_t st, int cus) {
+int conv3x3_pipe_launch(const ConvCall& c, int cus) {
+  const int64_t N = c.N, C = c.C, K = c.K;
   PipeGeom g;
-  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K;
+  g.N = (int)N; g.H = (int)c.H; g.W = (int)c.W; g.C = (int)C; g.K = (int)K;
   g.Wp = g.W + 1;
   g.FS = (g.H + 1) * (g.W + 1);
   g.MQ = (uint32_t)(N * g.FS);
@@ -515,9 +514,9 @@ int conv3x3_pipe_launch(const int8_t* x, const int8_t* w, const float* bias, con
   uint32_t grid = (uint32_t)cus & ~7u;             // one workgroup per CU, a multiple of 8 (a workgroup's tiles stay on its XCD)
   if (grid > (g.ntiles & ~7u)) grid = g.ntiles & ~7u;      // (every workgroup owns at least one tile)
   if (grid < 8 || g.hp > 24) return DLMCQ_EINVAL;
-  if (C == 128) return conv3x3_pipe_go<2>(x, w, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, st, grid);
-  if (C == 256) return conv3x3_pipe_go<4>(x, w, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, st, grid);
-  if (C == 512) return conv3x3_pipe_go<8>(x, w, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, st, grid);
+  if (C == 128) return conv3x3_pipe_go<2>(c, g, grid);
+  if (C == 256) return conv3x3_pipe_go<4>(c, g, grid);
+  if (C == 512) return conv3x3_pipe_go<8>(c, g, grid);
   return DLMCQ_EINVAL;
 }
 

@@ -758,45 +758,108 @@ static ConvPlan conv_plan(int64_t C, int64_t K, int64_t R, int64_t S, bool dual)
   return p;
 }
 
-// A pad shortcut (the PADRES instantiations; dlmcq_conv2d_i8_nhwc_padres): ep.residual is the dense fp32 NHWC source [N][h][w][c] of
-// pad(x[:, ::stride, ::stride, :]) with `clo` zero channels in front
-struct PadRes {
-  int h, w, c, stride, clo;
+// The swapped epilogue writes whole 16-byte code rows of full tiles and nothing else: codes only, no fp32 output, no shortcut, a
+// width that divides K.  ONE definition: the 192-wide adjustment, the 256-wide narrowing and the SWAP flag all ask it.
+static bool swap_ok(const ConvCall& c, const ConvPlan& plan, int bn) {
+  return plan.swap && c.ep.codes && !c.out && !c.ep.residual && bn > 0 && c.K % bn == 0 && aligned16(c.ep.codes);
+}
+
+// An instantiation of conv_i8_mfma_kernel as a value: the tile width and the kernel's boolean template parameters by name.  The
+// grid is sized from the same `bn` the launcher instantiates, so the width launched and the width tiled for cannot differ.
+enum : unsigned { CV_DUAL = 1, CV_ADIR = 2, CV_ASYM = 4, CV_SWAP = 8, CV_R6 = 16, CV_XOFF = 32, CV_NARROW = 64, CV_PADRES = 128 };
+struct ConvVariant {
+  int bn;
+  unsigned flags;
 };
 
-static int conv_launch(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
-                       const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N, int64_t H,
-                       int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                       int32_t dilation, int32_t x_is_unsigned, dlmcq_stream_t stream, const ConvEpi& ep_in = ConvEpi{},
-                       const ConvSeg2* seg2 = nullptr, const ConvPlan* forced = nullptr, int64_t* mm_count = nullptr,
-                       const PadRes* padres = nullptr) {
-  // (observer partials - ep.mm - come from the tiled kernel's fp32 epilogue only: a call another kernel takes reports 0 partials)
-  ConvEpi ep = ep_in;
+// Pure: the variant of a call that no specialised kernel took, from the (adjusted) plan and the record.
+//  - asymmetric weights and the dual kernel always take their activations straight to registers, whatever the plan says;
+//  - XOFF and NARROW calls arrive with plan.swap off and plan.adir on (conv_launch), a pad shortcut is a NARROW call;
+//  - ReLU6 (DLMCQ_ACT_RELU6) selects the R6 twin: the same kernel with the upper bound.
+static ConvVariant conv_variant(const ConvCall& c, const ConvPlan& plan) {
+  const ConvEpi& ep = c.ep;
+  const bool dual = c.seg2 != nullptr;
+  unsigned f = 0;
+  if (dual) f |= CV_DUAL;
+  if (plan.adir || ep.w_off || dual) f |= CV_ADIR;
+  if (ep.w_off) f |= CV_ASYM;
+  if (!dual && swap_ok(c, plan, plan.bn)) f |= CV_SWAP;
+  if (ep.relu == DLMCQ_ACT_RELU6) f |= CV_R6;
+  if (ep.x_off) f |= CV_XOFF;
+  if (ep.kf) f |= CV_NARROW;
+  if (c.padres) f |= CV_PADRES;
+  return ConvVariant{plan.bn, f};
+}
+
+// THE (width, flags) pairs the library instantiates - one list for the refusal (conv_variant_built) and the launch
+// (conv_variant_launch).  Everything but the dual kernel comes with its ReLU6 twin (the dual entry point refuses ReLU6).
+//  - 192-wide tiles: the swapped asymmetric codes-only kernel alone (MobileOne-S1's 192 -> 192 layers)
+//  - 256-wide tiles: the swapped codes-only kernels alone (one third fewer operand bytes per MAC, two workgroups per CU)
+#define DLMCQ_CV_R6_TOO(X, BN, F) X(BN, F) X(BN, (F) | CV_R6)
+#define DLMCQ_CV_TABLE(X)                                                                                                  \
+  DLMCQ_CV_R6_TOO(X, 64, 0) DLMCQ_CV_R6_TOO(X, 128, 0)                             /* both operands through the ring */     \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR)                                                         \
+  DLMCQ_CV_R6_TOO(X, 64, CV_SWAP) DLMCQ_CV_R6_TOO(X, 128, CV_SWAP) DLMCQ_CV_R6_TOO(X, 256, CV_SWAP)                        \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_SWAP) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR | CV_SWAP) DLMCQ_CV_R6_TOO(X, 256, CV_ADIR | CV_SWAP) \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_ASYM) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR | CV_ASYM)                                     \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_ASYM | CV_SWAP) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR | CV_ASYM | CV_SWAP)                 \
+  DLMCQ_CV_R6_TOO(X, 192, CV_ADIR | CV_ASYM | CV_SWAP)                                                                     \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_XOFF) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR | CV_XOFF)                                     \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_ASYM | CV_XOFF) DLMCQ_CV_R6_TOO(X, 128, CV_ADIR | CV_ASYM | CV_XOFF)                 \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_NARROW) DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_ASYM | CV_NARROW)                        \
+  DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_NARROW | CV_PADRES) DLMCQ_CV_R6_TOO(X, 64, CV_ADIR | CV_ASYM | CV_NARROW | CV_PADRES) \
+  X(64, CV_DUAL | CV_ADIR) X(128, CV_DUAL | CV_ADIR)
+
+constexpr bool conv_variant_built(ConvVariant v) {
+#define DLMCQ_CV_HAS(BN, F) if (v.bn == BN && v.flags == (F)) return true;
+  DLMCQ_CV_TABLE(DLMCQ_CV_HAS)
+#undef DLMCQ_CV_HAS
+  return false;
+}
+
+// value -> kernel: the one place the kernel's positional template list is spelt (LAB: the lab library's what-bounds-the-step variants)
+template <int BN, unsigned F, int LAB = 0>
+static int conv_tiled_go(const ConvCall& c, const ConvGeom& g, const ConvSeg2& s2) {
+  hipLaunchKernelGGL((conv_i8_mfma_kernel<BN, (F & CV_DUAL) != 0, (F & CV_ADIR) != 0, (F & CV_ASYM) != 0, LAB, (F & CV_SWAP) != 0,
+                                          (F & CV_R6) != 0, (F & CV_XOFF) != 0, (F & CV_NARROW) != 0, (F & CV_PADRES) != 0>),
+                     dim3((uint32_t)((int64_t)g.nblk_m * g.nblk_n)), dim3(256), 0, c.st, c.x, c.w, c.out, c.bias, c.wsum, c.s_in, c.zp_in,
+                     c.s_w, g, c.shift, c.ep, s2);
+  return launch_status();
+}
+
+static int conv_variant_launch(ConvVariant v, const ConvCall& c, const ConvGeom& g, const ConvSeg2& s2) {
+#define DLMCQ_CV_GO(BN, F) if (v.bn == BN && v.flags == (F)) return conv_tiled_go<BN, (F)>(c, g, s2);
+  DLMCQ_CV_TABLE(DLMCQ_CV_GO)
+#undef DLMCQ_CV_GO
+  return DLMCQ_EINVAL;
+}
+
+// A pad shortcut's five scalars ride in the second pair's geometry, which a single-pair kernel does not otherwise read (see the
+// kernel: sg.g.H / W / C = the source's, sg.g.stride = its pixel stride, sg.g.pad = the zero channels in front)
+static void seg2_carry_padres(ConvSeg2& s2, const PadRes& pr) {
+  s2.g.H = pr.h; s2.g.W = pr.w; s2.g.C = pr.c; s2.g.stride = pr.stride; s2.g.pad = pr.clo;
+}
+
+// Validate, route, launch.  `forced`: the lab entry point's plan instead of conv_plan's; `mm_count`: where the observed entry point
+// learns how many observer partials the launch wrote (ep.mm - they come from the tiled kernel's fp32 epilogue only: a call another
+// kernel takes reports 0 partials).
+static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm_count = nullptr) {
+  ConvEpi& ep = c.ep;
+  const ConvSeg2* const seg2 = c.seg2;
+  const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, R = c.R, S = c.S, P = c.P, Q = c.Q, M = c.M;
   if (mm_count) *mm_count = 0;
-  if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || stride < 1 || pad < 0 || dilation < 1)
-    return DLMCQ_EINVAL;
+  if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || c.stride < 1 || c.pad < 0 || c.dil < 1) return DLMCQ_EINVAL;
   if (C % CV_BK != 0) return DLMCQ_EINVAL;  // the K step is 64 input channels
-  const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1;
-  const int64_t Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;
-  const int64_t M = N * P * Q;
   if (M == 0) return DLMCQ_OK;
-  if (!x || !w || !(out || ep.codes) || !wsum || !in_scale || !w_scale) return DLMCQ_EINVAL;
+  if (!c.x || !c.w || !(c.out || ep.codes) || !c.wsum || !c.s_in || !c.s_w) return DLMCQ_EINVAL;
   if (ep.codes && (!ep.q_scale || ep.q_lo > ep.q_hi || ep.q_lo < -128.0f || ep.q_hi > 255.0f || ep.q_hi - ep.q_lo > 255.0f ||
                    ep.q_form < DLMCQ_FORM_EMULATE || ep.q_form > DLMCQ_FORM_SYMMETRIC))
     return DLMCQ_EINVAL;
-  if (!aligned16(x) || !aligned16(w) || (out && !aligned16(out)) || (ep.residual && !aligned16(ep.residual)) ||
+  if (!aligned16(c.x) || !aligned16(c.w) || (c.out && !aligned16(c.out)) || (ep.residual && !aligned16(ep.residual)) ||
       (ep.codes && !aligned4(ep.codes)))
     return DLMCQ_EALIGN;
   if (M >= (1ll << 31) || N * H * W * C >= (1ll << 40) || K >= (1 << 24)) return DLMCQ_ERANGE;
-  ConvGeom g;
-  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-  g.stride = stride; g.pad = pad; g.dil = dilation; g.P = (int)P; g.Q = (int)Q; g.M = M;
-  g.qdiv = make_fastdiv((uint32_t)Q);
-  g.pdiv = make_fastdiv((uint32_t)P);
-  const int shift = x_is_unsigned ? 128 : 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int8_t* xs = reinterpret_cast<const int8_t*>(x);
   ConvPlan plan = forced ? *forced : conv_plan(C, K, R, S, seg2 != nullptr);
   // asymmetric weights always take their activations straight to registers (the row sums come from the fragments), so conv_plan's
   // 64-wide choice for deep 1x1 reductions - made for the ring-fed kernels - only multiplies the activation re-reads there:
@@ -804,7 +867,7 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   if (!forced && ep.w_off && plan.bn == 64 && K > 64 && K % 128 == 0) plan.bn = 128;
   // ... and widths of 192, 576, ... (no multiple of 128) 192-wide ones - codes-only layers with the swapped epilogue (MobileOne-S1's
   // 192 -> 192 layers at 28^2: one tile column fewer, a third fewer re-reads of the activations)
-  if (!forced && ep.w_off && plan.bn == 64 && K % 192 == 0 && plan.swap && ep.codes && !out && !ep.residual && aligned16(ep.codes)) plan.bn = 192;
+  if (!forced && ep.w_off && plan.bn == 64 && swap_ok(c, plan, 192)) plan.bn = 192;
   // the specialised kernels, unless the caller (DLMCQ_FORCE_TILED) or a lab plan keeps the call on this file's kernel;
   // DLMCQ_ROUTE_ONLY: the decision is the answer, nothing is launched
   // a float activation offset (ep.x_off) runs on the XOFF instantiations of this file's kernel only: the specialised kernels decline
@@ -828,8 +891,8 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   }
   // a pad shortcut is an addressing mode of the narrow epilogue's shortcut; the output pixels must be exactly the source's subsampled
   // ones (P = ceil(h / stride), Q = ceil(w / stride): no output pixel then reads outside the source)
-  if (padres) {
-    const PadRes& pr = *padres;
+  if (c.padres) {
+    const PadRes& pr = *c.padres;
     if (!narrow || !ep.residual || pr.h < 1 || pr.w < 1 || pr.stride < 1 || pr.c < 4 || pr.c % 4 != 0 || pr.clo < 0 || pr.clo % 4 != 0 ||
         (int64_t)pr.clo + pr.c > ep.kf || P != ((int64_t)pr.h + pr.stride - 1) / pr.stride || Q != ((int64_t)pr.w + pr.stride - 1) / pr.stride)
       return DLMCQ_EINVAL;
@@ -840,36 +903,25 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
   ep.mm = nullptr;                    // (the specialised kernels below do not write partials)
   // (only the block-end kernel knows the chunk-major form of the fp32 block tensors: a call that carries the bits and would land
   //  elsewhere is refused, never silently read row-major.  Callers ask first: DLMCQ_ROUTE_ONLY without the bits)
-  if ((ep.ctl & (DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR)) &&
-      !(special && conv_pwr_applies(N, H, W, C, K, R, S, stride, pad, dilation, ep, out, seg2)))
-    return DLMCQ_EINVAL;
-  if (special && conv_pw_applies(N, H, W, C, K, R, S, stride, pad, dilation, ep, out, seg2 != nullptr))
-    return route_only ? DLMCQ_ROUTE_PW : conv_pw_launch(xs, w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, shift, ep, st);
-  if (special && conv_pwr_applies(N, H, W, C, K, R, S, stride, pad, dilation, ep, out, seg2))
-    return route_only ? DLMCQ_ROUTE_PWR
-                      : conv_pwr_launch(xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, stride, shift, ep, st, seg2);
-  if (special && conv3x3_halo_applies(N, H, W, C, K, R, S, stride, pad, dilation, ep, out, seg2 != nullptr)) {
+  if ((ep.ctl & (DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR)) && !(special && conv_pwr_applies(c))) return DLMCQ_EINVAL;
+  if (special && conv_pw_applies(c)) return route_only ? DLMCQ_ROUTE_PW : conv_pw_launch(c);
+  if (special && conv_pwr_applies(c)) return route_only ? DLMCQ_ROUTE_PWR : conv_pwr_launch(c);
+  if (special && conv3x3_halo_applies(c)) {
     // ... persistent and pipelined across tiles on request (DLMCQ_PIPELINED: csrc/conv3x3_pipe_i8.hip - bit-identical, measured slower)
-    if ((ep.ctl & DLMCQ_PIPELINED) && conv3x3_pipe_applies(N, H, W, C, K, stride, ep, device_cus()))
-      return route_only ? DLMCQ_ROUTE_HALO3X3_PIPE
-                        : conv3x3_pipe_launch(xs, w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, shift, ep, st, device_cus());
-    return route_only ? DLMCQ_ROUTE_HALO3X3
-                      : conv3x3_halo_launch(xs, w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, stride, shift, ep, st);
+    if ((ep.ctl & DLMCQ_PIPELINED) && conv3x3_pipe_applies(c, device_cus()))
+      return route_only ? DLMCQ_ROUTE_HALO3X3_PIPE : conv3x3_pipe_launch(c, device_cus());
+    return route_only ? DLMCQ_ROUTE_HALO3X3 : conv3x3_halo_launch(c);
   }
-  // 256-wide tiles exist for the swapped codes-only layers only (one third fewer operand bytes per MAC, two workgroups per CU)
-  const bool swap_ok = plan.swap && ep.codes && !out && !ep.residual && K % plan.bn == 0 && aligned16(ep.codes);
-  // (192-wide tiles: the swapped asymmetric codes-only instantiation is the only one - a forced plan that asks for them anywhere
-  //  else would compute nblk_n for 192 and launch the 128-wide kernel, leaving channels unwritten)
-  if (plan.bn != 64 && plan.bn != 128 && plan.bn != 256 && !(plan.bn == 192 && ep.w_off && swap_ok && !seg2)) return DLMCQ_EINVAL;
-  if (plan.bn == 256 && (seg2 || ep.w_off || !swap_ok)) {
+  // 256-wide tiles exist for the swapped codes-only layers only; fp32 outputs, shortcuts, asymmetric weights and the dual form narrow
+  // to the 128-wide kernels here, in place (a forced plan is refused instead: the lab asked for exactly that width)
+  if (plan.bn == 256 && (seg2 || ep.w_off || !swap_ok(c, plan, 256))) {
     if (forced) return DLMCQ_EINVAL;
-    ConvPlan p2 = plan;                  // (fp32 outputs, shortcuts, asymmetric weights: the 128-wide kernels)
-    p2.bn = 128;
-    return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                       x_is_unsigned, stream, ep_in, seg2, &p2, mm_count);
+    plan.bn = 128;
   }
-  g.nblk_m = (int)((M + CV_BM - 1) / CV_BM);
-  g.nblk_n = (int)((K + plan.bn - 1) / plan.bn);
+  const ConvVariant v = conv_variant(c, plan);
+  if (!conv_variant_built(v)) return DLMCQ_EINVAL;      // (a forced width or combination the library does not hold)
+  ConvGeom g = conv_geom(c);
+  conv_geom_tiles(g, v.bn);
   const int64_t nwg = (int64_t)g.nblk_m * g.nblk_n;
   if (nwg >= (1ll << 31)) return DLMCQ_ERANGE;
   ConvSeg2 s2{};
@@ -877,70 +929,16 @@ static int conv_launch(const void* x, const int8_t* w, float* out, const float* 
     s2 = *seg2;
     s2.g.nblk_m = g.nblk_m;
     s2.g.nblk_n = g.nblk_n;
-    if (s2.g.M != g.M || s2.g.K != g.K || s2.g.P != g.P || s2.g.Q != g.Q || ep.w_off) return DLMCQ_EINVAL;
+    if (s2.g.M != g.M || s2.g.K != g.K || s2.g.P != g.P || s2.g.Q != g.Q) return DLMCQ_EINVAL;
   }
-  if (padres) {       // (no second pair: its geometry carries the shortcut's - see the kernel)
-    s2.g.H = padres->h; s2.g.W = padres->w; s2.g.C = padres->c; s2.g.stride = padres->stride; s2.g.pad = padres->clo;
-  }
+  if (c.padres) seg2_carry_padres(s2, *c.padres);
   if (route_only) return DLMCQ_ROUTE_TILED;
-  if (mm_req && out) {                             // one partial per workgroup of this launch
+  if (mm_req && c.out) {                             // one partial per workgroup of this launch
     ep.mm = mm_req;
     ep.mm_np = (int)nwg;
     if (mm_count) *mm_count = nwg;
   }
-#define DLMCQ_CONV_ARGS dim3((uint32_t)nwg), dim3(256), 0, st, xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, s2
-  // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound (the dual entry point refuses it)
-  auto launch = [&](auto r6) {
-    constexpr bool R6 = decltype(r6)::value;
-    if (padres) {
-      if (ep.w_off) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, false, true, true>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, false, true, true>), DLMCQ_CONV_ARGS);
-    } else if (narrow) {
-      if (ep.w_off) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, false, true>), DLMCQ_CONV_ARGS);
-    } else if (xoff) {
-      if (ep.w_off) {
-        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
-        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, false, R6, true>), DLMCQ_CONV_ARGS);
-      } else {
-        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6, true>), DLMCQ_CONV_ARGS);
-        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, false, R6, true>), DLMCQ_CONV_ARGS);
-      }
-    } else if (seg2) {
-      if constexpr (!R6) {
-        if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, true, true>), DLMCQ_CONV_ARGS);
-        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, true, true>), DLMCQ_CONV_ARGS);
-      }
-    } else if (ep.w_off && plan.swap && ep.codes && !out && !ep.residual && K % plan.bn == 0 && aligned16(ep.codes)) {
-      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
-      else if (plan.bn == 192) hipLaunchKernelGGL((conv_i8_mfma_kernel<192, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, true, R6>), DLMCQ_CONV_ARGS);
-    } else if (ep.w_off) {     // asymmetric per-channel weights (activations direct: the row sums come from their fragments)
-      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, true, 0, false, R6>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, true, 0, false, R6>), DLMCQ_CONV_ARGS);
-    } else if (swap_ok && plan.bn == 256) {
-      if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<256, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-    } else if (swap_ok) {
-      if (plan.bn == 64) {
-        if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-        else hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-      } else {
-        if (plan.adir) hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-        else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false, false, 0, true, R6>), DLMCQ_CONV_ARGS);
-      }
-    } else if (!plan.adir) {
-      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, false, false, 0, false, R6>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, false, false, 0, false, R6>), DLMCQ_CONV_ARGS);
-    } else {
-      if (plan.bn == 64) hipLaunchKernelGGL((conv_i8_mfma_kernel<64, false, true, false, 0, false, R6>), DLMCQ_CONV_ARGS);
-      else hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 0, false, R6>), DLMCQ_CONV_ARGS);
-    }
-  };
-  if (ep.relu == DLMCQ_ACT_RELU6) launch(std::true_type{});
-  else launch(std::false_type{});
-#undef DLMCQ_CONV_ARGS
-  return launch_status();
+  return conv_variant_launch(v, c, g, s2);
 }
 
 static ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point,
@@ -958,13 +956,16 @@ static ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const 
   return ep;
 }
 
+// the ABI's leading twenty arguments -> the record (every conv2d_i8_nhwc entry point and the lab's share them by name)
+#define DLMCQ_CALL_ARGS x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation, x_is_unsigned, stream
+#define DLMCQ_EPI_ARGS relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g
+
 extern "C" int dlmcq_conv2d_i8_nhwc_f32(const void* x, const int8_t* w, float* out, const float* bias,
                                         const int32_t* wsum, const float* in_scale, const float* in_zero_point,
                                         const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
                                         int64_t R, int64_t S, int32_t stride, int32_t pad, int32_t dilation,
                                         int32_t x_is_unsigned, dlmcq_stream_t stream) {
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream);
+  return conv_launch(conv_call(DLMCQ_CALL_ARGS));
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_fused(const void* x, const int8_t* w, float* out, const float* bias,
@@ -974,9 +975,9 @@ extern "C" int dlmcq_conv2d_i8_nhwc_fused(const void* x, const int8_t* w, float*
                                           int32_t x_is_unsigned, const float* residual, int32_t relu, void* codes,
                                           const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                           int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  const ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
+  return conv_launch(c);
 }
 
 extern "C" size_t dlmcq_conv2d_i8_observed_partials(int64_t M, int64_t K) {
@@ -992,15 +993,13 @@ extern "C" int dlmcq_conv2d_i8_nhwc_fused_observed(const void* x, const int8_t* 
                                                    int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, float* partials,
                                                    int64_t partials_capacity, int64_t* partials_count, dlmcq_stream_t stream) {
   if (!partials || !partials_count || !out) return DLMCQ_EINVAL;
-  const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / (stride > 0 ? stride : 1) + 1;
-  const int64_t Q = (W + 2 * pad - dilation * (S - 1) - 1) / (stride > 0 ? stride : 1) + 1;
-  if (K < 1 || N * P * Q < 1) return DLMCQ_EINVAL;        // (the query below is 0 there: no capacity check would stand)
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);      // (nothing is validated yet: conv_out_size does not divide by a stride of 0)
+  if (K < 1 || c.M < 1) return DLMCQ_EINVAL;        // (the query below is 0 there: no capacity check would stand)
   // three planes of `observed_partials` floats each (max, min, |x| bits: ConvEpi::mm)
-  if (partials_capacity < 3 * (int64_t)dlmcq_conv2d_i8_observed_partials(N * P * Q, K)) return DLMCQ_ESCRATCH;
-  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  ep.mm = partials;
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep, nullptr, nullptr, partials_count);
+  if (partials_capacity < 3 * (int64_t)dlmcq_conv2d_i8_observed_partials(c.M, K)) return DLMCQ_ESCRATCH;
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
+  c.ep.mm = partials;
+  return conv_launch(c, nullptr, partials_count);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_asym(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
@@ -1011,10 +1010,10 @@ extern "C" int dlmcq_conv2d_i8_nhwc_asym(const void* x, const int8_t* w, float* 
                                          const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                                          dlmcq_stream_t stream) {
   if (!w_offset) return DLMCQ_EINVAL;
-  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  ep.w_off = w_offset;
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
+  c.ep.w_off = w_offset;
+  return conv_launch(c);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
@@ -1026,14 +1025,14 @@ extern "C" int dlmcq_conv2d_i8_nhwc_xoff(const void* x, const int8_t* w, float* 
                                          const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
   if (!in_offset || !tap_sums) return DLMCQ_EINVAL;
   if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
-  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  ep.w_off = w_offset;
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
+  c.ep.w_off = w_offset;
   if (pad > 0) {      // (unpadded: no tap is ever out of bounds - the folded bias is the whole term, and every kernel may take the call)
-    ep.x_off = in_offset;
-    ep.x_tap = tap_sums;
+    c.ep.x_off = in_offset;
+    c.ep.x_tap = tap_sums;
   }
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep);
+  return conv_launch(c);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
@@ -1045,11 +1044,11 @@ extern "C" int dlmcq_conv2d_i8_nhwc_narrow(const void* x, const int8_t* w, float
                                            int64_t Kf, dlmcq_stream_t stream) {
   // fp32 rows of Kf floats beside code rows of K bytes: K the padded width, Kf the real one, inside K's last block of 64
   if (K < 64 || K % 64 != 0 || Kf % 4 != 0 || Kf > K || Kf <= K - 64) return DLMCQ_EINVAL;
-  ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  ep.w_off = w_offset;
-  ep.kf = (int)Kf;
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
+  c.ep.w_off = w_offset;
+  c.ep.kf = (int)Kf;
+  return conv_launch(c);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_padres(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
@@ -1065,39 +1064,26 @@ extern "C" int dlmcq_conv2d_i8_nhwc_padres(const void* x, const int8_t* w, float
   if (!res_src || res_h < 1 || res_w < 1 || res_c < 4 || res_stride < 1 || res_clo < 0 || res_h >= BIG || res_w >= BIG || res_c >= BIG ||
       res_clo >= BIG)
     return DLMCQ_EINVAL;
-  ConvEpi ep = make_epi(res_src, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  ep.w_off = w_offset;
-  ep.kf = (int)Kf;
   const PadRes pr{(int)res_h, (int)res_w, (int)res_c, res_stride, (int)res_clo};
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep, nullptr, nullptr, nullptr, &pr);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(res_src, DLMCQ_EPI_ARGS);
+  c.ep.w_off = w_offset;
+  c.ep.kf = (int)Kf;
+  c.padres = &pr;
+  return conv_launch(c);
 }
 
-static int make_seg2(ConvSeg2& s2, int64_t N, int64_t K, const void* x2, const int8_t* w2, const float* bias2,
-                     const int32_t* wsum2, const float* in_scale2, const float* in_zero_point2, const float* w_scale2,
-                     int64_t H2, int64_t W2, int64_t C2, int64_t R2, int64_t S2, int32_t stride2, int32_t pad2,
-                     int32_t dilation2, int32_t x2_is_unsigned) {
-  if (H2 < 1 || W2 < 1 || C2 < 1 || R2 < 1 || S2 < 1 || stride2 < 1 || pad2 < 0 || dilation2 < 1 || C2 % CV_BK != 0)
+// the dual form's second operand pair: its own record (the first pair's N and K), validated, as the kernel's ConvSeg2
+static int make_seg2(ConvSeg2& s2, const ConvCall& c2) {
+  if (c2.H < 1 || c2.W < 1 || c2.C < 1 || c2.R < 1 || c2.S < 1 || c2.stride < 1 || c2.pad < 0 || c2.dil < 1 || c2.C % CV_BK != 0)
     return DLMCQ_EINVAL;
-  if (N > 0 && (!x2 || !w2 || !wsum2 || !in_scale2 || !w_scale2)) return DLMCQ_EINVAL;
-  if (!aligned16(x2) || !aligned16(w2)) return DLMCQ_EALIGN;
-  if (N * H2 * W2 * C2 >= (1ll << 40)) return DLMCQ_ERANGE;
-  s2.x = static_cast<const int8_t*>(x2);
-  s2.w = w2;
-  s2.bias = bias2;
-  s2.wsum = wsum2;
-  s2.s_in = in_scale2;
-  s2.zp_in = in_zero_point2;
-  s2.s_w = w_scale2;
-  s2.shift = x2_is_unsigned ? 128 : 0;
-  ConvGeom& g = s2.g;
-  const int64_t P = (H2 + 2 * pad2 - dilation2 * (R2 - 1) - 1) / stride2 + 1;
-  const int64_t Q = (W2 + 2 * pad2 - dilation2 * (S2 - 1) - 1) / stride2 + 1;
-  if (P < 1 || Q < 1) return DLMCQ_EINVAL;
-  g.N = (int)N; g.H = (int)H2; g.W = (int)W2; g.C = (int)C2; g.K = (int)K; g.R = (int)R2; g.S = (int)S2;
-  g.stride = stride2; g.pad = pad2; g.dil = dilation2; g.P = (int)P; g.Q = (int)Q; g.M = N * P * Q;
-  g.qdiv = make_fastdiv((uint32_t)Q);
-  g.pdiv = make_fastdiv((uint32_t)P);
+  if (c2.N > 0 && (!c2.x || !c2.w || !c2.wsum || !c2.s_in || !c2.s_w)) return DLMCQ_EINVAL;
+  if (!aligned16(c2.x) || !aligned16(c2.w)) return DLMCQ_EALIGN;
+  if (c2.N * c2.H * c2.W * c2.C >= (1ll << 40)) return DLMCQ_ERANGE;
+  if (c2.P < 1 || c2.Q < 1) return DLMCQ_EINVAL;
+  s2.x = c2.x; s2.w = c2.w; s2.bias = c2.bias; s2.wsum = c2.wsum; s2.s_in = c2.s_in; s2.zp_in = c2.zp_in; s2.s_w = c2.s_w;
+  s2.shift = c2.shift;
+  s2.g = conv_geom(c2);
   return DLMCQ_OK;
 }
 
@@ -1114,35 +1100,36 @@ extern "C" int dlmcq_conv2d_i8_nhwc_dual(const void* x, const int8_t* w, float* 
                                          float q_ste_g, dlmcq_stream_t stream) {
   if (relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (no dual instantiation carries ReLU6's bound)
   ConvSeg2 s2{};
-  const int rc = make_seg2(s2, N, K, x2, w2, bias2, wsum2, in_scale2, in_zero_point2, w_scale2, H2, W2, C2, R2, S2, stride2,
-                           pad2, dilation2, x2_is_unsigned);
+  const int rc = make_seg2(s2, conv_call(x2, w2, nullptr, bias2, wsum2, in_scale2, in_zero_point2, w_scale2, N, H2, W2, C2, K, R2, S2,
+                                         stride2, pad2, dilation2, x2_is_unsigned, stream));
   if (rc != DLMCQ_OK) return rc;
-  const ConvEpi ep = make_epi(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep, &s2);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(nullptr, DLMCQ_EPI_ARGS);
+  c.seg2 = &s2;
+  return conv_launch(c);
 }
 
 #ifdef DLMCQ_LAB
+// The lab's direct launches of this file's kernel: the tiled-kernel checks conv_launch makes that a lab variant still needs (`bn`
+// must divide K: no partial column tiles), then the geometry
+static bool lab_geom(const ConvCall& c, int bn, ConvGeom& g) {
+  if (bn < 1 || c.C % CV_BK || c.K % bn || c.P < 1 || c.Q < 1 || c.M >= (1ll << 31)) return false;
+  g = conv_geom(c);
+  conv_geom_tiles(g, bn);
+  return true;
+}
+
 // phase stamps of one wave (tools/conv_trace.py): `trace` receives 24 x 8 uint64 shader-clock values
 extern "C" int dlmcq_x_conv2d_i8_trace(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
                                        const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t N,
                                        int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride,
                                        int32_t pad, int32_t dilation, int32_t x_is_unsigned, void* codes, const float* q_scale,
                                        dlmcq_stream_t stream, void* trace) {
-  ConvEpi ep = make_epi(static_cast<const float*>(trace), 1, codes, q_scale, nullptr, 0, 255, DLMCQ_FORM_ZEROPOINT, 0.0f);
-  const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1, Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
-  if (C % CV_BK || K % 128 || P < 1 || Q < 1) return DLMCQ_EINVAL;
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(static_cast<const float*>(trace), 1, codes, q_scale, nullptr, 0, 255, DLMCQ_FORM_ZEROPOINT, 0.0f);
   ConvGeom g;
-  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-  g.stride = stride; g.pad = pad; g.dil = dilation; g.P = (int)P; g.Q = (int)Q; g.M = N * P * Q;
-  g.qdiv = make_fastdiv((uint32_t)Q);
-  g.pdiv = make_fastdiv((uint32_t)P);
-  g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
-  g.nblk_n = (int)(K / 128);
-  hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, 1>), dim3((uint32_t)((int64_t)g.nblk_m * g.nblk_n)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int8_t*>(x), w, out, bias, wsum, in_scale,
-                     in_zero_point, w_scale, g, x_is_unsigned ? 128 : 0, ep, ConvSeg2{});
-  return launch_status();
+  if (!lab_geom(c, 128, g)) return DLMCQ_EINVAL;
+  return conv_tiled_go<128, CV_ADIR, 1>(c, g, ConvSeg2{});
 }
 
 // the same stamps for the dual kernel (a block's last 1x1 convolution + the 1x1 / stride-s convolution on its shortcut; fp32 out + codes)
@@ -1152,24 +1139,16 @@ extern "C" int dlmcq_x_conv2d_i8_dual_trace(const void* x, const int8_t* w, cons
                                             int64_t H2, int64_t W2, int64_t C2, int32_t stride2, float* out, void* codes,
                                             const float* q_scale, dlmcq_stream_t stream, void* trace) {
   ConvSeg2 s2{};
-  const int rc = make_seg2(s2, N, K, x2, w2, nullptr, wsum2, in_scale, in_zero_point, w_scale2, H2, W2, C2, 1, 1, stride2, 0, 1, 1);
+  const int rc = make_seg2(s2, conv_call(x2, w2, nullptr, nullptr, wsum2, in_scale, in_zero_point, w_scale2, N, H2, W2, C2, K, 1, 1,
+                                         stride2, 0, 1, 1, stream));
   if (rc != DLMCQ_OK) return rc;
-  ConvEpi ep = make_epi(static_cast<const float*>(trace), 1, codes, q_scale, nullptr, 0, 255, DLMCQ_FORM_ZEROPOINT, 0.0f);
-  if (C % CV_BK || C2 % CV_BK || K % 128) return DLMCQ_EINVAL;
+  ConvCall c = conv_call(x, w, out, nullptr, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, 1, 1, 1, 0, 1, 1, stream);
+  c.ep = make_epi(static_cast<const float*>(trace), 1, codes, q_scale, nullptr, 0, 255, DLMCQ_FORM_ZEROPOINT, 0.0f);
   ConvGeom g;
-  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = 1; g.S = 1;
-  g.stride = 1; g.pad = 0; g.dil = 1; g.P = (int)H; g.Q = (int)W; g.M = N * H * W;
-  g.qdiv = make_fastdiv((uint32_t)W);
-  g.pdiv = make_fastdiv((uint32_t)H);
-  g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
-  g.nblk_n = (int)(K / 128);
+  if (!lab_geom(c, 128, g) || s2.g.M != g.M) return DLMCQ_EINVAL;
   s2.g.nblk_m = g.nblk_m;
   s2.g.nblk_n = g.nblk_n;
-  if (s2.g.M != g.M) return DLMCQ_EINVAL;
-  hipLaunchKernelGGL((conv_i8_mfma_kernel<128, true, true, false, 1>), dim3((uint32_t)((int64_t)g.nblk_m * g.nblk_n)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int8_t*>(x), w, out, nullptr, wsum, in_scale,
-                     in_zero_point, w_scale, g, 128, ep, s2);
-  return launch_status();
+  return conv_tiled_go<128, CV_DUAL | CV_ADIR, 1>(c, g, s2);
 }
 
 // ---- lab library only (libdlmcq_lab.so, `make lab`): the same calls with an explicit tile plan, and the persistent
@@ -1185,94 +1164,51 @@ extern "C" int dlmcq_x_conv2d_i8_tuned(const void* x, const int8_t* w, float* ou
                                        int32_t relu, void* codes, const float* q_scale, const float* q_zero_point,
                                        int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream,
                                        int32_t bn, int32_t adir, int32_t pp_nbuf, int32_t pp_wps) {
-  const ConvEpi ep = make_epi(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  ConvCall c = conv_call(DLMCQ_CALL_ARGS);
+  c.ep = make_epi(residual, DLMCQ_EPI_ARGS);
   if (pp_wps != 0 && relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (the lab variants below have no ReLU6 instantiations)
+  ConvGeom g;
   if (pp_wps > 0) {
-    const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1, Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
-    if (C % CV_BK || K % bn || P < 1 || Q < 1 || N * P * Q >= (1ll << 31)) return DLMCQ_EINVAL;
-    ConvGeom g;
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-    g.stride = stride; g.pad = pad; g.dil = dilation; g.P = (int)P; g.Q = (int)Q; g.M = N * P * Q;
-    g.qdiv = make_fastdiv((uint32_t)Q);
-    g.pdiv = make_fastdiv((uint32_t)P);
-    return dlmcq_conv_pp_launch(reinterpret_cast<const int8_t*>(x), w, out, bias, wsum, in_scale, in_zero_point, w_scale, g,
-                                x_is_unsigned ? 128 : 0, ep, nullptr, bn, pp_nbuf, pp_wps, reinterpret_cast<hipStream_t>(stream));
+    if (!lab_geom(c, bn, g)) return DLMCQ_EINVAL;
+    return dlmcq_conv_pp_launch(c.x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, c.shift, c.ep, nullptr, bn, pp_nbuf, pp_wps, c.st);
   }
-  if (pp_wps <= -100) {    // the halo kernel's what-bounds-the-step variants (LAB = -pp_wps - 100); 1 = stamps into `residual`
-    if (!conv3x3_halo_applies(N, H, W, C, K, R, S, stride, pad, dilation, ConvEpi{nullptr, nullptr, ep.codes}, nullptr, false)) return DLMCQ_EINVAL;
-    ConvEpi e2 = ep;
-    e2.residual = nullptr;
-    return conv3x3_halo_launch(reinterpret_cast<const int8_t*>(x), w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K,
-                               stride, x_is_unsigned ? 128 : 0, e2, reinterpret_cast<hipStream_t>(stream), -pp_wps - 100,
-                               const_cast<float*>(residual));
-  }
-  if (pp_wps <= -40 && pp_wps > -100) {   // ... of the pointwise kernel (LAB = -pp_wps - 40; `bias` doubles as the weight offsets, `residual` as the stamp buffer)
-    ConvEpi e2 = ep;
-    e2.residual = nullptr;
-    e2.w_off = bias;
-    if (!conv_pw_applies(N, H, W, C, K, R, S, stride, pad, dilation, e2, out, false)) return DLMCQ_EINVAL;
-    return conv_pw_launch(reinterpret_cast<const int8_t*>(x), w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K,
-                          x_is_unsigned ? 128 : 0, e2, reinterpret_cast<hipStream_t>(stream), -pp_wps - 40, const_cast<float*>(residual));
-  }
-  if (pp_wps <= -20 && pp_wps > -100) {   // ... of the swapped asymmetric kernels (LAB = -pp_wps - 20, 0 = as built; `bias` doubles as the weight offsets)
-    const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1, Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
-    if (C % CV_BK || K % bn || (bn != 128 && bn != 192) || P < 1 || Q < 1 || N * P * Q >= (1ll << 31) || !ep.codes || out) return DLMCQ_EINVAL;
-    ConvGeom g;
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-    g.stride = stride; g.pad = pad; g.dil = dilation; g.P = (int)P; g.Q = (int)Q; g.M = N * P * Q;
-    g.qdiv = make_fastdiv((uint32_t)Q);
-    g.pdiv = make_fastdiv((uint32_t)P);
-    g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
-    g.nblk_n = (int)(K / bn);
-    const dim3 grid((uint32_t)((int64_t)g.nblk_m * g.nblk_n));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int8_t* xx = reinterpret_cast<const int8_t*>(x);
-    const int shift = x_is_unsigned ? 128 : 0;
-    ConvEpi e2 = ep;
-    e2.residual = nullptr;
-    e2.w_off = bias;
-#define DLMCQ_LABK(B, V) hipLaunchKernelGGL((conv_i8_mfma_kernel<B, false, true, true, V, true>), grid, dim3(256), 0, st, xx, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, e2, ConvSeg2{})
-#define DLMCQ_LABB(V) if (bn == 128) DLMCQ_LABK(128, V); else DLMCQ_LABK(192, V)
-    switch (-pp_wps - 20) {
-      case 0: DLMCQ_LABB(0); break;
-      case 2: DLMCQ_LABB(2); break;
-      case 3: DLMCQ_LABB(3); break;
-      case 4: DLMCQ_LABB(4); break;
-      case 6: DLMCQ_LABB(6); break;
-      case 7: DLMCQ_LABB(7); break;
-      default: return DLMCQ_EINVAL;
+  if (pp_wps < 0) {     // the what-bounds-the-step variants
+    ConvCall c2 = c;      // (the halo, pointwise and swapped ones take no shortcut: `residual` is their stamp buffer)
+    c2.ep.residual = nullptr;
+    if (pp_wps <= -100) {    // the halo kernel's (LAB = -pp_wps - 100); asked as a bare codes-only call
+      ConvCall c3 = c2;
+      c3.ep = ConvEpi{nullptr, nullptr, c.ep.codes};
+      c3.out = nullptr;
+      if (!conv3x3_halo_applies(c3)) return DLMCQ_EINVAL;
+      return conv3x3_halo_launch(c2, -pp_wps - 100, const_cast<float*>(residual));
     }
-#undef DLMCQ_LABB
+    if (pp_wps <= -40) {     // ... of the pointwise kernel (LAB = -pp_wps - 40; `bias` doubles as the weight offsets)
+      c2.ep.w_off = bias;
+      if (!conv_pw_applies(c2)) return DLMCQ_EINVAL;
+      return conv_pw_launch(c2, -pp_wps - 40, const_cast<float*>(residual));
+    }
+    if (pp_wps <= -20) {     // ... of the swapped asymmetric kernels (LAB = -pp_wps - 20, 0 = as built; `bias` doubles as the weight offsets)
+      c2.ep.w_off = bias;
+      if ((bn != 128 && bn != 192) || !lab_geom(c, bn, g) || !c.ep.codes || out) return DLMCQ_EINVAL;
+      switch ((bn == 192 ? 100 : 0) - pp_wps - 20) {
+#define DLMCQ_LABK(V) case V: return conv_tiled_go<128, CV_ADIR | CV_ASYM | CV_SWAP, V>(c2, g, ConvSeg2{}); \
+                      case 100 + V: return conv_tiled_go<192, CV_ADIR | CV_ASYM | CV_SWAP, V>(c2, g, ConvSeg2{})
+        DLMCQ_LABK(0); DLMCQ_LABK(2); DLMCQ_LABK(3); DLMCQ_LABK(4); DLMCQ_LABK(6); DLMCQ_LABK(7);
 #undef DLMCQ_LABK
-    return launch_status();
-  }
-  if (pp_wps < 0) {   // what-bounds-the-step variants of the 128-wide direct-A kernel (LAB = -pp_wps)
-    const int64_t P = (H + 2 * pad - dilation * (R - 1) - 1) / stride + 1, Q = (W + 2 * pad - dilation * (S - 1) - 1) / stride + 1;
-    if (C % CV_BK || K % 128 || P < 1 || Q < 1 || N * P * Q >= (1ll << 31)) return DLMCQ_EINVAL;
-    ConvGeom g;
-    g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.K = (int)K; g.R = (int)R; g.S = (int)S;
-    g.stride = stride; g.pad = pad; g.dil = dilation; g.P = (int)P; g.Q = (int)Q; g.M = N * P * Q;
-    g.qdiv = make_fastdiv((uint32_t)Q);
-    g.pdiv = make_fastdiv((uint32_t)P);
-    g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
-    g.nblk_n = (int)(K / 128);
-    const dim3 grid((uint32_t)((int64_t)g.nblk_m * g.nblk_n));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int8_t* xx = reinterpret_cast<const int8_t*>(x);
-    const int shift = x_is_unsigned ? 128 : 0;
-#define DLMCQ_LABK(V) hipLaunchKernelGGL((conv_i8_mfma_kernel<128, false, true, false, V>), grid, dim3(256), 0, st, xx, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep, ConvSeg2{})
+        default: return DLMCQ_EINVAL;
+      }
+    }
+    if (!lab_geom(c, 128, g)) return DLMCQ_EINVAL;      // ... of the 128-wide direct-A kernel (LAB = -pp_wps); it keeps the call's epilogue
     switch (-pp_wps) {
-      case 2: DLMCQ_LABK(2); break;
-      case 3: DLMCQ_LABK(3); break;
-      case 4: DLMCQ_LABK(4); break;
-      case 5: DLMCQ_LABK(5); break;
+#define DLMCQ_LABK(V) case V: return conv_tiled_go<128, CV_ADIR, V>(c, g, ConvSeg2{})
+      DLMCQ_LABK(2); DLMCQ_LABK(3); DLMCQ_LABK(4); DLMCQ_LABK(5);
+#undef DLMCQ_LABK
       default: return DLMCQ_EINVAL;
     }
-#undef DLMCQ_LABK
-    return launch_status();
   }
   const ConvPlan plan{bn, (adir & 1) != 0, (adir & 2) == 0, (adir & 4) != 0};     // adir bit 1: the unswapped epilogue; bit 2: the halo kernel (A/B runs)
-  return conv_launch(x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation,
-                     x_is_unsigned, stream, ep, nullptr, &plan);
+  return conv_launch(c, &plan);
 }
 #endif
+#undef DLMCQ_CALL_ARGS
+#undef DLMCQ_EPI_ARGS

@@ -1,4 +1,5 @@
-// Definitions shared by the int8 convolution translation units (conv_i8.hip, conv_i8_pp.hip).  Not part of the ABI.
+// Definitions shared by the int8 convolution translation units: the tiled kernel's device records and helpers, and the host-side call
+// record (ConvCall) that conv_launch (conv_i8.hip) and the kernel families it routes to pass around.  Not part of the ABI.
 #pragma once
 
 #include <type_traits>
@@ -107,18 +108,71 @@ __device__ __forceinline__ void bstore16i_nt(const i32x4& v, int voff, const v4i
 }
 constexpr int BUF_BIG = 0x7fff0000;   // a byte offset beyond every buffer these kernels accept (< 2^31 - 64 KiB)
 
-// conv3x3_i8.hip: the halo-tile kernel for 3x3 / stride 1 or 2 / pad 1 layers that emit only their consumer's codes
-bool conv3x3_halo_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                          int32_t dilation, const ConvEpi& ep, const float* out, bool dual);
-int conv3x3_halo_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                        const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
-                        int32_t stride, int shift, const ConvEpi& ep, hipStream_t st, int lab = 0, void* lab_trace = nullptr);
+// A pad shortcut (the PADRES instantiations of conv_i8_mfma_kernel; dlmcq_conv2d_i8_nhwc_padres): ep.residual is the dense fp32 NHWC source
+// [N][h][w][c] of pad(x[:, ::stride, ::stride, :]) with `clo` zero channels in front
+struct PadRes {
+  int h, w, c, stride, clo;
+};
 
-// conv3x3_pipe_i8.hip: the halo-tile kernel persistent and software-pipelined across tiles (stride 1, 128 / 256 / 512 input channels, plain quantiser)
-bool conv3x3_pipe_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t stride, const ConvEpi& ep, int cus);
-int conv3x3_pipe_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                        const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int shift,
-                        const ConvEpi& ep, hipStream_t st, int cus);
+// One int8 convolution as the host dispatch sees it: what an entry point of conv_i8.hip received, once, by name.  conv_launch and
+// every kernel family it routes to (conv_pw_*, conv_pwr_*, conv3x3_halo_*, conv3x3_pipe_*) take this record and fill their own device
+// records (ConvGeom, PwArgs, PwrArgs, HaloGeom, PipeGeom) from it.
+struct ConvCall {
+  const int8_t* x;
+  const int8_t* w;
+  float* out;
+  const float* bias;
+  const int32_t* wsum;
+  const float* s_in;
+  const float* zp_in;
+  const float* s_w;
+  int64_t N, H, W, C, K, R, S;
+  int32_t stride, pad, dil;
+  int shift;                 // 128 when the activation codes are unsigned bytes, else 0
+  hipStream_t st;
+  ConvEpi ep;
+  const ConvSeg2* seg2;      // the dual form's second operand pair, or null
+  const PadRes* padres;      // a pad shortcut's source geometry, or null
+  int64_t P, Q, M;           // derived by conv_call: the output's height and width, N * P * Q
+};
+
+// THE output-size formula.  (A stride below 1 is refused by whoever validates the call; until then it must not divide by zero:
+// dlmcq_conv2d_i8_nhwc_fused_observed sizes its partial planes before conv_launch has looked at the arguments.)
+inline int64_t conv_out_size(int64_t in, int64_t taps, int32_t stride, int32_t pad, int32_t dil) {
+  return (in + 2 * pad - dil * (taps - 1) - 1) / (stride > 0 ? stride : 1) + 1;
+}
+
+// the record of an entry point's ABI arguments; the fields particular to an entry point (ep, seg2, padres) are the caller's to set
+inline ConvCall conv_call(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale,
+                          const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
+                          int64_t R, int64_t S, int32_t stride, int32_t pad, int32_t dilation, int32_t x_is_unsigned,
+                          dlmcq_stream_t stream) {
+  ConvCall c{};
+  c.x = static_cast<const int8_t*>(x); c.w = w; c.out = out; c.bias = bias; c.wsum = wsum; c.s_in = in_scale; c.zp_in = in_zero_point;
+  c.s_w = w_scale;
+  c.N = N; c.H = H; c.W = W; c.C = C; c.K = K; c.R = R; c.S = S; c.stride = stride; c.pad = pad; c.dil = dilation;
+  c.shift = x_is_unsigned ? 128 : 0;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  c.P = conv_out_size(H, R, stride, pad, dilation);
+  c.Q = conv_out_size(W, S, stride, pad, dilation);
+  c.M = N * c.P * c.Q;
+  return c;
+}
+
+// the tiled kernels' geometry of a validated call (every field < 2^31); the tile counts are conv_geom_tiles'
+inline ConvGeom conv_geom(const ConvCall& c) {
+  ConvGeom g{};
+  g.N = (int)c.N; g.H = (int)c.H; g.W = (int)c.W; g.C = (int)c.C; g.K = (int)c.K; g.R = (int)c.R; g.S = (int)c.S;
+  g.stride = c.stride; g.pad = c.pad; g.dil = c.dil; g.P = (int)c.P; g.Q = (int)c.Q; g.M = c.M;
+  g.qdiv = make_fastdiv((uint32_t)c.Q);
+  g.pdiv = make_fastdiv((uint32_t)c.P);
+  return g;
+}
+inline void conv_geom_tiles(ConvGeom& g, int bn) {     // CV_BM pixels x bn channels per workgroup
+  g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
+  g.nblk_n = (g.K + bn - 1) / bn;
+}
+
 // compute units of the current device (cached: one device per process, dlmc/_native.py)
 inline int device_cus() {
   static int cus = 0;
@@ -131,19 +185,24 @@ inline int device_cus() {
   return cus;
 }
 
+// The kernel families conv_launch routes to.  `applies` answers for the whole record - the problem, the epilogue, the fp32 output and
+// the second pair - and `launch` may be called only where it said yes.
+// conv3x3_i8.hip: the halo-tile kernel for 3x3 / stride 1 or 2 / pad 1 layers that emit only their consumer's codes
+bool conv3x3_halo_applies(const ConvCall& c);
+int conv3x3_halo_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
+
+// conv3x3_pipe_i8.hip: the halo-tile kernel persistent and software-pipelined across tiles (stride 1, 128 / 256 / 512 input channels,
+// plain quantiser); asked only about calls the halo kernel takes
+bool conv3x3_pipe_applies(const ConvCall& c, int cus);
+int conv3x3_pipe_launch(const ConvCall& c, int cus);
+
 // conv_pw_i8.hip: pointwise codes-to-codes layers with the weights resident in LDS (MobileOne's 1x1 layers)
-bool conv_pw_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                     int32_t dilation, const ConvEpi& ep, const float* out, bool dual);
-int conv_pw_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                   const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int shift,
-                   const ConvEpi& ep, hipStream_t st, int lab = 0, void* lab_trace = nullptr);
+bool conv_pw_applies(const ConvCall& c);
+int conv_pw_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
 
 // conv_pwr_i8.hip: 1 x 1 block ends with an fp32 shortcut (+ fp32 output) + ReLU + codes, the weights resident in LDS
-bool conv_pwr_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                      int32_t dilation, const ConvEpi& ep, const float* out, const ConvSeg2* seg2);
-int conv_pwr_launch(const int8_t* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale,
-                    const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t stride,
-                    int shift, const ConvEpi& ep, hipStream_t st, const ConvSeg2* seg2 = nullptr);
+bool conv_pwr_applies(const ConvCall& c);
+int conv_pwr_launch(const ConvCall& c);
 
 // conv_dwm_i8.hip: depthwise 3 x 3 / stride 1 / padding 1 codes-to-codes layers on the matrix cores (diagonal weight fragments)
 bool conv_dwm_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad, const ConvEpi& ep,

@@ -291,15 +291,14 @@ constexpr bool pw_built(int64_t C, int bn) {
 }
 
 // where the kernel applies: codes in, codes out, nothing else attached; the widths MobileOne-S1 uses
-bool conv_pw_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                     int32_t dilation, const ConvEpi& ep, const float* out, bool dual) {
-  if (R != 1 || S != 1 || stride != 1 || pad != 0 || dilation != 1 || dual || out || ep.residual || !ep.codes) return false;
+bool conv_pw_applies(const ConvCall& c) {
+  const ConvEpi& ep = c.ep;
+  if (c.R != 1 || c.S != 1 || c.stride != 1 || c.pad != 0 || c.dil != 1 || c.seg2 || c.out || ep.residual || !ep.codes) return false;
   if (!epi_plain(ep)) return false;                             // (other quantisers: the tiled kernel)
-  if (K > 1024 || !pw_built(C, pw_slice(K))) return false;       // (exactly the (C, slice) pairs conv_pw_launch instantiates)
+  if (c.K > 1024 || !pw_built(c.C, pw_slice(c.K))) return false;       // (exactly the (C, slice) pairs conv_pw_launch instantiates)
   if (!aligned16(ep.codes)) return false;
-  const int64_t M = N * H * W;
-  if (M < 4096) return false;                                   // (the weights are loaded once per workgroup: a few blocks per wave at least)
-  if (M * C >= (int64_t)BUF_BIG || M * K >= (int64_t)BUF_BIG) return false;     // 32-bit buffer offsets
+  if (c.M < 4096) return false;                                 // (the weights are loaded once per workgroup: a few blocks per wave at least)
+  if (c.M * c.C >= (int64_t)BUF_BIG || c.M * c.K >= (int64_t)BUF_BIG) return false;     // 32-bit buffer offsets
   return true;
 }
 
@@ -339,13 +338,14 @@ static int pw_go(const PwArgs& a0, const ConvEpi& ep, hipStream_t st) {
   return launch_status();
 }
 
-int conv_pw_launch(const int8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                   const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int shift,
-                   const ConvEpi& ep, hipStream_t st, int lab, void* lab_trace) {
+int conv_pw_launch(const ConvCall& c, int lab, void* lab_trace) {
+  const ConvEpi& ep = c.ep;
+  const int64_t C = c.C, K = c.K;
+  const hipStream_t st = c.st;
   PwArgs a{};
   a.trace = static_cast<unsigned long long*>(lab_trace);
-  a.x = x; a.w = w; a.s_w = w_scale; a.wsum = wsum; a.bias = bias; a.s_in = in_scale; a.zp_in = in_zero_point;
-  a.M = (int)(N * H * W); a.K = (int)K; a.shift = shift;
+  a.x = c.x; a.w = c.w; a.s_w = c.s_w; a.wsum = c.wsum; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
+  a.M = (int)c.M; a.K = (int)K; a.shift = c.shift;
   a.nblk = (a.M + 31) / 32;
   const bool asym = ep.w_off != nullptr;
   const int bn = pw_slice(K);

@@ -319,14 +319,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_pwr_i8_kernel(PwrArgs a,
 }
 
 // where the kernel applies: a 1 x 1 block end with an fp32 shortcut and ReLU that emits its consumer's plain codes
-bool conv_pwr_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t pad,
-                      int32_t dilation, const ConvEpi& ep, const float* out, const ConvSeg2* seg2) {
-  if (R != 1 || S != 1 || pad != 0 || dilation != 1 || !ep.relu || ep.w_off) return false;
+bool conv_pwr_applies(const ConvCall& c) {
+  const ConvEpi& ep = c.ep;
+  const float* const out = c.out;
+  const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, P = c.P, Q = c.Q, M = c.M;
+  const int32_t stride = c.stride;
+  if (c.R != 1 || c.S != 1 || c.pad != 0 || c.dil != 1 || !ep.relu || ep.w_off) return false;
   if (ep.relu == DLMCQ_ACT_RELU6) return false;                 // (ReLU only: ReLU6 block ends take the tiled kernel)
   if (ep.codes ? !epi_plain(ep) : !out) return false;            // (other quantisers: the tiled kernel)
-  const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
-  const int64_t M = N * P * Q;
-  if (seg2) {
+  if (const ConvSeg2* const seg2 = c.seg2) {
     // the dual form (a stage's first block: one addend is the block's last 1x1 convolution - 256 channels, read row by row -, the
     // other the 1x1 / stride-s convolution on the shortcut - 512 channels, sampled; either may be the call's first pair): ResNet-50's
     // 28^2 -> 14^2 block, whose two weight slices ((256 + 512) x 128 bytes) fit the LDS together; fp32 output and codes
@@ -376,14 +377,16 @@ static int pwr_go(const PwrArgs& a0, const ConvEpi& ep, hipStream_t st) {
   return launch_status();
 }
 
-int conv_pwr_launch(const int8_t* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale,
-                    const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int32_t stride,
-                    int shift, const ConvEpi& ep, hipStream_t st, const ConvSeg2* seg2) {
-  const int64_t P = (H - 1) / stride + 1, Q = (W - 1) / stride + 1;
+int conv_pwr_launch(const ConvCall& c) {
+  const ConvEpi& ep = c.ep;
+  const ConvSeg2* const seg2 = c.seg2;
+  float* const out = c.out;
+  const int64_t C = c.C;
+  const hipStream_t st = c.st;
   PwrArgs a{};
-  a.x = x; a.w = w; a.s_w = w_scale; a.wsum = wsum; a.bias = bias; a.s_in = in_scale; a.zp_in = in_zero_point;
+  a.x = c.x; a.w = c.w; a.s_w = c.s_w; a.wsum = c.wsum; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
   a.residual = ep.residual; a.out = out;
-  a.M = (int)(N * P * Q); a.K = (int)K; a.shift = shift;
+  a.M = (int)c.M; a.K = (int)c.K; a.shift = c.shift;
   a.nblk = a.M / 32;
   const bool fcm = (ep.ctl & (ep.residual ? DLMCQ_FP32_IN_CHUNK_MAJOR : DLMCQ_FP32_OUT_CHUNK_MAJOR)) != 0;
   a.f_rowb = fcm ? 256 : a.K * 4;
@@ -397,9 +400,9 @@ int conv_pwr_launch(const int8_t* x, const int8_t* w, float* out, const float* b
   constexpr int N2 = DLMCQ_PWR_NW256, N5 = DLMCQ_PWR_NW512;
   if (seg2) {
     const ConvGeom& g2 = seg2->g;
-    a.P = (int)P; a.Q = (int)Q;
-    a.qdiv = make_fastdiv((uint32_t)Q);
-    a.pdiv = make_fastdiv((uint32_t)P);
+    a.P = (int)c.P; a.Q = (int)c.Q;
+    a.qdiv = make_fastdiv((uint32_t)c.Q);
+    a.pdiv = make_fastdiv((uint32_t)c.P);
     if (C == 256) {      // the call's first pair is the row-by-row one
       a.x2 = seg2->x; a.w2 = seg2->w; a.s_w2 = seg2->s_w; a.wsum2 = seg2->wsum; a.bias2 = seg2->bias; a.s_in2 = seg2->s_in; a.zp_in2 = seg2->zp_in;
       a.shift2 = seg2->shift; a.H2 = g2.H; a.W2 = g2.W; a.stride2 = g2.stride;
@@ -408,8 +411,8 @@ int conv_pwr_launch(const int8_t* x, const int8_t* w, float* out, const float* b
     // ... or the sampled one: the roles change places (the sum's operand order is kept: first pair + second pair)
     a.x = seg2->x; a.w = seg2->w; a.s_w = seg2->s_w; a.wsum = seg2->wsum; a.bias = seg2->bias; a.s_in = seg2->s_in; a.zp_in = seg2->zp_in;
     a.shift = seg2->shift;
-    a.x2 = x; a.w2 = w; a.s_w2 = w_scale; a.wsum2 = wsum; a.bias2 = bias; a.s_in2 = in_scale; a.zp_in2 = in_zero_point;
-    a.shift2 = shift; a.H2 = (int)H; a.W2 = (int)W; a.stride2 = stride;
+    a.x2 = c.x; a.w2 = c.w; a.s_w2 = c.s_w; a.wsum2 = c.wsum; a.bias2 = c.bias; a.s_in2 = c.s_in; a.zp_in2 = c.zp_in;
+    a.shift2 = c.shift; a.H2 = (int)c.H; a.W2 = (int)c.W; a.stride2 = c.stride;
     return pwr_go<256, 6, true, true, 512, true>(a, ep, st);
   }
   if (!ep.codes) return C == 256 ? pwr_go<256, N2, true, false>(a, ep, st) : (C == 512 ? pwr_go<512, N5, true, false>(a, ep, st) : DLMCQ_EINVAL);
