@@ -817,6 +817,20 @@ constexpr bool conv_variant_built(ConvVariant v) {
   return false;
 }
 
+// DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_VARIANT: the variant as the route query's answer (include/dlmcq.h: tag | width << 8 | flags)
+static_assert((CV_DUAL | CV_ADIR | CV_ASYM | CV_SWAP | CV_R6 | CV_XOFF | CV_NARROW | CV_PADRES) == 0xff, "the flags are the answer's low byte");
+constexpr int conv_variant_answer(ConvVariant v) { return DLMCQ_ROUTE_VARIANT_TAG | (v.bn << 8) | (int)v.flags; }
+
+// The table itself, for tests (absent from include/dlmcq.h): fills up to `cap` (width, flags) pairs in the table's order and returns how
+// many there are - expanded from DLMCQ_CV_TABLE, so the list a test sees is the list conv_variant_launch holds
+extern "C" int dlmcq_x_conv_variant_table(int32_t* bn, uint32_t* flags, int cap) {
+  int n = 0;
+#define DLMCQ_CV_LIST(BN, F) if (n < cap) { if (bn) bn[n] = BN; if (flags) flags[n] = (F); } ++n;
+  DLMCQ_CV_TABLE(DLMCQ_CV_LIST)
+#undef DLMCQ_CV_LIST
+  return n;
+}
+
 // value -> kernel: the one place the kernel's positional template list is spelt (LAB: the lab library's what-bounds-the-step variants)
 template <int BN, unsigned F, int LAB = 0>
 static int conv_tiled_go(const ConvCall& c, const ConvGeom& g, const ConvSeg2& s2) {
@@ -848,6 +862,7 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   const ConvSeg2* const seg2 = c.seg2;
   const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, R = c.R, S = c.S, P = c.P, Q = c.Q, M = c.M;
   if (mm_count) *mm_count = 0;
+  if ((ep.ctl & DLMCQ_ROUTE_VARIANT) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (a question about the route, never a launch)
   if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || c.stride < 1 || c.pad < 0 || c.dil < 1) return DLMCQ_EINVAL;
   if (C % CV_BK != 0) return DLMCQ_EINVAL;  // the K step is 64 input channels
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;
@@ -932,7 +947,7 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
     if (s2.g.M != g.M || s2.g.K != g.K || s2.g.P != g.P || s2.g.Q != g.Q) return DLMCQ_EINVAL;
   }
   if (c.padres) seg2_carry_padres(s2, *c.padres);
-  if (route_only) return DLMCQ_ROUTE_TILED;
+  if (route_only) return (ep.ctl & DLMCQ_ROUTE_VARIANT) ? conv_variant_answer(v) : DLMCQ_ROUTE_TILED;
   if (mm_req && c.out) {                             // one partial per workgroup of this launch
     ep.mm = mm_req;
     ep.mm_np = (int)nwg;

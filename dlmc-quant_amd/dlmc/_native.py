@@ -33,6 +33,10 @@ FP32_IN_CHUNK_MAJOR = 0x2000   # DLMCQ_FP32_IN_CHUNK_MAJOR: a chain call's fp32 
 FP32_OUT_CHUNK_MAJOR = 0x4000  # DLMCQ_FP32_OUT_CHUNK_MAJOR: ... and / or its fp32 block output
 PAD_CODE0 = 0x8000       # DLMCQ_PAD_CODE0: quantize_pad_nhwc4's border holds code 0 (a float-offset quantiser's padding)
 PIPELINED = 0x1000       # DLMCQ_PIPELINED (opt-in): the persistent, software-pipelined halo-tile 3x3 kernel where it applies
+ROUTE_VARIANT = 0x10000  # DLMCQ_ROUTE_VARIANT: with ROUTE_ONLY, a ROUTE_TILED answer names the tiled kernel's instantiation instead (decode_variant)
+ROUTE_VARIANT_TAG = 1 << 24
+# the `flags` of such an answer: conv_i8_mfma_kernel's boolean template parameters (include/dlmcq.h)
+CV_DUAL, CV_ADIR, CV_ASYM, CV_SWAP, CV_R6, CV_XOFF, CV_NARROW, CV_PADRES = 1, 2, 4, 8, 16, 32, 64, 128
 ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE, ROUTE_GAP = 1, 2, 3, 4, 5, 6, 7, 8
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
              ROUTE_DWM: "conv_dwm", ROUTE_HALO3X3_PIPE: "conv3x3_pipe", ROUTE_GAP: "conv_gap"}     # the profile tag (bench.py's kernel families) of each route
@@ -199,6 +203,23 @@ def route(rc):
     if rc <= 0:
         raise DlmcqError(f"{lib.dlmcq_strerror(rc).decode()} (code {rc})" if rc < 0 else "route query returned DLMCQ_OK (an empty problem)")
     return rc
+
+
+def decode_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_VARIANT call -> (tile width, flags) of the conv_i8_mfma_kernel instantiation, or None when the
+    answer is no variant (another kernel's ROUTE_*, DLMCQ_OK, a refusal)."""
+    if rc < ROUTE_VARIANT_TAG or rc >> 25:
+        return None
+    return (rc >> 8) & 0xffff, rc & 0xff
+
+
+def conv_variant_table():
+    """[(tile width, flags)]: the instantiations of conv_i8_mfma_kernel the library holds, as its own launcher lists them."""
+    fn = experimental("dlmcq_x_conv_variant_table", [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_int])
+    n = fn(None, None, 0)
+    bn, flags = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)()
+    assert fn(bn, flags, n) == n
+    return [(int(b), int(f)) for b, f in zip(bn, flags)]
 
 
 def stream_ptr():

@@ -112,6 +112,16 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * holds code 0 (with DLMCQ_EMIT_SHIFT128: the byte 0x80) instead of the code of x' = 0.  The padding of a float-offset quantiser
  * (x^ = q * s^ + o, o no code) for dlmcq_conv2d_i8_stem_xoff with a zero point of 0. */
 #define DLMCQ_PAD_CODE0 0x8000
+/* DLMCQ_ROUTE_VARIANT (the dlmcq_conv2d_i8_nhwc_* entry points that take DLMCQ_ROUTE_ONLY; OR-able only TOGETHER with DLMCQ_ROUTE_ONLY -
+ * alone it is DLMCQ_EINVAL): where the route query would answer DLMCQ_ROUTE_TILED it answers WHICH instantiation of conv_i8_mfma_kernel the
+ * call launches instead:  DLMCQ_ROUTE_VARIANT_TAG | (tile width << 8) | flags,  with the tile width in channels (64, 128, 192 or 256) and
+ * `flags` the kernel's boolean template parameters: 1 DUAL (two operand pairs), 2 ADIR (activations straight to registers), 4 ASYM
+ * (per-channel weight offsets), 8 SWAP (the codes-only epilogue in the swapped accumulator layout), 16 R6 (ReLU6), 32 XOFF (float
+ * activation offset), 64 NARROW (narrow fp32 rows), 128 PADRES (pad shortcut).  Always above every DLMCQ_ROUTE_*; every other answer -
+ * another kernel's route, DLMCQ_OK for an empty problem, a refusal - is what it is without the bit.  (tests/: which of the library's
+ * instantiations a case really runs.) */
+#define DLMCQ_ROUTE_VARIANT 0x10000
+#define DLMCQ_ROUTE_VARIANT_TAG (1 << 24)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */

@@ -240,3 +240,97 @@ def identity_pw(k, c, nz, gen, density=0.05):
     for i in range(nz):
         b[m + i] = EDGE_VALUES[i % len(EDGE_VALUES)]
     return wq, b
+
+
+# ------------------------------------------------------------------------------------------------ full-range operands, dyadic scales
+# The int32 accumulation of the int8 kernels is exact and their dequantisation is ONE fma.  With power-of-two scales the fp32 result is
+# therefore the real-valued result for operands over the whole byte range, as long as every fp32 stage of the epilogue's chain stays
+# representable (sums below 2^24 units): the layers below have codes uniform over all 256 byte values, weight codes uniform in +-127,
+# per-channel weight scales 2^-(10 + k % 5) that differ from channel to channel, an input scale 2^e != 1 and biases that are multiples of
+# each channel's s_in * s_w[k] - and are still compared with no tolerance (tests/test_gpu_tiled_variants.py).
+FULL_TARGET_SIGMA = 12.0        # standard deviation of the outputs of the widest-scale channels: a good share of them lies in (0, 6)
+TIE_SCALES = (0.25, 2.0 ** -5, 0.5)     # the consumer scales of tests/test_gpu_tiled_variants.py: the biases carry tie fractions against them
+
+
+@dataclass
+class FullLayer:
+    """codes (N, C, H, W) uint8 / int8 over the full byte range; wq int8 (K, C, R, S) in +-127, zero on channels [0, nz) and [live, K);
+    s_w fp32 [K] dyadic; w_int int [K] or None: the weight offset in units of s_w[k]; s_in a power of two; bias fp32 [K]."""
+    codes: torch.Tensor
+    zp: int
+    wq: torch.Tensor
+    s_w: torch.Tensor
+    w_int: Optional[torch.Tensor]
+    s_in: float
+    bias: torch.Tensor
+    nz: int
+    live: int
+
+    @property
+    def unit(self):                 # s_in * s_w[k], float64 (a power of two: exact)
+        return self.s_in * self.s_w.double()
+
+    @property
+    def w_off(self):
+        return None if self.w_int is None else exact_f32(self.w_int.double() * self.s_w.double(), "weight offset")
+
+    def xint(self):
+        return self.codes.double() - self.zp
+
+    def w64(self):
+        w = self.wq.double() if self.w_int is None else self.wq.double() + self.w_int.double().reshape(-1, 1, 1, 1)
+        return w * self.s_w.double().reshape(-1, 1, 1, 1)
+
+
+def full_range_bias(k, nz, live, unit, gen, edge=True):
+    """Bias [k], every entry a multiple of its channel's unit: the edge values (or 0: `edge=False`, a residual carries them) on the
+    zero-weight channels [0, nz), tie fractions against the consumer scales plus small integers on [nz, live), 0 on [live, k)."""
+    b = torch.zeros(k, dtype=torch.float64)
+    n = live - nz
+    idx = torch.arange(n)
+    s = torch.tensor(TIE_SCALES, dtype=torch.float64)[idx % len(TIE_SCALES)]
+    frac = torch.tensor(TIE_FRACTIONS, dtype=torch.float64)[(idx // len(TIE_SCALES)) % len(TIE_FRACTIONS)]
+    b[nz:live] = s * (frac + torch.randint(-3, 4, (n,), generator=gen).double())
+    q = b[nz:live] / unit[nz:live]
+    assert bool((q == q.round()).all()), "a bias is no multiple of its channel's s_in * s_w[k]"
+    b = b.float()
+    if edge:
+        for i in range(nz):
+            b[i] = EDGE_VALUES[i % len(EDGE_VALUES)]
+    return b
+
+
+def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asym=False, zp=None, live=None, edge_bias=True, zp_side=None):
+    """Random full-range operands (see above).  zp: the input zero point - default: an integer in 1..254 other than 128 for uint8 codes,
+    0 for int8 codes.  `live`: channels [live, k)
+    are all zero (the padding of a narrow layer).  `zp_side`: "high" / "low" - a uint8 zero point above / below 128 (padded calls: the pad-table
+    byte has its high bit set, or not; a wrong sign or shift of the padding shows in the first); default: either."""
+    s = r if s is None else s
+    live = k if live is None else live
+    nz = min(len(EDGE_VALUES), live - max(8, live // 4))
+    if signed_in:
+        codes = torch.randint(-128, 128, (n, c, h, w), generator=gen).to(torch.int8)
+        zp = 0 if zp is None else zp
+    else:
+        codes = torch.randint(0, 256, (n, c, h, w), generator=gen).to(torch.uint8)
+        if zp is None:
+            d = int(torch.randint(1, 127, (1,), generator=gen))
+            up = bool(torch.randint(0, 2, (1,), generator=gen)) if zp_side is None else zp_side == "high"
+            zp = 128 + d if up else 128 - d
+    wq = torch.randint(-127, 128, (k, c, r, s), generator=gen).to(torch.int8)
+    wq[:nz] = 0
+    wq[live:] = 0
+    s_w = (2.0 ** -(10 + torch.arange(k) % 5).double()).float()
+    w_int = None
+    if asym:
+        w_int = torch.randint(-1, 2, (k,), generator=gen)
+        w_int[:nz] = 0
+        w_int[live:] = 0
+    # the input scale: a power of two that puts the widest-scale channels' outputs at FULL_TARGET_SIGMA (from the shape alone: the
+    # integer sum of r s c products of a uniform byte about its zero point and a uniform weight code)
+    mean = (-0.5 if signed_in else 127.5) - zp
+    sigma_int = math.sqrt(r * s * c) * math.sqrt((127 * 128) / 3.0) * math.sqrt((256 * 256 - 1) / 12.0 + mean * mean)
+    s_in = 2.0 ** round(math.log2(FULL_TARGET_SIGMA / (sigma_int * 2.0 ** -10)))
+    lay = FullLayer(codes, int(zp), wq, s_w, w_int, s_in, torch.zeros(k), nz, live)
+    lay.bias = full_range_bias(k, nz, live, lay.unit, gen, edge=edge_bias)
+    return lay
