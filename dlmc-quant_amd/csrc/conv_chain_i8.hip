@@ -23,37 +23,19 @@
 namespace dlmcq {
 
 struct ChainArgs {
-  // GEMM 1: block end.  x codes [M][C1], w1 [KD][C1] int8, per-channel scale / code sum / bias [KD]
-  const int8_t* x;
-  const int8_t* w1;
-  const float* s_w1;
-  const int32_t* wsum1;
-  const float* bias1;
-  const float* s_in1;
-  const float* zp_in1;
+  // GEMM 1: block end.  x codes [M][C1], w [KD][C1] int8, per-channel scale / code sum / bias [KD]
+  ChainOp o1;
   int shift1;
   const float* residual;   // fp32 [M][KD] (required unless the shortcut is a convolution: C2 > 0)
-  // the shortcut as a second 1x1 convolution into the same tile (C2 > 0; the block's downsample): x2 codes [N][H2][W2][C2]
-  // sampled at (p * stride2, q * stride2), w2 [KD][C2]
-  const int8_t* x2;
-  const int8_t* w2;
-  const float* s_w2;
-  const int32_t* wsum2;
-  const float* bias2;
-  const float* s_in2;
-  const float* zp_in2;
+  // the shortcut as a second 1x1 convolution into the same tile (C2 > 0; the block's downsample): x codes [N][H2][W2][C2]
+  // sampled at (p * stride2, q * stride2), w [KD][C2]
+  ChainOp o2;
   int shift2, P, Q, H2, W2, stride2;
   FastDiv qdiv, pdiv;
   // the shortcut RECOMPUTED (CA > 0; the second block of a stage): it is the output relu?(conv1x1(xa, wa) + conv1x1(xb sampled, wb)) of the
   // stage's first, convolution-shortcut block, whose operands are handed over instead of its fp32 tensor.  The sampled operand (xb, wb, ...)
-  // travels in the x2 / w2 / ... fields above, the unit-stride one here: xa codes [M][CA], wa [KD][CA]
-  const int8_t* xa;
-  const int8_t* wa;
-  const float* s_wa;
-  const int32_t* wsuma;
-  const float* biasa;
-  const float* s_ina;
-  const float* zp_ina;
+  // travels in o2 above, the unit-stride one here: x codes [M][CA], w [KD][CA]
+  ChainOp oa;
   int shifta, relu_sc;
   float* out;              // fp32 [M][KD] or null
   uint8_t* codes;          // [M][KD] or null
@@ -71,6 +53,10 @@ struct ChainArgs {
   int lab;                     // lab builds: 1 = no shortcut loads (timing only)
   unsigned long long* trace;   // lab builds: 64 clock-stamp slots per workgroup (null: none)
 };
+// (the kernel's scalar argument loads stay where they were when the three operands were spelt field by field)
+static_assert(sizeof(ChainOp) == 56 && offsetof(ChainArgs, residual) == 64 && offsetof(ChainArgs, P) == 132 && offsetof(ChainArgs, relu_sc) == 236 &&
+              offsetof(ChainArgs, out) == 240 && offsetof(ChainArgs, w3) == 256 && offsetof(ChainArgs, M) == 304 &&
+              offsetof(ChainArgs, f_rowq) == 316 && sizeof(ChainArgs) == 344, "ChainArgs: a field moved");
 
 template <int CTRL>
 __device__ __forceinline__ float quad_dpp(float v) {
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
   {
     const int lrw = tid >> 2;                                 // = wave * 16 + (lane >> 2): the row of a 64-row unit this lane fetches
     const int sgw = ((tid & 3) ^ ((lrw >> 2) & 3)) * 16;
-    const int8_t* xp = a.x + (row0 + (lrw < rows_here ? lrw : rows_here - 1)) * C1 + sgw;
+    const int8_t* xp = a.o1.x + (row0 + (lrw < rows_here ? lrw : rows_here - 1)) * C1 + sgw;
 #pragma unroll
     for (int s = 0; s < S1; ++s)
       __builtin_amdgcn_global_load_lds((gptr_t)(xp + s * 64), (lptr_t)(lds + WCH + s * 4096 + (tid >> 6) * 1024), 16, 0, 0);
@@ -196,20 +182,20 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
       const uint32_t m = (uint32_t)(row0 + (lrw < rows_here ? lrw : rows_here - 1));
       const uint32_t t = fdiv(m, a.qdiv), nn = fdiv(t, a.pdiv);
       const int q = (int)(m - t * (uint32_t)a.Q), pp = (int)(t - nn * (uint32_t)a.P);
-      const int8_t* xp2 = a.x2 + (((int64_t)nn * a.H2 + pp * a.stride2) * a.W2 + q * a.stride2) * C2 + sgw;
+      const int8_t* xp2 = a.o2.x + (((int64_t)nn * a.H2 + pp * a.stride2) * a.W2 + q * a.stride2) * C2 + sgw;
 #pragma unroll
       for (int s = 0; s < S2; ++s)
         __builtin_amdgcn_global_load_lds((gptr_t)(xp2 + s * 64), (lptr_t)(lds + WCH + (S1 + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
     }
     if constexpr (RC) {      // the previous block's operands: xa row for row like x, xb sampled like the convolution shortcut's x2
-      const int8_t* xpa = a.xa + (row0 + (lrw < rows_here ? lrw : rows_here - 1)) * CA + sgw;
+      const int8_t* xpa = a.oa.x + (row0 + (lrw < rows_here ? lrw : rows_here - 1)) * CA + sgw;
 #pragma unroll
       for (int s = 0; s < SA; ++s)
         __builtin_amdgcn_global_load_lds((gptr_t)(xpa + s * 64), (lptr_t)(lds + WCH + (S1 + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
       const uint32_t m = (uint32_t)(row0 + (lrw < rows_here ? lrw : rows_here - 1));
       const uint32_t t = fdiv(m, a.qdiv), nn = fdiv(t, a.pdiv);
       const int q = (int)(m - t * (uint32_t)a.Q), pp = (int)(t - nn * (uint32_t)a.P);
-      const int8_t* xpb = a.x2 + (((int64_t)nn * a.H2 + pp * a.stride2) * a.W2 + q * a.stride2) * CB + sgw;
+      const int8_t* xpb = a.o2.x + (((int64_t)nn * a.H2 + pp * a.stride2) * a.W2 + q * a.stride2) * CB + sgw;
 #pragma unroll
       for (int s = 0; s < SB; ++s)
         __builtin_amdgcn_global_load_lds((gptr_t)(xpb + s * 64), (lptr_t)(lds + WCH + (S1 + SA + s) * 4096 + (tid >> 6) * 1024), 16, 0, 0);
@@ -335,22 +321,22 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
   const int lrow = lane >> 2, pslot = lane & 3;
   const int drow = wave * 16 + lrow;                       // row of a 64-row unit this lane fetches
   const int dseg = (pslot ^ ((drow >> 2) & 3)) * 16;
-  const int8_t* w1p = a.w1 + (int64_t)drow * C1 + dseg;    // + chunk * 64 * C1 + s * 64
+  const int8_t* w1p = a.o1.w + (int64_t)drow * C1 + dseg;    // + chunk * 64 * C1 + s * 64
   // W3's rows are dealt to the LDS rows so that accumulator register i of GEMM 2 (weights as the A operand) is channel
   // 16 hsel + i of its 32-channel block: LDS row d of a block holds channel 16 ((d >> 2) & 1) + 4 (d >> 3) + (d & 3)
   const int d3 = drow & 31;
   const int prow3 = (drow & 32) + 16 * ((d3 >> 2) & 1) + 4 * (d3 >> 3) + (d3 & 3);
   const int8_t* w3p = a.w3 + (int64_t)prow3 * a.w3_row + dseg;  // + unit * 64 * w3_row + chunk * w3_chunk
   const int cvo = drow < rows_here ? (int)((row0 + drow) * a.KD + dseg) : CH_BIG;   // this lane's 16 bytes of the code tile, chunk 0
-  const void* const pars[4] = {a.s_w1, a.wsum1, a.bias1 ? (const void*)a.bias1 : (const void*)a.s_w1, a.s_w1};
+  const void* const pars[4] = {a.o1.s_w, a.o1.wsum, a.o1.bias ? (const void*)a.o1.bias : (const void*)a.o1.s_w, a.o1.s_w};
   const int32_t* parp = static_cast<const int32_t*>(wave == 0 ? pars[0] : wave == 1 ? pars[1] : wave == 2 ? pars[2] : pars[3]) + lane;
-  const int8_t* w2p = DUALH ? a.w2 + (int64_t)drow * C2 + dseg : nullptr;
-  const void* const pars2[4] = {a.s_w2, a.wsum2, a.bias2 ? (const void*)a.bias2 : (const void*)a.s_w2, a.s_w2};
+  const int8_t* w2p = DUALH ? a.o2.w + (int64_t)drow * C2 + dseg : nullptr;
+  const void* const pars2[4] = {a.o2.s_w, a.o2.wsum, a.o2.bias ? (const void*)a.o2.bias : (const void*)a.o2.s_w, a.o2.s_w};
   const int32_t* parp2 = static_cast<const int32_t*>(wave == 0 ? pars2[0] : wave == 1 ? pars2[1] : wave == 2 ? pars2[2] : pars2[3]) + lane;
   // the recomputed shortcut's weights and tables: Wa in units S1.., Wb behind it; tables 1 (a) and 2 (b) of the chunk's NPD = 3
-  const int8_t* wap = RC ? a.wa + (int64_t)drow * CA + dseg : nullptr;
-  const int8_t* wbp = RC ? a.w2 + (int64_t)drow * CB + dseg : nullptr;
-  const void* const parsa[4] = {a.s_wa, a.wsuma, a.biasa ? (const void*)a.biasa : (const void*)a.s_wa, a.s_wa};
+  const int8_t* wap = RC ? a.oa.w + (int64_t)drow * CA + dseg : nullptr;
+  const int8_t* wbp = RC ? a.o2.w + (int64_t)drow * CB + dseg : nullptr;
+  const void* const parsa[4] = {a.oa.s_w, a.oa.wsum, a.oa.bias ? (const void*)a.oa.bias : (const void*)a.oa.s_w, a.oa.s_w};
   const int32_t* parpa = static_cast<const int32_t*>(wave == 0 ? parsa[0] : wave == 1 ? parsa[1] : wave == 2 ? parsa[2] : parsa[3]) + lane;
 
   f32x4 res[2][4];
@@ -417,13 +403,13 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
     }
   };
 
-  const float sin1 = a.s_in1[0];
-  const float zpf1 = a.zp_in1 ? a.zp_in1[0] : 0.0f;
+  const float sin1 = a.o1.s_in[0];
+  const float zpf1 = a.o1.zp_in ? a.o1.zp_in[0] : 0.0f;
   const int dz1 = a.shift1 - (int)__builtin_rintf(zpf1);
-  const float sin1b = (DUALH || RC) ? a.s_in2[0] : 0.0f;
-  const int dz1b = (DUALH || RC) ? a.shift2 - (int)__builtin_rintf(a.zp_in2 ? a.zp_in2[0] : 0.0f) : 0;
-  const float sin1a = RC ? a.s_ina[0] : 0.0f;
-  const int dz1a = RC ? a.shifta - (int)__builtin_rintf(a.zp_ina ? a.zp_ina[0] : 0.0f) : 0;
+  const float sin1b = (DUALH || RC) ? a.o2.s_in[0] : 0.0f;
+  const int dz1b = (DUALH || RC) ? a.shift2 - (int)__builtin_rintf(a.o2.zp_in ? a.o2.zp_in[0] : 0.0f) : 0;
+  const float sin1a = RC ? a.oa.s_in[0] : 0.0f;
+  const int dz1a = RC ? a.shifta - (int)__builtin_rintf(a.oa.zp_in ? a.oa.zp_in[0] : 0.0f) : 0;
   ConvEpi e1 = ep1;
   e1.codes = reinterpret_cast<uint8_t*>(uintptr_t(1));   // the quantiser is always needed (GEMM 2 reads its codes)
   // FL >= 0 also says: both quantisers are the plain unsigned-byte one (epi_plain_q; the launcher checks) - code4n_plain, whose
@@ -474,7 +460,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
           acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af2[s][ks], bf, acc, 0, 0, 0);
         }
       const float mult2 = sin1b * *reinterpret_cast<const float*>(pp + 1024);
-      const float bv2 = a.bias2 ? *reinterpret_cast<const float*>(pp + 1024 + 512) : 0.0f;
+      const float bv2 = a.o2.bias ? *reinterpret_cast<const float*>(pp + 1024 + 512) : 0.0f;
       const f32x2 c2{corr2f, corr2f}, m2{mult2, mult2}, b2{bv2, bv2};
 #pragma unroll
       for (int i = 0; i < 8; ++i) extra2[i] = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
@@ -498,7 +484,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afb[s][ks], bf, acc, 0, 0, 0);
           }
         const float multb = sin1b * *reinterpret_cast<const float*>(pp + 2048);
-        const float bvb = a.bias2 ? *reinterpret_cast<const float*>(pp + 2048 + 512) : 0.0f;
+        const float bvb = a.o2.bias ? *reinterpret_cast<const float*>(pp + 2048 + 512) : 0.0f;
         const f32x2 c2{corrbf, corrbf}, m2{multb, multb}, b2{bvb, bvb};
 #pragma unroll
         for (int i = 0; i < 8; ++i) eb[i] = pk_fma(f32x2{(float)acc[2 * i], (float)acc[2 * i + 1]} + c2, m2, b2);
@@ -515,7 +501,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(afa[s][ks], bf, acc, 0, 0, 0);
           }
         const float multa = sin1a * *reinterpret_cast<const float*>(pp + 1024);
-        const float bva = a.biasa ? *reinterpret_cast<const float*>(pp + 1024 + 512) : 0.0f;
+        const float bva = a.oa.bias ? *reinterpret_cast<const float*>(pp + 1024 + 512) : 0.0f;
         const f32x2 c2{corraf, corraf}, m2{multa, multa}, b2{bva, bva};
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -552,7 +538,7 @@ __global__ __launch_bounds__(256, CHAIN_WGS(C1 + C2 + CA + CB, KB)) void conv_ch
     CHAIN_FINE(0);
     // ---- epilogue 1 ----
     const float mult = sin1 * *reinterpret_cast<const float*>(pp);
-    const float bv = a.bias1 ? *reinterpret_cast<const float*>(pp + 512) : 0.0f;
+    const float bv = a.o1.bias ? *reinterpret_cast<const float*>(pp + 512) : 0.0f;
     float v[16];
     {
       const f32x2 c2{corrf, corrf}, m2{mult, mult}, b2{bv, bv};
@@ -691,87 +677,131 @@ static int g_chain_lab = 0;
 extern "C" void dlmcq_x_chain_lab(int flags) { g_chain_lab = flags; }
 #endif
 
-static int chain_launch(ChainArgs& a, int64_t M, int64_t C, int64_t K, int64_t C2, int64_t K2, int32_t relu, void* codes,
-                        const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
-                        int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi,
-                        int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream, int64_t CA = 0, int64_t CB = 0) {
-  if (relu == DLMCQ_ACT_RELU6 || relu2 == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only: the flags below read any non-zero value as ReLU)
-  if (q_lo != 0 || q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
-  if (q2_form & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED)) return DLMCQ_EINVAL;   // (no other kernel, no route query here)
-  const bool w3cm = (q2_form & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (q2_form & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
-  // (a call without a shortcut tensor - the convolution-shortcut form - or without an output has ONE fp32 tensor: its layout is the call's)
-  const bool icm = (C2 == 0 && a.residual) ? (q2_form & DLMCQ_FP32_IN_CHUNK_MAJOR) != 0 : ocm;
-  const bool ocm2 = a.out ? ocm : icm;
-  q2_form &= ~(DLMCQ_W2_CHUNK_MAJOR | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR);
-  if (icm != ocm2 && C2 == 0 && C == 128 && K2 == 128) return DLMCQ_EINVAL;   // (no registers for two offset sets there: conv_chain_i8_kernel)
-  a.w3_row = w3cm ? 64 : (int)K;
-  a.w3_chunk = w3cm ? (int)K2 * 64 : 64;
-  ConvEpi ep1{}, ep2{};
-  if (q2_lo > q2_hi || q2_lo < -128 || q2_hi > 255 || q2_hi - q2_lo > 255 || q_form < DLMCQ_FORM_EMULATE ||
-      q_form > DLMCQ_FORM_SYMMETRIC || !epi_set_form(ep2, q2_form, q2_lo, q2_hi))
+// value -> kernel: one launcher per instantiation, and THE table of the instantiations there are - 7 rows x 3 forms of the first
+// epilogue (FL = 3: ReLU + fp32 output, 1: ReLU, -1: read at run time), 21 + 2 kernels.  A null entry: no such kernel.
+typedef void (*ChainGo)(dim3 grid, size_t dyn, hipStream_t st, const ChainArgs& a, const ConvEpi& ep1, const ConvEpi& ep2);
+template <int C1, int KB, int C2, int FL, int CA, int CB>
+static void chain_go(dim3 grid, size_t dyn, hipStream_t st, const ChainArgs& a, const ConvEpi& ep1, const ConvEpi& ep2) {
+  hipLaunchKernelGGL((conv_chain_i8_kernel<C1, KB, C2, FL, CA, CB>), grid, dim3(256), dyn, st, a, ep1, ep2);
+}
+struct ChainVariant {
+  int C1, KB, C2, CA, CB;
+  ChainGo go[3];      // FL = 3, 1, -1
+};
+#define DLMCQ_CHAIN_ROW(C1, KB, C2) {C1, KB, C2, 0, 0, {chain_go<C1, KB, C2, 3, 0, 0>, chain_go<C1, KB, C2, 1, 0, 0>, chain_go<C1, KB, C2, -1, 0, 0>}}
+static const ChainVariant CHAIN_TABLE[] = {
+    // the recomputing form is built for the plan's launch alone: stage 1's second block, ReLU, plain quantisers (no run-time-flag form)
+    {64, 64, 0, 64, 64, {chain_go<64, 64, 0, 3, 64, 64>, chain_go<64, 64, 0, 1, 64, 64>, nullptr}},
+    DLMCQ_CHAIN_ROW(64, 64, 0), DLMCQ_CHAIN_ROW(64, 128, 0), DLMCQ_CHAIN_ROW(128, 128, 0), DLMCQ_CHAIN_ROW(128, 256, 0),
+    DLMCQ_CHAIN_ROW(256, 256, 0),
+    DLMCQ_CHAIN_ROW(64, 64, 64), DLMCQ_CHAIN_ROW(128, 128, 256),       // the convolution shortcut: ResNet-50's stages 1 and 2
+};
+#undef DLMCQ_CHAIN_ROW
+
+static bool op_given(const ChainOp& p) { return p.x && p.w && p.wsum && p.s_in && p.s_w; }
+
+// Validates the record - every refusal of every chain entry point, in one order - and launches.
+static int chain_launch(const ChainCall& c) {
+  const ChainOperand &o = c.own, &s = c.sampled, &u = c.unit;
+  const bool res = (c.uses & CHAIN_RESIDUAL) != 0, smp = (c.uses & CHAIN_SAMPLED) != 0, unt = (c.uses & CHAIN_UNIT) != 0;
+  const int64_t C = o.C, K = c.K, K2 = c.K2, C2 = (smp && !unt) ? s.C : 0, CA = unt ? u.C : 0, CB = unt ? s.C : 0;
+  if (o.N < 0 || o.H < 1 || o.W < 1 || C < 1 || K < 1 || K2 < 1 || K % 64 != 0) return DLMCQ_EINVAL;
+  if (unt && u.C < 1) return DLMCQ_EINVAL;
+  if (smp && (s.H < 1 || s.W < 1 || s.C < 1 || s.stride < 1)) return DLMCQ_EINVAL;
+  if (smp && ((s.H - 1) / s.stride + 1 != o.H || (s.W - 1) / s.stride + 1 != o.W)) return DLMCQ_EINVAL;   // every operand gives [N, H, W, K]
+  if (unt && c.relu_shortcut == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;
+  const int64_t M = o.N * o.H * o.W;
+  if (M == 0) return DLMCQ_OK;
+  const ConvEpi &ep1 = c.ep1, &ep2 = c.ep2;
+  if (!op_given(o.p) || (smp && !op_given(s.p)) || (unt && !op_given(u.p)) || (res && !c.residual) || !c.second.w || !c.second.wsum ||
+      !c.second.s_w || !ep2.codes || !ep1.q_scale || !ep2.q_scale)
+    return DLMCQ_EINVAL;
+  if (!aligned16(o.p.x) || !aligned16(o.p.w) || (smp && (!aligned16(s.p.x) || !aligned16(s.p.w))) ||
+      (unt && (!aligned16(u.p.x) || !aligned16(u.p.w))) || !aligned16(c.second.w) || (res && !aligned16(c.residual)) ||
+      (c.out && !aligned16(c.out)) || (ep1.codes && !aligned16(ep1.codes)) || !aligned16(ep2.codes))
+    return DLMCQ_EALIGN;
+  if (smp && (M >= (1ll << 31) || o.N * s.H * s.W * s.C >= (1ll << 40))) return DLMCQ_ERANGE;
+  if (ep1.relu == DLMCQ_ACT_RELU6 || ep2.relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
+  if (c.q_lo != 0 || c.q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
+  if (ep2.ctl & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED)) return DLMCQ_EINVAL;   // (no other kernel, no route query here)
+  const bool w3cm = (c.layout & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (c.layout & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
+  // (a call without a shortcut tensor or without an output has ONE fp32 tensor: its layout is the call's)
+  const bool icm = res ? (c.layout & DLMCQ_FP32_IN_CHUNK_MAJOR) != 0 : ocm;
+  const bool ocm2 = c.out ? ocm : icm;
+  if (icm != ocm2 && C == 128 && K2 == 128) return DLMCQ_EINVAL;   // (no registers for two offset sets there: conv_chain_i8_kernel)
+  if (c.q2_lo > c.q2_hi || c.q2_lo < -128 || c.q2_hi > 255 || c.q2_hi - c.q2_lo > 255 || c.q_form < DLMCQ_FORM_EMULATE ||
+      c.q_form > DLMCQ_FORM_SYMMETRIC || ep2.q_form < 0)
     return DLMCQ_EINVAL;
   if (M * K * 4 > (int64_t)CH_BIG) return DLMCQ_ERANGE;   // 32-bit buffer offsets
-  a.M = (int)M; a.KD = (int)K;
-  a.f_rowq = icm ? 64 : (int)K;
-  a.f_cstep = icm ? (int)M * 256 : 256;
-  a.o_rowq = ocm2 ? 64 : (int)K;
-  a.o_cstep = ocm2 ? (int)M * 256 : 256;
-#ifdef DLMCQ_LAB
-  a.trace = g_chain_trace;
-  a.lab = g_chain_lab;
-#endif
   // Tile height: 64 rows.  A chunk costs a workgroup the same time at 32 .. 64 rows (round 5, tools/chain_ab.py --rows: a 14^2 launch takes
   // 238 / 218 / 241 / 249 / 258 / 323 us at 64 / 56 / 49 / 48 / 40 / 32 rows, every other shape is fastest at 64), so shorter tiles only pay
   // where they keep a nearly empty last round from costing a whole tile's life: ResNet-50's 14^2 chains at batch 512 - 1 568 tiles on the
   // 512 slots of the two-workgroup instantiations, 3.06 rounds - run 3.5 rounds of 56-row tiles 8 % faster.  The rule: few rounds, the last
   // one less than an eighth full.
+  int rows_per_tile = c.rows_per_tile;
   if (rows_per_tile <= 0) {
     const int64_t t64 = (M + 63) / 64, slots = 256 * CHAIN_WGS((int)(C + C2 + CA + CB), (int)K2);
     const int64_t full = t64 / slots, left = t64 % slots;
     rows_per_tile = (full >= 2 && full <= 4 && left > 0 && left * 8 < slots) ? 56 : 64;
   }
-  a.rows_per_tile = rows_per_tile;
-  if (a.rows_per_tile > 64) return DLMCQ_EINVAL;
-  ep1.relu = relu != 0; ep1.q_scale = q_scale; ep1.q_zp = q_zero_point; ep1.q_lo = (float)q_lo; ep1.q_hi = (float)q_hi;
-  ep1.q_g = q_ste_g; ep1.q_form = q_form; ep1.codes = static_cast<uint8_t*>(codes);
-  ep2.relu = relu2 != 0; ep2.q_scale = q2_scale; ep2.q_zp = q2_zero_point; ep2.q_lo = (float)q2_lo; ep2.q_hi = (float)q2_hi;
-  ep2.q_g = q2_ste_g; ep2.codes = static_cast<uint8_t*>(codes2);
-  const int64_t tiles = (M + a.rows_per_tile - 1) / a.rows_per_tile;
+  if (rows_per_tile > 64) return DLMCQ_EINVAL;
+  const int64_t tiles = (M + rows_per_tile - 1) / rows_per_tile;
   if (tiles >= (1ll << 31)) return DLMCQ_ERANGE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((uint32_t)tiles), block(256);
+  // the plan's launches end their first layer with a ReLU: those get the instantiation that knows its flags at compile time
+  const int fl = (ep1.relu && epi_plain_q(ep1) && epi_plain_q(ep2)) ? (c.out ? 3 : 1) : -1;
+  ChainGo go = nullptr;
+  for (const ChainVariant& v : CHAIN_TABLE)
+    if (v.C1 == C && v.KB == K2 && v.C2 == C2 && v.CA == CA && v.CB == CB) go = v.go[fl == 3 ? 0 : fl == 1 ? 1 : 2];
+  if (!go) return DLMCQ_EINVAL;
+
+  ChainArgs a{};
+  a.o1 = o.p; a.shift1 = o.shift;
+  a.residual = res ? c.residual : nullptr;
+  if (smp) {
+    a.o2 = s.p; a.shift2 = s.shift;
+    a.P = (int)o.H; a.Q = (int)o.W; a.H2 = (int)s.H; a.W2 = (int)s.W; a.stride2 = s.stride;
+    a.qdiv = make_fastdiv((uint32_t)o.W);
+    a.pdiv = make_fastdiv((uint32_t)o.H);
+  }
+  if (unt) { a.oa = u.p; a.shifta = u.shift; a.relu_sc = c.relu_shortcut != 0; }
+  a.out = c.out; a.codes = ep1.codes;
+  a.w3 = c.second.w; a.s_w3 = c.second.s_w; a.wsum3 = c.second.wsum; a.bias3 = c.second.bias; a.codes2 = ep2.codes;
+  a.w3_row = w3cm ? 64 : (int)K;
+  a.w3_chunk = w3cm ? (int)K2 * 64 : 64;
+  a.M = (int)M; a.KD = (int)K; a.rows_per_tile = rows_per_tile;
+  a.f_rowq = icm ? 64 : (int)K;
+  a.f_cstep = icm ? (int)M * 256 : 256;
+  a.o_rowq = ocm2 ? 64 : (int)K;
+  a.o_cstep = ocm2 ? (int)M * 256 : 256;
   size_t dyn = 0;
 #ifdef DLMCQ_LAB
+  a.trace = g_chain_trace;
+  a.lab = g_chain_lab;
   dyn = (g_chain_lab & 128 ? 40960 : 0) + (g_chain_lab & 256 ? 81920 : 0);   // timing only: unused dynamic LDS = fewer workgroups per CU
 #endif
-  // the plan's launches end their first layer with a ReLU: those get the instantiation that knows its flags at compile time
-  const int fl = (relu && epi_plain_q(ep1) && epi_plain_q(ep2)) ? (a.out ? 3 : 1) : -1;
-#define DLMCQ_CHAIN_GO(...)                                                                                          \
-  do {                                                                                                               \
-    if (fl == 3) hipLaunchKernelGGL((conv_chain_i8_kernel<__VA_ARGS__, 3>), grid, block, dyn, st, a, ep1, ep2);       \
-    else if (fl == 1) hipLaunchKernelGGL((conv_chain_i8_kernel<__VA_ARGS__, 1>), grid, block, dyn, st, a, ep1, ep2);  \
-    else hipLaunchKernelGGL((conv_chain_i8_kernel<__VA_ARGS__, -1>), grid, block, dyn, st, a, ep1, ep2);              \
-  } while (0)
-  if (CA > 0) {
-    // the recomputing form is built for the plan's launch alone: stage 1's second block, ReLU, plain quantisers (no run-time-flag form)
-    if (!(C == 64 && K2 == 64 && CA == 64 && CB == 64) || fl < 0) return DLMCQ_EINVAL;
-    if (fl == 3) hipLaunchKernelGGL((conv_chain_i8_kernel<64, 64, 0, 3, 64, 64>), grid, block, dyn, st, a, ep1, ep2);
-    else hipLaunchKernelGGL((conv_chain_i8_kernel<64, 64, 0, 1, 64, 64>), grid, block, dyn, st, a, ep1, ep2);
-  } else if (C2 == 0) {
-    if (C == 64 && K2 == 64) DLMCQ_CHAIN_GO(64, 64, 0);
-    else if (C == 64 && K2 == 128) DLMCQ_CHAIN_GO(64, 128, 0);
-    else if (C == 128 && K2 == 128) DLMCQ_CHAIN_GO(128, 128, 0);
-    else if (C == 128 && K2 == 256) DLMCQ_CHAIN_GO(128, 256, 0);
-    else if (C == 256 && K2 == 256) DLMCQ_CHAIN_GO(256, 256, 0);
-    else return DLMCQ_EINVAL;
-  } else {
-    if (C == 64 && C2 == 64 && K2 == 64) DLMCQ_CHAIN_GO(64, 64, 64);
-    else if (C == 128 && C2 == 256 && K2 == 128) DLMCQ_CHAIN_GO(128, 128, 256);
-    else return DLMCQ_EINVAL;
-  }
-#undef DLMCQ_CHAIN_GO
+  go(dim3((uint32_t)tiles), dyn, c.st, a, ep1, ep2);
   return launch_status();
 }
+
+// what every chain entry point ends with: the block's width and outputs, the first quantiser, the second layer and its quantiser
+static void chain_tail(ChainCall& c, int64_t K, float* out, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point,
+                       int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, const int8_t* w2, const float* bias2, const int32_t* wsum2,
+                       const float* w_scale2, int64_t K2, int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point,
+                       int32_t q2_lo, int32_t q2_hi, int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
+  constexpr int32_t LAYOUT = DLMCQ_W2_CHUNK_MAJOR | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR;
+  c.K = K; c.K2 = K2; c.out = out;
+  c.second = ChainOp{nullptr, w2, w_scale2, wsum2, bias2, nullptr, nullptr};
+  c.ep1 = make_epi(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  c.ep2 = make_epi(nullptr, relu2, codes2, q2_scale, q2_zero_point, q2_lo, q2_hi, q2_form & ~LAYOUT, q2_ste_g);
+  c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form; c.q2_lo = q2_lo; c.q2_hi = q2_hi;
+  c.layout = (uint32_t)(q2_form & LAYOUT);
+  c.rows_per_tile = rows_per_tile;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+}
+// (the second layer is `2` in the ABI's argument names, `3` where the block has two operands of its own)
+#define DLMCQ_CHAIN_TAIL(n)                                                                                                       \
+  K, out, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, w##n, bias##n, wsum##n, w_scale##n, K##n, relu##n, codes##n, \
+      q##n##_scale, q##n##_zero_point, q##n##_lo, q##n##_hi, q##n##_form, q##n##_ste_g, rows_per_tile, stream
 
 extern "C" int dlmcq_conv2d_i8_nhwc_chain(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
                                           const float* in_scale, const float* in_zero_point, const float* w_scale, int64_t M,
@@ -781,20 +811,12 @@ extern "C" int dlmcq_conv2d_i8_nhwc_chain(const void* x, const int8_t* w, float*
                                           const int32_t* wsum2, const float* w_scale2, int64_t K2, int32_t relu2, void* codes2,
                                           const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi,
                                           int32_t q2_form, float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
-  if (M < 0 || C < 1 || K < 1 || K2 < 1 || K % 64 != 0) return DLMCQ_EINVAL;
-  if (M == 0) return DLMCQ_OK;
-  if (!x || !w || !wsum || !in_scale || !w_scale || !residual || !w2 || !wsum2 || !w_scale2 || !codes2 || !q_scale || !q2_scale)
-    return DLMCQ_EINVAL;
-  if (!aligned16(x) || !aligned16(w) || !aligned16(w2) || !aligned16(residual) || (out && !aligned16(out)) ||
-      (codes && !aligned16(codes)) || !aligned16(codes2))
-    return DLMCQ_EALIGN;
-  ChainArgs a{};
-  a.x = static_cast<const int8_t*>(x); a.w1 = w; a.s_w1 = w_scale; a.wsum1 = wsum; a.bias1 = bias;
-  a.s_in1 = in_scale; a.zp_in1 = in_zero_point; a.shift1 = x_is_unsigned ? 128 : 0;
-  a.residual = residual; a.out = out; a.codes = static_cast<uint8_t*>(codes);
-  a.w3 = w2; a.s_w3 = w_scale2; a.wsum3 = wsum2; a.bias3 = bias2; a.codes2 = static_cast<uint8_t*>(codes2);
-  return chain_launch(a, M, C, K, 0, K2, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, relu2, codes2, q2_scale,
-                      q2_zero_point, q2_lo, q2_hi, q2_form, q2_ste_g, rows_per_tile, stream);
+  ChainCall c{};
+  c.uses = CHAIN_RESIDUAL;
+  c.own = chain_operand(x, w, bias, wsum, in_scale, in_zero_point, w_scale, M, 1, 1, C, 1, x_is_unsigned);
+  c.residual = residual;
+  chain_tail(c, DLMCQ_CHAIN_TAIL(2));
+  return chain_launch(c);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_dual_chain(const void* x, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
@@ -808,30 +830,12 @@ extern "C" int dlmcq_conv2d_i8_nhwc_dual_chain(const void* x, const int8_t* w, f
                                                const int32_t* wsum3, const float* w_scale3, int64_t K3, int32_t relu3, void* codes3,
                                                const float* q3_scale, const float* q3_zero_point, int32_t q3_lo, int32_t q3_hi,
                                                int32_t q3_form, float q3_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
-  if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || K3 < 1 || K % 64 != 0 || H2 < 1 || W2 < 1 || C2 < 1 || stride2 < 1)
-    return DLMCQ_EINVAL;
-  if ((H2 - 1) / stride2 + 1 != H || (W2 - 1) / stride2 + 1 != W) return DLMCQ_EINVAL;   // both pairs give [N, H, W, K]
-  const int64_t M = N * H * W;
-  if (M == 0) return DLMCQ_OK;
-  if (!x || !w || !wsum || !in_scale || !w_scale || !x2 || !w2 || !wsum2 || !in_scale2 || !w_scale2 || !w3 || !wsum3 || !w_scale3 ||
-      !codes3 || !q_scale || !q3_scale)
-    return DLMCQ_EINVAL;
-  if (!aligned16(x) || !aligned16(w) || !aligned16(x2) || !aligned16(w2) || !aligned16(w3) || (out && !aligned16(out)) ||
-      (codes && !aligned16(codes)) || !aligned16(codes3))
-    return DLMCQ_EALIGN;
-  if (M >= (1ll << 31) || N * H2 * W2 * C2 >= (1ll << 40)) return DLMCQ_ERANGE;
-  ChainArgs a{};
-  a.x = static_cast<const int8_t*>(x); a.w1 = w; a.s_w1 = w_scale; a.wsum1 = wsum; a.bias1 = bias;
-  a.s_in1 = in_scale; a.zp_in1 = in_zero_point; a.shift1 = x_is_unsigned ? 128 : 0;
-  a.x2 = static_cast<const int8_t*>(x2); a.w2 = w2; a.s_w2 = w_scale2; a.wsum2 = wsum2; a.bias2 = bias2;
-  a.s_in2 = in_scale2; a.zp_in2 = in_zero_point2; a.shift2 = x2_is_unsigned ? 128 : 0;
-  a.P = (int)H; a.Q = (int)W; a.H2 = (int)H2; a.W2 = (int)W2; a.stride2 = stride2;
-  a.qdiv = make_fastdiv((uint32_t)W);
-  a.pdiv = make_fastdiv((uint32_t)H);
-  a.residual = nullptr; a.out = out; a.codes = static_cast<uint8_t*>(codes);
-  a.w3 = w3; a.s_w3 = w_scale3; a.wsum3 = wsum3; a.bias3 = bias3; a.codes2 = static_cast<uint8_t*>(codes3);
-  return chain_launch(a, M, C, K, C2, K3, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, relu3, codes3, q3_scale,
-                      q3_zero_point, q3_lo, q3_hi, q3_form, q3_ste_g, rows_per_tile, stream);
+  ChainCall c{};
+  c.uses = CHAIN_SAMPLED;
+  c.own = chain_operand(x, w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, 1, x_is_unsigned);
+  c.sampled = chain_operand(x2, w2, bias2, wsum2, in_scale2, in_zero_point2, w_scale2, N, H2, W2, C2, stride2, x2_is_unsigned);
+  chain_tail(c, DLMCQ_CHAIN_TAIL(3));
+  return chain_launch(c);
 }
 
 extern "C" int dlmcq_conv2d_i8_nhwc_recompute_chain(
@@ -844,31 +848,12 @@ extern "C" int dlmcq_conv2d_i8_nhwc_recompute_chain(
     int32_t q_form, float q_ste_g, const int8_t* w2, const float* bias2, const int32_t* wsum2, const float* w_scale2, int64_t K2,
     int32_t relu2, void* codes2, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo, int32_t q2_hi, int32_t q2_form,
     float q2_ste_g, int32_t rows_per_tile, dlmcq_stream_t stream) {
-  if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || K2 < 1 || K % 64 != 0 || Ca < 1 || Hb < 1 || Wb < 1 || Cb < 1 || strideb < 1)
-    return DLMCQ_EINVAL;
-  if ((Hb - 1) / strideb + 1 != H || (Wb - 1) / strideb + 1 != W) return DLMCQ_EINVAL;   // the recomputed block gives [N, H, W, K] too
-  if (relu_shortcut == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;
-  const int64_t M = N * H * W;
-  if (M == 0) return DLMCQ_OK;
-  if (!x || !w || !wsum || !in_scale || !w_scale || !xa || !wa || !wsuma || !in_scalea || !w_scalea || !xb || !wb || !wsumb ||
-      !in_scaleb || !w_scaleb || !w2 || !wsum2 || !w_scale2 || !codes2 || !q_scale || !q2_scale)
-    return DLMCQ_EINVAL;
-  if (!aligned16(x) || !aligned16(w) || !aligned16(xa) || !aligned16(wa) || !aligned16(xb) || !aligned16(wb) || !aligned16(w2) ||
-      (out && !aligned16(out)) || (codes && !aligned16(codes)) || !aligned16(codes2))
-    return DLMCQ_EALIGN;
-  if (M >= (1ll << 31) || N * Hb * Wb * Cb >= (1ll << 40)) return DLMCQ_ERANGE;
-  ChainArgs a{};
-  a.x = static_cast<const int8_t*>(x); a.w1 = w; a.s_w1 = w_scale; a.wsum1 = wsum; a.bias1 = bias;
-  a.s_in1 = in_scale; a.zp_in1 = in_zero_point; a.shift1 = x_is_unsigned ? 128 : 0;
-  a.xa = static_cast<const int8_t*>(xa); a.wa = wa; a.s_wa = w_scalea; a.wsuma = wsuma; a.biasa = biasa;
-  a.s_ina = in_scalea; a.zp_ina = in_zero_pointa; a.shifta = xa_is_unsigned ? 128 : 0; a.relu_sc = relu_shortcut != 0;
-  a.x2 = static_cast<const int8_t*>(xb); a.w2 = wb; a.s_w2 = w_scaleb; a.wsum2 = wsumb; a.bias2 = biasb;
-  a.s_in2 = in_scaleb; a.zp_in2 = in_zero_pointb; a.shift2 = xb_is_unsigned ? 128 : 0;
-  a.P = (int)H; a.Q = (int)W; a.H2 = (int)Hb; a.W2 = (int)Wb; a.stride2 = strideb;
-  a.qdiv = make_fastdiv((uint32_t)W);
-  a.pdiv = make_fastdiv((uint32_t)H);
-  a.residual = nullptr; a.out = out; a.codes = static_cast<uint8_t*>(codes);
-  a.w3 = w2; a.s_w3 = w_scale2; a.wsum3 = wsum2; a.bias3 = bias2; a.codes2 = static_cast<uint8_t*>(codes2);
-  return chain_launch(a, M, C, K, 0, K2, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, relu2, codes2, q2_scale,
-                      q2_zero_point, q2_lo, q2_hi, q2_form, q2_ste_g, rows_per_tile, stream, Ca, Cb);
+  ChainCall c{};
+  c.uses = CHAIN_UNIT | CHAIN_SAMPLED;
+  c.own = chain_operand(x, w, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, 1, x_is_unsigned);
+  c.unit = chain_operand(xa, wa, biasa, wsuma, in_scalea, in_zero_pointa, w_scalea, N, H, W, Ca, 1, xa_is_unsigned);
+  c.sampled = chain_operand(xb, wb, biasb, wsumb, in_scaleb, in_zero_pointb, w_scaleb, N, Hb, Wb, Cb, strideb, xb_is_unsigned);
+  c.relu_shortcut = relu_shortcut;
+  chain_tail(c, DLMCQ_CHAIN_TAIL(2));
+  return chain_launch(c);
 }

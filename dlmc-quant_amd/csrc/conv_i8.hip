@@ -956,21 +956,6 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   return conv_variant_launch(v, c, g, s2);
 }
 
-static ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point,
-                        int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g) {
-  ConvEpi ep{};
-  ep.residual = residual;
-  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  if (!epi_set_form(ep, q_form, q_lo, q_hi)) ep.q_form = -1;     // (conv_launch refuses it)
-  return ep;
-}
-
 // the ABI's leading twenty arguments -> the record (every conv2d_i8_nhwc entry point and the lab's share them by name)
 #define DLMCQ_CALL_ARGS x, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, H, W, C, K, R, S, stride, pad, dilation, x_is_unsigned, stream
 #define DLMCQ_EPI_ARGS relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g

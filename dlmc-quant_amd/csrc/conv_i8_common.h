@@ -1,5 +1,6 @@
 // Definitions shared by the int8 convolution translation units: the tiled kernel's device records and helpers, and the host-side call
-// record (ConvCall) that conv_launch (conv_i8.hip) and the kernel families it routes to pass around.  Not part of the ABI.
+// records: ConvCall, which conv_launch (conv_i8.hip) and the kernel families it routes to pass around, and ChainCall (conv_chain_i8.hip).
+// Not part of the ABI.
 #pragma once
 
 #include <type_traits>
@@ -172,6 +173,68 @@ inline void conv_geom_tiles(ConvGeom& g, int bn) {     // CV_BM pixels x bn chan
   g.nblk_m = (int)((g.M + CV_BM - 1) / CV_BM);
   g.nblk_n = (g.K + bn - 1) / bn;
 }
+
+// an entry point's eight quantiser arguments (+ its shortcut tensor) -> the epilogue record
+inline ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                        int32_t q_hi, int32_t q_form, float q_ste_g) {
+  ConvEpi ep{};
+  ep.residual = residual;
+  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
+  ep.codes = static_cast<uint8_t*>(codes);
+  ep.q_scale = q_scale;
+  ep.q_zp = q_zero_point;
+  ep.q_lo = (float)q_lo;
+  ep.q_hi = (float)q_hi;
+  ep.q_g = q_ste_g;
+  if (!epi_set_form(ep, q_form, q_lo, q_hi)) ep.q_form = -1;     // (conv_launch and chain_launch refuse it)
+  return ep;
+}
+
+// The seven pointers of one 1x1 operand of the chain kernels (conv_chain_i8.hip), as its device record ChainArgs holds them three times
+struct ChainOp {
+  const int8_t* x;
+  const int8_t* w;
+  const float* s_w;
+  const int32_t* wsum;
+  const float* bias;
+  const float* s_in;
+  const float* zp_in;
+};
+
+// ... and with its geometry, as an entry point received it: x codes [N][H][W][C], read at (p * stride, q * stride)
+struct ChainOperand {
+  ChainOp p;
+  int64_t N, H, W, C;
+  int32_t stride;
+  int shift;                 // 128 when the activation codes are unsigned bytes, else 0
+};
+
+inline ChainOperand chain_operand(const void* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
+                                  const float* in_zero_point, const float* w_scale, int64_t N, int64_t H, int64_t W, int64_t C,
+                                  int32_t stride, int32_t x_is_unsigned) {
+  return ChainOperand{{static_cast<const int8_t*>(x), w, w_scale, wsum, bias, in_scale, in_zero_point}, N, H, W, C, stride,
+                      x_is_unsigned ? 128 : 0};
+}
+
+// One chain launch as the host sees it: what an entry point of conv_chain_i8.hip received, once, by name.  `uses` says which of the
+// shortcut's three sources the entry point has - chain_launch requires exactly those and ignores the others.
+enum : unsigned { CHAIN_RESIDUAL = 1, CHAIN_SAMPLED = 2, CHAIN_UNIT = 4 };
+struct ChainCall {
+  unsigned uses;
+  ChainOperand own;          // the block end: [N][H][W][C] -> K channels (the plain form passes its M rows as N x 1 x 1)
+  ChainOperand sampled;      // CHAIN_SAMPLED: the 1x1 / stride-s convolution on the shortcut (its own block's, or the recomputed block's)
+  ChainOperand unit;         // CHAIN_UNIT: the recomputed block's unit-stride operand
+  const float* residual;     // CHAIN_RESIDUAL: fp32 [M][K]
+  int32_t relu_shortcut;     // CHAIN_UNIT: the recomputed block's own activation
+  float* out;                // fp32 [M][K] or null
+  int64_t K, K2;
+  ChainOp second;            // the next 1x1 reduction K -> K2: w, s_w, wsum, bias (its input is ep1's codes)
+  ConvEpi ep1, ep2;          // ep1.codes [M][K] or null, ep2.codes [M][K2]
+  int32_t q_lo, q_hi, q_form, q2_lo, q2_hi;   // the ranges and ep1's form as passed (make_epi folds them; chain_launch validates these)
+  uint32_t layout;           // DLMCQ_W2_CHUNK_MAJOR | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR of the second `q_form`
+  int32_t rows_per_tile;
+  hipStream_t st;
+};
 
 // compute units of the current device (cached: one device per process, dlmc/_native.py)
 inline int device_cus() {

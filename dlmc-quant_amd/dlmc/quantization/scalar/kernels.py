@@ -772,11 +772,26 @@ def conv2d_i8_dual(a, b, relu=False, emit=None, want_out=True, force_tiled=False
 
 CHAIN_SHAPES = {(64, 64), (64, 128), (128, 128), (128, 256), (256, 256)}   # (C, K2) pairs dlmcq_conv2d_i8_nhwc_chain is built for
 CHAIN_ONE_LAYOUT = {(128, 128)}    # ... and those whose two fp32 tensors must share one layout (row-major or ChunkMajor, not one of each)
+DUAL_CHAIN_SHAPES = {(64, 64, 64), (128, 256, 128)}   # (C, C2, K3) triples dlmcq_conv2d_i8_nhwc_dual_chain is built for
+RECOMPUTE_CHAIN_SHAPES = {(64, 64, 64, 64)}   # (C, Ca, Cb, K2) dlmcq_conv2d_i8_nhwc_recompute_chain is built for: ResNet-50's stage 1
+
+
+def _chain_fits(k, m):
+    """What every chain kernel asks of its block tensor [m, k]: whole 64-channel chunks, 32-bit byte offsets."""
+    return k % 64 == 0 and m * k * 4 <= 0x7fff0000
 
 
 def chain_supported(c, k, k2, m):
     """Whether dlmcq_conv2d_i8_nhwc_chain takes a block end [m, c] -> [m, k] followed by a reduction to k2."""
-    return (c, k2) in CHAIN_SHAPES and k % 64 == 0 and m * k * 4 <= 0x7fff0000
+    return (c, k2) in CHAIN_SHAPES and _chain_fits(k, m)
+
+
+def dual_chain_supported(c, c2, k, k3, m):
+    return (c, c2, k3) in DUAL_CHAIN_SHAPES and _chain_fits(k, m)
+
+
+def recompute_chain_supported(c, ca, cb, k, k2, m):
+    return (c, ca, cb, k2) in RECOMPUTE_CHAIN_SHAPES and _chain_fits(k, m)
 
 
 def chunk_major(wq):
@@ -902,6 +917,28 @@ def _second_weights(b):
     return wc, N.W2_CHUNK_MAJOR
 
 
+def _chain(entry, o, mid, b, relu, emit, want_out, want_codes, ocm, relu2, emit2, flags, rows_per_tile, nbytes, ops):
+    """What the three chain wrappers share (`entry`: "chain", "dual_chain" or "recompute_chain").  `o`: the block end's _Operand; `mid`: the entry point's arguments between the eight leading
+    pointers and `relu` (the problem, the shortcut's operands); `b`: the second layer (wq, wsum, bias, w_scale, optional wq_chunk);
+    `ocm`: the fp32 output as a ChunkMajor; `flags`: layout bits for the second form besides the two this function adds; `nbytes`, `ops`:
+    the launch's algorithmic bytes and operations, the wrapper's to state.  Returns (out or None, codes or None, codes2)."""
+    c, what = o.codes, "conv2d_i8_" + entry
+    (n, K_), (h, w_), K2 = o.shape[:2], o.geom[:2], b["wq"].shape[0]
+
+    def alloc(k, dtype):
+        return torch.empty((n, k, h, w_), dtype=dtype, device=c.device, memory_format=torch.channels_last)
+    out = (ChunkMajor.empty(n, K_, h, w_, c.device) if ocm else alloc(K_, torch.float32)) if want_out else None
+    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, c, False, what)
+    q2 = _quantiser(emit2, lambda dtype: alloc(K2, dtype), c, True, what)
+    b2, ws2 = _bias_c(b["bias"]), _flat(b["w_scale"], c, K2)
+    w2t, w2flag = _second_weights(b)
+    flags |= w2flag | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
+    PROFILE.launch("conv_chain", nbytes, lambda: N.check(getattr(N.lib, "dlmcq_conv2d_i8_nhwc_" + entry)(
+        *_head(o, out.buf if ocm else out), *mid, int(bool(relu)), *_q_args(q), N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2,
+        int(bool(relu2)), *_q_args(q2, flags), int(rows_per_tile), N.stream_ptr())), ops)
+    return out, q[0], q2[0]
+
+
 def conv2d_i8_chain(a, b, residual, relu=True, emit=None, want_out=True, want_codes=False, relu2=True, emit2=None,
                     rows_per_tile=0, out_chunk_major=False):
     """A block's last 1x1 convolution (+ residual, ReLU, the consumer's quantiser `emit`) and the next block's first 1x1
@@ -918,7 +955,6 @@ def conv2d_i8_chain(a, b, residual, relu=True, emit=None, want_out=True, want_co
     res_cm, residual = (residual, residual.buf) if icm else (None, residual)
     N.require_gpu(b["wq"], residual)
     o = _operand(a)
-    c = o.codes
     (n, K_), (h, w_, ch, R, S, _, _, _, uns) = o.shape[:2], o.geom
     K2, R2, S2, C2 = b["wq"].shape
     if (R, S, R2, S2) != (1, 1, 1, 1) or C2 != K_ or emit is None or emit2 is None:
@@ -928,28 +964,9 @@ def conv2d_i8_chain(a, b, residual, relu=True, emit=None, want_out=True, want_co
     if not icm:
         residual = _nhwc(residual)
     m = n * h * w_
-
-    def alloc(k, dtype):
-        return torch.empty((n, k, h, w_), dtype=dtype, device=c.device, memory_format=torch.channels_last)
-    out = (ChunkMajor.empty(n, K_, h, w_, c.device) if ocm else alloc(K_, torch.float32)) if want_out else None
-    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, c, False, "conv2d_i8_chain")
-    q2 = _quantiser(emit2, lambda dtype: alloc(K2, dtype), c, True, "conv2d_i8_chain")
-    b2, ws2 = _bias_c(b["bias"]), _flat(b["w_scale"], c, K2)
-    nbytes = c.numel() + a["wq"].numel() + b["wq"].numel() + m * K_ * (4 + 4 * want_out + want_codes) + m * K2
-    w2t, w2flag = _second_weights(b)
-    flags = w2flag | (N.FP32_IN_CHUNK_MAJOR if icm else 0) | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)
-    PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_chain(
-        *_head(o, out.buf if ocm else out), m, ch, K_, uns, N.ptr(residual), int(bool(relu)), *_q_args(q),
-        N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2, int(bool(relu2)), *_q_args(q2, flags), int(rows_per_tile), N.stream_ptr())),
-        2 * m * K_ * (ch + K2))
-    return out, q[0], q2[0]
-
-
-DUAL_CHAIN_SHAPES = {(64, 64, 64), (128, 256, 128)}   # (C, C2, K3) triples dlmcq_conv2d_i8_nhwc_dual_chain is built for
-
-
-def dual_chain_supported(c, c2, k, k3, m):
-    return (c, c2, k3) in DUAL_CHAIN_SHAPES and k % 64 == 0 and m * k * 4 <= 0x7fff0000
+    nbytes = o.codes.numel() + a["wq"].numel() + b["wq"].numel() + m * K_ * (4 + 4 * want_out + want_codes) + m * K2
+    return _chain("chain", o, (m, ch, K_, uns, N.ptr(residual)), b, relu, emit, want_out, want_codes, ocm, relu2, emit2,
+                  N.FP32_IN_CHUNK_MAJOR if icm else 0, rows_per_tile, nbytes, 2 * m * K_ * (ch + K2))
 
 
 def conv2d_i8_dual_chain(a, b, c3, relu=True, emit=None, want_out=True, want_codes=False, relu3=True, emit3=None, rows_per_tile=0,
@@ -965,31 +982,11 @@ def conv2d_i8_dual_chain(a, b, c3, relu=True, emit=None, want_out=True, want_cod
     if (tuple(a["wq"].shape[1:3]), tuple(b["wq"].shape[1:3]), tuple(c3["wq"].shape[1:3])) != ((1, 1),) * 3 or st != 1 or pd or pd2 \
             or b["wq"].shape[0] != K_ or c3["wq"].shape[3] != K_ or emit is None or emit3 is None:
         raise ValueError("conv2d_i8_dual_chain: three unpadded 1x1 convolutions, the third reading the codes of the sum of the first two")
-
-    def alloc(k, dtype):
-        return torch.empty((n, k, h, w_), dtype=dtype, device=oa.codes.device, memory_format=torch.channels_last)
-    fcm = bool(out_chunk_major) and want_out
-    out = (ChunkMajor.empty(n, K_, h, w_, oa.codes.device) if fcm else alloc(K_, torch.float32)) if want_out else None
-    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, oa.codes, False, "conv2d_i8_dual_chain")
-    q3 = _quantiser(emit3, lambda dtype: alloc(K3, dtype), oa.codes, True, "conv2d_i8_dual_chain")
-    b3, ws3 = _bias_c(c3["bias"]), _flat(c3["w_scale"], oa.codes, K3)
     m = n * h * w_
     nbytes = oa.codes.numel() + ob.codes.numel() // (st2 * st2) + a["wq"].numel() + b["wq"].numel() + c3["wq"].numel() + \
         m * K_ * (4 * want_out + want_codes) + m * K3
-    w3t, w3flag = _second_weights(c3)
-    PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_dual_chain(
-        *_head(oa, out.buf if fcm else out), n, h, w_, ch, K_, uns, *ob.ptrs, h2, w2, ch2, st2, uns2, int(bool(relu)), *_q_args(q),
-        N.ptr(w3t), N.ptr(b3), N.ptr(c3["wsum"]), N.ptr(ws3), K3, int(bool(relu3)),
-        *_q_args(q3, w3flag | (N.FP32_OUT_CHUNK_MAJOR if fcm else 0)), int(rows_per_tile), N.stream_ptr())),
-        2 * m * K_ * (ch + ch2 + K3))
-    return out, q[0], q3[0]
-
-
-RECOMPUTE_CHAIN_SHAPES = {(64, 64, 64, 64)}   # (C, Ca, Cb, K2) dlmcq_conv2d_i8_nhwc_recompute_chain is built for: ResNet-50's stage 1
-
-
-def recompute_chain_supported(c, ca, cb, k, k2, m):
-    return (c, ca, cb, k2) in RECOMPUTE_CHAIN_SHAPES and k % 64 == 0 and m * k * 4 <= 0x7fff0000
+    return _chain("dual_chain", oa, (n, h, w_, ch, K_, uns, *ob.ptrs, h2, w2, ch2, st2, uns2), c3, relu, emit, want_out,
+                  want_codes, bool(out_chunk_major) and want_out, relu3, emit3, 0, rows_per_tile, nbytes, 2 * m * K_ * (ch + ch2 + K3))
 
 
 def conv2d_i8_recompute_chain(a, b, pa, pb, relu_shortcut=True, relu=True, emit=None, want_out=True, want_codes=False, relu2=True,
@@ -1000,7 +997,6 @@ def conv2d_i8_recompute_chain(a, b, pa, pb, relu_shortcut=True, relu=True, emit=
     (dlmcq_conv2d_i8_nhwc_recompute_chain).  `a`, `b` and the rest as in conv2d_i8_chain.  Returns (out or None, codes or None, codes2)."""
     N.require_gpu(b["wq"])
     o, oa, ob = _operand(a), _operand(pa), _operand(pb)
-    c = o.codes
     (n, K_), (h, w_, ch, R, S, st, pd, _, uns) = o.shape[:2], o.geom
     _, _, cha, Ra, Sa, sta, pda, _, unsa = oa.geom
     hb, wb_, chb, Rb, Sb, stb, pdb, _, unsb = ob.geom
@@ -1010,25 +1006,13 @@ def conv2d_i8_recompute_chain(a, b, pa, pb, relu_shortcut=True, relu=True, emit=
     if oa.shape != o.shape or ob.shape != o.shape:
         raise ValueError(f"conv2d_i8_recompute_chain: the block gives {o.shape}, its recomputed shortcut {oa.shape} and {ob.shape}")
     m = n * h * w_
-
-    def alloc(k, dtype):
-        return torch.empty((n, k, h, w_), dtype=dtype, device=c.device, memory_format=torch.channels_last)
-    ocm = bool(out_chunk_major) and want_out
-    out = (ChunkMajor.empty(n, K_, h, w_, c.device) if ocm else alloc(K_, torch.float32)) if want_out else None
-    q = _quantiser(emit, lambda dtype: alloc(K_, dtype) if want_codes else None, c, False, "conv2d_i8_recompute_chain")
-    q2 = _quantiser(emit2, lambda dtype: alloc(K2, dtype), c, True, "conv2d_i8_recompute_chain")
-    b2, ws2 = _bias_c(b["bias"]), _flat(b["w_scale"], c, K2)
     # algorithmic bytes: the launch's real operands - three code tensors (the strided one where it is sampled) and four weight tensors in,
     # no fp32 in; ops: the MACs it executes, the two recomputed reductions included
-    nbytes = c.numel() + oa.codes.numel() + ob.codes.numel() // (stb * stb) + a["wq"].numel() + pa["wq"].numel() + pb["wq"].numel() + \
+    nbytes = o.codes.numel() + oa.codes.numel() + ob.codes.numel() // (stb * stb) + a["wq"].numel() + pa["wq"].numel() + pb["wq"].numel() + \
         b["wq"].numel() + m * K_ * (4 * want_out + want_codes) + m * K2
-    w2t, w2flag = _second_weights(b)
-    PROFILE.launch("conv_chain", nbytes, lambda: N.check(N.lib.dlmcq_conv2d_i8_nhwc_recompute_chain(
-        *_head(o, out.buf if ocm else out), n, h, w_, ch, K_, uns, *oa.ptrs, cha, unsa, *ob.ptrs, hb, wb_, chb, stb, unsb,
-        int(bool(relu_shortcut)), int(bool(relu)), *_q_args(q), N.ptr(w2t), N.ptr(b2), N.ptr(b["wsum"]), N.ptr(ws2), K2, int(bool(relu2)),
-        *_q_args(q2, w2flag | (N.FP32_OUT_CHUNK_MAJOR if ocm else 0)), int(rows_per_tile), N.stream_ptr())),
-        2 * m * K_ * (ch + cha + chb + K2))
-    return out, q[0], q2[0]
+    mid = (n, h, w_, ch, K_, uns, *oa.ptrs, cha, unsa, *ob.ptrs, hb, wb_, chb, stb, unsb, int(bool(relu_shortcut)))
+    return _chain("recompute_chain", o, mid, b, relu, emit, want_out, want_codes, bool(out_chunk_major) and want_out, relu2, emit2,
+                  0, rows_per_tile, nbytes, 2 * m * K_ * (ch + cha + chb + K2))
 
 
 def quantize_pad_nhwc4(x, scale, zero_point, lo, hi, form, pad, g=0.0, shift128=False, pad_code0=False):

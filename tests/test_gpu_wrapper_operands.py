@@ -167,6 +167,22 @@ def test_conv2d_i8_dual_chain():
           K.conv2d_i8_dual_chain(a, b, c3, emit=e, emit3=e3, **kw))
 
 
+def test_conv2d_i8_recompute_chain():
+    N, K = _mods()
+    g = _gen(19)
+    a, b = _operand(g, 2, 64, 5, 128), _layer(g, 64, 1, 128, 0.001)          # M = 50 rows: a partial 64-row tile, two chunks
+    pa, pb = _operand(g, 2, 64, 5, 128), _operand(g, 2, 64, 10, 128, stride=2)
+    assert K.recompute_chain_supported(64, 64, 64, 128, 64, 50)
+
+    def emits(scale):     # the recomputing form takes the plain quantiser alone: [0, 255], zero point 0 passed as none
+        return (K.EmitCodes(torch.full((1,), scale, device=DEV), None, 0, 255, N.FORM_ZEROPOINT),
+                K.EmitCodes(torch.tensor(scale, device=DEV, requires_grad=True), None, 0, 255, N.FORM_ZEROPOINT))
+    (e, le), (e2, le2) = emits(0.05), emits(0.11)
+    kw = dict(want_out=True, want_codes=True)
+    _same(K.conv2d_i8_recompute_chain(_loose(a), _loose(b), _loose(pa), _loose(pb), emit=le, emit2=le2, **kw),
+          K.conv2d_i8_recompute_chain(a, b, pa, pb, emit=e, emit2=e2, **kw))
+
+
 @pytest.mark.parametrize("pool", [False, True])
 def test_conv2d_i8_stem(pool):
     N, K = _mods()
