@@ -463,32 +463,104 @@ bool conv3x3_halo_applies(const ConvCall& c) {
   return true;
 }
 
+// WHICH instantiation a call runs, as a value: (column width, stride 2, halo pieces allocated per buffer, halo buffers, re-centred uint8 codes,
+// compile-time plain quantiser).  The launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_HALO_VARIANT) read this one record.
+struct HaloVariant {
+  int bn;
+  bool s2;
+  int hp, nhb;
+  bool xs, plain;
+};
+
+// halo pieces (16 frame positions each) a chunk's tile needs: stride 1 ceil((TM + 2 Wp + 2) / 16), a stride-2 phase tile ceil((TM + Wp + 2) / 16)
+static int halo_pieces(const ConvCall& c) { return (256 + (c.stride == 2 ? 1 : 2) * ((int)c.Q + 1) + 2 + 15) / 16; }
+
+// Pure: the record of a call conv3x3_halo_applies took; false = no instantiation holds its tile (applies' width limits keep that from happening).
+//  - stride 1: 24 pieces per buffer (images up to 62 pixels wide: 6 per wave), else 32 (8 per wave, fewer workgroups per CU); two buffers, or ONE for
+//    64-wide tiles over a single chunk (C = 64: nothing to prefetch);
+//  - stride 2: three phase-tile buffers of 18 pieces (Wp <= 30) or 20 (Wp <= 62).
+static bool halo_variant(const ConvCall& c, HaloVariant& v) {
+  const int hp = halo_pieces(c);
+  v.bn = c.K % 128 == 0 ? 128 : 64;
+  v.s2 = c.stride == 2;
+  if (hp > (v.s2 ? 20 : 32)) return false;
+  v.hp = v.s2 ? (hp > 18 ? 20 : 18) : (hp > 24 ? 32 : 24);
+  v.nhb = v.s2 ? 3 : (v.bn == 64 && c.C == 64 ? 1 : 2);
+  v.xs = c.shift != 0;
+  v.plain = epi_plain(c.ep);
+  return true;
+}
+
+// THE instantiations the library holds: (BN, S2, pieces per buffer, buffers, WPE = waves per SIMD the registers are budgeted for), each with
+// and without XS and PLAIN - one list for the launch (halo_variant_launch) and for tests (conv3x3_halo_table).
+//  - (128, 32, 2) and stride 2's (128, 20): 81 / 87 KB of LDS, one workgroup per CU; (64, *, 1): the LDS saved buys a third / fourth workgroup
+#define DLMCQ_HALO_TABLE(X)                                                                                                          \
+  DLMCQ_HALO_TABLE_(X, true, true) DLMCQ_HALO_TABLE_(X, true, false) DLMCQ_HALO_TABLE_(X, false, true) DLMCQ_HALO_TABLE_(X, false, false)
+#define DLMCQ_HALO_TABLE_(X, XS, PLAIN)                                                                                        \
+  X(128, false, 24, 2, 2, XS, PLAIN) X(128, false, 32, 2, 1, XS, PLAIN) X(64, false, 24, 1, 4, XS, PLAIN) X(64, false, 32, 1, 3, XS, PLAIN) \
+  X(64, false, 24, 2, 2, XS, PLAIN) X(64, false, 32, 2, 2, XS, PLAIN) X(128, true, 18, 3, 2, XS, PLAIN) X(128, true, 20, 3, 1, XS, PLAIN)   \
+  X(64, true, 18, 3, 2, XS, PLAIN) X(64, true, 20, 3, 2, XS, PLAIN)
+
+// include/dlmcq.h: tag | width << 16 | pieces << 8 | buffers << 4 | 4 S2 | 2 XS | 1 PLAIN
+constexpr int halo_variant_answer(int bn, bool s2, int hp, int nhb, bool xs, bool plain) {
+  return DLMCQ_ROUTE_HALO_VARIANT_TAG | (bn << 16) | (hp << 8) | (nhb << 4) | (s2 ? 4 : 0) | (xs ? 2 : 0) | (plain ? 1 : 0);
+}
+
+int conv3x3_halo_answer(const ConvCall& c) {
+  HaloVariant v;
+  if (!halo_variant(c, v)) return DLMCQ_EINVAL;      // (what the launch answers)
+  return halo_variant_answer(v.bn, v.s2, v.hp, v.nhb, v.xs, v.plain);
+}
+
+int conv3x3_halo_table(int32_t* answers, int cap) {
+  int n = 0;
+#define DLMCQ_HALO_LIST(BN, S2, HP, NHB, WPE, XS, PLAIN) if (n < cap && answers) answers[n] = halo_variant_answer(BN, S2, HP, NHB, XS, PLAIN); ++n;
+  DLMCQ_HALO_TABLE(DLMCQ_HALO_LIST)
+#undef DLMCQ_HALO_LIST
+  return n;
+}
+
+// value -> kernel: the one place the product's positional template list is spelt (four waves of 64 pixels x BN channels; stride 1 requests
+// HP / 4 pieces per wave, stride 2 five per wave of which HP are allocated)
+template <int BN, bool S2, int HP, int NHB, int WPE, bool XS, bool PLAIN>
+static int halo_go(const ConvCall& c, const HaloGeom& g, int64_t nwg) {
+  hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN, 256, 4, 1, S2 ? 5 : HP / 4, NHB, WPE, XS, 0, S2, HP, PLAIN>), dim3((uint32_t)nwg), dim3(256), 0,
+                     c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep, static_cast<unsigned long long*>(nullptr));
+  return launch_status();
+}
+
+static int halo_variant_launch(const HaloVariant& v, const ConvCall& c, const HaloGeom& g, int64_t nwg) {
+#define DLMCQ_HALO_GO(BN, S2, HP, NHB, WPE, XS, PLAIN) \
+  if (v.bn == BN && v.s2 == S2 && v.hp == HP && v.nhb == NHB && v.xs == XS && v.plain == PLAIN) return halo_go<BN, S2, HP, NHB, WPE, XS, PLAIN>(c, g, nwg);
+  DLMCQ_HALO_TABLE(DLMCQ_HALO_GO)
+#undef DLMCQ_HALO_GO
+  return DLMCQ_EINVAL;
+}
+
 int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
   constexpr int TM = 256;
-  const ConvEpi& ep = c.ep;
   const int64_t N = c.N, C = c.C, K = c.K;
-  const int shift = c.shift;
-  const int bn = K % 128 == 0 ? 128 : 64;
-  const bool s2 = c.stride == 2;
-  const bool plain = epi_plain(ep);
+  HaloVariant hv;
+  if (!halo_variant(c, hv)) return DLMCQ_EINVAL;
+  const int bn = hv.bn;
   HaloGeom g;
   g.N = (int)N; g.Hin = (int)c.H; g.Win = (int)c.W; g.H = (int)c.P; g.W = (int)c.Q; g.C = (int)C; g.K = (int)K;
   g.Wp = g.W + 1;
   g.FS = (g.H + 1) * (g.W + 1);
   g.MQ = (uint32_t)(N * g.FS);
   g.nblk_n = (int)(K / bn);
-  g.hp = (TM + (s2 ? 1 : 2) * g.Wp + 2 + 15) / 16;
+  g.hp = halo_pieces(c);
   g.fsdiv = make_fastdiv((uint32_t)g.FS);
   g.wpdiv = make_fastdiv((uint32_t)g.Wp);
   const int64_t nblk_m = ((int64_t)g.MQ + TM - 1) / TM;
   const int64_t nwg = nblk_m * g.nblk_n;
   if (nwg >= (1ll << 31)) return DLMCQ_ERANGE;
-  unsigned long long* const trace = static_cast<unsigned long long*>(lab_trace);
-#define DLMCQ_HALO_ARGS(NW) dim3((uint32_t)nwg), dim3(NW * 64), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, shift, ep, trace
 #ifdef DLMCQ_LAB
+  unsigned long long* const trace = static_cast<unsigned long long*>(lab_trace);
+#define DLMCQ_HALO_ARGS(NW) dim3((uint32_t)nwg), dim3(NW * 64), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep, trace
   if (lab) {     // lab: variant = lab % 100 on the product tiling, + 100 for the 8-wave tiling (100 = its product code); stride 1 only
     const int v = lab % 100;
-    if (s2 || g.hp > 24 || (v == 1 && !trace)) return DLMCQ_EINVAL;
+    if (hv.s2 || g.hp > 24 || (v == 1 && !trace)) return DLMCQ_EINVAL;
     if (lab >= 100) {
       if (bn != 128) return DLMCQ_EINVAL;
       switch (v) {
@@ -517,58 +589,11 @@ int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
     }
     return launch_status();
   }
+#undef DLMCQ_HALO_ARGS
 #else
   if (lab) return DLMCQ_EINVAL;
 #endif
-#define DLMCQ_HALO_GO(NW, ...)                                                                            \
-  do {                                                                                                   \
-    if (shift) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<__VA_ARGS__>), DLMCQ_HALO_ARGS(NW));           \
-    else hipLaunchKernelGGL((conv3x3_halo_i8_kernel<__VA_ARGS__>), DLMCQ_HALO_ARGS(NW));                 \
-  } while (0)
-  if (s2) {
-    // stride 2: three phase-tile buffers of 18 pieces (Wp <= 30: two workgroups per CU at 128 channels) or 20 (Wp <= 62)
-    if (g.hp > 20) return DLMCQ_EINVAL;
-    const bool big = g.hp > 18;
-#define DLMCQ_HALO_S2(BN_, HPA_, WPE_)                                                                                                         \
-  do {                                                                                                                                        \
-    if (shift && plain) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, 5, 3, WPE_, true, 0, true, HPA_, true>), DLMCQ_HALO_ARGS(4));  \
-    else if (shift) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, 5, 3, WPE_, true, 0, true, HPA_>), DLMCQ_HALO_ARGS(4));            \
-    else if (plain) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, 5, 3, WPE_, false, 0, true, HPA_, true>), DLMCQ_HALO_ARGS(4));     \
-    else hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, 5, 3, WPE_, false, 0, true, HPA_>), DLMCQ_HALO_ARGS(4));                      \
-  } while (0)
-    if (bn == 128) {
-      if (!big) DLMCQ_HALO_S2(128, 18, 2);
-      else DLMCQ_HALO_S2(128, 20, 1);      // (87 KB of LDS: one workgroup per CU)
-    } else {
-      if (!big) DLMCQ_HALO_S2(64, 18, 2);
-      else DLMCQ_HALO_S2(64, 20, 2);
-    }
-#undef DLMCQ_HALO_S2
-    return launch_status();
-  }
-  if (g.hp > 32) return DLMCQ_EINVAL;
-  const bool wide = g.hp > 24;        // images wider than 57 pixels: 8 halo pieces per wave, one workgroup per CU
-#undef DLMCQ_HALO_GO
-#define DLMCQ_HALO_GO(BN_, HPW_, NHB_, WPE_)                                                                                                              \
-  do {                                                                                                                                                   \
-    if (shift && plain) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, HPW_, NHB_, WPE_, true, 0, false, 4 * HPW_, true>), DLMCQ_HALO_ARGS(4));  \
-    else if (shift) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, HPW_, NHB_, WPE_, true>), DLMCQ_HALO_ARGS(4));                                \
-    else if (plain) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, HPW_, NHB_, WPE_, false, 0, false, 4 * HPW_, true>), DLMCQ_HALO_ARGS(4));     \
-    else hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN_, TM, 4, 1, HPW_, NHB_, WPE_, false>), DLMCQ_HALO_ARGS(4));                                          \
-  } while (0)
-  if (bn == 128) {
-    if (!wide) DLMCQ_HALO_GO(128, 6, 2, 2);
-    else DLMCQ_HALO_GO(128, 8, 2, 1);
-  } else if (C == 64) {
-    if (!wide) DLMCQ_HALO_GO(64, 6, 1, 4);
-    else DLMCQ_HALO_GO(64, 8, 1, 3);
-  } else {
-    if (!wide) DLMCQ_HALO_GO(64, 6, 2, 2);
-    else DLMCQ_HALO_GO(64, 8, 2, 2);
-  }
-#undef DLMCQ_HALO_GO
-#undef DLMCQ_HALO_ARGS
-  return launch_status();
+  return halo_variant_launch(hv, c, g, nwg);
 }
 
 }  // namespace dlmcq

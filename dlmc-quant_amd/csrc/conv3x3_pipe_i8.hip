@@ -466,12 +466,40 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_i8_kernel(
 #endif
 }
 
-template <int NCH>
+// WHICH instantiation a call runs, as a value: (chunks of 64 input channels per tile, re-centred uint8 codes).  THE instantiations the library
+// holds - one list for the launch and for tests (conv3x3_pipe_table); the launch and the route query (DLMCQ_ROUTE_ONLY |
+// DLMCQ_ROUTE_HALO_VARIANT) read one record.
+struct PipeVariant {
+  int nch;
+  bool xs;
+};
+#define DLMCQ_PIPE_TABLE(X) X(2, true) X(2, false) X(4, true) X(4, false) X(8, true) X(8, false)
+
+static PipeVariant pipe_variant(const ConvCall& c) { return PipeVariant{(int)(c.C >> 6), c.shift != 0}; }
+
+// include/dlmcq.h: tag | chunks << 8 | 2 XS
+constexpr int pipe_variant_answer(int nch, bool xs) { return DLMCQ_ROUTE_PIPE_VARIANT_TAG | (nch << 8) | (xs ? 2 : 0); }
+
+int conv3x3_pipe_answer(const ConvCall& c) {
+  const PipeVariant v = pipe_variant(c);
+#define DLMCQ_PIPE_HAS(NCH, XS) if (v.nch == NCH && v.xs == XS) return pipe_variant_answer(NCH, XS);
+  DLMCQ_PIPE_TABLE(DLMCQ_PIPE_HAS)
+#undef DLMCQ_PIPE_HAS
+  return DLMCQ_EINVAL;      // (what the launch answers)
+}
+
+int conv3x3_pipe_table(int32_t* answers, int cap) {
+  int n = 0;
+#define DLMCQ_PIPE_LIST(NCH, XS) if (n < cap && answers) answers[n] = pipe_variant_answer(NCH, XS); ++n;
+  DLMCQ_PIPE_TABLE(DLMCQ_PIPE_LIST)
+#undef DLMCQ_PIPE_LIST
+  return n;
+}
+
+template <int NCH, bool XS>
 static int conv3x3_pipe_go(const ConvCall& c, const PipeGeom& g, uint32_t grid) {
-  if (c.shift) hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, true>), dim3(grid), dim3(512), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in,
-                                  c.zp_in, c.s_w, g, c.shift, c.ep);
-  else hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, false>), dim3(grid), dim3(512), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in,
-                          c.s_w, g, c.shift, c.ep);
+  hipLaunchKernelGGL((conv3x3_pipe_i8_kernel<NCH, XS>), dim3(grid), dim3(512), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g,
+                     c.shift, c.ep);
   return launch_status();
 }
 
@@ -514,9 +542,10 @@ int conv3x3_pipe_launch(const ConvCall& c, int cus) {
   uint32_t grid = (uint32_t)cus & ~7u;             // one workgroup per CU, a multiple of 8 (a workgroup's tiles stay on its XCD)
   if (grid > (g.ntiles & ~7u)) grid = g.ntiles & ~7u;      // (every workgroup owns at least one tile)
   if (grid < 8 || g.hp > 24) return DLMCQ_EINVAL;
-  if (C == 128) return conv3x3_pipe_go<2>(c, g, grid);
-  if (C == 256) return conv3x3_pipe_go<4>(c, g, grid);
-  if (C == 512) return conv3x3_pipe_go<8>(c, g, grid);
+  const PipeVariant v = pipe_variant(c);
+#define DLMCQ_PIPE_GO(NCH, XS) if (v.nch == NCH && v.xs == XS) return conv3x3_pipe_go<NCH, XS>(c, g, grid);
+  DLMCQ_PIPE_TABLE(DLMCQ_PIPE_GO)
+#undef DLMCQ_PIPE_GO
   return DLMCQ_EINVAL;
 }
 

@@ -26,7 +26,7 @@ struct ConvEpi {
   int q_form;
   int relu;                // DLMCQ_ACT_*: 0 none, 1 ReLU, 2 ReLU6 (the upper bound: a compile-time flag of the kernels that implement it)
   uint32_t q_xor;          // 0x80808080 when the codes are stored as int8 `code - 128` (DLMCQ_EMIT_SHIFT128), else 0
-  uint32_t ctl;            // host side only: DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED | DLMCQ_ROUTE_VARIANT as passed in `q_form`
+  uint32_t ctl;            // host side only: DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED | DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT as passed in `q_form`
   // observer partials of the fp32 OUTPUT (dlmcq_conv2d_i8_nhwc_fused_observed; the tiled kernel only): every workgroup writes the
   // (max, min, max of |x|'s bits) of the values it stored at entry blockIdx.x of three planes of `mm_np` floats each - observer.hip's
   // partial layout, reduced by dlmcq_minmax_finalize_f32.  The calibrating first batch: the consumer's min/max pass (one read of the
@@ -83,7 +83,7 @@ __device__ __forceinline__ f32x4 xoff_sub4(const f32x4& v, float o, const f32x4&
 static inline bool epi_set_form(ConvEpi& ep, int32_t q_form, int32_t q_lo, int32_t q_hi) {
   const bool shifted = (q_form & DLMCQ_EMIT_SHIFT128) != 0;
   constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR |
-                          DLMCQ_ROUTE_VARIANT;
+                          DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT;
   ep.ctl = (uint32_t)q_form & CTL;
   ep.q_form = q_form & ~(DLMCQ_EMIT_SHIFT128 | CTL);
   ep.q_xor = shifted ? 0x80808080u : 0u;

@@ -831,6 +831,12 @@ extern "C" int dlmcq_x_conv_variant_table(int32_t* bn, uint32_t* flags, int cap)
   return n;
 }
 
+// The 3x3 kernels' tables likewise (absent from include/dlmcq.h): `which` 0 = conv3x3_halo_i8_kernel's, 1 = conv3x3_pipe_i8_kernel's; fills up to
+// `cap` DLMCQ_ROUTE_HALO_VARIANT answers in the table's order and returns how many there are (-1: no such table)
+extern "C" int dlmcq_x_conv3x3_variant_table(int which, int32_t* answers, int cap) {
+  return which == 0 ? conv3x3_halo_table(answers, cap) : which == 1 ? conv3x3_pipe_table(answers, cap) : -1;
+}
+
 // value -> kernel: the one place the kernel's positional template list is spelt (LAB: the lab library's what-bounds-the-step variants)
 template <int BN, unsigned F, int LAB = 0>
 static int conv_tiled_go(const ConvCall& c, const ConvGeom& g, const ConvSeg2& s2) {
@@ -862,7 +868,7 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   const ConvSeg2* const seg2 = c.seg2;
   const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, R = c.R, S = c.S, P = c.P, Q = c.Q, M = c.M;
   if (mm_count) *mm_count = 0;
-  if ((ep.ctl & DLMCQ_ROUTE_VARIANT) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (a question about the route, never a launch)
+  if ((ep.ctl & (DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT)) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (questions about the route, never a launch)
   if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || c.stride < 1 || c.pad < 0 || c.dil < 1) return DLMCQ_EINVAL;
   if (C % CV_BK != 0) return DLMCQ_EINVAL;  // the K step is 64 input channels
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;
@@ -923,9 +929,11 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   if (special && conv_pwr_applies(c)) return route_only ? DLMCQ_ROUTE_PWR : conv_pwr_launch(c);
   if (special && conv3x3_halo_applies(c)) {
     // ... persistent and pipelined across tiles on request (DLMCQ_PIPELINED: csrc/conv3x3_pipe_i8.hip - bit-identical, measured slower)
+    // (DLMCQ_ROUTE_HALO_VARIANT: the route query names the instantiation - the record the launch itself reads - instead of the family)
+    const bool which = (ep.ctl & DLMCQ_ROUTE_HALO_VARIANT) != 0;
     if ((ep.ctl & DLMCQ_PIPELINED) && conv3x3_pipe_applies(c, device_cus()))
-      return route_only ? DLMCQ_ROUTE_HALO3X3_PIPE : conv3x3_pipe_launch(c, device_cus());
-    return route_only ? DLMCQ_ROUTE_HALO3X3 : conv3x3_halo_launch(c);
+      return route_only ? (which ? conv3x3_pipe_answer(c) : DLMCQ_ROUTE_HALO3X3_PIPE) : conv3x3_pipe_launch(c, device_cus());
+    return route_only ? (which ? conv3x3_halo_answer(c) : DLMCQ_ROUTE_HALO3X3) : conv3x3_halo_launch(c);
   }
   // 256-wide tiles exist for the swapped codes-only layers only; fp32 outputs, shortcuts, asymmetric weights and the dual form narrow
   // to the 128-wide kernels here, in place (a forced plan is refused instead: the lab asked for exactly that width)

@@ -253,11 +253,15 @@ inline int device_cus() {
 // conv3x3_i8.hip: the halo-tile kernel for 3x3 / stride 1 or 2 / pad 1 layers that emit only their consumer's codes
 bool conv3x3_halo_applies(const ConvCall& c);
 int conv3x3_halo_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
+int conv3x3_halo_answer(const ConvCall& c);                    // DLMCQ_ROUTE_HALO_VARIANT: which instantiation the launch picks (include/dlmcq.h)
+int conv3x3_halo_table(int32_t* answers, int cap);             // every instantiation the launcher holds, as such answers; returns how many
 
 // conv3x3_pipe_i8.hip: the halo-tile kernel persistent and software-pipelined across tiles (stride 1, 128 / 256 / 512 input channels,
 // plain quantiser); asked only about calls the halo kernel takes
 bool conv3x3_pipe_applies(const ConvCall& c, int cus);
 int conv3x3_pipe_launch(const ConvCall& c, int cus);
+int conv3x3_pipe_answer(const ConvCall& c);
+int conv3x3_pipe_table(int32_t* answers, int cap);
 
 // conv_pw_i8.hip: pointwise codes-to-codes layers with the weights resident in LDS (MobileOne's 1x1 layers)
 bool conv_pw_applies(const ConvCall& c);

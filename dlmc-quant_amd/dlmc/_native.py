@@ -35,7 +35,10 @@ PAD_CODE0 = 0x8000       # DLMCQ_PAD_CODE0: quantize_pad_nhwc4's border holds co
 PIPELINED = 0x1000       # DLMCQ_PIPELINED (opt-in): the persistent, software-pipelined halo-tile 3x3 kernel where it applies
 ROUTE_VARIANT = 0x10000  # DLMCQ_ROUTE_VARIANT: with ROUTE_ONLY, a ROUTE_TILED answer names the tiled kernel's instantiation instead (decode_variant)
 ROUTE_VARIANT_TAG = 1 << 24
-# the `flags` of such an answer: conv_i8_mfma_kernel's boolean template parameters (include/dlmcq.h)
+ROUTE_HALO_VARIANT = 0x20000  # DLMCQ_ROUTE_HALO_VARIANT: with ROUTE_ONLY, a ROUTE_HALO3X3 / ROUTE_HALO3X3_PIPE answer names the instantiation instead (decode_halo_variant)
+ROUTE_HALO_VARIANT_TAG, ROUTE_PIPE_VARIANT_TAG = 1 << 25, 1 << 26
+HV_PLAIN, HV_XS, HV_S2 = 1, 2, 4   # the flags of such an answer (include/dlmcq.h)
+# the `flags` of a ROUTE_VARIANT answer: conv_i8_mfma_kernel's boolean template parameters (include/dlmcq.h)
 CV_DUAL, CV_ADIR, CV_ASYM, CV_SWAP, CV_R6, CV_XOFF, CV_NARROW, CV_PADRES = 1, 2, 4, 8, 16, 32, 64, 128
 ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE, ROUTE_GAP = 1, 2, 3, 4, 5, 6, 7, 8
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
@@ -220,6 +223,29 @@ def conv_variant_table():
     bn, flags = (ctypes.c_int32 * n)(), (ctypes.c_uint32 * n)()
     assert fn(bn, flags, n) == n
     return [(int(b), int(f)) for b, f in zip(bn, flags)]
+
+
+def decode_halo_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_HALO_VARIANT call -> ("halo", column width, stride 2, halo pieces per buffer, halo buffers, XS, PLAIN) of the
+    conv3x3_halo_i8_kernel instantiation, ("pipe", chunks, XS) of the conv3x3_pipe_i8_kernel one, or None when the answer is neither (another
+    kernel's ROUTE_*, a tiled variant, DLMCQ_OK, a refusal)."""
+    if rc >> 27 or rc < ROUTE_HALO_VARIANT_TAG:
+        return None
+    if rc & ROUTE_PIPE_VARIANT_TAG:
+        return None if rc & ROUTE_HALO_VARIANT_TAG else ("pipe", (rc >> 8) & 0xff, bool(rc & HV_XS))
+    return ("halo", (rc >> 16) & 0x1ff, bool(rc & HV_S2), (rc >> 8) & 0xff, (rc >> 4) & 0xf, bool(rc & HV_XS), bool(rc & HV_PLAIN))
+
+
+def conv3x3_variant_tables():
+    """(halo records, pipe records), decoded: the instantiations of the two 3x3 kernels the library holds, as its own launchers list them."""
+    fn = experimental("dlmcq_x_conv3x3_variant_table", [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    out = []
+    for which in (0, 1):
+        n = fn(which, None, 0)
+        answers = (ctypes.c_int32 * n)()
+        assert fn(which, answers, n) == n
+        out.append([decode_halo_variant(int(a)) for a in answers])
+    return tuple(out)
 
 
 def stream_ptr():

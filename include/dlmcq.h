@@ -122,6 +122,20 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * instantiations a case really runs.) */
 #define DLMCQ_ROUTE_VARIANT 0x10000
 #define DLMCQ_ROUTE_VARIANT_TAG (1 << 24)
+/* DLMCQ_ROUTE_HALO_VARIANT (as DLMCQ_ROUTE_VARIANT: OR-able only TOGETHER with DLMCQ_ROUTE_ONLY, alone it is DLMCQ_EINVAL for every entry point):
+ * where the route query would answer DLMCQ_ROUTE_HALO3X3 or DLMCQ_ROUTE_HALO3X3_PIPE it answers WHICH instantiation of the 3x3 kernel the call
+ * launches instead - the record the launcher itself picks the kernel from:
+ *   conv3x3_halo_i8_kernel:  DLMCQ_ROUTE_HALO_VARIANT_TAG | (column width << 16) | (halo pieces per buffer << 8) | (halo buffers << 4) | flags
+ *     column width 64 or 128 channels; halo pieces of 16 frame positions allocated per buffer: 24 or 32 (stride 1), 18 or 20 (stride 2);
+ *     halo buffers 1, 2, or 3 (stride 2);  flags: 4 S2 (stride 2), 2 XS (uint8 codes, re-centred on read), 1 PLAIN (the compile-time plain
+ *     unsigned-byte quantiser);
+ *   conv3x3_pipe_i8_kernel:  DLMCQ_ROUTE_PIPE_VARIANT_TAG | (chunks of 64 input channels << 8) | flags      chunks 2, 4 or 8; flags: 2 XS.
+ * Both above every DLMCQ_ROUTE_* and every DLMCQ_ROUTE_VARIANT answer; what DLMCQ_ROUTE_VARIANT means is untouched, the two bits may be
+ * passed together, and every other answer - another kernel's route, a tiled variant, DLMCQ_OK for an empty problem, a refusal - is what it
+ * is without the bit. */
+#define DLMCQ_ROUTE_HALO_VARIANT 0x20000
+#define DLMCQ_ROUTE_HALO_VARIANT_TAG (1 << 25)
+#define DLMCQ_ROUTE_PIPE_VARIANT_TAG (1 << 26)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */

@@ -25,6 +25,7 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "conv_dispatch_routes.json")
 
 EINVAL, ERANGE, ESCRATCH, EALIGN = -1, -2, -3, -4
 FORM_ZEROPOINT, SHIFT128, FORCE_TILED, ROUTE_ONLY, PIPELINED, IN_CM, OUT_CM = 2, 0x100, 0x400, 0x800, 0x1000, 0x2000, 0x4000
+HALO_VARIANT = 0x20000      # DLMCQ_ROUTE_HALO_VARIANT
 ROUTES = {"tiled": 1, "halo3x3": 2, "pw": 3, "pwr": 4, "halo3x3_pipe": 7}
 P = 4096            # a placeholder pointer: non-null, 16-byte aligned, never dereferenced
 P4, P2 = P + 4, P + 2   # 4-byte aligned only; 2-byte aligned only
@@ -117,6 +118,21 @@ def cases():
     add("pipe_512-1024/n12_56", "fused", ctl=PIPELINED, N=12, H=56, W=56, C=512, K=1024, R=3, S=3, pad=1)       # K > the pipelined kernel's 512
     add("pipe_256-512/n2_56", "fused", ctl=PIPELINED, N=2, H=56, W=56, C=256, K=512, R=3, S=3, pad=1)           # too few tiles
     add("pipe_64-64/n12_56", "fused", ctl=PIPELINED, N=12, H=56, W=56, C=64, K=64, R=3, S=3, pad=1)
+    # DLMCQ_ROUTE_HALO_VARIANT: which instantiation of the 3x3 kernels (the only entries not recorded from the parent library, which did not
+    # know the bit: they were added by the commit that introduced it, from its own library; every other entry is unchanged)
+    for stag, C, K, stride in (("r50_64-64_3x3", 64, 64, 1), ("r50_128-128_3x3", 128, 128, 1), ("r50_256-128_3x3s2", 256, 128, 2), ("64-192_3x3s2", 128, 192, 2)):
+        for ztag, N, H, W in (("n2_48", 2, 48, 48), ("n1_14", 1, 14, 14), ("n1_4x100", 1, 4, 100)):
+            geo = dict(N=N, H=H, W=W, C=C, K=K, R=3, S=3, stride=stride, pad=1)
+            for mtag, m in (("codes", dict()), ("codes_zp", dict(q_zp=P, q_lo=-128, q_hi=127)), ("codes_int8", dict(uns=0)), ("codes_r6", dict(relu=2)),
+                            ("out_codes", dict(out=P))):
+                add(f"{stag}/{ztag}/{mtag}+which", "fused", ctl=HALO_VARIANT, **geo, **m)
+            add(f"{stag}/{ztag}/codes+which+tiled", "fused", ctl=HALO_VARIANT | FORCE_TILED, **geo)
+    for C in (128, 256, 512):
+        add(f"pipe_{C}-512/n12_56+which", "fused", ctl=PIPELINED | HALO_VARIANT, N=12, H=56, W=56, C=C, K=512, R=3, S=3, pad=1)
+        add(f"pipe_{C}-512/n12_56/int8+which", "fused", ctl=PIPELINED | HALO_VARIANT, uns=0, N=12, H=56, W=56, C=C, K=512, R=3, S=3, pad=1)
+    add("pipe_256-512/n2_56+which", "fused", ctl=PIPELINED | HALO_VARIANT, N=2, H=56, W=56, C=256, K=512, R=3, S=3, pad=1)      # too few tiles: the halo kernel's record
+    add("r50_64-256/n2_48/codes+which", "fused", ctl=HALO_VARIANT, N=2, H=48, W=48, C=64, K=256)                              # (pointwise: unchanged)
+    add("r50_64-64_3x3/n2_48/codes+which", "asym", ctl=HALO_VARIANT, N=2, H=48, W=48, C=64, K=64, R=3, S=3, pad=1)
     # chunk-major fp32 tensors: only a call that lands on the block-end kernel may carry the bits
     blk = dict(N=2, H=48, W=48, C=512, K=2048, res=P, out=P)
     for tag, ctl in (("in", IN_CM), ("out", OUT_CM), ("both", IN_CM | OUT_CM)):

@@ -12,13 +12,15 @@ from oracle import fakequant_oracle as O
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-# N, C, H, W, K  (frame pitch W + 1; halo pieces per chunk = ceil((256 + 2 (W + 1) + 2) / 16): <= 24 -> HPW 3, else HPW 4)
+# N, C, H, W, K[, stride]  (frame pitch Wp = W + 1 of the OUTPUT; halo pieces a chunk's tile needs: stride 1 ceil((256 + 2 Wp + 2) / 16) -
+# up to 24 (W <= 62) the 24-piece instantiations, six per wave, else the 32-piece ones, eight per wave; a stride-2 phase tile
+# ceil((256 + Wp + 2) / 16): 18 pieces up to Wp = 30, else 20.  tests/halo_variant_cases.py has both sides of each split per instantiation)
 SHAPES = [
     (3, 64, 7, 7, 128),        # FS = 64: four images per tile, 23 % junk rows
     (2, 128, 14, 14, 128),     # two chunks: the halo double buffer
     (1, 64, 28, 28, 256),      # two column blocks
-    (2, 64, 56, 56, 128),      # Wp = 57: 24 halo pieces (the HPW = 3 limit)
-    (1, 64, 5, 70, 128),       # Wp = 71: HPW = 4 instantiation
+    (2, 64, 56, 56, 128),      # Wp = 57: 24 halo pieces
+    (1, 64, 5, 70, 128),       # Wp = 71: a 32-piece instantiation
     (1, 64, 3, 118, 128),      # Wp = 119: the widest image the kernel takes (32 pieces)
     (5, 256, 14, 14, 256),     # ResNet-50 stage 3 / RepVGG stage 3 shape, tiles crossing images
     (3, 512, 7, 7, 512),       # ResNet-50 stage 4 shape: 72 K steps

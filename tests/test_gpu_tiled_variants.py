@@ -9,7 +9,7 @@ DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_VARIANT, for the very arguments about to be launc
 Reference: float64 convolution of the DEQUANTISED operands (zero padding) + bias + shortcut + second pair, the activation, exact_f32.
 Why the kernel's fp32 result must equal it bit for bit: the int32 sums are exact, every scale is a power of two, and every fp32 operation
 of the epilogue's chain (conv_epilogue.h / conv_i8.hip) is a single rounding of an exact value - so it is exact whenever its real-valued
-result is an fp32 number.  The conditions, asserted on the CPU before any launch (`_pair_stages`, `reference`):
+result is an fp32 number.  The conditions, asserted on the CPU before any launch (tests/exact_stages.py: `pair_stages`; `reference`):
   * |SUM q' qw|, |(shift - zp) SUM qw| and their sum below 2^24 (the sum is converted to fp32);
   * dequant1 = fma(sum, s_in s_w[k], bias[k]) representable (a multiple of the unit s_in s_w[k] below 2^24 units);
   * ASYM: woff = s_in * w_off[k] representable (w_off an integer multiple of s_w[k]); the row sum SUM (q - zp) over the real taps below
@@ -23,20 +23,17 @@ ReLU, ReLU6's bound and the quantiser add no rounding to the fp32 value.  No for
 Unswapped pairs: fp32 output and codes together; SWAP pairs: codes, against the oracle's quantiser of the exact fp32 reference.  Buffers
 are sentinel-filled and checked beyond the written extent (rows past M; NARROW: fp32 rows are kf wide, nothing beyond M * kf)."""
 import functools
-import math
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import exact_layers as X
 import test_conv_dispatch_host as D
 import tiled_variant_cases as V
+from exact_stages import XOFF_O, assert_final_units, nhwc, pair_stages as _pair_stages, sentinel as _sentinel      # (shared with the halo file)
 from test_gpu_epilogue_exact import DEV, expect_codes, same, settle
 
 pytestmark = pytest.mark.gpu
-LIMIT = float(1 << 24)
-XOFF_O = -101           # the float activation offset in units of s_in
 
 
 def quant_of(kind, relu):
@@ -48,49 +45,6 @@ def quant_of(kind, relu):
     if kind == "shift":
         return X.Quant(s, shift128=True)
     return X.Quant(2.0 ** -5, -100.0, -128, 127) if relu == 2 else X.Quant(0.5, 3.0, -128, 127)
-
-
-def _conv(x, w, g, second=False):
-    sfx = "2" if second else ""
-    return F.conv2d(x, w, stride=g["stride" + sfx], padding=g["pad" + sfx], dilation=g["dil" + sfx])
-
-
-def _pair_stages(lay, g, shift, second=False, xoff=False):
-    """One operand pair: (true float64 result before shortcut / activation, the bias the kernel is handed, tap sums or None), with the
-    chain's conditions asserted stage by stage."""
-    u = lay.unit.reshape(1, -1, 1, 1)
-    xi = lay.xint()
-    A = _conv(xi, lay.wq.double(), g, second)                        # SUM (q - zp) qw over the real taps = SUM q' qw + (shift - zp) SUM qw
-    wsum = lay.wq.double().sum(dim=(1, 2, 3))
-    corr = ((shift - lay.zp) * wsum).reshape(1, -1, 1, 1)
-    assert float((A - corr).abs().max()) < LIMIT and float(corr.abs().max()) < LIMIT and float(A.abs().max()) < LIMIT
-    bias = lay.bias
-    o = XOFF_O * lay.s_in if xoff else 0.0
-    x_true = xi * lay.s_in
-    tap_f = None
-    if xoff:
-        x_true = x_true + o                                          # x^ = q s + o, zero padded as a value: the padding is 0, not o
-        tap = lay.w64().sum(dim=1)                                   # [K, R, S]: per-tap sums of the dequantised weights
-        tap_f = X.exact_f32(tap, "tap sums")
-        assert bool((tap.abs().sum(dim=(1, 2)) / lay.s_w.double() < LIMIT).all())
-        bias = X.exact_f32(lay.bias.double() + o * tap.sum(dim=(1, 2)), "folded bias")
-    true = _conv(x_true, lay.w64(), g, second) + lay.bias.double().reshape(1, -1, 1, 1)
-    v = X.exact_f32(A * u + bias.double().reshape(1, -1, 1, 1), "dequant1").double()
-    live_ = (v / u)[:, lay.nz:]                                     # (channels [0, nz) carry the edge values: 0 * unit + bias, exact as it is)
-    assert float(live_[live_.isfinite()].abs().max()) < LIMIT
-    if lay.w_int is not None:
-        woff = X.exact_f32(lay.s_in * lay.w_off.double(), "s_in * w_off").double().reshape(1, -1, 1, 1)
-        s0 = _conv(xi, torch.ones(1, *lay.wq.shape[1:], dtype=torch.float64), g, second)
-        assert float(s0.abs().max()) < LIMIT
-        v = X.exact_f32(v + X.exact_f32(s0 * woff, "rowsum * woff").double(), "+ weight-offset term").double()
-    if xoff:
-        ones = torch.ones(1, 1, *xi.shape[2:], dtype=torch.float64)
-        inside = _conv(ones, tap.unsqueeze(1), g)                    # the in-bounds taps' sum per output pixel
-        border = tap.sum(dim=(1, 2)).reshape(1, -1, 1, 1) - inside
-        v = X.exact_f32(v - o * border, "- o * border").double()
-    ok = (v == true) | (v.isnan() & true.isnan())
-    assert bool(ok.all()), "the staged chain and the convolution of the dequantised operands disagree"
-    return true, bias, tap_f
 
 
 @functools.lru_cache(maxsize=None)
@@ -126,19 +80,8 @@ def reference(bn, flags, index):
             res[:, live:] = 0.0                                      # (NARROW: the padded columns have no shortcut)
         ops["res"] = res
         true = X.exact_f32(true + res.double(), "+ shortcut").double()
-    units = (true / lay.unit.reshape(1, -1, 1, 1))[:, lay.nz:]
-    assert float(units[units.isfinite()].abs().max()) < LIMIT          # the final value in units of s_in * s_w[k]
+    assert_final_units(true, lay)                                      # the final value in units of s_in * s_w[k]
     return ops, true
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def _sentinel(numel, dtype):
-    t = torch.empty(numel, dtype=dtype, device=DEV)
-    t.view(torch.uint8).fill_(0xA5)
-    return t
 
 
 def run_case(case, errs):
