@@ -529,114 +529,119 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void conv_dw_i8_kernel(const uint32_t*
 
 using namespace dlmcq;
 
-static int dw_launch(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale, const float* in_zero_point,
-                     const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S,
-                     int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
-                     const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream,
-                     const float* x_off = nullptr, const float* x_tap = nullptr) {
-  if (N < 0 || H < 1 || W < 1 || C < 4 || (C & 3) || R < 1 || S < 1 || R > 7 || S > 7 || stride < 1 || pad < 0) return DLMCQ_EINVAL;
-  const int64_t P = (H + 2 * pad - R) / stride + 1, Q = (W + 2 * pad - S) / stride + 1;
-  if (P < 1 || Q < 1) return DLMCQ_EINVAL;
-  const uint32_t ctl = (uint32_t)q_form & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY);     // (include/dlmcq.h: control bits of `q_form`)
-  q_form &= ~(DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY);
-  if (N == 0) return DLMCQ_OK;
-  if (!x || !w || !(out || codes) || !in_scale || !w_scale) return DLMCQ_EINVAL;
-  if (codes && (!q_scale || q_lo > q_hi || q_lo < -128 || q_hi > 255 || q_hi - q_lo > 255 || q_form < DLMCQ_FORM_EMULATE ||
-                q_form > DLMCQ_FORM_SYMMETRIC))
+// THE table of the depthwise instantiations: one macro line gives a row's key and the launcher of the kernel it names.  The two 3 x 3
+// families in (FAST 0 / 1 / 2) x R6 x XOFF, the generic kernel in R6: 12 + 12 + 2 = 26.
+enum DwFamily { DW_P2, DW_3, DW_GENERIC };     // conv_dw3p2_i8_kernel (two pixels per thread), conv_dw3_i8_kernel, conv_dw_i8_kernel
+typedef void (*DwGo)(dim3 grid, size_t lds, const DwCall& c, const DwGeom& g);
+template <typename XT, typename WT,
+          void (*KERNEL)(const XT*, const WT*, float*, const float*, const float*, const float*, const float*, const float*, DwGeom, int, ConvEpi)>
+static void dw_go(dim3 grid, size_t lds, const DwCall& c, const DwGeom& g) {
+  hipLaunchKernelGGL(KERNEL, grid, dim3(DLMCQ_BLOCK), lds, c.st, static_cast<const XT*>(c.x), reinterpret_cast<const WT*>(c.w), c.out, c.bias, c.s_in,
+                     c.zp_in, c.s_w, c.w_off, g, c.x_signed, c.ep);
+}
+struct DwVariant {
+  DwFamily family;
+  int fast;
+  bool r6, xoff;
+  DwGo go;
+};
+#define DLMCQ_DW_V(FAMILY, KERNEL, FAST, R6, XOFF) {FAMILY, FAST, R6, XOFF, dw_go<u32x4, int8_t, KERNEL<FAST, R6, XOFF>>},
+#define DLMCQ_DW_FAMILY(FAMILY, KERNEL)                                                                                         \
+  DLMCQ_DW_V(FAMILY, KERNEL, 0, false, false) DLMCQ_DW_V(FAMILY, KERNEL, 1, false, false) DLMCQ_DW_V(FAMILY, KERNEL, 2, false, false) \
+  DLMCQ_DW_V(FAMILY, KERNEL, 0, true, false) DLMCQ_DW_V(FAMILY, KERNEL, 1, true, false) DLMCQ_DW_V(FAMILY, KERNEL, 2, true, false)    \
+  DLMCQ_DW_V(FAMILY, KERNEL, 0, false, true) DLMCQ_DW_V(FAMILY, KERNEL, 1, false, true) DLMCQ_DW_V(FAMILY, KERNEL, 2, false, true)    \
+  DLMCQ_DW_V(FAMILY, KERNEL, 0, true, true) DLMCQ_DW_V(FAMILY, KERNEL, 1, true, true) DLMCQ_DW_V(FAMILY, KERNEL, 2, true, true)
+#define DLMCQ_DW_GENERIC_V(R6) {DW_GENERIC, 0, R6, false, dw_go<uint32_t, uint32_t, conv_dw_i8_kernel<R6>>},
+static const DwVariant DW_TABLE[] = {DLMCQ_DW_FAMILY(DW_P2, conv_dw3p2_i8_kernel) DLMCQ_DW_FAMILY(DW_3, conv_dw3_i8_kernel)
+                                     DLMCQ_DW_GENERIC_V(false) DLMCQ_DW_GENERIC_V(true)};
+#undef DLMCQ_DW_GENERIC_V
+#undef DLMCQ_DW_FAMILY
+#undef DLMCQ_DW_V
+static_assert(sizeof(DW_TABLE) / sizeof(DW_TABLE[0]) == 26, "the instantiations");
+
+// What really differs between the families: the work items a thread walks (hence the grid and the dividers) and the LDS table's size
+static dim3 dw_p2_shape(const DwCall& c, DwGeom& g, int, size_t& lds) {      // two output pixels per thread (LDS: 48 B per channel)
+  const int64_t qpairs = (c.Q + 1) / 2;
+  g.cdiv = make_fastdiv((uint32_t)(c.C / 16));
+  g.qdiv = make_fastdiv((uint32_t)qpairs);
+  const int64_t b16 = (c.N * c.P * qpairs * (c.C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
+  lds = (size_t)(c.C / 16) * (3 * 17 * 16);
+  return dim3((uint32_t)(b16 < 4096 ? b16 : 4096));
+}
+static dim3 dw_3_shape(const DwCall& c, DwGeom& g, int fast, size_t& lds) {
+  g.cdiv = make_fastdiv((uint32_t)(c.C / 16));
+  const int64_t b16 = (c.N * c.P * c.Q * (c.C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
+  // every workgroup packs the layer's weights into its LDS table first: a grid of a few workgroups per CU, each walking many pixels
+  lds = fast ? (size_t)(c.C / 16) * (17 * 16 + 9 * 16 + 9 * 8) : (size_t)c.C * sizeof(DwTab);
+  return dim3((uint32_t)(b16 < 4096 ? b16 : 4096));
+}
+static dim3 dw_generic_shape(const DwCall& c, DwGeom&, int, size_t& lds) {
+  const int64_t blocks = (c.N * c.P * c.Q * (c.C / 4) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
+  lds = 0;
+  return dim3((uint32_t)(blocks < (1 << 20) ? blocks : (1 << 20)));
+}
+
+// the record of a depthwise entry point's ABI arguments; ep.x_off / ep.x_tap are the caller's to set.  Of `q_form`'s flag bits only the
+// two control bits are taken (dw_launch): the rest of it goes into the epilogue as it came.
+static DwCall dw_call(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale, const float* in_zero_point,
+                      const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S,
+                      int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
+                      const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
+  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY;     // (include/dlmcq.h: control bits of `q_form`)
+  DwCall c{};
+  c.x = x; c.w = w; c.out = out; c.bias = bias; c.s_in = in_scale; c.zp_in = in_zero_point; c.s_w = w_scale; c.w_off = w_offset;
+  c.N = N; c.H = H; c.W = W; c.C = C; c.R = R; c.S = S; c.stride = stride; c.pad = pad;
+  c.x_signed = x_is_unsigned ? 0 : 1;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  c.ep = make_epi_form(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form & ~CTL, q_ste_g);
+  c.ctl = (uint32_t)q_form & CTL;
+  c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form;
+  c.P = conv_out_size(H, R, stride, pad, 1);
+  c.Q = conv_out_size(W, S, stride, pad, 1);
+  return c;
+}
+
+static int dw_launch(const DwCall& c) {
+  if (c.N < 0 || c.H < 1 || c.W < 1 || c.C < 4 || (c.C & 3) || c.R < 1 || c.S < 1 || c.R > 7 || c.S > 7 || c.stride < 1 || c.pad < 0)
     return DLMCQ_EINVAL;
-  if (!aligned4(x) || !aligned4(w) || !aligned16(w_scale) || (w_offset && !aligned16(w_offset)) || (bias && !aligned16(bias)) ||
-      (out && !aligned16(out)) || (codes && !aligned4(codes)))
+  if (c.P < 1 || c.Q < 1) return DLMCQ_EINVAL;
+  if (c.N == 0) return DLMCQ_OK;
+  if (!c.x || !c.w || !(c.out || c.ep.codes) || !c.s_in || !c.s_w) return DLMCQ_EINVAL;
+  if (quantiser_check(c.ep.codes, c.ep.q_scale, c.q_lo, c.q_hi, c.q_form, DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY) != DLMCQ_OK) return DLMCQ_EINVAL;
+  if (!aligned4(c.x) || !aligned4(c.w) || !aligned16(c.s_w) || (c.w_off && !aligned16(c.w_off)) || (c.bias && !aligned16(c.bias)) ||
+      (c.out && !aligned16(c.out)) || (c.ep.codes && !aligned4(c.ep.codes)))
     return DLMCQ_EALIGN;
-  if (N * P * Q * (C / 4) >= (1ll << 31) || N * H * W * (C / 4) >= (1ll << 31)) return DLMCQ_ERANGE;
-  DwGeom g;
-  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.C4 = (int)(C / 4); g.R = (int)R; g.S = (int)S; g.stride = stride; g.pad = pad;
-  g.P = (int)P; g.Q = (int)Q;
-  g.cdiv = make_fastdiv((uint32_t)g.C4);
-  g.qdiv = make_fastdiv((uint32_t)Q);
-  g.pdiv = make_fastdiv((uint32_t)P);
-  ConvEpi ep{};
-  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  ep.q_form = q_form;
-  ep.x_off = x_off;
-  ep.x_tap = x_tap;
-  const bool xoff = x_off != nullptr;
-  const int64_t total = N * P * Q * (C / 4);
-  const int64_t blocks = (total + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!(ctl & DLMCQ_FORCE_TILED) && !xoff && conv_dwm_applies(N, H, W, C, R, S, stride, pad, ep, out, x)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores
-    if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DWM;
-    return conv_dwm_launch(static_cast<const int8_t*>(x), w, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C,
-                           x_is_unsigned ? 0 : 1, ep, st);
+  if (c.N * c.P * c.Q * (c.C / 4) >= (1ll << 31) || c.N * c.H * c.W * (c.C / 4) >= (1ll << 31)) return DLMCQ_ERANGE;
+  const bool xoff = c.ep.x_off != nullptr;
+  if (!(c.ctl & DLMCQ_FORCE_TILED) && !xoff && conv_dwm_applies(c)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores
+    if (c.ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DWM;
+    return conv_dwm_launch(c);
   }
-  const bool wide = R == 3 && S == 3 && C % 16 == 0 && C <= 2048 && aligned16(x) && (!codes || aligned16(codes));
+  const bool wide = c.R == 3 && c.S == 3 && c.C % 16 == 0 && c.C <= 2048 && aligned16(c.x) && (!c.ep.codes || aligned16(c.ep.codes));
   if (xoff && !wide) return DLMCQ_EINVAL;           // (the border term: the 3 x 3 kernels only)
-  if (ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
-  const bool r6 = ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
-  if (wide && stride == 1 && pad == 1 && C <= 1024) {     // two output pixels per thread (LDS: 48 B per channel)
-    g.cdiv = make_fastdiv((uint32_t)(C / 16));
-    const int64_t qpairs = (Q + 1) / 2;
-    g.qdiv = make_fastdiv((uint32_t)qpairs);
-    const int64_t b16 = (N * P * qpairs * (C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
-    const int fast = (!out && epi_plain(ep)) ? (w_offset ? 1 : 2) : 0;
-#define DLMCQ_DWP2(...) hipLaunchKernelGGL((conv_dw3p2_i8_kernel<__VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), (size_t)(C / 16) * (3 * 17 * 16), st, \
-                                           static_cast<const u32x4*>(x), w, out, bias, in_scale, in_zero_point, w_scale, w_offset, g,              \
-                                           x_is_unsigned ? 0 : 1, ep)
-    if (xoff) {
-      if (r6) {
-        if (fast == 1) DLMCQ_DWP2(1, true, true);
-        else if (fast == 2) DLMCQ_DWP2(2, true, true);
-        else DLMCQ_DWP2(0, true, true);
-      } else if (fast == 1) DLMCQ_DWP2(1, false, true);
-      else if (fast == 2) DLMCQ_DWP2(2, false, true);
-      else DLMCQ_DWP2(0, false, true);
-    } else if (r6) {
-      if (fast == 1) DLMCQ_DWP2(1, true);
-      else if (fast == 2) DLMCQ_DWP2(2, true);
-      else DLMCQ_DWP2(0, true);
-    } else if (fast == 1) DLMCQ_DWP2(1);
-    else if (fast == 2) DLMCQ_DWP2(2);
-    else DLMCQ_DWP2(0);
-#undef DLMCQ_DWP2
-  } else if (wide) {
-    g.cdiv = make_fastdiv((uint32_t)(C / 16));
-    const int64_t b16 = (N * P * Q * (C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
-    // every workgroup packs the layer's weights into its LDS table first: a grid of a few workgroups per CU, each walking many pixels
-    const int fast = (!out && epi_plain(ep)) ? (w_offset ? 1 : 2) : 0;
-#define DLMCQ_DW3(F, ...) hipLaunchKernelGGL((conv_dw3_i8_kernel<F __VA_ARGS__>), dim3((uint32_t)(b16 < 4096 ? b16 : 4096)), dim3(DLMCQ_BLOCK), \
-                                        F ? (size_t)(C / 16) * (17 * 16 + 9 * 16 + 9 * 8) : (size_t)C * sizeof(DwTab), st, static_cast<const u32x4*>(x), w, \
-                                        out, bias, in_scale, in_zero_point, w_scale, w_offset, g, x_is_unsigned ? 0 : 1, ep)
-    if (xoff) {
-      if (r6) {
-        if (fast == 1) DLMCQ_DW3(1, , true, true);
-        else if (fast == 2) DLMCQ_DW3(2, , true, true);
-        else DLMCQ_DW3(0, , true, true);
-      } else if (fast == 1) DLMCQ_DW3(1, , false, true);
-      else if (fast == 2) DLMCQ_DW3(2, , false, true);
-      else DLMCQ_DW3(0, , false, true);
-    } else if (r6) {
-      if (fast == 1) DLMCQ_DW3(1, , true);
-      else if (fast == 2) DLMCQ_DW3(2, , true);
-      else DLMCQ_DW3(0, , true);
-    } else if (fast == 1) DLMCQ_DW3(1);
-    else if (fast == 2) DLMCQ_DW3(2);
-    else DLMCQ_DW3(0);
-#undef DLMCQ_DW3
-  } else {
-#define DLMCQ_DWG(...) hipLaunchKernelGGL((conv_dw_i8_kernel<__VA_ARGS__>), dim3((uint32_t)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(DLMCQ_BLOCK), 0, st, \
-                                          static_cast<const uint32_t*>(x), reinterpret_cast<const uint32_t*>(w), out, bias, in_scale, in_zero_point, w_scale, \
-                                          w_offset, g, x_is_unsigned ? 0 : 1, ep)
-    if (r6) DLMCQ_DWG(true);
-    else DLMCQ_DWG();
-#undef DLMCQ_DWG
-  }
+  if (c.ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
+  // the key.  FAST (the 3 x 3 families): a codes-only layer with the plain quantiser, 1 asymmetric / 2 symmetric weights
+  const DwFamily family = !wide ? DW_GENERIC : (c.stride == 1 && c.pad == 1 && c.C <= 1024) ? DW_P2 : DW_3;
+  const int fast = (wide && !c.out && epi_plain(c.ep)) ? (c.w_off ? 1 : 2) : 0;
+  const bool r6 = c.ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
+  const DwVariant* v = nullptr;
+  for (const DwVariant& t : DW_TABLE)
+    if (t.family == family && t.fast == fast && t.r6 == r6 && t.xoff == xoff) v = &t;
+  if (!v) return DLMCQ_EINVAL;
+  DwGeom g;
+  g.N = (int)c.N; g.H = (int)c.H; g.W = (int)c.W; g.C4 = (int)(c.C / 4); g.R = (int)c.R; g.S = (int)c.S; g.stride = c.stride; g.pad = c.pad;
+  g.P = (int)c.P; g.Q = (int)c.Q;
+  g.cdiv = make_fastdiv((uint32_t)g.C4);
+  g.qdiv = make_fastdiv((uint32_t)c.Q);
+  g.pdiv = make_fastdiv((uint32_t)c.P);
+  size_t lds = 0;
+  const dim3 grid = (family == DW_P2 ? dw_p2_shape : family == DW_3 ? dw_3_shape : dw_generic_shape)(c, g, fast, lds);
+  v->go(grid, lds, c, g);
   return launch_status();
 }
+
+#define DLMCQ_DW_ABI x, w, out, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C, R, S, stride, pad, x_is_unsigned, relu, codes, q_scale, \
+                     q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream
 
 extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
                                        const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N,
@@ -644,8 +649,7 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* ou
                                        int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
                                        const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                                        dlmcq_stream_t stream) {
-  return dw_launch(x, w, out, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C, R, S, stride, pad, x_is_unsigned, relu, codes,
-                   q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream);
+  return dw_launch(dw_call(DLMCQ_DW_ABI));
 }
 
 extern "C" int dlmcq_conv2d_dw_i8_nhwc_xoff(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
@@ -656,7 +660,11 @@ extern "C" int dlmcq_conv2d_dw_i8_nhwc_xoff(const void* x, const int8_t* w, floa
                                             const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
   if (!in_offset || !tap_sums) return DLMCQ_EINVAL;
   if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
-  // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
-  return dw_launch(x, w, out, bias, in_scale, in_zero_point, w_scale, w_offset, N, H, W, C, R, S, stride, pad, x_is_unsigned, relu, codes,
-                   q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream, pad > 0 ? in_offset : nullptr, pad > 0 ? tap_sums : nullptr);
+  DwCall c = dw_call(DLMCQ_DW_ABI);
+  if (pad > 0) {     // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
+    c.ep.x_off = in_offset;
+    c.ep.x_tap = tap_sums;
+  }
+  return dw_launch(c);
 }
+#undef DLMCQ_DW_ABI

@@ -233,55 +233,53 @@ __global__ __launch_bounds__(256, 3) void conv_dwm_i8_kernel(DwmArgs a, ConvEpi 
 
 // where the kernel applies: 3 x 3 / stride 1 / padding 1, codes only with the plain quantiser, whole 64-channel chunks, a halo tile
 // of at most 16 pieces
-bool conv_dwm_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad, const ConvEpi& ep,
-                      const float* out, const void* x) {
-  if (R != 3 || S != 3 || stride != 1 || pad != 1 || out || !epi_plain(ep)) return false;
-  if (C < 64 || (C & 63) || !aligned16(x) || !aligned16(ep.codes)) return false;
-  if ((DWM_TP + 2 * (W + 1) + 2 + 15) / 16 > 20 || W < 14) return false;        // (a piece of 16 positions wraps at most one frame row)
-  if (N * (H + 1) * (W + 1) + 4096 >= (1ll << 31) || N * H * W * C >= (int64_t)BUF_BIG) return false;     // 32-bit positions and buffer offsets
-  return N * H * W >= 4096;                                     // (weights and constants are set up once per workgroup)
+bool conv_dwm_applies(const DwCall& c) {
+  if (c.R != 3 || c.S != 3 || c.stride != 1 || c.pad != 1 || c.out || !epi_plain(c.ep)) return false;
+  if (c.C < 64 || (c.C & 63) || !aligned16(c.x) || !aligned16(c.ep.codes)) return false;
+  if ((DWM_TP + 2 * (c.W + 1) + 2 + 15) / 16 > 20 || c.W < 14) return false;        // (a piece of 16 positions wraps at most one frame row)
+  if (c.N * (c.H + 1) * (c.W + 1) + 4096 >= (1ll << 31) || c.N * c.H * c.W * c.C >= (int64_t)BUF_BIG) return false;     // 32-bit positions and buffer offsets
+  return c.N * c.H * c.W >= 4096;                               // (weights and constants are set up once per workgroup)
 }
 
-int conv_dwm_launch(const int8_t* x, const int8_t* w, const float* bias, const float* in_scale, const float* in_zero_point,
-                    const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int x_signed,
-                    const ConvEpi& ep, hipStream_t st) {
+// THE table of the instantiations: halo pieces per wave (4 or 5) x signed input codes x ReLU6
+typedef void (*DwmKernel)(DwmArgs, ConvEpi);
+struct DwmVariant {
+  int hpw;
+  bool xs, r6;
+  DwmKernel kernel;
+};
+#define DLMCQ_DWM_V(HPW, XS, R6) {HPW, XS, R6, &conv_dwm_i8_kernel<HPW, XS, R6>},
+#define DLMCQ_DWM_QUAD(HPW) DLMCQ_DWM_V(HPW, false, false) DLMCQ_DWM_V(HPW, true, false) DLMCQ_DWM_V(HPW, false, true) DLMCQ_DWM_V(HPW, true, true)
+static const DwmVariant DWM_TABLE[] = {DLMCQ_DWM_QUAD(4) DLMCQ_DWM_QUAD(5)};
+#undef DLMCQ_DWM_QUAD
+#undef DLMCQ_DWM_V
+static_assert(sizeof(DWM_TABLE) / sizeof(DWM_TABLE[0]) == 8, "the instantiations");
+
+int conv_dwm_launch(const DwCall& c) {
   DwmArgs a{};
-  a.x = x; a.w = w; a.s_w = w_scale; a.o_w = w_offset; a.bias = bias; a.s_in = in_scale; a.zp_in = in_zero_point;
-  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.C = (int)C; a.x_signed = x_signed;
-  a.Wp = (int)W + 1;
-  a.FS = (int)((H + 1) * (W + 1));
-  a.MQ = (uint32_t)(N * a.FS);
+  a.x = static_cast<const int8_t*>(c.x); a.w = c.w; a.s_w = c.s_w; a.o_w = c.w_off; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
+  a.N = (int)c.N; a.H = (int)c.H; a.W = (int)c.W; a.C = (int)c.C; a.x_signed = c.x_signed;
+  a.Wp = (int)c.W + 1;
+  a.FS = (int)((c.H + 1) * (c.W + 1));
+  a.MQ = (uint32_t)(c.N * a.FS);
   a.hp = (DWM_TP + 2 * a.Wp + 2 + 15) / 16;
   a.ntiles = (int)(((int64_t)a.MQ + DWM_TP - 1) / DWM_TP);
-  a.nchunks = (int)(C / 64);
+  a.nchunks = (int)(c.C / 64);
   a.fsdiv = make_fastdiv((uint32_t)a.FS);
   a.wpdiv = make_fastdiv((uint32_t)a.Wp);
-  a.codes = ep.codes;
-  static int cus = 0;      // (one device per process: dlmc/_native.py)
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-              ? prop.multiProcessorCount : 256;
-  }
-  const int hpw = (a.hp + 3) / 4;
+  a.codes = c.ep.codes;
   // workgroups: three per CU (registers) in groups of `nchunks` that share their positions on one XCD
-  int ngroups = ((cus * 3) / a.nchunks) & ~7;
+  int ngroups = ((device_cus() * 3) / a.nchunks) & ~7;
   if (ngroups < 8) ngroups = 8;
   const int maxg = (a.ntiles + 7) & ~7;
   if (ngroups > maxg) ngroups = maxg;
-  const dim3 grid((uint32_t)(ngroups * a.nchunks)), block(256);
-#define DLMCQ_DWM_GO(HP_)                                                                                     \
-  do {                                                                                                        \
-    if (ep.relu == DLMCQ_ACT_RELU6) {                                                                         \
-      if (x_signed) hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, true, true>), grid, block, 0, st, a, ep);       \
-      else hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, false, true>), grid, block, 0, st, a, ep);               \
-    } else if (x_signed) hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, true>), grid, block, 0, st, a, ep);       \
-    else hipLaunchKernelGGL((conv_dwm_i8_kernel<HP_, false>), grid, block, 0, st, a, ep);                      \
-  } while (0)
-  if (hpw <= 4) DLMCQ_DWM_GO(4);
-  else DLMCQ_DWM_GO(5);
-#undef DLMCQ_DWM_GO
+  const int hpw = (a.hp + 3) / 4 <= 4 ? 4 : 5;
+  const bool xs = c.x_signed != 0, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
+  const DwmVariant* v = nullptr;
+  for (const DwmVariant& t : DWM_TABLE)
+    if (t.hpw == hpw && t.xs == xs && t.r6 == r6) v = &t;
+  if (!v) return DLMCQ_EINVAL;
+  hipLaunchKernelGGL(v->kernel, dim3((uint32_t)(ngroups * a.nchunks)), dim3(256), 0, c.st, a, c.ep);
   return launch_status();
 }
 

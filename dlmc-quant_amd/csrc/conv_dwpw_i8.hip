@@ -356,6 +356,59 @@ extern "C" int dlmcq_dwpw_pack_table(const int8_t* w, const float* bias, const f
   return launch_status();
 }
 
+// One depthwise + pointwise unit as the host sees it: what the entry point received, by name - the kernel's record with the pointers and
+// flags in place, the sizes as passed, both epilogues (ep1: the depthwise layer's, always quantising; ep2: the unit's) and both
+// quantisers' ranges and forms as passed (dwpw_launch validates these: no flag bit of either form is taken)
+struct DwPwCall {
+  DwPwArgs a;
+  int64_t N, H, W, C, K;
+  ConvEpi ep1, ep2;
+  int32_t q_lo, q_hi, q_form, q2_lo, q2_hi, q2_form;
+  hipStream_t st;
+};
+
+// THE table of the instantiations: pointwise width x halo pieces per wave
+typedef void (*DwPwKernel)(DwPwArgs, ConvEpi, ConvEpi);
+struct DwPwVariant {
+  int kb, hpw;
+  DwPwKernel kernel;
+};
+#define DLMCQ_DWPW_V(KB, HPW) {KB, HPW, &conv_dwpw_i8_kernel<KB, HPW>},
+static const DwPwVariant DWPW_TABLE[] = {DLMCQ_DWPW_V(128, 2) DLMCQ_DWPW_V(128, 3) DLMCQ_DWPW_V(192, 2) DLMCQ_DWPW_V(192, 3) DLMCQ_DWPW_V(512, 2)
+                                         DLMCQ_DWPW_V(512, 3)};
+#undef DLMCQ_DWPW_V
+static_assert(sizeof(DWPW_TABLE) / sizeof(DWPW_TABLE[0]) == 6, "the instantiations");
+
+static int dwpw_launch(const DwPwCall& c) {
+  const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K;
+  if (c.ep1.relu == DLMCQ_ACT_RELU6 || c.ep2.relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
+  if (N < 0 || H < 1 || W < 1 || C < 64 || (C & 63) || (K != 128 && K != 192 && K != 512)) return DLMCQ_EINVAL;
+  if (N == 0) return DLMCQ_OK;
+  DwPwArgs a = c.a;
+  if (!a.x || !a.table || !c.ep1.q_scale || !a.w || !a.wsum || !a.s_in || !a.s_w || !a.codes || !c.ep2.q_scale) return DLMCQ_EINVAL;
+  if (c.q_lo != 0 || c.q_hi != 255) return DLMCQ_EINVAL;      // the matrix step reads the depthwise codes as unsigned bytes (shift 128)
+  if (!aligned16(a.x) || !aligned16(a.table) || !aligned16(a.w) || !aligned16(a.codes)) return DLMCQ_EALIGN;
+  if (!quantiser_form_ok(c.q_lo, c.q_hi, c.q_form, 0) || quantiser_check(a.codes, c.ep2.q_scale, c.q2_lo, c.q2_hi, c.q2_form, 0) != DLMCQ_OK)
+    return DLMCQ_EINVAL;                                      // (no flag bits: SHIFT128 included)
+  a.Wp = (int)W + 1;
+  a.FS = (int)((H + 1) * (W + 1));
+  const int64_t mq = N * a.FS;
+  if (mq + 4096 >= (1ll << 31) || N * H * W * (C > K ? C : K) >= (1ll << 40)) return DLMCQ_ERANGE;
+  a.hp = (DWPW_TP + 2 * a.Wp + 2 + 15) / 16;
+  if (a.hp > 12) return DLMCQ_EINVAL;                      // images wider than 61 pixels: two launches (the plan does that)
+  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.C = (int)C; a.K = (int)K;
+  a.MQ = (uint32_t)mq;
+  a.fsdiv = make_fastdiv((uint32_t)a.FS);
+  a.wpdiv = make_fastdiv((uint32_t)a.Wp);
+  const int hpw = (a.hp + 3) / 4 <= 2 ? 2 : 3;     // halo pieces per wave
+  const DwPwVariant* v = nullptr;
+  for (const DwPwVariant& t : DWPW_TABLE)
+    if (t.kb == K && t.hpw == hpw) v = &t;
+  if (!v) return DLMCQ_EINVAL;
+  hipLaunchKernelGGL(v->kernel, dim3((uint32_t)((mq + DWPW_TP - 1) / DWPW_TP)), dim3(256), 0, c.st, a, c.ep1, c.ep2);
+  return launch_status();
+}
+
 extern "C" int dlmcq_conv2d_dwpw_i8_nhwc(const void* x, const void* dw_table, int32_t dw_asym, int32_t dw_bias, int32_t dw_relu,
                                          const float* in_zero_point, int64_t N, int64_t H, int64_t W, int64_t C, int32_t x_is_unsigned,
                                          const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
@@ -363,49 +416,19 @@ extern "C" int dlmcq_conv2d_dwpw_i8_nhwc(const void* x, const void* dw_table, in
                                          const float* pw_in_scale, const float* w_scale, const float* w_offset, int64_t K,
                                          int32_t relu, void* codes, const float* q2_scale, const float* q2_zero_point, int32_t q2_lo,
                                          int32_t q2_hi, int32_t q2_form, float q2_ste_g, dlmcq_stream_t stream) {
-  if (dw_relu == DLMCQ_ACT_RELU6 || relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
-  if (N < 0 || H < 1 || W < 1 || C < 64 || (C & 63) || (K != 128 && K != 192 && K != 512)) return DLMCQ_EINVAL;
-  if (N == 0) return DLMCQ_OK;
-  if (!x || !dw_table || !q_scale || !w || !wsum || !pw_in_scale || !w_scale || !codes || !q2_scale) return DLMCQ_EINVAL;
-  if (q_lo != 0 || q_hi != 255) return DLMCQ_EINVAL;      // the matrix step reads the depthwise codes as unsigned bytes (shift 128)
-  if (!aligned16(x) || !aligned16(dw_table) || !aligned16(w) || !aligned16(codes)) return DLMCQ_EALIGN;
-  ConvEpi ep1{}, ep2{};
-  if (q2_lo > q2_hi || q2_lo < -128 || q2_hi > 255 || q2_hi - q2_lo > 255 || q_form < DLMCQ_FORM_EMULATE || q_form > DLMCQ_FORM_SYMMETRIC ||
-      q2_form < DLMCQ_FORM_EMULATE || q2_form > DLMCQ_FORM_SYMMETRIC || !epi_set_form(ep2, q2_form, q2_lo, q2_hi))   // (no flag bits: SHIFT128 included)
-    return DLMCQ_EINVAL;
-  DwPwArgs a{};
-  a.Wp = (int)W + 1;
-  a.FS = (int)((H + 1) * (W + 1));
-  const int64_t mq = N * a.FS;
-  if (mq + 4096 >= (1ll << 31) || N * H * W * (C > K ? C : K) >= (1ll << 40)) return DLMCQ_ERANGE;
-  a.hp = (DWPW_TP + 2 * a.Wp + 2 + 15) / 16;
-  if (a.hp > 12) return DLMCQ_EINVAL;                      // images wider than 61 pixels: two launches (the plan does that)
+  DwPwCall c{};
+  DwPwArgs& a = c.a;
   a.x = static_cast<const int8_t*>(x);
   a.table = static_cast<const uint32_t*>(dw_table);
   a.dw_asym = dw_asym != 0; a.dw_bias = dw_bias != 0; a.dw_relu = dw_relu != 0; a.x_signed = x_is_unsigned ? 0 : 1;
   a.w = w; a.s_w = w_scale; a.wsum = wsum; a.bias = bias; a.w_off = w_offset; a.s_in = pw_in_scale; a.zp_in = q_zero_point;
-  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.C = (int)C; a.K = (int)K;
-  a.MQ = (uint32_t)mq;
-  a.fsdiv = make_fastdiv((uint32_t)a.FS);
-  a.wpdiv = make_fastdiv((uint32_t)a.Wp);
   a.codes = static_cast<uint8_t*>(codes);
   a.zp_x = in_zero_point;
-  ep1.relu = dw_relu != 0; ep1.q_scale = q_scale; ep1.q_zp = q_zero_point; ep1.q_lo = (float)q_lo; ep1.q_hi = (float)q_hi; ep1.q_g = q_ste_g;
-  ep1.q_form = q_form; ep1.codes = reinterpret_cast<uint8_t*>(uintptr_t(1));     // (the quantiser is always needed: the matrix step reads its codes)
-  ep2.relu = relu != 0; ep2.q_scale = q2_scale; ep2.q_zp = q2_zero_point; ep2.q_lo = (float)q2_lo; ep2.q_hi = (float)q2_hi; ep2.q_g = q2_ste_g;
-  ep2.codes = a.codes;
-  const int64_t tiles = (mq + DWPW_TP - 1) / DWPW_TP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((uint32_t)tiles), block(256);
-  const int hpw = (a.hp + 3) / 4;     // halo pieces per wave
-#define DLMCQ_DWPW_GO(KB_)                                                                                  \
-  do {                                                                                                      \
-    if (hpw <= 2) hipLaunchKernelGGL((conv_dwpw_i8_kernel<KB_, 2>), grid, block, 0, st, a, ep1, ep2);        \
-    else hipLaunchKernelGGL((conv_dwpw_i8_kernel<KB_, 3>), grid, block, 0, st, a, ep1, ep2);                 \
-  } while (0)
-  if (K == 128) DLMCQ_DWPW_GO(128);
-  else if (K == 192) DLMCQ_DWPW_GO(192);
-  else DLMCQ_DWPW_GO(512);
-#undef DLMCQ_DWPW_GO
-  return launch_status();
+  c.N = N; c.H = H; c.W = W; c.C = C; c.K = K;
+  // (the depthwise quantiser is always needed - the matrix step reads its codes -, so its epilogue gets a non-null `codes`)
+  c.ep1 = make_epi_form(nullptr, dw_relu, reinterpret_cast<uint8_t*>(uintptr_t(1)), q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  c.ep2 = make_epi_form(nullptr, relu, codes, q2_scale, q2_zero_point, q2_lo, q2_hi, q2_form, q2_ste_g);
+  c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form; c.q2_lo = q2_lo; c.q2_hi = q2_hi; c.q2_form = q2_form;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  return dwpw_launch(c);
 }

@@ -1,4 +1,5 @@
-// Epilogue shared by the int8 convolution kernels (conv_i8.hip, conv_stem_i8.hip).  Not part of the ABI.
+// Epilogue shared by every int8 convolution kernel (the conv*_i8.hip files) and, for its quantiser, by the pooling kernels (gap.hip,
+// avgpool.hip).  Not part of the ABI.
 #pragma once
 
 #include "dlmcq_internal.h"
@@ -88,6 +89,44 @@ static inline bool epi_set_form(ConvEpi& ep, int32_t q_form, int32_t q_lo, int32
   ep.q_form = q_form & ~(DLMCQ_EMIT_SHIFT128 | CTL);
   ep.q_xor = shifted ? 0x80808080u : 0u;
   return ep.q_form >= DLMCQ_FORM_EMULATE && ep.q_form <= DLMCQ_FORM_SYMMETRIC && (!shifted || (q_lo >= 0 && q_hi <= 255));
+}
+
+// THE range test of a consumer's quantiser as an entry point received it.  `accept`: the bits of `q_form` beyond the form number that
+// the entry point takes (DLMCQ_EMIT_SHIFT128, control bits) - every other bit puts the form out of range.  The first-layer, depthwise
+// and dwpw entry points take none (dw: its two control bits), so with `codes` they refuse every flag; WITHOUT `codes` nothing is looked
+// at and `q_form` passes as it came (tests/golden/dw_stem_refusals.json pins both).
+static inline bool quantiser_form_ok(int32_t q_lo, int32_t q_hi, int32_t q_form, int32_t accept) {
+  const int32_t form = q_form & ~accept;
+  return form >= DLMCQ_FORM_EMULATE && form <= DLMCQ_FORM_SYMMETRIC && (!(q_form & accept & DLMCQ_EMIT_SHIFT128) || (q_lo >= 0 && q_hi <= 255));
+}
+static inline int quantiser_check(const void* codes, const float* q_scale, int32_t q_lo, int32_t q_hi, int32_t q_form, int32_t accept) {
+  if (codes && (!q_scale || q_lo > q_hi || q_lo < -128 || q_hi > 255 || q_hi - q_lo > 255 || !quantiser_form_ok(q_lo, q_hi, q_form, accept)))
+    return DLMCQ_EINVAL;
+  return DLMCQ_OK;
+}
+
+// an entry point's quantiser arguments (+ its shortcut tensor) -> the epilogue record, `form` taken as it is: no flag bit is read out
+// of it (the entry points whose quantiser_check accepts none).  w_off, x_off and x_tap are the caller's to set.
+static inline ConvEpi make_epi_form(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                             int32_t q_hi, int32_t form, float q_ste_g) {
+  ConvEpi ep{};
+  ep.residual = residual;
+  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
+  ep.codes = static_cast<uint8_t*>(codes);
+  ep.q_scale = q_scale;
+  ep.q_zp = q_zero_point;
+  ep.q_lo = (float)q_lo;
+  ep.q_hi = (float)q_hi;
+  ep.q_g = q_ste_g;
+  ep.q_form = form;
+  return ep;
+}
+// ... with DLMCQ_EMIT_SHIFT128 and the control bits of `q_form` read out (epi_set_form): the tiled, chain and pooled-head entry points
+static inline ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                        int32_t q_hi, int32_t q_form, float q_ste_g) {
+  ConvEpi ep = make_epi_form(residual, relu, codes, q_scale, q_zero_point, q_lo, q_hi, 0, q_ste_g);
+  if (!epi_set_form(ep, q_form, q_lo, q_hi)) ep.q_form = -1;     // (conv_launch and chain_launch refuse it)
+  return ep;
 }
 
 // the quantiser of every post-ReLU tensor in the frozen plans: unsigned byte range, no zero point (EpiQuant::code4n<N, true>)

@@ -15,19 +15,13 @@ __device__ __forceinline__ void gap_finish4(const f32x4& s, int HW, const EpiQua
   if (codes) *reinterpret_cast<uint32_t*>(codes + at) = eq.code4(m);
 }
 
-// the seven quantiser arguments of an entry point -> ep (codes, constants, form, shifted emission, control bits in ep.ctl); the checks
-// of conv_launch (csrc/conv_i8.hip)
+// the seven quantiser arguments of an entry point -> ep (codes, constants, form, shifted emission, control bits in ep.ctl), checked
+// as conv_launch (csrc/conv_i8.hip) checks them; which control bits it takes is the caller's to say
 static inline int gap_set_quantiser(ConvEpi& ep, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                     int32_t q_form, float q_ste_g) {
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  if (!epi_set_form(ep, q_form, q_lo, q_hi)) return DLMCQ_EINVAL;
-  if (ep.codes && (!ep.q_scale || q_lo > q_hi || q_lo < -128 || q_hi > 255 || q_hi - q_lo > 255)) return DLMCQ_EINVAL;
-  return DLMCQ_OK;
+  ep = make_epi(nullptr, 0, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  if (ep.q_form < 0) return DLMCQ_EINVAL;
+  return quantiser_check(codes, q_scale, q_lo, q_hi, ep.q_form, 0);     // (the form: already without its flags)
 }
 
 }  // namespace dlmcq

@@ -1,5 +1,6 @@
 // Definitions shared by the int8 convolution translation units: the tiled kernel's device records and helpers, and the host-side call
-// records: ConvCall, which conv_launch (conv_i8.hip) and the kernel families it routes to pass around, and ChainCall (conv_chain_i8.hip).
+// records: ConvCall, which conv_launch (conv_i8.hip) and the kernel families it routes to pass around, ChainCall (conv_chain_i8.hip),
+// StemCall (conv_stem_i8.hip, conv_stem_pool7_i8.hip) and DwCall (conv_dw_i8.hip, conv_dwm_i8.hip).
 // Not part of the ABI.
 #pragma once
 
@@ -174,22 +175,6 @@ inline void conv_geom_tiles(ConvGeom& g, int bn) {     // CV_BM pixels x bn chan
   g.nblk_n = (g.K + bn - 1) / bn;
 }
 
-// an entry point's eight quantiser arguments (+ its shortcut tensor) -> the epilogue record
-inline ConvEpi make_epi(const float* residual, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
-                        int32_t q_hi, int32_t q_form, float q_ste_g) {
-  ConvEpi ep{};
-  ep.residual = residual;
-  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  if (!epi_set_form(ep, q_form, q_lo, q_hi)) ep.q_form = -1;     // (conv_launch and chain_launch refuse it)
-  return ep;
-}
-
 // The seven pointers of one 1x1 operand of the chain kernels (conv_chain_i8.hip), as its device record ChainArgs holds them three times
 struct ChainOp {
   const int8_t* x;
@@ -271,18 +256,53 @@ int conv_pw_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
 bool conv_pwr_applies(const ConvCall& c);
 int conv_pwr_launch(const ConvCall& c);
 
+// One first-layer convolution as the host sees it: what an entry point of conv_stem_i8.hip received, once, by name.  `x` is the padded
+// NHWC4 code buffer [N][Hp][Wp][4]; ep.w_off / ep.x_off / ep.x_tap (and C, xpad with them) are the entry point's to set.
+struct StemCall {
+  const uint8_t* x;
+  const int8_t* w;
+  float* out;
+  const float* bias;
+  const int32_t* wsum;
+  const float* s_in;
+  const float* zp_in;
+  const float* s_w;
+  int64_t C, N, Hp, Wp, K, R, S;   // C: real input channels (asymmetric weights: which operand bytes count), else 4
+  int32_t stride, xpad;            // xpad: the padding the buffer carries (float activation offset only)
+  int shift;                       // 128 when the activation codes are unsigned bytes, else 0
+  hipStream_t st;
+  ConvEpi ep;
+  int32_t q_lo, q_hi, q_form;      // the quantiser's range and form as passed (stem_check validates these)
+  int64_t P, Q, M;                 // derived by stem_call: the output's height and width, N * P * Q
+};
+
+// One depthwise convolution as the host sees it (conv_dw_i8.hip's entry points; conv_dwm_i8.hip takes the same record)
+struct DwCall {
+  const void* x;
+  const int8_t* w;
+  float* out;
+  const float* bias;
+  const float* s_in;
+  const float* zp_in;
+  const float* s_w;
+  const float* w_off;
+  int64_t N, H, W, C, R, S;
+  int32_t stride, pad;
+  int x_signed;
+  hipStream_t st;
+  ConvEpi ep;                      // ep.q_form: `q_form` without the two control bits; ep.x_off / ep.x_tap: the _xoff entry point's
+  uint32_t ctl;                    // DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY as passed in `q_form`
+  int32_t q_lo, q_hi, q_form;      // as passed (dw_launch validates these)
+  int64_t P, Q;                    // derived by dw_call
+};
+
 // conv_dwm_i8.hip: depthwise 3 x 3 / stride 1 / padding 1 codes-to-codes layers on the matrix cores (diagonal weight fragments)
-bool conv_dwm_applies(int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad, const ConvEpi& ep,
-                      const float* out, const void* x);
-int conv_dwm_launch(const int8_t* x, const int8_t* w, const float* bias, const float* in_scale, const float* in_zero_point,
-                    const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int x_signed,
-                    const ConvEpi& ep, hipStream_t st);
+bool conv_dwm_applies(const DwCall& c);
+int conv_dwm_launch(const DwCall& c);
 
 // conv_stem_pool7_i8.hip: the ResNet first layer (7x7 / 2 + ReLU + 3x3 / 2 max-pool + quantiser) with the pooling in registers
-bool stem_pool7_applies(int64_t Hp, int64_t Wp, int64_t K, int64_t R, int64_t S, int32_t stride, const float* out, const void* codes);
-int stem_pool7_launch(const uint8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                      const float* in_zero_point, const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t S, int shift,
-                      const ConvEpi& ep, hipStream_t st);
+bool stem_pool7_applies(const StemCall& c);
+int stem_pool7_launch(const StemCall& c);
 
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

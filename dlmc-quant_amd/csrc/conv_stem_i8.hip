@@ -699,123 +699,6 @@ extern "C" int dlmcq_quantize_weight_stem_i8(const float* w, int8_t* wq, int32_t
   return launch_status();
 }
 
-static int stem_launch(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale,
-                       const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t C, int64_t N, int64_t Hp,
-                       int64_t Wp, int64_t K, int64_t R, int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
-                       const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
-                       dlmcq_stream_t stream, const float* x_off = nullptr, const float* x_tap = nullptr, int32_t x_pad = 0) {
-  if (N < 0 || Hp < 1 || Wp < 1 || K < 1 || R < 1 || R > ST_MAXR || S < 1 || S > 8 || stride < 1) return DLMCQ_EINVAL;
-  if (Hp < R || Wp < S || (K & 3)) return DLMCQ_EINVAL;
-  const int64_t P = (Hp - R) / stride + 1, Q = (Wp - S) / stride + 1;
-  const int64_t M = N * P * Q;
-  if (M == 0) return DLMCQ_OK;
-  if (!xpad || !w || !(out || codes) || !wsum || !in_scale || !w_scale) return DLMCQ_EINVAL;
-  if (codes && (!q_scale || q_lo > q_hi || q_lo < -128 || q_hi > 255 || q_hi - q_lo > 255 || q_form < DLMCQ_FORM_EMULATE ||
-                q_form > DLMCQ_FORM_SYMMETRIC))
-    return DLMCQ_EINVAL;
-  if (!aligned4(xpad) || !aligned16(w) || (out && !aligned16(out)) || (codes && !aligned4(codes))) return DLMCQ_EALIGN;
-  if (M >= (1ll << 31) || N * Hp * Wp >= (1ll << 31)) return DLMCQ_ERANGE;
-  StemGeom g;
-  g.N = (int)N; g.Hp = (int)Hp; g.Wp = (int)Wp; g.K = (int)K; g.R = (int)R; g.stride = stride; g.P = (int)P; g.Q = (int)Q;
-  g.S = (int)S; g.C = (int)C;
-  g.M = M;
-  g.ntiles = (int)((M + 31) / 32);
-  g.qdiv = make_fastdiv((uint32_t)Q);
-  g.pdiv = make_fastdiv((uint32_t)P);
-  g.xpad = x_pad;
-  ConvEpi ep{};
-  ep.w_off = w_offset;
-  ep.x_off = x_off;
-  ep.x_tap = x_tap;
-  ep.relu = relu == DLMCQ_ACT_RELU6 ? DLMCQ_ACT_RELU6 : (relu != 0);
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  ep.q_form = q_form;
-  const int wgs = (g.ntiles + 3) / 4;
-  const dim3 grid((uint32_t)(wgs < 2048 ? wgs : 2048), (uint32_t)((K + 63) / 64));
-  const int shift = x_is_unsigned ? 128 : 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const uint8_t* xs = static_cast<const uint8_t*>(xpad);
-#define DLMCQ_STEM_ARGS grid, dim3(256), 0, st, xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep
-#define DLMCQ_STEM_CASE(RR) \
-  case RR:                  \
-    if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<RR, true, false, R6>), DLMCQ_STEM_ARGS); \
-    else hipLaunchKernelGGL((conv_stem_i8_kernel<RR, false, false, R6>), DLMCQ_STEM_ARGS);         \
-    break;
-  // ReLU6 (DLMCQ_ACT_RELU6) selects the R6 instantiations: the same kernels with the upper bound
-  auto launch = [&](auto r6) {
-    constexpr bool R6 = decltype(r6)::value;
-    if (x_off) {       // (the entry point has checked R: 3 or 7)
-      if (R == 3) {
-        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, false, R6, true>), DLMCQ_STEM_ARGS);
-        else hipLaunchKernelGGL((conv_stem_i8_kernel<3, false, false, R6, true>), DLMCQ_STEM_ARGS);
-      } else {
-        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<7, true, false, R6, true>), DLMCQ_STEM_ARGS);
-        else hipLaunchKernelGGL((conv_stem_i8_kernel<7, false, false, R6, true>), DLMCQ_STEM_ARGS);
-      }
-      return;
-    }
-    // 3 x 3 first layers that emit only codes (RepVGG, MobileOne): the swapped epilogue
-    if (R == 3 && !out && codes && K % 64 == 0 && aligned16(codes)) {
-      if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<3, true, true, R6>), DLMCQ_STEM_ARGS);
-      else hipLaunchKernelGGL((conv_stem_i8_kernel<3, false, true, R6>), DLMCQ_STEM_ARGS);
-      return;
-    }
-    switch ((int)R) {
-      DLMCQ_STEM_CASE(1) DLMCQ_STEM_CASE(2) DLMCQ_STEM_CASE(3) DLMCQ_STEM_CASE(4) DLMCQ_STEM_CASE(5) DLMCQ_STEM_CASE(6)
-      default:
-        if (w_offset) hipLaunchKernelGGL((conv_stem_i8_kernel<7, true, false, R6>), DLMCQ_STEM_ARGS);
-        else hipLaunchKernelGGL((conv_stem_i8_kernel<7, false, false, R6>), DLMCQ_STEM_ARGS);
-        break;
-    }
-  };
-  if (ep.relu == DLMCQ_ACT_RELU6) launch(std::true_type{});
-  else launch(std::false_type{});
-#undef DLMCQ_STEM_CASE
-#undef DLMCQ_STEM_ARGS
-  return launch_status();
-}
-
-extern "C" int dlmcq_conv2d_i8_stem_fused(const void* xpad, const int8_t* w, float* out, const float* bias,
-                                          const int32_t* wsum, const float* in_scale, const float* in_zero_point,
-                                          const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
-                                          int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
-                                          const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
-                                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  return stem_launch(xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, nullptr, 4, N, Hp, Wp, K, R, S, stride,
-                     x_is_unsigned, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream);
-}
-
-extern "C" int dlmcq_conv2d_i8_stem_asym(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
-                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
-                                         const float* w_offset, int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
-                                         int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
-                                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
-                                         int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  if (!w_offset || C < 1 || C > 4) return DLMCQ_EINVAL;
-  return stem_launch(xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, w_offset, C, N, Hp, Wp, K, R, S, stride,
-                     x_is_unsigned, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream);
-}
-
-extern "C" int dlmcq_conv2d_i8_stem_xoff(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
-                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
-                                         const float* w_offset, int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
-                                         int64_t S, int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes,
-                                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
-                                         float q_ste_g, const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
-  if (!in_offset || !tap_sums || C < 1 || C > 4 || pad < 0 || 2 * (int64_t)pad >= Hp || 2 * (int64_t)pad >= Wp) return DLMCQ_EINVAL;
-  if (pad > 0 && R != 3 && R != 7) return DLMCQ_EINVAL;     // (the XOFF instantiations: 3 x 3 and 7 x 7 filters)
-  if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
-  // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
-  return stem_launch(xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, w_offset, w_offset ? C : 4, N, Hp, Wp, K, R, S, stride,
-                     x_is_unsigned, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream, pad > 0 ? in_offset : nullptr,
-                     pad > 0 ? tap_sums : nullptr, pad);
-}
-
 extern "C" int dlmcq_maxpool_codes_nhwc(const void* x, void* y, int64_t N, int64_t H, int64_t W, int64_t C, int32_t kernel,
                                         int32_t stride, int32_t pad, int32_t x_is_unsigned, dlmcq_stream_t stream) {
   if (N < 0 || H < 1 || W < 1 || C < 4 || (C & 3) || kernel < 1 || stride < 1 || pad < 0 || 2 * pad > kernel) return DLMCQ_EINVAL;
@@ -842,61 +725,172 @@ extern "C" int dlmcq_maxpool_codes_nhwc(const void* x, void* y, int64_t N, int64
   return launch_status();
 }
 
+// THE tables of the first-layer instantiations: one macro line gives a row's key and the kernel it names.
+// conv_stem_i8_kernel: R = 1 .. 7 unswapped, the swapped epilogue for R = 3, the float activation offset for R = 3 and 7 - each with
+// symmetric / asymmetric weights and ReLU / ReLU6: 28 + 4 + 8 = 40.  conv_stem_pool_i8_kernel: R = 1 .. 7.
+typedef void (*StemKernel)(const uint8_t*, const int8_t*, float*, const float*, const int32_t*, const float*, const float*, const float*, StemGeom,
+                           int, ConvEpi);
+typedef void (*StemPoolKernel)(const uint8_t*, const int8_t*, float*, const float*, const int32_t*, const float*, const float*, const float*,
+                               StemPoolGeom, int, ConvEpi);
+struct StemVariant {
+  int R;
+  bool asym, swap, r6, xoff;
+  StemKernel kernel;
+};
+struct StemPoolVariant {
+  int R;
+  StemPoolKernel kernel;
+};
+#define DLMCQ_STEM_V(R, ASYM, SWAP, R6, XOFF) {R, ASYM, SWAP, R6, XOFF, &conv_stem_i8_kernel<R, ASYM, SWAP, R6, XOFF>},
+#define DLMCQ_STEM_QUAD(R, SWAP, XOFF) \
+  DLMCQ_STEM_V(R, false, SWAP, false, XOFF) DLMCQ_STEM_V(R, true, SWAP, false, XOFF) DLMCQ_STEM_V(R, false, SWAP, true, XOFF) \
+  DLMCQ_STEM_V(R, true, SWAP, true, XOFF)
+#define DLMCQ_STEM_POOL_V(R) {R, &conv_stem_pool_i8_kernel<R>},
+static const StemVariant STEM_TABLE[] = {
+    DLMCQ_STEM_QUAD(1, false, false) DLMCQ_STEM_QUAD(2, false, false) DLMCQ_STEM_QUAD(3, false, false) DLMCQ_STEM_QUAD(4, false, false)
+    DLMCQ_STEM_QUAD(5, false, false) DLMCQ_STEM_QUAD(6, false, false) DLMCQ_STEM_QUAD(7, false, false)
+    DLMCQ_STEM_QUAD(3, true, false)                                      // codes only, K % 64 == 0
+    DLMCQ_STEM_QUAD(3, false, true) DLMCQ_STEM_QUAD(7, false, true)      // dlmcq_conv2d_i8_stem_xoff with padding
+};
+static const StemPoolVariant STEM_POOL_TABLE[] = {DLMCQ_STEM_POOL_V(1) DLMCQ_STEM_POOL_V(2) DLMCQ_STEM_POOL_V(3) DLMCQ_STEM_POOL_V(4)
+                                                  DLMCQ_STEM_POOL_V(5) DLMCQ_STEM_POOL_V(6) DLMCQ_STEM_POOL_V(7)};
+#undef DLMCQ_STEM_POOL_V
+#undef DLMCQ_STEM_QUAD
+#undef DLMCQ_STEM_V
+static_assert(sizeof(STEM_TABLE) / sizeof(STEM_TABLE[0]) == 40 && sizeof(STEM_POOL_TABLE) / sizeof(STEM_POOL_TABLE[0]) == ST_MAXR, "the instantiations");
+
+// the record of a first-layer entry point's ABI arguments; ep.w_off / ep.x_off / ep.x_tap, C and xpad are the caller's to set.  No flag
+// bit of `q_form` is taken (stem_check): the form goes into the epilogue as it came.
+static StemCall stem_call(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum, const float* in_scale,
+                          const float* in_zero_point, const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R, int64_t S,
+                          int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale, const float* q_zero_point,
+                          int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
+  StemCall c{};
+  c.x = static_cast<const uint8_t*>(xpad); c.w = w; c.out = out; c.bias = bias; c.wsum = wsum; c.s_in = in_scale; c.zp_in = in_zero_point;
+  c.s_w = w_scale;
+  c.C = 4; c.N = N; c.Hp = Hp; c.Wp = Wp; c.K = K; c.R = R; c.S = S; c.stride = stride;
+  c.shift = x_is_unsigned ? 128 : 0;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  c.ep = make_epi_form(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form;
+  c.P = (Hp - R) / (stride > 0 ? stride : 1) + 1;     // (a stride below 1 is refused by stem_check; until then it must not divide by zero)
+  c.Q = (Wp - S) / (stride > 0 ? stride : 1) + 1;
+  c.M = N * c.P * c.Q;
+  return c;
+}
+
+// Every check the four first-layer entry points share, in one order (tests/golden/dw_stem_refusals.json pins it).  DLMCQ_OK with
+// c.M == 0: an empty problem, nothing to launch.  (M < N * Hp * Wp: the second bound covers every 32-bit index of both kernels.)
+static int stem_check(const StemCall& c) {
+  if (c.N < 0 || c.Hp < 1 || c.Wp < 1 || c.K < 1 || c.R < 1 || c.R > ST_MAXR || c.S < 1 || c.S > 8 || c.stride < 1) return DLMCQ_EINVAL;
+  if (c.Hp < c.R || c.Wp < c.S || (c.K & 3)) return DLMCQ_EINVAL;
+  if (c.M == 0) return DLMCQ_OK;
+  if (!c.x || !c.w || !(c.out || c.ep.codes) || !c.wsum || !c.s_in || !c.s_w) return DLMCQ_EINVAL;
+  if (quantiser_check(c.ep.codes, c.ep.q_scale, c.q_lo, c.q_hi, c.q_form, 0) != DLMCQ_OK) return DLMCQ_EINVAL;
+  if (!aligned4(c.x) || !aligned16(c.w) || (c.out && !aligned16(c.out)) || (c.ep.codes && !aligned4(c.ep.codes))) return DLMCQ_EALIGN;
+  if (c.M >= (1ll << 31) || c.N * c.Hp * c.Wp >= (1ll << 31)) return DLMCQ_ERANGE;
+  return DLMCQ_OK;
+}
+
+static int stem_launch(const StemCall& c) {
+  const int rc = stem_check(c);
+  if (rc != DLMCQ_OK || c.M == 0) return rc;
+  StemGeom g;
+  g.N = (int)c.N; g.Hp = (int)c.Hp; g.Wp = (int)c.Wp; g.K = (int)c.K; g.R = (int)c.R; g.stride = c.stride; g.P = (int)c.P; g.Q = (int)c.Q;
+  g.S = (int)c.S; g.C = (int)c.C;
+  g.M = c.M;
+  g.ntiles = (int)((c.M + 31) / 32);
+  g.qdiv = make_fastdiv((uint32_t)c.Q);
+  g.pdiv = make_fastdiv((uint32_t)c.P);
+  g.xpad = c.xpad;
+  // the key: a float offset (the entry point has checked R: 3 or 7) has the unswapped epilogue; 3 x 3 first layers that emit only codes
+  // (RepVGG, MobileOne) the swapped one
+  const bool xoff = c.ep.x_off != nullptr;
+  const bool swap = !xoff && c.R == 3 && !c.out && c.ep.codes && c.K % 64 == 0 && aligned16(c.ep.codes);
+  const bool asym = c.ep.w_off != nullptr, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
+  const StemVariant* v = nullptr;
+  for (const StemVariant& t : STEM_TABLE)
+    if (t.R == c.R && t.asym == asym && t.swap == swap && t.r6 == r6 && t.xoff == xoff) v = &t;
+  if (!v) return DLMCQ_EINVAL;
+  const int wgs = (g.ntiles + 3) / 4;
+  const dim3 grid((uint32_t)(wgs < 2048 ? wgs : 2048), (uint32_t)((c.K + 63) / 64));
+  hipLaunchKernelGGL(v->kernel, grid, dim3(256), 0, c.st, c.x, c.w, c.out, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep);
+  return launch_status();
+}
+
+#define DLMCQ_STEM_ABI xpad, w, out, bias, wsum, in_scale, in_zero_point, w_scale, N, Hp, Wp, K, R, S, stride, x_is_unsigned, relu, codes, q_scale, \
+                       q_zero_point, q_lo, q_hi, q_form, q_ste_g, stream
+
+extern "C" int dlmcq_conv2d_i8_stem_fused(const void* xpad, const int8_t* w, float* out, const float* bias,
+                                          const int32_t* wsum, const float* in_scale, const float* in_zero_point,
+                                          const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
+                                          int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
+                                          const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
+  return stem_launch(stem_call(DLMCQ_STEM_ABI));
+}
+
+extern "C" int dlmcq_conv2d_i8_stem_asym(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                         const float* w_offset, int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
+                                         int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
+                                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                                         int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
+  if (!w_offset || C < 1 || C > 4) return DLMCQ_EINVAL;
+  StemCall c = stem_call(DLMCQ_STEM_ABI);
+  c.ep.w_off = w_offset;
+  c.C = C;
+  return stem_launch(c);
+}
+
+extern "C" int dlmcq_conv2d_i8_stem_xoff(const void* xpad, const int8_t* w, float* out, const float* bias, const int32_t* wsum,
+                                         const float* in_scale, const float* in_zero_point, const float* w_scale,
+                                         const float* w_offset, int64_t C, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
+                                         int64_t S, int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes,
+                                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                                         float q_ste_g, const float* in_offset, const float* tap_sums, dlmcq_stream_t stream) {
+  if (!in_offset || !tap_sums || C < 1 || C > 4 || pad < 0 || 2 * (int64_t)pad >= Hp || 2 * (int64_t)pad >= Wp) return DLMCQ_EINVAL;
+  if (pad > 0 && R != 3 && R != 7) return DLMCQ_EINVAL;     // (the XOFF instantiations: 3 x 3 and 7 x 7 filters)
+  if (!aligned16(tap_sums)) return DLMCQ_EALIGN;
+  StemCall c = stem_call(DLMCQ_STEM_ABI);
+  c.ep.w_off = w_offset;
+  if (w_offset) c.C = C;
+  if (pad > 0) {     // (unpadded: no tap is ever out of bounds - the folded bias is the whole term)
+    c.ep.x_off = in_offset;
+    c.ep.x_tap = tap_sums;
+  }
+  c.xpad = pad;
+  return stem_launch(c);
+}
+
 extern "C" int dlmcq_conv2d_i8_stem_pool_fused(const void* xpad, const int8_t* w, float* out, const float* bias,
                                                const int32_t* wsum, const float* in_scale, const float* in_zero_point,
                                                const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t K, int64_t R,
                                                int64_t S, int32_t stride, int32_t x_is_unsigned, int32_t relu, void* codes,
                                                const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                                int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  if (relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
-  if (N < 0 || Hp < 1 || Wp < 1 || K < 4 || K > 64 || (K & 3) || R < 1 || R > ST_MAXR || S < 1 || S > 8 || stride < 1)
-    return DLMCQ_EINVAL;
-  if (Hp < R || Wp < S) return DLMCQ_EINVAL;
-  const int64_t P = (Hp - R) / stride + 1, Q = (Wp - S) / stride + 1;
-  const int64_t PP = (P + 2 - 3) / 2 + 1, QP = (Q + 2 - 3) / 2 + 1;     // MaxPool2d(3, 2, 1), floor mode
-  if (PP < 1 || QP < 1) return DLMCQ_EINVAL;
-  if (N == 0) return DLMCQ_OK;
-  if (!xpad || !w || !(out || codes) || !wsum || !in_scale || !w_scale) return DLMCQ_EINVAL;
-  if (codes && (!q_scale || q_lo > q_hi || q_lo < -128 || q_hi > 255 || q_hi - q_lo > 255 || q_form < DLMCQ_FORM_EMULATE ||
-                q_form > DLMCQ_FORM_SYMMETRIC))
-    return DLMCQ_EINVAL;
-  if (!aligned4(xpad) || !aligned16(w) || (out && !aligned16(out)) || (codes && !aligned4(codes))) return DLMCQ_EALIGN;
+  if (relu == DLMCQ_ACT_RELU6 || K > 64) return DLMCQ_EINVAL;     // (ReLU only; one 64-channel slab)
+  const StemCall c = stem_call(DLMCQ_STEM_ABI);
+  const int rc = stem_check(c);
+  if (rc != DLMCQ_OK || c.M == 0) return rc;
+  // the ResNet shape (7 rows, stride 2, 64 channels, codes only): pooling in registers (conv_stem_pool7_i8.hip)
+  if (stem_pool7_applies(c) && aligned16(c.ep.codes) && aligned16(c.x)) return stem_pool7_launch(c);
   StemPoolGeom g;
-  g.N = (int)N; g.Hp = (int)Hp; g.Wp = (int)Wp; g.K = (int)K; g.stride = stride; g.P = (int)P; g.Q = (int)Q;
-  g.PP = (int)PP; g.QP = (int)QP;
-  g.tiles_h = (int)((PP + SP_TH - 1) / SP_TH);
-  g.tiles_w = (int)((QP + SP_TW - 1) / SP_TW);
-  const int64_t wgs = N * g.tiles_h * g.tiles_w;
-  if (wgs >= (1ll << 31) || N * Hp * Wp >= (1ll << 31)) return DLMCQ_ERANGE;
+  g.N = (int)c.N; g.Hp = (int)c.Hp; g.Wp = (int)c.Wp; g.K = (int)c.K; g.stride = stride; g.P = (int)c.P; g.Q = (int)c.Q;
+  g.PP = (int)((c.P + 2 - 3) / 2 + 1);     // MaxPool2d(3, 2, 1), floor mode
+  g.QP = (int)((c.Q + 2 - 3) / 2 + 1);
+  g.tiles_h = (g.PP + SP_TH - 1) / SP_TH;
+  g.tiles_w = (g.QP + SP_TW - 1) / SP_TW;
+  const int64_t wgs = c.N * g.tiles_h * g.tiles_w;       // (< N * Hp * Wp < 2^31: stem_check)
   g.twdiv = make_fastdiv((uint32_t)g.tiles_w);
   g.thdiv = make_fastdiv((uint32_t)g.tiles_h);
   g.nwork = (uint32_t)wgs;
-  ConvEpi ep{};
-  ep.relu = relu != 0;
-  ep.codes = static_cast<uint8_t*>(codes);
-  ep.q_scale = q_scale;
-  ep.q_zp = q_zero_point;
-  ep.q_lo = (float)q_lo;
-  ep.q_hi = (float)q_hi;
-  ep.q_g = q_ste_g;
-  ep.q_form = q_form;
-  const int shift = x_is_unsigned ? 128 : 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const uint8_t* xs = static_cast<const uint8_t*>(xpad);
-  // the ResNet shape (7 rows, stride 2, 64 channels, codes only): pooling in registers (conv_stem_pool7_i8.hip)
-  if (stem_pool7_applies(Hp, Wp, K, R, S, stride, out, codes) && aligned16(codes) && aligned16(xpad))
-    return stem_pool7_launch(xs, w, bias, wsum, in_scale, in_zero_point, w_scale, N, Hp, Wp, S, shift, ep, st);
-#define DLMCQ_SP_ARGS dim3((uint32_t)(wgs < 1024 ? wgs : 1024)), dim3(256), 0, st, xs, w, out, bias, wsum, in_scale, in_zero_point, w_scale, g, shift, ep
-  switch ((int)R) {
-    case 1: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<1>), DLMCQ_SP_ARGS); break;
-    case 2: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<2>), DLMCQ_SP_ARGS); break;
-    case 3: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<3>), DLMCQ_SP_ARGS); break;
-    case 4: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<4>), DLMCQ_SP_ARGS); break;
-    case 5: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<5>), DLMCQ_SP_ARGS); break;
-    case 6: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<6>), DLMCQ_SP_ARGS); break;
-    default: hipLaunchKernelGGL((conv_stem_pool_i8_kernel<7>), DLMCQ_SP_ARGS); break;
-  }
-#undef DLMCQ_SP_ARGS
+  const StemPoolVariant* v = nullptr;
+  for (const StemPoolVariant& t : STEM_POOL_TABLE)
+    if (t.R == c.R) v = &t;
+  if (!v) return DLMCQ_EINVAL;
+  hipLaunchKernelGGL(v->kernel, dim3((uint32_t)(wgs < 1024 ? wgs : 1024)), dim3(256), 0, c.st, c.x, c.w, c.out, c.bias,
+                     c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep);
   return launch_status();
 }
-
+#undef DLMCQ_STEM_ABI

@@ -347,40 +347,36 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool7_i8_kernel(const uint8_
 }
 
 // Whether the in-register pooling kernel takes this first layer, and the launch (conv_stem_i8.hip asks).
-bool stem_pool7_applies(int64_t Hp, int64_t Wp, int64_t K, int64_t R, int64_t S, int32_t stride, const float* out, const void* codes) {
-  if (R != 7 || S > 8 || stride != 2 || K != 64 || out || !codes) return false;
-  const int64_t P = (Hp - R) / stride + 1, Q = (Wp - S) / stride + 1;
-  if ((P & 1) || (Q & 1) || P < 2 || Q < 2) return false;            // every pooled pixel's window ends inside the convolution output
+bool stem_pool7_applies(const StemCall& c) {
+  if (c.R != 7 || c.S > 8 || c.stride != 2 || c.K != 64 || c.out || !c.ep.codes) return false;
+  if ((c.P & 1) || (c.Q & 1) || c.P < 2 || c.Q < 2) return false;    // every pooled pixel's window ends inside the convolution output
   return true;
 }
 
-int stem_pool7_launch(const uint8_t* x, const int8_t* w, const float* bias, const int32_t* wsum, const float* in_scale,
-                      const float* in_zero_point, const float* w_scale, int64_t N, int64_t Hp, int64_t Wp, int64_t S, int shift,
-                      const ConvEpi& ep, hipStream_t st) {
+int stem_pool7_launch(const StemCall& c) {
   Pool7Geom g;
-  g.N = (int)N; g.Hp = (int)Hp; g.Wp = (int)Wp;
-  g.P = (int)((Hp - 7) / 2 + 1);
-  g.Q = (int)((Wp - S) / 2 + 1);
+  g.N = (int)c.N; g.Hp = (int)c.Hp; g.Wp = (int)c.Wp;
+  g.P = (int)c.P;
+  g.Q = (int)c.Q;
   g.PP = g.P / 2;                                                    // MaxPool2d(3, 2, 1) on an even size
   g.QP = g.Q / 2;
   g.xtiles = (g.QP + 30) / 31;
   g.rows_per_band = 14;
   g.bands = (g.PP + g.rows_per_band - 1) / g.rows_per_band;
-  const int64_t tasks = N * g.bands * g.xtiles;
-  if (tasks >= (1ll << 31) || N * Hp * Wp * 4 >= (1ll << 40)) return DLMCQ_ERANGE;
+  const int64_t tasks = c.N * g.bands * g.xtiles;
+  if (tasks >= (1ll << 31) || c.N * c.Hp * c.Wp * 4 >= (1ll << 40)) return DLMCQ_ERANGE;
   g.ntasks = (uint32_t)tasks;
   g.xtdiv = make_fastdiv((uint32_t)g.xtiles);
   g.bdiv = make_fastdiv((uint32_t)g.bands);
-  g.xbytes = N * Hp * Wp * 4;
+  g.xbytes = c.N * c.Hp * c.Wp * 4;
 #ifdef DLMCQ_LAB
 #define P7_LAB_ARG , Pool7Img{}
 #else
 #define P7_LAB_ARG
 #endif
-  if (shift) hipLaunchKernelGGL(conv_stem_pool7_i8_kernel<true>, dim3((uint32_t)((tasks + 3) / 4)), dim3(256), 0, st, x, w, bias, wsum, in_scale,
-                                in_zero_point, w_scale, g, shift, ep P7_LAB_ARG);
-  else hipLaunchKernelGGL(conv_stem_pool7_i8_kernel<false>, dim3((uint32_t)((tasks + 3) / 4)), dim3(256), 0, st, x, w, bias, wsum, in_scale,
-                          in_zero_point, w_scale, g, shift, ep P7_LAB_ARG);
+  auto kernel = c.shift ? conv_stem_pool7_i8_kernel<true> : conv_stem_pool7_i8_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)((tasks + 3) / 4)), dim3(256), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift,
+                     c.ep P7_LAB_ARG);
   return launch_status();
 }
 
