@@ -34,7 +34,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -930,6 +930,41 @@ def _avgpool_window(node, modules):
     return x, k
 
 
+def _code_readers(planned, t):
+    """Who takes fp32 node `t` as codes from a stand-alone quantising node (the average-pool and gate passes): "gemm" plan convolutions
+    that read it through their activation argument - as their own node or as an operand of a dual node - with input channels % 4 == 0,
+    all sharing one activation quantiser and one channel count.  Returns (that quantiser, the takers, whether anyone else reads `t` as
+    fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or they disagree."""
+    def reader(u):
+        """(activation spec, convolution) with which plan node `u` reads `t` as codes, else None."""
+        d = planned.get(u)
+        if d is None or d.spec.kind != "gemm":
+            return None
+        if d.dual:
+            ops = [(d.dual_inputs[i], (d.mod, d.dual_mod)[i]) for i in (0, 1) if u.args[i] is t]
+            if not ops or len({a.key for a, _ in ops}) != 1:
+                return None
+        elif u.args[0] is t and t not in u.args[1:]:
+            ops = [(d.spec.act, d.mod)]
+        else:
+            return None
+        a, m = ops[0]
+        return (a, m) if m.weight.dim() == 4 and m.groups == 1 and all(mm.weight.shape[1] == m.weight.shape[1] for _, mm in ops) else None
+
+    readers = {u: reader(u) for u in t.users}
+    takers = [u for u, r in readers.items() if r is not None]
+    if not takers or len({readers[u][0].key for u in takers}) != 1:      # (the max-pool rule: one quantiser for all code readers)
+        return None
+    emit, conv = readers[takers[0]]
+    c = int(conv.weight.shape[1])
+    if c % 4 or c < 4 or any(int(readers[u][1].weight.shape[1]) != c for u in takers):
+        return None
+    # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (a dual node
+    # is never handed shifted codes by the main pass either)
+    shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers])
+    return emit, takers, len(takers) != len(readers), c, _ceil64(c), _zp_fill(emit) - (128 if shift else 0), shift
+
+
 def _avgpool_pass(gm, report, planned, dry_run):
     """Windowed average pools (fuse_inference(avg_pools=True)): `AvgPool2d(s, s) -> plan convolution` becomes a node that hands the
     convolution its activation codes (AvgPoolLayer).  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for
@@ -937,48 +972,119 @@ def _avgpool_pass(gm, report, planned, dry_run):
     graph = gm.graph
     modules = dict(gm.named_modules())
     count = 0
-
-    def reader(u, pool):
-        """(activation spec, convolution) with which plan node `u` reads `pool` as codes, else None."""
-        d = planned.get(u)
-        if d is None or d.spec.kind != "gemm":
-            return None
-        if d.dual:
-            ops = [(d.dual_inputs[i], (d.mod, d.dual_mod)[i]) for i in (0, 1) if u.args[i] is pool]
-            if not ops or len({a.key for a, _ in ops}) != 1:
-                return None
-        elif u.args[0] is pool and pool not in u.args[1:]:
-            ops = [(d.spec.act, d.mod)]
-        else:
-            return None
-        a, m = ops[0]
-        return (a, m) if m.weight.dim() == 4 and m.groups == 1 and all(mm.weight.shape[1] == m.weight.shape[1] for _, mm in ops) else None
-
     for pool in list(graph.nodes):
         win = _avgpool_window(pool, modules)
         if win is None:
             continue
         x, s = win
-        readers = {u: reader(u, pool) for u in pool.users}
-        takers = [u for u, r in readers.items() if r is not None]
-        if not takers or len({readers[u][0].key for u in takers}) != 1:      # (the max-pool rule: one quantiser for all code readers)
+        taken = _code_readers(planned, pool)
+        if taken is None:
             continue
-        emit, conv = readers[takers[0]]
-        c = int(conv.weight.shape[1])
-        if c % 4 or c < 4 or any(int(readers[u][1].weight.shape[1]) != c for u in takers):
-            continue
-        c_pad = _ceil64(c)
-        # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (a dual node
-        # is never handed shifted codes by the main pass either)
-        shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers])
-        want_out = len(takers) != len(readers)
-        module = _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, _zp_fill(emit) - (128 if shift else 0), shift)
+        emit, takers, want_out, c, c_pad, pad_code, shift = taken
+        module = _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, pad_code, shift)
         _, outs = _call_plan_module(gm, pool, f"_int8_avgpool_{count}", module, (x,))
         count += 1
         for u in list(pool.users):
             u.replace_input_with(pool, outs[1] if u in takers else outs[0])
         graph.erase_node(pool)
     report.avg_pools = count
+    _settle(gm, count)
+
+
+class GateLayer(nn.Module):
+    """A squeeze-excite channel gate `x * g` (x fp32 (N, C, H, W), g (N, C, 1, 1)) (+ ReLU / ReLU6) straight to the activation codes of
+    the plan layers that read the gated map (csrc/gate.hip): the multiply, the activation, the gated fp32 tensor and the consumer's
+    quantise pass as one read of the map.  `emit`: the readers' activation quantiser (_ActSpec); `act`: DLMCQ_ACT_*; the code rows are
+    `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32 tensor.  A `g`
+    of any other shape at run time (a per-tensor or spatial gate the trace could not tell apart) is multiplied, activated and quantised
+    with torch and K.fake_quant: the values of the unfused graph.  Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, emit, want_out, act, c, c_pad, pad_code, shift=False):
+        super().__init__()
+        self.emit, self.want_out, self.act = emit, bool(want_out), int(act)
+        self.c, self.c_pad, self.pad_code, self.emit_shift = int(c), int(c_pad), int(pad_code), bool(shift)
+
+    def forward(self, x, g):
+        if x.dim() != 4 or x.dtype != torch.float32 or g.dtype != torch.float32 or tuple(g.shape) != (x.shape[0], x.shape[1], 1, 1) or x.shape[1] != self.c:
+            return self._unfused(x, g)
+        e = self.emit.emit(x.numel())       # (a QBase consumer's g: over its real input, the gated tensor)
+        e.shift128 = self.emit_shift
+        return K.gate_quant(x, g, act=self.act, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+
+    def _unfused(self, x, g):
+        v = x * g
+        v = F.relu6(v) if self.act == N.ACT_RELU6 else (torch.relu(v) if self.act == N.ACT_RELU else v)
+        a = self.emit
+        t = v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.contiguous()
+        codes = K.fake_quant(t, a.scale, a.zp, a.lo, a.hi, a.form, g=a.g(v.numel()), codes="i8", want_y=False)[1]
+        if self.emit_shift:
+            codes = (codes.view(torch.uint8) ^ 0x80).view(torch.int8)
+        if codes.dim() == 4 and codes.shape[1] < self.c_pad:
+            codes = _pad_channels(codes, self.c_pad, self.pad_code)
+        return (v if self.want_out else None), codes
+
+
+_MUL_FNS = (operator.mul, torch.mul)
+
+
+def _is_mul(node):
+    """An out-of-place multiply of two graph values: `a * b`, torch.mul(a, b), a.mul(b)."""
+    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, fx.Node) for a in node.args):
+        return False
+    return (node.op == "call_function" and node.target in _MUL_FNS) or (node.op == "call_method" and node.target == "mul")
+
+
+def _squeezed_from(g, modules, limit=16):
+    """The input of the global average pool (a spelling _pool_dims knows) that `g` derives from, walking back through first arguments
+    only (a multiply on the way - a swish - through either operand), at most `limit` nodes; None if none is reached."""
+    stack, seen = [g], 0
+    while stack and seen < limit:
+        n = stack.pop()
+        seen += 1
+        if _pool_dims(n, modules) is not None:
+            src = n.args[0] if n.args else n.kwargs.get("input")
+            return src if isinstance(src, fx.Node) else None
+        if n.op not in ("call_function", "call_method", "call_module") or not n.args:
+            continue
+        nxt = list(n.args) if _is_mul(n) else [n.args[0]]
+        stack.extend(a for a in reversed(nxt) if isinstance(a, fx.Node))
+    return None
+
+
+def _gate_pass(gm, report, planned, dry_run, relu6):
+    """Squeeze-excite gates (fuse_inference(gates=True)): `x * gate(pool(x))` (+ ReLU / ReLU6) `-> plan convolution` becomes a node
+    that hands the convolution its activation codes (GateLayer).  The squeeze path - pool, two small layers, the gate function - stays
+    as it is.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for the convolution behind the
+    gate stays - only its input changes, from fp32 to codes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+    for mul in list(graph.nodes):
+        if not _is_mul(mul) or mul.args[0] is mul.args[1]:
+            continue
+        a, b = mul.args
+        # exactly one operand derives from a global average pool, and that pool reads the other operand
+        gated = [(x, g) for x, g in ((a, b), (b, a)) if _squeezed_from(g, modules) is x]
+        if len(gated) != 1:
+            continue
+        x, g = gated[0]
+        act, last = N.ACT_NONE, mul
+        nxt = _sole_user(mul)
+        if nxt is not None and (_is_relu(nxt, modules) or (relu6 and _is_relu6(nxt, modules))):
+            act, last = (N.ACT_RELU if _is_relu(nxt, modules) else N.ACT_RELU6), nxt
+        taken = _code_readers(planned, last)
+        if taken is None:
+            continue
+        emit, takers, want_out, c, c_pad, pad_code, shift = taken
+        module = _DryNode() if dry_run else GateLayer(emit, want_out, act, c, c_pad, pad_code, shift)
+        _, outs = _call_plan_module(gm, last, f"_int8_gate_{count}", module, (x, g))
+        count += 1
+        for u in list(last.users):
+            u.replace_input_with(last, outs[1] if u in takers else outs[0])
+        if last is not mul:
+            graph.erase_node(last)
+        graph.erase_node(mul)
+    report.gates = count
     _settle(gm, count)
 
 
@@ -1206,6 +1312,7 @@ class FusionReport:
         self.narrow = 0       # channel-padded layers reading / writing their fp32 tensors at the real width (fuse_inference(narrow_rows=True))
         self.pad_shortcuts = 0   # option-A shortcuts (subsample + zero-pad) read in place by the layer's epilogue (fuse_inference(pad_shortcuts=True))
         self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
+        self.gates = 0        # squeeze-excite gates (x * g, + ReLU / ReLU6) handing the plan layers behind them their codes (fuse_inference(gates=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -1233,6 +1340,7 @@ class FusionReport:
                 (f"narrow fp32 rows={self.narrow}, " if self.narrow else "") +
                 (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
+                (f"gates on the plan={self.gates}, " if self.gates else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1771,7 +1879,7 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None):
+                   recompute_shortcuts=None, gates=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1850,7 +1958,26 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     (tests/test_gpu_avgpool.py: torch.equal against F.avg_pool2d on the device and between the two plans' logits).  Measured (tools/avgpool_shortcut_ab.py,
     profiles/avgpool_shortcut_ab.json; ResNet-20 / -56, options C / D, FSPTQ and QBase, batch 512 at 32^2, interleaved): flag off / flag on =
     0.976 ... 1.103 in ms per step, no case slower beyond the run-to-run spread.
-    Off by default: the plan without it is the plan as it was."""
+    Off by default: the plan without it is the plan as it was.
+    `gates=True`: a squeeze-excite channel gate `x * gate(squeeze(x))` in front of plan convolutions - EfficientNet's
+    MBConv, GhostNet, MobileNetV3, RepVGG-SE (`workloads.mobilenet_v2(se=True)`) - becomes a plan node (GateLayer, csrc/gate.hip) that
+    multiplies the fp32 map by its (N, C, 1, 1) gate, applies the ReLU / ReLU6 behind the multiply and hands those convolutions their
+    activation codes in one pass; the gated fp32 tensor, the activation and the consumer's quantise pass leave the step
+    (`fusion_report.gates` counts the nodes).  The squeeze path - pool, two small layers, gate function - stays as it is.  Taken:
+    `a * b`, torch.mul(a, b), a.mul(b) of two graph values where exactly one operand derives, through first arguments only (either
+    operand of a multiply on the way; at most 16 nodes back), from a global average pool in a spelling the head pass knows
+    (nn.AdaptiveAvgPool2d(1), F.adaptive_avg_pool2d(x, 1), x.mean((2, 3))) and that pool reads the other operand; a ReLU, or a ReLU6
+    under `relu6`, that is the multiply's only reader is absorbed; the readers follow the average-pool rule ("gemm" plan convolutions
+    through their activation argument, input channels a multiple of 4, one quantiser and one channel count; padded, shifted and
+    g-scaled as there; other readers get the fp32 map from the same launch).  Left as they are: a gate that does not derive from a pool
+    of x, F.avg_pool2d(x, x.size(3)), spatial gates, in-place mul_, readers of different quantisers, depthwise or first-layer readers.
+    A gate that at run time is not (N, C, 1, 1) is multiplied, activated and quantised by torch and K.fake_quant inside the node - the
+    unfused graph's values.  One IEEE multiply rounded to fp32, then the device's own ReLU (clamp_min: NaN passes, -0 becomes +0): the
+    plan is bit-identical to the plan without the flag (tests/test_gpu_gate.py: fp32 bits and codes against torch on the device,
+    torch.equal between the two plans' logits).  Measured (tools/gate_ab.py, profiles/gate_ab.json; MobileNetV2-SE, 17 gates, batch 1024
+    at 224^2, interleaved): flag off / flag on = 40.23 / 32.58 ms per step (FSPTQ W8A8) and 40.51 / 32.87 (QBase W8A8), ratio 1.23 at
+    a run-to-run spread of 0.19 ms; the gate kernel moves 4.4 TB/s over its 17 launches (the average-pool kernel's launch-bound nodes:
+    0.9 - 2.6 TB/s).  No case slower.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -1869,6 +1996,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             node.replace_all_uses_with(node.args[0])
             graph.erase_node(node)
     planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts).run(report)
+    if gates:           # (first: the squeeze's global pool is a plain node still, and so are the nodes behind the gate)
+        _gate_pass(gm, report, planned, dry_run, relu6)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
         _avgpool_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)

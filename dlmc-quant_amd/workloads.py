@@ -209,16 +209,48 @@ def _conv_bn_relu6(cin, cout, k, stride=1, groups=1):
                          nn.ReLU6(inplace=True))
 
 
+class SqueezeExcite(nn.Module):
+    """A squeeze-and-excitation block (public architecture, Hu et al. 2018): x * gate(squeeze(x)), the gate one value per image and
+    channel.  `squeeze="linear"`: global average pool, flatten, Linear(c, reduced), swish, Linear(reduced, c), back to (N, C, 1, 1) -
+    EfficientNet's spelling (efficientnet_block.py:44-59); `squeeze="conv"`: the pool kept (N, C, 1, 1), two 1x1 convolutions with a ReLU
+    between them - GhostNet's and MobileNetV3's (ghostnet.py:44-61).  `gate`: "sigmoid", or "hardsigmoid" = relu6(v + 3) / 6."""
+
+    def __init__(self, c, reduced, gate="sigmoid", squeeze="linear"):
+        super().__init__()
+        if gate not in ("sigmoid", "hardsigmoid") or squeeze not in ("linear", "conv"):
+            raise ValueError(f"SqueezeExcite: gate 'sigmoid' or 'hardsigmoid', squeeze 'linear' or 'conv', not {gate!r} / {squeeze!r}")
+        self.gate, self.squeeze = gate, squeeze
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        if squeeze == "linear":
+            self.reduce, self.expand = nn.Linear(c, reduced), nn.Linear(reduced, c)
+        else:
+            self.reduce, self.expand = nn.Conv2d(c, reduced, 1, bias=True), nn.Conv2d(reduced, c, 1, bias=True)
+
+    def forward(self, x):
+        v = self.pool(x)
+        if self.squeeze == "linear":
+            v = self.reduce(v.view(x.size(0), -1))
+            v = self.expand(v * torch.sigmoid(v)).view(x.size(0), x.size(1), 1, 1)
+        else:
+            v = self.expand(F.relu(self.reduce(v)))
+        return x * (torch.sigmoid(v) if self.gate == "sigmoid" else F.relu6(v + 3.) / 6.)
+
+
 class InvertedResidual(nn.Module):
     """MobileNetV2's unit: 1x1 expansion (t > 1) + depthwise 3x3 + linear 1x1 projection, BN after every convolution, ReLU6 after
-    the first two; the identity shortcut where stride is 1 and the width is kept."""
+    the first two; the identity shortcut where stride is 1 and the width is kept.  `se=True`: a squeeze-excite gate (MobileNetV3's:
+    1x1 convolutions, a quarter of the expanded width rounded up to a multiple of 8, hard sigmoid) between the depthwise and the
+    projection layer."""
 
-    def __init__(self, cin, cout, stride, t):
+    def __init__(self, cin, cout, stride, t, se=False):
         super().__init__()
         hidden = cin * t
         self.use_res = stride == 1 and cin == cout
         layers = [_conv_bn_relu6(cin, hidden, 1)] if t != 1 else []
-        layers += [_conv_bn_relu6(hidden, hidden, 3, stride, groups=hidden), nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
+        layers += [_conv_bn_relu6(hidden, hidden, 3, stride, groups=hidden)]
+        if se:
+            layers += [SqueezeExcite(hidden, (hidden // 4 + 7) // 8 * 8, gate="hardsigmoid", squeeze="conv")]
+        layers += [nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
         self.conv = nn.Sequential(*layers)
 
     def forward(self, x):
@@ -231,13 +263,13 @@ class MobileNetV2(nn.Module):
 
     SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))   # t, c, n, s
 
-    def __init__(self, num_classes=1000, dropout=0.2):
+    def __init__(self, num_classes=1000, dropout=0.2, se=False):
         super().__init__()
         cin = 32
         feats = [_conv_bn_relu6(3, cin, 3, stride=2)]
         for t, c, n, s in self.SETTINGS:
             for j in range(n):
-                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t))
+                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t, se))
                 cin = c
         feats.append(_conv_bn_relu6(cin, 1280, 1))
         self.features = nn.Sequential(*feats)
@@ -306,8 +338,9 @@ def mobileone_s1_deploy(num_classes=1000):
     return MobileOneDeploy(num_classes=num_classes)
 
 
-def mobilenet_v2(num_classes=1000):
-    return MobileNetV2(num_classes=num_classes)
+def mobilenet_v2(num_classes=1000, se=False):
+    """MobileNetV2; `se=True`: with a squeeze-excite gate in every inverted-residual block (17 gates; the default network is unchanged)."""
+    return MobileNetV2(num_classes=num_classes, se=se)
 
 
 def _named_option(option):

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Squeeze-excite gates on the int8 plan (fuse_inference(gates=True): the `x * gate` between every block's depthwise and projection
+layer handing the projection its activation codes - csrc/gate.hip - instead of an fp32 tensor the projection quantises itself) against
+the plan without `gates`: both plans built from ONE calibrated model and timed interleaved in one process.
+  cases: MobileNetV2-SE (workloads.mobilenet_v2(se=True): 17 gates) at 224^2, FSPTQ W8A8 (zero points set to exactly 0 after
+         calibration, as the tests do: every tensor a planned layer reads is a ReLU / ReLU6 output, a gated one or their pool) and
+         QBase W8A8.
+Per case: median / min / max ms per step of either plan, whether the flag-on plan is slower by more than the run-to-run spread, whether
+the logits are equal, and per gate node the kernel's time and achieved bytes per second (per pixel: 4 C read, 4 C written if the fp32
+tensor is wanted, c_pad code bytes written; the N x C gate once).  Writes profiles/gate_ab.json (and prints it).
+usage: python tools/gate_ab.py [batch] [rounds]"""
+import copy
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
+import torch  # noqa: E402
+
+import workloads as W  # noqa: E402
+from act_offset_ab import QBASE_W8A8  # noqa: E402
+from dlmc.quantization.scalar.FSPTQuant import FSPTQBase  # noqa: E402
+from dlmc.quantization.scalar.modules.base import QBase  # noqa: E402
+from dlmc.utils.fuse import GateLayer, fuse_inference  # noqa: E402
+from dlmc.utils.merge_bn import merge_bn  # noqa: E402
+from dlmc.utils.quantize import quantize_model  # noqa: E402
+from relu6_ab import QCFG as FSPTQ_W8A8, timed  # noqa: E402
+
+CASES = [("mobilenet_v2_se_fsptq_w8a8", "fsptq"), ("mobilenet_v2_se_qbase_w8a8", "qbase")]
+
+
+def gate_kernel_times(plan, x, reps=20):
+    """Per GateLayer node: its inputs as the plan hands them over, then the node alone, `reps` launches between two events."""
+    seen, hooks, rows = {}, [], []
+    for name, m in plan.named_modules():
+        if isinstance(m, GateLayer):
+            hooks.append(m.register_forward_pre_hook(lambda mod, a, name=name: seen.__setitem__(name, a)))
+    plan(x)
+    for h in hooks:
+        h.remove()
+    mods = dict(plan.named_modules())
+    for name, (t, g) in seen.items():
+        m = mods[name]
+        run = lambda t, m=m, g=g: m(t, g)  # noqa: E731
+        for _ in range(3):
+            run(t)
+        ms = timed(run, t, reps)
+        n, c, h, w = t.shape
+        nbytes = n * h * w * (c * (4 + 4 * m.want_out) + m.c_pad) + n * c * 4
+        rows.append({"node": name, "input": [n, c, h, w], "floats_per_input_pixel": int(t.stride(3)), "c_pad": m.c_pad, "act": m.act,
+                     "fp32_written": m.want_out, "us": round(ms * 1e3, 2), "bytes": nbytes, "gb_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1)})
+    return rows
+
+
+def main():
+    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
+    dev = "cuda:0"
+    out = {"model": "mobilenet_v2(se=True)", "batch": batch, "rounds": rounds, "steps_per_round": 3, "resolution": 224}
+    for tag, fam in CASES:
+        torch.manual_seed(2333)
+        model = merge_bn(W.mobilenet_v2(se=True).to(dev).eval(), inplace=True, allow_missing=True)
+        if fam == "fsptq":
+            quantize_model(model, copy.deepcopy(FSPTQ_W8A8), None, "FSPTQ", int8_gemm=True)
+        else:
+            quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
+        x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
+        with torch.no_grad():
+            model(x[:64])                                   # calibrate
+            for m in model.modules():
+                if isinstance(m, FSPTQBase):
+                    m.in_offset.zero_()
+                    m._zp_is_int = None
+                elif isinstance(m, QBase) and m.in_offset is not None:
+                    m.in_offset.zero_()
+            plans = {"gates": fuse_inference(model, gates=True), "flag_off": fuse_inference(model)}
+            logits = {k: p(x) for k, p in plans.items()}
+            kernels = gate_kernel_times(plans["gates"], x)
+            for p in plans.values():                        # warm-up
+                timed(p, x, 2)
+            ms = {k: [] for k in plans}
+            for _ in range(rounds):                         # interleaved: A, B, A, B, ...
+                for k, p in plans.items():
+                    ms[k].append(timed(p, x, 3))
+        total = sum(r["bytes"] for r in kernels)
+        us = sum(r["us"] for r in kernels)
+        res = {"logits_equal": bool(torch.equal(logits["gates"], logits["flag_off"])), "gate_kernels": kernels,
+               "gate_kernels_total": {"us": round(us, 1), "bytes": total, "gb_per_s": round(total / (us * 1e-6) / 1e9, 1)}}
+        for k, v in ms.items():
+            rep = plans[k].fusion_report
+            res[k] = {"ms_per_step_median": round(sorted(v)[len(v) // 2], 3), "ms_per_step_min": round(min(v), 3),
+                      "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v], "int8_layers": rep.layers,
+                      "gates": rep.gates, "fp32_outputs": rep.fp32_outputs, "not_eligible": len(rep.skipped)}
+        on, off = res["gates"], res["flag_off"]
+        spread = max(on["ms_per_step_max"] - on["ms_per_step_min"], off["ms_per_step_max"] - off["ms_per_step_min"])
+        res["run_to_run_spread_ms"] = round(spread, 3)
+        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
+        res["flag_on_slower_beyond_spread"] = bool(on["ms_per_step_median"] - off["ms_per_step_median"] > spread)
+        out[tag] = res
+        del model, plans, x, logits
+        torch.cuda.empty_cache()
+    text = json.dumps(out, indent=1)
+    with open(os.path.join(ROOT, "profiles", "gate_ab.json"), "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
