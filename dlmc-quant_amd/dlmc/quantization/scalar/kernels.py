@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1234,6 +1234,37 @@ def gate_quant(x, gate, act=None, emit=None, want_out=True, c_pad=None, pad_code
     PROFILE.launch("gate", m * (c * (4 + 4 * want_out) + c_pad * (emit is not None)) + n * c * 4, lambda: N.check(N.lib.dlmcq_gate_nhwc_f32(
         N.ptr(x), N.ptr(gate), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, c_pad, int(pad_code), _act(False, act), *_q_args(q)[1:],
         N.stream_ptr())))
+    return out, q[0]
+
+
+def swish_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
+    """Swish / SiLU `x * sigmoid(x)` of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_swish_nhwc_f32: e = expf(-x), d = 1 + e, s = 1 / d,
+    v = x * s, each step rounded to fp32 - the operation sequence of `x * torch.sigmoid(x)`.  `x` is read in place when it is
+    channels_last or a channel slice of a channels_last tensor, else copied to channels_last.  Returns `(out or None, codes or None)`, both
+    channels_last: fp32 (N, C, H, W) unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the
+    activated values, `c_pad` channels wide (default C), channels C .. c_pad - 1 holding the byte `pad_code` (the consumer's zero point;
+    code 0 under a float activation offset; either minus 128 with `emit.shift128`)."""
+    N.require_gpu(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("swish_quant: an fp32 (N, C, H, W) tensor")
+    n, c, h, w_ = x.shape
+    if not want_out and emit is None:
+        raise ValueError("swish_quant: nothing to produce (want_out=False without emit)")
+    c_pad = c if c_pad is None else int(c_pad)
+    if c_pad != c and emit is None:
+        raise ValueError("swish_quant: c_pad pads the code rows (emit=None writes none)")
+    xs = _nhwc_rows(x)
+    if xs is None:
+        x = _nhwc(x)
+        xs = c
+
+    def alloc(dtype, ch=c_pad):
+        return torch.empty((n, ch, h, w_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
+    out = alloc(torch.float32, c) if want_out else None
+    q = _quantiser(emit, alloc, x, True, "swish_quant")
+    m = n * h * w_
+    PROFILE.launch("swish", m * (c * (4 + 4 * want_out) + c_pad * (emit is not None)), lambda: N.check(N.lib.dlmcq_swish_nhwc_f32(
+        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, c_pad, int(pad_code), *_q_args(q)[1:], N.stream_ptr())))
     return out, q[0]
 
 

@@ -34,7 +34,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -930,16 +930,21 @@ def _avgpool_window(node, modules):
     return x, k
 
 
-def _code_readers(planned, t):
-    """Who takes fp32 node `t` as codes from a stand-alone quantising node (the average-pool and gate passes): "gemm" plan convolutions
-    that read it through their activation argument - as their own node or as an operand of a dual node - with input channels % 4 == 0,
-    all sharing one activation quantiser and one channel count.  Returns (that quantiser, the takers, whether anyone else reads `t` as
-    fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or they disagree."""
+def _code_readers(planned, t, dw=False, dwpw=False):
+    """Who takes fp32 node `t` as codes from a stand-alone quantising node (the average-pool, gate and swish passes): "gemm" plan
+    convolutions that read it through their activation argument - as their own node or as an operand of a dual node - with input
+    channels % 4 == 0, all sharing one activation quantiser and one channel count; with `dw` (the swish pass: MBConv's expansion swish is
+    read by the depthwise layer) "dw" plan convolutions too, which take channel-padded codes as the main pass hands them over (`dwpw`:
+    fuse_inference's flag, under which a depthwise layer reads no shifted codes).  Returns (that quantiser, the takers, whether anyone
+    else reads `t` as fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or they disagree."""
     def reader(u):
         """(activation spec, convolution) with which plan node `u` reads `t` as codes, else None."""
         d = planned.get(u)
-        if d is None or d.spec.kind != "gemm":
+        if d is None or d.spec.kind not in (("gemm", "dw") if dw else ("gemm",)):
             return None
+        if d.spec.kind == "dw":
+            ok = not d.dual and u.args[0] is t and t not in u.args[1:] and d.mod.weight.dim() == 4
+            return (d.spec.act, d.mod) if ok else None
         if d.dual:
             ops = [(d.dual_inputs[i], (d.mod, d.dual_mod)[i]) for i in (0, 1) if u.args[i] is t]
             if not ops or len({a.key for a, _ in ops}) != 1:
@@ -955,13 +960,15 @@ def _code_readers(planned, t):
     takers = [u for u, r in readers.items() if r is not None]
     if not takers or len({readers[u][0].key for u in takers}) != 1:      # (the max-pool rule: one quantiser for all code readers)
         return None
+    def width(m):      # input channels of reader `m` (depthwise: one per output channel)
+        return int(m.weight.shape[0] if m.groups != 1 else m.weight.shape[1])
     emit, conv = readers[takers[0]]
-    c = int(conv.weight.shape[1])
-    if c % 4 or c < 4 or any(int(readers[u][1].weight.shape[1]) != c for u in takers):
+    c = width(conv)
+    if c % 4 or c < 4 or any(width(readers[u][1]) != c for u in takers):
         return None
     # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (a dual node
     # is never handed shifted codes by the main pass either)
-    shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers])
+    shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers], dwpw)
     return emit, takers, len(takers) != len(readers), c, _ceil64(c), _zp_fill(emit) - (128 if shift else 0), shift
 
 
@@ -1060,7 +1067,7 @@ def _gate_pass(gm, report, planned, dry_run, relu6):
     modules = dict(gm.named_modules())
     count = 0
     for mul in list(graph.nodes):
-        if not _is_mul(mul) or mul.args[0] is mul.args[1]:
+        if not _is_mul(mul) or mul.args[0] is mul.args[1] or _swish_of(mul, modules) is not None:      # (x * sigmoid(x): no gate)
             continue
         a, b = mul.args
         # exactly one operand derives from a global average pool, and that pool reads the other operand
@@ -1085,6 +1092,137 @@ def _gate_pass(gm, report, planned, dry_run, relu6):
             graph.erase_node(last)
         graph.erase_node(mul)
     report.gates = count
+    _settle(gm, count)
+
+
+class SwishLayer(nn.Module):
+    """Swish / SiLU `x * sigmoid(x)` of an fp32 (N, C, H, W) map straight to the activation codes of the plan layers that read the
+    activated map (csrc/swish.hip): the sigmoid, the multiply, the activated fp32 tensor and the consumer's quantise pass as one read
+    of the map.  `emit`: the readers' activation quantiser (_ActSpec), or None where nobody takes codes (the map is then activated in one
+    pass instead of two); the code rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes /
+    _pad_channels build from the fp32 tensor.  `c`: None where no reader fixes it.  An input that at run time is no 4-D fp32 map of `c`
+    channels (a multiple of 4) is activated and quantised with torch and K.fake_quant: the values of the unfused graph.  Returns
+    `(fp32 or None, codes or None)`."""
+
+    def __init__(self, emit, want_out, c, c_pad, pad_code, shift=False):
+        super().__init__()
+        self.emit, self.want_out = emit, bool(want_out or emit is None)
+        self.c, self.c_pad = (None if c is None else int(c)), (None if c_pad is None else int(c_pad))
+        self.pad_code, self.emit_shift = int(pad_code), bool(shift)
+
+    def forward(self, x):
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != (x.shape[1] if self.c is None else self.c) or x.shape[1] % 4 or not x.is_cuda:
+            return self._unfused(x)
+        if self.emit is None:
+            return K.swish_quant(x)
+        e = self.emit.emit(x.numel())       # (a QBase consumer's g: over its real input, the activated tensor)
+        e.shift128 = self.emit_shift
+        return K.swish_quant(x, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+
+    def _unfused(self, x):
+        v = x * torch.sigmoid(x)
+        a = self.emit
+        if a is None:
+            return v, None
+        t = v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.contiguous()
+        codes = K.fake_quant(t, a.scale, a.zp, a.lo, a.hi, a.form, g=a.g(v.numel()), codes="i8", want_y=False)[1]
+        if self.emit_shift:
+            codes = (codes.view(torch.uint8) ^ 0x80).view(torch.int8)
+        if codes.dim() == 4 and codes.shape[1] < self.c_pad:
+            codes = _pad_channels(codes, self.c_pad, self.pad_code)
+        return (v if self.want_out else None), codes
+
+
+class _DrySwishLayer(SwishLayer):
+    """fuse_inference(dry_run=...): a SwishLayer's decision (emit, want_out, c, c_pad, pad_code, emit_shift).  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+_SIGMOID_FNS = (torch.sigmoid, F.sigmoid)
+_SILU_FNS = (F.silu,)
+_SwishDecision = collections.namedtuple("_SwishDecision", "last x nodes emit takers want_out c c_pad pad_code shift")
+
+
+def _swish_of(node, modules):
+    """(x, the nodes that compute it) if `node` is swish of graph value x in a spelling the plan takes - `x * torch.sigmoid(x)` with
+    either operand first, x.sigmoid(), torch.mul / x.mul(...), the sigmoid read by that multiply alone; nn.SiLU; F.silu(x), not in place
+    (an nn.SiLU(inplace=True) only where nothing else reads x) - else None.  A user module whose body is one of these is traced into
+    it.  A gate `x * sigmoid(f(pool(x)))` is none of them: the sigmoid's argument must BE the other operand."""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        x = node.args[0] if len(node.args) == 1 and not node.kwargs else None
+        ok = type(m) is nn.SiLU and isinstance(x, fx.Node) and (not m.inplace or len(x.users) == 1)
+        return (x, [node]) if ok else None
+    if node.op == "call_function" and node.target in _SILU_FNS:
+        ok = len(node.args) == 1 and isinstance(node.args[0], fx.Node) and set(node.kwargs) <= {"inplace"} and not node.kwargs.get("inplace", False)
+        return (node.args[0], [node]) if ok else None
+    if not _is_mul(node) or node.args[0] is node.args[1]:
+        return None
+    for x, s in (node.args, node.args[::-1]):
+        sig = ((s.op == "call_function" and s.target in _SIGMOID_FNS) or (s.op == "call_method" and s.target == "sigmoid"))
+        if sig and not s.kwargs and len(s.args) == 1 and s.args[0] is x and len(s.users) == 1:
+            return x, [node, s]
+    return None
+
+
+def _is_map(x, planned, modules, limit=8):
+    """Whether graph value `x` is known to be a 4-D (N, C, H, W) tensor: the fp32 output of a plan convolution or of a plan node of the
+    average-pool / gate / swish passes, a 2-D convolution, batch norm or pool module's, or a sum with one (at most `limit` nodes back).
+    The swish on the (N, mid) vector of a squeeze path is none and stays in torch."""
+    stack, seen = [x], 0
+    while stack and seen < limit:
+        n = stack.pop()
+        seen += 1
+        if n.op == "call_function" and n.target is operator.getitem and isinstance(n.args[0], fx.Node) and n.args[1] == 0:
+            d = planned.get(n.args[0])
+            if d is not None:
+                if d.mod.weight.dim() == 4:
+                    return True
+            elif n.args[0].op == "call_module" and isinstance(modules.get(n.args[0].target), (AvgPoolLayer, GateLayer, SwishLayer)):
+                return True
+        elif n.op == "call_module":
+            if isinstance(modules.get(n.target), (nn.Conv2d, nn.BatchNorm2d, nn.MaxPool2d, nn.AvgPool2d, nn.AdaptiveAvgPool2d)):
+                return True
+        elif _is_add(n):
+            stack.extend(n.args)
+    return False
+
+
+def _swish_pass(gm, report, planned, dry_run, dwpw):
+    """Swish activations (fuse_inference(swish=True)): `x * sigmoid(x)` / SiLU of a 4-D map becomes a node (SwishLayer) that hands the
+    plan convolutions behind it - depthwise ones included - their activation codes and every other reader (a squeeze-excite pool, the
+    gate node, a shortcut add) the activated fp32 map from the same launch.  Per swish: decide (_SwishDecision; reads the graph, changes
+    nothing), build (the module, by mode), splice.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that
+    is for the convolution behind the swish stays - only its input changes, from fp32 to codes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+
+    def decide(node):
+        found = _swish_of(node, modules)
+        if found is None:
+            return None
+        x, nodes = found
+        taken = _code_readers(planned, node, dw=True, dwpw=dwpw)
+        if taken is None:      # nobody takes codes: one pass over the map instead of two, where it is known to be a map
+            return _SwishDecision(node, x, nodes, None, (), True, None, None, 0, False) if _is_map(x, planned, modules) else None
+        return _SwishDecision(node, x, nodes, *taken)
+
+    count = 0
+    for node in list(graph.nodes):
+        d = decide(node)
+        if d is None:
+            continue
+        module = (_DrySwishLayer if dry_run else SwishLayer)(d.emit, d.want_out, d.c, d.c_pad, d.pad_code, d.shift)
+        _, outs = _call_plan_module(gm, d.last, f"_int8_swish_{count}", module, (d.x,))
+        modules[f"_int8_swish_{count}"] = module
+        count += 1
+        for u in list(d.last.users):
+            u.replace_input_with(d.last, outs[1] if u in d.takers else outs[0])
+        for n in d.nodes:
+            graph.erase_node(n)
+    report.swishes = count
     _settle(gm, count)
 
 
@@ -1313,6 +1451,7 @@ class FusionReport:
         self.pad_shortcuts = 0   # option-A shortcuts (subsample + zero-pad) read in place by the layer's epilogue (fuse_inference(pad_shortcuts=True))
         self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
         self.gates = 0        # squeeze-excite gates (x * g, + ReLU / ReLU6) handing the plan layers behind them their codes (fuse_inference(gates=True))
+        self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -1341,6 +1480,7 @@ class FusionReport:
                 (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
                 (f"gates on the plan={self.gates}, " if self.gates else "") +
+                (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1879,7 +2019,7 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None, gates=False):
+                   recompute_shortcuts=None, gates=False, swish=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -1977,7 +2117,22 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     torch.equal between the two plans' logits).  Measured (tools/gate_ab.py, profiles/gate_ab.json; MobileNetV2-SE, 17 gates, batch 1024
     at 224^2, interleaved): flag off / flag on = 40.23 / 32.58 ms per step (FSPTQ W8A8) and 40.51 / 32.87 (QBase W8A8), ratio 1.23 at
     a run-to-run spread of 0.19 ms; the gate kernel moves 4.4 TB/s over its 17 launches (the average-pool kernel's launch-bound nodes:
-    0.9 - 2.6 TB/s).  No case slower.  Off by default: the plan without it is the plan as it was."""
+    0.9 - 2.6 TB/s).  No case slower.  Off by default: the plan without it is the plan as it was.
+    `swish=True`: swish / SiLU `x * sigmoid(x)` of a 4-D map - EfficientNet's MBConv activation
+    (`workloads.mobilenet_v2(se=True, act="swish")`) - becomes a plan node (SwishLayer, csrc/swish.hip) that hands the plan convolutions
+    behind it, depthwise ones included, their activation codes in one pass and every other reader (a squeeze-excite pool, the gate node, a
+    shortcut add) the activated fp32 map from the same launch (`fusion_report.swishes` counts the nodes).  Taken: `x * torch.sigmoid(x)`
+    with either operand first, x.sigmoid(), torch.mul / x.mul, the sigmoid read by that multiply alone; nn.SiLU; F.silu, not in place; a
+    user module whose body is one of these.  The readers follow the average-pool rule, plus depthwise plan convolutions; a swish nobody
+    takes as codes is a node too where its input is known to be a map.  Left as they are: the swish on the (N, mid) vector inside a
+    squeeze path, F.silu(inplace=True), a sigmoid with a second reader.  An input that at run time is no 4-D fp32 map of the planned width
+    takes the node's torch path.  e = expf(-x), d = 1 + e, s = 1 / d, v = x * s, each rounded to fp32: within 3 * 2^-23 relative of the
+    real value and, as measured, bit-identical to x * torch.sigmoid(x) on the device (F.silu differs in the last bit of a quarter of the
+    elements) - the plan of a network that spells the multiply is bit-identical to the plan without the flag (tests/test_swish_gpu.py).
+    The pass runs before the gate pass, which finds its gates behind the swish nodes.  Measured (tools/swish_ab.py,
+    profiles/swish_ab.json; the MBConv-SE network, 35 swishes, batch 1024 at 224^2, gates=True in both, interleaved): flag off / flag on
+    = 67.53 / 41.80 ms per step (FSPTQ W8A8), 67.58 / 41.97 (QBase W8A8), ratio 1.61 at a spread of 0.14 / 0.24 ms.  Off by default: the
+    plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -1996,6 +2151,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
             node.replace_all_uses_with(node.args[0])
             graph.erase_node(node)
     planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts).run(report)
+    if swish:           # (before the gate pass, which finds its gated map and the squeeze's pool behind a swish node's fp32 output)
+        _swish_pass(gm, report, planned, dry_run, dwpw)
     if gates:           # (first: the squeeze's global pool is a plain node still, and so are the nodes behind the gate)
         _gate_pass(gm, report, planned, dry_run, relu6)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)

@@ -209,6 +209,22 @@ def _conv_bn_relu6(cin, cout, k, stride=1, groups=1):
                          nn.ReLU6(inplace=True))
 
 
+class Swish(nn.Module):
+    """x * sigmoid(x) as a module of its own (EfficientNet's activation, efficientnet_block.py:36-41): traced into the multiply."""
+
+    def forward(self, x):
+        return x * torch.sigmoid(x)
+
+
+def _conv_bn_act(cin, cout, k, stride=1, groups=1, act="relu6"):
+    """_conv_bn_relu6, the activation `act`: "relu6" (that very block) or "swish"."""
+    if act == "relu6":
+        return _conv_bn_relu6(cin, cout, k, stride, groups)
+    if act != "swish":
+        raise ValueError(f"activation 'relu6' or 'swish', not {act!r}")
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout), Swish())
+
+
 class SqueezeExcite(nn.Module):
     """A squeeze-and-excitation block (public architecture, Hu et al. 2018): x * gate(squeeze(x)), the gate one value per image and
     channel.  `squeeze="linear"`: global average pool, flatten, Linear(c, reduced), swish, Linear(reduced, c), back to (N, C, 1, 1) -
@@ -240,15 +256,19 @@ class InvertedResidual(nn.Module):
     """MobileNetV2's unit: 1x1 expansion (t > 1) + depthwise 3x3 + linear 1x1 projection, BN after every convolution, ReLU6 after
     the first two; the identity shortcut where stride is 1 and the width is kept.  `se=True`: a squeeze-excite gate (MobileNetV3's:
     1x1 convolutions, a quarter of the expanded width rounded up to a multiple of 8, hard sigmoid) between the depthwise and the
-    projection layer."""
+    projection layer.  `act="swish"`: EfficientNet's MBConv (efficientnet_block.py:44-59, efficientnet.py:29-34) - swish where ReLU6
+    was, and with `se` its squeeze-excite block: Linear layers on the flattened pool, a quarter of the block's INPUT width between them,
+    a swish there too, a sigmoid gate.  The depthwise layer stays 3x3 with symmetric padding."""
 
-    def __init__(self, cin, cout, stride, t, se=False):
+    def __init__(self, cin, cout, stride, t, se=False, act="relu6"):
         super().__init__()
         hidden = cin * t
         self.use_res = stride == 1 and cin == cout
-        layers = [_conv_bn_relu6(cin, hidden, 1)] if t != 1 else []
-        layers += [_conv_bn_relu6(hidden, hidden, 3, stride, groups=hidden)]
-        if se:
+        layers = [_conv_bn_act(cin, hidden, 1, act=act)] if t != 1 else []
+        layers += [_conv_bn_act(hidden, hidden, 3, stride, groups=hidden, act=act)]
+        if se and act == "swish":
+            layers += [SqueezeExcite(hidden, max(1, cin // 4), gate="sigmoid", squeeze="linear")]
+        elif se:
             layers += [SqueezeExcite(hidden, (hidden // 4 + 7) // 8 * 8, gate="hardsigmoid", squeeze="conv")]
         layers += [nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
         self.conv = nn.Sequential(*layers)
@@ -263,15 +283,15 @@ class MobileNetV2(nn.Module):
 
     SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))   # t, c, n, s
 
-    def __init__(self, num_classes=1000, dropout=0.2, se=False):
+    def __init__(self, num_classes=1000, dropout=0.2, se=False, act="relu6"):
         super().__init__()
         cin = 32
-        feats = [_conv_bn_relu6(3, cin, 3, stride=2)]
+        feats = [_conv_bn_act(3, cin, 3, stride=2, act=act)]
         for t, c, n, s in self.SETTINGS:
             for j in range(n):
-                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t, se))
+                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t, se, act))
                 cin = c
-        feats.append(_conv_bn_relu6(cin, 1280, 1))
+        feats.append(_conv_bn_act(cin, 1280, 1, act=act))
         self.features = nn.Sequential(*feats)
         self.pool = nn.AdaptiveAvgPool2d(1)
         self.classifier = nn.Sequential(nn.Dropout(dropout), nn.Linear(1280, num_classes))
@@ -338,9 +358,11 @@ def mobileone_s1_deploy(num_classes=1000):
     return MobileOneDeploy(num_classes=num_classes)
 
 
-def mobilenet_v2(num_classes=1000, se=False):
-    """MobileNetV2; `se=True`: with a squeeze-excite gate in every inverted-residual block (17 gates; the default network is unchanged)."""
-    return MobileNetV2(num_classes=num_classes, se=se)
+def mobilenet_v2(num_classes=1000, se=False, act="relu6"):
+    """MobileNetV2; `se=True`: with a squeeze-excite gate in every inverted-residual block (17 gates; the default network is unchanged).
+    `act="swish"`: x * sigmoid(x) where ReLU6 was (35 swishes on maps) and, with `se`, EfficientNet's squeeze-excite block - its MBConv
+    at MobileNetV2's widths."""
+    return MobileNetV2(num_classes=num_classes, se=se, act=act)
 
 
 def _named_option(option):

@@ -877,6 +877,32 @@ int dlmcq_gate_nhwc_f32(const float* x, const float* gate, float* out, void* cod
                         int64_t x_stride, int64_t c_pad, int32_t pad_code, int32_t act, const float* q_scale, const float* q_zero_point,
                         int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- swish / SiLU x * sigmoid(x): fp32 and / or the consumer's activation codes ----
+ * For image n, pixel (h, w), channel c, with x = x[n, h, w, c]:
+ *     e = expf(-x)          the device library's accurate expf
+ *     d = fl32(1 + e)       one IEEE add
+ *     s = fl32(1 / d)       one IEEE division, correctly rounded
+ *     v = fl32(x * s)       one IEEE multiply, rounded to fp32 before anything else reads it (never contracted into the quantiser's
+ *                           arithmetic)
+ *     out = v;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused; DLMCQ_EMIT_SHIFT128 accepted) of v - the
+ *                      code dlmcq_fake_quant_f32 gives for it
+ * - the operation sequence of torch's x * torch.sigmoid(x), element by element; within 3 * 2^-23 relative of the real x * sigmoid(x) for
+ * |x| <= 80.  x <= -88.8: v = -0; x = -inf: NaN (as -inf * 0); x = +inf: +inf; NaN stays NaN; denormals are kept.  There is no
+ * activation argument.  No atomics, no scratch: the result depends neither on the launch geometry nor on the run.
+ *   x        fp32 [N, H, W, x_stride] row-major, of which channels 0 .. C - 1 are read (x_stride >= C, x_stride % 4 == 0: the channel
+ *            slice of a wider NHWC tensor is read in place), 16-byte aligned
+ *   out      fp32 [N, H, W, C] dense, 16-byte aligned, or NULL
+ *   codes    bytes [N, H, W, c_pad], 4-byte aligned, or NULL (needs q_scale); c_pad >= C, c_pad % 4 == 0; channels C .. c_pad - 1 receive
+ *            the byte `pad_code` (-128 .. 255, its low 8 bits are stored as given: the caller passes the consumer's zero point, code 0
+ *            under a float activation offset, or either minus 128 beside DLMCQ_EMIT_SHIFT128)
+ * DLMCQ_EINVAL: H < 1, W < 1, C < 4, C % 4, x_stride < C, x_stride % 4, c_pad < C, c_pad % 4, pad_code outside -128 .. 255, x NULL, both
+ * outputs NULL, c_pad != C without codes, an invalid quantiser, any control or layout bit in q_form (refused, not stripped).
+ * DLMCQ_EALIGN: x / out not 16-byte aligned, codes not 4-byte aligned.  DLMCQ_ERANGE: N * H * W * c_pad / 4 reaches 2^31.  N == 0:
+ * DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+int dlmcq_swish_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int64_t H, int64_t W, int64_t C, int64_t x_stride,
+                         int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                         int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Swish activations on the int8 plan (fuse_inference(swish=True): every `x * sigmoid(x)` of a map one launch of csrc/swish.hip that
+hands the plan convolutions behind it their activation codes and everybody else the activated fp32 map) against the plan that runs
+torch's sigmoid and multiply and lets the consumer quantise - `gates=True` in both: both plans built from ONE calibrated model and timed
+interleaved, step by step, in one process.
+  cases: the MBConv-SE network (workloads.mobilenet_v2(se=True, act="swish"): 35 swishes on maps, 17 gates) at 224^2, FSPTQ W8A8 (zero
+         points set to exactly 0 after calibration, as the tests do) and QBase W8A8.
+Per case: median ms per step of either plan over `steps` single steps each (A, B, A, B, ...), the run-to-run spread = the interquartile
+range of the flag-off plan's steps, whether the flag-on plan is faster by more than that, max |delta logit| and top-1 agreement between
+the two plans, and per swish node the kernel's time, bytes per second (per pixel: 4 C read, 4 C written if the fp32 map is wanted, c_pad
+code bytes written) and elements per second.  Writes profiles/swish_ab.json (and prints it).
+usage: python tools/swish_ab.py [batch] [steps]"""
+import copy
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
+import torch  # noqa: E402
+
+import workloads as W  # noqa: E402
+from act_offset_ab import QBASE_W8A8  # noqa: E402
+from dlmc.quantization.scalar.FSPTQuant import FSPTQBase  # noqa: E402
+from dlmc.quantization.scalar.modules.base import QBase  # noqa: E402
+from dlmc.utils.fuse import SwishLayer, fuse_inference  # noqa: E402
+from dlmc.utils.merge_bn import merge_bn  # noqa: E402
+from dlmc.utils.quantize import quantize_model  # noqa: E402
+from relu6_ab import QCFG as FSPTQ_W8A8, timed  # noqa: E402
+
+CASES = [("mbconv_se_fsptq_w8a8", "fsptq"), ("mbconv_se_qbase_w8a8", "qbase")]
+
+
+def quartiles(v):
+    s = sorted(v)
+    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]  # noqa: E731
+    return q(0.25), q(0.5), q(0.75)
+
+
+def swish_kernel_times(plan, x, reps=20):
+    """Per SwishLayer node: its input as the plan hands it over, then the node alone, `reps` launches between two events."""
+    seen, hooks, rows = {}, [], []
+    for name, m in plan.named_modules():
+        if isinstance(m, SwishLayer):
+            hooks.append(m.register_forward_pre_hook(lambda mod, a, name=name: seen.__setitem__(name, a[0])))
+    plan(x)
+    for h in hooks:
+        h.remove()
+    mods = dict(plan.named_modules())
+    for name, t in seen.items():
+        m = mods[name]
+        for _ in range(3):
+            m(t)
+        ms = timed(m, t, reps)
+        n, c, h, w = t.shape
+        codes = m.c_pad if m.emit is not None else 0
+        nbytes = n * h * w * (c * (4 + 4 * m.want_out) + codes)
+        rows.append({"node": name, "input": [n, c, h, w], "floats_per_input_pixel": int(t.stride(3)), "c_pad": m.c_pad,
+                     "codes_written": m.emit is not None, "fp32_written": m.want_out, "us": round(ms * 1e3, 2), "bytes": nbytes,
+                     "gb_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1), "gelem_per_s": round(t.numel() / (ms * 1e-3) / 1e9, 1)})
+    return rows
+
+
+def main():
+    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 24
+    dev = "cuda:0"
+    out = {"model": "mobilenet_v2(se=True, act='swish')", "batch": batch, "steps_per_plan": steps, "resolution": 224}
+    for tag, fam in CASES:
+        torch.manual_seed(2333)
+        model = merge_bn(W.mobilenet_v2(se=True, act="swish").to(dev).eval(), inplace=True, allow_missing=True)
+        if fam == "fsptq":
+            quantize_model(model, copy.deepcopy(FSPTQ_W8A8), None, "FSPTQ", int8_gemm=True)
+        else:
+            quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
+        x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
+        with torch.no_grad():
+            model(x[:64])                                   # calibrate
+            for m in model.modules():
+                if isinstance(m, FSPTQBase):
+                    m.in_offset.zero_()
+                    m._zp_is_int = None
+                elif isinstance(m, QBase) and m.in_offset is not None:
+                    m.in_offset.zero_()
+            plans = {"swish": fuse_inference(model, gates=True, swish=True), "flag_off": fuse_inference(model, gates=True)}
+            logits = {k: p(x) for k, p in plans.items()}
+            kernels = swish_kernel_times(plans["swish"], x)
+            for p in plans.values():                        # warm-up
+                timed(p, x, 3)
+            ms = {k: [] for k in plans}
+            for _ in range(steps):                          # interleaved: A, B, A, B, ...
+                for k, p in plans.items():
+                    ms[k].append(timed(p, x, 1))
+        total, elems = sum(r["bytes"] for r in kernels), sum(r["input"][0] * r["input"][1] * r["input"][2] * r["input"][3] for r in kernels)
+        us = sum(r["us"] for r in kernels)
+        a, b = logits["swish"].float(), logits["flag_off"].float()
+        res = {"logits_equal": bool(torch.equal(a, b)), "max_abs_delta_logit": float((a - b).abs().max()),
+               "top1_agreement": float((a.argmax(1) == b.argmax(1)).float().mean()), "swish_kernels": kernels,
+               "swish_kernels_total": {"us": round(us, 1), "bytes": total, "gb_per_s": round(total / (us * 1e-6) / 1e9, 1),
+                                       "gelem_per_s": round(elems / (us * 1e-6) / 1e9, 1)}}
+        for k, v in ms.items():
+            rep = plans[k].fusion_report
+            q1, med, q3 = quartiles(v)
+            res[k] = {"ms_per_step_median": round(med, 3), "ms_per_step_q1": round(q1, 3), "ms_per_step_q3": round(q3, 3),
+                      "ms_per_step_min": round(min(v), 3), "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v],
+                      "int8_layers": rep.layers, "gates": rep.gates, "swishes": rep.swishes, "fp32_outputs": rep.fp32_outputs,
+                      "not_eligible": len(rep.skipped)}
+        on, off = res["swish"], res["flag_off"]
+        spread = off["ms_per_step_q3"] - off["ms_per_step_q1"]
+        res["run_to_run_spread_ms"] = round(spread, 3)      # (the interquartile range of the baseline's steps)
+        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
+        res["flag_on_faster_beyond_spread"] = bool(off["ms_per_step_median"] - on["ms_per_step_median"] > spread)
+        out[tag] = res
+        del model, plans, x, logits
+        torch.cuda.empty_cache()
+    text = json.dumps(out, indent=1)
+    with open(os.path.join(ROOT, "profiles", "swish_ab.json"), "w") as f:
+        f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
