@@ -1167,105 +1167,79 @@ def _nhwc_rows(x):
     return xs if ok else None
 
 
-def avgpool_quant(x, window, emit=None, want_out=True, c_pad=None, pad_code=0):
-    """nn.AvgPool2d(window, window) (no padding, floor) of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_avgpool_nhwc_f32: a
-    sequential fp32 sum from +0 in row-major window order and a true division (torch's own loop: the pooled values are bit-identical to
-    F.avg_pool2d(x, window)).  `x` is read in place when it is channels_last or a channel slice of a channels_last tensor, else copied to
-    channels_last.  Returns `(pooled or None, codes or None)`, both channels_last: fp32 (N, C, H // window, W // window) unless
-    `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the pooled values, `c_pad` channels wide
-    (default C), channels C .. c_pad - 1 holding the byte `pad_code` (the consumer's zero point; code 0 under a float activation
-    offset; either minus 128 with `emit.shift128`)."""
-    N.require_gpu(x)
+def _fp32_map(name, x):
+    """The shape (n, c, h, w) of `x`, which has to be an fp32 4-D tensor."""
     if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError("avgpool_quant: an fp32 (N, C, H, W) tensor")
+        raise ValueError(f"{name}: an fp32 (N, C, H, W) tensor")
+    return tuple(x.shape)
+
+
+def _map_codes(name, x, p, q_, emit, want_out, c_pad, pad_code, tag, read, issue):
+    """avgpool_quant, gate_quant and swish_quant (csrc/map_codes.h) behind their own checks: fp32 map `x` (_fp32_map) to `(out or None,
+    codes or None)`, both channels_last with `p` x `q_` pixels.  `x` is read in place when it is channels_last or a channel slice of a
+    channels_last tensor, else copied to channels_last.  `out`: fp32, C channels, unless `want_out=False`; `codes`: with
+    `emit=EmitCodes(...)` the consumer's activation codes of the same values, `c_pad` channels wide (default C), channels C .. c_pad - 1
+    holding the byte `pad_code` (the consumer's zero point; code 0 under a float activation offset; either minus 128 with
+    `emit.shift128`).  `tag`, `read`: profile tag and bytes read; `issue(x, out, codes, x_stride, c_pad, pad_code, *quantiser, stream)`
+    calls the entry point with the marshalled arguments all three take."""
     if not want_out and emit is None:
-        raise ValueError("avgpool_quant: nothing to produce (want_out=False without emit)")
-    n, c, h, w_ = x.shape
+        raise ValueError(f"{name}: nothing to produce (want_out=False without emit)")
+    n, c = x.shape[:2]
     c_pad = c if c_pad is None else int(c_pad)
     if c_pad != c and emit is None:
-        raise ValueError("avgpool_quant: c_pad pads the code rows (emit=None writes none)")
-    s = int(window)
+        raise ValueError(f"{name}: c_pad pads the code rows (emit=None writes none)")
     xs = _nhwc_rows(x)
     if xs is None:
-        x = _nhwc(x)
-        xs = c
-    p, q_ = (h // s, w_ // s) if s > 0 else (0, 0)
+        x, xs = _nhwc(x), c
 
     def alloc(dtype, ch=c_pad):
         return torch.empty((n, ch, p, q_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
     out = alloc(torch.float32, c) if want_out else None
-    q = _quantiser(emit, alloc, x, True, "avgpool_quant")
-    m = n * p * q_
-    PROFILE.launch("avgpool", m * (c * (4 * s * s + 4 * want_out) + c_pad * (emit is not None)), lambda: N.check(N.lib.dlmcq_avgpool_nhwc_f32(
-        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, s, c_pad, int(pad_code), *_q_args(q)[1:], N.stream_ptr())))
+    q = _quantiser(emit, alloc, x, True, name)
+    codes, *tail = _q_args(q)
+    PROFILE.launch(tag, read + n * p * q_ * (c * 4 * want_out + c_pad * (emit is not None)), lambda: N.check(issue(
+        N.ptr(x), N.ptr(out), codes, xs, c_pad, int(pad_code), *tail, N.stream_ptr())))
     return out, q[0]
+
+
+def avgpool_quant(x, window, emit=None, want_out=True, c_pad=None, pad_code=0):
+    """nn.AvgPool2d(window, window) (no padding, floor) of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_avgpool_nhwc_f32: a
+    sequential fp32 sum from +0 in row-major window order and a true division (torch's own loop: the pooled values are bit-identical to
+    F.avg_pool2d(x, window)).  Returns `(pooled or None, codes or None)`: fp32 (N, C, H // window, W // window) and the consumer's
+    activation codes of the pooled values; the inputs read in place, `emit`, `want_out`, `c_pad` and `pad_code` as _map_codes says."""
+    N.require_gpu(x)
+    n, c, h, w_ = _fp32_map("avgpool_quant", x)
+    s = int(window)
+    p, q_ = (h // s, w_ // s) if s > 0 else (0, 0)
+    return _map_codes("avgpool_quant", x, p, q_, emit, want_out, c_pad, pad_code, "avgpool", n * p * q_ * c * 4 * s * s,
+                      lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_avgpool_nhwc_f32(xp, op, cp, n, h, w_, c, xs, s, cpad, pad, *tail))
 
 
 def gate_quant(x, gate, act=None, emit=None, want_out=True, c_pad=None, pad_code=0):
     """A squeeze-excite channel gate `x * gate` of an fp32 (N, C, H, W) map, C % 4 == 0, (+ `act`: N.ACT_NONE / ACT_RELU / ACT_RELU6) by
     dlmcq_gate_nhwc_f32: one IEEE multiply per element, then torch's relu / relu6 - the values of `act(x * gate.view(N, C, 1, 1))`, bit
-    for bit.  `gate`: any fp32 tensor of N * C elements shaped (N, C, 1, 1) or (N, C), made dense.  `x` is read in place when it is
-    channels_last or a channel slice of a channels_last tensor, else copied to channels_last.  Returns `(out or None, codes or None)`, both
-    channels_last: fp32 (N, C, H, W) unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the gated
-    values, `c_pad` channels wide (default C), channels C .. c_pad - 1 holding the byte `pad_code` (the consumer's zero point; code 0
-    under a float activation offset; either minus 128 with `emit.shift128`)."""
+    for bit.  `gate`: any fp32 tensor of N * C elements shaped (N, C, 1, 1) or (N, C), made dense.  Returns `(out or None, codes or
+    None)`: fp32 (N, C, H, W) and the consumer's activation codes of the gated values; the inputs read in place, `emit`, `want_out`,
+    `c_pad` and `pad_code` as _map_codes says."""
     N.require_gpu(x, gate)
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError("gate_quant: an fp32 (N, C, H, W) tensor")
-    n, c, h, w_ = x.shape
+    n, c, h, w_ = _fp32_map("gate_quant", x)
     if gate.dtype != torch.float32 or tuple(gate.shape) not in ((n, c, 1, 1), (n, c)):
         raise ValueError(f"gate_quant: an fp32 gate of shape ({n}, {c}, 1, 1) or ({n}, {c}), not {gate.dtype} {tuple(gate.shape)}")
-    if not want_out and emit is None:
-        raise ValueError("gate_quant: nothing to produce (want_out=False without emit)")
-    c_pad = c if c_pad is None else int(c_pad)
-    if c_pad != c and emit is None:
-        raise ValueError("gate_quant: c_pad pads the code rows (emit=None writes none)")
     gate = gate.detach().reshape(n, c).contiguous()
-    xs = _nhwc_rows(x)
-    if xs is None:
-        x = _nhwc(x)
-        xs = c
-
-    def alloc(dtype, ch=c_pad):
-        return torch.empty((n, ch, h, w_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
-    out = alloc(torch.float32, c) if want_out else None
-    q = _quantiser(emit, alloc, x, True, "gate_quant")
-    m = n * h * w_
-    PROFILE.launch("gate", m * (c * (4 + 4 * want_out) + c_pad * (emit is not None)) + n * c * 4, lambda: N.check(N.lib.dlmcq_gate_nhwc_f32(
-        N.ptr(x), N.ptr(gate), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, c_pad, int(pad_code), _act(False, act), *_q_args(q)[1:],
-        N.stream_ptr())))
-    return out, q[0]
+    return _map_codes("gate_quant", x, h, w_, emit, want_out, c_pad, pad_code, "gate", n * h * w_ * c * 4 + n * c * 4,
+                      lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_gate_nhwc_f32(xp, N.ptr(gate), op, cp, n, h, w_, c, xs, cpad, pad,
+                                                                                         _act(False, act), *tail))
 
 
 def swish_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
     """Swish / SiLU `x * sigmoid(x)` of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_swish_nhwc_f32: e = expf(-x), d = 1 + e, s = 1 / d,
-    v = x * s, each step rounded to fp32 - the operation sequence of `x * torch.sigmoid(x)`.  `x` is read in place when it is
-    channels_last or a channel slice of a channels_last tensor, else copied to channels_last.  Returns `(out or None, codes or None)`, both
-    channels_last: fp32 (N, C, H, W) unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the
-    activated values, `c_pad` channels wide (default C), channels C .. c_pad - 1 holding the byte `pad_code` (the consumer's zero point;
-    code 0 under a float activation offset; either minus 128 with `emit.shift128`)."""
+    v = x * s, each step rounded to fp32 - the operation sequence of `x * torch.sigmoid(x)`.  Returns `(out or None, codes or None)`:
+    fp32 (N, C, H, W) and the consumer's activation codes of the activated values; the inputs read in place, `emit`, `want_out`, `c_pad`
+    and `pad_code` as _map_codes says."""
     N.require_gpu(x)
-    if x.dim() != 4 or x.dtype != torch.float32:
-        raise ValueError("swish_quant: an fp32 (N, C, H, W) tensor")
-    n, c, h, w_ = x.shape
-    if not want_out and emit is None:
-        raise ValueError("swish_quant: nothing to produce (want_out=False without emit)")
-    c_pad = c if c_pad is None else int(c_pad)
-    if c_pad != c and emit is None:
-        raise ValueError("swish_quant: c_pad pads the code rows (emit=None writes none)")
-    xs = _nhwc_rows(x)
-    if xs is None:
-        x = _nhwc(x)
-        xs = c
-
-    def alloc(dtype, ch=c_pad):
-        return torch.empty((n, ch, h, w_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
-    out = alloc(torch.float32, c) if want_out else None
-    q = _quantiser(emit, alloc, x, True, "swish_quant")
-    m = n * h * w_
-    PROFILE.launch("swish", m * (c * (4 + 4 * want_out) + c_pad * (emit is not None)), lambda: N.check(N.lib.dlmcq_swish_nhwc_f32(
-        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h, w_, c, xs, c_pad, int(pad_code), *_q_args(q)[1:], N.stream_ptr())))
-    return out, q[0]
+    n, c, h, w_ = _fp32_map("swish_quant", x)
+    return _map_codes("swish_quant", x, h, w_, emit, want_out, c_pad, pad_code, "swish", n * h * w_ * c * 4,
+                      lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_swish_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail))
 
 
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):

@@ -875,24 +875,48 @@ class GapHeadLayer(nn.Module):
                                residual=residual, act=a._act_arg(), emit=emit, want_out=self.want_out)
 
 
-class AvgPoolLayer(nn.Module):
+class _MapCodesLayer(nn.Module):
+    """What the plan nodes that read an fp32 map once and hand its readers activation codes share (AvgPoolLayer, GateLayer, SwishLayer;
+    csrc/map_codes.h).  `emit`: the readers' activation quantiser (_ActSpec); `want_out`: whether anyone reads the fp32 values; the code
+    rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32
+    tensor; `shift`: the codes are stored as `code - 128`."""
+
+    def __init__(self, emit, want_out, c, c_pad, pad_code, shift):
+        super().__init__()
+        self.emit, self.want_out = emit, bool(want_out)
+        self.c, self.c_pad, self.pad_code, self.emit_shift = int(c), int(c_pad), int(pad_code), bool(shift)
+
+    def _to_codes(self, numel):
+        """The keyword arguments every K.*_quant wrapper ends with; `numel`: the consumer's real input (a QBase consumer's g)."""
+        e = self.emit.emit(numel)
+        e.shift128 = self.emit_shift
+        return dict(emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+
+    def _torch_codes(self, v):
+        """`(v or None, codes)` of fp32 values `v` computed with torch, quantised with K.fake_quant: the values of the unfused graph."""
+        a = self.emit
+        t = v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.contiguous()
+        codes = K.fake_quant(t, a.scale, a.zp, a.lo, a.hi, a.form, g=a.g(v.numel()), codes="i8", want_y=False)[1]
+        if self.emit_shift:
+            codes = (codes.view(torch.uint8) ^ 0x80).view(torch.int8)
+        if codes.dim() == 4 and codes.shape[1] < self.c_pad:
+            codes = _pad_channels(codes, self.c_pad, self.pad_code)
+        return (v if self.want_out else None), codes
+
+
+class AvgPoolLayer(_MapCodesLayer):
     """A windowed average pool (nn.AvgPool2d(s, s) / F.avg_pool2d(x, s): window = stride, no padding, floor) of an fp32 map straight to
     the activation codes of the plan layers that read it (csrc/avgpool.hip) - the shortcut of a ResNet-C / -D block: the pool, the pooled
-    fp32 tensor and the consumer's quantise pass as one read of the map.  `emit`: the readers' activation quantiser (_ActSpec); the code
-    rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32 tensor.
-    Returns `(fp32 or None, codes)`."""
+    fp32 tensor and the consumer's quantise pass as one read of the map.  Returns `(fp32 or None, codes)`."""
 
     def __init__(self, window, emit, want_out, c, c_pad, pad_code, shift=False):
-        super().__init__()
-        self.window, self.emit, self.want_out = int(window), emit, bool(want_out)
-        self.c, self.c_pad, self.pad_code, self.emit_shift = int(c), int(c_pad), int(pad_code), bool(shift)
+        super().__init__(emit, want_out, c, c_pad, pad_code, shift)
+        self.window = int(window)
 
     def forward(self, x):
         n, c, h, w = x.shape
         s = self.window
-        e = self.emit.emit(n * c * (h // s) * (w // s))       # (a QBase consumer's g: over its real input, the pooled tensor)
-        e.shift128 = self.emit_shift
-        return K.avgpool_quant(x, s, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+        return K.avgpool_quant(x, s, **self._to_codes(n * c * (h // s) * (w // s)))      # (the pooled tensor)
 
 
 _AVGPOOL_NAMES = ("input", "kernel_size", "stride", "padding", "ceil_mode", "count_include_pad", "divisor_override")
@@ -930,13 +954,32 @@ def _avgpool_window(node, modules):
     return x, k
 
 
+_CodeReaders = collections.namedtuple("_CodeReaders", "emit takers want_out c c_pad pad_code shift")
+
+
+def _decided(r):
+    """What a _CodeReaders (or a record built on it) decides for the plan node, as a _MapCodesLayer's constructor arguments."""
+    return dict(emit=r.emit, want_out=r.want_out, c=r.c, c_pad=r.c_pad, pad_code=r.pad_code, shift=r.shift)
+
+
+def _splice_map_node(gm, last, name, module, args, takers, erase):
+    """Put `module` into the plan as `name`, called with `args`, in place of fp32 node `last`: `takers` read its codes (output 1),
+    everyone else its fp32 map (output 0); then `erase` the nodes it replaces, in that order."""
+    _, outs = _call_plan_module(gm, last, name, module, args)
+    for u in list(last.users):
+        u.replace_input_with(last, outs[1] if u in takers else outs[0])
+    for n in erase:
+        gm.graph.erase_node(n)
+
+
 def _code_readers(planned, t, dw=False, dwpw=False):
     """Who takes fp32 node `t` as codes from a stand-alone quantising node (the average-pool, gate and swish passes): "gemm" plan
     convolutions that read it through their activation argument - as their own node or as an operand of a dual node - with input
     channels % 4 == 0, all sharing one activation quantiser and one channel count; with `dw` (the swish pass: MBConv's expansion swish is
     read by the depthwise layer) "dw" plan convolutions too, which take channel-padded codes as the main pass hands them over (`dwpw`:
-    fuse_inference's flag, under which a depthwise layer reads no shifted codes).  Returns (that quantiser, the takers, whether anyone
-    else reads `t` as fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or they disagree."""
+    fuse_inference's flag, under which a depthwise layer reads no shifted codes).  Returns a _CodeReaders (that quantiser, the takers,
+    whether anyone else reads `t` as fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or
+    they disagree."""
     def reader(u):
         """(activation spec, convolution) with which plan node `u` reads `t` as codes, else None."""
         d = planned.get(u)
@@ -969,7 +1012,7 @@ def _code_readers(planned, t, dw=False, dwpw=False):
     # shifted codes (`code - 128`) where every taker is a plan convolution on its own node that reads them as they are (a dual node
     # is never handed shifted codes by the main pass either)
     shift = _emits_shifted(emit, [(None, None) if planned[u].dual else (planned[u].spec, planned[u].mod) for u in takers], dwpw)
-    return emit, takers, len(takers) != len(readers), c, _ceil64(c), _zp_fill(emit) - (128 if shift else 0), shift
+    return _CodeReaders(emit, takers, len(takers) != len(readers), c, _ceil64(c), _zp_fill(emit) - (128 if shift else 0), shift)
 
 
 def _avgpool_pass(gm, report, planned, dry_run):
@@ -987,48 +1030,32 @@ def _avgpool_pass(gm, report, planned, dry_run):
         taken = _code_readers(planned, pool)
         if taken is None:
             continue
-        emit, takers, want_out, c, c_pad, pad_code, shift = taken
-        module = _DryNode() if dry_run else AvgPoolLayer(s, emit, want_out, c, c_pad, pad_code, shift)
-        _, outs = _call_plan_module(gm, pool, f"_int8_avgpool_{count}", module, (x,))
+        module = _DryNode() if dry_run else AvgPoolLayer(s, **_decided(taken))
+        _splice_map_node(gm, pool, f"_int8_avgpool_{count}", module, (x,), taken.takers, [pool])
         count += 1
-        for u in list(pool.users):
-            u.replace_input_with(pool, outs[1] if u in takers else outs[0])
-        graph.erase_node(pool)
     report.avg_pools = count
     _settle(gm, count)
 
 
-class GateLayer(nn.Module):
+class GateLayer(_MapCodesLayer):
     """A squeeze-excite channel gate `x * g` (x fp32 (N, C, H, W), g (N, C, 1, 1)) (+ ReLU / ReLU6) straight to the activation codes of
     the plan layers that read the gated map (csrc/gate.hip): the multiply, the activation, the gated fp32 tensor and the consumer's
-    quantise pass as one read of the map.  `emit`: the readers' activation quantiser (_ActSpec); `act`: DLMCQ_ACT_*; the code rows are
-    `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32 tensor.  A `g`
+    quantise pass as one read of the map.  `act`: DLMCQ_ACT_*.  A `g`
     of any other shape at run time (a per-tensor or spatial gate the trace could not tell apart) is multiplied, activated and quantised
     with torch and K.fake_quant: the values of the unfused graph.  Returns `(fp32 or None, codes)`."""
 
     def __init__(self, emit, want_out, act, c, c_pad, pad_code, shift=False):
-        super().__init__()
-        self.emit, self.want_out, self.act = emit, bool(want_out), int(act)
-        self.c, self.c_pad, self.pad_code, self.emit_shift = int(c), int(c_pad), int(pad_code), bool(shift)
+        super().__init__(emit, want_out, c, c_pad, pad_code, shift)
+        self.act = int(act)
 
     def forward(self, x, g):
         if x.dim() != 4 or x.dtype != torch.float32 or g.dtype != torch.float32 or tuple(g.shape) != (x.shape[0], x.shape[1], 1, 1) or x.shape[1] != self.c:
             return self._unfused(x, g)
-        e = self.emit.emit(x.numel())       # (a QBase consumer's g: over its real input, the gated tensor)
-        e.shift128 = self.emit_shift
-        return K.gate_quant(x, g, act=self.act, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+        return K.gate_quant(x, g, act=self.act, **self._to_codes(x.numel()))      # (the gated tensor)
 
     def _unfused(self, x, g):
         v = x * g
-        v = F.relu6(v) if self.act == N.ACT_RELU6 else (torch.relu(v) if self.act == N.ACT_RELU else v)
-        a = self.emit
-        t = v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.contiguous()
-        codes = K.fake_quant(t, a.scale, a.zp, a.lo, a.hi, a.form, g=a.g(v.numel()), codes="i8", want_y=False)[1]
-        if self.emit_shift:
-            codes = (codes.view(torch.uint8) ^ 0x80).view(torch.int8)
-        if codes.dim() == 4 and codes.shape[1] < self.c_pad:
-            codes = _pad_channels(codes, self.c_pad, self.pad_code)
-        return (v if self.want_out else None), codes
+        return self._torch_codes(F.relu6(v) if self.act == N.ACT_RELU6 else (torch.relu(v) if self.act == N.ACT_RELU else v))
 
 
 _MUL_FNS = (operator.mul, torch.mul)
@@ -1082,55 +1109,34 @@ def _gate_pass(gm, report, planned, dry_run, relu6):
         taken = _code_readers(planned, last)
         if taken is None:
             continue
-        emit, takers, want_out, c, c_pad, pad_code, shift = taken
-        module = _DryNode() if dry_run else GateLayer(emit, want_out, act, c, c_pad, pad_code, shift)
-        _, outs = _call_plan_module(gm, last, f"_int8_gate_{count}", module, (x, g))
+        module = _DryNode() if dry_run else GateLayer(act=act, **_decided(taken))
+        _splice_map_node(gm, last, f"_int8_gate_{count}", module, (x, g), taken.takers, [last, mul] if last is not mul else [mul])
         count += 1
-        for u in list(last.users):
-            u.replace_input_with(last, outs[1] if u in takers else outs[0])
-        if last is not mul:
-            graph.erase_node(last)
-        graph.erase_node(mul)
     report.gates = count
     _settle(gm, count)
 
 
-class SwishLayer(nn.Module):
+class SwishLayer(_MapCodesLayer):
     """Swish / SiLU `x * sigmoid(x)` of an fp32 (N, C, H, W) map straight to the activation codes of the plan layers that read the
     activated map (csrc/swish.hip): the sigmoid, the multiply, the activated fp32 tensor and the consumer's quantise pass as one read
-    of the map.  `emit`: the readers' activation quantiser (_ActSpec), or None where nobody takes codes (the map is then activated in one
-    pass instead of two); the code rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes /
-    _pad_channels build from the fp32 tensor.  `c`: None where no reader fixes it.  An input that at run time is no 4-D fp32 map of `c`
-    channels (a multiple of 4) is activated and quantised with torch and K.fake_quant: the values of the unfused graph.  Returns
-    `(fp32 or None, codes or None)`."""
+    of the map.  `emit`: None where nobody takes codes (the map is then activated in one pass instead of two, and always written); `c`,
+    `c_pad`: None where no reader fixes them.  An input that at run time is no 4-D fp32 map of `c` channels (a multiple of 4) is
+    activated and quantised with torch and K.fake_quant: the values of the unfused graph.  Returns `(fp32 or None, codes or None)`."""
 
     def __init__(self, emit, want_out, c, c_pad, pad_code, shift=False):
-        super().__init__()
-        self.emit, self.want_out = emit, bool(want_out or emit is None)
-        self.c, self.c_pad = (None if c is None else int(c)), (None if c_pad is None else int(c_pad))
-        self.pad_code, self.emit_shift = int(pad_code), bool(shift)
+        super().__init__(emit, want_out or emit is None, c or 0, c_pad or 0, pad_code, shift)
+        self.c, self.c_pad = (None if c is None else self.c), (None if c_pad is None else self.c_pad)
 
     def forward(self, x):
         if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != (x.shape[1] if self.c is None else self.c) or x.shape[1] % 4 or not x.is_cuda:
             return self._unfused(x)
         if self.emit is None:
             return K.swish_quant(x)
-        e = self.emit.emit(x.numel())       # (a QBase consumer's g: over its real input, the activated tensor)
-        e.shift128 = self.emit_shift
-        return K.swish_quant(x, emit=e, want_out=self.want_out, c_pad=self.c_pad, pad_code=self.pad_code)
+        return K.swish_quant(x, **self._to_codes(x.numel()))      # (the activated tensor)
 
     def _unfused(self, x):
         v = x * torch.sigmoid(x)
-        a = self.emit
-        if a is None:
-            return v, None
-        t = v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.contiguous()
-        codes = K.fake_quant(t, a.scale, a.zp, a.lo, a.hi, a.form, g=a.g(v.numel()), codes="i8", want_y=False)[1]
-        if self.emit_shift:
-            codes = (codes.view(torch.uint8) ^ 0x80).view(torch.int8)
-        if codes.dim() == 4 and codes.shape[1] < self.c_pad:
-            codes = _pad_channels(codes, self.c_pad, self.pad_code)
-        return (v if self.want_out else None), codes
+        return (v, None) if self.emit is None else self._torch_codes(v)
 
 
 class _DrySwishLayer(SwishLayer):
@@ -1142,7 +1148,7 @@ class _DrySwishLayer(SwishLayer):
 
 _SIGMOID_FNS = (torch.sigmoid, F.sigmoid)
 _SILU_FNS = (F.silu,)
-_SwishDecision = collections.namedtuple("_SwishDecision", "last x nodes emit takers want_out c c_pad pad_code shift")
+_SwishDecision = collections.namedtuple("_SwishDecision", ("last", "x", "nodes") + _CodeReaders._fields)
 
 
 def _swish_of(node, modules):
@@ -1180,7 +1186,7 @@ def _is_map(x, planned, modules, limit=8):
             if d is not None:
                 if d.mod.weight.dim() == 4:
                     return True
-            elif n.args[0].op == "call_module" and isinstance(modules.get(n.args[0].target), (AvgPoolLayer, GateLayer, SwishLayer)):
+            elif n.args[0].op == "call_module" and isinstance(modules.get(n.args[0].target), _MapCodesLayer):
                 return True
         elif n.op == "call_module":
             if isinstance(modules.get(n.target), (nn.Conv2d, nn.BatchNorm2d, nn.MaxPool2d, nn.AvgPool2d, nn.AdaptiveAvgPool2d)):
@@ -1206,7 +1212,7 @@ def _swish_pass(gm, report, planned, dry_run, dwpw):
         x, nodes = found
         taken = _code_readers(planned, node, dw=True, dwpw=dwpw)
         if taken is None:      # nobody takes codes: one pass over the map instead of two, where it is known to be a map
-            return _SwishDecision(node, x, nodes, None, (), True, None, None, 0, False) if _is_map(x, planned, modules) else None
+            return _SwishDecision(node, x, nodes, *_CodeReaders(None, (), True, None, None, 0, False)) if _is_map(x, planned, modules) else None
         return _SwishDecision(node, x, nodes, *taken)
 
     count = 0
@@ -1214,14 +1220,10 @@ def _swish_pass(gm, report, planned, dry_run, dwpw):
         d = decide(node)
         if d is None:
             continue
-        module = (_DrySwishLayer if dry_run else SwishLayer)(d.emit, d.want_out, d.c, d.c_pad, d.pad_code, d.shift)
-        _, outs = _call_plan_module(gm, d.last, f"_int8_swish_{count}", module, (d.x,))
+        module = (_DrySwishLayer if dry_run else SwishLayer)(**_decided(d))
+        _splice_map_node(gm, d.last, f"_int8_swish_{count}", module, (d.x,), d.takers, d.nodes)
         modules[f"_int8_swish_{count}"] = module
         count += 1
-        for u in list(d.last.users):
-            u.replace_input_with(d.last, outs[1] if u in d.takers else outs[0])
-        for n in d.nodes:
-            graph.erase_node(n)
     report.swishes = count
     _settle(gm, count)
 

@@ -9,7 +9,6 @@ Per case: median / min / max ms per step of either plan, whether the flag-on pla
 the logits are equal, and per pool node the kernel's time and achieved bytes per second (bytes per output pixel and channel: 4 s^2 read,
 4 written if the fp32 tensor is wanted, 1 written per padded code).  Writes profiles/avgpool_shortcut_ab.json (and prints it).
 usage: python tools/avgpool_shortcut_ab.py [batch] [rounds]"""
-import copy
 import json
 import os
 import sys
@@ -19,32 +18,19 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from act_offset_ab import QBASE_W8A8  # noqa: E402
-from dlmc.quantization.scalar.FSPTQuant import FSPTQBase  # noqa: E402
 from dlmc.utils.fuse import AvgPoolLayer, fuse_inference  # noqa: E402
 from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
-from relu6_ab import QCFG as FSPTQ_W8A8, timed  # noqa: E402
+from node_times import calibrated, node_times  # noqa: E402
+from relu6_ab import timed  # noqa: E402
 
 CASES = [(f"cifar_resnet{depth}_option_{opt.lower()}_{fam}", depth, opt, fam)
          for depth in (20, 56) for opt in ("C", "D") for fam in ("fsptq_w8a8", "qbase_w8a8")]
 
 
 def pool_kernel_times(plan, x, reps=20):
-    """Per AvgPoolLayer node: its input as the plan hands it over, then the node alone, `reps` launches between two events."""
-    seen, hooks, rows = {}, [], []
-    for name, m in plan.named_modules():
-        if isinstance(m, AvgPoolLayer):
-            hooks.append(m.register_forward_pre_hook(lambda mod, a, name=name: seen.__setitem__(name, a[0])))
-    plan(x)
-    for h in hooks:
-        h.remove()
-    mods = dict(plan.named_modules())
-    for name, t in seen.items():
-        m = mods[name]
-        for _ in range(3):
-            m(t)
-        ms = timed(m, t, reps)
+    """Per AvgPoolLayer node (node_times): the kernel's time and bytes per second."""
+    rows = []
+    for name, m, (t,), ms in node_times(plan, x, AvgPoolLayer, reps):
         n, c, h, w = t.shape
         s = m.window
         pix = n * (h // s) * (w // s)
@@ -62,19 +48,10 @@ def main():
     for tag, depth, opt, fam in CASES:
         torch.manual_seed(2333)
         model = merge_bn(W.CifarResNet((depth - 2) // 6, option=opt).to(dev).eval(), inplace=True, allow_missing=True)
-        if fam.startswith("fsptq"):
-            quantize_model(model, copy.deepcopy(FSPTQ_W8A8), None, "FSPTQ", int8_gemm=True)
-            kw = {}
-        else:
-            quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
-            kw = dict(act_offsets=True)
+        kw = {} if fam.startswith("fsptq") else dict(act_offsets=True)
         x = torch.relu(torch.randn(batch, 3, 32, 32, device=dev))
+        calibrated(model, fam, x, zero_qbase=False)
         with torch.no_grad():
-            model(x[:64])                                   # calibrate
-            for m in model.modules():
-                if isinstance(m, FSPTQBase):
-                    m.in_offset.zero_()
-                    m._zp_is_int = None
             plans = {"avg_pools": fuse_inference(model, avg_pools=True, **kw), "flag_off": fuse_inference(model, **kw)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = pool_kernel_times(plans["avg_pools"], x)

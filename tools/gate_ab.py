@@ -9,7 +9,6 @@ Per case: median / min / max ms per step of either plan, whether the flag-on pla
 the logits are equal, and per gate node the kernel's time and achieved bytes per second (per pixel: 4 C read, 4 C written if the fp32
 tensor is wanted, c_pad code bytes written; the N x C gate once).  Writes profiles/gate_ab.json (and prints it).
 usage: python tools/gate_ab.py [batch] [rounds]"""
-import copy
 import json
 import os
 import sys
@@ -19,33 +18,18 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from act_offset_ab import QBASE_W8A8  # noqa: E402
-from dlmc.quantization.scalar.FSPTQuant import FSPTQBase  # noqa: E402
-from dlmc.quantization.scalar.modules.base import QBase  # noqa: E402
 from dlmc.utils.fuse import GateLayer, fuse_inference  # noqa: E402
 from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
-from relu6_ab import QCFG as FSPTQ_W8A8, timed  # noqa: E402
+from node_times import calibrated, node_times  # noqa: E402
+from relu6_ab import timed  # noqa: E402
 
 CASES = [("mobilenet_v2_se_fsptq_w8a8", "fsptq"), ("mobilenet_v2_se_qbase_w8a8", "qbase")]
 
 
 def gate_kernel_times(plan, x, reps=20):
-    """Per GateLayer node: its inputs as the plan hands them over, then the node alone, `reps` launches between two events."""
-    seen, hooks, rows = {}, [], []
-    for name, m in plan.named_modules():
-        if isinstance(m, GateLayer):
-            hooks.append(m.register_forward_pre_hook(lambda mod, a, name=name: seen.__setitem__(name, a)))
-    plan(x)
-    for h in hooks:
-        h.remove()
-    mods = dict(plan.named_modules())
-    for name, (t, g) in seen.items():
-        m = mods[name]
-        run = lambda t, m=m, g=g: m(t, g)  # noqa: E731
-        for _ in range(3):
-            run(t)
-        ms = timed(run, t, reps)
+    """Per GateLayer node (node_times): the kernel's time and bytes per second."""
+    rows = []
+    for name, m, (t, g), ms in node_times(plan, x, GateLayer, reps):
         n, c, h, w = t.shape
         nbytes = n * h * w * (c * (4 + 4 * m.want_out) + m.c_pad) + n * c * 4
         rows.append({"node": name, "input": [n, c, h, w], "floats_per_input_pixel": int(t.stride(3)), "c_pad": m.c_pad, "act": m.act,
@@ -61,19 +45,9 @@ def main():
     for tag, fam in CASES:
         torch.manual_seed(2333)
         model = merge_bn(W.mobilenet_v2(se=True).to(dev).eval(), inplace=True, allow_missing=True)
-        if fam == "fsptq":
-            quantize_model(model, copy.deepcopy(FSPTQ_W8A8), None, "FSPTQ", int8_gemm=True)
-        else:
-            quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
         x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
+        calibrated(model, fam, x)
         with torch.no_grad():
-            model(x[:64])                                   # calibrate
-            for m in model.modules():
-                if isinstance(m, FSPTQBase):
-                    m.in_offset.zero_()
-                    m._zp_is_int = None
-                elif isinstance(m, QBase) and m.in_offset is not None:
-                    m.in_offset.zero_()
             plans = {"gates": fuse_inference(model, gates=True), "flag_off": fuse_inference(model)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = gate_kernel_times(plans["gates"], x)

@@ -10,7 +10,6 @@ range of the flag-off plan's steps, whether the flag-on plan is faster by more t
 the two plans, and per swish node the kernel's time, bytes per second (per pixel: 4 C read, 4 C written if the fp32 map is wanted, c_pad
 code bytes written) and elements per second.  Writes profiles/swish_ab.json (and prints it).
 usage: python tools/swish_ab.py [batch] [steps]"""
-import copy
 import json
 import os
 import sys
@@ -20,13 +19,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "
 import torch  # noqa: E402
 
 import workloads as W  # noqa: E402
-from act_offset_ab import QBASE_W8A8  # noqa: E402
-from dlmc.quantization.scalar.FSPTQuant import FSPTQBase  # noqa: E402
-from dlmc.quantization.scalar.modules.base import QBase  # noqa: E402
 from dlmc.utils.fuse import SwishLayer, fuse_inference  # noqa: E402
 from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
-from relu6_ab import QCFG as FSPTQ_W8A8, timed  # noqa: E402
+from node_times import calibrated, node_times  # noqa: E402
+from relu6_ab import timed  # noqa: E402
 
 CASES = [("mbconv_se_fsptq_w8a8", "fsptq"), ("mbconv_se_qbase_w8a8", "qbase")]
 
@@ -38,20 +34,9 @@ def quartiles(v):
 
 
 def swish_kernel_times(plan, x, reps=20):
-    """Per SwishLayer node: its input as the plan hands it over, then the node alone, `reps` launches between two events."""
-    seen, hooks, rows = {}, [], []
-    for name, m in plan.named_modules():
-        if isinstance(m, SwishLayer):
-            hooks.append(m.register_forward_pre_hook(lambda mod, a, name=name: seen.__setitem__(name, a[0])))
-    plan(x)
-    for h in hooks:
-        h.remove()
-    mods = dict(plan.named_modules())
-    for name, t in seen.items():
-        m = mods[name]
-        for _ in range(3):
-            m(t)
-        ms = timed(m, t, reps)
+    """Per SwishLayer node (node_times): the kernel's time, bytes and elements per second."""
+    rows = []
+    for name, m, (t,), ms in node_times(plan, x, SwishLayer, reps):
         n, c, h, w = t.shape
         codes = m.c_pad if m.emit is not None else 0
         nbytes = n * h * w * (c * (4 + 4 * m.want_out) + codes)
@@ -69,19 +54,9 @@ def main():
     for tag, fam in CASES:
         torch.manual_seed(2333)
         model = merge_bn(W.mobilenet_v2(se=True, act="swish").to(dev).eval(), inplace=True, allow_missing=True)
-        if fam == "fsptq":
-            quantize_model(model, copy.deepcopy(FSPTQ_W8A8), None, "FSPTQ", int8_gemm=True)
-        else:
-            quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
         x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
+        calibrated(model, fam, x)
         with torch.no_grad():
-            model(x[:64])                                   # calibrate
-            for m in model.modules():
-                if isinstance(m, FSPTQBase):
-                    m.in_offset.zero_()
-                    m._zp_is_int = None
-                elif isinstance(m, QBase) and m.in_offset is not None:
-                    m.in_offset.zero_()
             plans = {"swish": fuse_inference(model, gates=True, swish=True), "flag_off": fuse_inference(model, gates=True)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = swish_kernel_times(plans["swish"], x)
