@@ -582,12 +582,12 @@ static dim3 dw_generic_shape(const DwCall& c, DwGeom&, int, size_t& lds) {
 }
 
 // the record of a depthwise entry point's ABI arguments; ep.x_off / ep.x_tap are the caller's to set.  Of `q_form`'s flag bits only the
-// two control bits are taken (dw_launch): the rest of it goes into the epilogue as it came.
+// three control bits are taken (dw_launch): the rest of it goes into the epilogue as it came.
 static DwCall dw_call(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale, const float* in_zero_point,
                       const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S,
                       int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
                       const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY;     // (include/dlmcq.h: control bits of `q_form`)
+  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT;     // (include/dlmcq.h: control bits of `q_form`)
   DwCall c{};
   c.x = x; c.w = w; c.out = out; c.bias = bias; c.s_in = in_scale; c.zp_in = in_zero_point; c.s_w = w_scale; c.w_off = w_offset;
   c.N = N; c.H = H; c.W = W; c.C = C; c.R = R; c.S = S; c.stride = stride; c.pad = pad;
@@ -601,32 +601,58 @@ static DwCall dw_call(const void* x, const int8_t* w, float* out, const float* b
   return c;
 }
 
+// The key of a validated call the vector kernels take, and the record DW_TABLE holds for it (null: none - the table is complete, so
+// never).  FAST (the 3 x 3 families): a codes-only layer with the plain quantiser, 1 asymmetric / 2 symmetric weights.  Computed ONCE per
+// call: the launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT) read this one record.
+static const DwVariant* dw_variant(const DwCall& c, bool wide, bool xoff) {
+  const DwFamily family = !wide ? DW_GENERIC : (c.stride == 1 && c.pad == 1 && c.C <= 1024) ? DW_P2 : DW_3;
+  const int fast = (wide && !c.out && epi_plain(c.ep)) ? (c.w_off ? 1 : 2) : 0;
+  const bool r6 = c.ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
+  for (const DwVariant& t : DW_TABLE)
+    if (t.family == family && t.fast == fast && t.r6 == r6 && t.xoff == xoff) return &t;
+  return nullptr;
+}
+// ... as the route query's answer (include/dlmcq.h: tag | family << 8 | FAST << 4 | 2 XOFF | 1 R6)
+static int dw_variant_answer(const DwVariant& v) {
+  return DLMCQ_ROUTE_DW_VARIANT_TAG | ((int)v.family << 8) | (v.fast << 4) | (v.xoff ? 2 : 0) | (v.r6 ? 1 : 0);
+}
+
+// The two tables, for tests (absent from include/dlmcq.h): `which` 0 = DW_TABLE, 1 = conv_dwm_i8_kernel's; fills up to `cap`
+// DLMCQ_ROUTE_DW_VARIANT answers in the table's order and returns how many there are (-1: no such table)
+extern "C" int dlmcq_x_dw_variant_table(int which, int32_t* answers, int cap) {
+  if (which == 1) return conv_dwm_table(answers, cap);
+  if (which != 0) return -1;
+  int n = 0;
+  for (const DwVariant& t : DW_TABLE) {
+    if (answers && n < cap) answers[n] = dw_variant_answer(t);
+    ++n;
+  }
+  return n;
+}
+
 static int dw_launch(const DwCall& c) {
+  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT;
+  if ((c.ctl & DLMCQ_ROUTE_DW_VARIANT) && !(c.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (a question about the route, never a launch)
   if (c.N < 0 || c.H < 1 || c.W < 1 || c.C < 4 || (c.C & 3) || c.R < 1 || c.S < 1 || c.R > 7 || c.S > 7 || c.stride < 1 || c.pad < 0)
     return DLMCQ_EINVAL;
   if (c.P < 1 || c.Q < 1) return DLMCQ_EINVAL;
   if (c.N == 0) return DLMCQ_OK;
   if (!c.x || !c.w || !(c.out || c.ep.codes) || !c.s_in || !c.s_w) return DLMCQ_EINVAL;
-  if (quantiser_check(c.ep.codes, c.ep.q_scale, c.q_lo, c.q_hi, c.q_form, DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY) != DLMCQ_OK) return DLMCQ_EINVAL;
+  if (quantiser_check(c.ep.codes, c.ep.q_scale, c.q_lo, c.q_hi, c.q_form, CTL) != DLMCQ_OK) return DLMCQ_EINVAL;
   if (!aligned4(c.x) || !aligned4(c.w) || !aligned16(c.s_w) || (c.w_off && !aligned16(c.w_off)) || (c.bias && !aligned16(c.bias)) ||
       (c.out && !aligned16(c.out)) || (c.ep.codes && !aligned4(c.ep.codes)))
     return DLMCQ_EALIGN;
   if (c.N * c.P * c.Q * (c.C / 4) >= (1ll << 31) || c.N * c.H * c.W * (c.C / 4) >= (1ll << 31)) return DLMCQ_ERANGE;
   const bool xoff = c.ep.x_off != nullptr;
+  const bool which = (c.ctl & DLMCQ_ROUTE_DW_VARIANT) != 0;     // (the route query names the instantiation instead of the family)
   if (!(c.ctl & DLMCQ_FORCE_TILED) && !xoff && conv_dwm_applies(c)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores
-    if (c.ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DWM;
+    if (c.ctl & DLMCQ_ROUTE_ONLY) return which ? conv_dwm_answer(c) : DLMCQ_ROUTE_DWM;
     return conv_dwm_launch(c);
   }
   const bool wide = c.R == 3 && c.S == 3 && c.C % 16 == 0 && c.C <= 2048 && aligned16(c.x) && (!c.ep.codes || aligned16(c.ep.codes));
   if (xoff && !wide) return DLMCQ_EINVAL;           // (the border term: the 3 x 3 kernels only)
-  if (c.ctl & DLMCQ_ROUTE_ONLY) return DLMCQ_ROUTE_DW;
-  // the key.  FAST (the 3 x 3 families): a codes-only layer with the plain quantiser, 1 asymmetric / 2 symmetric weights
-  const DwFamily family = !wide ? DW_GENERIC : (c.stride == 1 && c.pad == 1 && c.C <= 1024) ? DW_P2 : DW_3;
-  const int fast = (wide && !c.out && epi_plain(c.ep)) ? (c.w_off ? 1 : 2) : 0;
-  const bool r6 = c.ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
-  const DwVariant* v = nullptr;
-  for (const DwVariant& t : DW_TABLE)
-    if (t.family == family && t.fast == fast && t.r6 == r6 && t.xoff == xoff) v = &t;
+  const DwVariant* v = dw_variant(c, wide, xoff);
+  if (c.ctl & DLMCQ_ROUTE_ONLY) return !which ? DLMCQ_ROUTE_DW : v ? dw_variant_answer(*v) : DLMCQ_EINVAL;
   if (!v) return DLMCQ_EINVAL;
   DwGeom g;
   g.N = (int)c.N; g.H = (int)c.H; g.W = (int)c.W; g.C4 = (int)(c.C / 4); g.R = (int)c.R; g.S = (int)c.S; g.stride = c.stride; g.pad = c.pad;
@@ -635,7 +661,7 @@ static int dw_launch(const DwCall& c) {
   g.qdiv = make_fastdiv((uint32_t)c.Q);
   g.pdiv = make_fastdiv((uint32_t)c.P);
   size_t lds = 0;
-  const dim3 grid = (family == DW_P2 ? dw_p2_shape : family == DW_3 ? dw_3_shape : dw_generic_shape)(c, g, fast, lds);
+  const dim3 grid = (v->family == DW_P2 ? dw_p2_shape : v->family == DW_3 ? dw_3_shape : dw_generic_shape)(c, g, v->fast, lds);
   v->go(grid, lds, c, g);
   return launch_status();
 }

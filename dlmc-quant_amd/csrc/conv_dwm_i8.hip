@@ -255,8 +255,15 @@ static const DwmVariant DWM_TABLE[] = {DLMCQ_DWM_QUAD(4) DLMCQ_DWM_QUAD(5)};
 #undef DLMCQ_DWM_V
 static_assert(sizeof(DWM_TABLE) / sizeof(DWM_TABLE[0]) == 8, "the instantiations");
 
-int conv_dwm_launch(const DwCall& c) {
-  DwmArgs a{};
+// The kernel's record of a call conv_dwm_applies took, and the table's record for it (null: none - the table is complete, so never):
+// computed ONCE per call - the launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT) read this one plan
+struct DwmPlan {
+  DwmArgs a;
+  const DwmVariant* v;
+};
+static DwmPlan conv_dwm_plan(const DwCall& c) {
+  DwmPlan p{};
+  DwmArgs& a = p.a;
   a.x = static_cast<const int8_t*>(c.x); a.w = c.w; a.s_w = c.s_w; a.o_w = c.w_off; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
   a.N = (int)c.N; a.H = (int)c.H; a.W = (int)c.W; a.C = (int)c.C; a.x_signed = c.x_signed;
   a.Wp = (int)c.W + 1;
@@ -268,18 +275,39 @@ int conv_dwm_launch(const DwCall& c) {
   a.fsdiv = make_fastdiv((uint32_t)a.FS);
   a.wpdiv = make_fastdiv((uint32_t)a.Wp);
   a.codes = c.ep.codes;
+  const int hpw = (a.hp + 3) / 4 <= 4 ? 4 : 5;
+  const bool xs = c.x_signed != 0, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
+  for (const DwmVariant& t : DWM_TABLE)
+    if (t.hpw == hpw && t.xs == xs && t.r6 == r6) p.v = &t;
+  return p;
+}
+// ... as the route query's answer (include/dlmcq.h: tag | halo pieces per wave << 8 | 2 XS | 1 R6)
+static int conv_dwm_variant_answer(const DwmVariant& v) { return DLMCQ_ROUTE_DWM_VARIANT_TAG | (v.hpw << 8) | (v.xs ? 2 : 0) | (v.r6 ? 1 : 0); }
+
+int conv_dwm_answer(const DwCall& c) {
+  const DwmPlan p = conv_dwm_plan(c);
+  return p.v ? conv_dwm_variant_answer(*p.v) : DLMCQ_EINVAL;
+}
+
+int conv_dwm_table(int32_t* answers, int cap) {
+  int n = 0;
+  for (const DwmVariant& t : DWM_TABLE) {
+    if (answers && n < cap) answers[n] = conv_dwm_variant_answer(t);
+    ++n;
+  }
+  return n;
+}
+
+int conv_dwm_launch(const DwCall& c) {
+  const DwmPlan p = conv_dwm_plan(c);
+  if (!p.v) return DLMCQ_EINVAL;
+  const DwmArgs& a = p.a;
   // workgroups: three per CU (registers) in groups of `nchunks` that share their positions on one XCD
   int ngroups = ((device_cus() * 3) / a.nchunks) & ~7;
   if (ngroups < 8) ngroups = 8;
   const int maxg = (a.ntiles + 7) & ~7;
   if (ngroups > maxg) ngroups = maxg;
-  const int hpw = (a.hp + 3) / 4 <= 4 ? 4 : 5;
-  const bool xs = c.x_signed != 0, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
-  const DwmVariant* v = nullptr;
-  for (const DwmVariant& t : DWM_TABLE)
-    if (t.hpw == hpw && t.xs == xs && t.r6 == r6) v = &t;
-  if (!v) return DLMCQ_EINVAL;
-  hipLaunchKernelGGL(v->kernel, dim3((uint32_t)(ngroups * a.nchunks)), dim3(256), 0, c.st, a, c.ep);
+  hipLaunchKernelGGL(p.v->kernel, dim3((uint32_t)(ngroups * a.nchunks)), dim3(256), 0, c.st, a, c.ep);
   return launch_status();
 }
 

@@ -290,8 +290,8 @@ struct DwCall {
   int32_t stride, pad;
   int x_signed;
   hipStream_t st;
-  ConvEpi ep;                      // ep.q_form: `q_form` without the two control bits; ep.x_off / ep.x_tap: the _xoff entry point's
-  uint32_t ctl;                    // DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY as passed in `q_form`
+  ConvEpi ep;                      // ep.q_form: `q_form` without the control bits; ep.x_off / ep.x_tap: the _xoff entry point's
+  uint32_t ctl;                    // DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT as passed in `q_form`
   int32_t q_lo, q_hi, q_form;      // as passed (dw_launch validates these)
   int64_t P, Q;                    // derived by dw_call
 };
@@ -299,6 +299,8 @@ struct DwCall {
 // conv_dwm_i8.hip: depthwise 3 x 3 / stride 1 / padding 1 codes-to-codes layers on the matrix cores (diagonal weight fragments)
 bool conv_dwm_applies(const DwCall& c);
 int conv_dwm_launch(const DwCall& c);
+int conv_dwm_answer(const DwCall& c);                          // DLMCQ_ROUTE_DW_VARIANT: which instantiation the launch picks (include/dlmcq.h)
+int conv_dwm_table(int32_t* answers, int cap);                 // every instantiation the launcher holds, as such answers; returns how many
 
 // conv_stem_pool7_i8.hip: the ResNet first layer (7x7 / 2 + ReLU + 3x3 / 2 max-pool + quantiser) with the pooling in registers
 bool stem_pool7_applies(const StemCall& c);

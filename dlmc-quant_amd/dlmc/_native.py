@@ -38,6 +38,10 @@ ROUTE_VARIANT_TAG = 1 << 24
 ROUTE_HALO_VARIANT = 0x20000  # DLMCQ_ROUTE_HALO_VARIANT: with ROUTE_ONLY, a ROUTE_HALO3X3 / ROUTE_HALO3X3_PIPE answer names the instantiation instead (decode_halo_variant)
 ROUTE_HALO_VARIANT_TAG, ROUTE_PIPE_VARIANT_TAG = 1 << 25, 1 << 26
 HV_PLAIN, HV_XS, HV_S2 = 1, 2, 4   # the flags of such an answer (include/dlmcq.h)
+ROUTE_DW_VARIANT = 0x40000  # DLMCQ_ROUTE_DW_VARIANT: with ROUTE_ONLY, a ROUTE_DW / ROUTE_DWM answer of the depthwise entry points names the instantiation instead (decode_dw_variant)
+ROUTE_DW_VARIANT_TAG, ROUTE_DWM_VARIANT_TAG = 1 << 27, 1 << 28
+DV_R6, DV_XOFF, DV_XS = 1, 2, 2    # the flags of such an answer: R6 in both, XOFF in a DW_TABLE answer, XS in a DWM_TABLE one (include/dlmcq.h)
+DW_FAMILIES = ("p2", "dw3", "generic")   # conv_dw3p2_i8_kernel, conv_dw3_i8_kernel, conv_dw_i8_kernel: the family field of a DW_TABLE answer
 # the `flags` of a ROUTE_VARIANT answer: conv_i8_mfma_kernel's boolean template parameters (include/dlmcq.h)
 CV_DUAL, CV_ADIR, CV_ASYM, CV_SWAP, CV_R6, CV_XOFF, CV_NARROW, CV_PADRES = 1, 2, 4, 8, 16, 32, 64, 128
 ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO3X3_PIPE, ROUTE_GAP = 1, 2, 3, 4, 5, 6, 7, 8
@@ -247,6 +251,30 @@ def conv3x3_variant_tables():
         answers = (ctypes.c_int32 * n)()
         assert fn(which, answers, n) == n
         out.append([decode_halo_variant(int(a)) for a in answers])
+    return tuple(out)
+
+
+def decode_dw_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_DW_VARIANT call of a depthwise entry point -> ("dw", family ("p2" / "dw3" / "generic"), FAST, R6, XOFF) of the
+    csrc/conv_dw_i8.hip instantiation, ("dwm", halo pieces per wave, XS, R6) of the conv_dwm_i8_kernel one, or None when the answer is neither
+    (a ROUTE_*, another kernel's variant, DLMCQ_OK, a refusal)."""
+    if rc >> 29 or rc < ROUTE_DW_VARIANT_TAG:
+        return None
+    if rc & ROUTE_DWM_VARIANT_TAG:
+        return None if rc & ROUTE_DW_VARIANT_TAG else ("dwm", (rc >> 8) & 0xff, bool(rc & DV_XS), bool(rc & DV_R6))
+    family = (rc >> 8) & 0xff
+    return None if family >= len(DW_FAMILIES) else ("dw", DW_FAMILIES[family], (rc >> 4) & 0xf, bool(rc & DV_R6), bool(rc & DV_XOFF))
+
+
+def dw_variant_tables():
+    """(DW_TABLE records, DWM_TABLE records), decoded: the depthwise instantiations the library holds, as its own launchers list them."""
+    fn = experimental("dlmcq_x_dw_variant_table", [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    out = []
+    for which in (0, 1):
+        n = fn(which, None, 0)
+        answers = (ctypes.c_int32 * n)()
+        assert fn(which, answers, n) == n
+        out.append([decode_dw_variant(int(a)) for a in answers])
     return tuple(out)
 
 

@@ -136,6 +136,20 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
 #define DLMCQ_ROUTE_HALO_VARIANT 0x20000
 #define DLMCQ_ROUTE_HALO_VARIANT_TAG (1 << 25)
 #define DLMCQ_ROUTE_PIPE_VARIANT_TAG (1 << 26)
+/* DLMCQ_ROUTE_DW_VARIANT (dlmcq_conv2d_dw_i8_nhwc and dlmcq_conv2d_dw_i8_nhwc_xoff; as the two bits above: OR-able only TOGETHER with
+ * DLMCQ_ROUTE_ONLY, alone it is DLMCQ_EINVAL; every entry point that takes no route query refuses it as it refuses any bit it does not
+ * know): where the route query would answer DLMCQ_ROUTE_DW or DLMCQ_ROUTE_DWM it answers WHICH instantiation the call launches instead -
+ * the record the launcher itself picks the kernel from:
+ *   csrc/conv_dw_i8.hip:   DLMCQ_ROUTE_DW_VARIANT_TAG | (family << 8) | (FAST << 4) | flags
+ *     family 0 conv_dw3p2_i8_kernel (3x3 / 1 / 1, two pixels per thread), 1 conv_dw3_i8_kernel (any other 3x3), 2 conv_dw_i8_kernel (any
+ *     filter up to 7x7); FAST 0 (any epilogue), 1 / 2 (codes only with the plain quantiser, asymmetric / symmetric weights);
+ *     flags: 2 XOFF (float activation offset), 1 R6 (ReLU6);
+ *   conv_dwm_i8_kernel:    DLMCQ_ROUTE_DWM_VARIANT_TAG | (halo pieces per wave << 8) | flags        pieces 4 or 5; flags: 2 XS (int8
+ *     codes: no re-centring), 1 R6.
+ * Both above every other answer; every other answer - DLMCQ_OK for an empty problem, a refusal - is what it is without the bit. */
+#define DLMCQ_ROUTE_DW_VARIANT 0x40000
+#define DLMCQ_ROUTE_DW_VARIANT_TAG (1 << 27)
+#define DLMCQ_ROUTE_DWM_VARIANT_TAG (1 << 28)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */

@@ -265,6 +265,7 @@ class FullLayer:
     bias: torch.Tensor
     nz: int
     live: int
+    groups: int = 1                 # the depthwise form: groups = channels, wq (C, 1, R, S)
 
     @property
     def unit(self):                 # s_in * s_w[k], float64 (a power of two: exact)
@@ -300,24 +301,31 @@ def full_range_bias(k, nz, live, unit, gen, edge=True):
     return b
 
 
-def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asym=False, zp=None, live=None, edge_bias=True, zp_side=None):
-    """Random full-range operands (see above).  zp: the input zero point - default: an integer in 1..254 other than 128 for uint8 codes,
+def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asym=False, zp=None, live=None, edge_bias=True, zp_side=None,
+                          depthwise=False):
+    """Random full-range operands (see above).  `depthwise`: k == c groups of one channel - wq is (C, 1, R, S), the input scale is sized
+    from the R S taps of one channel, and the codes lie in memory as NHWC (a permuted view: the depthwise tensors are large).  zp: the input zero point - default: an integer in 1..254 other than 128 for uint8 codes,
     0 for int8 codes.  `live`: channels [live, k)
     are all zero (the padding of a narrow layer).  `zp_side`: "high" / "low" - a uint8 zero point above / below 128 (padded calls: the pad-table
     byte has its high bit set, or not; a wrong sign or shift of the padding shows in the first); default: either."""
     s = r if s is None else s
     live = k if live is None else live
     nz = min(len(EDGE_VALUES), live - max(8, live // 4))
+    assert not depthwise or k == c
+    shape = (n, h, w, c) if depthwise else (n, c, h, w)
     if signed_in:
-        codes = torch.randint(-128, 128, (n, c, h, w), generator=gen).to(torch.int8)
+        codes = torch.randint(-128, 128, shape, generator=gen).to(torch.int8)
         zp = 0 if zp is None else zp
     else:
-        codes = torch.randint(0, 256, (n, c, h, w), generator=gen).to(torch.uint8)
+        codes = torch.randint(0, 256, shape, generator=gen).to(torch.uint8)
         if zp is None:
             d = int(torch.randint(1, 127, (1,), generator=gen))
             up = bool(torch.randint(0, 2, (1,), generator=gen)) if zp_side is None else zp_side == "high"
             zp = 128 + d if up else 128 - d
-    wq = torch.randint(-127, 128, (k, c, r, s), generator=gen).to(torch.int8)
+    if depthwise:
+        codes = codes.permute(0, 3, 1, 2)
+    cin = 1 if depthwise else c
+    wq = torch.randint(-127, 128, (k, cin, r, s), generator=gen).to(torch.int8)
     wq[:nz] = 0
     wq[live:] = 0
     s_w = (2.0 ** -(10 + torch.arange(k) % 5).double()).float()
@@ -329,8 +337,31 @@ def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asy
     # the input scale: a power of two that puts the widest-scale channels' outputs at FULL_TARGET_SIGMA (from the shape alone: the
     # integer sum of r s c products of a uniform byte about its zero point and a uniform weight code)
     mean = (-0.5 if signed_in else 127.5) - zp
-    sigma_int = math.sqrt(r * s * c) * math.sqrt((127 * 128) / 3.0) * math.sqrt((256 * 256 - 1) / 12.0 + mean * mean)
+    sigma_int = math.sqrt(r * s * cin) * math.sqrt((127 * 128) / 3.0) * math.sqrt((256 * 256 - 1) / 12.0 + mean * mean)
     s_in = 2.0 ** round(math.log2(FULL_TARGET_SIGMA / (sigma_int * 2.0 ** -10)))
-    lay = FullLayer(codes, int(zp), wq, s_w, w_int, s_in, torch.zeros(k), nz, live)
+    if depthwise and s_in == 1.0:
+        s_in = 0.5                  # (a 1 x 1 filter: the target lands on 1, and a scale of 1 hides a dropped multiplication)
+    lay = FullLayer(codes, int(zp), wq, s_w, w_int, s_in, torch.zeros(k), nz, live, c if depthwise else 1)
     lay.bias = full_range_bias(k, nz, live, lay.unit, gen, edge=edge_bias)
     return lay
+
+
+def second_gemm_full_ref(codes1, q1, wq2, s_w2, bias2, act2=1, w_int2=None):
+    """second_gemm_ref on full-range operands: the 1x1 layer that reads the reference's own first-stage codes as (code - zp) * q1.scale
+    against weight codes in +-127 with dyadic per-channel scales s_w2 [K] and, in the asymmetric form, a weight offset of w_int2[k] units
+    of s_w2[k].  codes1: (N, C, P, Q) bytes of quantise(.., q1), unshifted; asserts |SUM (code - zp) qw| < 2^24 (the kernel's fma takes
+    the integer sum as an fp32 number) and that the result is one."""
+    assert q1.lo == 0 and q1.hi == 255 and not q1.shift128
+    ci = codes1.to(torch.int32).double() - (0.0 if q1.zp is None else q1.zp)
+    isum = F.conv2d(ci, wq2.double())
+    assert float(isum.abs().max()) < float(1 << 24), "the second layer's integer sum is no fp32 number"
+    w = wq2.double() if w_int2 is None else wq2.double() + w_int2.double().reshape(-1, 1, 1, 1)
+    y = F.conv2d(ci * q1.scale, w * s_w2.double().reshape(-1, 1, 1, 1))
+    unit = q1.scale * s_w2.double().reshape(1, -1, 1, 1)
+    first = exact_f32(isum * unit + bias2.double().reshape(1, -1, 1, 1), "second layer: fma(sum, s_in s_w, bias)").double()
+    if w_int2 is not None:
+        first = exact_f32(first + ci.sum(dim=1, keepdim=True) * (w_int2.double().reshape(1, -1, 1, 1) * unit), "second layer: + rowsum * s_in w_off").double()
+    y = y + bias2.double().reshape(1, -1, 1, 1)
+    ok = (first == y) | (first.isnan() & y.isnan())
+    assert bool(ok.all()), "second layer: the staged chain and the convolution of the dequantised operands disagree"
+    return exact_f32(activation(y, act2), "second layer output")
