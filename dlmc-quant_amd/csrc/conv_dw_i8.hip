@@ -8,14 +8,9 @@
 //     EXACTLY (|S1| <= 9 * 255 * 255), so the arithmetic is the integer arithmetic of conv_i8.hip;
 //   * out = s_in * (s_w[c] * S1 + o_w[c] * S0) + bias[c]; asymmetric weights (w' = qw * s_w + o_w, ops.py:129-136) cost one
 //     more multiply-add per element; ReLU and the consumer's quantiser (conv_epilogue.h) follow in registers.
-#include "conv_i8_common.h"
+#include "conv_dw_common.h"     // DwGeom, u32x4, dot4_from, DW_BIG, dw_call, dw_checks: shared with conv_dw5_i8.hip
 
 namespace dlmcq {
-
-struct DwGeom {
-  int N, H, W, C4, R, S, stride, pad, P, Q;    // C4 = C / 4
-  FastDiv cdiv, qdiv, pdiv;
-};
 
 __device__ __forceinline__ f32x4 bytes_u(uint32_t a) {
   return f32x4{(float)(a & 0xff), (float)((a >> 8) & 0xff), (float)((a >> 16) & 0xff), (float)(a >> 24)};   // v_cvt_f32_ubyte0..3
@@ -23,17 +18,6 @@ __device__ __forceinline__ f32x4 bytes_u(uint32_t a) {
 __device__ __forceinline__ f32x4 bytes_s(uint32_t a) {
   return f32x4{(float)(int8_t)a, (float)(int8_t)(a >> 8), (float)(int8_t)(a >> 16), (float)(int8_t)(a >> 24)};
 }
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// the first v_dot4_i32_i8 of a chain in its three-address form: the compiler renders __builtin_amdgcn_sdot4 as the accumulating
-// v_dot4c_i32_i8, which needs a v_mov of the start value whenever that value is shared between chains (it always is here)
-__device__ __forceinline__ int dot4_from(uint32_t a, uint32_t b, int c) {
-  int d;
-  asm("v_dot4_i32_i8 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-constexpr int DW_BIG = 0x7fff0000;      // a byte offset beyond every tensor the buffer-addressed tap loads accept
 
 // 3 x 3, 16 channels per thread (C % 16 == 0): every tap is ONE 16-byte load per lane, all 9 taps requested before the first
 // is used; a tap outside the image reads a clamped address and is replaced by the zero point.  The first version converted
@@ -581,26 +565,6 @@ static dim3 dw_generic_shape(const DwCall& c, DwGeom&, int, size_t& lds) {
   return dim3((uint32_t)(blocks < (1 << 20) ? blocks : (1 << 20)));
 }
 
-// the record of a depthwise entry point's ABI arguments; ep.x_off / ep.x_tap are the caller's to set.  Of `q_form`'s flag bits only the
-// three control bits are taken (dw_launch): the rest of it goes into the epilogue as it came.
-static DwCall dw_call(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale, const float* in_zero_point,
-                      const float* w_scale, const float* w_offset, int64_t N, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S,
-                      int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes, const float* q_scale,
-                      const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT;     // (include/dlmcq.h: control bits of `q_form`)
-  DwCall c{};
-  c.x = x; c.w = w; c.out = out; c.bias = bias; c.s_in = in_scale; c.zp_in = in_zero_point; c.s_w = w_scale; c.w_off = w_offset;
-  c.N = N; c.H = H; c.W = W; c.C = C; c.R = R; c.S = S; c.stride = stride; c.pad = pad;
-  c.x_signed = x_is_unsigned ? 0 : 1;
-  c.st = reinterpret_cast<hipStream_t>(stream);
-  c.ep = make_epi_form(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form & ~CTL, q_ste_g);
-  c.ctl = (uint32_t)q_form & CTL;
-  c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form;
-  c.P = conv_out_size(H, R, stride, pad, 1);
-  c.Q = conv_out_size(W, S, stride, pad, 1);
-  return c;
-}
-
 // The key of a validated call the vector kernels take, and the record DW_TABLE holds for it (null: none - the table is complete, so
 // never).  FAST (the 3 x 3 families): a codes-only layer with the plain quantiser, 1 asymmetric / 2 symmetric weights.  Computed ONCE per
 // call: the launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT) read this one record.
@@ -631,18 +595,8 @@ extern "C" int dlmcq_x_dw_variant_table(int which, int32_t* answers, int cap) {
 }
 
 static int dw_launch(const DwCall& c) {
-  constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT;
-  if ((c.ctl & DLMCQ_ROUTE_DW_VARIANT) && !(c.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (a question about the route, never a launch)
-  if (c.N < 0 || c.H < 1 || c.W < 1 || c.C < 4 || (c.C & 3) || c.R < 1 || c.S < 1 || c.R > 7 || c.S > 7 || c.stride < 1 || c.pad < 0)
-    return DLMCQ_EINVAL;
-  if (c.P < 1 || c.Q < 1) return DLMCQ_EINVAL;
-  if (c.N == 0) return DLMCQ_OK;
-  if (!c.x || !c.w || !(c.out || c.ep.codes) || !c.s_in || !c.s_w) return DLMCQ_EINVAL;
-  if (quantiser_check(c.ep.codes, c.ep.q_scale, c.q_lo, c.q_hi, c.q_form, CTL) != DLMCQ_OK) return DLMCQ_EINVAL;
-  if (!aligned4(c.x) || !aligned4(c.w) || !aligned16(c.s_w) || (c.w_off && !aligned16(c.w_off)) || (c.bias && !aligned16(c.bias)) ||
-      (c.out && !aligned16(c.out)) || (c.ep.codes && !aligned4(c.ep.codes)))
-    return DLMCQ_EALIGN;
-  if (c.N * c.P * c.Q * (c.C / 4) >= (1ll << 31) || c.N * c.H * c.W * (c.C / 4) >= (1ll << 31)) return DLMCQ_ERANGE;
+  int status;
+  if (!dw_checks(c, false, status)) return status;     // (conv_dw_common.h: the checks, in their one order)
   const bool xoff = c.ep.x_off != nullptr;
   const bool which = (c.ctl & DLMCQ_ROUTE_DW_VARIANT) != 0;     // (the route query names the instantiation instead of the family)
   if (!(c.ctl & DLMCQ_FORCE_TILED) && !xoff && conv_dwm_applies(c)) {   // codes-only 3 x 3 / 1 / 1 layers: the multiply-adds on the matrix cores

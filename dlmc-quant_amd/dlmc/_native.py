@@ -108,6 +108,8 @@ SIGNATURES = {
                                                   _f32, _i64, _p]),
     "dlmcq_conv2d_dw_i8_nhwc": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
                                               _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_conv2d_dw5_i8_nhwc": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
+                                               _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_conv2d_i8_nhwc_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                                 _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _f32, _p, _p, _p]),
     "dlmcq_conv2d_dw_i8_nhwc_xoff": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32,
@@ -264,6 +266,26 @@ def decode_dw_variant(rc):
         return None if rc & ROUTE_DW_VARIANT_TAG else ("dwm", (rc >> 8) & 0xff, bool(rc & DV_XS), bool(rc & DV_R6))
     family = (rc >> 8) & 0xff
     return None if family >= len(DW_FAMILIES) else ("dw", DW_FAMILIES[family], (rc >> 4) & 0xf, bool(rc & DV_R6), bool(rc & DV_XOFF))
+
+
+ROUTE_DW5_VARIANT_TAG = 1 << 29      # DLMCQ_ROUTE_DW5_VARIANT_TAG: dlmcq_conv2d_dw5_i8_nhwc's answer to ROUTE_ONLY | ROUTE_DW_VARIANT
+
+
+def decode_dw5_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_DW_VARIANT call of dlmcq_conv2d_dw5_i8_nhwc -> ("dw5", FAST, R6) of the conv_dw5_i8_kernel
+    instantiation, or None when the answer is none (DLMCQ_OK, a refusal, another entry point's answer)."""
+    if rc < ROUTE_DW5_VARIANT_TAG or rc >> 30 or rc & ~(ROUTE_DW5_VARIANT_TAG | 0x31) or (rc >> 4) & 3 == 3:
+        return None
+    return ("dw5", (rc >> 4) & 3, bool(rc & DV_R6))
+
+
+def dw5_variant_table():
+    """The conv_dw5_i8_kernel instantiations the library holds, decoded, as its own launcher lists them (csrc/conv_dw5_i8.hip: DW5_TABLE)."""
+    fn = experimental("dlmcq_x_dw5_variant_table", [ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    n = fn(None, 0)
+    answers = (ctypes.c_int32 * n)()
+    assert fn(answers, n) == n
+    return [decode_dw5_variant(int(a)) for a in answers]
 
 
 def dw_variant_tables():

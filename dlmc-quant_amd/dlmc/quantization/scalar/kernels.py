@@ -685,6 +685,47 @@ def conv2d_dw_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, strid
     return (out, q[0]) if emit is not None else out
 
 
+DW5_MAX_C = 2048      # channels dlmcq_conv2d_dw5_i8_nhwc's LDS table holds
+
+
+def dw5_supported(c, stride, padding, kernel_size):
+    """Whether dlmcq_conv2d_dw5_i8_nhwc takes a depthwise layer of c channels: 5 x 5, padding 2, stride 1 or 2,
+    c % 16 == 0, c <= 2048 - the entry point's own geometry rules (csrc/conv_dw5_i8.hip)."""
+    return int(kernel_size) == 5 and int(padding) == 2 and int(stride) in (1, 2) and c % 16 == 0 and 16 <= c <= DW5_MAX_C
+
+
+def dw5_profitable(c, h, w, stride):
+    """Whether the 5 x 5 kernel was measured faster than the generic one (dlmcq_conv2d_dw_i8_nhwc's route) on a supported layer of c padded
+    channels and an h x w input (tools/dw5_ab.py, profiles/dw5_ab.json).  No shape of the sweep was slower - the
+    narrowest margin, 1152 channels at 7 x 7, is 1.8 times - so every supported layer is taken."""
+    return True
+
+
+def conv2d_dw5_i8(codes, wq, bias, in_scale, in_zp, w_scale, w_offset=None, stride=1, relu=False, emit=None, want_out=True, act=None):
+    """Depthwise 5 x 5 convolution with padding 2 on activation codes, on the integer dot-product kernel (dlmcq_conv2d_dw5_i8_nhwc):
+    conv2d_dw_i8's arguments without `padding`, and bit for bit its result on wq [5, 5, C] for an integer input zero point.  C % 16 == 0,
+    C <= 2048, stride 1 or 2 (K.dw5_supported); no float activation offset."""
+    N.require_gpu(codes, wq)
+    n, c, h, w_ = codes.shape
+    codes = _nhwc(codes)
+    if tuple(wq.shape[:2]) != (5, 5):
+        raise ValueError(f"conv2d_dw5_i8: weights [5, 5, C], not {tuple(wq.shape)}")
+    P, Q = _out_hw(h, w_, 5, 5, stride, 2)
+    if not want_out and emit is None:
+        raise ValueError("conv2d_dw5_i8: nothing to produce (want_out=False without emit)")
+
+    def alloc(dtype):
+        return torch.empty((n, c, P, Q), dtype=dtype, device=codes.device, memory_format=torch.channels_last)
+    q = _quantiser(emit, alloc, codes, False, "conv2d_dw5_i8")
+    out = alloc(torch.float32) if want_out else None
+    small = (_bias_c(bias), _flat(in_scale, codes), _flat(in_zp, codes), _flat(w_scale, codes), _flat(w_offset, codes))
+    args = (N.ptr(codes), N.ptr(wq), N.ptr(out), *map(N.ptr, small), n, h, w_, c, int(stride), 2, int(codes.dtype == torch.uint8), _act(relu, act))
+    oe = n * c * P * Q
+    PROFILE.launch("conv_dw5", codes.numel() + wq.numel() + oe * (4 * want_out + (emit is not None)),
+                   lambda: N.check(N.lib.dlmcq_conv2d_dw5_i8_nhwc(*args, *_q_args(q, 0), N.stream_ptr())), 2 * oe * 25)
+    return (out, q[0]) if emit is not None else out
+
+
 DWPW_WIDTHS = (128, 192, 512)      # pointwise output widths dlmcq_conv2d_dwpw_i8_nhwc is built for
 
 

@@ -154,6 +154,18 @@ def _xoff_kernel_exists(mod, kind):
     return w.shape[2] in (3, 7)          # "stem"
 
 
+def _takes_dw5(spec, mod):
+    """Whether a planned layer runs on the 5 x 5 depthwise kernel under fuse_inference(dw5=True): a depthwise 5 x 5 filter with padding 2
+    and stride 1 or 2 in both axes, at most 2048 channels once padded to 64, an input quantiser without a float offset (that kernel has no
+    border term: such a padded 5 x 5 layer is not planned at all, _xoff_kernel_exists), and no shape measured slower (K.dw5_profitable)."""
+    w = mod.weight
+    if spec.kind != "dw" or spec.act.xoff or w.dim() != 4 or tuple(w.shape[2:]) != (5, 5):
+        return False
+    if len(set(mod.stride)) != 1 or len(set(mod.padding)) != 1 or tuple(getattr(mod, "dilation", (1, 1))) != (1, 1):
+        return False
+    return K.dw5_supported(_ceil64(w.shape[0]), mod.stride[0], mod.padding[0], 5)
+
+
 def _fsptq_spec(mod, kind):
     if not (mod.act_quant and mod.wt_quant) or mod.in_scale.numel() != 1:
         return None
@@ -233,7 +245,7 @@ class _PlanLayer(nn.Module):
         self.xoff_padded = False     # the border term runs in the kernel (the *_xoff entry points)
 
     def _structure(self, layer, spec, relu=False, emit=None, want_out=True, pool=None, relu6=False, narrow=False, pad_shortcut=None,
-                   emit_shift=False):
+                   emit_shift=False, dw5=False):
         """What the plan's passes read off a node - the layer's shape and quantisers, and what the main pass decided for it
         (_Decision.options).  The whole of a `dry_run="chains"` stand-in; needs no GPU."""
         self.layer, self.act, self.kind = layer, spec.act, spec.kind
@@ -261,6 +273,8 @@ class _PlanLayer(nn.Module):
         # epilogue (K.PadShortcut, dlmcq_conv2d_i8_nhwc_padres: the narrow path, at k == k_pad too)
         self.pad_shortcut = pad_shortcut
         self.emit_shift = bool(emit_shift)      # (see __init__; stand-ins: False - the chain pass clears it anyway)
+        # the 5 x 5 integer dot-product kernel (fuse_inference(dw5=True); DwInt8Layer only): K.conv2d_dw5_i8 instead of K.conv2d_dw_i8
+        self.dw5 = bool(dw5)
 
     def _fold_offset(self, tap):
         """A float activation offset o (act.xoff): `tap` [k_pad, R, S] (float64, on the device) = per output channel and tap the sum of the
@@ -454,7 +468,7 @@ class Int8Layer(_PlanLayer):
 
 
 class DwInt8Layer(Int8Layer):
-    """A depthwise convolution of the frozen plan (csrc/conv_dw_i8.hip): codes in, codes (and / or fp32) out."""
+    """A depthwise convolution of the frozen plan (csrc/conv_dw_i8.hip; `dw5`: csrc/conv_dw5_i8.hip): codes in, codes (and / or fp32) out."""
 
     def __init__(self, layer, spec, **kw):
         _PlanLayer.__init__(self, layer, spec, **kw)
@@ -478,9 +492,13 @@ class DwInt8Layer(Int8Layer):
         codes = self._codes(x)
         numel = self._real_numel(codes)
         emit = self._emit_for(codes.shape[0], self.k, *self._out_hw(codes))
-        res = K.conv2d_dw_i8(codes, self.wq, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale, self.w_off,
-                             stride=lay.stride[0], padding=lay.padding[0], act=self._act_arg(), emit=emit, want_out=self.want_out,
-                             **self._xoff_kw())
+        if self.dw5:      # (5 x 5 / padding 2 / no float offset: decided by the main pass)
+            res = K.conv2d_dw5_i8(codes, self.wq, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale, self.w_off,
+                                  stride=lay.stride[0], act=self._act_arg(), emit=emit, want_out=self.want_out)
+        else:
+            res = K.conv2d_dw_i8(codes, self.wq, self._bias(), self._in_scale(numel), self._zp(codes), self.w_scale, self.w_off,
+                                 stride=lay.stride[0], padding=lay.padding[0], act=self._act_arg(), emit=emit, want_out=self.want_out,
+                                 **self._xoff_kw())
         out, out_codes = res if emit is not None else (res, None)
         return self._finish(out, out_codes)
 
@@ -1453,6 +1471,7 @@ class FusionReport:
         self.pad_shortcuts = 0   # option-A shortcuts (subsample + zero-pad) read in place by the layer's epilogue (fuse_inference(pad_shortcuts=True))
         self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
         self.gates = 0        # squeeze-excite gates (x * g, + ReLU / ReLU6) handing the plan layers behind them their codes (fuse_inference(gates=True))
+        self.dw5 = 0          # 5x5 depthwise layers on the integer dot-product kernel, csrc/conv_dw5_i8.hip (fuse_inference(dw5=True))
         self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
@@ -1468,6 +1487,7 @@ class FusionReport:
         self.act_offset += d.spec.act.xoff + (d.dual and d.dual_spec.act.xoff)
         self.residual += d.residual is not None
         self.narrow += d.narrow
+        self.dw5 += d.dw5
         self.pad_shortcuts += d.pad_shortcut is not None
         self.emit += d.emit is not None
         self.fp32_outputs += d.want_out
@@ -1483,6 +1503,7 @@ class FusionReport:
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
                 (f"gates on the plan={self.gates}, " if self.gates else "") +
                 (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
+                (f"5x5 depthwise on the dot-product kernel={self.dw5}, " if self.dw5 else "") +
                 f"not eligible={self.skipped})")
 
 
@@ -1797,6 +1818,7 @@ class _Decision:
         self.pad_shortcut = None               # `residual` is an option-A shortcut (_PadShortcut), read in place at its source
         self.emit, self.takers = None, ()      # the quantiser (_ActSpec) of the readers that take codes, and those readers
         self.want_out, self.narrow = True, False       # someone reads the fp32 output; fp32 rows at the real width
+        self.dw5 = False                       # a depthwise 5x5 / padding 2 layer on csrc/conv_dw5_i8.hip's kernel (fuse_inference(dw5=True))
         self.dual_mod = self.dual_spec = None  # the convolution on the shortcut, run by the same (dual) kernel, and its spec
         self.dual_inputs = None                # a dual node's activation quantisers: of its input 0, of its input 1
 
@@ -1819,7 +1841,7 @@ class _Decision:
 
     def options(self):
         """The decision as _PlanLayer._structure takes it."""
-        return dict(relu=self.relu, relu6=self.relu6, emit=self.emit, want_out=self.want_out, pool=self.pool, narrow=self.narrow,
+        return dict(relu=self.relu, relu6=self.relu6, emit=self.emit, want_out=self.want_out, pool=self.pool, narrow=self.narrow, dw5=self.dw5,
                     pad_shortcut=None if self.pad_shortcut is None else (self.pad_shortcut.stride, self.pad_shortcut.lo))
 
 
@@ -1833,7 +1855,8 @@ class _MainPass:
     build (the module, by mode), splice (the graph), FusionReport.count.  A new flag is a field of _Decision set in `decide`, handed to
     the node by `_Decision.options` / `_PlanLayer._structure` and counted in `FusionReport.count`."""
 
-    def __init__(self, gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts):
+    def __init__(self, gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts, dw5=False):
+        self.dw5 = dw5
         self.gm, self.graph, self.modules = gm, gm.graph, dict(gm.named_modules())
         self.dry_run, self.weight_blob, self.dwpw = dry_run, weight_blob, dwpw
         self.relu6, self.act_offsets, self.narrow_rows, self.pad_shortcuts = relu6, act_offsets, narrow_rows, pad_shortcuts
@@ -1919,6 +1942,7 @@ class _MainPass:
         self._decide_dual(d, unpadded)
         # every narrow-capable layer that writes fp32 (or reads a shortcut) does so at the real width
         d.narrow = bool(can_narrow and (d.want_out or d.residual is not None))
+        d.dw5 = bool(self.dw5 and _takes_dw5(spec, mod))
         return d
 
     def _decide_pool(self, d):
@@ -2021,7 +2045,7 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None, gates=False, swish=False):
+                   recompute_shortcuts=None, gates=False, swish=False, dw5=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2134,7 +2158,20 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     The pass runs before the gate pass, which finds its gates behind the swish nodes.  Measured (tools/swish_ab.py,
     profiles/swish_ab.json; the MBConv-SE network, 35 swishes, batch 1024 at 224^2, gates=True in both, interleaved): flag off / flag on
     = 67.53 / 41.80 ms per step (FSPTQ W8A8), 67.58 / 41.97 (QBase W8A8), ratio 1.61 at a spread of 0.14 / 0.24 ms.  Off by default: the
-    plan without it is the plan as it was."""
+    plan without it is the plan as it was.
+    `dw5=True`: a depthwise 5x5 layer with padding 2 and stride 1 or 2 - 9 of the 16 depthwise layers of EfficientNet-B0,
+    MobileNetV3's (`workloads.InvertedResidual(..., k=5)`) - runs on the integer dot-product kernel of csrc/conv_dw5_i8.hip (K.conv2d_dw5_i8:
+    byte transposes + v_dot4_i32_i8, as the 3x3 kernels) instead of the any-filter kernel, which converts every byte of every tap to fp32
+    (`fusion_report.dw5` counts the layers).  Taken: a "dw" plan layer whose filter is 5x5, padding 2 and stride 1 or 2 in both axes, at most
+    2048 channels once padded to 64, whose input quantiser has no float offset; everything else about the node - codes in, codes and / or
+    fp32 out, ReLU / ReLU6, channel padding, shifted codes - is as it is.  Left on today's route: any other filter or padding (the reference's
+    SameConv, an F.pad in front of an unpadded convolution, included), wider layers; a padded 5x5 layer behind a float activation offset
+    stays unplanned.  Same exact integer sums, same fp32 steps in the same order: bit-identical to the plan without the flag
+    (tests/test_gpu_dw5.py: torch.equal against K.conv2d_dw_i8 and between the two plans' logits).  Measured stand-alone (tools/dw5_ab.py,
+    profiles/dw5_ab.json; the five 5x5 layer shapes of EfficientNet-B0 at batch 256, interleaved): 1.8 - 5.1 times the generic kernel's
+    rate on codes-only layers, 1.4 times with the fp32 output, every case beyond the run-to-run spread; the whole
+    EfficientNet-B0 plan (`workloads.efficientnet_b0()`, batch 128, gates and swish on): flag off / on = 6.86 / 6.85 ms per step (FSPTQ W8A8),
+    6.54 / 6.28 (QBase W8A8), logits equal.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -2152,7 +2189,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         if node.op == "call_module" and isinstance(modules[node.target], (nn.Identity, nn.Dropout)) and len(node.args) == 1:
             node.replace_all_uses_with(node.args[0])
             graph.erase_node(node)
-    planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts).run(report)
+    planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts, dw5).run(report)
     if swish:           # (before the gate pass, which finds its gated map and the squeeze's pool behind a swish node's fp32 output)
         _swish_pass(gm, report, planned, dry_run, dwpw)
     if gates:           # (first: the squeeze's global pool is a plain node still, and so are the nodes behind the gate)

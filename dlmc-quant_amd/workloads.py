@@ -258,14 +258,15 @@ class InvertedResidual(nn.Module):
     1x1 convolutions, a quarter of the expanded width rounded up to a multiple of 8, hard sigmoid) between the depthwise and the
     projection layer.  `act="swish"`: EfficientNet's MBConv (efficientnet_block.py:44-59, efficientnet.py:29-34) - swish where ReLU6
     was, and with `se` its squeeze-excite block: Linear layers on the flattened pool, a quarter of the block's INPUT width between them,
-    a swish there too, a sigmoid gate.  The depthwise layer stays 3x3 with symmetric padding."""
+    a swish there too, a sigmoid gate.  `k`: the depthwise filter, 3 or 5 (EfficientNet's stages 3, 5 and 6 have 5), always with the symmetric
+    padding (k - 1) / 2 carried by the convolution."""
 
-    def __init__(self, cin, cout, stride, t, se=False, act="relu6"):
+    def __init__(self, cin, cout, stride, t, se=False, act="relu6", k=3):
         super().__init__()
         hidden = cin * t
         self.use_res = stride == 1 and cin == cout
         layers = [_conv_bn_act(cin, hidden, 1, act=act)] if t != 1 else []
-        layers += [_conv_bn_act(hidden, hidden, 3, stride, groups=hidden, act=act)]
+        layers += [_conv_bn_act(hidden, hidden, k, stride, groups=hidden, act=act)]
         if se and act == "swish":
             layers += [SqueezeExcite(hidden, max(1, cin // 4), gate="sigmoid", squeeze="linear")]
         elif se:
@@ -287,9 +288,9 @@ class MobileNetV2(nn.Module):
         super().__init__()
         cin = 32
         feats = [_conv_bn_act(3, cin, 3, stride=2, act=act)]
-        for t, c, n, s in self.SETTINGS:
+        for t, c, n, s, *k in self.SETTINGS:       # (a fifth entry: the stage's depthwise filter)
             for j in range(n):
-                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t, se, act))
+                feats.append(InvertedResidual(cin, c, s if j == 0 else 1, t, se, act, *k))
                 cin = c
         feats.append(_conv_bn_act(cin, 1280, 1, act=act))
         self.features = nn.Sequential(*feats)
@@ -299,6 +300,14 @@ class MobileNetV2(nn.Module):
 
     def forward(self, x):
         return self.classifier(torch.flatten(self.pool(self.features(x)), 1))
+
+
+class EfficientNetB0(MobileNetV2):
+    """EfficientNet-B0 (public architecture, Tan & Le 2019, table 1) on MobileNetV2's frame: a 32-channel 3x3 / 2 first layer, seven MBConv
+    stages (expansion, channels, repeats, stride, depthwise filter), a 1280-channel 1x1 head.  9 of its 16 depthwise layers are 5x5, with
+    padding 2 carried by the convolution (torchvision's and timm's spelling; not the reference's F.pad in front of an unpadded one)."""
+
+    SETTINGS = ((1, 16, 1, 1, 3), (6, 24, 2, 2, 3), (6, 40, 2, 2, 5), (6, 80, 3, 2, 3), (6, 112, 3, 1, 5), (6, 192, 4, 2, 5), (6, 320, 1, 1, 3))
 
 
 class CifarResNet(nn.Module):
@@ -363,6 +372,12 @@ def mobilenet_v2(num_classes=1000, se=False, act="relu6"):
     `act="swish"`: x * sigmoid(x) where ReLU6 was (35 swishes on maps) and, with `se`, EfficientNet's squeeze-excite block - its MBConv
     at MobileNetV2's widths."""
     return MobileNetV2(num_classes=num_classes, se=se, act=act)
+
+
+def efficientnet_b0(num_classes=1000, se=True, act="swish"):
+    """EfficientNet-B0: MBConv blocks (`mobilenet_v2(se=True, act="swish")`'s) with the paper's stage table - 5x5 depthwise layers in
+    stages 3, 5 and 6.  `se` / `act` as in mobilenet_v2."""
+    return EfficientNetB0(num_classes=num_classes, se=se, act=act)
 
 
 def _named_option(option):

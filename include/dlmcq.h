@@ -150,6 +150,10 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
 #define DLMCQ_ROUTE_DW_VARIANT 0x40000
 #define DLMCQ_ROUTE_DW_VARIANT_TAG (1 << 27)
 #define DLMCQ_ROUTE_DWM_VARIANT_TAG (1 << 28)
+/* dlmcq_conv2d_dw5_i8_nhwc's answer to DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT (the only control bits it takes, and only together): WHICH
+ * instantiation of conv_dw5_i8_kernel (csrc/conv_dw5_i8.hip) the call launches,  DLMCQ_ROUTE_DW5_VARIANT_TAG | (FAST << 4) | flags,  FAST 0 / 1 / 2
+ * and flags: 1 R6 as above.  Above every other answer. */
+#define DLMCQ_ROUTE_DW5_VARIANT_TAG (1 << 29)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */
@@ -601,6 +605,19 @@ int dlmcq_conv2d_dw_i8_nhwc(const void* x, const int8_t* w, float* out, const fl
                             int64_t W, int64_t C, int64_t R, int64_t S, int32_t stride, int32_t pad, int32_t x_is_unsigned,
                             int32_t relu, void* codes, const float* q_scale, const float* q_zero_point, int32_t q_lo,
                             int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
+/* Depthwise 5x5 convolution with padding 2 and stride 1 or 2 (the 5x5 layers of the MBConv family) on the integer dot-product path
+ * (csrc/conv_dw5_i8.hip): the arguments of dlmcq_conv2d_dw_i8_nhwc without R, S, the same arithmetic, and bit for bit the result that call gives
+ * for R = S = 5 - for an INTEGER input zero point in the byte range (the kernel reads (int)in_zero_point[0], as the 3x3 kernels do).
+ * C % 16 == 0, C <= 2048, stride 1 or 2, pad == 2 (DLMCQ_EINVAL otherwise); x and codes 16-byte aligned, the per-channel arrays and out as in
+ * dlmcq_conv2d_dw_i8_nhwc (DLMCQ_EALIGN otherwise); the other checks are that entry point's, in its order (N == 0: DLMCQ_OK, nothing launched).
+ * Control bits in q_form: DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_DW_VARIANT together validate, launch nothing and answer the instantiation
+ * (DLMCQ_ROUTE_DW5_VARIANT_TAG); either alone, DLMCQ_FORCE_TILED and every other bit are DLMCQ_EINVAL.  No float activation offset. */
+int dlmcq_conv2d_dw5_i8_nhwc(const void* x, const int8_t* w, float* out, const float* bias, const float* in_scale,
+                             const float* in_zero_point, const float* w_scale, const float* w_offset, int64_t N, int64_t H,
+                             int64_t W, int64_t C, int32_t stride, int32_t pad, int32_t x_is_unsigned, int32_t relu, void* codes,
+                             const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                             dlmcq_stream_t stream);
 
 /*
  * A MobileOne / MobileNet unit as ONE launch (round 4): depthwise 3x3 / stride 1 / pad 1 (+ ReLU + quantiser) followed by the
