@@ -698,6 +698,33 @@ static const ChainVariant CHAIN_TABLE[] = {
 };
 #undef DLMCQ_CHAIN_ROW
 
+// The table, for tests (absent from include/dlmcq.h): per row six integers - C1, KB, C2, CA, CB and a mask of the FL slots that exist
+// (bit 0: FL = 3, bit 1: FL = 1, bit 2: FL = -1) -, in the table's order, up to `cap_rows` rows; returns how many rows there are
+extern "C" int dlmcq_x_chain_variant_table(int32_t* rows, int cap_rows) {
+  int n = 0;
+  for (const ChainVariant& v : CHAIN_TABLE) {
+    if (rows && n < cap_rows) {
+      int32_t* r = rows + 6 * n;
+      r[0] = v.C1; r[1] = v.KB; r[2] = v.C2; r[3] = v.CA; r[4] = v.CB;
+      r[5] = (v.go[0] ? 1 : 0) | (v.go[1] ? 2 : 0) | (v.go[2] ? 4 : 0);
+    }
+    ++n;
+  }
+  return n;
+}
+
+// What chain_launch decides for a validated call, ONCE: the launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_CHAIN_VARIANT) read
+// this one record.
+struct ChainPick {
+  int row, slot;           // CHAIN_TABLE[row].go[slot]; slot 0 / 1 / 2: FL = 3 / 1 / -1
+  int rows_per_tile;       // as passed, or the automatic rule's
+  bool icm, ocm2;          // the resolved layouts of the fp32 shortcut read / block output written (chunk-major)
+};
+// ... as the route query's answer (include/dlmcq.h: tag | row << 16 | slot << 12 | rows per tile << 4 | ocm << 1 | icm)
+static int chain_variant_answer(const ChainPick& k) {
+  return DLMCQ_ROUTE_CHAIN_VARIANT_TAG | (k.row << 16) | (k.slot << 12) | (k.rows_per_tile << 4) | (k.ocm2 ? 2 : 0) | (k.icm ? 1 : 0);
+}
+
 static bool op_given(const ChainOp& p) { return p.x && p.w && p.wsum && p.s_in && p.s_w; }
 
 // Validates the record - every refusal of every chain entry point, in one order - and launches.
@@ -723,7 +750,8 @@ static int chain_launch(const ChainCall& c) {
   if (smp && (M >= (1ll << 31) || o.N * s.H * s.W * s.C >= (1ll << 40))) return DLMCQ_ERANGE;
   if (ep1.relu == DLMCQ_ACT_RELU6 || ep2.relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
   if (c.q_lo != 0 || c.q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
-  if (ep2.ctl & (DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED | DLMCQ_ROUTE_HALO_VARIANT)) return DLMCQ_EINVAL;   // (no other kernel, no route query here)
+  if (ep2.ctl & (DLMCQ_FORCE_TILED | DLMCQ_PIPELINED | DLMCQ_ROUTE_HALO_VARIANT)) return DLMCQ_EINVAL;   // (no other kernel here)
+  if (((ep2.ctl & DLMCQ_ROUTE_ONLY) != 0) != c.which) return DLMCQ_EINVAL;   // (one route query: both bits, DLMCQ_ROUTE_CHAIN_VARIANT's; either alone is none)
   const bool w3cm = (c.layout & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (c.layout & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
   // (a call without a shortcut tensor or without an output has ONE fp32 tensor: its layout is the call's)
   const bool icm = res ? (c.layout & DLMCQ_FP32_IN_CHUNK_MAJOR) != 0 : ocm;
@@ -738,7 +766,10 @@ static int chain_launch(const ChainCall& c) {
   // where they keep a nearly empty last round from costing a whole tile's life: ResNet-50's 14^2 chains at batch 512 - 1 568 tiles on the
   // 512 slots of the two-workgroup instantiations, 3.06 rounds - run 3.5 rounds of 56-row tiles 8 % faster.  The rule: few rounds, the last
   // one less than an eighth full.
-  int rows_per_tile = c.rows_per_tile;
+  ChainPick pick{};
+  pick.icm = icm; pick.ocm2 = ocm2;
+  int& rows_per_tile = pick.rows_per_tile;
+  rows_per_tile = c.rows_per_tile;
   if (rows_per_tile <= 0) {
     const int64_t t64 = (M + 63) / 64, slots = 256 * CHAIN_WGS((int)(C + C2 + CA + CB), (int)K2);
     const int64_t full = t64 / slots, left = t64 % slots;
@@ -750,9 +781,14 @@ static int chain_launch(const ChainCall& c) {
   // the plan's launches end their first layer with a ReLU: those get the instantiation that knows its flags at compile time
   const int fl = (ep1.relu && epi_plain_q(ep1) && epi_plain_q(ep2)) ? (c.out ? 3 : 1) : -1;
   ChainGo go = nullptr;
+  pick.slot = fl == 3 ? 0 : fl == 1 ? 1 : 2;
   for (const ChainVariant& v : CHAIN_TABLE)
-    if (v.C1 == C && v.KB == K2 && v.C2 == C2 && v.CA == CA && v.CB == CB) go = v.go[fl == 3 ? 0 : fl == 1 ? 1 : 2];
+    if (v.C1 == C && v.KB == K2 && v.C2 == C2 && v.CA == CA && v.CB == CB) {
+      pick.row = (int)(&v - CHAIN_TABLE);
+      go = v.go[pick.slot];
+    }
   if (!go) return DLMCQ_EINVAL;
+  if (c.which) return chain_variant_answer(pick);     // (the route query: everything validated, nothing launched)
 
   ChainArgs a{};
   a.o1 = o.p; a.shift1 = o.shift;
@@ -769,10 +805,10 @@ static int chain_launch(const ChainCall& c) {
   a.w3_row = w3cm ? 64 : (int)K;
   a.w3_chunk = w3cm ? (int)K2 * 64 : 64;
   a.M = (int)M; a.KD = (int)K; a.rows_per_tile = rows_per_tile;
-  a.f_rowq = icm ? 64 : (int)K;
-  a.f_cstep = icm ? (int)M * 256 : 256;
-  a.o_rowq = ocm2 ? 64 : (int)K;
-  a.o_cstep = ocm2 ? (int)M * 256 : 256;
+  a.f_rowq = pick.icm ? 64 : (int)K;
+  a.f_cstep = pick.icm ? (int)M * 256 : 256;
+  a.o_rowq = pick.ocm2 ? 64 : (int)K;
+  a.o_cstep = pick.ocm2 ? (int)M * 256 : 256;
   size_t dyn = 0;
 #ifdef DLMCQ_LAB
   a.trace = g_chain_trace;
@@ -792,7 +828,8 @@ static void chain_tail(ChainCall& c, int64_t K, float* out, int32_t relu, void* 
   c.K = K; c.K2 = K2; c.out = out;
   c.second = ChainOp{nullptr, w2, w_scale2, wsum2, bias2, nullptr, nullptr};
   c.ep1 = make_epi(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
-  c.ep2 = make_epi(nullptr, relu2, codes2, q2_scale, q2_zero_point, q2_lo, q2_hi, q2_form & ~LAYOUT, q2_ste_g);
+  c.ep2 = make_epi(nullptr, relu2, codes2, q2_scale, q2_zero_point, q2_lo, q2_hi, q2_form & ~(LAYOUT | DLMCQ_ROUTE_CHAIN_VARIANT), q2_ste_g);
+  c.which = (q2_form & DLMCQ_ROUTE_CHAIN_VARIANT) != 0;      // (this entry point's own bit: epi_set_form, everyone's, does not know it)
   c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form; c.q2_lo = q2_lo; c.q2_hi = q2_hi;
   c.layout = (uint32_t)(q2_form & LAYOUT);
   c.rows_per_tile = rows_per_tile;

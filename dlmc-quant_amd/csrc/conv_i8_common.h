@@ -217,6 +217,7 @@ struct ChainCall {
   ConvEpi ep1, ep2;          // ep1.codes [M][K] or null, ep2.codes [M][K2]
   int32_t q_lo, q_hi, q_form, q2_lo, q2_hi;   // the ranges and ep1's form as passed (make_epi folds them; chain_launch validates these)
   uint32_t layout;           // DLMCQ_W2_CHUNK_MAJOR | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR of the second `q_form`
+  bool which;                // DLMCQ_ROUTE_CHAIN_VARIANT of the second `q_form` (DLMCQ_ROUTE_ONLY itself travels in ep2.ctl)
   int32_t rows_per_tile;
   hipStream_t st;
 };

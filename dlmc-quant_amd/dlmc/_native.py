@@ -40,6 +40,9 @@ ROUTE_HALO_VARIANT_TAG, ROUTE_PIPE_VARIANT_TAG = 1 << 25, 1 << 26
 HV_PLAIN, HV_XS, HV_S2 = 1, 2, 4   # the flags of such an answer (include/dlmcq.h)
 ROUTE_DW_VARIANT = 0x40000  # DLMCQ_ROUTE_DW_VARIANT: with ROUTE_ONLY, a ROUTE_DW / ROUTE_DWM answer of the depthwise entry points names the instantiation instead (decode_dw_variant)
 ROUTE_DW_VARIANT_TAG, ROUTE_DWM_VARIANT_TAG = 1 << 27, 1 << 28
+ROUTE_CHAIN_VARIANT = 0x80000  # DLMCQ_ROUTE_CHAIN_VARIANT: with ROUTE_ONLY, in the chain entry points' last form: which conv_chain_i8_kernel instantiation, tile height and layouts (decode_chain_variant)
+ROUTE_CHAIN_VARIANT_TAG = 1 << 30
+CHAIN_FL = (3, 1, -1)              # the FL slot of such an answer -> the first epilogue's compile-time form (csrc/conv_chain_i8.hip)
 DV_R6, DV_XOFF, DV_XS = 1, 2, 2    # the flags of such an answer: R6 in both, XOFF in a DW_TABLE answer, XS in a DWM_TABLE one (include/dlmcq.h)
 DW_FAMILIES = ("p2", "dw3", "generic")   # conv_dw3p2_i8_kernel, conv_dw3_i8_kernel, conv_dw_i8_kernel: the family field of a DW_TABLE answer
 # the `flags` of a ROUTE_VARIANT answer: conv_i8_mfma_kernel's boolean template parameters (include/dlmcq.h)
@@ -298,6 +301,25 @@ def dw_variant_tables():
         assert fn(which, answers, n) == n
         out.append([decode_dw_variant(int(a)) for a in answers])
     return tuple(out)
+
+
+def decode_chain_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_CHAIN_VARIANT call of a chain entry point -> ("chain", table row, FL (3 / 1 / -1), rows per tile, icm, ocm) -
+    the conv_chain_i8_kernel instantiation the call launches (row: its index in chain_variant_table()), the tile height and the resolved
+    layouts of the fp32 shortcut read / block output written - or None when the answer is none (DLMCQ_OK, a refusal, another entry point's)."""
+    if rc < ROUTE_CHAIN_VARIANT_TAG or rc & 0x3ff0c80c or (rc >> 12) & 3 == 3:
+        return None
+    return ("chain", (rc >> 16) & 0xf, CHAIN_FL[(rc >> 12) & 3], (rc >> 4) & 0x7f, bool(rc & 1), bool(rc & 2))
+
+
+def chain_variant_table():
+    """[(C1, KB, C2, CA, CB, (FL, ...))]: the rows of the chain launcher's table (csrc/conv_chain_i8.hip: CHAIN_TABLE) in its order, each with
+    the first-epilogue forms it holds a kernel for."""
+    fn = experimental("dlmcq_x_chain_variant_table", [ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    n = fn(None, 0)
+    rows = (ctypes.c_int32 * (6 * n))()
+    assert fn(rows, n) == n
+    return [tuple(int(v) for v in rows[6 * i:6 * i + 5]) + (tuple(f for b, f in enumerate(CHAIN_FL) if rows[6 * i + 5] >> b & 1),) for i in range(n)]
 
 
 def stream_ptr():

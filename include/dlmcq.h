@@ -154,6 +154,19 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * instantiation of conv_dw5_i8_kernel (csrc/conv_dw5_i8.hip) the call launches,  DLMCQ_ROUTE_DW5_VARIANT_TAG | (FAST << 4) | flags,  FAST 0 / 1 / 2
  * and flags: 1 R6 as above.  Above every other answer. */
 #define DLMCQ_ROUTE_DW5_VARIANT_TAG (1 << 29)
+/* DLMCQ_ROUTE_CHAIN_VARIANT (the last form argument - `q2_form` / `q3_form` - of dlmcq_conv2d_i8_nhwc_chain, _dual_chain and _recompute_chain
+ * only; honoured only TOGETHER with DLMCQ_ROUTE_ONLY: either bit alone stays DLMCQ_EINVAL there, and every other entry point refuses it as it
+ * refuses any bit it does not know): nothing is launched; the call is validated exactly as the real call is and answers WHICH instantiation
+ * of conv_chain_i8_kernel (csrc/conv_chain_i8.hip) it would launch and how - the record the launcher itself reads:
+ *   DLMCQ_ROUTE_CHAIN_VARIANT_TAG | (row << 16) | (FL slot << 12) | (rows per tile << 4) | (ocm << 1) | icm
+ *     row: the index of the (C1, KB, C2, CA, CB) row in the launcher's table (dlmcq_x_chain_variant_table lists it, for tests);
+ *     FL slot: 0, 1, 2 for the first epilogue's compile-time form FL = 3 (ReLU + fp32 output), 1 (ReLU), -1 (read at run time);
+ *     rows per tile: the tile height the launch uses, 1 .. 64 - `rows_per_tile` as passed, or what the automatic rule picks for 0;
+ *     icm / ocm: the resolved layouts of the fp32 shortcut read / the fp32 block output (1: chunk-major), as the kernel is handed them -
+ *     a call with one fp32 tensor has one layout, and both bits carry it.
+ * Above every other answer; DLMCQ_OK for an empty problem and every refusal are what they are without the bits. */
+#define DLMCQ_ROUTE_CHAIN_VARIANT 0x80000
+#define DLMCQ_ROUTE_CHAIN_VARIANT_TAG (1 << 30)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */

@@ -365,3 +365,32 @@ def second_gemm_full_ref(codes1, q1, wq2, s_w2, bias2, act2=1, w_int2=None):
     ok = (first == y) | (first.isnan() & y.isnan())
     assert bool(ok.all()), "second layer: the staged chain and the convolution of the dequantised operands disagree"
     return exact_f32(activation(y, act2), "second layer output")
+
+
+@dataclass
+class SecondLayer:
+    """The 1x1 layer behind a first quantiser (chain, dual chain, recomputing chain): wq int8 (K2, K, 1, 1) in +-127, zero on the edge
+    channels [0, nz); s_w fp32 [K2] dyadic; bias fp32 [K2], multiples of q1.scale * s_w[k] on the live channels, the edge values on the others."""
+    wq: torch.Tensor
+    s_w: torch.Tensor
+    bias: torch.Tensor
+    nz: int
+
+
+def make_full_range_second(gen, codes1, q1, k2):
+    """Full-range operands of the layer that reads the REFERENCE's own first-stage codes `codes1` (N, K, P, Q; bytes of quantise(.., q1),
+    unshifted) as (code - zp) * q1.scale: weight codes uniform in +-127, per-channel dyadic scales s_w[k] = 2^(e - k % 5) that differ from
+    channel to channel, biases that are multiples of each channel's q1.scale * s_w[k] and carry the tie fractions of full_range_bias.  e is
+    sized the way make_full_range_layer sizes its input scale - a power of two from the shape (K products per sum, a uniform weight code)
+    and from the codes' own second moment about the zero point - so that the widest channels' outputs have FULL_TARGET_SIGMA."""
+    k = codes1.shape[1]
+    nz = min(len(EDGE_VALUES), k2 - max(8, k2 // 4))
+    wq = torch.randint(-127, 128, (k2, k, 1, 1), generator=gen).to(torch.int8)
+    wq[:nz] = 0
+    ci = codes1.to(torch.int32).double() - (0.0 if q1.zp is None else q1.zp)
+    sigma_int = math.sqrt(k * float((ci * ci).mean()) * (127 * 128) / 3.0)
+    e = round(math.log2(FULL_TARGET_SIGMA / (q1.scale * sigma_int)))
+    s_w = (2.0 ** (e - torch.arange(k2) % 5).double()).float()
+    lay = SecondLayer(wq, s_w, torch.zeros(k2), nz)
+    lay.bias = full_range_bias(k2, nz, k2, q1.scale * s_w.double(), gen)
+    return lay

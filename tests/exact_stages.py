@@ -129,6 +129,45 @@ def dw_pair_stages(lay, g, shift, xoff=False):
     return true, bias, tap_f
 
 
+def chain_stages(own, shift, *, residual=None, sampled=None, shift_s=0, stride=1, unit=None, shift_u=0, relu_shortcut=0):
+    """The first epilogue of conv_chain_i8_kernel on full-range operands: the true float64 value (N, K, P, Q) before the block's own
+    activation, every partial result asserted to be an fp32 number in the kernel's order -
+        plain form:        fma(S, s_in s_w, b)                                     + residual
+        dual form:         fma(S2, ..) of the SAMPLED operand first;  fma(S, ..) + that
+        recomputing form:  fma(Sb, ..) sampled, fma(Sa, ..) unit;  a + b;  ReLU?;  fma(S, ..) + that   (the shortcut rounded to fp32 as the dual form stores it)
+    each fma under pair_stages' conditions (integer sums below 2^24, the result a multiple of the unit below 2^24 units).  And, as dw_pair_stages
+    does, so that no association order of the terms can differ: the SUM OF THE TERMS' MAGNITUDES stays below 2^24 units of the smallest unit among
+    them, per channel, on the live channels (the edge channels of the extra operands are zero: there the sum is the edge value + 0)."""
+    g1 = dict(stride=1, pad=0, dil=1)
+    v, _, _ = pair_stages(own, g1, shift)
+    terms, units = [v], [own.unit]
+    if unit is not None:                                                 # the recomputed block: unit-stride operand a, sampled operand b
+        assert sampled is not None and residual is None
+        vb, _, _ = pair_stages(sampled, dict(stride=stride, pad=0, dil=1), shift_s)
+        va, _, _ = pair_stages(unit, g1, shift_u)
+        sc = X.exact_f32(va + vb, "recomputed shortcut: a + b").double()
+        sc = X.exact_f32(X.activation(sc, 1 if relu_shortcut else 0), "recomputed shortcut").double()
+        true = X.exact_f32(v + sc, "+ recomputed shortcut").double()
+        terms += [va, vb]
+        units += [unit.unit, sampled.unit]
+    elif sampled is not None:
+        assert residual is None
+        vs, _, _ = pair_stages(sampled, dict(stride=stride, pad=0, dil=1), shift_s)
+        true = X.exact_f32(v + vs, "+ convolution shortcut").double()
+        terms.append(vs)
+        units.append(sampled.unit)
+    else:
+        r = residual.double()
+        true = X.exact_f32(v + r, "+ shortcut").double()
+        terms.append(r)
+        units.append(torch.full_like(own.unit, 0.25))                   # (edge_residual: multiples of 1/4 on the live channels)
+    u = torch.stack(units).min(dim=0).values.reshape(1, -1, 1, 1)
+    mags = (sum(t.abs() for t in terms) / u)[:, own.nz:]
+    assert float(mags[mags.isfinite()].max()) < LIMIT, "the terms' magnitudes add up to 2^24 units or more"
+    assert_final_units(true, own)
+    return true
+
+
 def assert_final_units(true, lay):
     """The final pre-activation value in units of s_in * s_w[k], on the live channels: below 2^24."""
     units = (true / lay.unit.reshape(1, -1, 1, 1))[:, lay.nz:]

@@ -39,13 +39,14 @@ def test_library_exports_the_test_only_tables():
     """The dlmcq_x_* table listings the variant tests read are exported, and deliberately absent from the header."""
     from dlmc import _native as N
     lib = ctypes.CDLL(N.LIB_PATH)
-    for s in ("dlmcq_x_conv_variant_table", "dlmcq_x_conv3x3_variant_table", "dlmcq_x_dw_variant_table"):
+    for s in ("dlmcq_x_conv_variant_table", "dlmcq_x_conv3x3_variant_table", "dlmcq_x_dw_variant_table", "dlmcq_x_chain_variant_table"):
         assert hasattr(lib, s), f"libdlmcq.so lacks {s}"
         assert s not in declared_symbols()
     assert len(N.conv_variant_table()) == 48 and [len(t) for t in N.conv3x3_variant_tables()] == [40, 6]
     assert N.experimental("dlmcq_x_conv3x3_variant_table", [ctypes.c_int, ctypes.c_void_p, ctypes.c_int])(2, None, 0) == -1      # no such table
     assert [len(t) for t in N.dw_variant_tables()] == [26, 8] and None not in sum(N.dw_variant_tables(), [])
     assert N.experimental("dlmcq_x_dw_variant_table", [ctypes.c_int, ctypes.c_void_p, ctypes.c_int])(2, None, 0) == -1
+    assert len(N.chain_variant_table()) == 8 and sum(len(r[5]) for r in N.chain_variant_table()) == 23
 
 
 def test_argument_validation_needs_no_gpu():

@@ -5,7 +5,8 @@ must equal tests/golden/chain_refusals.json exactly, case for case.  The fixture
 rewritten around one call record (ChainCall); its `header` names that commit.  A rewrite that changes a refusal's code, or the order two
 refusals are checked in, fails here.
 
-The chain entry points have no route query, so the sweep holds ONLY calls that are answered without a launch: every refusal, and the
+The sweep makes no route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_CHAIN_VARIANT: tests/test_chain_variants_host.py; either bit alone is a refusal, and
+ROUTE_ONLY alone is in it), so it holds ONLY calls that are answered without a launch: every refusal, and the
 empty problem (DLMCQ_OK before any pointer is looked at).  No accepted call is in it - the generator asserts that every recorded value
 is negative or belongs to a case with no rows - and the calls are made in a child process that hides the GPUs (HIP_VISIBLE_DEVICES=-1)
 and first asks the HIP runtime for its device count: it makes no library call unless the answer is zero or an error.  A regression that
