@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1281,6 +1281,63 @@ def swish_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
     n, c, h, w_ = _fp32_map("swish_quant", x)
     return _map_codes("swish_quant", x, h, w_, emit, want_out, c_pad, pad_code, "swish", n * h * w_ * c * 4,
                       lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_swish_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail))
+
+
+def gelu_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
+    """GELU in its erf form (nn.GELU() / F.gelu(x), approximate="none") by dlmcq_gelu_nhwc_f32: z = x * fl32(1 / sqrt(2)), e = erff(z),
+    f = 1 + e, h = x * 0.5, v = h * f, each step rounded to fp32 - the operation order of torch's device kernel.  `x`: an fp32 4-D
+    tensor is an (N, C, H, W) map, C % 4 == 0, handled as swish_quant handles it (read in place when channels_last or a channel slice
+    of a channels_last tensor); an fp32 tensor of any other rank is dense rows [..., C], C % 4 == 0 (copied when not contiguous), passed
+    as N = rows, H = W = 1.  Returns `(out or None, codes or None)` in the input's shape (code rows `c_pad` wide); `emit`, `want_out`,
+    `c_pad` and `pad_code` as _map_codes says."""
+    N.require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() < 1:
+        raise ValueError("gelu_quant: an fp32 (N, C, H, W) map or fp32 rows [..., C]")
+    lead = None
+    if x.dim() != 4:
+        lead, x = tuple(x.shape[:-1]), x.reshape(-1, x.shape[-1]).contiguous()
+        x = x.view(x.shape[0], x.shape[1], 1, 1)
+    n, c, h, w_ = x.shape
+    out, codes = _map_codes("gelu_quant", x, h, w_, emit, want_out, c_pad, pad_code, "gelu", n * h * w_ * c * 4,
+                            lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_gelu_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail))
+    if lead is not None:
+        out = None if out is None else out.reshape(*lead, c)
+        codes = None if codes is None else codes.reshape(*lead, codes.shape[1])
+    return out, codes
+
+
+LAYERNORM_MAX_C = 2048    # dlmcq_layernorm_rows_f32: a row lives in one wave's registers (8 quads of 4 floats per lane)
+
+
+def layernorm_quant(x, weight, bias, eps, emit=None, want_out=True):
+    """nn.LayerNorm((C,)) of dense fp32 rows `x` [..., C], C % 4 == 0, 4 <= C <= LAYERNORM_MAX_C, by dlmcq_layernorm_rows_f32: a two-pass
+    mean / biased variance in a fixed summation order (include/dlmcq.h), r = 1 / sqrt(var + eps), v = ((x - mean) * r) * weight + bias,
+    each step rounded to fp32.  `weight`, `bias`: fp32 [C] or None.  Returns `(out or None, codes or None)` in the input's shape: fp32
+    unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the same values (plain codes: the
+    readers are Linear layers; EmitCodes.shift128 is an error)."""
+    N.require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() < 1:
+        raise ValueError("layernorm_quant: fp32 rows [..., C]")
+    if not want_out and emit is None:
+        raise ValueError("layernorm_quant: nothing to produce (want_out=False without emit)")
+    c = x.shape[-1]
+    for name, t in (("weight", weight), ("bias", bias)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (c,)):
+            raise ValueError(f"layernorm_quant: an fp32 {name} of shape ({c},), not {t.dtype} {tuple(t.shape)}")
+    shape = tuple(x.shape)
+    x = x.detach().reshape(-1, c).contiguous()
+    m = x.shape[0]
+    weight, bias = _bias_c(weight), _bias_c(bias)
+
+    def alloc(dtype):
+        return torch.empty(shape, dtype=dtype, device=x.device)
+    out = alloc(torch.float32) if want_out else None
+    q = _quantiser(emit, alloc, x, False, "layernorm_quant")
+    codes, *tail = _q_args(q)
+    PROFILE.launch("layernorm", m * c * (4 + 4 * want_out + (emit is not None)) + 4 * c * ((weight is not None) + (bias is not None)),
+                   lambda: N.check(N.lib.dlmcq_layernorm_rows_f32(N.ptr(x), N.ptr(weight), N.ptr(bias), N.ptr(out), codes, m, c, float(eps),
+                                                                  *tail, N.stream_ptr())))
+    return out, q[0]
 
 
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):

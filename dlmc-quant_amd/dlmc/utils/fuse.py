@@ -34,7 +34,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -921,6 +921,11 @@ class _MapCodesLayer(nn.Module):
             codes = _pad_channels(codes, self.c_pad, self.pad_code)
         return (v if self.want_out else None), codes
 
+    def _torch_rows(self, v):
+        """_torch_codes of dense rows [..., C] of any rank (no channel axis to pad: the readers are Linear layers), in `v`'s shape."""
+        _, codes = self._torch_codes(v.reshape(-1, v.shape[-1]))
+        return (v if self.want_out else None), codes.reshape(v.shape)
+
 
 class AvgPoolLayer(_MapCodesLayer):
     """A windowed average pool (nn.AvgPool2d(s, s) / F.avg_pool2d(x, s): window = stride, no padding, floor) of an fp32 map straight to
@@ -990,12 +995,14 @@ def _splice_map_node(gm, last, name, module, args, takers, erase):
         gm.graph.erase_node(n)
 
 
-def _code_readers(planned, t, dw=False, dwpw=False):
+def _code_readers(planned, t, dw=False, dwpw=False, linear=False):
     """Who takes fp32 node `t` as codes from a stand-alone quantising node (the average-pool, gate and swish passes): "gemm" plan
     convolutions that read it through their activation argument - as their own node or as an operand of a dual node - with input
     channels % 4 == 0, all sharing one activation quantiser and one channel count; with `dw` (the swish pass: MBConv's expansion swish is
     read by the depthwise layer) "dw" plan convolutions too, which take channel-padded codes as the main pass hands them over (`dwpw`:
-    fuse_inference's flag, under which a depthwise layer reads no shifted codes).  Returns a _CodeReaders (that quantiser, the takers,
+    fuse_inference's flag, under which a depthwise layer reads no shifted codes); with `linear` (the LayerNorm and GELU passes) "gemm"
+    plan layers with a 2-D weight - Linear layers, which read rows [..., C] - too: they take plain codes of their in-features (a multiple
+    of 64: no padding, never shifted), and either every taker is one or none is.  Returns a _CodeReaders (that quantiser, the takers,
     whether anyone else reads `t` as fp32, channels, code-row width, pad code, shifted emission), or None where no such reader exists or
     they disagree."""
     def reader(u):
@@ -1015,6 +1022,8 @@ def _code_readers(planned, t, dw=False, dwpw=False):
         else:
             return None
         a, m = ops[0]
+        if linear and not d.dual and m.weight.dim() == 2:
+            return a, m
         return (a, m) if m.weight.dim() == 4 and m.groups == 1 and all(mm.weight.shape[1] == m.weight.shape[1] for _, mm in ops) else None
 
     readers = {u: reader(u) for u in t.users}
@@ -1022,7 +1031,9 @@ def _code_readers(planned, t, dw=False, dwpw=False):
     if not takers or len({readers[u][0].key for u in takers}) != 1:      # (the max-pool rule: one quantiser for all code readers)
         return None
     def width(m):      # input channels of reader `m` (depthwise: one per output channel)
-        return int(m.weight.shape[0] if m.groups != 1 else m.weight.shape[1])
+        return int(m.weight.shape[0] if m.weight.dim() == 4 and m.groups != 1 else m.weight.shape[1])
+    if len({readers[u][1].weight.dim() for u in takers}) != 1:      # (`linear`: rows or a map, not both)
+        return None
     emit, conv = readers[takers[0]]
     c = width(conv)
     if c % 4 or c < 4 or any(width(readers[u][1]) != c for u in takers):
@@ -1243,6 +1254,135 @@ def _swish_pass(gm, report, planned, dry_run, dwpw):
         modules[f"_int8_swish_{count}"] = module
         count += 1
     report.swishes = count
+    _settle(gm, count)
+
+
+class LayerNormLayer(_MapCodesLayer):
+    """nn.LayerNorm((C,)) of fp32 rows [..., C] straight to the activation codes of the Linear plan layers that read the normalised
+    rows (csrc/layernorm.hip): the normalisation, the normalised fp32 tensor and the consumer's quantise pass as one read of the rows.
+    `norm`: the nn.LayerNorm, whose parameters and eps are read at every call; `emit`: the readers' activation quantiser; `want_out`:
+    whether anyone reads the fp32 values; `c` = the readers' in-features.  An input that at run time is no fp32 device tensor of width
+    `c` (or parameters that are not fp32) is normalised with F.layer_norm and quantised with K.fake_quant: the values of the unfused
+    graph.  Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, norm, emit, want_out, c):
+        super().__init__(emit, want_out, c, c, 0, False)
+        self.norm = norm
+
+    def forward(self, x):
+        m = self.norm
+        fp32 = all(p is None or p.dtype == torch.float32 for p in (m.weight, m.bias))
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 1 and x.shape[-1] == self.c and fp32):
+            return self._torch_rows(F.layer_norm(x, m.normalized_shape, m.weight, m.bias, m.eps))
+        return K.layernorm_quant(x, m.weight, m.bias, m.eps, emit=self.emit.emit(x.numel()), want_out=self.want_out)
+
+
+class _DryLayerNormLayer(LayerNormLayer):
+    """fuse_inference(dry_run=...): a LayerNormLayer's decision (norm, emit, want_out, c).  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+def _layernorm_pass(gm, report, planned, dry_run):
+    """LayerNorms (fuse_inference(layer_norms=True)): `nn.LayerNorm((C,)) -> Linear plan layers` becomes a node that hands the Linear
+    layers their activation codes (LayerNormLayer) and anyone else the normalised fp32 rows from the same launch.  Taken: an nn.LayerNorm
+    called with one positional argument, normalising the last dimension only, C % 4 == 0, 4 <= C <= K.LAYERNORM_MAX_C, a finite eps > 0,
+    with at least one taker, every taker a Linear of C in-features.  `planned`: plan node -> what the main pass decided for it
+    (_Decision); whatever that is for the Linear behind the LayerNorm stays - only its input changes, from fp32 to codes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+    for node in list(graph.nodes):
+        m = modules.get(node.target) if node.op == "call_module" else None
+        if type(m) is not nn.LayerNorm or len(node.args) != 1 or node.kwargs or not isinstance(node.args[0], fx.Node):
+            continue
+        shape = tuple(m.normalized_shape)
+        if len(shape) != 1 or shape[0] % 4 or not 4 <= shape[0] <= K.LAYERNORM_MAX_C or not (m.eps > 0 and math.isfinite(m.eps)):
+            continue
+        taken = _code_readers(planned, node, linear=True)
+        if taken is None or taken.c != shape[0] or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):
+            continue
+        module = (_DryLayerNormLayer if dry_run else LayerNormLayer)(m, taken.emit, taken.want_out, taken.c)
+        _splice_map_node(gm, node, f"_int8_layernorm_{count}", module, (node.args[0],), taken.takers, [node])
+        count += 1
+    report.layer_norms = count
+    _settle(gm, count)
+
+
+_GELU_ALPHA = 0.70710678118654752440      # 1 / sqrt(2): as a Python scalar torch multiplies an fp32 tensor by its fp32 rounding
+
+
+class GeluLayer(_MapCodesLayer):
+    """GELU in its erf form (approximate="none") straight to the activation codes of the plan layers that read the activated tensor
+    (csrc/gelu.hip): the activation, the activated fp32 tensor and the consumer's quantise pass as one read.  `rows`: the readers are
+    Linear layers - the input is rows [..., c] of any rank; else plan convolutions - the input is an (N, c, H, W) map and the code rows
+    are `c_pad` wide, as a SwishLayer's.  An input that at run time is no fp32 device tensor of that form takes the same five steps in
+    torch ops and K.fake_quant.  Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, emit, want_out, c, c_pad, pad_code, shift=False, rows=False):
+        super().__init__(emit, want_out, c, c_pad, pad_code, shift)
+        self.rows = bool(rows)
+
+    @staticmethod
+    def _gelu(x):
+        """csrc/gelu.hip's five steps in torch ops (each one rounded to the tensor's dtype)."""
+        return (x * 0.5) * (1.0 + torch.erf(x * _GELU_ALPHA))
+
+    def forward(self, x):
+        device_fp32 = x.is_cuda and x.dtype == torch.float32
+        if self.rows:
+            if not (device_fp32 and x.dim() >= 1 and x.shape[-1] == self.c):
+                return self._torch_rows(self._gelu(x))
+            out, codes = K.gelu_quant(x.reshape(-1, self.c), **self._to_codes(x.numel()))
+            return (None if out is None else out.reshape(x.shape)), codes.reshape(x.shape)
+        if not (device_fp32 and x.dim() == 4 and x.shape[1] == self.c):
+            return self._torch_codes(self._gelu(x))
+        return K.gelu_quant(x, **self._to_codes(x.numel()))
+
+
+class _DryGeluLayer(GeluLayer):
+    """fuse_inference(dry_run=...): a GeluLayer's decision (emit, want_out, c, c_pad, pad_code, emit_shift, rows).  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+def _gelu_of(node, modules):
+    """The graph value x if `node` is the erf-form GELU of x in a spelling the plan takes - nn.GELU() / nn.GELU(approximate="none") called
+    with one positional argument, F.gelu(x) / F.gelu(x, approximate="none") (positional too) - else None.  The tanh form is none of them.
+    A user module whose body is one of these is traced into it."""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        x = node.args[0] if len(node.args) == 1 and not node.kwargs else None
+        return x if type(m) is nn.GELU and m.approximate == "none" and isinstance(x, fx.Node) else None
+    if node.op == "call_function" and node.target in (F.gelu, torch._C._nn.gelu):
+        if not 1 <= len(node.args) <= 2 or not set(node.kwargs) <= {"approximate"} or (len(node.args) == 2 and node.kwargs):
+            return None
+        approximate = node.args[1] if len(node.args) == 2 else node.kwargs.get("approximate", "none")
+        return node.args[0] if approximate == "none" and isinstance(node.args[0], fx.Node) else None
+    return None
+
+
+def _gelu_pass(gm, report, planned, dry_run, dwpw):
+    """GELUs (fuse_inference(gelu=True)): `GELU -> plan layers` becomes a node that hands the plan layers behind it their activation codes
+    (GeluLayer) and anyone else the activated fp32 tensor from the same launch.  The takers are Linear plan layers (rows) or 4-D "gemm"
+    plan convolutions (a map: the channel-padded code rows of the average-pool rule), never both; a GELU nobody takes as codes is left
+    alone.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for the layer behind the GELU stays
+    - only its input changes, from fp32 to codes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+    for node in list(graph.nodes):
+        x = _gelu_of(node, modules)
+        taken = _code_readers(planned, node, dwpw=dwpw, linear=True) if x is not None else None
+        if taken is None:
+            continue
+        rows = planned[taken.takers[0]].mod.weight.dim() == 2
+        module = (_DryGeluLayer if dry_run else GeluLayer)(rows=rows, **_decided(taken))
+        _splice_map_node(gm, node, f"_int8_gelu_{count}", module, (x,), taken.takers, [node])
+        count += 1
+    report.gelus = count
     _settle(gm, count)
 
 
@@ -1473,6 +1613,8 @@ class FusionReport:
         self.gates = 0        # squeeze-excite gates (x * g, + ReLU / ReLU6) handing the plan layers behind them their codes (fuse_inference(gates=True))
         self.dw5 = 0          # 5x5 depthwise layers on the integer dot-product kernel, csrc/conv_dw5_i8.hip (fuse_inference(dw5=True))
         self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
+        self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
+        self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -1503,6 +1645,8 @@ class FusionReport:
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
                 (f"gates on the plan={self.gates}, " if self.gates else "") +
                 (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
+                (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
+                (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
                 (f"5x5 depthwise on the dot-product kernel={self.dw5}, " if self.dw5 else "") +
                 f"not eligible={self.skipped})")
 
@@ -2045,7 +2189,7 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None, gates=False, swish=False, dw5=False):
+                   recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2171,7 +2315,25 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     profiles/dw5_ab.json; the five 5x5 layer shapes of EfficientNet-B0 at batch 256, interleaved): 1.8 - 5.1 times the generic kernel's
     rate on codes-only layers, 1.4 times with the fp32 output, every case beyond the run-to-run spread; the whole
     EfficientNet-B0 plan (`workloads.efficientnet_b0()`, batch 128, gates and swish on): flag off / on = 6.86 / 6.85 ms per step (FSPTQ W8A8),
-    6.54 / 6.28 (QBase W8A8), logits equal.  Off by default: the plan without it is the plan as it was."""
+    6.54 / 6.28 (QBase W8A8), logits equal.  Off by default: the plan without it is the plan as it was.
+    `layer_norms=True`, `gelu=True`: the two operators in front of a transformer block's Linear layers
+    (`workloads.vit_small()`) become plan nodes that hand those layers their activation codes in one read of the fp32 rows and every other
+    reader the fp32 values from the same launch (`fusion_report.layer_norms`, `.gelus` count the nodes).  `layer_norms`: an nn.LayerNorm
+    over the last dimension alone, called with one positional argument, C % 4 == 0, 4 <= C <= 2048, whose code readers are Linear plan
+    layers of C in-features sharing one quantiser (LayerNormLayer, csrc/layernorm.hip: one wave per row, two-pass mean / variance in a
+    fixed summation order).  `gelu`: nn.GELU() / F.gelu in the erf form (`approximate="none"`), not in place, a user module whose body is
+    one of these included, read by Linear plan layers (rows) or by 4-D "gemm" plan convolutions (a map with the channel-padded code rows
+    of the average-pool rule), never both (GeluLayer, csrc/gelu.hip: the fourth map-to-codes op).  Left as they are: F.layer_norm, a
+    LayerNorm over more dimensions, other widths, the tanh form, a LayerNorm or GELU nobody takes as codes, readers that disagree on
+    their quantiser.  Both passes run after the main pass, whose decisions for the Linear layers stay - only their input changes, from
+    fp32 to codes - and before the head pass; attention's products and softmax stay in torch.  An input that at run time is no fp32
+    device tensor of the planned width takes the node's torch restatement.  The codes are K.fake_quant of the node's own fp32 values bit
+    for bit, so the plan equals the flag-off plan of the network whose LayerNorm / GELU modules return the kernels' fp32 outputs
+    (tests/test_gpu_transformer.py); against torch's own LayerNorm the values differ in the last bits (another summation order), within
+    the stated bounds.  Measured (tools/transformer_ab.py, profiles/transformer_ab.json; ViT-S/16, 25 LayerNorm and 12 GELU nodes, batch
+    256 at 224^2, interleaved): flags off / on = 16.54 / 13.84 ms per step (FSPTQ W8A8), 16.52 / 13.84 (QBase W8A8), ratio 1.20 / 1.19 at a
+    spread of 0.06 ms; about half the logits differ, by at most 0.035 at a largest logit of 1.3.  Off by default: the plan without them
+    is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -2196,6 +2358,10 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _gate_pass(gm, report, planned, dry_run, relu6)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
         _avgpool_pass(gm, report, planned, dry_run)
+    if layer_norms:     # (after the main pass, whose decisions for the Linear layers stay; before the head pass, like the average pools)
+        _layernorm_pass(gm, report, planned, dry_run)
+    if gelu:
+        _gelu_pass(gm, report, planned, dry_run, dwpw)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and (not dry_run or dry_run == "chains"):

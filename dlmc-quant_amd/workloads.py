@@ -339,6 +339,67 @@ class CifarResNet(nn.Module):
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 
+class ViTAttention(nn.Module):
+    """Multi-head self-attention on tokens [B, T, dim]: one Linear to q, k and v (no bias), softmax(q k^T / sqrt(d)) v per head, one
+    Linear back to `dim`.  The two Linear layers are the quantisable part; the products and the softmax run in torch."""
+
+    def __init__(self, dim, heads, dim_head):
+        super().__init__()
+        self.heads, self.dim_head = heads, dim_head
+        self.to_qkv = nn.Linear(dim, 3 * heads * dim_head, bias=False)
+        self.to_out = nn.Linear(heads * dim_head, dim)
+
+    def forward(self, x):
+        qkv = self.to_qkv(x)
+        b, t = qkv.shape[0], qkv.shape[1]      # (read off the projection, not off x: the plan may hand to_qkv codes and write no fp32 x)
+        qkv = qkv.reshape(b, t, 3, self.heads, self.dim_head).permute(2, 0, 3, 1, 4)      # [3, B, heads, T, d]
+        q, k, v = qkv[0], qkv[1], qkv[2]
+        attn = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * self.dim_head ** -0.5, dim=-1)
+        out = torch.matmul(attn, v).permute(0, 2, 1, 3).reshape(b, t, self.heads * self.dim_head)
+        return self.to_out(out)
+
+
+class ViTBlock(nn.Module):
+    """A pre-norm encoder block: x = attn(norm(x)) + x; x = ff(norm(x)) + x, ff = Linear -> GELU -> Linear."""
+
+    def __init__(self, dim, heads, dim_head, mlp_dim):
+        super().__init__()
+        self.norm1, self.attn = nn.LayerNorm(dim), ViTAttention(dim, heads, dim_head)
+        self.norm2, self.fc1, self.act, self.fc2 = nn.LayerNorm(dim), nn.Linear(dim, mlp_dim), nn.GELU(), nn.Linear(mlp_dim, dim)
+
+    def forward(self, x):
+        x = self.attn(self.norm1(x)) + x
+        return self.fc2(self.act(self.fc1(self.norm2(x)))) + x
+
+
+class ViT(nn.Module):
+    """The vision transformer (public architecture, Dosovitskiy et al. 2021; the reference's spelling of it, model/classification/vit.py:
+    patches embedded by a Linear on the flattened patch, a cls token, a learned position embedding, pre-norm blocks, a LayerNorm -> Linear
+    head on the cls token) in plain torch - reshape / permute only.  Every Linear's in-features must be a multiple of 64 for the int8
+    plan to take it: patch_size^2 * channels, dim, heads * dim_head and mlp_dim."""
+
+    def __init__(self, image_size=224, patch_size=16, num_classes=1000, dim=384, depth=12, heads=6, mlp_dim=1536, dim_head=64, channels=3):
+        super().__init__()
+        if image_size % patch_size:
+            raise ValueError(f"ViT: image size {image_size} is no multiple of the patch size {patch_size}")
+        self.patch, self.grid, self.channels = patch_size, image_size // patch_size, channels
+        self.embed = nn.Linear(channels * patch_size * patch_size, dim)
+        self.cls_token = nn.Parameter(torch.randn(1, 1, dim) * 0.02)
+        self.pos_embedding = nn.Parameter(torch.randn(1, self.grid * self.grid + 1, dim) * 0.02)
+        self.blocks = nn.Sequential(*[ViTBlock(dim, heads, dim_head, mlp_dim) for _ in range(depth)])
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+
+    def forward(self, img):
+        p, g = self.patch, self.grid
+        # [B, C, g p, g p] -> [B, g g, p p C]: one row per patch, its pixels row-major with the channels innermost
+        x = img.reshape(-1, self.channels, g, p, g, p).permute(0, 2, 4, 3, 5, 1).reshape(-1, g * g, p * p * self.channels)
+        x = self.embed(x)
+        x = torch.cat((self.cls_token.expand(x.shape[0], -1, -1), x), dim=1) + self.pos_embedding
+        x = self.blocks(x)
+        return self.head(self.norm(x[:, 0]))
+
+
 def _init(model):
     for m in model.modules():
         if isinstance(m, nn.Conv2d):
@@ -378,6 +439,16 @@ def efficientnet_b0(num_classes=1000, se=True, act="swish"):
     """EfficientNet-B0: MBConv blocks (`mobilenet_v2(se=True, act="swish")`'s) with the paper's stage table - 5x5 depthwise layers in
     stages 3, 5 and 6.  `se` / `act` as in mobilenet_v2."""
     return EfficientNetB0(num_classes=num_classes, se=se, act=act)
+
+
+def vit_tiny(num_classes=1000):
+    """ViT-Ti/16: dim 192, depth 12, 3 heads of 64, MLP 768, 224^2 images (197 tokens)."""
+    return ViT(224, 16, num_classes, dim=192, depth=12, heads=3, mlp_dim=768)
+
+
+def vit_small(num_classes=1000):
+    """ViT-S/16: dim 384, depth 12, 6 heads of 64, MLP 1536, 224^2 images (197 tokens)."""
+    return ViT(224, 16, num_classes, dim=384, depth=12, heads=6, mlp_dim=1536)
 
 
 def _named_option(option):

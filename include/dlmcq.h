@@ -947,6 +947,55 @@ int dlmcq_swish_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int
                          int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- GELU (erf form) 0.5 x (1 + erf(x / sqrt(2))): fp32 and / or the consumer's activation codes ----
+ * For image n, pixel (h, w), channel c, with x = x[n, h, w, c] (dense rows [M, C]: N = M, H = W = 1):
+ *     z = fl32(x * 0.70710678118654752440f)   one IEEE multiply by fl32(1 / sqrt(2))
+ *     e = erff(z)                             the device library's accurate erff
+ *     f = fl32(1 + e)                         one IEEE add
+ *     h = fl32(x * 0.5f)
+ *     v = fl32(h * f)                         one IEEE multiply, rounded to fp32 before anything else reads it (never contracted into
+ *                                             the quantiser's arithmetic)
+ *     out = v;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused; DLMCQ_EMIT_SHIFT128 accepted) of v - the
+ *                      code dlmcq_fake_quant_f32 gives for it
+ * - the operation order of torch's device GELU kernel for approximate="none", element by element; with u = 2^-23 (|x| + |v*|) within
+ * 2 u of the real v* = x Phi(x).  x <= about -5.9: v = -0; x = -inf: NaN (as -inf * 0); x = +inf: +inf; NaN stays NaN; denormals are
+ * kept.  There is no tanh form.  No atomics, no scratch: the result depends neither on the launch geometry nor on the run.
+ * Arguments, layouts and return codes: exactly those of dlmcq_swish_nhwc_f32. */
+int dlmcq_gelu_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int64_t H, int64_t W, int64_t C, int64_t x_stride,
+                        int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                        int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
+/* ---- LayerNorm over the last dimension of dense fp32 rows: fp32 and / or the consumer's activation codes ----
+ * For row m, with x = x[m, 0 .. C - 1] as C / 4 quads of 4 floats, lane l (0 .. 63) owning quads l, l + 64, ...:
+ *     q_j  = fl32(fl32(x0 + x1) + fl32(x2 + x3))   the lane's j-th quad (a quad past the row's end: +0)
+ *     s_l  = the lane's q_j added pairwise in memory order, (q0 + q1) + (q2 + q3), ...: a balanced tree (1, 2, 4 or 8 quads: C <= 256,
+ *            512, 1024, 2048), not a running sum - 32 equal values added one by one drift by several ulp, which the bound below has no
+ *            room for
+ *     S    =the 64 lane sums combined by an xor butterfly with strides 32, 16, 8, 4, 2, 1
+ *     mean = fl32(S / (float)C)               a true division
+ *     d    = fl32(x - mean)
+ *     S2   = the same two-level sum of fl32(d * d)
+ *     var  = fl32(S2 / (float)C)              the biased variance
+ *     r    = fl32(1 / sqrtf(fl32(var + eps))) square root and division correctly rounded
+ *     v    = fl32(fl32(fl32(d * r) * gamma[c]) + beta[c])      gamma NULL: no multiply; beta NULL: no add
+ *     out = v;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused) of v - the code dlmcq_fake_quant_f32 gives
+ *                      for it.  The shifted emission is NOT accepted: the readers are Linear layers, which take plain codes.
+ * - nn.LayerNorm((C,)) up to the summation order: with n = (x - mean) / sqrt(var + eps) in real arithmetic on the same fp32 inputs and
+ * u = 2^-23 (|n gamma| + |beta| + |gamma| max_row|x| / sqrt(var + eps)), |v - (n gamma + beta)| <= 2 u.  A NaN or an infinity in a row
+ * makes the whole row NaN.  No LDS, no atomics, no scratch: a row's result depends neither on M nor on its index nor on the launch.
+ *   x        fp32 [M, C] dense, 16-byte aligned
+ *   gamma    fp32 [C], 16-byte aligned, or NULL (no scale)
+ *   beta     fp32 [C], 16-byte aligned, or NULL (no shift)
+ *   out      fp32 [M, C] dense, 16-byte aligned, or NULL
+ *   codes    bytes [M, C], 4-byte aligned, or NULL (needs q_scale)
+ * DLMCQ_EINVAL: M < 0, C < 4, C % 4, C > 2048, eps not finite or not > 0, x NULL, both outputs NULL, an invalid quantiser, any control
+ * or layout bit or DLMCQ_EMIT_SHIFT128 in q_form (refused, not stripped).  DLMCQ_EALIGN: x / gamma / beta / out not 16-byte aligned,
+ * codes not 4-byte aligned.  DLMCQ_ERANGE: M or M * C / 4 reaches 2^31.  M == 0: DLMCQ_OK, nothing launched.  A refused call writes
+ * nothing. */
+int dlmcq_layernorm_rows_f32(const float* x, const float* gamma, const float* beta, float* out, void* codes, int64_t M, int64_t C,
+                             float eps, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                             float q_ste_g, dlmcq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
