@@ -15,7 +15,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1338,6 +1338,58 @@ def layernorm_quant(x, weight, bias, eps, emit=None, want_out=True):
                    lambda: N.check(N.lib.dlmcq_layernorm_rows_f32(N.ptr(x), N.ptr(weight), N.ptr(bias), N.ptr(out), codes, m, c, float(eps),
                                                                   *tail, N.stream_ptr())))
     return out, q[0]
+
+
+ATTENTION_DIMS = (32, 64)    # dlmcq_attention_f32: the head dimensions the kernel is built for
+
+
+def attention_views(q, k, v):
+    """Whether dlmcq_attention_f32 reads `q` [B, H, Tq, D] and `k`, `v` [B, H, Tk, D] in place: fp32, D in ATTENTION_DIMS, Tk >= 1, unit
+    stride in D, every other stride a multiple of 4 elements and a token's row not overlapping the next, 16-byte aligned."""
+    if not (q.dim() == k.dim() == v.dim() == 4 and q.dtype == k.dtype == v.dtype == torch.float32):
+        return False
+    b, h, tq, d = q.shape
+    if d not in ATTENTION_DIMS or tuple(k.shape) != tuple(v.shape) or tuple(k.shape[:2]) != (b, h) or k.shape[3] != d or k.shape[2] < 1:
+        return False
+    for t in (q, k, v):
+        sb, sh, st, sd = t.stride()
+        if sd != 1 or any(s < 0 or s % 4 for s in (sb, sh, st)) or st < d or t.data_ptr() % 16:
+            return False
+    return True
+
+
+def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True):
+    """softmax(scale * q k^T) v of fp32 views `q` [B, H, Tq, D], `k`, `v` [B, H, Tk, D] (attention_views: read in place, the three
+    slices of one packed projection included) by dlmcq_attention_f32: one flash forward on the f32 matrix cores - k-ordered fmaf
+    chains, an online softmax over key blocks of 32 with the accurate expf, a true division at the end (include/dlmcq.h states the
+    order and the bound); no mask, no dropout.  `merged`: the result as [B, Tq, H * D], the merge-heads permute + reshape a free view;
+    else [B, H, Tq, D].  Returns `(out or None, codes or None)`: fp32 unless `want_out=False`, and with `emit=EmitCodes(...)` the
+    consumer's activation codes of the same values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error)."""
+    N.require_gpu(q, k, v)
+    if not attention_views(q, k, v):
+        raise ValueError("attention_quant: fp32 views q [B, H, Tq, D], k, v [B, H, Tk, D], D in (32, 64), unit stride in D, strides "
+                         "multiples of 4 elements, 16-byte aligned")
+    if not want_out and emit is None:
+        raise ValueError("attention_quant: nothing to produce (want_out=False without emit)")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"attention_quant: a finite scale, not {scale}")
+    q, k, v = q.detach(), k.detach(), v.detach()
+    b, h, tq, d = q.shape
+    tk = k.shape[2]
+    shape = (b, tq, h * d) if merged else (b, h, tq, d)
+    o_strides = (tq * h * d, d, h * d) if merged else (h * tq * d, tq * d, d)
+
+    def alloc(dtype):
+        return torch.empty(shape, dtype=dtype, device=q.device)
+    out = alloc(torch.float32) if want_out else None
+    qz = _quantiser(emit, alloc, q, False, "attention_quant")
+    codes, *tail = _q_args(qz)
+    PROFILE.launch("attention", 4 * b * h * d * (tq + 2 * tk) + b * h * tq * d * (4 * want_out + (emit is not None)),
+                   lambda: N.check(N.lib.dlmcq_attention_f32(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(out), codes, b, h, tq, tk, d,
+                                                             *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o_strides, scale,
+                                                             *tail, N.stream_ptr())), ops=4 * b * h * tq * tk * d)
+    return out, qz[0]
 
 
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):

@@ -34,7 +34,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -1310,6 +1310,225 @@ def _layernorm_pass(gm, report, planned, dry_run):
     _settle(gm, count)
 
 
+class AttentionLayer(_MapCodesLayer):
+    """softmax(scale * q k^T) v of fp32 views [B, H, T, D] as one flash-forward launch (csrc/attention.hip), and - `merged` - the
+    merge-heads `permute(0, 2, 1, 3)` + reshape behind it as a free view: the node returns [B, Tq, H * D] and hands the Linear plan
+    layer that reads it (`to_out`) its activation codes from the same launch.  `emit`: the reader's activation quantiser or None (an
+    fp32-only node); `want_out`: whether anyone reads the fp32 values; `c`: the reader's in-features; `scale`: the Python float of the
+    graph's multiply, or None (F.scaled_dot_product_attention's default, D ** -0.5); `sdpa`: None, or the keyword arguments of the
+    graph's F.scaled_dot_product_attention call; `flatten`: the tail is `flatten(2)`, else the reshape's three shape arguments arrive
+    at run time (graph values, checked there).  Not merged: [B, H, Tq, D], fp32 only.  The torch restatement - the graph's own ops,
+    then K.fake_quant - runs for anything that is not three fp32 device views the kernel reads in place (K.attention_views) with
+    D in K.ATTENTION_DIMS, a merged width other than H * D or `c`.  Returns `(fp32 or None, codes or None)`."""
+
+    def __init__(self, emit, want_out, c, scale, merged, sdpa=None, flatten=False):
+        super().__init__(emit, want_out, c, c, 0, False)
+        self.scale, self.merged, self.flatten = (None if scale is None else float(scale)), bool(merged), bool(flatten)
+        self.sdpa = None if sdpa is None else dict(sdpa)
+
+    def _torch(self, q, k, v, shape):
+        """The unfused graph: the products and the softmax as they were spelled, the tail, the reader's quantise pass."""
+        if self.sdpa is not None:
+            o = F.scaled_dot_product_attention(q, k, v, **self.sdpa)
+        else:
+            o = torch.matmul(torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * self.scale, dim=-1), v)
+        if self.merged:
+            o = o.permute(0, 2, 1, 3)
+            o = o.flatten(2) if self.flatten else o.reshape(*shape)
+        return self._torch_rows(o) if self.emit is not None else (o, None)
+
+    def forward(self, q, k, v, *shape):
+        ok = q.is_cuda and K.attention_views(q, k, v)
+        if ok and self.merged:
+            b, h, tq, d = q.shape
+            want = [b, tq, h * d]
+            if not self.flatten:      # (a reshape to three dimensions, at most one of them -1: the merged heads or something else)
+                dims = [int(x) for x in shape]
+                free = [i for i, x in enumerate(dims) if x == -1]
+                if len(free) == 1 and all(x == y for i, (x, y) in enumerate(zip(dims, want)) if i != free[0]):
+                    dims = want
+                ok = dims == want
+            ok = ok and (self.emit is None or h * d == self.c)
+        if not ok:
+            return self._torch(q, k, v, shape)
+        scale = q.shape[-1] ** -0.5 if self.scale is None else self.scale
+        emit = None if self.emit is None else self.emit.emit(q.numel())
+        return K.attention_quant(q, k, v, scale, emit=emit, want_out=self.want_out, merged=self.merged)
+
+
+class _DryAttentionLayer(AttentionLayer):
+    """fuse_inference(dry_run=...): an AttentionLayer's decision (emit, want_out, c, scale, merged, sdpa, flatten).  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+_MATMUL_FNS = (torch.matmul, operator.matmul)
+_MUL_FNS = (operator.mul, torch.mul)
+_SDPA_NAMES = ("query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale")
+
+
+def _one_user(node):
+    return isinstance(node, fx.Node) and len(node.users) == 1
+
+
+def _is_call(node, fns, method):
+    """`node` calls one of the functions `fns` or the tensor method `method`, without keyword arguments."""
+    if not isinstance(node, fx.Node) or node.kwargs:
+        return False
+    return (node.op == "call_function" and node.target in fns) or (node.op == "call_method" and node.target == method)
+
+
+def _softmax_of(node, modules):
+    """The graph value x if `node` is a softmax of x over its last axis of four (`-1` or `3`) in a spelling the plan takes -
+    torch.softmax, F.softmax, the method, an nn.Softmax module; no dtype argument - else None."""
+    if not isinstance(node, fx.Node):
+        return None
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        ok = type(m) is nn.Softmax and len(node.args) == 1 and not node.kwargs
+        x, dim = (node.args[0], m.dim) if ok else (None, None)
+    elif (node.op == "call_function" and node.target in (torch.softmax, F.softmax)) or (node.op == "call_method" and node.target == "softmax"):
+        if not 1 <= len(node.args) <= 2 or not set(node.kwargs) <= {"dim", "dtype", "_stacklevel"} or (len(node.args) == 2 and "dim" in node.kwargs):
+            return None
+        if node.kwargs.get("dtype") is not None:
+            return None
+        x, dim = node.args[0], (node.args[1] if len(node.args) == 2 else node.kwargs.get("dim"))
+    else:
+        return None
+    return x if isinstance(x, fx.Node) and isinstance(dim, int) and not isinstance(dim, bool) and dim in (-1, 3) else None
+
+
+def _attention_core(node, modules):
+    """(q, k, v, scale, sdpa keyword arguments or None, the nodes it is made of) if `node` is the last node of an attention core the
+    plan takes - `matmul(softmax(matmul(q, k.transpose(-1, -2)) * c, dim=-1), v)`, c a Python float on either side, every
+    intermediate read once; or F.scaled_dot_product_attention(q, k, v) without mask, dropout or causal flag, `scale` None or a float -
+    else None."""
+    if node.op == "call_function" and node.target is F.scaled_dot_product_attention:
+        if len(node.args) > len(_SDPA_NAMES) or not set(node.kwargs) <= set(_SDPA_NAMES[len(node.args):]):
+            return None
+        given = dict(zip(_SDPA_NAMES, node.args), **node.kwargs)
+        q, k, v, scale = given.get("query"), given.get("key"), given.get("value"), given.get("scale")
+        if not all(isinstance(t, fx.Node) for t in (q, k, v)) or given.get("attn_mask") is not None:
+            return None
+        p, causal = given.get("dropout_p", 0.0), given.get("is_causal", False)
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or p != 0 or causal is not False:
+            return None
+        if not (scale is None or (isinstance(scale, float) and math.isfinite(scale))):
+            return None
+        return q, k, v, scale, ({} if scale is None else {"scale": scale}), [node]
+    if not _is_call(node, _MATMUL_FNS, "matmul") or len(node.args) != 2:
+        return None
+    attn, v = node.args
+    scores = _softmax_of(attn, modules)
+    if scores is None or not isinstance(v, fx.Node) or not _one_user(attn) or not _one_user(scores):
+        return None
+    if not _is_call(scores, _MUL_FNS, "mul") or len(scores.args) != 2:
+        return None
+    dots, c = scores.args if isinstance(scores.args[0], fx.Node) else scores.args[::-1]
+    if not isinstance(c, float) or not math.isfinite(c) or not _one_user(dots):
+        return None
+    if not _is_call(dots, _MATMUL_FNS, "matmul") or len(dots.args) != 2:
+        return None
+    q, kt = dots.args
+    if not isinstance(q, fx.Node) or not _one_user(kt) or not _is_call(kt, (torch.transpose,), "transpose") or len(kt.args) != 3:
+        return None
+    k, d0, d1 = kt.args
+    if not isinstance(k, fx.Node) or {d0, d1} not in ({-1, -2}, {2, 3}, {-1, 2}, {-2, 3}) or isinstance(d0, bool) or isinstance(d1, bool):
+        return None
+    return q, k, v, c, None, [node, attn, scores, dots, kt]
+
+
+def _static_head_dim(node):
+    """D where the graph spells it as a Python int: `node` [B, H, T, D] is - through getitem's on leading axes and permutes that keep
+    the last axis last - a reshape / view whose last size is an int.  Else None (decided at run time)."""
+    for _ in range(4):
+        if not isinstance(node, fx.Node) or node.kwargs:
+            return None
+        if node.op == "call_function" and node.target is operator.getitem and isinstance(node.args[1], int):
+            node = node.args[0]
+        elif node.op == "call_method" and node.target == "permute":
+            dims = node.args[1:]
+            dims = tuple(dims[0]) if len(dims) == 1 and isinstance(dims[0], (tuple, list)) else dims
+            if not dims or dims[-1] not in (-1, len(dims) - 1):
+                return None
+            node = node.args[0]
+        elif node.op == "call_method" and node.target in ("reshape", "view"):
+            sizes = node.args[1:]
+            sizes = tuple(sizes[0]) if len(sizes) == 1 and isinstance(sizes[0], (tuple, list)) else sizes
+            last = sizes[-1] if sizes else None
+            return last if isinstance(last, int) and not isinstance(last, bool) and last > 0 else None
+        else:
+            return None
+    return None
+
+
+def _merge_heads_tail(node):
+    """(permute node, reshape node, its shape arguments or None for flatten(2)) if the sole reader of `node` [B, H, T, D] is
+    `permute(0, 2, 1, 3)` / `transpose(1, 2)` whose sole reader reshapes to rank 3 - `reshape` / `view` with three sizes (Python
+    ints or graph values) or `flatten(2)` - else None."""
+    if not _one_user(node):
+        return None
+    (perm,) = node.users
+    if perm.kwargs or perm.op != "call_method" or not perm.args or perm.args[0] is not node or not _one_user(perm):
+        return None
+    dims = perm.args[1:]
+    if len(dims) == 1 and isinstance(dims[0], (tuple, list)):
+        dims = tuple(dims[0])
+    if not ((perm.target == "permute" and tuple(dims) == (0, 2, 1, 3)) or (perm.target == "transpose" and tuple(sorted(dims)) == (1, 2))):
+        return None
+    (shape,) = perm.users
+    if shape.kwargs or not shape.args or shape.args[0] is not perm:
+        return None
+    if (shape.op == "call_method" and shape.target == "flatten") or (shape.op == "call_function" and shape.target is torch.flatten):
+        return (perm, shape, None) if tuple(shape.args[1:]) in ((2,), (2, -1), (2, 3)) else None
+    if shape.op != "call_method" or shape.target not in ("reshape", "view"):
+        return None
+    sizes = shape.args[1:]
+    if len(sizes) == 1 and isinstance(sizes[0], (tuple, list)):
+        sizes = tuple(sizes[0])
+    ok = len(sizes) == 3 and all(isinstance(x, fx.Node) or (isinstance(x, int) and not isinstance(x, bool)) for x in sizes)
+    return (perm, shape, tuple(sizes)) if ok else None
+
+
+def _attention_pass(gm, report, planned, dry_run):
+    """Attention (fuse_inference(attention=True)): the core `softmax(q k^T * c) v` (_attention_core) becomes one node (AttentionLayer,
+    csrc/attention.hip).  With the merge-heads tail behind it (_merge_heads_tail) the node stands where the reshape stood, returns
+    [B, Tq, H * D], and the Linear plan layers reading it - one quantiser, as for a LayerNorm - take its codes; anyone else reads the
+    fp32 values of the same launch.  Without the tail it stands where the second product stood and returns fp32 [B, H, Tq, D].
+    `planned`: plan node -> what the main pass decided for it (_Decision), which stays - only the reader's input changes."""
+    graph = gm.graph
+    modules = dict(gm.named_modules())
+    count = 0
+    for node in list(graph.nodes):
+        if node.op not in ("call_function", "call_method"):
+            continue
+        core = _attention_core(node, modules)
+        if core is None:
+            continue
+        q, k, v, scale, sdpa, made_of = core
+        if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:      # (a head dimension the kernel is not built for, spelled as an int)
+            continue
+        tail = _merge_heads_tail(node)
+        cls = _DryAttentionLayer if dry_run else AttentionLayer
+        name = f"_int8_attention_{count}"
+        if tail is None:
+            module = cls(None, True, 0, scale, False, sdpa)
+            _splice_map_node(gm, node, name, module, (q, k, v), [], made_of)
+        else:
+            perm, shape, sizes = tail
+            taken = _code_readers(planned, shape, linear=True)
+            if taken is not None and any(planned[u].mod.weight.dim() != 2 for u in taken.takers):
+                taken = None
+            module = (cls(None, True, 0, scale, True, sdpa, sizes is None) if taken is None else
+                      cls(taken.emit, taken.want_out, taken.c, scale, True, sdpa, sizes is None))
+            _splice_map_node(gm, shape, name, module, (q, k, v) + (sizes or ()), [] if taken is None else taken.takers,
+                             [shape, perm] + made_of)
+        count += 1
+    report.attentions = count
+    _settle(gm, count)
+
+
 _GELU_ALPHA = 0.70710678118654752440      # 1 / sqrt(2): as a Python scalar torch multiplies an fp32 tensor by its fp32 rounding
 
 
@@ -1615,6 +1834,7 @@ class FusionReport:
         self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
+        self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -1647,6 +1867,7 @@ class FusionReport:
                 (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
+                (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
                 (f"5x5 depthwise on the dot-product kernel={self.dw5}, " if self.dw5 else "") +
                 f"not eligible={self.skipped})")
 
@@ -2189,7 +2410,7 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False):
+                   recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2326,14 +2547,26 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     of the average-pool rule), never both (GeluLayer, csrc/gelu.hip: the fourth map-to-codes op).  Left as they are: F.layer_norm, a
     LayerNorm over more dimensions, other widths, the tanh form, a LayerNorm or GELU nobody takes as codes, readers that disagree on
     their quantiser.  Both passes run after the main pass, whose decisions for the Linear layers stay - only their input changes, from
-    fp32 to codes - and before the head pass; attention's products and softmax stay in torch.  An input that at run time is no fp32
+    fp32 to codes - and before the head pass; attention's products and softmax stay in torch unless `attention=True` (below).  An input that at run time is no fp32
     device tensor of the planned width takes the node's torch restatement.  The codes are K.fake_quant of the node's own fp32 values bit
     for bit, so the plan equals the flag-off plan of the network whose LayerNorm / GELU modules return the kernels' fp32 outputs
     (tests/test_gpu_transformer.py); against torch's own LayerNorm the values differ in the last bits (another summation order), within
     the stated bounds.  Measured (tools/transformer_ab.py, profiles/transformer_ab.json; ViT-S/16, 25 LayerNorm and 12 GELU nodes, batch
     256 at 224^2, interleaved): flags off / on = 16.54 / 13.84 ms per step (FSPTQ W8A8), 16.52 / 13.84 (QBase W8A8), ratio 1.20 / 1.19 at a
     spread of 0.06 ms; about half the logits differ, by at most 0.035 at a largest logit of 1.3.  Off by default: the plan without them
-    is the plan as it was."""
+    is the plan as it was.
+    `attention=True`: `matmul(softmax(matmul(q, k.transpose(-1, -2)) * c, dim=-1), v)` - c a Python float on either
+    side; torch.softmax, F.softmax, the method or an nn.Softmax module over the last axis; every intermediate read once - or
+    F.scaled_dot_product_attention(q, k, v) without mask, dropout or causal flag becomes one AttentionLayer node (csrc/attention.hip: a
+    flash forward on the f32 matrix cores, fp32 semantics, the stated operation order and error bound of include/dlmcq.h;
+    `fusion_report.attentions` counts the nodes).  With the merge-heads tail behind it - `permute(0, 2, 1, 3)` / `transpose(1, 2)`,
+    then `reshape` / `view` to three sizes or `flatten(2)`, each read once - the node stands where the reshape stood, writes
+    [B, Tq, H * D] directly and hands the Linear plan layers that read it (one quantiser) their activation codes from the same launch;
+    without it the node stands where the second product stood, fp32 only.  Left alone: a mask added to the scores, is_causal, dropout,
+    a softmax over another axis, scores with a second reader, a head dimension spelled as an int other than 32 or 64.  At run time,
+    anything that is not three fp32 device views the kernel reads in place (unit stride in D, strides multiples of 4 elements, 16-byte
+    aligned, D 32 or 64), or a reshape that turns out not to merge the heads, takes the node's torch restatement: the graph's own ops.
+    Runs after the LayerNorm and GELU passes.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -2362,6 +2595,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _layernorm_pass(gm, report, planned, dry_run)
     if gelu:
         _gelu_pass(gm, report, planned, dry_run, dwpw)
+    if attention:
+        _attention_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and (not dry_run or dry_run == "chains"):

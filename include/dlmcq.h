@@ -996,6 +996,46 @@ int dlmcq_layernorm_rows_f32(const float* x, const float* gamma, const float* be
                              float eps, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
                              float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- Scaled dot-product attention softmax(scale q k^T) v: fp32 and / or the activation codes of the projection behind it ----
+ * One flash forward per query tile (csrc/attention.hip): nothing of size Tq x Tk touches memory.  No mask, no causal flag, no dropout.
+ * For query row i of one (b, h), keys j = 0 .. Tk - 1 in blocks of 32 (the online softmax's key block), u = 2^-24:
+ *     a_ij = the k-ordered fmaf chain over D from +0 (v_mfma_f32_32x32x2_f32: bit for bit fmaf(q[D-1], k[D-1], ... fmaf(q[0], k[0], +0)))
+ *     s_ij = fl32(a_ij * scale)               one IEEE multiply
+ *     per key block, m the running maximum (-inf at first), keys past Tk - 1 holding s = -inf:
+ *     m'   = max(m, max_j s_ij)               NaNs dropped by the maximum: a NaN score reaches p instead
+ *     m~   = m', or 0 where m' = -inf
+ *     al   = expf(fl32(m - m~))               the device library's accurate expf (1 ulp), not v_exp_f32
+ *     p_ij = expf(fl32(s_ij - m~))
+ *     l_h  = fl32(fl32(l_h * al) + t_h)       h = bit 2 of the key index; t_h: the half's 16 p_ij added one by one in ascending key order
+ *     w_g  = the chain fmaf(v_j[c], p_ij, w_g) from +0 over the block's keys 8 g .. 8 g + 7 in the order 0 4 1 5 2 6 3 7 (+ 8 g), g = 0 .. 3
+ *     o_ic = fl32(fl32(o_ic * al) + fl32(fl32(w_0 + w_1) + fl32(w_2 + w_3)))      chains of 8 and a tree: one chain over alike summands drifts
+ *     at the end: l = fl32(l_0 + l_1), out_ic = fl32(o_ic / l)      a true division, correctly rounded
+ *     out = out_ic;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused) of out_ic - the code dlmcq_fake_quant_f32
+ *                    gives for it.  The shifted emission is NOT accepted: the reader is a Linear layer, which takes plain codes.
+ * Non-finite inputs give the NaNs of the unfused graph (matmul, multiply, softmax, matmul), element for element: a NaN in q_i makes
+ * row i NaN and no other; a NaN in any k_j makes every row of the head NaN; a +inf score makes its row NaN; a NaN in v_j[c] makes
+ * column c of every row of the head NaN and leaves the other columns finite.
+ * Against real arithmetic on the same fp32 inputs (p*, o* real), with delta_i = (D + 1) u scale max_j sum_k |q_ik k_jk|, nb = ceil(Tk / 32)
+ * and kappa = 2 (104 + 2 + 3 nb + 32 nb) + 1:
+ *     |out_ic - o*_ic| <= (2 delta_i + kappa u) sum_j p*_ij |v_jc| + 2^-126 max_j |v_jc|
+ * (csrc/attention.hip derives it: 104 is the largest m - s whose term is not 0 in fp32, the last summand stands for such terms).
+ * No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.
+ *   q        fp32 view [B, H, Tq, D]: element strides q_sb, q_sh, q_st (batch, head, token), unit stride in D, 16-byte aligned
+ *   k, v     fp32 views [B, H, Tk, D], strides k_* / v_*, likewise - the packed [B, T, 3, H, D] output of one projection is three such
+ *            views, read in place
+ *   out      fp32, written at b o_sb + h o_sh + t o_st + c (o_sb = Tq H D, o_sh = D, o_st = H D: [B, Tq, H D], the merged heads), 16-byte
+ *            aligned, or NULL
+ *   codes    bytes at the same element offsets, 4-byte aligned, or NULL (needs q_scale)
+ * DLMCQ_EINVAL: B, H or Tq < 0, Tk < 1, D not 32 or 64, scale not finite, a stride negative or no multiple of 4, a token stride below D,
+ * q / k / v NULL, both outputs NULL, an invalid quantiser, any control or layout bit or DLMCQ_EMIT_SHIFT128 in q_form (refused, not
+ * stripped).  DLMCQ_EALIGN: q / k / v / out not 16-byte aligned, codes not 4-byte aligned.  DLMCQ_ERANGE: B, H, Tq, Tk, B * H or
+ * B * H * ceil(Tq / 128) reaches 2^31.  B * H * Tq == 0: DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
+                        int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
+                        int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
+                        const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                        dlmcq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
