@@ -837,6 +837,11 @@ extern "C" int dlmcq_x_conv3x3_variant_table(int which, int32_t* answers, int ca
   return which == 0 ? conv3x3_halo_table(answers, cap) : which == 1 ? conv3x3_pipe_table(answers, cap) : -1;
 }
 
+// The weight-resident 1 x 1 kernels' tables likewise: `which` 0 = conv_pw_i8_kernel's, 1 = conv_pwr_i8_kernel's; DLMCQ_ROUTE_PW_VARIANT answers
+extern "C" int dlmcq_x_pw_variant_table(int which, int32_t* answers, int cap) {
+  return which == 0 ? conv_pw_table(answers, cap) : which == 1 ? conv_pwr_table(answers, cap) : -1;
+}
+
 // value -> kernel: the one place the kernel's positional template list is spelt (LAB: the lab library's what-bounds-the-step variants)
 template <int BN, unsigned F, int LAB = 0>
 static int conv_tiled_go(const ConvCall& c, const ConvGeom& g, const ConvSeg2& s2) {
@@ -868,7 +873,7 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   const ConvSeg2* const seg2 = c.seg2;
   const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, R = c.R, S = c.S, P = c.P, Q = c.Q, M = c.M;
   if (mm_count) *mm_count = 0;
-  if ((ep.ctl & (DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT)) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;     // (questions about the route, never a launch)
+  if ((ep.ctl & (DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_PW_VARIANT)) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;    // (questions about the route, never a launch)
   if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || c.stride < 1 || c.pad < 0 || c.dil < 1) return DLMCQ_EINVAL;
   if (C % CV_BK != 0) return DLMCQ_EINVAL;  // the K step is 64 input channels
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;
@@ -925,8 +930,10 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   // (only the block-end kernel knows the chunk-major form of the fp32 block tensors: a call that carries the bits and would land
   //  elsewhere is refused, never silently read row-major.  Callers ask first: DLMCQ_ROUTE_ONLY without the bits)
   if ((ep.ctl & (DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR)) && !(special && conv_pwr_applies(c))) return DLMCQ_EINVAL;
-  if (special && conv_pw_applies(c)) return route_only ? DLMCQ_ROUTE_PW : conv_pw_launch(c);
-  if (special && conv_pwr_applies(c)) return route_only ? DLMCQ_ROUTE_PWR : conv_pwr_launch(c);
+  // (DLMCQ_ROUTE_PW_VARIANT: the route query names the instantiation - the record the launch itself reads - instead of the family)
+  const bool which_pw = (ep.ctl & DLMCQ_ROUTE_PW_VARIANT) != 0;
+  if (special && conv_pw_applies(c)) return route_only ? (which_pw ? conv_pw_answer(c) : DLMCQ_ROUTE_PW) : conv_pw_launch(c);
+  if (special && conv_pwr_applies(c)) return route_only ? (which_pw ? conv_pwr_answer(c) : DLMCQ_ROUTE_PWR) : conv_pwr_launch(c);
   if (special && conv3x3_halo_applies(c)) {
     // ... persistent and pipelined across tiles on request (DLMCQ_PIPELINED: csrc/conv3x3_pipe_i8.hip - bit-identical, measured slower)
     // (DLMCQ_ROUTE_HALO_VARIANT: the route query names the instantiation - the record the launch itself reads - instead of the family)

@@ -252,10 +252,14 @@ int conv3x3_pipe_table(int32_t* answers, int cap);
 // conv_pw_i8.hip: pointwise codes-to-codes layers with the weights resident in LDS (MobileOne's 1x1 layers)
 bool conv_pw_applies(const ConvCall& c);
 int conv_pw_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
+int conv_pw_answer(const ConvCall& c);
+int conv_pw_table(int32_t* answers, int cap);
 
 // conv_pwr_i8.hip: 1 x 1 block ends with an fp32 shortcut (+ fp32 output) + ReLU + codes, the weights resident in LDS
 bool conv_pwr_applies(const ConvCall& c);
 int conv_pwr_launch(const ConvCall& c);
+int conv_pwr_answer(const ConvCall& c);
+int conv_pwr_table(int32_t* answers, int cap);
 
 // One first-layer convolution as the host sees it: what an entry point of conv_stem_i8.hip received, once, by name.  `x` is the padded
 // NHWC4 code buffer [N][Hp][Wp][4]; ep.w_off / ep.x_off / ep.x_tap (and C, xpad with them) are the entry point's to set.
@@ -275,6 +279,8 @@ struct StemCall {
   ConvEpi ep;
   int32_t q_lo, q_hi, q_form;      // the quantiser's range and form as passed (stem_check validates these)
   int64_t P, Q, M;                 // derived by stem_call: the output's height and width, N * P * Q
+  bool which;                      // DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_PW_VARIANT in `q_form`: validate, launch nothing, answer the instantiation
+  bool lone;                       // DLMCQ_ROUTE_PW_VARIANT without DLMCQ_ROUTE_ONLY: refused whatever else the call holds
 };
 
 // One depthwise convolution as the host sees it (conv_dw_i8.hip's entry points; conv_dwm_i8.hip takes the same record)
@@ -306,6 +312,7 @@ int conv_dwm_table(int32_t* answers, int cap);                 // every instanti
 // conv_stem_pool7_i8.hip: the ResNet first layer (7x7 / 2 + ReLU + 3x3 / 2 max-pool + quantiser) with the pooling in registers
 bool stem_pool7_applies(const StemCall& c);
 int stem_pool7_launch(const StemCall& c);
+bool stem_pool7_xs(const StemCall& c);     // which of its two instantiations (XS): read by the launch and by the route query
 
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

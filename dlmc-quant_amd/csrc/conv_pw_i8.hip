@@ -338,20 +338,32 @@ static int pw_go(const PwArgs& a0, const ConvEpi& ep, hipStream_t st) {
   return launch_status();
 }
 
+// Which instantiation conv_pw_launch runs for a call conv_pw_applies took, computed ONCE: the launch and the route query
+// (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_PW_VARIANT) read this one record
+struct PwVariant {
+  int C, bn;         // input channels, slice width
+  bool asym, r6;
+};
+static PwVariant pw_variant(const ConvCall& c) {
+  return PwVariant{(int)c.C, pw_slice(c.K), c.ep.w_off != nullptr, c.ep.relu == DLMCQ_ACT_RELU6};
+}
+// include/dlmcq.h: tag | C / 64 << 8 | slice / 64 << 4 | flags
+static int pw_variant_answer(const PwVariant& v) {
+  return DLMCQ_ROUTE_PW_VARIANT_TAG | ((v.C / 64) << 8) | ((v.bn / 64) << 4) | (v.asym ? 2 : 0) | (v.r6 ? 1 : 0);
+}
+
 int conv_pw_launch(const ConvCall& c, int lab, void* lab_trace) {
   const ConvEpi& ep = c.ep;
-  const int64_t C = c.C, K = c.K;
   const hipStream_t st = c.st;
+  const PwVariant v = pw_variant(c);
   PwArgs a{};
   a.trace = static_cast<unsigned long long*>(lab_trace);
   a.x = c.x; a.w = c.w; a.s_w = c.s_w; a.wsum = c.wsum; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
-  a.M = (int)c.M; a.K = (int)K; a.shift = c.shift;
+  a.M = (int)c.M; a.K = (int)c.K; a.shift = c.shift;
   a.nblk = (a.M + 31) / 32;
-  const bool asym = ep.w_off != nullptr;
-  const int bn = pw_slice(K);
 #ifdef DLMCQ_LAB
 #define DLMCQ_PWL(CC, BB, L) \
-  if (C == CC && bn == BB && lab == L && asym) return pw_go<CC, BB, true, L>(a, ep, st)
+  if (v.C == CC && v.bn == BB && lab == L && v.asym) return pw_go<CC, BB, true, L>(a, ep, st)
 #define DLMCQ_PWLS(CC, BB) DLMCQ_PWL(CC, BB, 1); DLMCQ_PWL(CC, BB, 2); DLMCQ_PWL(CC, BB, 4); DLMCQ_PWL(CC, BB, 6); DLMCQ_PWL(CC, BB, 7); DLMCQ_PWL(CC, BB, 8); DLMCQ_PWL(CC, BB, 9)
   DLMCQ_PWLS(128, 128);
   DLMCQ_PWLS(192, 192);
@@ -361,14 +373,31 @@ int conv_pw_launch(const ConvCall& c, int lab, void* lab_trace) {
 #undef DLMCQ_PWL
 #endif
   if (lab) return DLMCQ_EINVAL;
-  const bool r6 = ep.relu == DLMCQ_ACT_RELU6;     // (the R6 instantiations: ReLU6's upper bound)
 #define DLMCQ_PW(CC, BB)                                                                                       \
-  if (C == CC && bn == BB)                                                                                     \
-    return r6 ? (asym ? pw_go<CC, BB, true, 0, true>(a, ep, st) : pw_go<CC, BB, false, 0, true>(a, ep, st))     \
-              : (asym ? pw_go<CC, BB, true>(a, ep, st) : pw_go<CC, BB, false>(a, ep, st));
+  if (v.C == CC && v.bn == BB)                                                                                 \
+    return v.r6 ? (v.asym ? pw_go<CC, BB, true, 0, true>(a, ep, st) : pw_go<CC, BB, false, 0, true>(a, ep, st)) \
+                : (v.asym ? pw_go<CC, BB, true>(a, ep, st) : pw_go<CC, BB, false>(a, ep, st));
   DLMCQ_PW_PAIRS(DLMCQ_PW)
 #undef DLMCQ_PW
   return DLMCQ_EINVAL;
+}
+
+int conv_pw_answer(const ConvCall& c) {
+  const PwVariant v = pw_variant(c);
+  return pw_built(v.C, v.bn) ? pw_variant_answer(v) : DLMCQ_EINVAL;
+}
+
+// the table itself, for tests: DLMCQ_PW_PAIRS x ASYM x R6, in the table's order
+int conv_pw_table(int32_t* answers, int cap) {
+  int n = 0;
+#define DLMCQ_PW_LIST(CC, BB)                                                      \
+  for (int f = 0; f < 4; ++f) {                                                    \
+    if (n < cap && answers) answers[n] = pw_variant_answer(PwVariant{CC, BB, (f & 2) != 0, (f & 1) != 0}); \
+    ++n;                                                                           \
+  }
+  DLMCQ_PW_PAIRS(DLMCQ_PW_LIST)
+#undef DLMCQ_PW_LIST
+  return n;
 }
 
 }  // namespace dlmcq

@@ -377,11 +377,28 @@ static int pwr_go(const PwrArgs& a0, const ConvEpi& ep, hipStream_t st) {
   return launch_status();
 }
 
+// Which instantiation conv_pwr_launch runs for a call conv_pwr_applies took, computed ONCE: the launch and the route query
+// (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_PW_VARIANT) read this one record.  The dual form is one kernel (256 channels row by row, 512 sampled,
+// fp32 output and codes) with either pair as the call's first: C is the row-by-row pair's depth, swp says the sampled one came first.
+struct PwrVariant {
+  int C;
+  bool outf, codes;
+  int C2;
+  bool swp;
+};
+static PwrVariant pwr_variant(const ConvCall& c) {
+  if (c.seg2) return PwrVariant{256, true, true, 512, c.C != 256};
+  return PwrVariant{(int)c.C, c.out != nullptr, c.ep.codes != nullptr, 0, false};
+}
+// include/dlmcq.h: tag | C / 256 << 4 | flags
+static int pwr_variant_answer(const PwrVariant& v) {
+  return DLMCQ_ROUTE_PWR_VARIANT_TAG | ((v.C / 256) << 4) | (v.swp ? 8 : 0) | (v.C2 ? 4 : 0) | (v.outf ? 2 : 0) | (v.codes ? 1 : 0);
+}
+
 int conv_pwr_launch(const ConvCall& c) {
   const ConvEpi& ep = c.ep;
   const ConvSeg2* const seg2 = c.seg2;
   float* const out = c.out;
-  const int64_t C = c.C;
   const hipStream_t st = c.st;
   PwrArgs a{};
   a.x = c.x; a.w = c.w; a.s_w = c.s_w; a.wsum = c.wsum; a.bias = c.bias; a.s_in = c.s_in; a.zp_in = c.zp_in;
@@ -398,12 +415,13 @@ int conv_pwr_launch(const ConvCall& c) {
 #define DLMCQ_PWR_NW512 8
 #endif
   constexpr int N2 = DLMCQ_PWR_NW256, N5 = DLMCQ_PWR_NW512;
+  const PwrVariant v = pwr_variant(c);
   if (seg2) {
     const ConvGeom& g2 = seg2->g;
     a.P = (int)c.P; a.Q = (int)c.Q;
     a.qdiv = make_fastdiv((uint32_t)c.Q);
     a.pdiv = make_fastdiv((uint32_t)c.P);
-    if (C == 256) {      // the call's first pair is the row-by-row one
+    if (!v.swp) {      // the call's first pair is the row-by-row one
       a.x2 = seg2->x; a.w2 = seg2->w; a.s_w2 = seg2->s_w; a.wsum2 = seg2->wsum; a.bias2 = seg2->bias; a.s_in2 = seg2->s_in; a.zp_in2 = seg2->zp_in;
       a.shift2 = seg2->shift; a.H2 = g2.H; a.W2 = g2.W; a.stride2 = g2.stride;
       return pwr_go<256, 6, true, true, 512, false>(a, ep, st);
@@ -415,10 +433,27 @@ int conv_pwr_launch(const ConvCall& c) {
     a.shift2 = c.shift; a.H2 = (int)c.H; a.W2 = (int)c.W; a.stride2 = c.stride;
     return pwr_go<256, 6, true, true, 512, true>(a, ep, st);
   }
-  if (!ep.codes) return C == 256 ? pwr_go<256, N2, true, false>(a, ep, st) : (C == 512 ? pwr_go<512, N5, true, false>(a, ep, st) : DLMCQ_EINVAL);
-  if (C == 256) return out ? pwr_go<256, N2, true>(a, ep, st) : pwr_go<256, N2, false>(a, ep, st);
-  if (C == 512) return out ? pwr_go<512, N5, true>(a, ep, st) : pwr_go<512, N5, false>(a, ep, st);
+  if (!v.codes) return v.C == 256 ? pwr_go<256, N2, true, false>(a, ep, st) : (v.C == 512 ? pwr_go<512, N5, true, false>(a, ep, st) : DLMCQ_EINVAL);
+  if (v.C == 256) return v.outf ? pwr_go<256, N2, true>(a, ep, st) : pwr_go<256, N2, false>(a, ep, st);
+  if (v.C == 512) return v.outf ? pwr_go<512, N5, true>(a, ep, st) : pwr_go<512, N5, false>(a, ep, st);
   return DLMCQ_EINVAL;
+}
+
+int conv_pwr_answer(const ConvCall& c) {
+  const PwrVariant v = pwr_variant(c);
+  return (v.C == 256 || v.C == 512) ? pwr_variant_answer(v) : DLMCQ_EINVAL;
+}
+
+// the table itself, for tests: the eight instantiations conv_pwr_launch names, in its order
+int conv_pwr_table(int32_t* answers, int cap) {
+  const PwrVariant all[] = {{256, true, true, 512, false}, {256, true, true, 512, true}, {256, true, false, 0, false}, {512, true, false, 0, false},
+                            {256, true, true, 0, false},   {256, false, true, 0, false}, {512, true, true, 0, false},  {512, false, true, 0, false}};
+  int n = 0;
+  for (const PwrVariant& v : all) {
+    if (n < cap && answers) answers[n] = pwr_variant_answer(v);
+    ++n;
+  }
+  return n;
 }
 
 }  // namespace dlmcq

@@ -771,6 +771,12 @@ static StemCall stem_call(const void* xpad, const int8_t* w, float* out, const f
   c.C = 4; c.N = N; c.Hp = Hp; c.Wp = Wp; c.K = K; c.R = R; c.S = S; c.stride = stride;
   c.shift = x_is_unsigned ? 128 : 0;
   c.st = reinterpret_cast<hipStream_t>(stream);
+  // the one question these entry points take: both bits together (stem_check refuses the variant bit alone; DLMCQ_ROUTE_ONLY alone is a bit
+  // like any other, refused by the quantiser's check)
+  constexpr int32_t QUERY = DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_PW_VARIANT;
+  c.which = (q_form & QUERY) == QUERY;
+  c.lone = !c.which && (q_form & DLMCQ_ROUTE_PW_VARIANT);
+  if (c.which) q_form &= ~QUERY;
   c.ep = make_epi_form(nullptr, relu, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   c.q_lo = q_lo; c.q_hi = q_hi; c.q_form = q_form;
   c.P = (Hp - R) / (stride > 0 ? stride : 1) + 1;     // (a stride below 1 is refused by stem_check; until then it must not divide by zero)
@@ -782,6 +788,7 @@ static StemCall stem_call(const void* xpad, const int8_t* w, float* out, const f
 // Every check the four first-layer entry points share, in one order (tests/golden/dw_stem_refusals.json pins it).  DLMCQ_OK with
 // c.M == 0: an empty problem, nothing to launch.  (M < N * Hp * Wp: the second bound covers every 32-bit index of both kernels.)
 static int stem_check(const StemCall& c) {
+  if (c.lone) return DLMCQ_EINVAL;     // (a question about the instantiation, never a launch)
   if (c.N < 0 || c.Hp < 1 || c.Wp < 1 || c.K < 1 || c.R < 1 || c.R > ST_MAXR || c.S < 1 || c.S > 8 || c.stride < 1) return DLMCQ_EINVAL;
   if (c.Hp < c.R || c.Wp < c.S || (c.K & 3)) return DLMCQ_EINVAL;
   if (c.M == 0) return DLMCQ_OK;
@@ -790,6 +797,44 @@ static int stem_check(const StemCall& c) {
   if (!aligned4(c.x) || !aligned16(c.w) || (c.out && !aligned16(c.out)) || (c.ep.codes && !aligned4(c.ep.codes))) return DLMCQ_EALIGN;
   if (c.M >= (1ll << 31) || c.N * c.Hp * c.Wp >= (1ll << 31)) return DLMCQ_ERANGE;
   return DLMCQ_OK;
+}
+
+// Which instantiation a validated call runs, computed ONCE: the launch and the route query (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_PW_VARIANT) read
+// this one record.  A float offset (the entry point has checked R: 3 or 7) has the unswapped epilogue; 3 x 3 first layers that emit only
+// codes (RepVGG, MobileOne) the swapped one.
+static const StemVariant* stem_variant(const StemCall& c) {
+  const bool xoff = c.ep.x_off != nullptr;
+  const bool swap = !xoff && c.R == 3 && !c.out && c.ep.codes && c.K % 64 == 0 && aligned16(c.ep.codes);
+  const bool asym = c.ep.w_off != nullptr, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
+  for (const StemVariant& t : STEM_TABLE)
+    if (t.R == c.R && t.asym == asym && t.swap == swap && t.r6 == r6 && t.xoff == xoff) return &t;
+  return nullptr;
+}
+// include/dlmcq.h: tag | kernel << 12 | R << 4 | flags
+static int stem_variant_answer(const StemVariant& v) {
+  return DLMCQ_ROUTE_STEM_VARIANT_TAG | (v.R << 4) | (v.xoff ? 8 : 0) | (v.swap ? 4 : 0) | (v.asym ? 2 : 0) | (v.r6 ? 1 : 0);
+}
+static const StemPoolVariant* stem_pool_variant(const StemCall& c) {
+  for (const StemPoolVariant& t : STEM_POOL_TABLE)
+    if (t.R == c.R) return &t;
+  return nullptr;
+}
+// the pooled first layer: the ResNet shape (7 rows, stride 2, 64 channels, codes only) pools in registers (conv_stem_pool7_i8.hip)
+static int stem_pool_answer(const StemPoolVariant& v) { return DLMCQ_ROUTE_STEM_VARIANT_TAG | (1 << 12) | (v.R << 4); }
+// (stem_pool7_xs, conv_stem_pool7_i8.hip: the one template parameter of the in-register kernel, read by its launch and by the query)
+static int stem_pool7_answer(bool xs) { return DLMCQ_ROUTE_STEM_VARIANT_TAG | (2 << 12) | (xs ? 1 : 0); }
+static bool stem_pool7_takes(const StemCall& c) { return stem_pool7_applies(c) && aligned16(c.ep.codes) && aligned16(c.x); }
+
+// The tables themselves, for tests (absent from include/dlmcq.h): fills up to `cap` answers in the tables' order - STEM_TABLE, then
+// STEM_POOL_TABLE, then the two conv_stem_pool7_i8_kernel instantiations - and returns how many there are
+extern "C" int dlmcq_x_stem_variant_table(int32_t* answers, int cap) {
+  int n = 0;
+  auto put = [&](int a) { if (n < cap && answers) answers[n] = a; ++n; };
+  for (const StemVariant& t : STEM_TABLE) put(stem_variant_answer(t));
+  for (const StemPoolVariant& t : STEM_POOL_TABLE) put(stem_pool_answer(t));
+  put(stem_pool7_answer(false));
+  put(stem_pool7_answer(true));
+  return n;
 }
 
 static int stem_launch(const StemCall& c) {
@@ -803,15 +848,9 @@ static int stem_launch(const StemCall& c) {
   g.qdiv = make_fastdiv((uint32_t)c.Q);
   g.pdiv = make_fastdiv((uint32_t)c.P);
   g.xpad = c.xpad;
-  // the key: a float offset (the entry point has checked R: 3 or 7) has the unswapped epilogue; 3 x 3 first layers that emit only codes
-  // (RepVGG, MobileOne) the swapped one
-  const bool xoff = c.ep.x_off != nullptr;
-  const bool swap = !xoff && c.R == 3 && !c.out && c.ep.codes && c.K % 64 == 0 && aligned16(c.ep.codes);
-  const bool asym = c.ep.w_off != nullptr, r6 = c.ep.relu == DLMCQ_ACT_RELU6;
-  const StemVariant* v = nullptr;
-  for (const StemVariant& t : STEM_TABLE)
-    if (t.R == c.R && t.asym == asym && t.swap == swap && t.r6 == r6 && t.xoff == xoff) v = &t;
+  const StemVariant* const v = stem_variant(c);
   if (!v) return DLMCQ_EINVAL;
+  if (c.which) return stem_variant_answer(*v);
   const int wgs = (g.ntiles + 3) / 4;
   const dim3 grid((uint32_t)(wgs < 2048 ? wgs : 2048), (uint32_t)((c.K + 63) / 64));
   hipLaunchKernelGGL(v->kernel, grid, dim3(256), 0, c.st, c.x, c.w, c.out, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep);
@@ -873,8 +912,7 @@ extern "C" int dlmcq_conv2d_i8_stem_pool_fused(const void* xpad, const int8_t* w
   const StemCall c = stem_call(DLMCQ_STEM_ABI);
   const int rc = stem_check(c);
   if (rc != DLMCQ_OK || c.M == 0) return rc;
-  // the ResNet shape (7 rows, stride 2, 64 channels, codes only): pooling in registers (conv_stem_pool7_i8.hip)
-  if (stem_pool7_applies(c) && aligned16(c.ep.codes) && aligned16(c.x)) return stem_pool7_launch(c);
+  if (stem_pool7_takes(c)) return c.which ? stem_pool7_answer(stem_pool7_xs(c)) : stem_pool7_launch(c);
   StemPoolGeom g;
   g.N = (int)c.N; g.Hp = (int)c.Hp; g.Wp = (int)c.Wp; g.K = (int)c.K; g.stride = stride; g.P = (int)c.P; g.Q = (int)c.Q;
   g.PP = (int)((c.P + 2 - 3) / 2 + 1);     // MaxPool2d(3, 2, 1), floor mode
@@ -885,10 +923,9 @@ extern "C" int dlmcq_conv2d_i8_stem_pool_fused(const void* xpad, const int8_t* w
   g.twdiv = make_fastdiv((uint32_t)g.tiles_w);
   g.thdiv = make_fastdiv((uint32_t)g.tiles_h);
   g.nwork = (uint32_t)wgs;
-  const StemPoolVariant* v = nullptr;
-  for (const StemPoolVariant& t : STEM_POOL_TABLE)
-    if (t.R == c.R) v = &t;
+  const StemPoolVariant* const v = stem_pool_variant(c);
   if (!v) return DLMCQ_EINVAL;
+  if (c.which) return stem_pool_answer(*v);
   hipLaunchKernelGGL(v->kernel, dim3((uint32_t)(wgs < 1024 ? wgs : 1024)), dim3(256), 0, c.st, c.x, c.w, c.out, c.bias,
                      c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep);
   return launch_status();

@@ -114,6 +114,13 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool7_i8_kernel(const uint8_
   const int64_t img0 = (int64_t)n * g.Hp * g.Wp * 4;
   const int64_t win0 = (int64_t)(16 * q0 - 8);                      // byte offset of the window in a row (-8 for the first tile)
   const int rowbytes = g.Wp * 4;
+  // A unit wholly outside the buffer only ever reaches pixels that do not exist: its load is clamped into the buffer and brings whatever.
+  // A unit that STRADDLES an end of the buffer (the window starts 8 bytes before a row: the first unit of row 0 of image 0; the unit over
+  // the last bytes of the last image where the buffer's size is not 8 mod 16) holds pixels that do exist, and clamping shifts them inside
+  // the unit.  Only the first band of image 0 and the last band of the last image can hold one (`edge`, wave-uniform): there the lane
+  // that owns such a unit rewrites it after the DMA has landed, pixel by pixel (x is 16-byte aligned, the unit 8 mod 16: whole dwords),
+  // zeros where the buffer ends.  Everything is drained around the rewrite, so the loop's counted waits see a shorter queue, never a longer.
+  const bool edge = __builtin_amdgcn_readfirstlane((int)((n == 0 && p0 == 0) || ((int)n == g.N - 1 && band == g.bands - 1))) != 0;
   auto issue_group = [&](int p) {
     int8_t* const dst = ring + (((p + 1) & 3) * 4) * P7_ROWB;
 #pragma unroll
@@ -121,8 +128,28 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool7_i8_kernel(const uint8_
       const int i = k * 64 + lane;
       const int r = i / 34, u = i - r * 34;
       int64_t off = img0 + (int64_t)(4 * p + 5 + r) * rowbytes + win0 + u * 16;
-      off = off < 0 ? 0 : (off > g.xbytes - 16 ? g.xbytes - 16 : off);   // (bytes outside the buffer only ever reach pixels that do not exist)
+      off = off < 0 ? 0 : (off > g.xbytes - 16 ? g.xbytes - 16 : off);
       if (i < 4 * 34) __builtin_amdgcn_global_load_lds((gptr_t)(x + off), (lptr_t)(dst + k * 1024), 16, 0, 0);
+    }
+    if (edge) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the units above are in the ring
+#pragma unroll 1
+      for (int k = 0; k < 3; ++k) {
+        const int i = k * 64 + lane;
+        const int r = i / 34, u = i - r * 34;
+        const int64_t off = img0 + (int64_t)(4 * p + 5 + r) * rowbytes + win0 + u * 16;
+        const bool straddles = (off < 0 && off > -16) || (off > g.xbytes - 16 && off < g.xbytes);
+        if (i < 4 * 34 && straddles) {
+          int v[4];
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const int64_t at = off + 4 * d;
+            v[d] = (at >= 0 && at < g.xbytes) ? *reinterpret_cast<const int*>(x + at) : 0;
+          }
+          *reinterpret_cast<i32x4*>(dst + i * 16) = i32x4{v[0], v[1], v[2], v[3]};
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
   };
 #ifdef DLMCQ_LAB
@@ -353,6 +380,9 @@ bool stem_pool7_applies(const StemCall& c) {
   return true;
 }
 
+// which instantiation a call this kernel takes runs: XS, uint8 codes re-centred on read (the launch below and the route query read this)
+bool stem_pool7_xs(const StemCall& c) { return c.shift != 0; }
+
 int stem_pool7_launch(const StemCall& c) {
   Pool7Geom g;
   g.N = (int)c.N; g.Hp = (int)c.Hp; g.Wp = (int)c.Wp;
@@ -374,7 +404,7 @@ int stem_pool7_launch(const StemCall& c) {
 #else
 #define P7_LAB_ARG
 #endif
-  auto kernel = c.shift ? conv_stem_pool7_i8_kernel<true> : conv_stem_pool7_i8_kernel<false>;
+  auto kernel = stem_pool7_xs(c) ? conv_stem_pool7_i8_kernel<true> : conv_stem_pool7_i8_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3((uint32_t)((tasks + 3) / 4)), dim3(256), 0, c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift,
                      c.ep P7_LAB_ARG);
   return launch_status();

@@ -325,6 +325,62 @@ def chain_variant_table():
     return [tuple(int(v) for v in rows[6 * i:6 * i + 5]) + (tuple(f for b, f in enumerate(CHAIN_FL) if rows[6 * i + 5] >> b & 1),) for i in range(n)]
 
 
+ROUTE_PW_VARIANT = 0x100000  # DLMCQ_ROUTE_PW_VARIANT: with ROUTE_ONLY, a ROUTE_PW / ROUTE_PWR answer names the instantiation instead (decode_pw_variant); the first-layer entry points answer theirs (decode_stem_variant)
+ROUTE_STEM_VARIANT_TAG, ROUTE_PW_VARIANT_TAG, ROUTE_PWR_VARIANT_TAG = 1 << 21, 1 << 22, 1 << 23
+STEM_KERNELS = ("stem", "pool", "pool7")   # conv_stem_i8_kernel, conv_stem_pool_i8_kernel, conv_stem_pool7_i8_kernel: the kernel field of a first-layer answer
+
+
+def decode_stem_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_PW_VARIANT call of a first-layer entry point -> ("stem", R, ASYM, SWAP, R6, XOFF) of the conv_stem_i8_kernel
+    instantiation, ("pool", R) of the conv_stem_pool_i8_kernel one, ("pool7", XS) of the conv_stem_pool7_i8_kernel one, or None when the answer
+    is none (DLMCQ_OK, a refusal, another entry point's answer)."""
+    if rc < ROUTE_STEM_VARIANT_TAG or rc >> 22 or rc & 0x1fc000 or rc & 0xf80:
+        return None
+    kernel, r, flags = (rc >> 12) & 3, (rc >> 4) & 7, rc & 15
+    if kernel == 0:
+        return ("stem", r, bool(flags & 2), bool(flags & 4), bool(flags & 1), bool(flags & 8)) if 1 <= r <= 7 else None
+    if kernel == 1:
+        return ("pool", r) if 1 <= r <= 7 and not flags else None
+    return ("pool7", bool(flags & 1)) if kernel == 2 and r == 0 and flags < 2 else None
+
+
+def decode_pw_variant(rc):
+    """Answer of a ROUTE_ONLY | ROUTE_PW_VARIANT call of the tiled entry points -> ("pw", input channels, slice width, ASYM, R6) of the
+    conv_pw_i8_kernel instantiation, ("pwr", C, fp32 output, codes, dual form, SWP) of the conv_pwr_i8_kernel one, or None when the answer is
+    neither (a ROUTE_*, another kernel's variant, DLMCQ_OK, a refusal)."""
+    if rc < ROUTE_PW_VARIANT_TAG or rc >> 24:
+        return None
+    if rc & ROUTE_PWR_VARIANT_TAG:
+        if rc & ROUTE_PW_VARIANT_TAG or rc & 0x3fffc0:
+            return None
+        return ("pwr", 256 * ((rc >> 4) & 3), bool(rc & 2), bool(rc & 1), bool(rc & 4), bool(rc & 8))
+    if rc & 0x3fe00c:
+        return None
+    return ("pw", 64 * ((rc >> 8) & 0x1f), 64 * ((rc >> 4) & 0xf), bool(rc & 2), bool(rc & 1))
+
+
+def stem_variant_table():
+    """The first-layer instantiations the library holds, decoded, as its own launchers list them (csrc/conv_stem_i8.hip: STEM_TABLE, STEM_POOL_TABLE,
+    and the two of csrc/conv_stem_pool7_i8.hip)."""
+    fn = experimental("dlmcq_x_stem_variant_table", [ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    n = fn(None, 0)
+    answers = (ctypes.c_int32 * n)()
+    assert fn(answers, n) == n
+    return [decode_stem_variant(int(a)) for a in answers]
+
+
+def pw_variant_tables():
+    """(conv_pw_i8_kernel records, conv_pwr_i8_kernel records), decoded: the instantiations the library holds, as its own launchers list them."""
+    fn = experimental("dlmcq_x_pw_variant_table", [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int])
+    out = []
+    for which in (0, 1):
+        n = fn(which, None, 0)
+        answers = (ctypes.c_int32 * n)()
+        assert fn(which, answers, n) == n
+        out.append([decode_pw_variant(int(a)) for a in answers])
+    return tuple(out)
+
+
 def stream_ptr():
     """The hipStream_t torch is currently launching on (kernels are enqueued there, asynchronously)."""
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -167,6 +167,28 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * Above every other answer; DLMCQ_OK for an empty problem and every refusal are what they are without the bits. */
 #define DLMCQ_ROUTE_CHAIN_VARIANT 0x80000
 #define DLMCQ_ROUTE_CHAIN_VARIANT_TAG (1 << 30)
+/* DLMCQ_ROUTE_PW_VARIANT (as the four bits above: honoured only TOGETHER with DLMCQ_ROUTE_ONLY, alone it is DLMCQ_EINVAL for every entry
+ * point, and every entry point that does not take it refuses it as it refuses any bit it does not know).  Two families take it:
+ *   dlmcq_conv2d_i8_nhwc_fused / _dual (and the other entry points in front of the same dispatch: _asym carries the pointwise kernel's
+ *   asymmetric weights): where the route query would answer DLMCQ_ROUTE_PW or DLMCQ_ROUTE_PWR it answers WHICH instantiation the call
+ *   launches instead - the record the launcher itself picks the kernel from:
+ *     conv_pw_i8_kernel:   DLMCQ_ROUTE_PW_VARIANT_TAG | (input channels / 64 << 8) | (slice width / 64 << 4) | flags
+ *       the nine (input channels, slice width) pairs of csrc/conv_pw_i8.hip; flags: 2 ASYM (per-channel weight offsets), 1 R6 (ReLU6);
+ *     conv_pwr_i8_kernel:  DLMCQ_ROUTE_PWR_VARIANT_TAG | (C / 256 << 4) | flags
+ *       C 256 or 512: the depth of the reduction read row by row; flags: 8 SWP (dual form: the sampled pair is the call's first), 4 DUAL
+ *       (the shortcut is a second, sampled 512-deep reduction), 2 OUTF (the fp32 output is stored), 1 CODES (the consumer's codes are);
+ *     every other answer - the tiled route, a 3x3 route, DLMCQ_OK for an empty problem, a refusal - is what it is without the bit.
+ *   dlmcq_conv2d_i8_stem_fused / _stem_asym / _stem_xoff / _stem_pool_fused (which take no other control bit, DLMCQ_ROUTE_ONLY alone
+ *   included): the call is validated exactly as the real call is, nothing is launched, and the answer is the instantiation:
+ *     DLMCQ_ROUTE_STEM_VARIANT_TAG | (kernel << 12) | (R << 4) | flags
+ *       kernel 0 conv_stem_i8_kernel: R 1 .. 7 filter rows; flags: 8 XOFF (float activation offset), 4 SWAP (codes-only swapped epilogue),
+ *       2 ASYM, 1 R6;  kernel 1 conv_stem_pool_i8_kernel: R 1 .. 7, no flags;  kernel 2 conv_stem_pool7_i8_kernel: R field 0, flags: 1 XS
+ *       (uint8 codes, re-centred on read).
+ * All three tags lie below every other variant tag and above every DLMCQ_ROUTE_*: no answer equals another family's. */
+#define DLMCQ_ROUTE_PW_VARIANT 0x100000
+#define DLMCQ_ROUTE_STEM_VARIANT_TAG (1 << 21)
+#define DLMCQ_ROUTE_PW_VARIANT_TAG (1 << 22)
+#define DLMCQ_ROUTE_PWR_VARIANT_TAG (1 << 23)
 #define DLMCQ_ROUTE_TILED 1   /* conv_i8_mfma_kernel (csrc/conv_i8.hip) */
 #define DLMCQ_ROUTE_HALO3X3 2 /* conv3x3_halo_i8_kernel (csrc/conv3x3_i8.hip) */
 #define DLMCQ_ROUTE_PW 3      /* conv_pw_i8_kernel (csrc/conv_pw_i8.hip) */
