@@ -11,7 +11,8 @@
 //     Output pixel (n, y, x) is "row" q = n FS + y Wp + x of the GEMM, and its tap (r, s) reads frame position
 //     q + r Wp + s: the convolution is a 1-D stencil over the linear frame, nine FIXED shifts of one sequence.
 //     Rows q with x = W or y = H are junk (3.5 % of the rows at 56^2, 6.8 % at 28^2, 12.9 % at 14^2, 23 % at 7^2): they are
-//     multiplied and never stored.
+//     multiplied and never stored - unless the launch takes the DENSE row mapping (below: the template's comment), whose rows are
+//     the real pixels only.
 //   * THE HALO TILE.  A workgroup owns TM consecutive rows q (they may span image rows and images) for BN output
 //     channels.  Per 64-channel chunk of the reduction it stages frame positions [q0, q0 + TM + 2 Wp + 2) x 64 bytes ONCE
 //     in LDS (LDS-DMA, 16 positions per wave-instruction, the source address of a lane decided once per tile; border
@@ -45,8 +46,10 @@ struct HaloGeom {
   int Wp, FS;            // W + 1, (H + 1) (W + 1)
   uint32_t MQ;           // N FS: rows of the linear frame space
   int nblk_n;
-  int hp;                // halo pieces (16 frame positions each) a chunk's tile needs: ceil((TM + 2 Wp + 2) / 16)
+  int hp;                // halo pieces (16 frame positions each) a chunk's tile needs: ceil((TM + 2 Wp + 2) / 16); DENSE: halo_dense_pieces
   FastDiv fsdiv, wpdiv;
+  uint32_t M;            // DENSE: N H W, the real pixels
+  FastDiv wdiv, hwdiv;   // DENSE: pixel index -> its row of the batch (/ W) and its image (/ H W)
 };
 
 // LAB (lab library only; results are garbage except for 0 and 1, only the time means something): 1 = clock stamps into `trace`;
@@ -67,7 +70,13 @@ constexpr int halo_cs(bool s2, int t) { return !s2 ? t % 3 : (halo_tap(true, t) 
 // vector instructions per K step.
 // PLAIN (the launcher has checked epi_plain): the consumer's quantiser is the plain unsigned-byte one - the epilogue on channel pairs with
 // EpiQuant::code4n_plain (conv_epilogue.h; 6.75 instead of ~9 vector instructions per element), the same bytes.
-template <int BN, int TM, int NW, int WC, int HPW, int NHB, int WPE, bool XS, int LAB = 0, bool S2 = false, int HPA = HPW * NW, bool PLAIN = false>
+// DENSE (stride 1): a tile's rows are TM consecutive REAL pixels p = (n H + y) W + x instead of TM consecutive frame positions: no junk row is
+// multiplied, quantised or staged.  Pixel p sits at frame position q(p) = p + p / W + (p / H W) Wp (one skipped position per image row, Wp more
+// per image); the tile stages the span [q(p0), q(p0 + TM - 1) + 2 Wp + 2] and a lane keeps the halo position q(p) - q(p0) of each of its
+// PB rows instead of one shared base - the nine shifts stay constants added to it.  The launcher (halo_dense_pieces) takes the mapping
+// only where the longer span still fits the instantiation's HPA pieces.
+template <int BN, int TM, int NW, int WC, int HPW, int NHB, int WPE, bool XS, int LAB = 0, bool S2 = false, int HPA = HPW * NW, bool PLAIN = false,
+          bool DENSE = false>
 __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
     const int8_t* __restrict__ x, const int8_t* __restrict__ w, const float* __restrict__ bias, const int32_t* __restrict__ wsum,
     const float* __restrict__ s_in, const float* __restrict__ zp_in, const float* __restrict__ s_w, HaloGeom g, int shift, ConvEpi ep,
@@ -103,7 +112,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
   constexpr int OPER = RING + NHB * HALO;
   constexpr int LDS_BYTES = OPER < STAGE ? STAGE : OPER;
   constexpr int PAR_BYTES = 3 * BN * 4;
-  static_assert(PB >= 1 && CB >= 1 && NBW >= 1 && NBW * NW * 1024 == SLAB && HPW <= 8 && BN % 64 == 0 && (S2 ? NHB == 3 : (NHB == 1 || NHB == 2)) && HPA <= HPW * NW, "tile shape");
+  static_assert(PB >= 1 && CB >= 1 && NBW >= 1 && NBW * NW * 1024 == SLAB && HPW <= 8 && BN % 64 == 0 && (S2 ? NHB == 3 : (NHB == 1 || NHB == 2)) && HPA <= HPW * NW && !(DENSE && S2), "tile shape");
   __shared__ __attribute__((aligned(1024))) int8_t lds[LDS_BYTES + PAR_BYTES];
   int8_t* const ring = lds;
   int8_t* const halo = lds + RING;
@@ -114,7 +123,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
   const uint32_t qd = nwg >> 3, rm = nwg & 7u;
   const uint32_t tile = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + slot;
   const int bn = tile % g.nblk_n, bm = tile / g.nblk_n;
-  const uint32_t q0 = (uint32_t)bm * TM;
+  const uint32_t r0 = (uint32_t)bm * TM;     // the tile's first row: a frame position, or (DENSE) a pixel index
+  auto frame_of = [&](uint32_t p) { return p + fdiv(p, g.wdiv) + fdiv(p, g.hwdiv) * (uint32_t)g.Wp; };
+  const uint32_t q0 = DENSE ? frame_of(r0) : r0;     // the first frame position the tile stages
   const int n0 = bn * BN;
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, l31 = lane & 31, hsel = lane >> 5;
@@ -227,6 +238,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
     woff[1] = woff[0] ^ 32;
   }
   const int pbase = wp * PW + l31;             // this lane's pixel row of block 0 (halo position of tap (0, 0))
+  int pden[PB];                                // DENSE: the halo position of this lane's row of every block
+#pragma unroll
+  for (int jp = 0; jp < PB; ++jp) pden[jp] = DENSE ? (int)(frame_of(r0 + (uint32_t)(pbase + jp * 32)) - q0) : 0;
   const int tap_r1 = g.Wp, tap_r2 = 2 * g.Wp;
 
   i32x16 acc[CB][PB];
@@ -245,13 +259,22 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
   i32x4 wfA[CB], pfA[PB], wfB[CB], pfB[PB];
   auto read_frags = [&](auto u_c, auto t_c, auto ks_c, const int8_t* hbuf, i32x4 (&wf)[CB], i32x4 (&pf)[PB]) {
     constexpr int U = decltype(u_c)::value, t = decltype(t_c)::value, ks = decltype(ks_c)::value;
-    const int p0 = pbase + (halo_rs(S2, t) == 0 ? 0 : (halo_rs(S2, t) == 1 ? tap_r1 : tap_r2)) + halo_cs(S2, t);
-    const int pa = (p0 * 64 + ((hsel ^ ((p0 >> 2) & 3)) << 4)) ^ (ks << 5);     // ((p + 32 jp) >> 2) & 3 = (p >> 2) & 3
+    const int sh = (halo_rs(S2, t) == 0 ? 0 : (halo_rs(S2, t) == 1 ? tap_r1 : tap_r2)) + halo_cs(S2, t);
     const int8_t* const sb = ring + U * SLAB;
 #pragma unroll
     for (int jc = 0; jc < CB; ++jc) wf[jc] = *reinterpret_cast<const i32x4*>(sb + woff[ks] + jc * 2048);
+    if constexpr (DENSE) {
 #pragma unroll
-    for (int jp = 0; jp < PB; ++jp) pf[jp] = *reinterpret_cast<const i32x4*>(hbuf + pa + jp * 2048);
+      for (int jp = 0; jp < PB; ++jp) {
+        const int p0 = pden[jp] + sh;
+        pf[jp] = *reinterpret_cast<const i32x4*>(hbuf + ((p0 * 64 + ((hsel ^ ((p0 >> 2) & 3)) << 4)) ^ (ks << 5)));
+      }
+    } else {
+      const int p0 = pbase + sh;
+      const int pa = (p0 * 64 + ((hsel ^ ((p0 >> 2) & 3)) << 4)) ^ (ks << 5);     // ((p + 32 jp) >> 2) & 3 = (p >> 2) & 3
+#pragma unroll
+      for (int jp = 0; jp < PB; ++jp) pf[jp] = *reinterpret_cast<const i32x4*>(hbuf + pa + jp * 2048);
+    }
   };
   auto multiply = [&](const i32x4 (&wf)[CB], i32x4 (&pf)[PB]) {
     if (XS && LAB != 6) {
@@ -364,6 +387,11 @@ __global__ __launch_bounds__(NW * 64, WPE) void conv3x3_halo_i8_kernel(
   const EpiQuant eq(ep, ep.relu != 0);            // code(relu(v)) = max(code(v), code(0))
   int8_t* const stg = lds;
   auto row_addr = [&](int rr, bool& ok) -> uint8_t* {   // tile row -> the pixel's K code bytes (ok = it is a pixel of the batch)
+    if constexpr (DENSE) {                              // every row is a pixel: only the last tile's tail is not
+      const uint32_t p = r0 + (uint32_t)rr;
+      ok = p < g.M;
+      return ep.codes + (int64_t)p * g.K + n0;
+    }
     const uint32_t q = q0 + (uint32_t)rr;
     const uint32_t n = fdiv(q, g.fsdiv);
     const uint32_t rem = q - n * (uint32_t)g.FS;
@@ -470,16 +498,32 @@ struct HaloVariant {
   bool s2;
   int hp, nhb;
   bool xs, plain;
+  bool dense;     // the row mapping: real pixels only (DENSE) or the frame's positions, junk rows included
 };
 
 // halo pieces (16 frame positions each) a chunk's tile needs: stride 1 ceil((TM + 2 Wp + 2) / 16), a stride-2 phase tile ceil((TM + Wp + 2) / 16)
 static int halo_pieces(const ConvCall& c) { return (256 + (c.stride == 2 ? 1 : 2) * ((int)c.Q + 1) + 2 + 15) / 16; }
 
+// ... and under the dense row mapping (stride 1), the worst tile: TM consecutive pixels cross at most ceil((TM - 1) / W) row ends (one skipped
+// position each) and ceil((TM - 1) / (H W)) image ends (Wp more each), so the span is TM + those + 2 Wp + 2 positions wherever the tile starts
+static int64_t halo_dense_pieces(const ConvCall& c) {
+  const int64_t W = c.Q, HW = c.P * c.Q, Wp = W + 1;
+  return (256 + (255 + W - 1) / W + Wp * ((255 + HW - 1) / HW) + 2 * Wp + 2 + 15) / 16;
+}
+
+// The dense mapping is taken where it costs no workgroup per CU: the longer span must fit the 24 pieces of the buffers the frame mapping gets for
+// the same layer.  At 28^2, 14^2, 7^2 it needs 23, 22, 23; at 56^2 28 (the 32-piece buffers: one workgroup per CU less - frame mapping, 3.5 % junk);
+// a stride-2 phase tile would need 21 - 22 pieces at every ResNet size against the 18 that keep two workgroups per CU (frame mapping).
+// `frame_rows` (lab): the frame mapping regardless, for A/B timing in one process.
+static bool halo_dense(const ConvCall& c, int hp, bool frame_rows = false) {
+  return !frame_rows && c.stride == 1 && hp == 24 && halo_dense_pieces(c) <= 24;
+}
+
 // Pure: the record of a call conv3x3_halo_applies took; false = no instantiation holds its tile (applies' width limits keep that from happening).
 //  - stride 1: 24 pieces per buffer (images up to 62 pixels wide: 6 per wave), else 32 (8 per wave, fewer workgroups per CU); two buffers, or ONE for
 //    64-wide tiles over a single chunk (C = 64: nothing to prefetch);
 //  - stride 2: three phase-tile buffers of 18 pieces (Wp <= 30) or 20 (Wp <= 62).
-static bool halo_variant(const ConvCall& c, HaloVariant& v) {
+static bool halo_variant(const ConvCall& c, HaloVariant& v, bool frame_rows = false) {
   const int hp = halo_pieces(c);
   v.bn = c.K % 128 == 0 ? 128 : 64;
   v.s2 = c.stride == 2;
@@ -488,6 +532,7 @@ static bool halo_variant(const ConvCall& c, HaloVariant& v) {
   v.nhb = v.s2 ? 3 : (v.bn == 64 && c.C == 64 ? 1 : 2);
   v.xs = c.shift != 0;
   v.plain = epi_plain(c.ep);
+  v.dense = halo_dense(c, v.hp, frame_rows);
   return true;
 }
 
@@ -501,15 +546,21 @@ static bool halo_variant(const ConvCall& c, HaloVariant& v) {
   X(64, false, 24, 2, 2, XS, PLAIN) X(64, false, 32, 2, 2, XS, PLAIN) X(128, true, 18, 3, 2, XS, PLAIN) X(128, true, 20, 3, 1, XS, PLAIN)   \
   X(64, true, 18, 3, 2, XS, PLAIN) X(64, true, 20, 3, 2, XS, PLAIN)
 
-// include/dlmcq.h: tag | width << 16 | pieces << 8 | buffers << 4 | 4 S2 | 2 XS | 1 PLAIN
-constexpr int halo_variant_answer(int bn, bool s2, int hp, int nhb, bool xs, bool plain) {
-  return DLMCQ_ROUTE_HALO_VARIANT_TAG | (bn << 16) | (hp << 8) | (nhb << 4) | (s2 ? 4 : 0) | (xs ? 2 : 0) | (plain ? 1 : 0);
+// ... and the records of the table above that also exist with the dense row mapping (the stride-1 24-piece ones: halo_dense)
+#define DLMCQ_HALO_DENSE_TABLE(X)                                                                                                          \
+  DLMCQ_HALO_DENSE_TABLE_(X, true, true) DLMCQ_HALO_DENSE_TABLE_(X, true, false) DLMCQ_HALO_DENSE_TABLE_(X, false, true) DLMCQ_HALO_DENSE_TABLE_(X, false, false)
+#define DLMCQ_HALO_DENSE_TABLE_(X, XS, PLAIN) X(128, false, 24, 2, 2, XS, PLAIN) X(64, false, 24, 1, 4, XS, PLAIN) X(64, false, 24, 2, 2, XS, PLAIN)
+
+// include/dlmcq.h: tag | width << 16 | pieces << 8 | buffers << 4 | 4 S2 | 2 XS | 1 PLAIN; `dense` (8) only where the caller asked for the row
+// mapping too (DLMCQ_ROUTE_HALO_ROWS): the answers without that bit are what they were
+constexpr int halo_variant_answer(int bn, bool s2, int hp, int nhb, bool xs, bool plain, bool dense = false) {
+  return DLMCQ_ROUTE_HALO_VARIANT_TAG | (bn << 16) | (hp << 8) | (nhb << 4) | (dense ? 8 : 0) | (s2 ? 4 : 0) | (xs ? 2 : 0) | (plain ? 1 : 0);
 }
 
 int conv3x3_halo_answer(const ConvCall& c) {
   HaloVariant v;
   if (!halo_variant(c, v)) return DLMCQ_EINVAL;      // (what the launch answers)
-  return halo_variant_answer(v.bn, v.s2, v.hp, v.nhb, v.xs, v.plain);
+  return halo_variant_answer(v.bn, v.s2, v.hp, v.nhb, v.xs, v.plain, v.dense && (c.ep.ctl & DLMCQ_ROUTE_HALO_ROWS));
 }
 
 int conv3x3_halo_table(int32_t* answers, int cap) {
@@ -520,16 +571,29 @@ int conv3x3_halo_table(int32_t* answers, int cap) {
   return n;
 }
 
+int conv3x3_halo_dense_table(int32_t* answers, int cap) {
+  int n = 0;
+#define DLMCQ_HALO_LIST(BN, S2, HP, NHB, WPE, XS, PLAIN) if (n < cap && answers) answers[n] = halo_variant_answer(BN, S2, HP, NHB, XS, PLAIN, true); ++n;
+  DLMCQ_HALO_DENSE_TABLE(DLMCQ_HALO_LIST)
+#undef DLMCQ_HALO_LIST
+  return n;
+}
+
 // value -> kernel: the one place the product's positional template list is spelt (four waves of 64 pixels x BN channels; stride 1 requests
 // HP / 4 pieces per wave, stride 2 five per wave of which HP are allocated)
-template <int BN, bool S2, int HP, int NHB, int WPE, bool XS, bool PLAIN>
+template <int BN, bool S2, int HP, int NHB, int WPE, bool XS, bool PLAIN, bool DENSE = false>
 static int halo_go(const ConvCall& c, const HaloGeom& g, int64_t nwg) {
-  hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN, 256, 4, 1, S2 ? 5 : HP / 4, NHB, WPE, XS, 0, S2, HP, PLAIN>), dim3((uint32_t)nwg), dim3(256), 0,
+  hipLaunchKernelGGL((conv3x3_halo_i8_kernel<BN, 256, 4, 1, S2 ? 5 : HP / 4, NHB, WPE, XS, 0, S2, HP, PLAIN, DENSE>), dim3((uint32_t)nwg), dim3(256), 0,
                      c.st, c.x, c.w, c.bias, c.wsum, c.s_in, c.zp_in, c.s_w, g, c.shift, c.ep, static_cast<unsigned long long*>(nullptr));
   return launch_status();
 }
 
 static int halo_variant_launch(const HaloVariant& v, const ConvCall& c, const HaloGeom& g, int64_t nwg) {
+#define DLMCQ_HALO_GO(BN, S2, HP, NHB, WPE, XS, PLAIN) \
+  if (v.dense && v.bn == BN && v.s2 == S2 && v.hp == HP && v.nhb == NHB && v.xs == XS && v.plain == PLAIN) return halo_go<BN, S2, HP, NHB, WPE, XS, PLAIN, true>(c, g, nwg);
+  DLMCQ_HALO_DENSE_TABLE(DLMCQ_HALO_GO)
+#undef DLMCQ_HALO_GO
+  if (v.dense) return DLMCQ_EINVAL;
 #define DLMCQ_HALO_GO(BN, S2, HP, NHB, WPE, XS, PLAIN) \
   if (v.bn == BN && v.s2 == S2 && v.hp == HP && v.nhb == NHB && v.xs == XS && v.plain == PLAIN) return halo_go<BN, S2, HP, NHB, WPE, XS, PLAIN>(c, g, nwg);
   DLMCQ_HALO_TABLE(DLMCQ_HALO_GO)
@@ -540,8 +604,12 @@ static int halo_variant_launch(const HaloVariant& v, const ConvCall& c, const Ha
 int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
   constexpr int TM = 256;
   const int64_t N = c.N, C = c.C, K = c.K;
+  // lab 200 / 201: the product kernel / its stamped build (lab 1) with the frame row mapping where the launch takes the dense one - the two
+  // mappings timed in one process; every other lab variant exists with the frame mapping only
+  const bool frame_rows = lab > 1;
+  if (lab == 200 || lab == 201) lab -= 200;
   HaloVariant hv;
-  if (!halo_variant(c, hv)) return DLMCQ_EINVAL;
+  if (!halo_variant(c, hv, frame_rows)) return DLMCQ_EINVAL;
   const int bn = hv.bn;
   HaloGeom g;
   g.N = (int)N; g.Hin = (int)c.H; g.Win = (int)c.W; g.H = (int)c.P; g.W = (int)c.Q; g.C = (int)C; g.K = (int)K;
@@ -549,10 +617,13 @@ int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
   g.FS = (g.H + 1) * (g.W + 1);
   g.MQ = (uint32_t)(N * g.FS);
   g.nblk_n = (int)(K / bn);
-  g.hp = halo_pieces(c);
+  g.hp = hv.dense ? (int)halo_dense_pieces(c) : halo_pieces(c);
   g.fsdiv = make_fastdiv((uint32_t)g.FS);
   g.wpdiv = make_fastdiv((uint32_t)g.Wp);
-  const int64_t nblk_m = ((int64_t)g.MQ + TM - 1) / TM;
+  g.M = (uint32_t)(N * g.H * g.W);
+  g.wdiv = make_fastdiv((uint32_t)g.W);
+  g.hwdiv = make_fastdiv((uint32_t)(g.H * g.W));
+  const int64_t nblk_m = ((hv.dense ? (int64_t)g.M : (int64_t)g.MQ) + TM - 1) / TM;
   const int64_t nwg = nblk_m * g.nblk_n;
   if (nwg >= (1ll << 31)) return DLMCQ_ERANGE;
 #ifdef DLMCQ_LAB
@@ -572,7 +643,11 @@ int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
     } else if (bn == 128) {
       switch (v) {
 #define DLMCQ_HALO_LAB(V) case V: hipLaunchKernelGGL((conv3x3_halo_i8_kernel<128, TM, 4, 1, 6, 2, 2, true, V>), DLMCQ_HALO_ARGS(4)); break
-        DLMCQ_HALO_LAB(1); DLMCQ_HALO_LAB(2); DLMCQ_HALO_LAB(3); DLMCQ_HALO_LAB(4); DLMCQ_HALO_LAB(6); DLMCQ_HALO_LAB(7); DLMCQ_HALO_LAB(8);
+        case 1:
+          if (hv.dense) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<128, TM, 4, 1, 6, 2, 2, true, 1, false, 24, false, true>), DLMCQ_HALO_ARGS(4));
+          else hipLaunchKernelGGL((conv3x3_halo_i8_kernel<128, TM, 4, 1, 6, 2, 2, true, 1>), DLMCQ_HALO_ARGS(4));
+          break;
+        DLMCQ_HALO_LAB(2); DLMCQ_HALO_LAB(3); DLMCQ_HALO_LAB(4); DLMCQ_HALO_LAB(6); DLMCQ_HALO_LAB(7); DLMCQ_HALO_LAB(8);
         DLMCQ_HALO_LAB(9); DLMCQ_HALO_LAB(10); DLMCQ_HALO_LAB(11);
 #undef DLMCQ_HALO_LAB
         default: return DLMCQ_EINVAL;
@@ -581,7 +656,11 @@ int conv3x3_halo_launch(const ConvCall& c, int lab, void* lab_trace) {
       if (C != 64) return DLMCQ_EINVAL;
       switch (v) {
 #define DLMCQ_HALO_LAB(V) case V: hipLaunchKernelGGL((conv3x3_halo_i8_kernel<64, TM, 4, 1, 6, 1, 4, true, V>), DLMCQ_HALO_ARGS(4)); break
-        DLMCQ_HALO_LAB(1); DLMCQ_HALO_LAB(2); DLMCQ_HALO_LAB(3); DLMCQ_HALO_LAB(4); DLMCQ_HALO_LAB(6); DLMCQ_HALO_LAB(7); DLMCQ_HALO_LAB(8);
+        case 1:
+          if (hv.dense) hipLaunchKernelGGL((conv3x3_halo_i8_kernel<64, TM, 4, 1, 6, 1, 4, true, 1, false, 24, false, true>), DLMCQ_HALO_ARGS(4));
+          else hipLaunchKernelGGL((conv3x3_halo_i8_kernel<64, TM, 4, 1, 6, 1, 4, true, 1>), DLMCQ_HALO_ARGS(4));
+          break;
+        DLMCQ_HALO_LAB(2); DLMCQ_HALO_LAB(3); DLMCQ_HALO_LAB(4); DLMCQ_HALO_LAB(6); DLMCQ_HALO_LAB(7); DLMCQ_HALO_LAB(8);
         DLMCQ_HALO_LAB(12); DLMCQ_HALO_LAB(13);
 #undef DLMCQ_HALO_LAB
         default: return DLMCQ_EINVAL;

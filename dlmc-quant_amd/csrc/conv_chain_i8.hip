@@ -750,7 +750,7 @@ static int chain_launch(const ChainCall& c) {
   if (smp && (M >= (1ll << 31) || o.N * s.H * s.W * s.C >= (1ll << 40))) return DLMCQ_ERANGE;
   if (ep1.relu == DLMCQ_ACT_RELU6 || ep2.relu == DLMCQ_ACT_RELU6) return DLMCQ_EINVAL;     // (ReLU only)
   if (c.q_lo != 0 || c.q_hi != 255) return DLMCQ_EINVAL;   // GEMM 2 reads the codes as uint8 (shift 128)
-  if (ep2.ctl & (DLMCQ_FORCE_TILED | DLMCQ_PIPELINED | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_PW_VARIANT)) return DLMCQ_EINVAL;   // (no other kernel here)
+  if (ep2.ctl & (DLMCQ_FORCE_TILED | DLMCQ_PIPELINED | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_HALO_ROWS | DLMCQ_ROUTE_PW_VARIANT)) return DLMCQ_EINVAL;   // (no other kernel here)
   if (((ep2.ctl & DLMCQ_ROUTE_ONLY) != 0) != c.which) return DLMCQ_EINVAL;   // (one route query: both bits, DLMCQ_ROUTE_CHAIN_VARIANT's; either alone is none)
   const bool w3cm = (c.layout & DLMCQ_W2_CHUNK_MAJOR) != 0, ocm = (c.layout & DLMCQ_FP32_OUT_CHUNK_MAJOR) != 0;
   // (a call without a shortcut tensor or without an output has ONE fp32 tensor: its layout is the call's)

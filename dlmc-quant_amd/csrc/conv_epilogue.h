@@ -84,7 +84,7 @@ __device__ __forceinline__ f32x4 xoff_sub4(const f32x4& v, float o, const f32x4&
 static inline bool epi_set_form(ConvEpi& ep, int32_t q_form, int32_t q_lo, int32_t q_hi) {
   const bool shifted = (q_form & DLMCQ_EMIT_SHIFT128) != 0;
   constexpr int32_t CTL = DLMCQ_FORCE_TILED | DLMCQ_ROUTE_ONLY | DLMCQ_PIPELINED | DLMCQ_FP32_IN_CHUNK_MAJOR | DLMCQ_FP32_OUT_CHUNK_MAJOR |
-                          DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_PW_VARIANT;
+                          DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_PW_VARIANT | DLMCQ_ROUTE_HALO_ROWS;
   ep.ctl = (uint32_t)q_form & CTL;
   ep.q_form = q_form & ~(DLMCQ_EMIT_SHIFT128 | CTL);
   ep.q_xor = shifted ? 0x80808080u : 0u;

@@ -834,7 +834,7 @@ extern "C" int dlmcq_x_conv_variant_table(int32_t* bn, uint32_t* flags, int cap)
 // The 3x3 kernels' tables likewise (absent from include/dlmcq.h): `which` 0 = conv3x3_halo_i8_kernel's, 1 = conv3x3_pipe_i8_kernel's; fills up to
 // `cap` DLMCQ_ROUTE_HALO_VARIANT answers in the table's order and returns how many there are (-1: no such table)
 extern "C" int dlmcq_x_conv3x3_variant_table(int which, int32_t* answers, int cap) {
-  return which == 0 ? conv3x3_halo_table(answers, cap) : which == 1 ? conv3x3_pipe_table(answers, cap) : -1;
+  return which == 0 ? conv3x3_halo_table(answers, cap) : which == 1 ? conv3x3_pipe_table(answers, cap) : which == 0x100 ? conv3x3_halo_dense_table(answers, cap) : -1;      // 0x100: table 0's records that also exist with the dense row mapping (flag 8)
 }
 
 // The weight-resident 1 x 1 kernels' tables likewise: `which` 0 = conv_pw_i8_kernel's, 1 = conv_pwr_i8_kernel's; DLMCQ_ROUTE_PW_VARIANT answers
@@ -874,6 +874,7 @@ static int conv_launch(ConvCall c, const ConvPlan* forced = nullptr, int64_t* mm
   const int64_t N = c.N, H = c.H, W = c.W, C = c.C, K = c.K, R = c.R, S = c.S, P = c.P, Q = c.Q, M = c.M;
   if (mm_count) *mm_count = 0;
   if ((ep.ctl & (DLMCQ_ROUTE_VARIANT | DLMCQ_ROUTE_HALO_VARIANT | DLMCQ_ROUTE_PW_VARIANT)) && !(ep.ctl & DLMCQ_ROUTE_ONLY)) return DLMCQ_EINVAL;    // (questions about the route, never a launch)
+  if ((ep.ctl & DLMCQ_ROUTE_HALO_ROWS) && (ep.ctl & (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_HALO_VARIANT)) != (DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_HALO_VARIANT)) return DLMCQ_EINVAL;
   if (N < 0 || H < 1 || W < 1 || C < 1 || K < 1 || R < 1 || S < 1 || c.stride < 1 || c.pad < 0 || c.dil < 1) return DLMCQ_EINVAL;
   if (C % CV_BK != 0) return DLMCQ_EINVAL;  // the K step is 64 input channels
   if (P < 1 || Q < 1) return DLMCQ_EINVAL;

@@ -241,6 +241,7 @@ bool conv3x3_halo_applies(const ConvCall& c);
 int conv3x3_halo_launch(const ConvCall& c, int lab = 0, void* lab_trace = nullptr);
 int conv3x3_halo_answer(const ConvCall& c);                    // DLMCQ_ROUTE_HALO_VARIANT: which instantiation the launch picks (include/dlmcq.h)
 int conv3x3_halo_table(int32_t* answers, int cap);             // every instantiation the launcher holds, as such answers; returns how many
+int conv3x3_halo_dense_table(int32_t* answers, int cap);       // ... and those of them that also exist with the dense row mapping (flag 8 set)
 
 // conv3x3_pipe_i8.hip: the halo-tile kernel persistent and software-pipelined across tiles (stride 1, 128 / 256 / 512 input channels,
 // plain quantiser); asked only about calls the halo kernel takes

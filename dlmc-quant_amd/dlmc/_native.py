@@ -38,6 +38,8 @@ ROUTE_VARIANT_TAG = 1 << 24
 ROUTE_HALO_VARIANT = 0x20000  # DLMCQ_ROUTE_HALO_VARIANT: with ROUTE_ONLY, a ROUTE_HALO3X3 / ROUTE_HALO3X3_PIPE answer names the instantiation instead (decode_halo_variant)
 ROUTE_HALO_VARIANT_TAG, ROUTE_PIPE_VARIANT_TAG = 1 << 25, 1 << 26
 HV_PLAIN, HV_XS, HV_S2 = 1, 2, 4   # the flags of such an answer (include/dlmcq.h)
+ROUTE_HALO_ROWS = 0x200000  # DLMCQ_ROUTE_HALO_ROWS: with ROUTE_ONLY | ROUTE_HALO_VARIANT, a halo answer also carries HV_DENSE when the launch's rows are real pixels only
+HV_DENSE = 8
 ROUTE_DW_VARIANT = 0x40000  # DLMCQ_ROUTE_DW_VARIANT: with ROUTE_ONLY, a ROUTE_DW / ROUTE_DWM answer of the depthwise entry points names the instantiation instead (decode_dw_variant)
 ROUTE_DW_VARIANT_TAG, ROUTE_DWM_VARIANT_TAG = 1 << 27, 1 << 28
 ROUTE_CHAIN_VARIANT = 0x80000  # DLMCQ_ROUTE_CHAIN_VARIANT: with ROUTE_ONLY, in the chain entry points' last form: which conv_chain_i8_kernel instantiation, tile height and layouts (decode_chain_variant)

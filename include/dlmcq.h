@@ -134,6 +134,11 @@ typedef void* dlmcq_stream_t; /* hipStream_t */
  * passed together, and every other answer - another kernel's route, a tiled variant, DLMCQ_OK for an empty problem, a refusal - is what it
  * is without the bit. */
 #define DLMCQ_ROUTE_HALO_VARIANT 0x20000
+/* DLMCQ_ROUTE_HALO_ROWS (only TOGETHER with DLMCQ_ROUTE_ONLY | DLMCQ_ROUTE_HALO_VARIANT, otherwise DLMCQ_EINVAL): a conv3x3_halo_i8_kernel answer
+ * also names the launch's ROW MAPPING - flag 8 DENSE: a tile's rows are consecutive real pixels (no junk row of the frame is multiplied), which
+ * the launcher takes for stride-1 layers whose longer halo span fits the 24-piece buffers; without the flag the rows are the frame's positions.
+ * Every answer without this bit, and every other answer with it, is what it was. */
+#define DLMCQ_ROUTE_HALO_ROWS 0x200000
 #define DLMCQ_ROUTE_HALO_VARIANT_TAG (1 << 25)
 #define DLMCQ_ROUTE_PIPE_VARIANT_TAG (1 << 26)
 /* DLMCQ_ROUTE_DW_VARIANT (dlmcq_conv2d_dw_i8_nhwc and dlmcq_conv2d_dw_i8_nhwc_xoff; as the two bits above: OR-able only TOGETHER with

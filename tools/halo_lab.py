@@ -20,7 +20,15 @@ from dlmc import _native as N  # noqa: E402
 CASES = {"c1": (64, 56, 64), "c1w": (64, 56, 128), "c2": (128, 28, 128), "c3": (256, 14, 256), "c4": (512, 7, 512)}   # C, H, K
 VARIANTS = {0: "product", 100: "8 waves of 64 x 64", 2: "no weight DMA", 3: "no halo DMA", 4: "no MFMA", 6: "no xor", 7: "no quantiser",
             8: "codes not staged", 9: "2nd slot starts 1/2 tile late", 10: "2nd slot starts 1/4 tile late", 11: "2nd slot starts 1 tile late",
-            12: "slot s of 4 starts s x 8 k clocks late", 13: "slot s of 4 starts s x 4 k clocks late"}
+            12: "slot s of 4 starts s x 8 k clocks late", 13: "slot s of 4 starts s x 4 k clocks late",
+            200: "frame rows (junk incl.)"}      # the product kernel with the frame row mapping where the launch takes the dense one
+
+
+def dense_rows(h, w):
+    """csrc/conv3x3_i8.hip halo_dense (stride 1): the dense row mapping's worst span fits the 24-piece buffers."""
+    need = lambda span: (span + 15) // 16
+    dense = 256 + (255 + w - 1) // w + (w + 1) * ((255 + h * w - 1) // (h * w)) + 2 * (w + 1) + 2
+    return need(256 + 2 * (w + 1) + 2) <= 24 and need(dense) <= 24
 
 
 def main():
@@ -29,6 +37,7 @@ def main():
     ap.add_argument("--cases", default="c2,c3,c4")
     ap.add_argument("--iters", type=int, default=8)
     ap.add_argument("--stamps", action="store_true")
+    ap.add_argument("--ab", action="store_true", help="only the product kernel and its frame-row form (200), with min / median / max")
     ap.add_argument("--generic", action="store_true", help="also time the generic kernel (128-wide, A direct)")
     args = ap.parse_args()
     lab = ctypes.CDLL(os.path.join(ROOT, "dlmc-quant_amd", "libdlmcq_lab.so"))
@@ -61,13 +70,15 @@ def main():
                 adir = 1                       # the generic kernel
             elif v > 0:
                 wps = -100 - v
-                res = N.ptr(trace) if v == 1 else None
+                res = N.ptr(trace) if v in (1, 201) else None
             rc = fn(N.ptr(xs[i]), N.ptr(wq), None, N.ptr(bias), N.ptr(wsum), N.ptr(s_in), N.ptr(zp), N.ptr(s_w), n, h, h, c, k, 3, 3,
                     1, 1, 1, 1, res, 1, N.ptr(cods[i]), N.ptr(q_s), N.ptr(q_z), 0, 255, N.FORM_ZEROPOINT, 0.0, N.stream_ptr(),
                     bn, adir, 0, wps)
             if rc:
                 raise RuntimeError(f"{name} variant {v}: rc {rc}")
-        vs = ([-1] if args.generic else []) + [v for v in VARIANTS if (v < 100 and (v < 9 or (k % 128 == 0 and v < 12) or (v >= 12 and c == 64 and k == 64))) or (v >= 100 and k % 128 == 0)]
+        vs = ([-1] if args.generic else []) + [v for v in VARIANTS if (v == 200 and dense_rows(h, h)) or (v < 100 and (v < 9 or (k % 128 == 0 and v < 12) or (v >= 12 and c == 64 and k == 64))) or (v == 100 and k % 128 == 0)]
+        if args.ab:
+            vs = [v for v in vs if v in (0, 200)]
         times = {v: [] for v in vs}
         for v in vs:
             run(v, 0)
@@ -85,11 +96,14 @@ def main():
         for v in vs:
             t = sorted(times[v])[len(times[v]) // 2]
             label = "generic kernel" if v == -1 else VARIANTS[v]
-            print(f"    {label:20s} {t:7.1f} us   {2 * macs / t / 1e6:6.0f} TOP/s (real pixels)", flush=True)
-        if args.stamps:
+            spread = f"   min {min(times[v]):7.1f} max {max(times[v]):7.1f}" if args.ab else ""
+            print(f"    {label:24s} {t:7.1f} us   {2 * macs / t / 1e6:6.0f} TOP/s (real pixels){spread}", flush=True)
+        for sv in ([1, 201] if dense_rows(h, h) else [1]) if args.stamps else []:
             trace.zero_()
-            run(1, 0)
+            run(sv, 0)
             torch.cuda.synchronize()
+            rows = n * h * h if sv == 1 and dense_rows(h, h) else n * (h + 1) * (h + 1)
+            print(f"    -- stamps, {'dense' if rows == n * h * h else 'frame'} rows --")
             tr = trace.cpu()
             st = tr[:64 * 8].view(64, 8)
             nstep = int((st[:, 4] > 0).sum())
@@ -98,8 +112,7 @@ def main():
                 r = st[sidx]
                 nxt = st[sidx + 1][0] if sidx + 1 < nstep else r[4]
                 print(f"      step {sidx:2d}: {int(r[1] - r[0]):6d} {int(r[2] - r[1]):6d} {int(r[3] - r[2]):6d} {int(r[4] - r[3]):6d}   ({int(nxt - r[0]):6d})")
-            fs = (h + 1) * (h + 1)
-            nwg = ((n * fs + 255) // 256) * (k // (128 if k % 128 == 0 else 64))
+            nwg = ((rows + 255) // 256) * (k // (128 if k % 128 == 0 else 64))
             wg = tr[64 * 8:64 * 8 + 6 * nwg].view(nwg, 6)
             pro = (wg[:, 1] - wg[:, 0]).float()
             loop = (wg[:, 2] - wg[:, 1]).float()
