@@ -131,6 +131,28 @@ __global__ __launch_bounds__(256) void conv_gap_i8_kernel(GapArgs a, ConvEpi ep)
   }
 }
 
+// What the launcher decides for a problem of N images, C -> K channels on `cus` compute units, once: the launch reads this record, and
+// dlmcq_x_gap_launch_record (tests) answers it
+struct GapLaunch {
+  int nt;          // 32-channel blocks per wave: slices of 64 nt channels
+  int nslice;      // K / (64 nt)
+  int ngroups;     // workgroups per slice; workgroup `group` owns images group, group + ngroups, ...
+  size_t lds;      // dynamic LDS bytes of a workgroup
+};
+
+static inline GapLaunch gap_launch_record(int64_t N, int C, int K, int cus) {
+  GapLaunch r;
+  // 128-wide slices (one activation fragment feeds two channel blocks) where two workgroups' weights still fit a CU's LDS
+  r.nt = (K % 128 == 0 && gap_lds_bytes(C, 128) <= 78 * 1024) ? 2 : 1;
+  r.nslice = K / (64 * r.nt);
+  int64_t ngroups = (2 * cus + r.nslice - 1) / r.nslice;               // ~2 workgroups per CU; each keeps its weights for N / ngroups images
+  if (ngroups > N) ngroups = N;
+  if (ngroups < 1) ngroups = 1;
+  r.ngroups = (int)ngroups;
+  r.lds = gap_lds_bytes(C, 64 * r.nt);
+  return r;
+}
+
 template <int NT>
 static int gap_go(const GapArgs& a, const ConvEpi& ep, size_t lds, int nwg, hipStream_t st) {
   auto kern = conv_gap_i8_kernel<NT>;
@@ -172,14 +194,17 @@ extern "C" int dlmcq_conv2d_i8_nhwc_gap(const void* x, const int8_t* w, float* p
   a.x = static_cast<const int8_t*>(x); a.w = w; a.s_w = w_scale; a.wsum = wsum; a.bias = bias; a.s_in = in_scale; a.zp_in = in_zero_point;
   a.pooled = pooled;
   a.N = (int)N; a.HW = (int)(H * W); a.C = (int)C; a.K = (int)K; a.shift = x_is_unsigned ? 128 : 0;
-  // 128-wide slices (one activation fragment feeds two channel blocks) where two workgroups' weights still fit a CU's LDS
-  const int nt = (K % 128 == 0 && gap_lds_bytes((int)C, 128) <= 78 * 1024) ? 2 : 1;
-  const int nslice = (int)K / (64 * nt);
-  int ngroups = (2 * device_cus() + nslice - 1) / nslice;              // ~2 workgroups per CU; each keeps its weights for N / ngroups images
-  if (ngroups > a.N) ngroups = a.N;
-  if (ngroups < 1) ngroups = 1;
-  a.ngroups = ngroups;
-  const size_t lds = gap_lds_bytes((int)C, 64 * nt);
+  const GapLaunch r = gap_launch_record(N, (int)C, (int)K, device_cus());
+  a.ngroups = r.ngroups;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return nt == 2 ? gap_go<2>(a, ep, lds, ngroups * nslice, st) : gap_go<1>(a, ep, lds, ngroups * nslice, st);
+  return r.nt == 2 ? gap_go<2>(a, ep, r.lds, r.ngroups * r.nslice, st) : gap_go<1>(a, ep, r.lds, r.ngroups * r.nslice, st);
+}
+
+// Tests only (not in include/dlmcq.h): the launch record of dlmcq_conv2d_i8_nhwc_gap for N images and C -> K channels on the CU count the
+// launcher uses - answer = {slice width, nslice, ngroups, dynamic LDS bytes}.  DLMCQ_EINVAL where the entry point refuses the shape.
+extern "C" int dlmcq_x_gap_launch_record(int64_t N, int64_t C, int64_t K, int64_t* answer4) {
+  if (!answer4 || N < 1 || C < 1 || K < 1 || C % 64 != 0 || C > DLMCQ_GAP_MAX_C || K % 64 != 0 || K >= (1 << 24)) return DLMCQ_EINVAL;
+  const GapLaunch r = gap_launch_record(N, (int)C, (int)K, device_cus());
+  answer4[0] = 64 * r.nt; answer4[1] = r.nslice; answer4[2] = r.ngroups; answer4[3] = (int64_t)r.lds;
+  return DLMCQ_OK;
 }

@@ -383,6 +383,16 @@ def pw_variant_tables():
     return tuple(out)
 
 
+def gap_launch_record(n, c, k):
+    """(slice width, nslice, ngroups, dynamic LDS bytes) of the launch dlmcq_conv2d_i8_nhwc_gap makes for n images and c -> k channels on this
+    process's device (256 CUs without one) - the launcher's own record (csrc/conv_gap_i8.hip: gap_launch_record).  A workgroup owns one
+    slice and the images group, group + ngroups, ...; shapes the entry point refuses raise DlmcqError."""
+    fn = experimental("dlmcq_x_gap_launch_record", [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_int64)])
+    answer = (ctypes.c_int64 * 4)()
+    check(fn(n, c, k, answer))
+    return tuple(int(v) for v in answer)
+
+
 def stream_ptr():
     """The hipStream_t torch is currently launching on (kernels are enqueued there, asynchronously)."""
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
