@@ -157,6 +157,8 @@ SIGNATURES = {
     "dlmcq_gelu_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_layernorm_rows_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_attention_f32": (ctypes.c_int, [_p, _p, _p, _p, _p] + [_i64] * 17 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_patch_rows_f32": (ctypes.c_int, [_p, _p, _p] + [_i64] * 8 + [_p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_tokens_assemble_f32": (ctypes.c_int, [_p, _p, _p, _p] + [_i64] * 6 + [_p]),
     "dlmcq_conv2d_i8_nhwc_gap": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p,
                                                _i32, _i32, _i32, _f32, _p]),
     "dlmcq_fold_bn_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p]),

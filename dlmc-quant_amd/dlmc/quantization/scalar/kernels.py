@@ -2,6 +2,8 @@
 
 Everything here is plumbing: shape bookkeeping, output allocation and the current-stream handle.
 The arithmetic happens in libdlmcq.so; tensors that are not on the GPU are refused (no fallback).
+Two wrappers of pure data movement, patch_rows_quant and assemble_tokens, restate in torch ops the inputs their kernels do not read in
+place (a channels_last image batch, misaligned views): the graph's own ops, the same values.
 """
 import collections
 import ctypes
@@ -15,7 +17,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "patch_rows_quant", "patch_rows_view", "patch_rows_torch", "PATCH_MAX_STRIP", "assemble_tokens", "tokens_view", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1338,6 +1340,100 @@ def layernorm_quant(x, weight, bias, eps, emit=None, want_out=True):
                    lambda: N.check(N.lib.dlmcq_layernorm_rows_f32(N.ptr(x), N.ptr(weight), N.ptr(bias), N.ptr(out), codes, m, c, float(eps),
                                                                   *tail, N.stream_ptr())))
     return out, q[0]
+
+
+PATCH_MAX_STRIP = 65536      # dlmcq_patch_rows_f32: elements of one (image, patch row) strip, whose codes are staged in LDS
+
+
+def patch_rows_torch(img, p):
+    """The patch rows [B, gh * gw, p * p * C] of an image batch (B, C, gh * p, gw * p) in torch ops: the graph's own reshape, permute
+    and reshape ('b c (h p1) (w p2) -> b (h w) (p1 p2 c)')."""
+    b, c, h, w = img.shape
+    gh, gw = h // p, w // p
+    return img.reshape(b, c, gh, p, gw, p).permute(0, 2, 4, 3, 5, 1).reshape(b, gh * gw, p * p * c)
+
+
+def patch_rows_view(img, p):
+    """Whether dlmcq_patch_rows_f32 reads the image batch `img` (B, C, H, W) in place for patches of p x p pixels: an fp32 device
+    tensor, p % 4 == 0, H and W multiples of p, unit stride along a line, every other stride a non-negative multiple of 4 elements,
+    a strip's gw * p * p * C elements within PATCH_MAX_STRIP, 16-byte aligned."""
+    if not (isinstance(p, int) and p >= 4 and p % 4 == 0 and img.dim() == 4 and img.dtype == torch.float32 and img.is_cuda):
+        return False
+    b, c, h, w = img.shape
+    if c < 1 or h < p or w < p or h % p or w % p or w * p * c > PATCH_MAX_STRIP:
+        return False
+    sb, sc, sh, sw = img.stride()
+    return sw == 1 and not any(s < 0 or s % 4 for s in (sb, sc, sh)) and img.data_ptr() % 16 == 0
+
+
+def patch_rows_quant(img, p, emit=None, want_out=True):
+    """The patch rows of a vision transformer, `img.reshape(B, C, gh, p, gw, p).permute(0, 2, 4, 3, 5, 1).reshape(B, gh * gw, p * p * C)`
+    of an image batch (B, C, gh * p, gw * p), by dlmcq_patch_rows_f32: one read of the image, read in place through its strides.
+    Returns `(rows or None, codes or None)`, both [B, gh * gw, p * p * C]: fp32 unless `want_out=False`, and with `emit=EmitCodes(...)`
+    the activation codes of the embedding that reads the rows - K.fake_quant of the rows, bit for bit (plain codes: the reader is a
+    Linear layer; EmitCodes.shift128 is an error).  An input the kernel does not take (patch_rows_view: not fp32, not on the device, a
+    stride along the lines other than 1 - a channels_last batch -, strides or a base that are not aligned, a strip too long for the
+    LDS) takes the torch restatement: patch_rows_torch, then K.fake_quant - the unfused graph's values."""
+    if img.dim() != 4 or not isinstance(p, int) or p < 1 or img.shape[2] % p or img.shape[3] % p:
+        raise ValueError(f"patch_rows_quant: an image batch (B, C, gh * p, gw * p), not {tuple(img.shape)} with p = {p!r}")
+    if not want_out and emit is None:
+        raise ValueError("patch_rows_quant: nothing to produce (want_out=False without emit)")
+    if emit is not None and emit.shift128:
+        raise ValueError("patch_rows_quant: this entry point does not emit shifted codes (EmitCodes.shift128)")
+    img = img.detach()
+    b, c, h, w = img.shape
+    gh, gw = h // p, w // p
+    if not patch_rows_view(img, p):
+        rows = patch_rows_torch(img, p)
+        codes = None
+        if emit is not None:
+            codes = fake_quant(rows.contiguous(), emit.scale, emit.zero_point, emit.lo, emit.hi, emit.form, g=emit.g, codes="i8",
+                               want_y=False)[1]
+        return (rows if want_out else None), codes
+    shape = (b, gh * gw, p * p * c)
+
+    def alloc(dtype):
+        return torch.empty(shape, dtype=dtype, device=img.device)
+    out = alloc(torch.float32) if want_out else None
+    q = _quantiser(emit, alloc, img, False, "patch_rows_quant")
+    codes, *tail = _q_args(q)
+    PROFILE.launch("patch_rows", img.numel() * (4 + 4 * want_out + (emit is not None)),
+                   lambda: N.check(N.lib.dlmcq_patch_rows_f32(N.ptr(img), N.ptr(out), codes, b, c, gh, gw, p, *img.stride()[:3], *tail,
+                                                              N.stream_ptr())))
+    return out, q[0]
+
+
+def tokens_view(e, cls, pos):
+    """Whether dlmcq_tokens_assemble_f32 takes the embedded patches `e` [B, T, C], the class token `cls` [1, 1, C] and the position
+    embedding `pos` [1, T + 1, C]: fp32 device tensors, T >= 1, C % 4 == 0; `e` with unit stride in C, a row stride that is a multiple
+    of 4 elements and rows b * T + i one stride apart (a dense tensor, or a column slice of one), 16-byte aligned."""
+    ts = (e, cls, pos)
+    if not all(isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 and t.is_cuda for t in ts):
+        return False
+    b, t, c = e.shape
+    if t < 1 or c < 4 or c % 4 or tuple(cls.shape) != (1, 1, c) or tuple(pos.shape) != (1, t + 1, c):
+        return False
+    sb, st, sc = e.stride()
+    if sc != 1 or st < c or st % 4 or (b > 1 and sb != t * st) or e.data_ptr() % 16:
+        return False
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in (cls, pos))
+
+
+def assemble_tokens(e, cls, pos):
+    """`torch.cat((cls.expand(B, -1, -1), e), 1) + pos` - a transformer's token tensor [B, T + 1, C] from the embedded patches `e`
+    [B, T, C], the class token `cls` [1, 1, C] and the position embedding `pos` [1, T + 1, C] - by dlmcq_tokens_assemble_f32: one IEEE
+    add per element in one pass, the bits of torch's concatenation and add.  fp32.  Inputs the kernel does not take (tokens_view: not
+    fp32, not on the device, other shapes, C % 4 != 0, rows of `e` that are not one stride apart or not aligned) take that torch
+    expression itself."""
+    if not tokens_view(e, cls, pos):
+        return torch.cat((cls.expand(e.shape[0], -1, -1), e), dim=1) + pos
+    e, cls, pos = e.detach(), cls.detach(), pos.detach()
+    b, t, c = e.shape
+    out = torch.empty((b, t + 1, c), dtype=torch.float32, device=e.device)
+    PROFILE.launch("tokens", 4 * c * (b * t + (t + 1) + 1 + b * (t + 1)),
+                   lambda: N.check(N.lib.dlmcq_tokens_assemble_f32(N.ptr(e), N.ptr(cls), N.ptr(pos), N.ptr(out), b, t, c, e.stride(1),
+                                                                   (t + 1) * c, c, N.stream_ptr())))
+    return out
 
 
 ATTENTION_DIMS = (32, 64)    # dlmcq_attention_f32: the head dimensions the kernel is built for

@@ -1605,6 +1605,215 @@ def _gelu_pass(gm, report, planned, dry_run, dwpw):
     _settle(gm, count)
 
 
+_PatchRows = collections.namedtuple("_PatchRows", "src chain c g1 g2 p emit takers want_out")
+_TokenAssemble = collections.namedtuple("_TokenAssemble", "x cls pos rows c chain")
+
+
+class PatchRowsLayer(_MapCodesLayer):
+    """A vision transformer's patch rows - `img.reshape(-1, C, g1, p, g2, p).permute(0, 2, 4, 3, 5, 1).reshape(-1, g1 * g2, p * p * C)` -
+    straight to the activation codes of the Linear plan layer that embeds them (csrc/patch_rows.hip): the strided copy, the fp32 rows
+    and the consumer's quantise pass as one read of the image.  `decision`: the pass's record (_PatchRows: channels, grid, patch size,
+    the readers' activation quantiser, whether anyone reads the fp32 rows).  An input that at run time is no (B, C, g1 * p, g2 * p)
+    batch takes the graph's own three ops and K.fake_quant; one of that shape which the kernel does not read in place (not fp32, not on
+    the device, channels_last, misaligned) takes K.patch_rows_quant's torch restatement: the unfused graph's values either way.
+    Returns `(fp32 or None, codes)`."""
+
+    def __init__(self, decision):
+        d = decision
+        k = d.p * d.p * d.c
+        super().__init__(d.emit, d.want_out, k, k, 0, False)
+        self.channels, self.grid, self.patch, self.tokens = int(d.c), (int(d.g1), int(d.g2)), int(d.p), int(d.g1 * d.g2)
+        self.decision = d._replace(src=d.src.name, chain=tuple(n.name for n in d.chain), takers=tuple(n.name for n in d.takers))
+
+    def forward(self, img):
+        (g1, g2), p, c = self.grid, self.patch, self.channels
+        if img.dim() != 4 or tuple(img.shape[1:]) != (c, g1 * p, g2 * p):
+            return self._torch_rows(img.reshape(-1, c, g1, p, g2, p).permute(0, 2, 4, 3, 5, 1).reshape(-1, g1 * g2, p * p * c))
+        return K.patch_rows_quant(img, p, emit=self.emit.emit(img.numel()), want_out=self.want_out)
+
+
+class _DryPatchRowsLayer(PatchRowsLayer):
+    """fuse_inference(dry_run=...): a PatchRowsLayer's decision.  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+class TokenAssembleLayer(nn.Module):
+    """`torch.cat((cls.expand(B, -1, -1), x), dim=1) + pos` - the class token in front of the embedded patches, the position embedding
+    added - as one launch (csrc/tokens.hip): fp32 [B, T + 1, C], the bits of the two torch ops.  The node is called with the graph's
+    own `cls` and `pos` parameters, which are therefore read at every call; `decision`: the pass's record (_TokenAssemble; `rows`: the
+    static n of a `pos[:, :n]` slice, or None; `c`: the width).  Inputs the kernel does not take run the torch expression itself
+    (K.assemble_tokens)."""
+
+    def __init__(self, decision):
+        super().__init__()
+        d = decision
+        self.rows, self.c = (None if d.rows is None else int(d.rows)), int(d.c)
+        self.decision = d._replace(x=d.x.name, cls=d.cls.name, pos=d.pos.name, chain=tuple(n.name for n in d.chain))
+
+    def forward(self, x, cls, pos):
+        return K.assemble_tokens(x, cls, pos if self.rows is None else pos[:, :self.rows])
+
+
+class _DryTokenAssembleLayer(TokenAssembleLayer):
+    """fuse_inference(dry_run=...): a TokenAssembleLayer's decision.  It cannot be run."""
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+def _static_sizes(node, methods):
+    """The sizes of `node` = x.reshape(...) / x.view(...) / x.permute(...) (one of `methods`; spelled one by one or as one tuple) if
+    every one of them is a Python int, else None."""
+    if not isinstance(node, fx.Node) or node.op != "call_method" or node.target not in methods or node.kwargs or len(node.args) < 2:
+        return None
+    sizes = node.args[1:]
+    if len(sizes) == 1 and isinstance(sizes[0], (tuple, list)):
+        sizes = tuple(sizes[0])
+    return tuple(sizes) if all(isinstance(s, int) and not isinstance(s, bool) for s in sizes) and isinstance(node.args[0], fx.Node) else None
+
+
+def _patch_rows_of(planned, last):
+    """What `last` is to the patch-embedding pass: None (no candidate: not a reshape to three sizes of a six-axis permute of a reshape
+    to six sizes), a str (a candidate left alone: why), or the _PatchRows decision."""
+    s3 = _static_sizes(last, ("reshape", "view"))
+    perm = last.args[0] if s3 is not None else None
+    order = _static_sizes(perm, ("permute",))
+    first = perm.args[0] if order is not None else None
+    s6 = _static_sizes(first, ("reshape", "view"))
+    if s3 is None or order is None or s6 is None or len(s3) != 3 or len(order) != 6 or len(s6) != 6:
+        return None
+    if order != (0, 2, 4, 3, 5, 1):
+        return f"a permute {order}, not (0, 2, 4, 3, 5, 1)"
+    if not (_one_user(first) and _one_user(perm)):
+        return "an intermediate of the rearrangement has a second reader"
+    lead, c, g1, p, g2, p2 = s6
+    if lead != -1 or s3[0] != -1 or min(c, g1, p, g2) < 1 or p != p2 or s3[1:] != (g1 * g2, p * p * c):
+        return f"sizes {s6} -> {s3} are not (-1, C, g1, p, g2, p) -> (-1, g1 * g2, p * p * C)"
+    if p % 4:
+        return f"patch size {p} is no multiple of 4"
+    if g2 * p * p * c > K.PATCH_MAX_STRIP:
+        return f"a strip of {g2 * p * p * c} elements does not fit the kernel's LDS"
+    taken = _code_readers(planned, last, linear=True)
+    if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):
+        return "no Linear plan layer (or no single quantiser) takes the rows as codes"
+    if taken.c != p * p * c:
+        return f"the Linear behind the rows has {taken.c} in-features, the rows {p * p * c}"
+    return _PatchRows(first.args[0], (last, perm, first), c, g1, g2, p, taken.emit, tuple(taken.takers), taken.want_out)
+
+
+def _fetch_attr(gm, node):
+    """The tensor behind get_attr node `node`, else None."""
+    if not isinstance(node, fx.Node) or node.op != "get_attr":
+        return None
+    obj = gm
+    for part in str(node.target).split("."):
+        obj = getattr(obj, part, None)
+    return obj if isinstance(obj, torch.Tensor) else None
+
+
+def _static_tokens(gm, planned, x):
+    """T where the graph says how many rows per image `x` [B, T, C] has - `x` is the fp32 output of a Linear plan layer (or that
+    layer's wrapper) fed by a PatchRowsLayer node or by a reshape / view to three static sizes - else None (checked at run time)."""
+    if x.op == "call_function" and x.target is operator.getitem and x.args[0] in planned:
+        x = x.args[0]
+    if x.op != "call_module" or len(x.args) != 1 or not isinstance(x.args[0], fx.Node):
+        return None
+    src = x.args[0]
+    if src.op == "call_function" and src.target is operator.getitem and src.args[0].op == "call_module":
+        m = dict(gm.named_modules()).get(src.args[0].target)
+        return m.tokens if isinstance(m, PatchRowsLayer) else None
+    s3 = _static_sizes(src, ("reshape", "view"))
+    return s3[1] if s3 is not None and len(s3) == 3 and s3[1] > 0 else None
+
+
+def _token_assemble_of(gm, planned, add):
+    """What `add` is to the patch-embedding pass: None (no candidate: not an add of a torch.cat whose first part is an expanded
+    parameter), a str (a candidate left alone: why), or the _TokenAssemble decision."""
+    if not _is_add(add):
+        return None
+    for cat, pos in (add.args, add.args[::-1]):
+        if cat.op == "call_function" and cat.target in (torch.cat, torch.concat, torch.concatenate) and cat.args:
+            break
+    else:
+        return None
+    parts = cat.args[0]
+    given = dict(zip(("dim",), cat.args[1:]), **cat.kwargs)
+    if not (isinstance(parts, (tuple, list)) and len(parts) == 2 and all(isinstance(t, fx.Node) for t in parts)) or len(cat.args) > 2:
+        return None
+    expand, x = parts
+    if not _is_call(expand, (), "expand") or _fetch_attr(gm, expand.args[0]) is None:
+        return None
+    if set(given) != {"dim"} or given["dim"] != 1 or isinstance(given["dim"], bool):
+        return "the concatenation is not along dim 1"
+    sizes = expand.args[1:]
+    if len(sizes) == 1 and isinstance(sizes[0], (tuple, list)):
+        sizes = tuple(sizes[0])
+    if len(sizes) != 3 or tuple(sizes[1:]) != (-1, -1):
+        return "the class token is not expanded along the batch alone"
+    if not (_one_user(expand) and _one_user(cat)):
+        return "an intermediate (the expanded class token, the concatenation) has a second reader"
+    if _inplace_add(add) and add.args[0] is not cat:
+        return "an in-place add into the position embedding"
+    rows, sliced = None, pos
+    if pos.op == "call_function" and pos.target is operator.getitem and len(pos.args) == 2:      # pos[:, :n], n a Python int
+        idx = pos.args[1]
+        ok = (isinstance(idx, tuple) and len(idx) == 2 and all(isinstance(s, slice) for s in idx) and idx[0] == slice(None) and
+              idx[1].start is None and idx[1].step is None and isinstance(idx[1].stop, int) and not isinstance(idx[1].stop, bool))
+        if not ok or not _one_user(pos):
+            return "the position embedding is sliced in another way than [:, :n] with a static n"
+        rows, pos = idx[1].stop, pos.args[0]
+    cls_t, pos_t = _fetch_attr(gm, expand.args[0]), _fetch_attr(gm, pos)
+    if pos_t is None:
+        return "the position embedding is not a parameter of the model"
+    if cls_t.dim() != 3 or tuple(cls_t.shape[:2]) != (1, 1) or cls_t.shape[2] % 4 or cls_t.shape[2] < 4:
+        return f"a class token of shape {tuple(cls_t.shape)}, not [1, 1, C] with C % 4 == 0"
+    c = int(cls_t.shape[2])
+    if pos_t.dim() != 3 or pos_t.shape[0] != 1 or pos_t.shape[2] != c or (rows is not None and not 2 <= rows <= pos_t.shape[1]):
+        return f"a position embedding of shape {tuple(pos_t.shape)}" + ("" if rows is None else f"[:, :{rows}]") + f", not [1, T + 1, {c}]"
+    length = int(pos_t.shape[1]) if rows is None else rows
+    tokens = _static_tokens(gm, planned, x)
+    if length < 2 or (tokens is not None and tokens + 1 != length):
+        return f"a position embedding of {length} rows for {'?' if tokens is None else tokens} + 1 tokens"
+    return _TokenAssemble(x, expand.args[0], pos, rows, c, (add, cat, expand) if rows is None else (add, sliced, cat, expand))
+
+
+def _patch_embed_pass(gm, report, planned, dry_run):
+    """The front of a vision transformer (fuse_inference(patch_embed=True)).  The rearrangement into patch rows in front of a Linear
+    plan layer becomes a node that hands that layer its activation codes from one read of the image (PatchRowsLayer; _patch_rows_of
+    says what is taken), and `cat((cls.expand(B, -1, -1), x), dim=1) + pos` one launch (TokenAssembleLayer; _token_assemble_of).
+    `planned`: plan node -> what the main pass decided for it (_Decision), which stays - only the embedding's input changes, from fp32
+    to codes.  A candidate that is left alone keeps its nodes, and `report.patch_embed_left` says why."""
+    graph = gm.graph
+    rows = tokens = 0
+    for node in list(graph.nodes):
+        d = _patch_rows_of(planned, node)
+        if isinstance(d, str):
+            report.patch_embed_left.append((node.name, d))
+        if not isinstance(d, _PatchRows):
+            continue
+        module = (_DryPatchRowsLayer if dry_run else PatchRowsLayer)(d)
+        _splice_map_node(gm, node, f"_int8_patch_rows_{rows}", module, (d.src,), d.takers, d.chain)
+        rows += 1
+    for node in list(graph.nodes):
+        d = _token_assemble_of(gm, planned, node)
+        if isinstance(d, str):
+            report.patch_embed_left.append((node.name, d))
+        if not isinstance(d, _TokenAssemble):
+            continue
+        name = f"_int8_tokens_{tokens}"
+        gm.add_module(name, (_DryTokenAssembleLayer if dry_run else TokenAssembleLayer)(d))
+        with graph.inserting_after(node):
+            call = graph.call_module(name, args=(d.x, d.cls, d.pos))
+        node.replace_all_uses_with(call)
+        for n in d.chain:
+            graph.erase_node(n)
+        tokens += 1
+    report.patch_rows, report.token_assemblies = rows, tokens
+    _settle(gm, rows + tokens)
+
+
 def _pool_dims(node, modules):
     """Rank of the result (4: keeps [N, C, 1, 1]; 2: [N, C]) if `node` is a global average pool in a spelling the plan folds -
     nn.AdaptiveAvgPool2d(1 | (1, 1)), F.adaptive_avg_pool2d(x, 1 | (1, 1)), x.mean((2, 3)) / torch.mean(x, (2, 3)) / [2, 3] / dim=,
@@ -1835,6 +2044,9 @@ class FusionReport:
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
         self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
+        self.patch_rows = 0   # patch rearrangements handing the embedding its codes from one read of the image (fuse_inference(patch_embed=True))
+        self.token_assemblies = 0   # class-token concatenations + position embeddings running as one launch (fuse_inference(patch_embed=True))
+        self.patch_embed_left = []  # (graph node, why): candidates of the patch-embedding pass that were left as they are
         self.gap_heads = []   # (plan node, "fused" | "separate"): global-average-pool heads handing the classifier its codes (gap_head=...)
         self.skipped = []
 
@@ -1868,6 +2080,9 @@ class FusionReport:
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
                 (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
+                (f"patch rows on the plan={self.patch_rows}, " if self.patch_rows else "") +
+                (f"token assemblies on the plan={self.token_assemblies}, " if self.token_assemblies else "") +
+                (f"patch embedding left alone={self.patch_embed_left}, " if self.patch_embed_left else "") +
                 (f"5x5 depthwise on the dot-product kernel={self.dw5}, " if self.dw5 else "") +
                 f"not eligible={self.skipped})")
 
@@ -2410,7 +2625,8 @@ class _MainPass:
 
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
-                   recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False):
+                   recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False,
+                   patch_embed=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2566,7 +2782,23 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     a softmax over another axis, scores with a second reader, a head dimension spelled as an int other than 32 or 64.  At run time,
     anything that is not three fp32 device views the kernel reads in place (unit stride in D, strides multiples of 4 elements, 16-byte
     aligned, D 32 or 64), or a reshape that turns out not to merge the heads, takes the node's torch restatement: the graph's own ops.
-    Runs after the LayerNorm and GELU passes.  Off by default: the plan without it is the plan as it was."""
+    Runs after the LayerNorm and GELU passes.  Off by default: the plan without it is the plan as it was.
+    `patch_embed=True`: what stands in front of a vision transformer's first block (`workloads.vit_small()`).  The
+    rearrangement `reshape | view(-1, C, g1, p, g2, p) -> permute(0, 2, 4, 3, 5, 1) -> reshape | view(-1, g1 * g2, p * p * C)` - every
+    size a Python int, each node read by the next alone, p % 4 == 0, a strip of g2 * p * p * C elements within 65536 - read by Linear
+    plan layers of p * p * C in-features sharing one quantiser becomes a PatchRowsLayer node (csrc/patch_rows.hip): one read of the
+    image hands the embedding its activation codes, and anyone else the fp32 rows (`fusion_report.patch_rows`).  The main pass's
+    decision for the embedding stays - only its input changes, from fp32 to codes.  `cat((cls.expand(B, -1, -1), x), dim=1) + pos` -
+    cls [1, 1, C] and pos [1, T + 1, C] parameters of the model, C % 4 == 0, x any fp32 value, each intermediate read once; the add in
+    either operand order or in place (`x += pos`), pos whole or as `pos[:, :n]` with a Python int n - becomes a TokenAssembleLayer node
+    (csrc/tokens.hip): one add per element in one launch (`fusion_report.token_assemblies`); the parameters are read at every call.
+    Left alone, with the reason in `fusion_report.patch_embed_left`: another permute, a second reader of an intermediate, a Linear of
+    other in-features, p % 4 != 0, a position embedding whose length is not the token count the graph states, a slice bound read from
+    a tensor (the reference's `pos[:, :(n + 1)]` with n from x.shape).  Both nodes are bit-identical to the ops they replace - no
+    arithmetic but the quantiser's in the first, one IEEE add in the second (tests/test_gpu_patch_rows.py, tests/test_gpu_tokens.py) -
+    so the plan's logits are torch.equal to the plan's without the flag (tests/test_gpu_patch_embed_plan.py).  At run time an input the
+    kernels do not take (not fp32, a channels_last image batch, misaligned) runs the same torch ops inside the node.  Runs after the
+    main pass and before the LayerNorm pass.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -2591,6 +2823,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _gate_pass(gm, report, planned, dry_run, relu6)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
         _avgpool_pass(gm, report, planned, dry_run)
+    if patch_embed:     # (after the main pass, whose decision for the embedding stays; before the LayerNorm pass, which reads the token tensor)
+        _patch_embed_pass(gm, report, planned, dry_run)
     if layer_norms:     # (after the main pass, whose decisions for the Linear layers stay; before the head pass, like the average pools)
         _layernorm_pass(gm, report, planned, dry_run)
     if gelu:

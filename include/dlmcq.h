@@ -1063,6 +1063,42 @@ int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* o
                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                         dlmcq_stream_t stream);
 
+/* ---- A vision transformer's patch rows: an fp32 image batch to fp32 rows and / or the activation codes of the embedding ----
+ * The rearrangement 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' of an image batch [B, C, gh p, gw p] into rows [B gh gw, p p C]:
+ *     row (b gh + gy) gw + gx, column (py p + px) C + c  =  img[b sb + c sc + (gy p + py) sh + gx p + px]
+ *     out = that value;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_gelu_nhwc_f32) of it - the code dlmcq_fake_quant_f32
+ *                        gives for it (NaN, infinities, -0 as there).  The shifted emission is NOT accepted: the reader is a Linear
+ *                        layer, which takes plain codes.
+ * No arithmetic but the quantiser's: every element is read once, moved and, for the codes, quantised once.  One workgroup per (b, gy)
+ * strip, whose codes - gw p p C consecutive bytes of the output - are staged in LDS (csrc/patch_rows.hip).  No atomics, no scratch:
+ * a row's result depends neither on B nor on the launch.
+ *   img      fp32 view [B, C, gh p, gw p]: element strides sb, sc, sh (batch, channel, image line), unit stride along a line,
+ *            16-byte aligned
+ *   out      fp32 [B gh gw, p p C] dense, 16-byte aligned, or NULL
+ *   codes    bytes [B gh gw, p p C] dense, 16-byte aligned, or NULL (needs q_scale)
+ * DLMCQ_EINVAL: B < 0, C, gh or gw < 1, p < 4 or p % 4, a stride negative or no multiple of 4, a strip of more than 65536 elements
+ * (gw p p C: the LDS a launch may ask for), img NULL, both outputs NULL, an invalid quantiser, any control or layout bit or
+ * DLMCQ_EMIT_SHIFT128 in q_form (refused, not stripped).  DLMCQ_EALIGN: img / out / codes not 16-byte aligned.  DLMCQ_ERANGE: B, gh,
+ * B gh, B gh gw or gh p reaches 2^31.  B == 0: DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+int dlmcq_patch_rows_f32(const float* img, float* out, void* codes, int64_t B, int64_t C, int64_t gh, int64_t gw, int64_t p, int64_t sb,
+                         int64_t sc, int64_t sh, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                         int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
+/* ---- A transformer's token tensor: the class token in front of the embedded patches, the position embedding added ----
+ *     out[b, 0, :]     = fl32(cls[:] + pos[0, :])
+ *     out[b, 1 + i, :] = fl32(e[b, i, :] + pos[1 + i, :])      i = 0 .. T - 1
+ * - one IEEE add per element: the bits of `torch.cat((cls.expand(B, -1, -1), e), 1) + pos` in either operand order.  fp32 only (the
+ * readers are the residual stream and a LayerNorm node).  No LDS, no atomics, no scratch (csrc/tokens.hip).
+ *   e        fp32 rows [B T, C], row b T + i e_stride floats after the first, 16-byte aligned
+ *   cls      fp32 [C], 16-byte aligned
+ *   pos      fp32 [T + 1, C] dense, 16-byte aligned
+ *   out      fp32 [B, T + 1, C]: element strides o_sb (image) and o_st (token), 16-byte aligned
+ * DLMCQ_EINVAL: B < 0, T < 1, C < 4, C % 4, e_stride or o_st below C or no multiple of 4, o_sb no multiple of 4 or below
+ * T o_st + C (two images' rows would meet), a NULL pointer.  DLMCQ_EALIGN: a pointer not 16-byte aligned.  DLMCQ_ERANGE: B, T + 1, C,
+ * a row stride, B (T + 1) or B (T + 1) C / 4 reaches 2^31.  B == 0: DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+int dlmcq_tokens_assemble_f32(const float* e, const float* cls, const float* pos, float* out, int64_t B, int64_t T, int64_t C,
+                              int64_t e_stride, int64_t o_sb, int64_t o_st, dlmcq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
