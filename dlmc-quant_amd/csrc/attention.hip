@@ -177,8 +177,8 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
 
 using namespace dlmcq;
 
-// The checks, in map_codes_call's order (csrc/map_codes.h): geometry (sizes, D, strides, scale), the seven quantiser arguments (every
-// control bit and the shifted emission refused: the reader is a Linear layer), an empty problem, null pointers, alignment, the 2^31 limits.
+// The checks: geometry (sizes, D, strides, scale), emit_set_quantiser (csrc/conv_gap.h; plain codes only: the reader is a Linear
+// layer), an empty problem, emit_check_pointers, the 2^31 limits.
 extern "C" int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
                                    int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
                                    int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
@@ -191,12 +191,11 @@ extern "C" int dlmcq_attention_f32(const float* q, const float* k, const float* 
     if (strides[i] < 0 || strides[i] % 4 != 0) return DLMCQ_EINVAL;
   if (q_st < D || k_st < D || v_st < D || o_st < D) return DLMCQ_EINVAL;      // (unit stride in D: a token's row does not overlap the next)
   ConvEpi ep{};
-  const int rc = gap_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
   if (rc != DLMCQ_OK) return rc;
-  if (ep.ctl || ep.q_xor) return DLMCQ_EINVAL;
   if (B == 0 || H == 0 || Tq == 0) return DLMCQ_OK;
-  if (!(out || codes) || !q || !k || !v) return DLMCQ_EINVAL;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(out) || !aligned4(codes)) return DLMCQ_EALIGN;      // (NULL is aligned)
+  rc = emit_check_pointers({q, k, v}, {}, out, codes, 4);
+  if (rc != DLMCQ_OK) return rc;
   constexpr int64_t LIM = 1ll << 31;
   const int64_t tiles = (Tq + DLMCQ_AT_ROWS - 1) / DLMCQ_AT_ROWS;
   if (B >= LIM || H >= LIM || Tq >= LIM || Tk >= LIM || B * H >= LIM || B * H * tiles >= LIM) return DLMCQ_ERANGE;

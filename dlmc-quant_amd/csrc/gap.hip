@@ -34,12 +34,11 @@ extern "C" int dlmcq_gap_nhwc_f32(const float* x, float* pooled, void* codes, in
                                   dlmcq_stream_t stream) {
   if (N < 0 || HW < 1 || C < 4 || C % 4 != 0) return DLMCQ_EINVAL;
   ConvEpi ep{};
-  const int rc = gap_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, false);
   if (rc != DLMCQ_OK) return rc;
-  if (ep.ctl) return DLMCQ_EINVAL;           // (row-major NHWC only: a chunk-major input, a route query or any other control bit is refused)
   if (N == 0) return DLMCQ_OK;
-  if (!x || !(pooled || codes)) return DLMCQ_EINVAL;
-  if (!aligned16(x) || (pooled && !aligned16(pooled)) || (codes && !aligned4(codes))) return DLMCQ_EALIGN;
+  rc = emit_check_pointers({x}, {}, pooled, codes, 4);
+  if (rc != DLMCQ_OK) return rc;
   if (N * (C / 4) >= (1ll << 31) || HW >= (1ll << 31)) return DLMCQ_ERANGE;
   const int64_t threads = N * (C / 4);
   hipLaunchKernelGGL(gap_nhwc_kernel, dim3((uint32_t)((threads + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK)), dim3(DLMCQ_BLOCK), 0,

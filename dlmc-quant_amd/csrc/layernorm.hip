@@ -118,19 +118,17 @@ static inline void layernorm_launch(const float* x, const float* gamma, const fl
 
 using namespace dlmcq;
 
-// The checks, in map_codes_call's order (csrc/map_codes.h): geometry and eps, the seven quantiser arguments (every control bit and the
-// shifted emission refused: the readers are Linear layers, which take plain codes), M == 0, null pointers, alignment, the 2^31 limits.
+// The checks: geometry and eps, emit_set_quantiser (csrc/conv_gap.h; plain codes only), M == 0, emit_check_pointers, the 2^31 limits.
 extern "C" int dlmcq_layernorm_rows_f32(const float* x, const float* gamma, const float* beta, float* out, void* codes, int64_t M, int64_t C,
                                         float eps, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                                         int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
   if (M < 0 || C < 4 || C % 4 != 0 || C > DLMCQ_LN_MAX_C || !(eps > 0.0f) || !(eps <= 3.402823466e+38f)) return DLMCQ_EINVAL;
   ConvEpi ep{};
-  const int rc = gap_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
   if (rc != DLMCQ_OK) return rc;
-  if (ep.ctl || ep.q_xor) return DLMCQ_EINVAL;
   if (M == 0) return DLMCQ_OK;
-  if (!(out || codes) || !x) return DLMCQ_EINVAL;
-  if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(out) || !aligned4(codes)) return DLMCQ_EALIGN;      // (NULL is aligned)
+  rc = emit_check_pointers({x}, {gamma, beta}, out, codes, 4);
+  if (rc != DLMCQ_OK) return rc;
   constexpr int64_t LIM = 1ll << 31;
   if (M >= LIM || M * (C / 4) >= LIM) return DLMCQ_ERANGE;
   const int m = (int)M, c4 = (int)(C / 4);

@@ -42,8 +42,8 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void map_codes_kernel(const float* __r
 }
 
 // Everything the entry points share, in the order that decides which code an argument set with two faults gets (the op's own EINVAL
-// checks come before the call): geometry, the seven quantiser arguments -> ep (every control / layout bit refused, not stripped: row-major
-// NHWC only), N == 0, null pointers, alignment, the 2^31 limits (thread and pixel indices are 32-bit; element offsets are 64-bit).
+// checks come before the call): geometry, the seven quantiser arguments -> ep (emit_set_quantiser, conv_gap.h), N == 0, null pointers
+// and alignment (emit_check_pointers), the 2^31 limits (thread and pixel indices are 32-bit; element offsets are 64-bit).
 // `in`: the fp32 inputs, the map first; H x W: the input map; P x Q: the output.  DLMCQ_OK with g.total == 0: nothing to launch.
 static inline int map_codes_call(MapRows& g, ConvEpi& ep, std::initializer_list<const void*> in, const float* out, void* codes, int64_t N,
                                  int64_t H, int64_t W, int64_t P, int64_t Q, int64_t C, int64_t x_stride, int64_t c_pad, int32_t pad_code,
@@ -52,17 +52,12 @@ static inline int map_codes_call(MapRows& g, ConvEpi& ep, std::initializer_list<
   g = MapRows{};
   if (N < 0 || H < 1 || W < 1 || C < 4 || C % 4 != 0) return DLMCQ_EINVAL;
   if (x_stride < C || x_stride % 4 != 0 || c_pad < C || c_pad % 4 != 0 || pad_code < -128 || pad_code > 255) return DLMCQ_EINVAL;
-  const int rc = gap_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, false);
   if (rc != DLMCQ_OK) return rc;
-  if (ep.ctl) return DLMCQ_EINVAL;
   if (!codes && c_pad != C) return DLMCQ_EINVAL;
   if (N == 0) return DLMCQ_OK;
-  if (!(out || codes)) return DLMCQ_EINVAL;
-  for (const void* p : in)
-    if (!p) return DLMCQ_EINVAL;
-  for (const void* p : in)
-    if (!aligned16(p)) return DLMCQ_EALIGN;
-  if ((out && !aligned16(out)) || (codes && !aligned4(codes))) return DLMCQ_EALIGN;
+  rc = emit_check_pointers(in, {}, out, codes, 4);
+  if (rc != DLMCQ_OK) return rc;
   constexpr int64_t LIM = 1ll << 31;
   if (H >= LIM || W >= LIM || x_stride >= LIM || c_pad >= LIM || N >= LIM || N * P >= LIM || N * P * Q >= LIM ||
       N * P * Q * (c_pad / 4) >= LIM)

@@ -93,8 +93,8 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void patch_rows_kernel(const float* __
 
 using namespace dlmcq;
 
-// The checks, in map_codes_call's order (csrc/map_codes.h): geometry, the seven quantiser arguments (every control bit and the shifted
-// emission refused: the readers are Linear layers, which take plain codes), B == 0, null pointers, alignment, the 2^31 limits.
+// The checks: geometry, emit_set_quantiser (csrc/conv_gap.h; plain codes only), B == 0, emit_check_pointers (the code rows are written
+// 16 bytes at a time), the 2^31 limits.
 extern "C" int dlmcq_patch_rows_f32(const float* img, float* out, void* codes, int64_t B, int64_t C, int64_t gh, int64_t gw, int64_t p,
                                     int64_t sb, int64_t sc, int64_t sh, const float* q_scale, const float* q_zero_point, int32_t q_lo,
                                     int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
@@ -106,12 +106,11 @@ extern "C" int dlmcq_patch_rows_f32(const float* img, float* out, void* codes, i
   if (C > DLMCQ_PATCH_MAX_STRIP || gw > DLMCQ_PATCH_MAX_STRIP || p > 256 ||gw * (p * p * C) > DLMCQ_PATCH_MAX_STRIP)
     return DLMCQ_EINVAL;
   ConvEpi ep{};
-  const int rc = gap_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
   if (rc != DLMCQ_OK) return rc;
-  if (ep.ctl || ep.q_xor) return DLMCQ_EINVAL;
   if (B == 0) return DLMCQ_OK;
-  if (!(out || codes) || !img) return DLMCQ_EINVAL;
-  if (!aligned16(img) || !aligned16(out) || !aligned16(codes)) return DLMCQ_EALIGN;      // (NULL is aligned)
+  rc = emit_check_pointers({img}, {}, out, codes, 16);
+  if (rc != DLMCQ_OK) return rc;
   if (B >= LIM || gh >= LIM || B * gh >= LIM || B * gh * gw >= LIM || gh * p >= LIM) return DLMCQ_ERANGE;
   const int k = (int)(p * p * C);
   const PatchGeom g{(int)C, (int)p, (int)gh, (int)gw, (int)(gw * p / 4), k, (int)(C * p), sb, sc, sh};

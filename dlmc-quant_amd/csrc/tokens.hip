@@ -34,7 +34,7 @@ __global__ __launch_bounds__(DLMCQ_BLOCK) void tokens_assemble_kernel(const f32x
 
 using namespace dlmcq;
 
-// The checks, in map_codes_call's order (csrc/map_codes.h) without a quantiser: geometry, B == 0, null pointers, alignment, the 2^31 limits.
+// The checks, in the order of csrc/conv_gap.h's helpers (no quantiser, `out` required): geometry, B == 0, null pointers, alignment, 2^31 limits.
 extern "C" int dlmcq_tokens_assemble_f32(const float* e, const float* cls, const float* pos, float* out, int64_t B, int64_t T, int64_t C,
                                          int64_t e_stride, int64_t o_sb, int64_t o_st, dlmcq_stream_t stream) {
   constexpr int64_t LIM = 1ll << 31;

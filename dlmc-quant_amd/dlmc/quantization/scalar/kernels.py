@@ -474,6 +474,23 @@ def _q_args(q, flags=0):
     return N.ptr(codes), N.ptr(q_scale), N.ptr(q_zp), lo, hi, form | flags, g
 
 
+def _emit_launch(name, tag, like, shape_or_alloc, emit, want_out, nbytes, issue, ops=0, shifted=False):
+    """The tail of the wrappers that return `(out or None, codes or None)` of one launch: fp32 `out` unless `want_out=False`, and with
+    `emit=EmitCodes(...)` the consumer's activation codes of the same values, each of `shape_or_alloc` (a shape on `like`'s device, or
+    `alloc(dtype)`); `issue(out, codes, *tail)` calls the entry point with the two pointers and `tail` = _q_args' six quantiser values
+    and the stream, and is recorded as PROFILE launch `tag` of `nbytes` bytes and `ops` operations.  `shifted`: as _quantiser says.
+    (A wrapper with a check of its own behind "nothing to produce" makes that one itself too, where it stands: the order decides what
+    a call with two faults is told.)"""
+    if not want_out and emit is None:
+        raise ValueError(f"{name}: nothing to produce (want_out=False without emit)")
+    alloc = shape_or_alloc if callable(shape_or_alloc) else lambda dtype: torch.empty(tuple(shape_or_alloc), dtype=dtype, device=like.device)
+    out = alloc(torch.float32) if want_out else None
+    q = _quantiser(emit, alloc, like, shifted, name)
+    args = (N.ptr(out), *_q_args(q), N.stream_ptr())
+    PROFILE.launch(tag, nbytes, lambda: N.check(issue(*args)), ops)
+    return out, q[0]
+
+
 def _as_chunk_major(out):
     """A channels_last fp32 (N, K, P, Q) tensor the kernel wrote chunk-major: the same memory, read as [K / 64][M][64]."""
     n, k, p, q = out.shape
@@ -1186,18 +1203,11 @@ def global_avgpool(x, emit=None, want_out=True):
     N.require_gpu(x)
     if x.dim() != 4 or x.dtype != torch.float32:
         raise ValueError("global_avgpool: an fp32 (N, C, H, W) tensor")
-    if not want_out and emit is None:
-        raise ValueError("global_avgpool: nothing to produce (want_out=False without emit)")
     x = _nhwc(x)
     n, c, h, w_ = x.shape
-
-    def alloc(dtype):
-        return torch.empty((n, c), dtype=dtype, device=x.device)
-    out = alloc(torch.float32) if want_out else None
-    q = _quantiser(emit, alloc, x, True, "global_avgpool")
-    PROFILE.launch("gap", x.numel() * 4 + n * c * (4 * want_out + (emit is not None)), lambda: N.check(N.lib.dlmcq_gap_nhwc_f32(
-        N.ptr(x), N.ptr(out), *_q_args(q)[:1], n, h * w_, c, *_q_args(q)[1:], N.stream_ptr())))
-    return (out, q[0]) if emit is not None else out
+    out, codes = _emit_launch("global_avgpool", "gap", x, (n, c), emit, want_out, x.numel() * 4 + n * c * (4 * want_out + (emit is not None)),
+                              lambda op, cp, *tail: N.lib.dlmcq_gap_nhwc_f32(N.ptr(x), op, cp, n, h * w_, c, *tail), shifted=True)
+    return (out, codes) if emit is not None else out
 
 
 def _nhwc_rows(x):
@@ -1235,14 +1245,10 @@ def _map_codes(name, x, p, q_, emit, want_out, c_pad, pad_code, tag, read, issue
     if xs is None:
         x, xs = _nhwc(x), c
 
-    def alloc(dtype, ch=c_pad):
-        return torch.empty((n, ch, p, q_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
-    out = alloc(torch.float32, c) if want_out else None
-    q = _quantiser(emit, alloc, x, True, name)
-    codes, *tail = _q_args(q)
-    PROFILE.launch(tag, read + n * p * q_ * (c * 4 * want_out + c_pad * (emit is not None)), lambda: N.check(issue(
-        N.ptr(x), N.ptr(out), codes, xs, c_pad, int(pad_code), *tail, N.stream_ptr())))
-    return out, q[0]
+    def alloc(dtype):      # (fp32: the map, C channels; else the code rows)
+        return torch.empty((n, c if dtype == torch.float32 else c_pad, p, q_), dtype=dtype, device=x.device, memory_format=torch.channels_last)
+    return _emit_launch(name, tag, x, alloc, emit, want_out, read + n * p * q_ * (c * 4 * want_out + c_pad * (emit is not None)),
+                        lambda op, cp, *tail: issue(N.ptr(x), op, cp, xs, c_pad, int(pad_code), *tail), shifted=True)
 
 
 def avgpool_quant(x, window, emit=None, want_out=True, c_pad=None, pad_code=0):
@@ -1330,16 +1336,9 @@ def layernorm_quant(x, weight, bias, eps, emit=None, want_out=True):
     x = x.detach().reshape(-1, c).contiguous()
     m = x.shape[0]
     weight, bias = _bias_c(weight), _bias_c(bias)
-
-    def alloc(dtype):
-        return torch.empty(shape, dtype=dtype, device=x.device)
-    out = alloc(torch.float32) if want_out else None
-    q = _quantiser(emit, alloc, x, False, "layernorm_quant")
-    codes, *tail = _q_args(q)
-    PROFILE.launch("layernorm", m * c * (4 + 4 * want_out + (emit is not None)) + 4 * c * ((weight is not None) + (bias is not None)),
-                   lambda: N.check(N.lib.dlmcq_layernorm_rows_f32(N.ptr(x), N.ptr(weight), N.ptr(bias), N.ptr(out), codes, m, c, float(eps),
-                                                                  *tail, N.stream_ptr())))
-    return out, q[0]
+    nbytes = m * c * (4 + 4 * want_out + (emit is not None)) + 4 * c * ((weight is not None) + (bias is not None))
+    return _emit_launch("layernorm_quant", "layernorm", x, shape, emit, want_out, nbytes, lambda op, cp, *tail: N.lib.dlmcq_layernorm_rows_f32(
+        N.ptr(x), N.ptr(weight), N.ptr(bias), op, cp, m, c, float(eps), *tail))
 
 
 PATCH_MAX_STRIP = 65536      # dlmcq_patch_rows_f32: elements of one (image, patch row) strip, whose codes are staged in LDS
@@ -1390,17 +1389,9 @@ def patch_rows_quant(img, p, emit=None, want_out=True):
             codes = fake_quant(rows.contiguous(), emit.scale, emit.zero_point, emit.lo, emit.hi, emit.form, g=emit.g, codes="i8",
                                want_y=False)[1]
         return (rows if want_out else None), codes
-    shape = (b, gh * gw, p * p * c)
-
-    def alloc(dtype):
-        return torch.empty(shape, dtype=dtype, device=img.device)
-    out = alloc(torch.float32) if want_out else None
-    q = _quantiser(emit, alloc, img, False, "patch_rows_quant")
-    codes, *tail = _q_args(q)
-    PROFILE.launch("patch_rows", img.numel() * (4 + 4 * want_out + (emit is not None)),
-                   lambda: N.check(N.lib.dlmcq_patch_rows_f32(N.ptr(img), N.ptr(out), codes, b, c, gh, gw, p, *img.stride()[:3], *tail,
-                                                              N.stream_ptr())))
-    return out, q[0]
+    return _emit_launch("patch_rows_quant", "patch_rows", img, (b, gh * gw, p * p * c), emit, want_out,
+                        img.numel() * (4 + 4 * want_out + (emit is not None)), lambda op, cp, *tail: N.lib.dlmcq_patch_rows_f32(
+                            N.ptr(img), op, cp, b, c, gh, gw, p, *img.stride()[:3], *tail))
 
 
 def tokens_view(e, cls, pos):
@@ -1475,17 +1466,10 @@ def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True):
     tk = k.shape[2]
     shape = (b, tq, h * d) if merged else (b, h, tq, d)
     o_strides = (tq * h * d, d, h * d) if merged else (h * tq * d, tq * d, d)
-
-    def alloc(dtype):
-        return torch.empty(shape, dtype=dtype, device=q.device)
-    out = alloc(torch.float32) if want_out else None
-    qz = _quantiser(emit, alloc, q, False, "attention_quant")
-    codes, *tail = _q_args(qz)
-    PROFILE.launch("attention", 4 * b * h * d * (tq + 2 * tk) + b * h * tq * d * (4 * want_out + (emit is not None)),
-                   lambda: N.check(N.lib.dlmcq_attention_f32(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(out), codes, b, h, tq, tk, d,
-                                                             *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o_strides, scale,
-                                                             *tail, N.stream_ptr())), ops=4 * b * h * tq * tk * d)
-    return out, qz[0]
+    nbytes = 4 * b * h * d * (tq + 2 * tk) + b * h * tq * d * (4 * want_out + (emit is not None))
+    return _emit_launch("attention_quant", "attention", q, shape, emit, want_out, nbytes, lambda op, cp, *tail: N.lib.dlmcq_attention_f32(
+        N.ptr(q), N.ptr(k), N.ptr(v), op, cp, b, h, tq, tk, d, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o_strides, scale, *tail),
+        ops=4 * b * h * tq * tk * d)
 
 
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):

@@ -18,6 +18,7 @@ explicit HIP launches of the plan, and the result can be captured with `dlmc.uti
 The plan snapshots weights and scales: re-fuse after changing them.
 """
 import collections
+import functools
 import math
 import os
 import operator
@@ -613,6 +614,11 @@ def _outputs_read(node):
     return gets if len(gets) == len(node.users) else None
 
 
+def _sole_user(node):
+    """The one reader of graph node `node`; None if it has none or several (or is no graph node: a Python scalar argument)."""
+    return next(iter(node.users)) if isinstance(node, fx.Node) and len(node.users) == 1 else None
+
+
 def _call_plan_module(gm, after, name, module, args, outputs=(0, 1)):
     """Add `module` to the plan as `name`, called with `args` behind node `after`.  Returns the call and {i: its `[i]` getitem}, made
     in the order of `outputs`."""
@@ -985,14 +991,62 @@ def _decided(r):
     return dict(emit=r.emit, want_out=r.want_out, c=r.c, c_pad=r.c_pad, pad_code=r.pad_code, shift=r.shift)
 
 
-def _splice_map_node(gm, last, name, module, args, takers, erase):
+def _splice_map_node(gm, last, name, module, args, takers, erase, outputs=2):
     """Put `module` into the plan as `name`, called with `args`, in place of fp32 node `last`: `takers` read its codes (output 1),
-    everyone else its fp32 map (output 0); then `erase` the nodes it replaces, in that order."""
-    _, outs = _call_plan_module(gm, last, name, module, args)
+    everyone else its fp32 map (output 0) - or, with `outputs=1`, the one tensor it returns; then `erase` the nodes it replaces, in
+    that order."""
+    call, outs = _call_plan_module(gm, last, name, module, args, (0, 1) if outputs == 2 else ())
     for u in list(last.users):
-        u.replace_input_with(last, outs[1] if u in takers else outs[0])
+        u.replace_input_with(last, (outs[1] if u in takers else outs[0]) if outs else call)
     for n in erase:
         gm.graph.erase_node(n)
+
+
+class _DryNode(nn.Module):
+    """fuse_inference(dry_run=...): a plan node that holds nothing (a main-pass node, a head, an average pool, a gate).  It cannot be run."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+
+    def forward(self, *args):
+        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+
+
+@functools.lru_cache(maxsize=None)
+def _dry(cls, init=None):
+    """The dry-run stand-in of plan node class `cls`: the subclass `_Dry<cls>` that is built like it (or by `init`), carries the same
+    decision in the same attributes and cannot be run.  (An average pool's and a gate's stand-in is the attribute-less _DryNode: the
+    recorded plans of tests/golden/plans/ print them so.)"""
+    if cls in (AvgPoolLayer, GateLayer):
+        return _DryNode
+    body = dict(forward=_DryNode.forward, __doc__=f"fuse_inference(dry_run=...): a {cls.__name__}'s decision.  It cannot be run.")
+    return type("_Dry" + cls.__name__, (cls,), dict(body, __init__=init) if init else body)
+
+
+# What a matcher of _run_node_pass decides: the plan node's module is `cls(**ctor)`; it is called with `args` in place of fp32 node
+# `last`; `takers` read its codes; it replaces the nodes `erase` (erased in that order).
+_Splice = collections.namedtuple("_Splice", "cls ctor last args takers erase")
+
+
+def _run_node_pass(gm, report, kind, field, match, dry_run, outputs=2):
+    """One pass that puts code-emitting nodes behind the main pass's plan.  `match(node, modules)` reads the graph and changes nothing:
+    a _Splice (taken), a str (a candidate left alone: why - collected in `report.patch_embed_left`) or None.  Every node of the graph
+    as the pass found it is asked in turn; a taken one becomes plan node `_int8_<kind>_<i>` - the module, or under `dry_run` its
+    stand-in (_dry) - of `outputs` outputs; `modules` (name -> module) is kept current for the matcher; `report.<field>` counts."""
+    modules = dict(gm.named_modules())
+    count = 0
+    for node in list(gm.graph.nodes):
+        d = match(node, modules)
+        if isinstance(d, str):
+            report.patch_embed_left.append((node.name, d))
+        if not isinstance(d, _Splice):
+            continue
+        name = f"_int8_{kind}_{count}"
+        modules[name] = (_dry(d.cls) if dry_run else d.cls)(**d.ctor)
+        _splice_map_node(gm, d.last, name, modules[name], d.args, d.takers, d.erase, outputs)
+        count += 1
+    setattr(report, field, count)
+    _settle(gm, count)
 
 
 def _code_readers(planned, t, dw=False, dwpw=False, linear=False):
@@ -1048,22 +1102,14 @@ def _avgpool_pass(gm, report, planned, dry_run):
     """Windowed average pools (fuse_inference(avg_pools=True)): `AvgPool2d(s, s) -> plan convolution` becomes a node that hands the
     convolution its activation codes (AvgPoolLayer).  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for
     the convolution behind the pool (dual operand, own node, narrow, chain) stays - only its input changes, from fp32 to codes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-    count = 0
-    for pool in list(graph.nodes):
+    def match(pool, modules):
         win = _avgpool_window(pool, modules)
-        if win is None:
-            continue
-        x, s = win
-        taken = _code_readers(planned, pool)
+        taken = _code_readers(planned, pool) if win is not None else None
         if taken is None:
-            continue
-        module = _DryNode() if dry_run else AvgPoolLayer(s, **_decided(taken))
-        _splice_map_node(gm, pool, f"_int8_avgpool_{count}", module, (x,), taken.takers, [pool])
-        count += 1
-    report.avg_pools = count
-    _settle(gm, count)
+            return None
+        x, s = win
+        return _Splice(AvgPoolLayer, dict(_decided(taken), window=s), pool, (x,), taken.takers, [pool])
+    _run_node_pass(gm, report, "avgpool", "avg_pools", match, dry_run)
 
 
 class GateLayer(_MapCodesLayer):
@@ -1090,11 +1136,16 @@ class GateLayer(_MapCodesLayer):
 _MUL_FNS = (operator.mul, torch.mul)
 
 
+def _is_call(node, fns, method):
+    """`node` calls one of the functions `fns` or the tensor method `method`, without keyword arguments."""
+    if not isinstance(node, fx.Node) or node.kwargs:
+        return False
+    return (node.op == "call_function" and node.target in fns) or (node.op == "call_method" and node.target == method)
+
+
 def _is_mul(node):
     """An out-of-place multiply of two graph values: `a * b`, torch.mul(a, b), a.mul(b)."""
-    if node.kwargs or len(node.args) != 2 or not all(isinstance(a, fx.Node) for a in node.args):
-        return False
-    return (node.op == "call_function" and node.target in _MUL_FNS) or (node.op == "call_method" and node.target == "mul")
+    return _is_call(node, _MUL_FNS, "mul") and len(node.args) == 2 and all(isinstance(a, fx.Node) for a in node.args)
 
 
 def _squeezed_from(g, modules, limit=16):
@@ -1119,30 +1170,23 @@ def _gate_pass(gm, report, planned, dry_run, relu6):
     that hands the convolution its activation codes (GateLayer).  The squeeze path - pool, two small layers, the gate function - stays
     as it is.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for the convolution behind the
     gate stays - only its input changes, from fp32 to codes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-    count = 0
-    for mul in list(graph.nodes):
+    def match(mul, modules):
         if not _is_mul(mul) or mul.args[0] is mul.args[1] or _swish_of(mul, modules) is not None:      # (x * sigmoid(x): no gate)
-            continue
+            return None
         a, b = mul.args
         # exactly one operand derives from a global average pool, and that pool reads the other operand
         gated = [(x, g) for x, g in ((a, b), (b, a)) if _squeezed_from(g, modules) is x]
         if len(gated) != 1:
-            continue
-        x, g = gated[0]
+            return None
         act, last = N.ACT_NONE, mul
         nxt = _sole_user(mul)
         if nxt is not None and (_is_relu(nxt, modules) or (relu6 and _is_relu6(nxt, modules))):
             act, last = (N.ACT_RELU if _is_relu(nxt, modules) else N.ACT_RELU6), nxt
         taken = _code_readers(planned, last)
         if taken is None:
-            continue
-        module = _DryNode() if dry_run else GateLayer(act=act, **_decided(taken))
-        _splice_map_node(gm, last, f"_int8_gate_{count}", module, (x, g), taken.takers, [last, mul] if last is not mul else [mul])
-        count += 1
-    report.gates = count
-    _settle(gm, count)
+            return None
+        return _Splice(GateLayer, dict(_decided(taken), act=act), last, gated[0], taken.takers, [last, mul] if last is not mul else [mul])
+    _run_node_pass(gm, report, "gate", "gates", match, dry_run)
 
 
 class SwishLayer(_MapCodesLayer):
@@ -1168,16 +1212,8 @@ class SwishLayer(_MapCodesLayer):
         return (v, None) if self.emit is None else self._torch_codes(v)
 
 
-class _DrySwishLayer(SwishLayer):
-    """fuse_inference(dry_run=...): a SwishLayer's decision (emit, want_out, c, c_pad, pad_code, emit_shift).  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
-
-
 _SIGMOID_FNS = (torch.sigmoid, F.sigmoid)
 _SILU_FNS = (F.silu,)
-_SwishDecision = collections.namedtuple("_SwishDecision", ("last", "x", "nodes") + _CodeReaders._fields)
 
 
 def _swish_of(node, modules):
@@ -1228,33 +1264,21 @@ def _is_map(x, planned, modules, limit=8):
 def _swish_pass(gm, report, planned, dry_run, dwpw):
     """Swish activations (fuse_inference(swish=True)): `x * sigmoid(x)` / SiLU of a 4-D map becomes a node (SwishLayer) that hands the
     plan convolutions behind it - depthwise ones included - their activation codes and every other reader (a squeeze-excite pool, the
-    gate node, a shortcut add) the activated fp32 map from the same launch.  Per swish: decide (_SwishDecision; reads the graph, changes
-    nothing), build (the module, by mode), splice.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that
-    is for the convolution behind the swish stays - only its input changes, from fp32 to codes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-
-    def decide(node):
+    gate node, a shortcut add) the activated fp32 map from the same launch.  `planned`: plan node -> what the main pass decided for it
+    (_Decision); whatever that is for the convolution behind the swish stays - only its input changes, from fp32 to codes."""
+    def match(node, modules):
         found = _swish_of(node, modules)
         if found is None:
             return None
         x, nodes = found
         taken = _code_readers(planned, node, dw=True, dwpw=dwpw)
-        if taken is None:      # nobody takes codes: one pass over the map instead of two, where it is known to be a map
-            return _SwishDecision(node, x, nodes, *_CodeReaders(None, (), True, None, None, 0, False)) if _is_map(x, planned, modules) else None
-        return _SwishDecision(node, x, nodes, *taken)
-
-    count = 0
-    for node in list(graph.nodes):
-        d = decide(node)
-        if d is None:
-            continue
-        module = (_DrySwishLayer if dry_run else SwishLayer)(**_decided(d))
-        _splice_map_node(gm, d.last, f"_int8_swish_{count}", module, (d.x,), d.takers, d.nodes)
-        modules[f"_int8_swish_{count}"] = module
-        count += 1
-    report.swishes = count
-    _settle(gm, count)
+        if taken is None:      # nobody takes codes: one pass over the map instead of two, where it is known to be a map (which an
+            #                    earlier swish node's fp32 output is: `modules` holds the nodes of this pass too)
+            if not _is_map(x, planned, modules):
+                return None
+            taken = _CodeReaders(None, (), True, None, None, 0, False)
+        return _Splice(SwishLayer, _decided(taken), node, (x,), taken.takers, nodes)
+    _run_node_pass(gm, report, "swish", "swishes", match, dry_run)
 
 
 class LayerNormLayer(_MapCodesLayer):
@@ -1277,37 +1301,25 @@ class LayerNormLayer(_MapCodesLayer):
         return K.layernorm_quant(x, m.weight, m.bias, m.eps, emit=self.emit.emit(x.numel()), want_out=self.want_out)
 
 
-class _DryLayerNormLayer(LayerNormLayer):
-    """fuse_inference(dry_run=...): a LayerNormLayer's decision (norm, emit, want_out, c).  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
-
-
 def _layernorm_pass(gm, report, planned, dry_run):
     """LayerNorms (fuse_inference(layer_norms=True)): `nn.LayerNorm((C,)) -> Linear plan layers` becomes a node that hands the Linear
     layers their activation codes (LayerNormLayer) and anyone else the normalised fp32 rows from the same launch.  Taken: an nn.LayerNorm
     called with one positional argument, normalising the last dimension only, C % 4 == 0, 4 <= C <= K.LAYERNORM_MAX_C, a finite eps > 0,
     with at least one taker, every taker a Linear of C in-features.  `planned`: plan node -> what the main pass decided for it
     (_Decision); whatever that is for the Linear behind the LayerNorm stays - only its input changes, from fp32 to codes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-    count = 0
-    for node in list(graph.nodes):
+    def match(node, modules):
         m = modules.get(node.target) if node.op == "call_module" else None
         if type(m) is not nn.LayerNorm or len(node.args) != 1 or node.kwargs or not isinstance(node.args[0], fx.Node):
-            continue
+            return None
         shape = tuple(m.normalized_shape)
         if len(shape) != 1 or shape[0] % 4 or not 4 <= shape[0] <= K.LAYERNORM_MAX_C or not (m.eps > 0 and math.isfinite(m.eps)):
-            continue
+            return None
         taken = _code_readers(planned, node, linear=True)
         if taken is None or taken.c != shape[0] or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):
-            continue
-        module = (_DryLayerNormLayer if dry_run else LayerNormLayer)(m, taken.emit, taken.want_out, taken.c)
-        _splice_map_node(gm, node, f"_int8_layernorm_{count}", module, (node.args[0],), taken.takers, [node])
-        count += 1
-    report.layer_norms = count
-    _settle(gm, count)
+            return None
+        ctor = dict(norm=m, emit=taken.emit, want_out=taken.want_out, c=taken.c)
+        return _Splice(LayerNormLayer, ctor, node, (node.args[0],), taken.takers, [node])
+    _run_node_pass(gm, report, "layernorm", "layer_norms", match, dry_run)
 
 
 class AttentionLayer(_MapCodesLayer):
@@ -1356,27 +1368,8 @@ class AttentionLayer(_MapCodesLayer):
         return K.attention_quant(q, k, v, scale, emit=emit, want_out=self.want_out, merged=self.merged)
 
 
-class _DryAttentionLayer(AttentionLayer):
-    """fuse_inference(dry_run=...): an AttentionLayer's decision (emit, want_out, c, scale, merged, sdpa, flatten).  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
-
-
 _MATMUL_FNS = (torch.matmul, operator.matmul)
-_MUL_FNS = (operator.mul, torch.mul)
 _SDPA_NAMES = ("query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale")
-
-
-def _one_user(node):
-    return isinstance(node, fx.Node) and len(node.users) == 1
-
-
-def _is_call(node, fns, method):
-    """`node` calls one of the functions `fns` or the tensor method `method`, without keyword arguments."""
-    if not isinstance(node, fx.Node) or node.kwargs:
-        return False
-    return (node.op == "call_function" and node.target in fns) or (node.op == "call_method" and node.target == method)
 
 
 def _softmax_of(node, modules):
@@ -1421,17 +1414,17 @@ def _attention_core(node, modules):
         return None
     attn, v = node.args
     scores = _softmax_of(attn, modules)
-    if scores is None or not isinstance(v, fx.Node) or not _one_user(attn) or not _one_user(scores):
+    if scores is None or not isinstance(v, fx.Node) or _sole_user(attn) is None or _sole_user(scores) is None:
         return None
     if not _is_call(scores, _MUL_FNS, "mul") or len(scores.args) != 2:
         return None
     dots, c = scores.args if isinstance(scores.args[0], fx.Node) else scores.args[::-1]
-    if not isinstance(c, float) or not math.isfinite(c) or not _one_user(dots):
+    if not isinstance(c, float) or not math.isfinite(c) or _sole_user(dots) is None:
         return None
     if not _is_call(dots, _MATMUL_FNS, "matmul") or len(dots.args) != 2:
         return None
     q, kt = dots.args
-    if not isinstance(q, fx.Node) or not _one_user(kt) or not _is_call(kt, (torch.transpose,), "transpose") or len(kt.args) != 3:
+    if not isinstance(q, fx.Node) or _sole_user(kt) is None or not _is_call(kt, (torch.transpose,), "transpose") or len(kt.args) != 3:
         return None
     k, d0, d1 = kt.args
     if not isinstance(k, fx.Node) or {d0, d1} not in ({-1, -2}, {2, 3}, {-1, 2}, {-2, 3}) or isinstance(d0, bool) or isinstance(d1, bool):
@@ -1467,17 +1460,15 @@ def _merge_heads_tail(node):
     """(permute node, reshape node, its shape arguments or None for flatten(2)) if the sole reader of `node` [B, H, T, D] is
     `permute(0, 2, 1, 3)` / `transpose(1, 2)` whose sole reader reshapes to rank 3 - `reshape` / `view` with three sizes (Python
     ints or graph values) or `flatten(2)` - else None."""
-    if not _one_user(node):
-        return None
-    (perm,) = node.users
-    if perm.kwargs or perm.op != "call_method" or not perm.args or perm.args[0] is not node or not _one_user(perm):
+    perm = _sole_user(node)
+    shape = _sole_user(perm)
+    if shape is None or perm.kwargs or perm.op != "call_method" or not perm.args or perm.args[0] is not node:
         return None
     dims = perm.args[1:]
     if len(dims) == 1 and isinstance(dims[0], (tuple, list)):
         dims = tuple(dims[0])
     if not ((perm.target == "permute" and tuple(dims) == (0, 2, 1, 3)) or (perm.target == "transpose" and tuple(sorted(dims)) == (1, 2))):
         return None
-    (shape,) = perm.users
     if shape.kwargs or not shape.args or shape.args[0] is not perm:
         return None
     if (shape.op == "call_method" and shape.target == "flatten") or (shape.op == "call_function" and shape.target is torch.flatten):
@@ -1497,36 +1488,23 @@ def _attention_pass(gm, report, planned, dry_run):
     [B, Tq, H * D], and the Linear plan layers reading it - one quantiser, as for a LayerNorm - take its codes; anyone else reads the
     fp32 values of the same launch.  Without the tail it stands where the second product stood and returns fp32 [B, H, Tq, D].
     `planned`: plan node -> what the main pass decided for it (_Decision), which stays - only the reader's input changes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-    count = 0
-    for node in list(graph.nodes):
-        if node.op not in ("call_function", "call_method"):
-            continue
-        core = _attention_core(node, modules)
+    def match(node, modules):
+        core = _attention_core(node, modules) if node.op in ("call_function", "call_method") else None
         if core is None:
-            continue
+            return None
         q, k, v, scale, sdpa, made_of = core
         if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:      # (a head dimension the kernel is not built for, spelled as an int)
-            continue
-        tail = _merge_heads_tail(node)
-        cls = _DryAttentionLayer if dry_run else AttentionLayer
-        name = f"_int8_attention_{count}"
-        if tail is None:
-            module = cls(None, True, 0, scale, False, sdpa)
-            _splice_map_node(gm, node, name, module, (q, k, v), [], made_of)
-        else:
-            perm, shape, sizes = tail
-            taken = _code_readers(planned, shape, linear=True)
-            if taken is not None and any(planned[u].mod.weight.dim() != 2 for u in taken.takers):
-                taken = None
-            module = (cls(None, True, 0, scale, True, sdpa, sizes is None) if taken is None else
-                      cls(taken.emit, taken.want_out, taken.c, scale, True, sdpa, sizes is None))
-            _splice_map_node(gm, shape, name, module, (q, k, v) + (sizes or ()), [] if taken is None else taken.takers,
-                             [shape, perm] + made_of)
-        count += 1
-    report.attentions = count
-    _settle(gm, count)
+            return None
+        perm, shape, sizes = _merge_heads_tail(node) or (None, None, ())
+        taken = _code_readers(planned, shape, linear=True) if shape is not None else None
+        if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
+            taken = _CodeReaders(None, [], True, 0, 0, 0, False)
+        ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, sdpa=sdpa,
+                    flatten=sizes is None)
+        if shape is None:
+            return _Splice(AttentionLayer, ctor, node, (q, k, v), [], made_of)
+        return _Splice(AttentionLayer, ctor, shape, (q, k, v) + (sizes or ()), taken.takers, [shape, perm] + made_of)
+    _run_node_pass(gm, report, "attention", "attentions", match, dry_run)
 
 
 _GELU_ALPHA = 0.70710678118654752440      # 1 / sqrt(2): as a Python scalar torch multiplies an fp32 tensor by its fp32 rounding
@@ -1560,13 +1538,6 @@ class GeluLayer(_MapCodesLayer):
         return K.gelu_quant(x, **self._to_codes(x.numel()))
 
 
-class _DryGeluLayer(GeluLayer):
-    """fuse_inference(dry_run=...): a GeluLayer's decision (emit, want_out, c, c_pad, pad_code, emit_shift, rows).  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
-
-
 def _gelu_of(node, modules):
     """The graph value x if `node` is the erf-form GELU of x in a spelling the plan takes - nn.GELU() / nn.GELU(approximate="none") called
     with one positional argument, F.gelu(x) / F.gelu(x, approximate="none") (positional too) - else None.  The tanh form is none of them.
@@ -1589,20 +1560,14 @@ def _gelu_pass(gm, report, planned, dry_run, dwpw):
     plan convolutions (a map: the channel-padded code rows of the average-pool rule), never both; a GELU nobody takes as codes is left
     alone.  `planned`: plan node -> what the main pass decided for it (_Decision); whatever that is for the layer behind the GELU stays
     - only its input changes, from fp32 to codes."""
-    graph = gm.graph
-    modules = dict(gm.named_modules())
-    count = 0
-    for node in list(graph.nodes):
+    def match(node, modules):
         x = _gelu_of(node, modules)
         taken = _code_readers(planned, node, dwpw=dwpw, linear=True) if x is not None else None
         if taken is None:
-            continue
+            return None
         rows = planned[taken.takers[0]].mod.weight.dim() == 2
-        module = (_DryGeluLayer if dry_run else GeluLayer)(rows=rows, **_decided(taken))
-        _splice_map_node(gm, node, f"_int8_gelu_{count}", module, (x,), taken.takers, [node])
-        count += 1
-    report.gelus = count
-    _settle(gm, count)
+        return _Splice(GeluLayer, dict(_decided(taken), rows=rows), node, (x,), taken.takers, [node])
+    _run_node_pass(gm, report, "gelu", "gelus", match, dry_run)
 
 
 _PatchRows = collections.namedtuple("_PatchRows", "src chain c g1 g2 p emit takers want_out")
@@ -1632,13 +1597,6 @@ class PatchRowsLayer(_MapCodesLayer):
         return K.patch_rows_quant(img, p, emit=self.emit.emit(img.numel()), want_out=self.want_out)
 
 
-class _DryPatchRowsLayer(PatchRowsLayer):
-    """fuse_inference(dry_run=...): a PatchRowsLayer's decision.  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
-
-
 class TokenAssembleLayer(nn.Module):
     """`torch.cat((cls.expand(B, -1, -1), x), dim=1) + pos` - the class token in front of the embedded patches, the position embedding
     added - as one launch (csrc/tokens.hip): fp32 [B, T + 1, C], the bits of the two torch ops.  The node is called with the graph's
@@ -1654,13 +1612,6 @@ class TokenAssembleLayer(nn.Module):
 
     def forward(self, x, cls, pos):
         return K.assemble_tokens(x, cls, pos if self.rows is None else pos[:, :self.rows])
-
-
-class _DryTokenAssembleLayer(TokenAssembleLayer):
-    """fuse_inference(dry_run=...): a TokenAssembleLayer's decision.  It cannot be run."""
-
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
 
 
 def _static_sizes(node, methods):
@@ -1686,7 +1637,7 @@ def _patch_rows_of(planned, last):
         return None
     if order != (0, 2, 4, 3, 5, 1):
         return f"a permute {order}, not (0, 2, 4, 3, 5, 1)"
-    if not (_one_user(first) and _one_user(perm)):
+    if _sole_user(first) is None or _sole_user(perm) is None:
         return "an intermediate of the rearrangement has a second reader"
     lead, c, g1, p, g2, p2 = s6
     if lead != -1 or s3[0] != -1 or min(c, g1, p, g2) < 1 or p != p2 or s3[1:] != (g1 * g2, p * p * c):
@@ -1752,7 +1703,7 @@ def _token_assemble_of(gm, planned, add):
         sizes = tuple(sizes[0])
     if len(sizes) != 3 or tuple(sizes[1:]) != (-1, -1):
         return "the class token is not expanded along the batch alone"
-    if not (_one_user(expand) and _one_user(cat)):
+    if _sole_user(expand) is None or _sole_user(cat) is None:
         return "an intermediate (the expanded class token, the concatenation) has a second reader"
     if _inplace_add(add) and add.args[0] is not cat:
         return "an in-place add into the position embedding"
@@ -1761,7 +1712,7 @@ def _token_assemble_of(gm, planned, add):
         idx = pos.args[1]
         ok = (isinstance(idx, tuple) and len(idx) == 2 and all(isinstance(s, slice) for s in idx) and idx[0] == slice(None) and
               idx[1].start is None and idx[1].step is None and isinstance(idx[1].stop, int) and not isinstance(idx[1].stop, bool))
-        if not ok or not _one_user(pos):
+        if not ok or _sole_user(pos) is None:
             return "the position embedding is sliced in another way than [:, :n] with a static n"
         rows, pos = idx[1].stop, pos.args[0]
     cls_t, pos_t = _fetch_attr(gm, expand.args[0]), _fetch_attr(gm, pos)
@@ -1785,33 +1736,15 @@ def _patch_embed_pass(gm, report, planned, dry_run):
     says what is taken), and `cat((cls.expand(B, -1, -1), x), dim=1) + pos` one launch (TokenAssembleLayer; _token_assemble_of).
     `planned`: plan node -> what the main pass decided for it (_Decision), which stays - only the embedding's input changes, from fp32
     to codes.  A candidate that is left alone keeps its nodes, and `report.patch_embed_left` says why."""
-    graph = gm.graph
-    rows = tokens = 0
-    for node in list(graph.nodes):
+    def rows(node, modules):
         d = _patch_rows_of(planned, node)
-        if isinstance(d, str):
-            report.patch_embed_left.append((node.name, d))
-        if not isinstance(d, _PatchRows):
-            continue
-        module = (_DryPatchRowsLayer if dry_run else PatchRowsLayer)(d)
-        _splice_map_node(gm, node, f"_int8_patch_rows_{rows}", module, (d.src,), d.takers, d.chain)
-        rows += 1
-    for node in list(graph.nodes):
+        return _Splice(PatchRowsLayer, dict(decision=d), node, (d.src,), d.takers, d.chain) if isinstance(d, _PatchRows) else d
+
+    def tokens(node, modules):
         d = _token_assemble_of(gm, planned, node)
-        if isinstance(d, str):
-            report.patch_embed_left.append((node.name, d))
-        if not isinstance(d, _TokenAssemble):
-            continue
-        name = f"_int8_tokens_{tokens}"
-        gm.add_module(name, (_DryTokenAssembleLayer if dry_run else TokenAssembleLayer)(d))
-        with graph.inserting_after(node):
-            call = graph.call_module(name, args=(d.x, d.cls, d.pos))
-        node.replace_all_uses_with(call)
-        for n in d.chain:
-            graph.erase_node(n)
-        tokens += 1
-    report.patch_rows, report.token_assemblies = rows, tokens
-    _settle(gm, rows + tokens)
+        return _Splice(TokenAssembleLayer, dict(decision=d), node, (d.x, d.cls, d.pos), (), d.chain) if isinstance(d, _TokenAssemble) else d
+    _run_node_pass(gm, report, "patch_rows", "patch_rows", rows, dry_run)
+    _run_node_pass(gm, report, "tokens", "token_assemblies", tokens, dry_run, outputs=1)
 
 
 def _pool_dims(node, modules):
@@ -2003,20 +1936,14 @@ class StemLayer(_PlanLayer):
         return (out, out_codes) if in_kernel else self._finish(out, out_codes)
 
 
-class _DryNode(nn.Module):
-    def forward(self, *args):
-        raise RuntimeError("fuse_inference(dry_run=...) builds the plan's structure only")
+def _structure_only(self, layer, spec, **decided):
+    nn.Module.__init__(self)
+    self._structure(layer, spec, **decided)
 
 
-class _DryInt8Layer(Int8Layer):
-    """fuse_inference(dry_run="chains"): an Int8Layer's structure - what the chain-level passes decide on - without its weight codes
-    (quantising them needs the GPU).  It cannot be run."""
-
-    def __init__(self, layer, spec, **decided):
-        nn.Module.__init__(self)
-        self._structure(layer, spec, **decided)
-
-    forward = _DryNode.forward
+# fuse_inference(dry_run="chains"): an Int8Layer's structure - what the chain-level passes decide on - without its weight codes
+# (quantising them needs the GPU)
+_DryInt8Layer = _dry(Int8Layer, _structure_only)
 
 
 def _is_int8(m):
@@ -2423,10 +2350,6 @@ class _Decision:
         """The decision as _PlanLayer._structure takes it."""
         return dict(relu=self.relu, relu6=self.relu6, emit=self.emit, want_out=self.want_out, pool=self.pool, narrow=self.narrow, dw5=self.dw5,
                     pad_shortcut=None if self.pad_shortcut is None else (self.pad_shortcut.stride, self.pad_shortcut.lo))
-
-
-def _sole_user(node):
-    return next(iter(node.users)) if len(node.users) == 1 else None
 
 
 class _MainPass:

@@ -5,7 +5,8 @@ builder that builds the same plan.  tests/golden/plans/ holds one such text per 
 import torch.fx as fx
 
 ATTRS = ("relu", "relu6", "want_out", "pool", "k", "c", "k_pad", "c_pad", "kind", "narrow", "pad_shortcut", "emit_shift", "out_cm",
-         "want_codes", "swapped", "defer_out", "recompute", "window", "pad_code")
+         "want_codes", "swapped", "defer_out", "recompute", "window", "pad_code", "rows", "merged", "flatten", "scale", "sdpa", "channels",
+         "grid", "patch", "tokens")
 PARTS = ("a", "b", "short", "main", "dw", "pw")       # the plan layers a wrapper node (dual, chain, depthwise + pointwise, head) holds
 
 
@@ -36,6 +37,10 @@ def module_text(m):
             fields.append(f"{name}.key={getattr(q, 'key', None)!r}")
     if hasattr(m, "w_off"):
         fields.append(f"w_off is None={getattr(m, 'w_off', None) is None}")
+    if hasattr(m, "norm"):
+        fields += [f"norm.{name}={getattr(m.norm, name)!r}" for name in ("normalized_shape", "eps")]
+    if hasattr(m, "decision"):       # a pass's record (a namedtuple): node names and numbers; a quantiser by its key
+        fields += [f"decision.{name}={getattr(v, 'key', v)!r}" for name, v in m.decision._asdict().items()]
     return f"{type(m).__name__}({', '.join(fields)})"
 
 

@@ -1,6 +1,7 @@
 """The plan `fuse_inference` builds, node for node, against recorded texts (tests/plan_dump.py, tests/golden/plans/): models marked
 calibrated by hand on the CPU, every case under `dry_run=True` (the main pass's decisions) and `dry_run="chains"` (the chain-level passes
-on stand-ins of the plan layers).  A change to the plan builder that is meant to keep the plans keeps these texts; one that is meant to
+on stand-ins of the plan layers); the passes that put code-emitting nodes behind the main pass (_node_pass_cases) under `dry_run=True`
+alone.  A change to the plan builder that is meant to keep the plans keeps these texts; one that is meant to
 change a plan regenerates the files it changes (`python tests/test_plan_snapshot_host.py`) and shows the difference for review.
 One file per case: the plan's text, or - first line `= <case>` - its difference (difflib.unified_diff, no context) from the text of that
 other case, which has its own file and test: most cases differ from a neighbour in a few lines, many in none."""
@@ -29,7 +30,38 @@ def model(name):
         return qbase_mobilenet(first_offset=True)[0]
     if name.startswith("cifar_resnet20_"):
         return calibrated(W.CifarResNet(3, option=name[-1]))
+    if name == "small_vit":
+        from transformer_nets import small_vit
+        return calibrated(small_vit())
+    if name == "mobilenet_v2_se_swish":
+        return calibrated(W.mobilenet_v2(se=True, act="swish"))
+    if name.startswith("left_"):
+        return _left_alone(name[len("left_"):])
     return calibrated(getattr(W, name)())
+
+
+def _left_alone(name):
+    """One model per code-emitting pass that the pass leaves as it is, from the LEFT_ALONE tables of the passes' host tests."""
+    import attention_nets
+    import test_avgpool_host
+    import test_gate_host
+    import test_patch_embed_host
+    import test_swish_host
+    import test_transformer_host
+    from test_gap_host import calibrated
+    kind, _, case = name.partition("_")
+    if kind == "swish":
+        return calibrated(test_swish_host.Toy(test_swish_host.LEFT_ALONE[case]))
+    if kind == "gate":
+        return calibrated(test_gate_host.Toy(test_gate_host.LEFT_ALONE[case]))
+    if kind == "avgpool":
+        pool, tail = test_avgpool_host.LEFT_ALONE[case]
+        return calibrated(test_avgpool_host.Toy(pool(), tail))
+    if kind == "rows":
+        return test_transformer_host.LEFT_ALONE[case]()
+    if kind == "attention":
+        return calibrated(attention_nets.LEFT_ALONE[case]())
+    return calibrated(test_patch_embed_host.LEFT[case][0]())
 
 
 def _cases():
@@ -45,8 +77,25 @@ def _cases():
             out += [(f"cifar_resnet20_{option}", dict(kw, avg_pools=True)) for kw in CIFAR_FLAGS]
     out = [(name, kw, dry) for name, kw in out for dry in (True, "chains")]
     # (ResNet-50's chain-level flags decide nothing without the chain passes: under "chains" only)
-    return out + [("resnet50", kw, "chains") for kw in (dict(recompute_shortcuts=True), dict(recompute_shortcuts=False), dict(block_layout=True),
-                                                        dict(block_layout=False), dict(chain_pairs=False))]
+    out += [("resnet50", kw, "chains") for kw in (dict(recompute_shortcuts=True), dict(recompute_shortcuts=False), dict(block_layout=True),
+                                                  dict(block_layout=False), dict(chain_pairs=False))]
+    return out + [(name, kw, True) for name, kw in _node_pass_cases()]
+
+
+TRANSFORMER = dict(patch_embed=True, layer_norms=True, gelu=True, attention=True)
+
+
+def _node_pass_cases():
+    """The passes that put a code-emitting node behind the main pass's plan (swish, gate, average pool, patch embedding, LayerNorm, GELU,
+    attention), under `dry_run=True` only: each transformer flag alone and all four, the squeeze-excite / swish networks, and per pass one
+    model it leaves alone (a matcher that starts taking more shows up here)."""
+    out = [("small_vit", {flag: True}) for flag in TRANSFORMER] + [("small_vit", TRANSFORMER), ("vit_small", TRANSFORMER)]
+    out += [("mobilenet_v2_se_swish", dict(gates=True)), ("mobilenet_v2_se_swish", dict(gates=True, swish=True)),
+            ("efficientnet_b0", dict(gates=True, swish=True, dw5=True))]
+    return out + [("left_swish_sigmoid_read_twice", dict(swish=True)), ("left_gate_spatial_gate", dict(gates=True)),
+                  ("left_avgpool_kernel_3_stride_2", dict(avg_pools=True)), ("left_rows_c_66", dict(layer_norms=True)),
+                  ("left_rows_tanh_gelu", dict(gelu=True)), ("left_attention_scores_read_twice", dict(attention=True)),
+                  ("left_patch_p_mod_4", dict(patch_embed=True)), ("left_patch_pos_of_the_wrong_length", dict(patch_embed=True))]
 
 
 def case_id(name, kw, dry):
