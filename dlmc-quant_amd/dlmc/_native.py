@@ -53,6 +53,9 @@ ROUTE_TILED, ROUTE_HALO3X3, ROUTE_PW, ROUTE_PWR, ROUTE_DW, ROUTE_DWM, ROUTE_HALO
 ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "conv_pw", ROUTE_PWR: "conv_pwr", ROUTE_DW: "conv_dw",
              ROUTE_DWM: "conv_dwm", ROUTE_HALO3X3_PIPE: "conv3x3_pipe", ROUTE_GAP: "conv_gap"}     # the profile tag (bench.py's kernel families) of each route
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2   # DLMCQ_ACT_*: the `relu` argument of the fused convolution entry points
+SQUEEZE_NONE, SQUEEZE_RELU, SQUEEZE_SWISH = 0, 1, 2   # DLMCQ_SQUEEZE_*: dlmcq_squeeze_gate_i8's activation between its two layers
+GATE_NONE, GATE_SIGMOID, GATE_HARDSIGMOID = 0, 1, 2   # DLMCQ_GATE_*: ... and its gate function
+SQUEEZE_MAX_C, SQUEEZE_MAX_R, SQUEEZE_IMAGES = 2048, 512, 4   # DLMCQ_SQUEEZE_MAX_C / _MAX_R / _IMAGES
 Y_DEQUANT, Y_CODES = 0, 1
 CODES_NONE, CODES_I8, CODES_P4 = 0, 1, 2
 MINMAX_ABSMAX, MINMAX_MINMAX, MINMAX_NEGMIN = 0, 1, 2
@@ -154,6 +157,7 @@ SIGNATURES = {
     "dlmcq_avgpool_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_gate_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_swish_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_squeeze_gate_i8": (ctypes.c_int, [_p] * 7 + [_i32] + [_p] * 4 + [_i32, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_gelu_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_layernorm_rows_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_attention_f32": (ctypes.c_int, [_p, _p, _p, _p, _p] + [_i64] * 17 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),

@@ -17,7 +17,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "patch_rows_quant", "patch_rows_view", "patch_rows_torch", "PATCH_MAX_STRIP", "assemble_tokens", "tokens_view", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "squeeze_gate", "squeeze_gate_torch", "squeeze_gate_supported", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "patch_rows_quant", "patch_rows_view", "patch_rows_torch", "PATCH_MAX_STRIP", "assemble_tokens", "tokens_view", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1289,6 +1289,131 @@ def swish_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
     n, c, h, w_ = _fp32_map("swish_quant", x)
     return _map_codes("swish_quant", x, h, w_, emit, want_out, c_pad, pad_code, "swish", n * h * w_ * c * 4,
                       lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_swish_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail))
+
+
+SQUEEZE_ACTS = {None: N.SQUEEZE_NONE, "none": N.SQUEEZE_NONE, "relu": N.SQUEEZE_RELU, "swish": N.SQUEEZE_SWISH}
+GATE_FNS = {None: N.GATE_NONE, "none": N.GATE_NONE, "sigmoid": N.GATE_SIGMOID, "hardsigmoid": N.GATE_HARDSIGMOID}
+
+# the two layers of a squeeze path, checked: layer 1 (wq [R, C], wsum [R], bias, in_scale, in_zp, w_scale), layer 2 (wq [C, R], wsum [C],
+# bias, w_scale) - the small tensors flat fp32 on the codes' device, a one-entry weight scale broadcast
+_Squeeze = collections.namedtuple("_Squeeze", "n c r w1 wsum1 b1 s1 zp1 ws1 w2 wsum2 b2 ws2 act fn")
+
+
+def _squeeze_operands(name, codes, l1, inner_act, emit, l2, gate_fn, want_gate, want_hidden):
+    """squeeze_gate's and squeeze_gate_torch's shared argument checks, in the order that decides what a call with two faults is told:
+    the two names, nothing to produce, the quantiser, the codes, layer 1, layer 2 - all before anything needs the GPU."""
+    if inner_act not in SQUEEZE_ACTS:
+        raise ValueError(f"{name}: inner_act is None, 'relu' or 'swish', not {inner_act!r}")
+    if gate_fn not in GATE_FNS:
+        raise ValueError(f"{name}: gate_fn is None, 'sigmoid' or 'hardsigmoid', not {gate_fn!r}")
+    if not (want_gate or want_hidden):
+        raise ValueError(f"{name}: nothing to produce (neither the gate nor the hidden values)")
+    if emit is None:
+        raise ValueError(f"{name}: the second layer's activation quantiser (emit=EmitCodes(...)) is required")
+    if emit.shift128:
+        raise ValueError(f"{name}: the hidden codes are plain codes (EmitCodes.shift128 is refused)")
+    if codes.dim() != 2 or codes.dtype not in (torch.uint8, torch.int8):
+        raise ValueError(f"{name}: activation codes (N, C), uint8 or int8, not {codes.dtype} {tuple(codes.shape)}")
+    n, c = codes.shape
+    w1, w2 = l1["wq"], l2["wq"]
+    w1 = w1.reshape(w1.shape[0], -1) if w1.dim() == 4 and w1.shape[1:3] == (1, 1) else w1
+    w2 = w2.reshape(w2.shape[0], -1) if w2.dim() == 4 and w2.shape[1:3] == (1, 1) else w2
+    if w1.dim() != 2 or w1.dtype != torch.int8 or w1.shape[1] != c or w1.shape[0] < 1:
+        raise ValueError(f"{name}: layer 1's weight codes are int8 [R, {c}], not {w1.dtype} {tuple(w1.shape)}")
+    r = w1.shape[0]
+    if w2.dim() != 2 or w2.dtype != torch.int8 or tuple(w2.shape) != (c, r):
+        raise ValueError(f"{name}: layer 2's weight codes are int8 [{c}, {r}], not {w2.dtype} {tuple(w2.shape)}")
+    for what, t, k in (("layer 1's wsum", l1["wsum"], r), ("layer 2's wsum", l2["wsum"], c)):
+        if t.dtype != torch.int32 or t.numel() != k:
+            raise ValueError(f"{name}: {what} is int32 [{k}], not {t.dtype} {tuple(t.shape)}")
+    for what, t, k in (("layer 1's bias", l1.get("bias"), r), ("layer 2's bias", l2.get("bias"), c)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != k):
+            raise ValueError(f"{name}: {what} is fp32 [{k}] or None, not {t.dtype} {tuple(t.shape)}")
+    for what, t, k in (("layer 1's w_scale", l1["w_scale"], r), ("layer 2's w_scale", l2["w_scale"], c)):
+        if isinstance(t, torch.Tensor) and t.numel() not in (1, k):
+            raise ValueError(f"{name}: {what} has 1 or {k} entries, not {t.numel()}")
+    N.require_gpu(codes, w1, w2)
+    codes = codes.contiguous()
+    return codes, _Squeeze(n, c, r, w1.contiguous(), l1["wsum"].reshape(-1).contiguous(), _bias_c(l1.get("bias")), _flat(l1["in_scale"], codes),
+                           _flat(l1.get("in_zp"), codes), _flat(l1["w_scale"], codes, r), w2.contiguous(), l2["wsum"].reshape(-1).contiguous(),
+                           _bias_c(l2.get("bias")), _flat(l2["w_scale"], codes, c), SQUEEZE_ACTS[inner_act], GATE_FNS[gate_fn])
+
+
+def _pad_cols(t, width, fill):
+    """2-D `t` with its rows widened to `width` columns of `fill` (a Python number or a one-entry tensor): a copy, or `t` as it is."""
+    n, c = t.shape
+    if c == width:
+        return t
+    out = torch.empty((n, width), dtype=t.dtype, device=t.device)
+    out[:, :c] = t
+    out[:, c:] = fill
+    return out
+
+
+def squeeze_gate_supported(c, r):
+    """Whether dlmcq_squeeze_gate_i8 takes a squeeze path of `c` channels and `r` hidden units (padded to a multiple of 4)."""
+    return c % 4 == 0 and 4 <= c <= N.SQUEEZE_MAX_C and 1 <= (r + 3) // 4 * 4 <= N.SQUEEZE_MAX_R
+
+
+def squeeze_gate_torch(codes, l1, inner_act, emit, l2, gate_fn, want_gate=True, want_hidden=False):
+    """squeeze_gate restated with the wrappers that were there before it - what squeeze_gate runs for widths its kernel does not take,
+    and the yardstick its tests compare it with bit for bit: the codes padded with their zero point and the weights with 0 to a multiple
+    of 64 (integer sums do not change), conv2d_i8, the activation in torch, fake_quant to the hidden codes, conv2d_i8, torch.sigmoid or
+    F.relu6(v + 3) / 6.  Returns `(gate or None, hidden or None)`, hidden (N, R)."""
+    codes, q = _squeeze_operands("squeeze_gate_torch", codes, l1, inner_act, emit, l2, gate_fn, want_gate, want_hidden)
+    c64, r64 = (q.c + 63) // 64 * 64, (q.r + 63) // 64 * 64
+    zp1 = 0 if q.zp1 is None else q.zp1.to(codes.dtype)
+    w1 = _pad_cols(q.w1, c64, 0).reshape(q.r, 1, 1, c64)
+    h = conv2d_i8(_pad_cols(codes, c64, zp1), w1, q.wsum1, q.b1, q.s1, q.zp1, q.ws1)
+    if q.act == N.SQUEEZE_RELU:
+        h = torch.relu(h)
+    elif q.act == N.SQUEEZE_SWISH:
+        h = h * torch.sigmoid(h)
+    hidden = h if want_hidden else None
+    if not want_gate:
+        return None, hidden
+    hq = fake_quant(h, emit.scale, emit.zero_point, emit.lo, emit.hi, emit.form, g=emit.g, codes="i8", want_y=False)[1]
+    s_h, zp2 = _flat(emit.scale, codes), _flat(emit.zero_point, codes)
+    if emit.form == FORM_QBASE:
+        sg = s_h * emit.g
+        s_h = (s_h - sg) + sg
+    w2 = _pad_cols(q.w2, r64, 0).reshape(q.c, 1, 1, r64)
+    v = conv2d_i8(_pad_cols(hq, r64, 0 if zp2 is None else zp2.to(hq.dtype)), w2, q.wsum2, q.b2, s_h, zp2, q.ws2)
+    if q.fn == N.GATE_SIGMOID:
+        v = torch.sigmoid(v)
+    elif q.fn == N.GATE_HARDSIGMOID:
+        v = torch.nn.functional.relu6(v + 3) / 6
+    return v, hidden
+
+
+def squeeze_gate(codes, l1, inner_act, emit, l2, gate_fn, want_gate=True, want_hidden=False):
+    """The squeeze path of a squeeze-excite block from its pooled activation codes (N, C) - global_avgpool's - to the fp32 gate (N, C), by
+    dlmcq_squeeze_gate_i8 in one launch: int8 layer 1 (`l1`: wq int8 [R, C], wsum, bias or None, in_scale, in_zp, w_scale), `inner_act`
+    (None, "relu", "swish"), the hidden quantiser `emit` (EmitCodes, plain codes), int8 layer 2 (`l2`: wq int8 [C, R], wsum, bias or None,
+    w_scale; its input scale and zero point are the quantiser's), `gate_fn` (None, "sigmoid", "hardsigmoid").  The operands are marshalled
+    as conv2d_i8 marshals its own; a hidden width that is no multiple of 4 is zero-padded here, per call (a plan pads once).  Returns
+    `(gate or None, hidden or None)`: `hidden` (N, R) the fp32 values behind `inner_act`, for tests and calibration.  Widths the kernel
+    does not take (C % 4, C > 2048, R > 512) run squeeze_gate_torch: the same values from the tiled kernels."""
+    codes, q = _squeeze_operands("squeeze_gate", codes, l1, inner_act, emit, l2, gate_fn, want_gate, want_hidden)
+    if not squeeze_gate_supported(q.c, q.r):
+        return squeeze_gate_torch(codes, l1, inner_act, emit, l2, gate_fn, want_gate, want_hidden)
+    n, c, r = q.n, q.c, q.r
+    r4 = (r + 3) // 4 * 4
+    w1, wsum1, b1, ws1, w2 = q.w1, q.wsum1, q.b1, q.ws1, q.w2
+    if r4 != r:
+        pad = lambda t, fill: torch.cat([t.reshape(-1), torch.full((r4 - r,), fill, dtype=t.dtype, device=t.device)])  # noqa: E731
+        w1 = torch.cat([w1, torch.zeros((r4 - r, c), dtype=torch.int8, device=w1.device)])
+        wsum1, ws1, b1 = pad(wsum1, 0), pad(ws1, 1.0), (None if b1 is None else pad(b1, 0.0))
+        w2 = _pad_cols(w2, r4, 0)
+    gate = torch.empty((n, c), dtype=torch.float32, device=codes.device) if want_gate else None
+    hidden = torch.empty((n, r4), dtype=torch.float32, device=codes.device) if want_hidden else None
+    qs, qz = _flat(emit.scale, codes), _flat(emit.zero_point, codes)
+    nbytes = n * c + w1.numel() + w2.numel() + 4 * n * c * want_gate + 4 * n * r4 * want_hidden
+    PROFILE.launch("squeeze", nbytes, lambda: N.check(N.lib.dlmcq_squeeze_gate_i8(
+        N.ptr(codes), N.ptr(w1), N.ptr(wsum1), N.ptr(b1), N.ptr(q.s1), N.ptr(q.zp1), N.ptr(ws1), q.act, N.ptr(w2), N.ptr(q.wsum2), N.ptr(q.b2),
+        N.ptr(q.ws2), q.fn, N.ptr(gate), N.ptr(hidden), n, c, r4, int(codes.dtype == torch.uint8), N.ptr(qs), N.ptr(qz), emit.lo, emit.hi,
+        emit.form, emit.g, N.stream_ptr())), 2 * n * (c * r4) * 2)
+    return gate, (hidden if hidden is None or r4 == r else hidden[:, :r])
 
 
 def gelu_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):

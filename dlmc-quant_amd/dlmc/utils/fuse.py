@@ -35,7 +35,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SqueezeLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -1028,9 +1028,9 @@ def _dry(cls, init=None):
 _Splice = collections.namedtuple("_Splice", "cls ctor last args takers erase")
 
 
-def _run_node_pass(gm, report, kind, field, match, dry_run, outputs=2):
+def _run_node_pass(gm, report, kind, field, match, dry_run, outputs=2, left=None):
     """One pass that puts code-emitting nodes behind the main pass's plan.  `match(node, modules)` reads the graph and changes nothing:
-    a _Splice (taken), a str (a candidate left alone: why - collected in `report.patch_embed_left`) or None.  Every node of the graph
+    a _Splice (taken), a str (a candidate left alone: why - collected in `left`, else `report.patch_embed_left`) or None.  Every node of the graph
     as the pass found it is asked in turn; a taken one becomes plan node `_int8_<kind>_<i>` - the module, or under `dry_run` its
     stand-in (_dry) - of `outputs` outputs; `modules` (name -> module) is kept current for the matcher; `report.<field>` counts."""
     modules = dict(gm.named_modules())
@@ -1038,7 +1038,7 @@ def _run_node_pass(gm, report, kind, field, match, dry_run, outputs=2):
     for node in list(gm.graph.nodes):
         d = match(node, modules)
         if isinstance(d, str):
-            report.patch_embed_left.append((node.name, d))
+            (report.patch_embed_left if left is None else left).append((node.name, d))
         if not isinstance(d, _Splice):
             continue
         name = f"_int8_{kind}_{count}"
@@ -1769,13 +1769,13 @@ def _pool_dims(node, modules):
     return None
 
 
-def _batch_size_of(node):
-    """Whether `node` is `t.size(0)` / `t.shape[0]` of some tensor `t` (the first argument of a `.view(N, -1)`)."""
+def _batch_size_of(node, dim=0):
+    """Whether `node` is `t.size(0)` / `t.shape[0]` of some tensor `t` (the first argument of a `.view(N, -1)`); `dim`: another axis."""
     if not isinstance(node, fx.Node):
         return False
     if node.op == "call_method" and node.target == "size":
-        return len(node.args) == 2 and node.args[1] == 0 and not node.kwargs
-    if node.op == "call_function" and node.target is operator.getitem and node.args[1] == 0:
+        return len(node.args) == 2 and node.args[1] == dim and not node.kwargs
+    if node.op == "call_function" and node.target is operator.getitem and node.args[1] == dim:
         src = node.args[0]
         return (isinstance(src, fx.Node) and ((src.op == "call_function" and src.target is getattr and src.args[1] == "shape") or
                                               (src.op == "call_method" and src.target == "size" and len(src.args) == 1)))
@@ -1893,6 +1893,256 @@ def _gap_pass(gm, report, mode, planned, dry_run):
     _settle(gm, count)
 
 
+# ------------------------------------------------------------------ the squeeze path of a squeeze-excite block
+# What _squeeze_pass decides for one node: graph names, widths, the two activations' names, whether the gate keeps (N, C, 1, 1), the two
+# layers' module names and input quantisers (_ActSpec), which of them the main pass had planned, and the nodes the node replaces.
+_SqueezeDecision = collections.namedtuple("_SqueezeDecision", "pool x c r r4 inner gate_fn rank4 layer1 layer2 q1 q2 planned chain")
+
+
+def _squeeze_weights(mod, spec):
+    """A squeeze layer's integer weight codes [K, C] (int16) and its weight scales [K] from its frozen spec (symmetric weights)."""
+    w = mod.weight.detach()
+    k = w.shape[0]
+    ws = spec.w_scale.detach().to(torch.float32).reshape(-1)
+    ws = (ws.expand(k) if ws.numel() == 1 else ws).contiguous()
+    if spec.w_codes is not None:
+        q = spec.w_codes()
+    else:
+        q = K.quantize_weight_krsc(w if w.dim() == 4 else w[:, :, None, None], ws, spec.w_lo, spec.w_hi)[0]
+    return q.reshape(k, -1).to(torch.int16), ws
+
+
+class SqueezeLayer(nn.Module):
+    """The squeeze path of a squeeze-excite block - global average pool, (flatten), a quantised Linear / 1x1 convolution, none | ReLU |
+    swish, a second such layer, (view), sigmoid | hard sigmoid - as two launches: K.global_avgpool hands layer 1 its activation codes
+    (N, C), K.squeeze_gate (csrc/squeeze_i8.hip) takes them to the fp32 gate.  `decision`: the pass's record (_SqueezeDecision);
+    `layers`: (module 1, its _LayerSpec, module 2, its _LayerSpec); `weights=False` (a dry run) quantises nothing.  The hidden width is
+    zero-padded to a multiple of 4 here, once.  An input that at run time is no channels_last fp32 (N, C, H, W) device map of the planned
+    width is converted and runs `restated`: the same values from the kernels that were there before.  Returns the gate, (N, C, 1, 1) or
+    (N, C) as the graph had it."""
+
+    def __init__(self, decision, layers, weights=True):
+        super().__init__()
+        d = decision
+        self.c, self.r, self.r4, self.inner, self.gate_fn, self.rank4 = int(d.c), int(d.r), int(d.r4), d.inner, d.gate_fn, bool(d.rank4)
+        mod1, spec1, mod2, spec2 = layers
+        self.act1, self.act2 = spec1.act, spec2.act
+        self.decision = d
+        self._deq = {}
+        if not weights:
+            return
+        (q1, ws1), (q2, ws2) = _squeeze_weights(mod1, spec1), _squeeze_weights(mod2, spec2)
+        dev, c, r, r4 = q1.device, self.c, self.r, self.r4
+        w1, w2 = torch.zeros((r4, c), dtype=torch.int16, device=dev), torch.zeros((c, r4), dtype=torch.int16, device=dev)
+        w1[:r], w2[:, :r] = q1, q2
+
+        def padded(v, fill):
+            out = torch.full((r4,), fill, dtype=torch.float32, device=dev)
+            out[:r] = v.detach().to(torch.float32).reshape(-1)
+            return out
+        for name, t in (("w1", w1.to(torch.int8)), ("wsum1", w1.sum(dim=1).to(torch.int32)), ("ws1", padded(ws1, 1.0)),
+                        ("b1", None if mod1.bias is None else padded(mod1.bias, 0.0)), ("w2", w2.to(torch.int8)),
+                        ("wsum2", w2.sum(dim=1).to(torch.int32)), ("ws2", ws2),
+                        ("b2", None if mod2.bias is None else mod2.bias.detach().to(torch.float32).reshape(-1).clone())):
+            self.register_buffer(name, None if t is None else t.contiguous(), persistent=False)
+
+    def _in_scale(self, numel):
+        """Layer 1's dequantising scale: QBase's is grad_scale(s, g) with g taken over the layer's input (as _PlanLayer._in_scale)."""
+        if not self.act1.needs_g:
+            return self.act1.scale
+        s = self._deq.get(numel)
+        if s is None:
+            s = self._deq[numel] = ste_scale_value(self.act1.scale, self.act1.g(numel)).contiguous()
+        return s
+
+    def _operands(self, n):
+        """K.squeeze_gate's arguments behind the codes for a batch of `n` images."""
+        l1 = dict(wq=self.w1, wsum=self.wsum1, bias=self.b1, in_scale=self._in_scale(n * self.c), in_zp=self.act1.zp, w_scale=self.ws1)
+        return l1, self.inner, self.act2.emit(n * self.r), dict(wq=self.w2, wsum=self.wsum2, bias=self.b2, w_scale=self.ws2), self.gate_fn
+
+    def _run(self, x, fn):
+        n = x.shape[0]
+        codes = K.global_avgpool(x, emit=self.act1.emit(n * self.c), want_out=False)[1]
+        gate = fn(codes, *self._operands(n))[0]
+        return gate.view(n, self.c, 1, 1) if self.rank4 else gate
+
+    def restated(self, x):
+        """The node's value from the wrappers that were there before it (K.squeeze_gate_torch), for any (N, C, H, W) input."""
+        if x.dim() != 4 or x.shape[1] != self.c:
+            raise ValueError(f"SqueezeLayer: a (N, {self.c}, H, W) map, not {tuple(x.shape)}")
+        return self._run(x.to(torch.float32).contiguous(memory_format=torch.channels_last), K.squeeze_gate_torch)
+
+    def forward(self, x):
+        # (NHWC rows: channels_last memory, or the channel slice a channel-padded plan layer returns as its fp32 output)
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or x.shape[1] != self.c or not (
+                x.is_contiguous(memory_format=torch.channels_last) or K._nhwc_rows(x) is not None):
+            return self.restated(x)
+        return self._run(x, K.squeeze_gate)
+
+
+def _squeeze_layer_shape_ok(mod):
+    """A Linear, or an unpadded 1x1 / stride 1 convolution without groups or dilation."""
+    w = mod.weight
+    if w.dim() == 2:
+        return True
+    return (w.dim() == 4 and tuple(w.shape[2:]) == (1, 1) and tuple(mod.stride) == (1, 1) and tuple(mod.padding) == (0, 0) and
+            mod.groups == 1 and tuple(mod.dilation) == (1, 1) and mod.padding_mode == "zeros")
+
+
+def _squeeze_refusal(mod, spec, weight_blob, pack_int4):
+    """Why a squeeze layer with frozen spec `spec` (None: it has none) stays as it is, or None."""
+    if isinstance(mod, FSPTQBase) and mod.qconfig["weight"].get("recon_type") in ("adaround", "dist_recon"):
+        return "AdaRound / dist_recon weights"
+    if isinstance(mod, QBase) and float(mod.in_offset.abs().max()) != 0:
+        return "a float activation offset"
+    if spec is None:
+        return "no frozen int8 quantisers (a disabled quantiser, a non-integer zero point or a range beyond a byte)"
+    if not spec.symmetric:
+        return "asymmetric weights"
+    if spec.w_hi > 127 or spec.w_lo < -128:
+        return "weights with an offset (codes beyond int8 are re-centred)"
+    if weight_blob is not None:
+        return "a plan built from an integer checkpoint (weight_blob)"
+    if pack_int4 and -8 <= spec.w_lo and spec.w_hi <= 15:
+        return "4-bit weights, which the plan stores packed (pack_int4)"
+    return None
+
+
+_DIV_FNS = (operator.truediv, torch.div, torch.true_divide)
+
+
+def _squeeze_gate_fn(node, src, modules):
+    """(name, nodes) if `node` starts the gate function of `src` in a spelling the plan takes - torch.sigmoid / F.sigmoid / .sigmoid() /
+    nn.Sigmoid; nn.Hardsigmoid, F.hardsigmoid; `relu6(src + 3) / 6` spelled out, each node read by the next alone - else None."""
+    if not isinstance(node, fx.Node):
+        return None
+    one = len(node.args) == 1 and node.args[0] is src
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        name = "sigmoid" if type(m) is nn.Sigmoid else ("hardsigmoid" if type(m) is nn.Hardsigmoid else None)
+        return (name, [node]) if name and one and not node.kwargs else None
+    if _is_call(node, _SIGMOID_FNS, "sigmoid") and one:
+        return "sigmoid", [node]
+    if node.op == "call_function" and node.target is F.hardsigmoid:
+        return ("hardsigmoid", [node]) if one and set(node.kwargs) <= {"inplace"} else None
+    num = lambda v, k: isinstance(v, (int, float)) and not isinstance(v, bool) and float(v) == k  # noqa: E731
+    if not (_is_call(node, (operator.add, torch.add), "add") and len(node.args) == 2 and
+            ((node.args[0] is src and num(node.args[1], 3.0)) or (node.args[1] is src and num(node.args[0], 3.0)))):
+        return None
+    r6 = _sole_user(node)
+    if r6 is None or not _is_relu6(r6, modules) or r6.args[0] is not node:
+        return None
+    div = _sole_user(r6)
+    if not (_is_call(div, _DIV_FNS, "div") and len(div.args) == 2 and div.args[0] is r6 and num(div.args[1], 6.0)):
+        return None
+    return "hardsigmoid", [node, r6, div]
+
+
+def _squeeze_pass(gm, report, planned, dry_run, weight_blob, pack_int4):
+    """Squeeze paths (fuse_inference(squeezes=True)): `pool(x) -> (flatten) -> layer -> none | ReLU | swish -> layer -> (view) -> sigmoid
+    | hard sigmoid`, every node read by the next alone, becomes one SqueezeLayer node called with `x`.  A layer is a QBase / FSPTQ Linear
+    or unpadded 1x1 / stride 1 convolution still in the graph (its frozen quantisers read with kind "gemm": this kernel pads nothing to
+    64), or the plan node the main pass made of one (with the ReLU it absorbed and the codes it hands the second layer).  `planned`:
+    plan node -> _Decision; absorbed plan nodes leave it and the report's counts, absorbed wrappers leave `report.skipped`.  A candidate
+    the kernel or the pass does not take stays as it is, with the reason in `report.squeeze_left`."""
+    absorbed = []
+
+    def layer(node, modules):
+        """(module, spec or None, ReLU absorbed, output node, [the nodes], _Decision or None) of a squeeze layer at `node`, else None."""
+        d = planned.get(node)
+        if d is not None:
+            gets = _outputs_read(node)
+            if (d.dual or d.residual is not None or d.pool is not None or d.relu6 or d.narrow or d.pad_shortcut is not None or
+                    d.spec.kind != "gemm" or gets is None or len(gets) != 1 or not _squeeze_layer_shape_ok(d.mod)):
+                return None
+            (i, out), = gets.items()
+            if (i == 1) != (d.emit is not None and not d.want_out):
+                return None
+            return d.mod, d.spec, d.relu, out, [node, out], d
+        if not isinstance(node, fx.Node) or node.op != "call_module" or len(node.args) != 1 or node.kwargs:
+            return None
+        mod = modules.get(node.target)
+        if not isinstance(mod, (QBase, FSPTQBase)) or not hasattr(mod, "weight") or not _squeeze_layer_shape_ok(mod):
+            return None
+        spec = _fsptq_spec(mod, "gemm") if isinstance(mod, FSPTQBase) else _qbase_spec(mod, "gemm", False)
+        return mod, spec, False, node, [node], None
+
+    def match(pool, modules):
+        rank = _pool_dims(pool, modules)
+        x = (pool.args[0] if pool.args else pool.kwargs.get("input")) if rank is not None else None
+        if not isinstance(x, fx.Node):
+            return None
+        chain, cur = [pool], pool
+        nxt = _sole_user(cur)
+        if (nxt is not None and nxt.target in ("flatten", "view", "reshape", torch.flatten) and _flatten_rank(nxt, cur, rank) == 2):
+            chain, cur, rank = chain + [nxt], nxt, 2
+            nxt = _sole_user(cur)
+        l1 = layer(nxt, modules)
+        if l1 is None or (l1[0].weight.dim() == 2) != (rank == 2):
+            return None
+        mod1, spec1, relu1, cur, nodes1, d1 = l1
+        chain += nodes1
+        inner, users = ("relu" if relu1 else None), list(cur.users)
+        if d1 is None or d1.emit is None:      # (else: the plan node hands the second layer its codes itself)
+            mul = next((u for u in users if _is_mul(u)), None)
+            sw = _swish_of(mul, modules) if len(users) == 2 and mul is not None else None
+            if sw is not None and sw[0] is cur and len(sw[1]) == 2 and set(sw[1]) == set(users) and inner is None:
+                inner, cur = "swish", mul
+                chain += sw[1][::-1]
+            elif len(users) == 1 and inner is None and _is_relu(users[0], modules) and users[0].args[0] is cur:
+                inner, cur = "relu", users[0]
+                chain.append(cur)
+            elif len(users) != 1:
+                return None
+        nxt = _sole_user(cur)
+        l2 = layer(nxt, modules)
+        if l2 is None or l2[2] or (l2[5] is not None and l2[5].emit is not None) or l2[0].weight.dim() != mod1.weight.dim():
+            return None
+        mod2, spec2, _, cur, nodes2, d2 = l2
+        chain += nodes2
+        r, c = int(mod1.weight.shape[0]), int(mod1.weight.shape[1])
+        if tuple(mod2.weight.shape[:2]) != (c, r):
+            return None
+        rank4 = rank == 4
+        nxt = _sole_user(cur)
+        if nxt is not None and not rank4 and nxt.op == "call_method" and nxt.target in ("view", "reshape") and not nxt.kwargs and nxt.args[0] is cur:
+            shape = nxt.args[1:]
+            shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else shape
+            if (len(shape) == 4 and _batch_size_of(shape[0]) and (shape[1] == c or _batch_size_of(shape[1], 1)) and shape[2] == 1 and shape[3] == 1):
+                chain, cur, rank4 = chain + [nxt], nxt, True
+                nxt = _sole_user(cur)
+        fn = _squeeze_gate_fn(nxt, cur, modules)
+        if fn is None:
+            return None
+        chain += fn[1]
+        # ---- a candidate: taken unless a quantiser or a width refuses
+        for mod, spec in ((mod1, spec1), (mod2, spec2)):
+            why = _squeeze_refusal(mod, spec, weight_blob, pack_int4)
+            if why is not None:
+                return why
+        if d1 is not None and d1.emit is not None and d1.emit.key != spec2.act.key:
+            return "the first layer emits another quantiser's codes than the second layer reads"
+        if not K.squeeze_gate_supported(c, r):
+            return f"widths beyond the kernel's limits ({c} channels, {r} hidden units)"
+        names = tuple(d.node.target if d is not None else n[0].target for d, n in ((d1, nodes1), (d2, nodes2)))
+        dec = _SqueezeDecision(pool.name, x.name, c, r, (r + 3) // 4 * 4, inner, fn[0], rank4, names[0], names[1], spec1.act, spec2.act,
+                               (d1 is not None, d2 is not None), tuple(n.name for n in chain))
+        absorbed.extend([(nodes1[0], d1, names[0]), (nodes2[0], d2, names[1])])
+        return _Splice(SqueezeLayer, dict(decision=dec, layers=(mod1, spec1, mod2, spec2), weights=not dry_run), chain[-1], (x,), (), chain[::-1])
+
+    _run_node_pass(gm, report, "squeeze", "squeezes", match, dry_run, outputs=1, left=report.squeeze_left)
+    for node, d, name in absorbed:
+        if d is None:
+            if name in report.skipped:
+                report.skipped.remove(name)
+            continue
+        planned.pop(node, None)
+        report.layers -= 1
+        report.relu -= d.relu
+        report.emit -= d.emit is not None
+        report.fp32_outputs -= d.want_out
+
+
 class StemLayer(_PlanLayer):
     """The network's first convolution (<= 4 input channels) of the frozen plan: the image is quantised into a
     zero-point-padded NHWC4 code buffer and convolved on the matrix cores (csrc/conv_stem_i8.hip)."""
@@ -1967,6 +2217,8 @@ class FusionReport:
         self.avg_pools = 0    # windowed average pools handing the plan layers behind them their codes (fuse_inference(avg_pools=True))
         self.gates = 0        # squeeze-excite gates (x * g, + ReLU / ReLU6) handing the plan layers behind them their codes (fuse_inference(gates=True))
         self.dw5 = 0          # 5x5 depthwise layers on the integer dot-product kernel, csrc/conv_dw5_i8.hip (fuse_inference(dw5=True))
+        self.squeezes = 0     # squeeze paths (pool, two small layers, gate function) running as two launches (fuse_inference(squeezes=True))
+        self.squeeze_left = []   # (pool node, why): squeeze paths the squeeze pass recognised and left as they are
         self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
@@ -2003,6 +2255,7 @@ class FusionReport:
                 (f"pad shortcuts={self.pad_shortcuts}, " if self.pad_shortcuts else "") +
                 (f"average pools on the plan={self.avg_pools}, " if self.avg_pools else "") +
                 (f"gates on the plan={self.gates}, " if self.gates else "") +
+                (f"squeezes on the plan={self.squeezes}, " if self.squeezes else "") +
                 (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
@@ -2549,7 +2802,7 @@ class _MainPass:
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
                    recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False,
-                   patch_embed=False):
+                   patch_embed=False, squeezes=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2721,7 +2974,20 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     arithmetic but the quantiser's in the first, one IEEE add in the second (tests/test_gpu_patch_rows.py, tests/test_gpu_tokens.py) -
     so the plan's logits are torch.equal to the plan's without the flag (tests/test_gpu_patch_embed_plan.py).  At run time an input the
     kernels do not take (not fp32, a channels_last image batch, misaligned) runs the same torch ops inside the node.  Runs after the
-    main pass and before the LayerNorm pass.  Off by default: the plan without it is the plan as it was."""
+    main pass and before the LayerNorm pass.  Off by default: the plan without it is the plan as it was.
+    `squeezes=True`: the squeeze path of a squeeze-excite block - a global average pool of x (a spelling the head pass
+    knows), an optional flatten / view / reshape(x.size(0), -1), a QBase or FSPTQ Linear or unpadded 1x1 / stride 1 convolution, nothing,
+    a ReLU or a swish (x * sigmoid(x)), a second such layer, an optional view(N, C, 1, 1), and torch.sigmoid, nn.Hardsigmoid,
+    F.hardsigmoid or the spelled-out relu6(v + 3) / 6, every node read by the next alone - becomes one SqueezeLayer node: the pool
+    kernel hands layer 1 its activation codes and one launch (csrc/squeeze_i8.hip) takes them to the fp32 gate, the hidden vector never
+    leaving the chip (`fusion_report.squeezes` counts the nodes).  The layers' frozen quantisers are read with kind "gemm" directly - the
+    64-channel rule of the tiled kernel does not apply - so EfficientNet's 4- to 48-wide layers leave `not eligible`; layers the main
+    pass had planned (MobileNetV2-SE's convolutions) leave `int8 layers`.  Left as they are, with the reason in
+    `fusion_report.squeeze_left`: asymmetric weights or weight codes beyond int8, a float activation offset, AdaRound / dist_recon
+    weights, more than 2048 channels or 512 hidden units, a plan built with `weight_blob`, 4-bit weights under `pack_int4`.  Runs behind
+    the gate pass, which therefore takes every gate it took.  The two layers compute dlmcq_conv2d_i8_nhwc_fused's values bit for bit
+    (tests/test_gpu_squeeze.py); against the plan without the flag the pooled sum's order and integer arithmetic where fp32 F.linear was
+    move values across quantiser ties, so logits differ in their last digits.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -2744,6 +3010,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _swish_pass(gm, report, planned, dry_run, dwpw)
     if gates:           # (first: the squeeze's global pool is a plain node still, and so are the nodes behind the gate)
         _gate_pass(gm, report, planned, dry_run, relu6)
+    if squeezes:        # (behind the gate pass: the gate node keeps reading the value the squeeze node now returns; before the head pass, which would take a squeeze's pool in front of a 64-aligned Linear for a head)
+        _squeeze_pass(gm, report, planned, dry_run, weight_blob, pack_int4)
     if avg_pools:       # (before the head and the chain passes, like the head pass: the nodes behind the pool are plain plan nodes still)
         _avgpool_pass(gm, report, planned, dry_run)
     if patch_embed:     # (after the main pass, whose decision for the embedding stays; before the LayerNorm pass, which reads the token tensor)

@@ -974,6 +974,55 @@ int dlmcq_swish_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int
                          int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- the squeeze path of a squeeze-excite block: pooled activation codes [N, C] -> the fp32 gate [N, C], one launch ----
+ * Two int8 layers on rows with an activation between them and the gate function behind them; the hidden vector stays on the chip.
+ * For image n, hidden unit r (0 .. R4 - 1) and channel c (0 .. C - 1):
+ *     S1 = SUM_c (x[n, c] - zp1) * w1[r, c]                 exact in int32; zp1 = in_zero_point1 (an integer value; NULL = 0)
+ *     h  = fma(fl32(S1), fl32(in_scale1 * w_scale1[r]), bias1[r])      the rounding chain of dlmcq_conv2d_i8_nhwc_fused: ONE fused
+ *                                                           multiply-add (bias1 NULL: + 0)
+ *     h  = inner_act(h)     DLMCQ_SQUEEZE_NONE | DLMCQ_SQUEEZE_RELU: h < 0 ? 0 : h (NaN and -0 pass, as that entry point's ReLU) |
+ *                           DLMCQ_SQUEEZE_SWISH: e = expf(-h), d = fl32(1 + e), s = fl32(1 / d), h = fl32(h * s) (dlmcq_swish_nhwc_f32's steps)
+ *     hidden[n, r] = h
+ *     qh = the quantiser (q_scale .. q_ste_g, forms EMULATE / QBASE / ZEROPOINT / SYMMETRIC as in dlmcq_conv2d_i8_nhwc_fused) of h - the
+ *          code dlmcq_fake_quant_f32 gives for it; uint8 when q_lo >= 0, else int8
+ *     S2 = SUM_r (qh - zp2) * w2[c, r]                      exact in int32; zp2 = q_zero_point as an integer zero point (NULL = 0) in
+ *                                                           every form
+ *     v  = fma(fl32(S2), fl32(s_h * w_scale2[c]), bias2[c])  s_h = the scale the form dequantises with: QBASE (s - s g) + s g, else q_scale
+ *     gate[n, c] = gate_fn(v)   DLMCQ_GATE_NONE: v | DLMCQ_GATE_SIGMOID: e = expf(-v), d = fl32(1 + e), g = fl32(1 / d) - the accurate expf and
+ *                           a correctly rounded division | DLMCQ_GATE_HARDSIGMOID: t = fl32(v + 3); t = t > 0 ? t : (t is NaN ? t : +0);
+ *                           t = t > 6 ? 6 : t (relu6 as the device's clamp has it: NaN passes, -0 becomes +0); g = fl32(t * fl32(1 / 6)) -
+ *                           `F.relu6(v + 3) / 6` as the device evaluates it, where a division by a host scalar is a multiplication by
+ *                           its rounded reciprocal
+ * - every step rounded to fp32 by itself; no atomics, no scratch: the result depends neither on the launch geometry nor on the run.
+ * It is dlmcq_conv2d_i8_nhwc_fused (H = W = R = S = 1) on x, the activation, dlmcq_fake_quant_f32 and the same entry point again, bit
+ * for bit, for layers too narrow for that entry point's 64-channel step.
+ *   x          activation codes [N, C] (uint8 when x_is_unsigned, else int8), 4-byte aligned
+ *   w1, wsum1  int8 [R4, C] (16-byte aligned) and its row sums [R4]; w2, wsum2: int8 [C, R4] (16-byte aligned) and its row sums [C].
+ *              Symmetric weights.  R4 is the hidden width rounded up to a multiple of 4: the caller pads w1's rows, wsum1, bias1 and
+ *              w2's columns with 0 (and w_scale1 with anything finite); a padded unit's code is multiplied by 0.
+ *   bias1 [R4], bias2 [C] or NULL; in_scale1, in_zero_point1, q_scale, q_zero_point: device scalars; w_scale1 [R4], w_scale2 [C]
+ *   gate       fp32 [N, C], hidden fp32 [N, R4] (the values behind inner_act), each 16-byte aligned or NULL; one of them is required.
+ *              Without `gate` layer 2 is not computed.
+ * DLMCQ_EINVAL: N < 0, C < 4, C > DLMCQ_SQUEEZE_MAX_C, C % 4, R4 < 1, R4 > DLMCQ_SQUEEZE_MAX_R, R4 % 4, inner_act or gate_fn outside
+ * 0 .. 2; then an invalid quantiser (q_scale NULL included), any control or layout bit or DLMCQ_EMIT_SHIFT128 in q_form (refused, not
+ * stripped); then, unless N == 0 (DLMCQ_OK, nothing launched, null pointers included): both outputs NULL, a required input NULL.
+ * DLMCQ_EALIGN: w1 / w2 / gate / hidden not 16-byte aligned, any other pointer not 4-byte aligned.  DLMCQ_ERANGE: N * C or N * R4
+ * reaches 2^31.  A refused call writes nothing.  One workgroup computes DLMCQ_SQUEEZE_IMAGES images. */
+#define DLMCQ_SQUEEZE_MAX_C 2048
+#define DLMCQ_SQUEEZE_MAX_R 512
+#define DLMCQ_SQUEEZE_IMAGES 4
+#define DLMCQ_SQUEEZE_NONE 0
+#define DLMCQ_SQUEEZE_RELU 1
+#define DLMCQ_SQUEEZE_SWISH 2
+#define DLMCQ_GATE_NONE 0
+#define DLMCQ_GATE_SIGMOID 1
+#define DLMCQ_GATE_HARDSIGMOID 2
+int dlmcq_squeeze_gate_i8(const void* x, const int8_t* w1, const int32_t* wsum1, const float* bias1, const float* in_scale1,
+                          const float* in_zero_point1, const float* w_scale1, int32_t inner_act, const int8_t* w2, const int32_t* wsum2,
+                          const float* bias2, const float* w_scale2, int32_t gate_fn, float* gate, float* hidden, int64_t N, int64_t C,
+                          int64_t R4, int32_t x_is_unsigned, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 /* ---- GELU (erf form) 0.5 x (1 + erf(x / sqrt(2))): fp32 and / or the consumer's activation codes ----
  * For image n, pixel (h, w), channel c, with x = x[n, h, w, c] (dense rows [M, C]: N = M, H = W = 1):
  *     z = fl32(x * 0.70710678118654752440f)   one IEEE multiply by fl32(1 / sqrt(2))
