@@ -203,7 +203,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pipe_i8_kernel(
     if (XS) {
 #pragma unroll
       for (int jp = 0; jp < PB; ++jp)
-        pf[jp] = i32x4{(int)(pf[jp].x ^ xorw), (int)(pf[jp].y ^ xorw), (int)(pf[jp].z ^ xorw), (int)(pf[jp].w ^ xorw)};
+        pf[jp] = flip128(pf[jp], xorw);
     }
 #pragma unroll
     for (int jc = 0; jc < CB; ++jc)

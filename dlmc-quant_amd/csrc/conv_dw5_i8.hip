@@ -203,8 +203,7 @@ static void dw5_go(dim3 grid, size_t lds, const DwCall& c, const DwGeom& g) {
 }
 template <int FAST, bool R6>
 static hipError_t dw5_big_lds() {      // tables above 64 KB (C >= 1152): the kernel's dynamic LDS limit, raised once
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dw5_i8_kernel<FAST, R6>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             DW5_MAX_C / 16 * DW5_RUN * 16);
+  return allow_dyn_lds<conv_dw5_i8_kernel<FAST, R6>>(DW5_MAX_C / 16 * DW5_RUN * 16);
 }
 struct Dw5Variant {
   int fast;
@@ -264,13 +263,8 @@ extern "C" int dlmcq_conv2d_dw5_i8_nhwc(const void* x, const int8_t* w, float* o
   g.pdiv = make_fastdiv((uint32_t)c.P);
   const size_t lds = (size_t)(c.C / 16) * DW5_RUN * 16;
   if (lds > 64 * 1024) {
-    static bool raised[DW5_VARIANTS] = {};
-    bool& done = raised[v - DW5_TABLE];
-    if (!done) {
-      const hipError_t e = v->big_lds();
-      if (e != hipSuccess) return (int)e;
-      done = true;
-    }
+    const hipError_t e = v->big_lds();
+    if (e != hipSuccess) return (int)e;
   }
   const int64_t blocks = (c.N * c.P * c.Q * (c.C / 16) + DLMCQ_BLOCK - 1) / DLMCQ_BLOCK;
   v->go(dim3((uint32_t)(blocks < DW5_GRID ? blocks : DW5_GRID)), lds, c, g);

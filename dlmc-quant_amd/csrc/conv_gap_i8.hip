@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void conv_gap_i8_kernel(GapArgs a, ConvEpi ep)
       i32x4 bf[2] = {*reinterpret_cast<const i32x4*>(xrow + s), *reinterpret_cast<const i32x4*>(xrow + s + 32)};
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        bf[h] = i32x4{(int)(bf[h].x ^ xorw), (int)(bf[h].y ^ xorw), (int)(bf[h].z ^ xorw), (int)(bf[h].w ^ xorw)};
+        bf[h] = flip128(bf[h], xorw);
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
           const i32x4 af = *reinterpret_cast<const i32x4*>(wrow + j * 32 * WLD + s + h * 32);
@@ -155,15 +155,7 @@ static inline GapLaunch gap_launch_record(int64_t N, int C, int K, int cus) {
 
 template <int NT>
 static int gap_go(const GapArgs& a, const ConvEpi& ep, size_t lds, int nwg, hipStream_t st) {
-  auto kern = conv_gap_i8_kernel<NT>;
-  static size_t attr = 0;      // the largest dynamic LDS size the kernel has been allowed so far
-  if (lds > attr) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr = lds;
-  }
-  hipLaunchKernelGGL(kern, dim3((uint32_t)nwg), dim3(256), lds, st, a, ep);
-  return launch_status();
+  return launch_dyn_lds<conv_gap_i8_kernel<NT>>(dim3((uint32_t)nwg), dim3(256), lds, st, a, ep);
 }
 
 }  // namespace dlmcq

@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : DUAL ? (BN == 128 ? 2 : 4) : 
         const int arow = wrow0 + l31;
         t = *reinterpret_cast<const i32x4*>(base + arow * BK + ((sg_ ^ ((arow >> 2) & 3)) << 4));
       }
-      const i32x4 af = i32x4{(int)(t.x ^ xorw), (int)(t.y ^ xorw), (int)(t.z ^ xorw), (int)(t.w ^ xorw)};
+      const i32x4 af = flip128(t, xorw);
       if (ASYM) {    // SUM of the int8 operand over the reduction (v_dot4_i32_i8 with a vector of ones)
         s0 = __builtin_amdgcn_sdot4(af.x, 0x01010101, s0, false);
         s0 = __builtin_amdgcn_sdot4(af.y, 0x01010101, s0, false);

@@ -234,6 +234,37 @@ inline int device_cus() {
   return cus;
 }
 
+// The weight-resident 1 x 1 kernels (conv_pw_i8.hip, conv_pwr_i8.hip): workgroups per column slice - `wgs` resident workgroups shared
+// among the `nslice` slices, in whole eights (the workgroups of a group sit on one XCD and share their pixels), eight at least, and no
+// more than give every one of a workgroup's `nw` waves a 32-pixel block
+inline int resident_groups(int wgs, int nslice, int nblk, int nw) {
+  int ngroups = (wgs / nslice) & ~7;
+  if (ngroups < 8) ngroups = 8;
+  const int maxg = ((nblk + nw - 1) / nw + 7) & ~7;
+  return ngroups > maxg ? maxg : ngroups;
+}
+
+// Dynamic LDS beyond the default limit has to be allowed per kernel: one record per kernel instantiation (KERN) of the largest size
+// allowed so far, and the attribute is set when a launch first needs more.  (A workgroup's LDS is at most 160 KB: the size fits an int.)
+template <auto KERN>
+inline hipError_t allow_dyn_lds(size_t lds) {
+  static size_t allowed = 0;
+  if (lds > allowed) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+    allowed = lds;
+  }
+  return hipSuccess;
+}
+// Launch KERN with `lds` bytes of dynamic LDS, allowed first
+template <auto KERN, typename... Args>
+inline int launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  const hipError_t e = allow_dyn_lds<KERN>(lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(KERN, grid, block, lds, st, args...);
+  return launch_status();
+}
+
 // The kernel families conv_launch routes to.  `applies` answers for the whole record - the problem, the epilogue, the fp32 output and
 // the second pair - and `launch` may be called only where it said yes.
 // conv3x3_i8.hip: the halo-tile kernel for 3x3 / stride 1 or 2 / pad 1 layers that emit only their consumer's codes
@@ -314,6 +345,25 @@ int conv_dwm_table(int32_t* answers, int cap);                 // every instanti
 bool stem_pool7_applies(const StemCall& c);
 int stem_pool7_launch(const StemCall& c);
 bool stem_pool7_xs(const StemCall& c);     // which of its two instantiations (XS): read by the launch and by the route query
+
+// uint8 -> int8 on a 16-byte MFMA fragment (xorw = 0x80808080 where the codes are unsigned bytes, else 0)
+__host__ __device__ __forceinline__ i32x4 flip128(const i32x4& v, uint32_t xorw) {
+  return i32x4{(int)(v.x ^ xorw), (int)(v.y ^ xorw), (int)(v.z ^ xorw), (int)(v.w ^ xorw)};
+}
+
+// A lane's 16 accumulators start from (shift - zp) * SUM qw of their 16 consecutive channels out of an LDS table (`tab`: the first of
+// them): four LDS reads instead of sixteen additions per block
+__device__ __forceinline__ void acc_from_lds(i32x16& acc, const void* tab) {
+  const i32x4* cop = reinterpret_cast<const i32x4*>(tab);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const i32x4 c4 = cop[q];
+    acc[4 * q] = c4.x;
+    acc[4 * q + 1] = c4.y;
+    acc[4 * q + 2] = c4.z;
+    acc[4 * q + 3] = c4.w;
+  }
+}
 
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

@@ -151,28 +151,17 @@ __global__ __launch_bounds__(NW * 64, PW_WPS(C, BN)) void conv_pw_i8_kernel(PwAr
 #pragma unroll
     for (int f = 0; f < NA; ++f) {
       asm volatile("" : "+v"(areg[f]));     // the asm-loaded fragments are valid from here on
-      areg[f] = i32x4{(int)(areg[f].x ^ xorw), (int)(areg[f].y ^ xorw), (int)(areg[f].z ^ xorw), (int)(areg[f].w ^ xorw)};   // uint8 -> int8, once for all passes
+      areg[f] = flip128(areg[f], xorw);     // uint8 -> int8, once for all passes
     }
     f32x2 s0f2 = f32x2{0.0f, 0.0f};
     // NP passes over NTP accumulator blocks each (the fragments stay in registers; what a pass holds besides them is NTP x 16
     // accumulators and the epilogue's ~70 registers)
     static_for<NP>([&](auto p_c) {
       constexpr int p = decltype(p_c)::value;
-      // the accumulators start from (shift - zp) * SUM qw of their channels (register i of block j: channel 32 j + 16 hsel + i):
-      // four LDS reads instead of sixteen additions per block
+      // the accumulators start from (shift - zp) * SUM qw of their channels (register i of block j: channel 32 j + 16 hsel + i)
       i32x16 acc[NTP];
 #pragma unroll
-      for (int j = 0; j < NTP; ++j) {
-        const i32x4* cop = reinterpret_cast<const i32x4*>(par + (BN + (p * NTP + j) * 32 + hsel * 16) * 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const i32x4 c4 = cop[q];
-          acc[j][4 * q] = c4.x;
-          acc[j][4 * q + 1] = c4.y;
-          acc[j][4 * q + 2] = c4.z;
-          acc[j][4 * q + 3] = c4.w;
-        }
-      }
+      for (int j = 0; j < NTP; ++j) acc_from_lds(acc[j], par + (BN + (p * NTP + j) * 32 + hsel * 16) * 4);
       int s0 = 0;
       static_for<NA>([&](auto f_c) {
         constexpr int f = decltype(f_c)::value;
@@ -314,28 +303,9 @@ static int pw_go(const PwArgs& a0, const ConvEpi& ep, hipStream_t st) {
   static_assert(LDS <= 160 * 1024, "LDS");
   PwArgs a = a0;
   a.nslice = a.K / BN;
-  static int cus = 0;      // (one device per process: dlmc/_native.py)
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-              ? prop.multiProcessorCount : 256;
-  }
-  const int wgs = cus * (BIGWG ? 1 : WPS);
-  int ngroups = (wgs / a.nslice) & ~7;                            // groups of `nslice` workgroups on one XCD share their pixels
-  if (ngroups < 8) ngroups = 8;
-  const int maxg = ((a.nblk + NW - 1) / NW + 7) & ~7;
-  if (ngroups > maxg) ngroups = maxg;
+  const int ngroups = resident_groups(device_cus() * (BIGWG ? 1 : WPS), a.nslice, a.nblk, NW);
   constexpr int NTP = BN == 192 ? 3 : (C >= 512 ? 1 : 2);      // (64-wide slices: one pass of two blocks)
-  auto kern = conv_pw_i8_kernel<C, BN, NTP, ASYM, NW, LAB, R6>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((uint32_t)(ngroups * a.nslice)), dim3(NW * 64), LDS, st, a, ep);
-  return launch_status();
+  return launch_dyn_lds<conv_pw_i8_kernel<C, BN, NTP, ASYM, NW, LAB, R6>>(dim3((uint32_t)(ngroups * a.nslice)), dim3(NW * 64), LDS, st, a, ep);
 }
 
 // Which instantiation conv_pw_launch runs for a call conv_pw_applies took, computed ONCE: the launch and the route query

@@ -191,13 +191,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_pwr_i8_kernel(PwrArgs a,
 #pragma unroll
     for (int f = 0; f < NA; ++f) {
       asm volatile("" : "+v"(areg[f]));     // the asm-loaded fragments are valid from here on
-      areg[f] = i32x4{(int)(areg[f].x ^ xorw), (int)(areg[f].y ^ xorw), (int)(areg[f].z ^ xorw), (int)(areg[f].w ^ xorw)};   // uint8 -> int8, once for all passes
+      areg[f] = flip128(areg[f], xorw);     // uint8 -> int8, once for all passes
     }
     if constexpr (!RES) {
 #pragma unroll
       for (int f = 0; f < NA2; ++f) {
         asm volatile("" : "+v"(areg2[f]));
-        areg2[f] = i32x4{(int)(areg2[f].x ^ xorw2), (int)(areg2[f].y ^ xorw2), (int)(areg2[f].z ^ xorw2), (int)(areg2[f].w ^ xorw2)};
+        areg2[f] = flip128(areg2[f], xorw2);
       }
     }
     const int vb = fbase(blk);                 // this block's fp32 rows
@@ -214,15 +214,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_pwr_i8_kernel(PwrArgs a,
       f32x2 ex[RES ? 1 : 8];
       if constexpr (!RES) {
         i32x16 acc2;
-        const i32x4* cop = reinterpret_cast<const i32x4*>(par + (4 * BN + p * 32 + hsel * 16) * 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const i32x4 c4 = cop[q];
-          acc2[4 * q] = c4.x;
-          acc2[4 * q + 1] = c4.y;
-          acc2[4 * q + 2] = c4.z;
-          acc2[4 * q + 3] = c4.w;
-        }
+        acc_from_lds(acc2, par + (4 * BN + p * 32 + hsel * 16) * 4);
         static_for<NA2>([&](auto f_c) {
           constexpr int f = decltype(f_c)::value;
           constexpr int s = f >> 1, ks = f & 1;
@@ -242,17 +234,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv_pwr_i8_kernel(PwrArgs a,
       }
       // the accumulators start from (shift - zp) * SUM qw of their channels (register i: channel 32 p + 16 hsel + i)
       i32x16 acc;
-      {
-        const i32x4* cop = reinterpret_cast<const i32x4*>(par + (BN + p * 32 + hsel * 16) * 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const i32x4 c4 = cop[q];
-          acc[4 * q] = c4.x;
-          acc[4 * q + 1] = c4.y;
-          acc[4 * q + 2] = c4.z;
-          acc[4 * q + 3] = c4.w;
-        }
-      }
+      acc_from_lds(acc, par + (BN + p * 32 + hsel * 16) * 4);
       static_for<NA>([&](auto f_c) {
         constexpr int f = decltype(f_c)::value;
         constexpr int s = f >> 1, ks = f & 1;
@@ -355,26 +337,8 @@ static int pwr_go(const PwrArgs& a0, const ConvEpi& ep, hipStream_t st) {
   static_assert(LDS <= 160 * 1024, "LDS");
   PwrArgs a = a0;
   a.nslice = a.K / PWR_BN;
-  static int cus = 0;      // (one device per process: dlmc/_native.py)
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-              ? prop.multiProcessorCount : 256;
-  }
-  int ngroups = (cus / a.nslice) & ~7;                            // one workgroup per CU; groups of `nslice` workgroups on one XCD share their pixels
-  if (ngroups < 8) ngroups = 8;
-  const int maxg = ((a.nblk + NW - 1) / NW + 7) & ~7;
-  if (ngroups > maxg) ngroups = maxg;
-  auto kern = conv_pwr_i8_kernel<C, NW, OUTF, CODES, C2, SWP>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((uint32_t)(ngroups * a.nslice)), dim3(NW * 64), LDS, st, a, ep);
-  return launch_status();
+  const int ngroups = resident_groups(device_cus(), a.nslice, a.nblk, NW);      // one workgroup per CU
+  return launch_dyn_lds<conv_pwr_i8_kernel<C, NW, OUTF, CODES, C2, SWP>>(dim3((uint32_t)(ngroups * a.nslice)), dim3(NW * 64), LDS, st, a, ep);
 }
 
 // Which instantiation conv_pwr_launch runs for a call conv_pwr_applies took, computed ONCE: the launch and the route query

@@ -251,15 +251,7 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if constexpr (SWAP) {      // the accumulators start from the zero-point term of their channels (four LDS reads instead of 16 additions)
-        const i32x4* cop = reinterpret_cast<const i32x4*>(ctab + 64 + j * 32 + hsel * 16);
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const i32x4 c4 = cop[q4];
-          acc[j][4 * q4] = c4.x;
-          acc[j][4 * q4 + 1] = c4.y;
-          acc[j][4 * q4 + 2] = c4.z;
-          acc[j][4 * q4 + 3] = c4.w;
-        }
+        acc_from_lds(acc[j], ctab + 64 + j * 32 + hsel * 16);
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[j][i] = 0;
@@ -268,7 +260,7 @@ __global__ __launch_bounds__(256) void conv_stem_i8_kernel(const uint8_t* __rest
     int s0 = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const i32x4 a = i32x4{(int)(af[r].x ^ xorw), (int)(af[r].y ^ xorw), (int)(af[r].z ^ xorw), (int)(af[r].w ^ xorw)};
+      const i32x4 a = flip128(af[r], xorw);
       if (ASYM) {
         s0 = __builtin_amdgcn_sdot4(a.x, maskw[0], s0, false);
         s0 = __builtin_amdgcn_sdot4(a.y, maskw[1], s0, false);
@@ -494,7 +486,7 @@ __global__ __launch_bounds__(256, 3) void conv_stem_pool_i8_kernel(const uint8_t
       for (int i = 0; i < 16; ++i) acc[j][i] = 0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const i32x4 a = i32x4{(int)(af[b][r].x ^ xorw), (int)(af[b][r].y ^ xorw), (int)(af[b][r].z ^ xorw), (int)(af[b][r].w ^ xorw)};
+      const i32x4 a = flip128(af[b][r], xorw);
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bfp[(r * 64 + j * 32) * 2], acc[j], 0, 0, 0);
     }

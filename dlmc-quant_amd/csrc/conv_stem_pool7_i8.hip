@@ -225,8 +225,8 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool7_i8_kernel(const uint8_
       i32x4 o2 = o, e2 = e, v0 = w0, v1 = w1;
       if (r + 1 < 7) fetch(r + 1, o2, e2, v0, v1);
       __builtin_amdgcn_sched_barrier(0);
-      const i32x4 ox = XS ? i32x4{(int)(o.x ^ xorw), (int)(o.y ^ xorw), (int)(o.z ^ xorw), (int)(o.w ^ xorw)} : o;
-      const i32x4 ex = XS ? i32x4{(int)(e.x ^ xorw), (int)(e.y ^ xorw), (int)(e.z ^ xorw), (int)(e.w ^ xorw)} : e;
+      const i32x4 ox = XS ? flip128(o, xorw) : o;
+      const i32x4 ex = XS ? flip128(e, xorw) : e;
       aE[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w0, ex, r == 0 ? zero16 : aE[0], 0, 0, 0);
       aO[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w0, ox, r == 0 ? zero16 : aO[0], 0, 0, 0);
       aE[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(w1, ex, r == 0 ? zero16 : aE[1], 0, 0, 0);
