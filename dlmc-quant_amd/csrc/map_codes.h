@@ -1,4 +1,4 @@
-// What the map-to-codes kernels (avgpool.hip, gate.hip, swish.hip) share: one read of an fp32 NHWC map, the op's own
+// What the map-to-codes kernels (avgpool.hip, gate.hip, swish.hip, hardswish.hip) share: one read of an fp32 NHWC map, the op's own
 // value per element, then fp32 [N, P, Q, C] and / or the consumer's activation codes [N, P, Q, c_pad].  Not part of the ABI.
 // One thread per (output pixel, 4 channels of the code row): one optional float4 store, four code bytes as one 32-bit word.  No LDS, no
 // atomics, no scratch: the result depends neither on the launch geometry nor on the run.  Input rows may be wider than the data

@@ -55,7 +55,8 @@ ROUTE_TAG = {ROUTE_TILED: "conv_i8", ROUTE_HALO3X3: "conv3x3_halo", ROUTE_PW: "c
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2   # DLMCQ_ACT_*: the `relu` argument of the fused convolution entry points
 SQUEEZE_NONE, SQUEEZE_RELU, SQUEEZE_SWISH = 0, 1, 2   # DLMCQ_SQUEEZE_*: dlmcq_squeeze_gate_i8's activation between its two layers
 GATE_NONE, GATE_SIGMOID, GATE_HARDSIGMOID = 0, 1, 2   # DLMCQ_GATE_*: ... and its gate function
-SQUEEZE_MAX_C, SQUEEZE_MAX_R, SQUEEZE_IMAGES = 2048, 512, 4   # DLMCQ_SQUEEZE_MAX_C / _MAX_R / _IMAGES
+HSWISH_MUL_FIRST, HSWISH_GATE_FIRST = 0, 1   # DLMCQ_HSWISH_*: dlmcq_hardswish_nhwc_f32's order of the two multiplies
+SQUEEZE_MAX_C, SQUEEZE_MAX_R, SQUEEZE_IMAGES = 2048, 512, 4  # DLMCQ_SQUEEZE_MAX_C / _MAX_R / _IMAGES
 Y_DEQUANT, Y_CODES = 0, 1
 CODES_NONE, CODES_I8, CODES_P4 = 0, 1, 2
 MINMAX_ABSMAX, MINMAX_MINMAX, MINMAX_NEGMIN = 0, 1, 2
@@ -157,6 +158,7 @@ SIGNATURES = {
     "dlmcq_avgpool_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_gate_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_swish_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_hardswish_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _i32, _p]),
     "dlmcq_squeeze_gate_i8": (ctypes.c_int, [_p] * 7 + [_i32] + [_p] * 4 + [_i32, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_gelu_nhwc_f32": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_layernorm_rows_f32": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _f32, _p, _p, _i32, _i32, _i32, _f32, _p]),

@@ -17,7 +17,7 @@ from ..._native import (CODES_I8, CODES_NONE, CODES_P4, FORM_EMULATE, FORM_QBASE
                         Y_CODES, Y_DEQUANT)
 
 __all__ = ["fake_quant", "dequant_codes", "dequant", "minmax", "observe_qparams", "qparams_from_minmax",
-           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "squeeze_gate", "squeeze_gate_torch", "squeeze_gate_supported", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "patch_rows_quant", "patch_rows_view", "patch_rows_torch", "PATCH_MAX_STRIP", "assemble_tokens", "tokens_view", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
+           "span_scale", "lsq_init", "l2norm_step", "adaround_weight", "adaround_weight_backward", "quantize_weight_krsc", "conv2d_i8", "global_avgpool", "avgpool_quant", "gate_quant", "swish_quant", "hardswish_quant", "squeeze_gate", "squeeze_gate_torch", "squeeze_gate_supported", "gelu_quant", "layernorm_quant", "LAYERNORM_MAX_C", "patch_rows_quant", "patch_rows_view", "patch_rows_torch", "PATCH_MAX_STRIP", "assemble_tokens", "tokens_view", "attention_quant", "attention_views", "ATTENTION_DIMS", "conv2d_i8_gap", "gap_head_supported", "gap_head_profitable", "pack_int4", "unpack_int4", "fake_quant_backward", "Segment", "FqMultiPlan", "fake_quant_multi", "fake_quant_multi_backward", "rootq_weight", "geometry", "channel_shape",
            "PROFILE"]
 
 
@@ -1289,6 +1289,25 @@ def swish_quant(x, emit=None, want_out=True, c_pad=None, pad_code=0):
     n, c, h, w_ = _fp32_map("swish_quant", x)
     return _map_codes("swish_quant", x, h, w_, emit, want_out, c_pad, pad_code, "swish", n * h * w_ * c * 4,
                       lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_swish_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail))
+
+
+HARDSWISH_ORDERS = {"mul_first": N.HSWISH_MUL_FIRST, "gate_first": N.HSWISH_GATE_FIRST}
+
+
+def hardswish_quant(x, order="mul_first", emit=None, want_out=True, c_pad=None, pad_code=0):
+    """Hard swish `x * relu6(x + 3) / 6` of an fp32 (N, C, H, W) map, C % 4 == 0, by dlmcq_hardswish_nhwc_f32: t = x + 3, r = relu6(t),
+    c = fl32(1 / 6), then `order="mul_first"`: v = (x * r) * c - nn.Hardswish, F.hardswish, `x * F.relu6(x + 3) / 6` - or
+    `order="gate_first"`: v = x * (r * c) - `x * (F.relu6(x + 3) / 6)`, `x * F.hardsigmoid(x)` - each step rounded to fp32.  Returns
+    `(out or None, codes or None)`: fp32 (N, C, H, W) and the consumer's activation codes of the activated values; the inputs read in
+    place, `emit`, `want_out`, `c_pad` and `pad_code` as _map_codes says."""
+    N.require_gpu(x)
+    n, c, h, w_ = _fp32_map("hardswish_quant", x)
+    if order not in HARDSWISH_ORDERS:
+        raise ValueError(f"hardswish_quant: order is 'mul_first' or 'gate_first', not {order!r}")
+    o = HARDSWISH_ORDERS[order]
+    return _map_codes("hardswish_quant", x, h, w_, emit, want_out, c_pad, pad_code, "hardswish", n * h * w_ * c * 4,
+                      lambda xp, op, cp, xs, cpad, pad, *tail: N.lib.dlmcq_hardswish_nhwc_f32(xp, op, cp, n, h, w_, c, xs, cpad, pad, *tail[:-1],
+                                                                                              o, tail[-1]))
 
 
 SQUEEZE_ACTS = {None: N.SQUEEZE_NONE, "none": N.SQUEEZE_NONE, "relu": N.SQUEEZE_RELU, "swish": N.SQUEEZE_SWISH}

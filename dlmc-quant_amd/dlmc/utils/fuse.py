@@ -35,7 +35,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SqueezeLayer", "SwishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SqueezeLayer", "SwishLayer", "HardswishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -900,8 +900,8 @@ class GapHeadLayer(nn.Module):
 
 
 class _MapCodesLayer(nn.Module):
-    """What the plan nodes that read an fp32 map once and hand its readers activation codes share (AvgPoolLayer, GateLayer, SwishLayer;
-    csrc/map_codes.h).  `emit`: the readers' activation quantiser (_ActSpec); `want_out`: whether anyone reads the fp32 values; the code
+    """What the plan nodes that read an fp32 map once and hand its readers activation codes share (AvgPoolLayer, GateLayer, SwishLayer,
+    HardswishLayer; csrc/map_codes.h).  `emit`: the readers' activation quantiser (_ActSpec); `want_out`: whether anyone reads the fp32 values; the code
     rows are `c_pad` wide with `pad_code` behind the `c` real channels - what Int8Layer._codes / _pad_channels build from the fp32
     tensor; `shift`: the codes are stored as `code - 128`."""
 
@@ -1173,6 +1173,8 @@ def _gate_pass(gm, report, planned, dry_run, relu6):
     def match(mul, modules):
         if not _is_mul(mul) or mul.args[0] is mul.args[1] or _swish_of(mul, modules) is not None:      # (x * sigmoid(x): no gate)
             return None
+        if _hardswish_multiply(mul, modules):      # (x * hardsigmoid(x), x * relu6(x + 3): no gate either)
+            return None
         a, b = mul.args
         # exactly one operand derives from a global average pool, and that pool reads the other operand
         gated = [(x, g) for x, g in ((a, b), (b, a)) if _squeezed_from(g, modules) is x]
@@ -1279,6 +1281,162 @@ def _swish_pass(gm, report, planned, dry_run, dwpw):
             taken = _CodeReaders(None, (), True, None, None, 0, False)
         return _Splice(SwishLayer, _decided(taken), node, (x,), taken.takers, nodes)
     _run_node_pass(gm, report, "swish", "swishes", match, dry_run)
+
+
+# ------------------------------------------------------------------ hard swish x * relu6(x + 3) / 6
+# The spellings _hardswish_of takes -> the order of csrc/hardswish.hip's two multiplies that computes the spelling's own values, and the
+# spelling again in torch (HardswishLayer._unfused).  "mul_*": (x * r) / 6 or (x * r) * (1 / 6); "gate_*": x * (r / 6) or x * (r * (1 / 6)),
+# r = relu6(x + 3); "hardsigmoid": x * hardsigmoid(x).
+_HARDSWISH_ORDER = {"hardswish": "mul_first", "mul_div": "mul_first", "mul_mul": "mul_first",
+                    "gate_div": "gate_first", "gate_mul": "gate_first", "hardsigmoid": "gate_first"}
+_HARDSWISH_TORCH = {"hardswish": F.hardswish,
+                    "mul_div": lambda x: x * F.relu6(x + 3.0) / 6.0,
+                    "mul_mul": lambda x: x * F.relu6(x + 3.0) * (1.0 / 6.0),
+                    "gate_div": lambda x: x * (F.relu6(x + 3.0) / 6.0),
+                    "gate_mul": lambda x: x * (F.relu6(x + 3.0) * (1.0 / 6.0)),
+                    "hardsigmoid": lambda x: x * F.hardsigmoid(x)}
+# What _hardswish_pass decides for one node: the graph value it activates, the spelling it replaces, the kernel's order, the nodes it
+# replaces (names).
+_HardswishDecision = collections.namedtuple("_HardswishDecision", "x spelling order chain")
+
+
+class HardswishLayer(_MapCodesLayer):
+    """Hard swish `x * relu6(x + 3) / 6` of an fp32 (N, C, H, W) map straight to the activation codes of the plan layers that read the
+    activated map (csrc/hardswish.hip): the add, the clamp, the multiplies, the activated fp32 tensor and the consumer's quantise pass
+    as one read of the map.  `order`: "mul_first" ((x * r) * fl32(1 / 6): nn.Hardswish's) or "gate_first" (x * (r * fl32(1 / 6)):
+    x * hardsigmoid(x)'s) - the order of the spelling the node replaces; `decision`: the pass's record (_HardswishDecision), None for a
+    node built by hand, which then restates nn.Hardswish or x * hardsigmoid(x).  `emit`: None where nobody takes codes (the map is then
+    activated in one pass, and always written); `c`, `c_pad`: None where no reader fixes them.  An input that at run time is no 4-D fp32
+    device map of `c` channels (a multiple of 4) is activated with the torch ops of the spelling that was matched and quantised with
+    K.fake_quant: the values of the unfused graph.  Returns `(fp32 or None, codes or None)`."""
+
+    def __init__(self, emit, want_out, c, c_pad, pad_code, shift=False, order="mul_first", decision=None):
+        super().__init__(emit, want_out or emit is None, c or 0, c_pad or 0, pad_code, shift)
+        self.c, self.c_pad = (None if c is None else self.c), (None if c_pad is None else self.c_pad)
+        if order not in K.HARDSWISH_ORDERS:
+            raise ValueError(f"HardswishLayer: order is 'mul_first' or 'gate_first', not {order!r}")
+        if decision is not None and _HARDSWISH_ORDER[decision.spelling] != order:
+            raise ValueError(f"HardswishLayer: the spelling {decision.spelling!r} is computed {_HARDSWISH_ORDER[decision.spelling]}, not {order}")
+        self.order = order
+        self.spelling = decision.spelling if decision is not None else ("hardswish" if order == "mul_first" else "hardsigmoid")
+        if decision is not None:
+            self.decision = decision
+
+    def forward(self, x):
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != (x.shape[1] if self.c is None else self.c) or x.shape[1] % 4 or not x.is_cuda:
+            return self._unfused(x)
+        if self.emit is None:
+            return K.hardswish_quant(x, self.order)
+        return K.hardswish_quant(x, self.order, **self._to_codes(x.numel()))      # (the activated tensor)
+
+    def _unfused(self, x):
+        v = _HARDSWISH_TORCH[self.spelling](x)
+        return (v, None) if self.emit is None else self._torch_codes(v)
+
+
+def _is_number(v, k):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and float(v) == k
+
+
+def _relu6_of_plus3(r6, modules):
+    """(x, [r6, add]) if `r6` is relu6(x + 3) - a ReLU6 in a spelling _is_relu6 knows, of `x + 3` / `3 + x` / torch.add / x.add with the
+    addend exactly 3, that sum read by the ReLU6 alone - else None."""
+    if not isinstance(r6, fx.Node) or not _is_relu6(r6, modules) or not r6.args:
+        return None
+    add = r6.args[0]
+    if not (_is_call(add, (operator.add, torch.add), "add") and len(add.args) == 2 and len(add.users) == 1):
+        return None
+    for x, k in (add.args, add.args[::-1]):
+        if isinstance(x, fx.Node) and _is_number(k, 3.0):
+            return x, [r6, add]
+    return None
+
+
+def _sixth_of(node, src):
+    """"div" if `node` is `src / 6`, "mul" if it is `src * (1 / 6)` (either operand first) - the divisor exactly 6, the factor exactly the
+    double 1 / 6 - else None."""
+    if _is_call(node, _DIV_FNS, "div") and len(node.args) == 2 and node.args[0] is src and _is_number(node.args[1], 6.0):
+        return "div"
+    if _is_call(node, _MUL_FNS, "mul") and len(node.args) == 2:
+        if any(a is src and _is_number(b, 1.0 / 6.0) for a, b in (node.args, node.args[::-1])):
+            return "mul"
+    return None
+
+
+def _hardswish_of(node, modules):
+    """(x, the nodes that compute it, the spelling) if `node` is the hard swish of graph value x in a spelling the plan takes, else None:
+    nn.Hardswish (an inplace one only where nothing else reads x); F.hardswish(x), not in place; `(x * r) / 6` and `x * (r / 6)` with
+    r = relu6(x + 3) spelled out - the addend exactly 3, the ReLU6 any spelling _is_relu6 knows, the divisor exactly 6 or the factor
+    exactly 1 / 6, the multiplies with either operand first, each intermediate read by the next node alone; `x * F.hardsigmoid(x)` /
+    `x * nn.Hardsigmoid()(x)`, not in place, the gate read by that multiply alone.  A user module whose body is one of these is traced
+    into it.  `x * hardsigmoid(y)`, a squeeze-excite gate `x * hardsigmoid(f(pool(x)))`, `+ 2` and `/ 5` are none of them."""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        x = node.args[0] if len(node.args) == 1 and not node.kwargs else None
+        ok = type(m) is nn.Hardswish and isinstance(x, fx.Node) and (not m.inplace or len(x.users) == 1)
+        return (x, [node], "hardswish") if ok else None
+    if node.op == "call_function" and node.target is F.hardswish:
+        ok = len(node.args) == 1 and isinstance(node.args[0], fx.Node) and set(node.kwargs) <= {"inplace"} and not node.kwargs.get("inplace", False)
+        return (node.args[0], [node], "hardswish") if ok else None
+    if not isinstance(node, fx.Node) or node.kwargs or len(node.args) != 2:
+        return None
+    # (x * r) / 6, (x * r) * (1 / 6): `node` scales the product
+    for mul in node.args:
+        if _is_mul(mul) and mul.args[0] is not mul.args[1] and len(mul.users) == 1 and _sixth_of(node, mul) is not None:
+            for x, r in (mul.args, mul.args[::-1]):
+                found = _relu6_of_plus3(r, modules) if len(r.users) == 1 else None
+                if found is not None and found[0] is x:
+                    return x, [node, mul] + found[1], "mul_" + _sixth_of(node, mul)
+    if not _is_mul(node) or node.args[0] is node.args[1]:
+        return None
+    # x * (r / 6), x * (r * (1 / 6)), x * hardsigmoid(x): `node` multiplies x by its gate
+    for x, g in (node.args, node.args[::-1]):
+        if len(g.users) != 1:
+            continue
+        if g.op == "call_module":
+            m = modules.get(g.target)
+            if type(m) is nn.Hardsigmoid and not m.inplace and len(g.args) == 1 and not g.kwargs and g.args[0] is x:
+                return x, [node, g], "hardsigmoid"
+        elif g.op == "call_function" and g.target is F.hardsigmoid:
+            if len(g.args) == 1 and g.args[0] is x and set(g.kwargs) <= {"inplace"} and not g.kwargs.get("inplace", False):
+                return x, [node, g], "hardsigmoid"
+        elif not g.kwargs and len(g.args) == 2:
+            for r in g.args:
+                found = _relu6_of_plus3(r, modules) if isinstance(r, fx.Node) and len(r.users) == 1 and _sixth_of(g, r) is not None else None
+                if found is not None and found[0] is x:
+                    return x, [node, g] + found[1], "gate_" + _sixth_of(g, r)
+    return None
+
+
+def _hardswish_multiply(mul, modules):
+    """Whether multiply `mul` is part of a hard swish _hardswish_of takes: its last node, or the product `x * r` its scaling reads."""
+    if _hardswish_of(mul, modules) is not None:
+        return True
+    nxt = _sole_user(mul)
+    found = _hardswish_of(nxt, modules) if nxt is not None else None
+    return found is not None and mul in found[1]
+
+
+def _hardswish_pass(gm, report, planned, dry_run, dwpw):
+    """Hard-swish activations (fuse_inference(hardswish=True)): nn.Hardswish / `x * relu6(x + 3) / 6` / `x * hardsigmoid(x)` of a 4-D map
+    becomes a node (HardswishLayer) that hands the plan convolutions behind it - depthwise ones included - their activation codes and
+    every other reader (a squeeze-excite pool, the gate node, a shortcut add) the activated fp32 map from the same launch, computed in
+    the order of the spelling it replaces.  Readers and the no-taker case: _swish_pass's.  `planned`: plan node -> what the main pass
+    decided for it (_Decision); whatever that is for the convolution behind the hard swish stays - only its input changes."""
+    def match(node, modules):
+        found = _hardswish_of(node, modules)
+        if found is None:
+            return None
+        x, nodes, spelling = found
+        taken = _code_readers(planned, node, dw=True, dwpw=dwpw)
+        if taken is None:      # nobody takes codes: one pass over the map instead of four, where it is known to be a map
+            if not _is_map(x, planned, modules):
+                return None
+            taken = _CodeReaders(None, (), True, None, None, 0, False)
+        order = _HARDSWISH_ORDER[spelling]
+        dec = _HardswishDecision(x.name, spelling, order, tuple(n.name for n in nodes))
+        return _Splice(HardswishLayer, dict(_decided(taken), order=order, decision=dec), node, (x,), taken.takers, nodes)
+    _run_node_pass(gm, report, "hardswish", "hardswishes", match, dry_run)
 
 
 class LayerNormLayer(_MapCodesLayer):
@@ -2220,6 +2378,7 @@ class FusionReport:
         self.squeezes = 0     # squeeze paths (pool, two small layers, gate function) running as two launches (fuse_inference(squeezes=True))
         self.squeeze_left = []   # (pool node, why): squeeze paths the squeeze pass recognised and left as they are
         self.swishes = 0      # swish / SiLU activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(swish=True))
+        self.hardswishes = 0  # hard-swish activations of 4-D maps handing the plan layers behind them their codes (fuse_inference(hardswish=True))
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
         self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
@@ -2257,6 +2416,7 @@ class FusionReport:
                 (f"gates on the plan={self.gates}, " if self.gates else "") +
                 (f"squeezes on the plan={self.squeezes}, " if self.squeezes else "") +
                 (f"swishes on the plan={self.swishes}, " if self.swishes else "") +
+                (f"hard swishes on the plan={self.hardswishes}, " if self.hardswishes else "") +
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
                 (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
@@ -2802,7 +2962,7 @@ class _MainPass:
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
                    recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False,
-                   patch_embed=False, squeezes=False):
+                   patch_embed=False, squeezes=False, hardswish=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -2987,7 +3147,25 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     weights, more than 2048 channels or 512 hidden units, a plan built with `weight_blob`, 4-bit weights under `pack_int4`.  Runs behind
     the gate pass, which therefore takes every gate it took.  The two layers compute dlmcq_conv2d_i8_nhwc_fused's values bit for bit
     (tests/test_gpu_squeeze.py); against the plan without the flag the pooled sum's order and integer arithmetic where fp32 F.linear was
-    move values across quantiser ties, so logits differ in their last digits.  Off by default: the plan without it is the plan as it was."""
+    move values across quantiser ties, so logits differ in their last digits.  Off by default: the plan without it is the plan as it was.
+    `hardswish=True`: hard swish `x * relu6(x + 3) / 6` of a 4-D map - MobileNetV3's activation
+    (`workloads.mobilenet_v3_large()`, `mobilenet_v3_small()`) - becomes a plan node (HardswishLayer, csrc/hardswish.hip) that hands the
+    plan convolutions behind it, depthwise ones included, their activation codes in one pass and every other reader (a squeeze-excite
+    pool, the gate node, a shortcut add) the activated fp32 map from the same launch (`fusion_report.hardswishes` counts the nodes).
+    Taken: nn.Hardswish (an inplace one only where nothing else reads its input); F.hardswish, not in place; the spelled-out
+    `x * relu6(x + 3) / 6` and `x * (relu6(x + 3) / 6)` - the addend exactly 3, F.relu6 / nn.ReLU6 / F.hardtanh(., 0, 6), `/ 6` or
+    `* (1 / 6)`, either operand first, each intermediate read by the next node alone; `x * F.hardsigmoid(x)` / `x * nn.Hardsigmoid()(x)`;
+    a user module whose body is one of these.  The two multiplies round differently in about a quarter of the elements, so the node
+    computes them in the order of the spelling it replaces (`.order`, `.decision`): (x * r) * fl32(1 / 6) for nn.Hardswish, F.hardswish
+    and `(x * r) / 6`, x * (r * fl32(1 / 6)) for `x * (r / 6)` and `x * hardsigmoid(x)` - bit-identical to those ops on the device, so
+    the plan's logits equal the flag-off plan's (tests/test_hardswish_gpu.py).  The readers and the no-taker case are the swish pass's.
+    Left as they are: the hard swish on the (N, hidden) vector of the classifier or inside a squeeze path, `x * hardsigmoid(y)`, a
+    squeeze-excite gate, F.hardswish(inplace=True), another addend or divisor, an intermediate with a second reader.  An input that at
+    run time is no 4-D fp32 map of the planned width takes the node's torch path: the spelling that was matched.  The pass runs beside
+    the swish pass, before the gate pass.  Measured (tools/hardswish_ab.py, profiles/hardswish_ab.json; batch 256 at 224^2, gates and dw5
+    on in both, interleaved): MobileNetV3-Large flag off / on = 6.61 / 5.17 ms per step (FSPTQ W8A8), 6.56 / 5.15 (QBase W8A8), beyond the
+    run-to-run spread; MobileNetV3-Small 3.69 / 3.78 and 3.34 / 3.32, inside it; logits equal in all four.  Off by default: the plan
+    without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -3008,6 +3186,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     planned = _MainPass(gm, dry_run, weight_blob, dwpw, relu6, act_offsets, narrow_rows, pad_shortcuts, dw5).run(report)
     if swish:           # (before the gate pass, which finds its gated map and the squeeze's pool behind a swish node's fp32 output)
         _swish_pass(gm, report, planned, dry_run, dwpw)
+    if hardswish:       # (beside the swish pass and before the gate pass, for the same reason)
+        _hardswish_pass(gm, report, planned, dry_run, dwpw)
     if gates:           # (first: the squeeze's global pool is a plain node still, and so are the nodes behind the gate)
         _gate_pass(gm, report, planned, dry_run, relu6)
     if squeezes:        # (behind the gate pass: the gate node keeps reading the value the squeeze node now returns; before the head pass, which would take a squeeze's pool in front of a 64-aligned Linear for a head)

@@ -217,12 +217,13 @@ class Swish(nn.Module):
 
 
 def _conv_bn_act(cin, cout, k, stride=1, groups=1, act="relu6"):
-    """_conv_bn_relu6, the activation `act`: "relu6" (that very block) or "swish"."""
+    """_conv_bn_relu6, the activation `act`: "relu6" (that very block), "swish", "relu" or "hardswish" (nn.Hardswish: MobileNetV3's)."""
     if act == "relu6":
         return _conv_bn_relu6(cin, cout, k, stride, groups)
-    if act != "swish":
-        raise ValueError(f"activation 'relu6' or 'swish', not {act!r}")
-    return nn.Sequential(nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout), Swish())
+    if act not in ("swish", "relu", "hardswish"):
+        raise ValueError(f"activation 'relu6', 'swish', 'relu' or 'hardswish', not {act!r}")
+    fn = Swish() if act == "swish" else (nn.ReLU(inplace=True) if act == "relu" else nn.Hardswish())
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout), fn)
 
 
 class SqueezeExcite(nn.Module):
@@ -308,6 +309,58 @@ class EfficientNetB0(MobileNetV2):
     padding 2 carried by the convolution (torchvision's and timm's spelling; not the reference's F.pad in front of an unpadded one)."""
 
     SETTINGS = ((1, 16, 1, 1, 3), (6, 24, 2, 2, 3), (6, 40, 2, 2, 5), (6, 80, 3, 2, 3), (6, 112, 3, 1, 5), (6, 192, 4, 2, 5), (6, 320, 1, 1, 3))
+
+
+class MobileNetV3Block(nn.Module):
+    """MobileNetV3's unit (Howard et al. 2019): 1x1 expansion to `expanded` channels (omitted where that is the input width) + depthwise
+    `k` x `k` + linear 1x1 projection, BN after every convolution, `act` ("relu" or "hardswish") after the first two; with `se` the
+    squeeze-excite gate between the depthwise and the projection layer (1x1 convolutions, a quarter of the expanded width rounded up
+    to a multiple of 8, ReLU, hard sigmoid); the identity shortcut where stride is 1 and the width is kept."""
+
+    def __init__(self, cin, k, expanded, cout, se, act, stride):
+        super().__init__()
+        self.use_res = stride == 1 and cin == cout
+        layers = [_conv_bn_act(cin, expanded, 1, act=act)] if expanded != cin else []
+        layers += [_conv_bn_act(expanded, expanded, k, stride, groups=expanded, act=act)]
+        if se:
+            layers += [SqueezeExcite(expanded, (expanded // 4 + 7) // 8 * 8, gate="hardsigmoid", squeeze="conv")]
+        layers += [nn.Sequential(nn.Conv2d(expanded, cout, 1, bias=False), nn.BatchNorm2d(cout))]
+        self.block = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.block(x) if self.use_res else self.block(x)
+
+
+class MobileNetV3(nn.Module):
+    """MobileNetV3 (public architecture, Howard et al. 2019, tables 1 and 2) in torchvision's module layout - `features.N` blocks whose
+    convolutions stand in front of their BatchNorm (merge_bn's default mapping), `avgpool`, a Linear -> Hardswish -> Dropout -> Linear
+    classifier.  `rows`: (depthwise filter, expanded, out, SE, activation "RE" | "HS", stride) per block; the first layer is 3x3 / 2 to
+    16 channels, the last 1x1 to six times the last block's width, both with hard swish; `hidden`: the classifier's width.  Large:
+    5 483 032 parameters, Small: 2 542 856."""
+
+    LARGE = ((3, 16, 16, False, "RE", 1), (3, 64, 24, False, "RE", 2), (3, 72, 24, False, "RE", 1), (5, 72, 40, True, "RE", 2),
+             (5, 120, 40, True, "RE", 1), (5, 120, 40, True, "RE", 1), (3, 240, 80, False, "HS", 2), (3, 200, 80, False, "HS", 1),
+             (3, 184, 80, False, "HS", 1), (3, 184, 80, False, "HS", 1), (3, 480, 112, True, "HS", 1), (3, 672, 112, True, "HS", 1),
+             (5, 672, 160, True, "HS", 2), (5, 960, 160, True, "HS", 1), (5, 960, 160, True, "HS", 1))
+    SMALL = ((3, 16, 16, True, "RE", 2), (3, 72, 24, False, "RE", 2), (3, 88, 24, False, "RE", 1), (5, 96, 40, True, "HS", 2),
+             (5, 240, 40, True, "HS", 1), (5, 240, 40, True, "HS", 1), (5, 120, 48, True, "HS", 1), (5, 144, 48, True, "HS", 1),
+             (5, 288, 96, True, "HS", 2), (5, 576, 96, True, "HS", 1), (5, 576, 96, True, "HS", 1))
+
+    def __init__(self, rows, hidden, num_classes=1000, dropout=0.2):
+        super().__init__()
+        cin = 16
+        feats = [_conv_bn_act(3, cin, 3, stride=2, act="hardswish")]
+        for k, expanded, cout, se, act, stride in rows:
+            feats.append(MobileNetV3Block(cin, k, expanded, cout, se, {"RE": "relu", "HS": "hardswish"}[act], stride))
+            cin = cout
+        feats.append(_conv_bn_act(cin, 6 * cin, 1, act="hardswish"))
+        self.features = nn.Sequential(*feats)
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.classifier = nn.Sequential(nn.Linear(6 * cin, hidden), nn.Hardswish(), nn.Dropout(dropout), nn.Linear(hidden, num_classes))
+        _init(self)
+
+    def forward(self, x):
+        return self.classifier(torch.flatten(self.avgpool(self.features(x)), 1))
 
 
 class CifarResNet(nn.Module):
@@ -439,6 +492,16 @@ def efficientnet_b0(num_classes=1000, se=True, act="swish"):
     """EfficientNet-B0: MBConv blocks (`mobilenet_v2(se=True, act="swish")`'s) with the paper's stage table - 5x5 depthwise layers in
     stages 3, 5 and 6.  `se` / `act` as in mobilenet_v2."""
     return EfficientNetB0(num_classes=num_classes, se=se, act=act)
+
+
+def mobilenet_v3_large(num_classes=1000):
+    """MobileNetV3-Large: 15 blocks, a 960-channel last layer, a 1280-wide classifier; 20 hard swishes on maps, 8 squeeze-excite gates."""
+    return MobileNetV3(MobileNetV3.LARGE, 1280, num_classes)
+
+
+def mobilenet_v3_small(num_classes=1000):
+    """MobileNetV3-Small: 11 blocks, a 576-channel last layer, a 1024-wide classifier; 18 hard swishes on maps, 9 squeeze-excite gates."""
+    return MobileNetV3(MobileNetV3.SMALL, 1024, num_classes)
 
 
 def vit_tiny(num_classes=1000):

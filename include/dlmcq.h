@@ -974,6 +974,29 @@ int dlmcq_swish_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int
                          int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
                          int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- hard swish x * relu6(x + 3) / 6: fp32 and / or the consumer's activation codes ----
+ * For image n, pixel (h, w), channel c, with x = x[n, h, w, c]:
+ *     t = fl32(x + 3)       one IEEE add
+ *     r = relu6(t)          t > 0 ? t : (t is NaN ? t : +0), then r > 6 ? 6 : r - the device's clamp (NaN passes, -0 becomes +0), as
+ *                           dlmcq_squeeze_gate_i8's DLMCQ_GATE_HARDSIGMOID
+ *     c = fl32(1 / 6)       the constant 0x3E2AAAAB: a division by the host scalar 6 is this multiplication on the device
+ *     order DLMCQ_HSWISH_MUL_FIRST:   v = fl32(fl32(x * r) * c)    nn.Hardswish, F.hardswish, (x * relu6(x + 3)) / 6
+ *     order DLMCQ_HSWISH_GATE_FIRST:  v = fl32(x * fl32(r * c))    x * (relu6(x + 3) / 6), x * hardsigmoid(x)
+ *     out = v;  code = the quantiser (q_scale .. q_ste_g, as in dlmcq_conv2d_i8_nhwc_fused; DLMCQ_EMIT_SHIFT128 accepted) of v - the
+ *                      code dlmcq_fake_quant_f32 gives for it
+ * - every step rounded to fp32 by itself, never contracted.  The two orders differ in the last bit of about a quarter of the elements;
+ * either is within 5 * 2^-24 relative of the real x * clip(x + 3, 0, 6) / 6, and exactly 0 where that is 0.  x <= -3: v = -0; x = -0:
+ * -0; x = -inf: NaN (as -inf * 0); x = +inf: +inf; NaN stays NaN; x >= 3: (x * 6) * c or x * (6 * c), which need not equal x;
+ * x > FLT_MAX / 6: +inf under DLMCQ_HSWISH_MUL_FIRST (x * 6 overflows), finite under DLMCQ_HSWISH_GATE_FIRST; denormals are kept.
+ * No atomics, no scratch: the result depends neither on the launch geometry nor on the run.
+ * Arguments, layouts and return codes: exactly those of dlmcq_swish_nhwc_f32, plus `order`.  DLMCQ_EINVAL first of all for an order
+ * outside 0 .. 1. */
+#define DLMCQ_HSWISH_MUL_FIRST 0
+#define DLMCQ_HSWISH_GATE_FIRST 1
+int dlmcq_hardswish_nhwc_f32(const float* x, float* out, void* codes, int64_t N, int64_t H, int64_t W, int64_t C, int64_t x_stride,
+                             int64_t c_pad, int32_t pad_code, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi,
+                             int32_t q_form, float q_ste_g, int32_t order, dlmcq_stream_t stream);
+
 /* ---- the squeeze path of a squeeze-excite block: pooled activation codes [N, C] -> the fp32 gate [N, C], one launch ----
  * Two int8 layers on rows with an activation between them and the gate function behind them; the hidden vector stays on the chip.
  * For image n, hidden unit r (0 .. R4 - 1) and channel c (0 .. C - 1):
