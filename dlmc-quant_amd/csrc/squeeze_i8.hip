@@ -186,6 +186,8 @@ extern "C" int dlmcq_squeeze_gate_i8(const void* x, const int8_t* w1, const int3
   // (the hidden codes stay in LDS: `ep.codes` is the "there is a quantiser" mark EpiQuant and the checks key on, never dereferenced)
   int rc = emit_set_quantiser(ep, &ep, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
   if (rc != DLMCQ_OK) return rc;
+  // (layer 2 re-reads the hidden bytes as uint8 or as int8: a range that is neither has no byte for its codes above 127)
+  if (q_lo < 0 && q_hi > 127) return DLMCQ_EINVAL;
   if (N == 0) return DLMCQ_OK;
   if (!(gate || hidden)) return DLMCQ_EINVAL;
   for (const void* p : {x, (const void*)w1, (const void*)wsum1, (const void*)in_scale1, (const void*)w_scale1, (const void*)w2,

@@ -1331,6 +1331,8 @@ def _squeeze_operands(name, codes, l1, inner_act, emit, l2, gate_fn, want_gate, 
         raise ValueError(f"{name}: the second layer's activation quantiser (emit=EmitCodes(...)) is required")
     if emit.shift128:
         raise ValueError(f"{name}: the hidden codes are plain codes (EmitCodes.shift128 is refused)")
+    if emit.lo < 0 and emit.hi > 127:
+        raise ValueError(f"{name}: the hidden codes are uint8 or int8 bytes, the range {emit.lo} .. {emit.hi} is neither")
     if codes.dim() != 2 or codes.dtype not in (torch.uint8, torch.int8):
         raise ValueError(f"{name}: activation codes (N, C), uint8 or int8, not {codes.dtype} {tuple(codes.shape)}")
     n, c = codes.shape

@@ -1028,7 +1028,8 @@ int dlmcq_hardswish_nhwc_f32(const float* x, float* out, void* codes, int64_t N,
  *              Without `gate` layer 2 is not computed.
  * DLMCQ_EINVAL: N < 0, C < 4, C > DLMCQ_SQUEEZE_MAX_C, C % 4, R4 < 1, R4 > DLMCQ_SQUEEZE_MAX_R, R4 % 4, inner_act or gate_fn outside
  * 0 .. 2; then an invalid quantiser (q_scale NULL included), any control or layout bit or DLMCQ_EMIT_SHIFT128 in q_form (refused, not
- * stripped); then, unless N == 0 (DLMCQ_OK, nothing launched, null pointers included): both outputs NULL, a required input NULL.
+ * stripped), a code range that is neither a uint8 nor an int8 one (q_lo < 0 and q_hi > 127: the hidden codes are bytes that layer 2
+ * reads as one or the other); then, unless N == 0 (DLMCQ_OK, nothing launched, null pointers included): both outputs NULL, a required input NULL.
  * DLMCQ_EALIGN: w1 / w2 / gate / hidden not 16-byte aligned, any other pointer not 4-byte aligned.  DLMCQ_ERANGE: N * C or N * R4
  * reaches 2^31.  A refused call writes nothing.  One workgroup computes DLMCQ_SQUEEZE_IMAGES images. */
 #define DLMCQ_SQUEEZE_MAX_C 2048

@@ -111,6 +111,38 @@ def quantise(v, q):
     return code_bytes(oracle_codes(v, q), q)
 
 
+def code_ints(v, q):
+    """The oracle's codes of an fp32 tensor as int64 (NaN -> 0, as code_of): the integers themselves, whatever byte the range stores
+    them in - `quantise(v, q).long()` wherever the range is a uint8 or an int8 one."""
+    assert v.dtype == torch.float32
+    return torch.nan_to_num(oracle_codes(v, q), nan=0.0).long()
+
+
+def dequant_scale(q):
+    """The fp32 scale a form dequantises with, float64: QBASE (s - s g) + s g in fp32 (the oracle's ste_scale), else the scale."""
+    s = f32(q.scale)
+    return float(O.ste_scale(s, q.g) if q.form == FORM_QBASE else s)
+
+
+def exact_fma(a64, m64, b64, what="fma"):
+    """fl32(a * m + b) as ONE rounding of the exact value - the device's fused multiply-add - from float64 tensors that hold fp32
+    numbers.  Asserted for every element, none left out: the three operands are fp32 numbers (so a * m, 24 x 24 bits, is exact in
+    float64) and the float64 sum p + b has no rounding error (Knuth's TwoSum: the error term is 0), so the single cast to fp32 is the
+    only rounding.  A sum that is not finite (a NaN or an infinity in b) needs no argument."""
+    a64, m64, b64 = torch.broadcast_tensors(a64, m64, b64)
+    for t in (a64, m64, b64):
+        back = t.float().double()
+        assert bool(((back == t) | (back.isnan() & t.isnan())).all()), f"{what}: an operand is no fp32 number"
+    p = a64 * m64
+    assert bool(((p != 0) | (a64 == 0) | (m64 == 0) | p.isnan()).all()), f"{what}: the product underflows float64"
+    s = p + b64
+    bb = s - p
+    err = (p - (s - bb)) + (b64 - bb)
+    ok = (err == 0) | ~s.isfinite()
+    assert bool(ok.all()), f"{what}: {int((~ok).sum())} float64 sums are not exact, e.g. {s[~ok].flatten()[:4].tolist()}"
+    return s.float()
+
+
 def exact_f32(v64, what="reference"):
     """float64 -> float32, asserting the cast is exact (NaN stays NaN)."""
     v32 = v64.float()
@@ -301,6 +333,13 @@ def full_range_bias(k, nz, live, unit, gen, edge=True):
     return b
 
 
+def full_range_sigma(taps, signed_in, zp):
+    """Standard deviation of the integer sum of `taps` products of a uniform byte about its zero point and a uniform weight code in
+    +-127 - from the shape alone."""
+    mean = (-0.5 if signed_in else 127.5) - zp
+    return math.sqrt(taps) * math.sqrt((127 * 128) / 3.0) * math.sqrt((256 * 256 - 1) / 12.0 + mean * mean)
+
+
 def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asym=False, zp=None, live=None, edge_bias=True, zp_side=None,
                           depthwise=False):
     """Random full-range operands (see above).  `depthwise`: k == c groups of one channel - wq is (C, 1, R, S), the input scale is sized
@@ -336,8 +375,7 @@ def make_full_range_layer(gen, n, c, h, w, k, r, s=None, *, signed_in=False, asy
         w_int[live:] = 0
     # the input scale: a power of two that puts the widest-scale channels' outputs at FULL_TARGET_SIGMA (from the shape alone: the
     # integer sum of r s c products of a uniform byte about its zero point and a uniform weight code)
-    mean = (-0.5 if signed_in else 127.5) - zp
-    sigma_int = math.sqrt(r * s * cin) * math.sqrt((127 * 128) / 3.0) * math.sqrt((256 * 256 - 1) / 12.0 + mean * mean)
+    sigma_int = full_range_sigma(r * s * cin, signed_in, zp)
     s_in = 2.0 ** round(math.log2(FULL_TARGET_SIGMA / (sigma_int * 2.0 ** -10)))
     if depthwise and s_in == 1.0:
         s_in = 0.5                  # (a 1 x 1 filter: the target lands on 1, and a scale of 1 hides a dropped multiplication)

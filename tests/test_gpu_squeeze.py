@@ -27,6 +27,13 @@ SHAPES = [(1, 4, 1), (3, 32, 8), (5, 96, 4), (7, 144, 6), (9, 240, 10), (2, 1152
           (G - 1, 48, 12), (G, 48, 12), (G + 1, 48, 12), (2 * G + 1, 48, 12)]
 INNER = [None, "relu", "swish"]
 WORST = {}
+SIGMOID_BOUND = 4 * 2.0 ** -24      # Part 2's relative bound (+ 2^-126 absolute): shared with tests/test_gpu_squeeze_exact.py
+
+
+def sigmoid_ratio(g, v):
+    """The largest |g - g*| / (SIGMOID_BOUND |g*| + 2^-126) of a sigmoid output `g` against float64 g* = 1 / (1 + exp(-v))."""
+    ref = 1.0 / (1.0 + torch.exp(-v.double()))
+    return float(((g.double() - ref).abs() / (SIGMOID_BOUND * ref.abs() + 2.0 ** -126)).max())
 
 
 def t(v):
@@ -95,8 +102,7 @@ def test_sigmoid_bound_and_hard_sigmoid(shape, inner):
         for name, q in quantisers().items():
             v = K.squeeze_gate(codes, l1, inner, emit_of(q), l2, None)[0]
             g = K.squeeze_gate(codes, l1, inner, emit_of(q), l2, "sigmoid")[0]
-            ref = 1.0 / (1.0 + torch.exp(-v.double()))
-            ratio = float(((g.double() - ref).abs() / (4 * 2.0 ** -24 * ref.abs() + 2.0 ** -126)).max())
+            ratio = sigmoid_ratio(g, v)
             WORST["sigmoid"] = max(WORST.get("sigmoid", 0.0), ratio)
             assert ratio <= 1.0, (name, unsigned, ratio)
             differ += int((g != torch.sigmoid(v)).sum())

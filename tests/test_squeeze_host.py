@@ -58,6 +58,7 @@ REFUSED = {
     "r4_0": (dict(r4=0), -1), "r4_mod_4": (dict(r4=6), -1), "r4_above_512": (dict(r4=516), -1),
     "inner_act_3": (dict(inner=3), -1), "inner_act_negative": (dict(inner=-1), -1), "gate_fn_3": (dict(fn=3), -1), "gate_fn_negative": (dict(fn=-1), -1),
     "no_scale": (dict(scale=None), -1), "lo_above_hi": (dict(lo=5, hi=4), -1), "range_beyond_a_byte": (dict(lo=-128, hi=255), -1),
+    "range_neither_u8_nor_s8": (dict(lo=-1, hi=200), -1), "range_neither_at_the_edge": (dict(lo=-1, hi=128), -1),
     "unknown_form": (dict(form=9), -1), "rootq_form": (dict(form=N.FORM_ROOTQ_ACT), -1),
     "shifted_emission": (dict(form=N.FORM_ZEROPOINT | N.EMIT_SHIFT128), -1), "force_tiled": (dict(form=N.FORM_ZEROPOINT | N.FORCE_TILED), -1),
     "route_only": (dict(form=N.FORM_ZEROPOINT | N.ROUTE_ONLY), -1), "chunk_major_out": (dict(form=N.FORM_ZEROPOINT | N.FP32_OUT_CHUNK_MAJOR), -1),
@@ -70,6 +71,7 @@ REFUSED = {
     "codes_reach_2_31": (dict(n=1 << 20, c=2048), -2), "hidden_reaches_2_31": (dict(n=1 << 22, c=4, r4=512), -2),
     # two faults at once: the earlier check answers (geometry, quantiser, the empty problem, pointers, alignment, 2^31)
     "geometry_before_quantiser": (dict(c=18, scale=None), -1), "quantiser_before_empty": (dict(n=0, form=9), -1),
+    "mixed_range_before_empty": (dict(n=0, lo=-1, hi=200), -1), "mixed_range_before_pointers": (dict(lo=-1, hi=200, w1=2 * A + 4), -1),
     "quantiser_before_pointers": (dict(scale=None, w1=2 * A + 4), -1), "null_before_alignment": (dict(w2=None, w1=2 * A + 4), -1),
     "alignment_before_range": (dict(n=1 << 20, c=2048, gate=12 * A + 4), -4), "no_output_before_alignment": (dict(gate=None, hidden=None, x=A + 2), -1),
 }
@@ -112,6 +114,8 @@ def _wrapper_refusals():
         "inner_act": (dict(inner_act="gelu"), ValueError, "inner_act"), "gate_fn": (dict(gate_fn="tanh"), ValueError, "gate_fn"),
         "nothing": (dict(want_gate=False), ValueError, "nothing to produce"), "no_quantiser": (dict(emit=None), ValueError, "quantiser"),
         "shifted": (dict(emit=shifted), ValueError, "shift128"),
+        "mixed_range": (dict(emit=K.EmitCodes(emit.scale, emit.zero_point, -1, 200, N.FORM_ZEROPOINT)), ValueError, "neither"),
+        "shifted_before_mixed_range": (dict(emit=shifted, codes=codes.float()), ValueError, "shift128"),
         "codes_fp32": (dict(codes=codes.float()), ValueError, "activation codes"), "codes_4d": (dict(codes=codes[:, :, None, None]), ValueError, "activation codes"),
         "w1_width": (dict(l1=dict(l1, wq=l1["wq"][:, :4])), ValueError, "layer 1's weight codes"),
         "w1_dtype": (dict(l1=dict(l1, wq=l1["wq"].to(torch.int16))), ValueError, "layer 1's weight codes"),
