@@ -12,81 +12,42 @@ operations, event times) - launches, time, TFLOP/s and bytes per second; and wha
 profile has no record of torch's own kernels, so the same op sequence (the views, two products, multiply, softmax, permute + reshape)
 is timed with events on a [batch, 197, 1152] projection output, and `to_out`'s quantise passes are read from the profile.
 Writes profiles/attention_ab.json (and prints it).
-usage: python tools/attention_ab.py [batch] [steps]"""
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from dlmc.quantization.scalar import kernels as K  # noqa: E402
-from dlmc.utils.fuse import fuse_inference  # noqa: E402
-from relu6_ab import timed  # noqa: E402
-from swish_ab import quartiles  # noqa: E402
-from transformer_ab import CASES, calibrate  # noqa: E402
+usage: python tools/attention_ab.py [batch] [steps] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc.utils.fuse import fuse_inference
 
 FLAGS = dict(layer_norms=True, gelu=True)
 
 
-def profile_step(plan, x):
-    plan(x)                                             # (warm)
-    K.PROFILE.reset()
-    K.PROFILE.enabled = True
-    try:
-        plan(x)
-        torch.cuda.synchronize()
-        return [(r[0], r[1], r[2].elapsed_time(r[3]), r[4]) for r in K.PROFILE.records]
-    finally:
-        K.PROFILE.enabled = False
-        K.PROFILE.reset()
-
-
-def unfused_attention_us(batch, heads, dim_head, tokens, dev, runs=9):
+def unfused_attention_us(batch, heads, dim_head, tokens, runs=9):
     """Median time of one block's attention as the flag-off plan runs it, in torch, on a projection output of the real shape."""
-    qkv = torch.randn(batch, tokens, 3 * heads * dim_head, device=dev)
+    qkv = torch.randn(batch, tokens, 3 * heads * dim_head, device=P.DEV)
 
-    def once():
+    def once(_):
         p = qkv.reshape(batch, tokens, 3, heads, dim_head).permute(2, 0, 3, 1, 4)
         q, k, v = p[0], p[1], p[2]
         attn = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * dim_head ** -0.5, dim=-1)
         return torch.matmul(attn, v).permute(0, 2, 1, 3).reshape(batch, tokens, heads * dim_head)
     for _ in range(2):
-        once()
-    ts = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        once()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return quartiles(ts)[1]
+        once(None)
+    return P.quartiles([P.timed(once, None, 1) * 1e3 for _ in range(runs)])[1]
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 24
-    dev = "cuda:0"
-    out = {"model": "vit_small()", "batch": batch, "steps_per_plan": steps, "resolution": 224, "both_plans": FLAGS}
-    for tag, fam in CASES:
-        torch.manual_seed(2333)
-        model = W.vit_small().to(dev).eval()
-        x = torch.randn(batch, 3, 224, 224, device=dev)
-        calibrate(model, fam, x)
+    arg = P.arguments(__doc__, batch=256, steps=24)
+    out = {"model": "vit_small()", "batch": arg.batch, "steps_per_plan": arg.steps, "resolution": 224, "both_plans": FLAGS}
+    for tag, fam in P.CASES:
+        model = P.seeded_model(W.vit_small, bn=False)
+        x = torch.randn(arg.batch, 3, 224, 224, device=P.DEV)
+        P.calibrate(model, fam, x)
         with torch.no_grad():
             plans = {"attention": fuse_inference(model, attention=True, **FLAGS), "flag_off": fuse_inference(model, **FLAGS)}
             logits = {k: p(x) for k, p in plans.items()}
-            recs = {k: profile_step(p, x) for k, p in plans.items()}
-            torch_us = unfused_attention_us(batch, 6, 64, 197, dev)
-            for p in plans.values():                        # warm-up
-                timed(p, x, 3)
-            ms = {k: [] for k in plans}
-            for _ in range(steps):                          # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 1))
+            recs = {k: P.profile_step(p, x) for k, p in plans.items()}
+            torch_us = unfused_attention_us(arg.batch, 6, 64, 197)
+            ms = P.interleaved(plans, x, 3, arg.steps, 1)
         a, b = logits["attention"].float(), logits["flag_off"].float()
         mine = [r for r in recs["attention"] if r[0] == "attention"]
         t_ms, nbytes, ops = sum(r[2] for r in mine), sum(r[1] for r in mine), sum(r[3] for r in mine)
@@ -103,25 +64,14 @@ def main():
                                       "quantise_us_flag_on": round(sum(fq["attention"]) * 1e3, 1)}}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            q1, med, q3 = quartiles(v)
-            res[k] = {"ms_per_step_median": round(med, 3), "ms_per_step_q1": round(q1, 3), "ms_per_step_q3": round(q3, 3),
-                      "ms_per_step_min": round(min(v), 3), "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v],
-                      "int8_layers": rep.layers, "layer_norms": rep.layer_norms, "gelus": rep.gelus, "attentions": rep.attentions,
-                      "fp32_outputs": rep.fp32_outputs, "not_eligible": len(rep.skipped)}
-        on, off = res["attention"], res["flag_off"]
-        res["flag_off_attention"]["share_of_step"] = round(12 * torch_us * 1e-3 / off["ms_per_step_median"], 3)
-        spread = off["ms_per_step_q3"] - off["ms_per_step_q1"]
-        res["run_to_run_spread_ms"] = round(spread, 3)      # (the interquartile range of the baseline's steps)
-        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
-        res["flag_on_faster_beyond_spread"] = bool(off["ms_per_step_median"] - on["ms_per_step_median"] > spread)
-        res["flag_on_slower_beyond_spread"] = bool(on["ms_per_step_median"] - off["ms_per_step_median"] > spread)
+            res[k] = dict(P.arm_summary(v, P.QUARTILES), int8_layers=rep.layers, layer_norms=rep.layer_norms, gelus=rep.gelus,
+                          attentions=rep.attentions, fp32_outputs=rep.fp32_outputs, not_eligible=len(rep.skipped))
+        res["flag_off_attention"]["share_of_step"] = round(12 * torch_us * 1e-3 / res["flag_off"]["ms_per_step_median"], 3)
+        res.update(P.verdict(res["attention"], res["flag_off"], "iqr_off"))
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "attention_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("attention_ab", out, arg.out)
 
 
 if __name__ == "__main__":

@@ -8,20 +8,11 @@ itself) against the plan without `avg_pools`: both plans built from ONE calibrat
 Per case: median / min / max ms per step of either plan, whether the flag-on plan is slower by more than the run-to-run spread, whether
 the logits are equal, and per pool node the kernel's time and achieved bytes per second (bytes per output pixel and channel: 4 s^2 read,
 4 written if the fp32 tensor is wanted, 1 written per padded code).  Writes profiles/avgpool_shortcut_ab.json (and prints it).
-usage: python tools/avgpool_shortcut_ab.py [batch] [rounds]"""
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from dlmc.utils.fuse import AvgPoolLayer, fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from node_times import calibrated, node_times  # noqa: E402
-from relu6_ab import timed  # noqa: E402
+usage: python tools/avgpool_shortcut_ab.py [batch] [rounds] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc.utils.fuse import AvgPoolLayer, fuse_inference
 
 CASES = [(f"cifar_resnet{depth}_option_{opt.lower()}_{fam}", depth, opt, fam)
          for depth in (20, 56) for opt in ("C", "D") for fam in ("fsptq_w8a8", "qbase_w8a8")]
@@ -30,7 +21,7 @@ CASES = [(f"cifar_resnet{depth}_option_{opt.lower()}_{fam}", depth, opt, fam)
 def pool_kernel_times(plan, x, reps=20):
     """Per AvgPoolLayer node (node_times): the kernel's time and bytes per second."""
     rows = []
-    for name, m, (t,), ms in node_times(plan, x, AvgPoolLayer, reps):
+    for name, m, (t,), ms in P.node_times(plan, x, AvgPoolLayer, reps):
         n, c, h, w = t.shape
         s = m.window
         pix = n * (h // s) * (w // s)
@@ -41,44 +32,28 @@ def pool_kernel_times(plan, x, reps=20):
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    dev = "cuda:0"
-    out = {"batch": batch, "rounds": rounds, "steps_per_round": 3, "resolution": 32}
+    a = P.arguments(__doc__, batch=512, rounds=7)
+    out = {"batch": a.batch, "rounds": a.rounds, "steps_per_round": 3, "resolution": 32}
     for tag, depth, opt, fam in CASES:
-        torch.manual_seed(2333)
-        model = merge_bn(W.CifarResNet((depth - 2) // 6, option=opt).to(dev).eval(), inplace=True, allow_missing=True)
+        model = P.seeded_model(lambda: W.CifarResNet((depth - 2) // 6, option=opt))
         kw = {} if fam.startswith("fsptq") else dict(act_offsets=True)
-        x = torch.relu(torch.randn(batch, 3, 32, 32, device=dev))
-        calibrated(model, fam, x, zero_qbase=False)
+        x = P.relu_images(a.batch, 32)
+        P.calibrated(model, fam, x, zero_qbase=False)
         with torch.no_grad():
             plans = {"avg_pools": fuse_inference(model, avg_pools=True, **kw), "flag_off": fuse_inference(model, **kw)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = pool_kernel_times(plans["avg_pools"], x)
-            for p in plans.values():                        # warm-up
-                timed(p, x, 2)
-            ms = {k: [] for k in plans}
-            for _ in range(rounds):                         # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 3))
+            ms = P.interleaved(plans, x, 2, a.rounds, 3)
         res = {"logits_equal": bool(torch.equal(logits["avg_pools"], logits["flag_off"])), "pool_kernels": kernels}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            res[k] = {"ms_per_step_median": round(sorted(v)[len(v) // 2], 3), "ms_per_step_min": round(min(v), 3),
-                      "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v], "int8_layers": rep.layers,
-                      "avg_pools": rep.avg_pools, "dual": rep.dual, "fp32_outputs": rep.fp32_outputs, "not_eligible": len(rep.skipped)}
-        on, off = res["avg_pools"], res["flag_off"]
-        spread = max(on["ms_per_step_max"] - on["ms_per_step_min"], off["ms_per_step_max"] - off["ms_per_step_min"])
-        res["run_to_run_spread_ms"] = round(spread, 3)
-        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
-        res["flag_on_slower_beyond_spread"] = bool(on["ms_per_step_median"] - off["ms_per_step_median"] > spread)
+            res[k] = dict(P.arm_summary(v), int8_layers=rep.layers, avg_pools=rep.avg_pools, dual=rep.dual, fp32_outputs=rep.fp32_outputs,
+                          not_eligible=len(rep.skipped))
+        res.update(P.verdict(res["avg_pools"], res["flag_off"], "range", ("slower",)))
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "avgpool_shortcut_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("avgpool_shortcut_ab", out, a.out)
 
 
 if __name__ == "__main__":

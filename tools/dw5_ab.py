@@ -10,25 +10,17 @@ kernel), two interleaved comparisons in one process:
 Writes profiles/dw5_ab.json (or --out) and prints it.
 usage: python tools/dw5_ab.py [--batch N] [--plan-batch N] [--rounds N] [--out FILE]"""
 import argparse
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from dlmc import _native as N  # noqa: E402
-from dlmc.quantization.scalar import kernels as K  # noqa: E402
-from dlmc.utils.fuse import fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from node_times import calibrated  # noqa: E402
-from relu6_ab import timed  # noqa: E402
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc import _native as N
+from dlmc.quantization.scalar import kernels as K
+from dlmc.utils.fuse import fuse_inference
 
 SHAPES = [(192, 56, 2), (256, 28, 1), (512, 14, 1), (704, 14, 1), (704, 14, 2), (1152, 7, 1)]      # padded channels, input map, stride
 VARIANTS = [("codes_sym", False, False), ("codes_asym", True, False), ("fp32_and_codes_sym", False, True)]
-DEV = "cuda:0"
+DEV = P.DEV
 
 
 def operands(batch, c, hw, gen):
@@ -60,10 +52,10 @@ def standalone(batch, rounds):
             equal = all(torch.equal(a, b) for a, b in zip(res["dw5"], res["generic"]) if a is not None)
             ms = {k: [] for k in runs}
             for f in runs.values():
-                timed(f, None, 3)
+                P.timed(f, None, 3)
             for _ in range(rounds):                         # interleaved: A, B, A, B, ...
                 for k, f in runs.items():
-                    ms[k].append(timed(f, None, 20))
+                    ms[k].append(P.timed(f, None, 20))
             new, old = stats(ms["dw5"]), stats(ms["generic"])
             spread = max(new["ms_max"] - new["ms_min"], old["ms_max"] - old["ms_min"])
             elems = batch * c * ((hw - 1) // stride + 1) ** 2
@@ -80,20 +72,14 @@ def standalone(batch, rounds):
 def whole_plan(batch, rounds):
     out = {}
     for tag, fam in (("efficientnet_b0_fsptq_w8a8", "fsptq"), ("efficientnet_b0_qbase_w8a8", "qbase")):
-        torch.manual_seed(2333)
-        model = merge_bn(W.efficientnet_b0().to(DEV).eval(), inplace=True, allow_missing=True)
-        x = torch.relu(torch.randn(batch, 3, 224, 224, device=DEV))
-        calibrated(model, fam, x)
+        model = P.seeded_model(W.efficientnet_b0)
+        x = P.relu_images(batch, 224)
+        P.calibrated(model, fam, x)
         with torch.no_grad():
             plans = {"dw5": fuse_inference(model, gates=True, swish=True, dw5=True), "flag_off": fuse_inference(model, gates=True, swish=True)}
             logits = {k: p(x) for k, p in plans.items()}
             torch.cuda.synchronize()
-            for p in plans.values():
-                timed(p, x, 2)
-            ms = {k: [] for k in plans}
-            for _ in range(rounds):
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 3))
+            ms = P.interleaved(plans, x, 2, rounds, 3)
         res = {"batch": batch, "logits_equal": bool(torch.equal(logits["dw5"], logits["flag_off"])), "dw5_layers": plans["dw5"].fusion_report.dw5,
                "int8_layers": plans["dw5"].fusion_report.layers, "dw5": stats(ms["dw5"]), "flag_off": stats(ms["flag_off"])}
         res["spread_ms"] = round(max(res[k]["ms_max"] - res[k]["ms_min"] for k in ("dw5", "flag_off")), 4)
@@ -110,15 +96,12 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--plan-batch", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dw5_ab.json"))
+    ap.add_argument("--out")
     a = ap.parse_args()
     out = {"standalone": standalone(a.batch, a.rounds), "whole_plan": whole_plan(a.plan_batch, a.rounds), "rounds": a.rounds}
     out["every_standalone_case_faster_beyond_spread"] = all(r["faster_beyond_spread"] for r in out["standalone"])
     out["every_result_equal"] = all(r["equal"] for r in out["standalone"]) and all(r["logits_equal"] for r in out["whole_plan"].values())
-    text = json.dumps(out, indent=1)
-    with open(a.out, "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("dw5_ab", out, a.out)
 
 
 if __name__ == "__main__":

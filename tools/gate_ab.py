@@ -8,20 +8,11 @@ the plan without `gates`: both plans built from ONE calibrated model and timed i
 Per case: median / min / max ms per step of either plan, whether the flag-on plan is slower by more than the run-to-run spread, whether
 the logits are equal, and per gate node the kernel's time and achieved bytes per second (per pixel: 4 C read, 4 C written if the fp32
 tensor is wanted, c_pad code bytes written; the N x C gate once).  Writes profiles/gate_ab.json (and prints it).
-usage: python tools/gate_ab.py [batch] [rounds]"""
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from dlmc.utils.fuse import GateLayer, fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from node_times import calibrated, node_times  # noqa: E402
-from relu6_ab import timed  # noqa: E402
+usage: python tools/gate_ab.py [batch] [rounds] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc.utils.fuse import GateLayer, fuse_inference
 
 CASES = [("mobilenet_v2_se_fsptq_w8a8", "fsptq"), ("mobilenet_v2_se_qbase_w8a8", "qbase")]
 
@@ -29,7 +20,7 @@ CASES = [("mobilenet_v2_se_fsptq_w8a8", "fsptq"), ("mobilenet_v2_se_qbase_w8a8",
 def gate_kernel_times(plan, x, reps=20):
     """Per GateLayer node (node_times): the kernel's time and bytes per second."""
     rows = []
-    for name, m, (t, g), ms in node_times(plan, x, GateLayer, reps):
+    for name, m, (t, g), ms in P.node_times(plan, x, GateLayer, reps):
         n, c, h, w = t.shape
         nbytes = n * h * w * (c * (4 + 4 * m.want_out) + m.c_pad) + n * c * 4
         rows.append({"node": name, "input": [n, c, h, w], "floats_per_input_pixel": int(t.stride(3)), "c_pad": m.c_pad, "act": m.act,
@@ -38,46 +29,29 @@ def gate_kernel_times(plan, x, reps=20):
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    dev = "cuda:0"
-    out = {"model": "mobilenet_v2(se=True)", "batch": batch, "rounds": rounds, "steps_per_round": 3, "resolution": 224}
+    a = P.arguments(__doc__, batch=1024, rounds=7)
+    out = {"model": "mobilenet_v2(se=True)", "batch": a.batch, "rounds": a.rounds, "steps_per_round": 3, "resolution": 224}
     for tag, fam in CASES:
-        torch.manual_seed(2333)
-        model = merge_bn(W.mobilenet_v2(se=True).to(dev).eval(), inplace=True, allow_missing=True)
-        x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
-        calibrated(model, fam, x)
+        model = P.seeded_model(lambda: W.mobilenet_v2(se=True))
+        x = P.relu_images(a.batch, 224)
+        P.calibrated(model, fam, x)
         with torch.no_grad():
             plans = {"gates": fuse_inference(model, gates=True), "flag_off": fuse_inference(model)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = gate_kernel_times(plans["gates"], x)
-            for p in plans.values():                        # warm-up
-                timed(p, x, 2)
-            ms = {k: [] for k in plans}
-            for _ in range(rounds):                         # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 3))
+            ms = P.interleaved(plans, x, 2, a.rounds, 3)
         total = sum(r["bytes"] for r in kernels)
         us = sum(r["us"] for r in kernels)
         res = {"logits_equal": bool(torch.equal(logits["gates"], logits["flag_off"])), "gate_kernels": kernels,
                "gate_kernels_total": {"us": round(us, 1), "bytes": total, "gb_per_s": round(total / (us * 1e-6) / 1e9, 1)}}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            res[k] = {"ms_per_step_median": round(sorted(v)[len(v) // 2], 3), "ms_per_step_min": round(min(v), 3),
-                      "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v], "int8_layers": rep.layers,
-                      "gates": rep.gates, "fp32_outputs": rep.fp32_outputs, "not_eligible": len(rep.skipped)}
-        on, off = res["gates"], res["flag_off"]
-        spread = max(on["ms_per_step_max"] - on["ms_per_step_min"], off["ms_per_step_max"] - off["ms_per_step_min"])
-        res["run_to_run_spread_ms"] = round(spread, 3)
-        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
-        res["flag_on_slower_beyond_spread"] = bool(on["ms_per_step_median"] - off["ms_per_step_median"] > spread)
+            res[k] = dict(P.arm_summary(v), int8_layers=rep.layers, gates=rep.gates, fp32_outputs=rep.fp32_outputs, not_eligible=len(rep.skipped))
+        res.update(P.verdict(res["gates"], res["flag_off"], "range", ("slower",)))
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "gate_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("gate_ab", out, a.out)
 
 
 if __name__ == "__main__":

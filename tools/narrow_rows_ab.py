@@ -3,35 +3,23 @@
 tensors at the real width) against the plan without the flag: both plans built from ONE calibrated model and timed interleaved in one
 process.
   case 1: MobileNetV2, FSPTQ W8A8, relu(N(0,1)) images, 224^2;
-  case 2: MobileNetV2, QBase W4A8 (tools/relu6_ab.py's QBASE_W4A8) with act_offsets=True, 224^2 - the plan of
+  case 2: MobileNetV2, QBase W4A8 (tools/plan_ab.py's QBASE_W4A8) with act_offsets=True, 224^2 - the plan of
           profiles/plan_profile_mobilenet_v2_qbase_act_offsets_b1024.txt;
   case 3: the CIFAR ResNet-20 (workloads.cifar_resnet20), QBase W8A8, 32^2.
 Per case: median / min / max ms per step of either plan, the route DLMCQ_ROUTE_ONLY reports for every narrow node, and whether the
 logits of the two plans are equal.  Writes profiles/narrow_rows_ab.json (and prints it).
-usage: python tools/narrow_rows_ab.py [batch] [rounds]"""
-import copy
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from act_offset_ab import QBASE_W8A8  # noqa: E402
-from bench import QCFG  # noqa: E402
-from dlmc import _native as N  # noqa: E402
-from dlmc.quantization.scalar import kernels as K  # noqa: E402
-from dlmc.utils.fuse import Int8Layer, fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
-from relu6_ab import QBASE_W4A8, timed  # noqa: E402
+usage: python tools/narrow_rows_ab.py [batch] [rounds] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc import _native as N
+from dlmc.quantization.scalar import kernels as K
+from dlmc.utils.fuse import Int8Layer, fuse_inference
 
 CASES = (  # tag, model, config, quantization type, fuse_inference arguments, resolution
-    ("mobilenet_v2_fsptq_w8a8", W.mobilenet_v2, QCFG, "FSPTQ", {}, 224),
-    ("mobilenet_v2_qbase_w4a8_act_offsets", W.mobilenet_v2, QBASE_W4A8, None, {"act_offsets": True}, 224),
-    ("cifar_resnet20_qbase_w8a8", W.cifar_resnet20, QBASE_W8A8, None, {}, 32),
+    ("mobilenet_v2_fsptq_w8a8", W.mobilenet_v2, P.FSPTQ_W8A8, "FSPTQ", {}, 224),
+    ("mobilenet_v2_qbase_w4a8_act_offsets", W.mobilenet_v2, P.QBASE_W4A8, None, {"act_offsets": True}, 224),
+    ("cifar_resnet20_qbase_w8a8", W.cifar_resnet20, P.QBASE_W8A8, None, {}, 32),
 )
 
 
@@ -60,40 +48,28 @@ def narrow_routes(plan, x):
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    dev = "cuda:0"
-    out = {"batch": batch, "rounds": rounds, "steps_per_round": 3}
+    a = P.arguments(__doc__, batch=1024, rounds=7)
+    out = {"batch": a.batch, "rounds": a.rounds, "steps_per_round": 3}
     for tag, make, cfg, qtype, kw, side in CASES:
-        torch.manual_seed(2333)
-        model = merge_bn(make().to(dev).eval(), inplace=True, allow_missing=True)
-        quantize_model(model, copy.deepcopy(cfg), None, **({"quantization_type": qtype, "int8_gemm": True} if qtype else {}))
-        x = torch.relu(torch.randn(batch, 3, side, side, device=dev))
+        model = P.seeded_model(make)
+        P.quantized(model, cfg, qtype)
+        x = P.relu_images(a.batch, side)
         with torch.no_grad():
             model(x[:64])                                   # calibrate
             plans = {"narrow_rows": fuse_inference(model, narrow_rows=True, **kw), "flag_off": fuse_inference(model, **kw)}
             logits = {k: p(x) for k, p in plans.items()}
             routes = narrow_routes(plans["narrow_rows"], x[:8])
-            for p in plans.values():                        # warm-up
-                timed(p, x, 2)
-            ms = {k: [] for k in plans}
-            for _ in range(rounds):                         # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 3))
+            ms = P.interleaved(plans, x, 2, a.rounds, 3)
         res = {"resolution": side, "logits_equal": bool(torch.equal(logits["narrow_rows"], logits["flag_off"])), "narrow_node_routes": routes}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            res[k] = {"ms_per_step_median": round(sorted(v)[len(v) // 2], 3), "ms_per_step_min": round(min(v), 3),
-                      "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v], "int8_layers": rep.layers,
-                      "residual_fused": rep.residual, "narrow_nodes": rep.narrow, "fp32_outputs": rep.fp32_outputs}
-        res["speedup_median"] = round(res["flag_off"]["ms_per_step_median"] / res["narrow_rows"]["ms_per_step_median"], 3)
+            res[k] = dict(P.arm_summary(v), int8_layers=rep.layers, residual_fused=rep.residual, narrow_nodes=rep.narrow,
+                          fp32_outputs=rep.fp32_outputs)
+        res["speedup_median"] = P.speedup_median(res["narrow_rows"], res["flag_off"])
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "narrow_rows_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("narrow_rows_ab", out, a.out)
 
 
 if __name__ == "__main__":

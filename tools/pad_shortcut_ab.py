@@ -6,24 +6,13 @@ slice and the `F.pad` of every transition block gone, the block's last convoluti
   case 2: the CIFAR ResNet-56 likewise.
 Per case: median / min / max ms per step of either plan, the route DLMCQ_ROUTE_ONLY reports for every node with a pad shortcut, and
 whether the logits of the two plans are equal.  Writes profiles/pad_shortcut_ab.json (and prints it).
-usage: python tools/pad_shortcut_ab.py [batch] [rounds]"""
-import copy
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from act_offset_ab import QBASE_W8A8  # noqa: E402
-from dlmc import _native as N  # noqa: E402
-from dlmc.quantization.scalar import kernels as K  # noqa: E402
-from dlmc.utils.fuse import Int8Layer, fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from dlmc.utils.quantize import quantize_model  # noqa: E402
-from relu6_ab import timed  # noqa: E402
+usage: python tools/pad_shortcut_ab.py [batch] [rounds] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc import _native as N
+from dlmc.quantization.scalar import kernels as K
+from dlmc.utils.fuse import Int8Layer, fuse_inference
 
 CASES = (  # tag, model
     ("cifar_resnet20_option_a_qbase_w8a8", lambda: W.cifar_resnet20(option="A")),
@@ -58,41 +47,28 @@ def pad_shortcut_routes(plan, x):
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
-    dev = "cuda:0"
-    out = {"batch": batch, "rounds": rounds, "steps_per_round": 3, "resolution": 32}
+    a = P.arguments(__doc__, batch=1024, rounds=7)
+    out = {"batch": a.batch, "rounds": a.rounds, "steps_per_round": 3, "resolution": 32}
     for tag, make in CASES:
-        torch.manual_seed(2333)
-        model = merge_bn(make().to(dev).eval(), inplace=True, allow_missing=True)
-        quantize_model(model, copy.deepcopy(QBASE_W8A8), None)
-        x = torch.relu(torch.randn(batch, 3, 32, 32, device=dev))
+        model = P.seeded_model(make)
+        P.quantized(model, P.QBASE_W8A8)
+        x = P.relu_images(a.batch, 32)
         with torch.no_grad():
             model(x[:64])                                   # calibrate
             plans = {"pad_shortcuts": fuse_inference(model, narrow_rows=True, pad_shortcuts=True), "flag_off": fuse_inference(model, narrow_rows=True)}
             logits = {k: p(x) for k, p in plans.items()}
             routes = pad_shortcut_routes(plans["pad_shortcuts"], x[:8])
-            for p in plans.values():                        # warm-up
-                timed(p, x, 2)
-            ms = {k: [] for k in plans}
-            for _ in range(rounds):                         # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 3))
+            ms = P.interleaved(plans, x, 2, a.rounds, 3)
         res = {"logits_equal": bool(torch.equal(logits["pad_shortcuts"], logits["flag_off"])), "pad_shortcut_node_routes": routes}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            res[k] = {"ms_per_step_median": round(sorted(v)[len(v) // 2], 3), "ms_per_step_min": round(min(v), 3),
-                      "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v], "int8_layers": rep.layers,
-                      "residual_fused": rep.residual, "narrow_nodes": rep.narrow, "pad_shortcuts": rep.pad_shortcuts,
-                      "fp32_outputs": rep.fp32_outputs}
-        res["speedup_median"] = round(res["flag_off"]["ms_per_step_median"] / res["pad_shortcuts"]["ms_per_step_median"], 3)
+            res[k] = dict(P.arm_summary(v), int8_layers=rep.layers, residual_fused=rep.residual, narrow_nodes=rep.narrow,
+                          pad_shortcuts=rep.pad_shortcuts, fp32_outputs=rep.fp32_outputs)
+        res["speedup_median"] = P.speedup_median(res["pad_shortcuts"], res["flag_off"])
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "pad_shortcut_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("pad_shortcut_ab", out, a.out)
 
 
 if __name__ == "__main__":

@@ -9,34 +9,19 @@ Per case: median ms per step of either plan over `steps` single steps each (A, B
 range of the flag-off plan's steps, whether the flag-on plan is faster by more than that, max |delta logit| and top-1 agreement between
 the two plans, and per swish node the kernel's time, bytes per second (per pixel: 4 C read, 4 C written if the fp32 map is wanted, c_pad
 code bytes written) and elements per second.  Writes profiles/swish_ab.json (and prints it).
-usage: python tools/swish_ab.py [batch] [steps]"""
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dlmc-quant_amd"), os.path.join(ROOT, "tools")]
-import torch  # noqa: E402
-
-import workloads as W  # noqa: E402
-from dlmc.utils.fuse import SwishLayer, fuse_inference  # noqa: E402
-from dlmc.utils.merge_bn import merge_bn  # noqa: E402
-from node_times import calibrated, node_times  # noqa: E402
-from relu6_ab import timed  # noqa: E402
+usage: python tools/swish_ab.py [batch] [steps] [--out PATH]"""
+import plan_ab as P  # (first: it puts the repository on the import path)
+import torch
+import workloads as W
+from dlmc.utils.fuse import SwishLayer, fuse_inference
 
 CASES = [("mbconv_se_fsptq_w8a8", "fsptq"), ("mbconv_se_qbase_w8a8", "qbase")]
-
-
-def quartiles(v):
-    s = sorted(v)
-    q = lambda f: s[min(len(s) - 1, int(f * len(s)))]  # noqa: E731
-    return q(0.25), q(0.5), q(0.75)
 
 
 def swish_kernel_times(plan, x, reps=20):
     """Per SwishLayer node (node_times): the kernel's time, bytes and elements per second."""
     rows = []
-    for name, m, (t,), ms in node_times(plan, x, SwishLayer, reps):
+    for name, m, (t,), ms in P.node_times(plan, x, SwishLayer, reps):
         n, c, h, w = t.shape
         codes = m.c_pad if m.emit is not None else 0
         nbytes = n * h * w * (c * (4 + 4 * m.want_out) + codes)
@@ -47,25 +32,17 @@ def swish_kernel_times(plan, x, reps=20):
 
 
 def main():
-    batch = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 24
-    dev = "cuda:0"
-    out = {"model": "mobilenet_v2(se=True, act='swish')", "batch": batch, "steps_per_plan": steps, "resolution": 224}
+    arg = P.arguments(__doc__, batch=1024, steps=24)
+    out = {"model": "mobilenet_v2(se=True, act='swish')", "batch": arg.batch, "steps_per_plan": arg.steps, "resolution": 224}
     for tag, fam in CASES:
-        torch.manual_seed(2333)
-        model = merge_bn(W.mobilenet_v2(se=True, act="swish").to(dev).eval(), inplace=True, allow_missing=True)
-        x = torch.relu(torch.randn(batch, 3, 224, 224, device=dev))
-        calibrated(model, fam, x)
+        model = P.seeded_model(lambda: W.mobilenet_v2(se=True, act="swish"))
+        x = P.relu_images(arg.batch, 224)
+        P.calibrated(model, fam, x)
         with torch.no_grad():
             plans = {"swish": fuse_inference(model, gates=True, swish=True), "flag_off": fuse_inference(model, gates=True)}
             logits = {k: p(x) for k, p in plans.items()}
             kernels = swish_kernel_times(plans["swish"], x)
-            for p in plans.values():                        # warm-up
-                timed(p, x, 3)
-            ms = {k: [] for k in plans}
-            for _ in range(steps):                          # interleaved: A, B, A, B, ...
-                for k, p in plans.items():
-                    ms[k].append(timed(p, x, 1))
+            ms = P.interleaved(plans, x, 3, arg.steps, 1)
         total, elems = sum(r["bytes"] for r in kernels), sum(r["input"][0] * r["input"][1] * r["input"][2] * r["input"][3] for r in kernels)
         us = sum(r["us"] for r in kernels)
         a, b = logits["swish"].float(), logits["flag_off"].float()
@@ -75,23 +52,13 @@ def main():
                                        "gelem_per_s": round(elems / (us * 1e-6) / 1e9, 1)}}
         for k, v in ms.items():
             rep = plans[k].fusion_report
-            q1, med, q3 = quartiles(v)
-            res[k] = {"ms_per_step_median": round(med, 3), "ms_per_step_q1": round(q1, 3), "ms_per_step_q3": round(q3, 3),
-                      "ms_per_step_min": round(min(v), 3), "ms_per_step_max": round(max(v), 3), "all_ms": [round(t, 3) for t in v],
-                      "int8_layers": rep.layers, "gates": rep.gates, "swishes": rep.swishes, "fp32_outputs": rep.fp32_outputs,
-                      "not_eligible": len(rep.skipped)}
-        on, off = res["swish"], res["flag_off"]
-        spread = off["ms_per_step_q3"] - off["ms_per_step_q1"]
-        res["run_to_run_spread_ms"] = round(spread, 3)      # (the interquartile range of the baseline's steps)
-        res["speedup_median"] = round(off["ms_per_step_median"] / on["ms_per_step_median"], 3)
-        res["flag_on_faster_beyond_spread"] = bool(off["ms_per_step_median"] - on["ms_per_step_median"] > spread)
+            res[k] = dict(P.arm_summary(v, P.QUARTILES), int8_layers=rep.layers, gates=rep.gates, swishes=rep.swishes,
+                          fp32_outputs=rep.fp32_outputs, not_eligible=len(rep.skipped))
+        res.update(P.verdict(res["swish"], res["flag_off"], "iqr_off", ("faster",)))
         out[tag] = res
         del model, plans, x, logits
         torch.cuda.empty_cache()
-    text = json.dumps(out, indent=1)
-    with open(os.path.join(ROOT, "profiles", "swish_ab.json"), "w") as f:
-        f.write(text + "\n")
-    print(text)
+    P.write_profile("swish_ab", out, arg.out)
 
 
 if __name__ == "__main__":
