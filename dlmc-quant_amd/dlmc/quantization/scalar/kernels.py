@@ -1618,6 +1618,83 @@ def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True):
         ops=4 * b * h * tq * tk * d)
 
 
+WINDOW_TOKENS = 64    # dlmcq_window_attention_f32: the most tokens of a window (one wave holds the T x T score tile)
+
+
+def window_term_view(t, tokens):
+    """`(rows, lead stride, row stride)` if dlmcq_window_attention_f32 reads the additive term `t` in place as `rows` tiles [T, T] -
+    fp32 of shape [..., T, T] whose leading axes are 1 but for at most one (a bias [H, T, T] or [1, H, T, T]; a mask [nW, T, T],
+    [nW, 1, T, T] or [1, nW, 1, T, T]; an expanded axis has stride 0), unit stride in the key index, both strides multiples of 4 elements,
+    the row stride at least T, 16-byte aligned, and the 16-byte piece that holds a row's last key inside the storage - else None."""
+    if t.dim() < 3 or t.dtype != torch.float32 or tuple(t.shape[-2:]) != (tokens, tokens):
+        return None
+    lead = [(n, s) for n, s in zip(t.shape[:-2], t.stride()[:-2]) if n != 1]
+    if len(lead) > 1:
+        return None
+    rows, s_lead = lead[0] if lead else (1, 0)
+    s_row = t.stride(-2) if tokens > 1 else 4      # (T = 1: one row, read as one piece)
+    if (tokens > 1 and t.stride(-1) != 1) or s_lead < 0 or s_lead % 4 or s_row < tokens or s_row % 4 or t.data_ptr() % 16:
+        return None
+    end = t.storage_offset() + (rows - 1) * s_lead + (tokens - 1) * s_row + (tokens + 3) // 4 * 4
+    return (rows, s_lead, s_row) if end * 4 <= t.untyped_storage().nbytes() else None
+
+
+def _window_term(t, tokens, what):
+    """The additive term `t` as `(tensor, rows, lead stride, row stride)`: itself where window_term_view holds, else a copy with rows
+    padded to a multiple of 4 floats (a contiguous [H, 49, 49] bias: the padding is never used).  One tile shared by every head or
+    window has lead stride 0 on either path."""
+    view = window_term_view(t, tokens)
+    if view is not None:
+        return (t, *view)
+    lead = [n for n in t.shape[:-2] if n != 1]
+    if t.dim() < 3 or t.dtype != torch.float32 or tuple(t.shape[-2:]) != (tokens, tokens) or len(lead) > 1:
+        raise ValueError(f"window_attention_quant: {what} is fp32 [..., T, T] with at most one leading axis that is not 1, not "
+                         f"{t.dtype} {tuple(t.shape)}")
+    rows, pad = (lead[0] if lead else 1), (tokens + 3) // 4 * 4
+    c = torch.empty((rows, tokens, pad), dtype=torch.float32, device=t.device)
+    c[:, :, :tokens] = t.reshape(rows, tokens, tokens)
+    return c, rows, (tokens * pad if rows > 1 else 0), pad
+
+
+def window_attention_views(q, k, v):
+    """Whether dlmcq_window_attention_f32 reads `q`, `k`, `v` [B, H, T, D] in place: attention_views, and one T <= WINDOW_TOKENS."""
+    return attention_views(q, k, v) and 1 <= q.shape[2] == k.shape[2] <= WINDOW_TOKENS
+
+
+def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want_out=True):
+    """softmax(scale * q k^T + bias + mask) v of fp32 views `q`, `k`, `v` [B, H, T, D] (window_attention_views: T <= 64, read in place, the
+    three slices of one packed projection included) by dlmcq_window_attention_f32: one wave per (b, h), the whole score tile in registers
+    (include/dlmcq.h states the order and the bound).  `bias`: fp32 [H, T, T] (or [1, H, T, T]) or None; `mask`: fp32 [nW, T, T] (or
+    Swin's broadcast spellings [nW, 1, T, T], [1, nW, 1, T, T]) or None - row b % nW applies to batch element b, B % nW == 0; both are read
+    in place where window_term_view holds, else copied - one copy per call - into rows padded to 4 floats; a [1, T, T] bias is shared by all heads.  Returns `(out or None, codes or None)`, the
+    merged heads [B, T, H * D]: fp32 unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the same
+    values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error)."""
+    N.require_gpu(q, k, v, *(t for t in (bias, mask) if t is not None))
+    if not window_attention_views(q, k, v):
+        raise ValueError("window_attention_quant: fp32 views q, k, v [B, H, T, D], T in 1 .. 64, D in (32, 64), unit stride in D, strides "
+                         "multiples of 4 elements, 16-byte aligned")
+    if not want_out and emit is None:
+        raise ValueError("window_attention_quant: nothing to produce (want_out=False without emit)")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"window_attention_quant: a finite scale, not {scale}")
+    q, k, v = q.detach(), k.detach(), v.detach()
+    b, h, t, d = q.shape
+    bt, rows, bias_sh, bias_st = _window_term(bias.detach(), t, "bias") if bias is not None else (None, h, 0, 0)
+    if rows not in (1, h):
+        raise ValueError(f"window_attention_quant: a bias of {rows} heads for {h}")
+    mt, nw, mask_sw, mask_st = _window_term(mask.detach(), t, "mask") if mask is not None else (None, 1, 0, 0)
+    if b % nw:
+        raise ValueError(f"window_attention_quant: a mask of {nw} windows for a batch of {b}")
+    terms = (bias is not None) + (mask is not None)
+    nbytes = 4 * b * h * d * 3 * t + b * h * t * d * (4 * want_out + (emit is not None)) + 4 * t * t * (h * (bias is not None) + nw * (mask is not None))
+    return _emit_launch("window_attention_quant", "window_attention", q, (b, t, h * d), emit, want_out, nbytes,
+                        lambda op, cp, *tail: N.lib.dlmcq_window_attention_f32(
+                            N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(bt), N.ptr(mt), op, cp, b, h, t, d, nw, *q.stride()[:3], *k.stride()[:3],
+                            *v.stride()[:3], t * h * d, d, h * d, bias_sh, bias_st, mask_sw, mask_st, scale, *tail),
+                        ops=4 * b * h * t * t * d + terms * b * h * t * t)
+
+
 def conv2d_i8_gap(codes, wq, wsum, bias, in_scale, in_zp, w_scale, residual=None, act=None, emit=None, want_out=True):
     """A 1 x 1 / stride 1 / unpadded int8 convolution (+ fp32 `residual` of its output's shape) (+ `act`: N.ACT_NONE / ACT_RELU /
     ACT_RELU6) and the global average pool of the result in ONE launch (dlmcq_conv2d_i8_nhwc_gap): the (N, K, H, W) map is never

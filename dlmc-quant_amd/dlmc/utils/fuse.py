@@ -35,7 +35,7 @@ from ..quantization.scalar.FSPTQuant.base import FSPTQBase
 from ..quantization.scalar.modules.base import QBase
 from ..quantization.scalar.RootQ.base import RootQBase
 
-__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SqueezeLayer", "SwishLayer", "HardswishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "FusionReport"]
+__all__ = ["fuse_inference", "StreamedPlan", "Int8Layer", "DualInt8Layer", "StemLayer", "GapLayer", "GapHeadLayer", "AvgPoolLayer", "GateLayer", "SqueezeLayer", "SwishLayer", "HardswishLayer", "LayerNormLayer", "GeluLayer", "AttentionLayer", "WindowAttentionLayer", "FusionReport"]
 
 
 # ---------------------------------------------------------------------------------- frozen quantiser specs
@@ -1665,6 +1665,167 @@ def _attention_pass(gm, report, planned, dry_run):
     _run_node_pass(gm, report, "attention", "attentions", match, dry_run)
 
 
+class WindowAttentionLayer(_MapCodesLayer):
+    """softmax(scale * q k^T + bias + mask) v of fp32 views [B, H, T, D], T <= 64 - a windowed transformer's attention - as one launch
+    (csrc/window_attention.hip: one wave per (window, head)), and the merge-heads tail behind it as a free view: the node returns
+    [B, T, H * D] and hands the Linear plan layer that reads it its activation codes from the same launch.  `emit`, `want_out`, `c`,
+    `merged`, `flatten`: as AttentionLayer; `scale`: the graph's Python float; `pre_scaled`: the graph multiplies q, not the product;
+    `has_bias` / `has_mask`: which additive terms arrive, in that order, behind q, k, v - the values the graph added (`bias.unsqueeze(0)`
+    [1, H, T, T]; `mask.unsqueeze(1).unsqueeze(0)` [1, nW, 1, T, T]: K.window_attention_quant resolves the broadcast views), and behind
+    the mask the graph's own nW - the second size of its five-size view, which the kernel path requires to be the mask's.  The torch
+    restatement - the graph's own ops, then K.fake_quant - runs for anything the kernel refuses: T > 64, D not 32 or 64, tensors that
+    are not fp32 device views read in place, terms of another shape, a merged width other than H * D or `c`.  Not merged: the kernel's
+    [B, T, H * D] permuted back to [B, H, T, D], fp32 only.  Returns `(fp32 or None, codes or None)`."""
+
+    def __init__(self, emit, want_out, c, scale, merged, pre_scaled, has_bias, has_mask, flatten=False):
+        super().__init__(emit, want_out, c, c, 0, False)
+        self.scale, self.merged, self.flatten = float(scale), bool(merged), bool(flatten)
+        self.pre_scaled, self.has_bias, self.has_mask = bool(pre_scaled), bool(has_bias), bool(has_mask)
+
+    def _torch(self, q, k, v, bias, mask, windows, shape):
+        """The unfused graph: the products, the additive terms and the softmax as they were spelled, the tail, the reader's quantise pass."""
+        s = torch.matmul(q * self.scale, k.transpose(-1, -2)) if self.pre_scaled else torch.matmul(q, k.transpose(-1, -2)) * self.scale
+        if bias is not None:
+            s = s + bias
+        if mask is not None:
+            h, t = s.shape[1], s.shape[2]
+            s = (s.view(-1, int(windows), h, t, s.shape[3]) + mask).view(-1, h, t, s.shape[3])
+        o = torch.matmul(torch.softmax(s, dim=-1), v)
+        if self.merged:
+            o = o.permute(0, 2, 1, 3)
+            o = o.flatten(2) if self.flatten else o.reshape(*shape)
+        return self._torch_rows(o) if self.emit is not None else (o, None)
+
+    def forward(self, q, k, v, *rest):
+        terms = list(rest[:self.has_bias + 2 * self.has_mask])
+        shape = rest[len(terms):]
+        bias = terms.pop(0) if self.has_bias else None
+        mask, windows = terms if self.has_mask else (None, None)
+        ok = q.is_cuda and K.window_attention_views(q, k, v)
+        if ok:
+            b, h, t, d = q.shape
+            ok = bias is None or (bias.dtype == torch.float32 and bias.dim() in (3, 4) and tuple(bias.shape[-3:]) in ((h, t, t), (1, t, t))
+                                  and bias.numel() == bias.shape[-3] * t * t)
+            if ok and mask is not None:
+                ok = (mask.dtype == torch.float32 and mask.dim() == 5 and tuple(mask.shape[2:]) == (1, t, t) and mask.shape[0] == 1
+                      and int(windows) == mask.shape[1] and b % mask.shape[1] == 0)
+        if ok and self.merged:
+            want = [b, t, h * d]
+            if not self.flatten:      # (AttentionLayer's rule: a reshape to three dimensions that merges the heads)
+                dims = [int(x) for x in shape]
+                free = [i for i, x in enumerate(dims) if x == -1]
+                if len(free) == 1 and all(x == y for i, (x, y) in enumerate(zip(dims, want)) if i != free[0]):
+                    dims = want
+                ok = dims == want
+            ok = ok and (self.emit is None or h * d == self.c)
+        if not ok:
+            return self._torch(q, k, v, bias, mask, windows, shape)
+        emit = None if self.emit is None else self.emit.emit(q.numel())
+        out, codes = K.window_attention_quant(q, k, v, self.scale, bias=bias, mask=mask, emit=emit, want_out=self.want_out)
+        return (out, codes) if self.merged else (out.view(b, t, h, d).permute(0, 2, 1, 3), None)
+
+
+def _scaled_scores(node):
+    """(q, k, c, pre_scaled, the nodes it is made of) if `node` is `matmul(q, k.transpose(-1, -2)) * c` or `matmul(q * c, k.transpose(
+    -1, -2))`, c a finite Python float on either side of its multiply, every intermediate read once - else None."""
+    def times_float(n):
+        if not _is_call(n, _MUL_FNS, "mul") or len(n.args) != 2:
+            return None
+        x, c = n.args if isinstance(n.args[0], fx.Node) else n.args[::-1]
+        return (x, c) if isinstance(x, fx.Node) and isinstance(c, float) and math.isfinite(c) else None
+
+    made_of, c = [node], None
+    if times_float(node) is not None:
+        node, c = times_float(node)
+        if _sole_user(node) is None:
+            return None
+        made_of.append(node)
+    if not _is_call(node, _MATMUL_FNS, "matmul") or len(node.args) != 2:
+        return None
+    q, kt = node.args
+    pre = c is None
+    if pre:
+        if not isinstance(q, fx.Node) or times_float(q) is None or _sole_user(q) is None:
+            return None
+        made_of.append(q)
+        q, c = times_float(q)
+    if not isinstance(q, fx.Node) or _sole_user(kt) is None or not _is_call(kt, (torch.transpose,), "transpose") or len(kt.args) != 3:
+        return None
+    k, d0, d1 = kt.args
+    if not isinstance(k, fx.Node) or {d0, d1} not in ({-1, -2}, {2, 3}, {-1, 2}, {-2, 3}) or isinstance(d0, bool) or isinstance(d1, bool):
+        return None
+    return q, k, c, pre, made_of + [kt]
+
+
+def _plus_term(node):
+    """The two operands if `node` is an out-of-place add of two graph values, else None."""
+    if not isinstance(node, fx.Node) or not _is_add(node) or _inplace_add(node):
+        return None
+    return node.args
+
+
+def _window_attention_core(node, modules):
+    """(q, k, v, c, pre_scaled, bias value or None, (mask value, the view's nW) or None, the nodes it is made of) if `node` is the last node of
+    `matmul(softmax(S, dim=-1), v)` with S the scaled scores (_scaled_scores) carrying at least one of `+ bias` and Swin's mask
+    spelling `(S.view(B // nW, nW, H, T, T) + mask5).view(-1, H, T, T)`, bias before mask, every intermediate read once - else None."""
+    if not _is_call(node, _MATMUL_FNS, "matmul") or len(node.args) != 2:
+        return None
+    attn, v = node.args
+    s = _softmax_of(attn, modules)
+    if s is None or not isinstance(v, fx.Node) or _sole_user(attn) is None or _sole_user(s) is None:
+        return None
+    made_of, bias, mask = [node, attn], None, None
+
+    def is_view(n, sizes):
+        return isinstance(n, fx.Node) and n.op == "call_method" and n.target in ("view", "reshape") and not n.kwargs and len(n.args) == 1 + sizes
+
+    if is_view(s, 4) and isinstance(s.args[0], fx.Node) and _sole_user(s.args[0]) is not None and _plus_term(s.args[0]) is not None:
+        add = s.args[0]
+        a, b = _plus_term(add)
+        five, mask = (a, b) if is_view(a, 5) else (b, a)
+        if not is_view(five, 5) or _sole_user(five) is None or not isinstance(five.args[0], fx.Node) or _sole_user(five.args[0]) is None:
+            return None
+        mask = (mask, five.args[2])
+        made_of += [s, add, five]
+        s = five.args[0]
+    core = _scaled_scores(s)
+    if core is None and _plus_term(s) is not None:
+        for x, t in (s.args, s.args[::-1]):
+            core = _scaled_scores(x) if _sole_user(x) is not None else None
+            if core is not None:
+                bias = t
+                made_of.append(s)
+                break
+    if core is None or (bias is None and mask is None):
+        return None
+    q, k, c, pre, nodes_ = core
+    return q, k, v, c, pre, bias, mask, made_of + nodes_
+
+
+def _window_attention_pass(gm, report, planned, dry_run):
+    """Window attention (fuse_inference(window_attention=True)): the core `softmax(q k^T * c + bias + mask) v` (_window_attention_core)
+    becomes one node (WindowAttentionLayer, csrc/window_attention.hip); the merge-heads tail and the Linear code readers are the
+    attention pass's.  The core without an additive term is not taken: it is `attention=True`'s."""
+    def match(node, modules):
+        core = _window_attention_core(node, modules) if node.op in ("call_function", "call_method") else None
+        if core is None:
+            return None
+        q, k, v, scale, pre, bias, mask, made_of = core
+        if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:
+            return None
+        perm, shape, sizes = _merge_heads_tail(node) or (None, None, ())
+        taken = _code_readers(planned, shape, linear=True) if shape is not None else None
+        if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
+            taken = _CodeReaders(None, [], True, 0, 0, 0, False)
+        ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, pre_scaled=pre,
+                    has_bias=bias is not None, has_mask=mask is not None, flatten=sizes is None)
+        args = (q, k, v) + (() if bias is None else (bias,)) + (mask or ())
+        if shape is None:
+            return _Splice(WindowAttentionLayer, ctor, node, args, [], made_of)
+        return _Splice(WindowAttentionLayer, ctor, shape, args + (sizes or ()), taken.takers, [shape, perm] + made_of)
+    _run_node_pass(gm, report, "window_attention", "window_attentions", match, dry_run)
+
+
 _GELU_ALPHA = 0.70710678118654752440      # 1 / sqrt(2): as a Python scalar torch multiplies an fp32 tensor by its fp32 rounding
 
 
@@ -2382,6 +2543,7 @@ class FusionReport:
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
         self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
+        self.window_attentions = 0   # biased / masked window attention cores running as one launch (fuse_inference(window_attention=True))
         self.patch_rows = 0   # patch rearrangements handing the embedding its codes from one read of the image (fuse_inference(patch_embed=True))
         self.token_assemblies = 0   # class-token concatenations + position embeddings running as one launch (fuse_inference(patch_embed=True))
         self.patch_embed_left = []  # (graph node, why): candidates of the patch-embedding pass that were left as they are
@@ -2420,6 +2582,7 @@ class FusionReport:
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
                 (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
+                (f"window attentions on the plan={self.window_attentions}, " if self.window_attentions else "") +
                 (f"patch rows on the plan={self.patch_rows}, " if self.patch_rows else "") +
                 (f"token assemblies on the plan={self.token_assemblies}, " if self.token_assemblies else "") +
                 (f"patch embedding left alone={self.patch_embed_left}, " if self.patch_embed_left else "") +
@@ -2962,7 +3125,7 @@ class _MainPass:
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
                    recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False,
-                   patch_embed=False, squeezes=False, hardswish=False):
+                   patch_embed=False, squeezes=False, hardswish=False, window_attention=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -3165,7 +3328,18 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     the swish pass, before the gate pass.  Measured (tools/hardswish_ab.py, profiles/hardswish_ab.json; batch 256 at 224^2, gates and dw5
     on in both, interleaved): MobileNetV3-Large flag off / on = 6.61 / 5.17 ms per step (FSPTQ W8A8), 6.56 / 5.15 (QBase W8A8), beyond the
     run-to-run spread; MobileNetV3-Small 3.69 / 3.78 and 3.34 / 3.32, inside it; logits equal in all four.  Off by default: the plan
-    without it is the plan as it was."""
+    without it is the plan as it was.
+    `window_attention=True`: the attention of a windowed transformer (`workloads.window_vit()`; Swin, LeViT, BEiT) -
+    `matmul(softmax(S, dim=-1), v)` with S = `matmul(q, k.transpose(-1, -2)) * c` or `matmul(q * c, k.transpose(-1, -2))`, c a Python
+    float, carrying at least one of `+ bias` (a graph value that broadcasts as [H, T, T] or [1, H, T, T]: the relative-position bias) and
+    Swin's shift mask `(S.view(B // nW, nW, H, T, T) + mask.unsqueeze(1).unsqueeze(0)).view(-1, H, T, T)`, bias before mask, every
+    intermediate read once - becomes one WindowAttentionLayer node (csrc/window_attention.hip: one wave per (window, head) holds the
+    whole score tile, T <= 64, D 32 or 64; the stated operation order and error bound of include/dlmcq.h;
+    `fusion_report.window_attentions` counts the nodes).  The merge-heads tail and the Linear code readers are `attention=True`'s.
+    Left alone: the core without an additive term (that is `attention=True`'s, and the two flags do not meet), a term added in place, a
+    second reader of an intermediate.  At run time anything the kernel refuses - more than 64 tokens, another head dimension, tensors
+    that are not fp32 device views read in place, terms of another shape - takes the node's torch restatement: the graph's own ops.
+    Runs after the LayerNorm, GELU and attention passes.  Off by default: the plan without it is the plan as it was."""
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -3202,6 +3376,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _gelu_pass(gm, report, planned, dry_run, dwpw)
     if attention:
         _attention_pass(gm, report, planned, dry_run)
+    if window_attention:      # (the cores with an additive term, which the attention pass leaves alone)
+        _window_attention_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and (not dry_run or dry_run == "chains"):

@@ -453,6 +453,89 @@ class ViT(nn.Module):
         return self.head(self.norm(x[:, 0]))
 
 
+class WindowAttention(nn.Module):
+    """Self-attention inside windows of `window` x `window` tokens (public architecture: Swin, Liu et al. 2021) on [B * nW, T, dim],
+    T = window^2, window index fastest: a packed qkv Linear, softmax(q k^T / sqrt(d) + bias + mask) v per head, one Linear back.  The
+    relative-position bias [heads, T, T] is gathered from a learned table of (2 window - 1)^2 offsets per head at every call;
+    `shift_mask`: the [nW, T, T] mask of a shifted block, 0 between tokens of one region and -100 else, for `grid` x `grid` windows
+    shifted by half a window."""
+
+    def __init__(self, dim, heads, window, shift_mask=False, grid=2):
+        super().__init__()
+        if dim % heads:
+            raise ValueError(f"WindowAttention: dim {dim} is no multiple of {heads} heads")
+        self.heads, self.dim_head, self.tokens = heads, dim // heads, window * window
+        self.to_qkv = nn.Linear(dim, 3 * dim)
+        self.to_out = nn.Linear(dim, dim)
+        self.bias_table = nn.Parameter(torch.randn((2 * window - 1) ** 2, heads) * 0.02)
+        at = torch.stack(torch.meshgrid(torch.arange(window), torch.arange(window), indexing="ij")).flatten(1)      # [2, T]
+        rel = at[:, :, None] - at[:, None, :] + window - 1
+        self.register_buffer("bias_index", (rel[0] * (2 * window - 1) + rel[1]).reshape(-1))
+        mask = None
+        if shift_mask:
+            side, shift = grid * window, window // 2
+            region = torch.zeros(side, side)
+            edges = (slice(0, -window), slice(-window, -shift), slice(-shift, None)) if shift else (slice(None),)
+            for i, rows in enumerate(edges):
+                for j, cols in enumerate(edges):
+                    region[rows, cols] = i * len(edges) + j
+            region = region.reshape(grid, window, grid, window).permute(0, 2, 1, 3).reshape(grid * grid, self.tokens)
+            differ = region[:, None, :] != region[:, :, None]
+            mask = torch.where(differ, -100.0, 0.0)
+        self.register_buffer("mask", mask)
+
+    def forward(self, x):
+        qkv = self.to_qkv(x)
+        b, t, heads = qkv.shape[0], self.tokens, self.heads
+        qkv = qkv.reshape(b, t, 3, heads, self.dim_head).permute(2, 0, 3, 1, 4)      # [3, B nW, heads, T, d]
+        q, k, v = qkv[0], qkv[1], qkv[2]
+        attn = torch.matmul(q, k.transpose(-1, -2)) * self.dim_head ** -0.5
+        bias = self.bias_table[self.bias_index].view(t, t, heads).permute(2, 0, 1).contiguous()
+        attn = attn + bias.unsqueeze(0)
+        if self.mask is not None:
+            windows = self.mask.shape[0]
+            attn = attn.view(b // windows, windows, heads, t, t) + self.mask.unsqueeze(1).unsqueeze(0)
+            attn = attn.view(-1, heads, t, t)
+        out = torch.matmul(torch.softmax(attn, dim=-1), v).permute(0, 2, 1, 3).reshape(b, t, heads * self.dim_head)
+        return self.to_out(out)
+
+
+class WindowBlock(nn.Module):
+    """ViTBlock with WindowAttention: x = attn(norm(x)) + x; x = ff(norm(x)) + x on window tokens [B * nW, T, dim]."""
+
+    def __init__(self, dim, heads, window, mlp_dim, shift_mask, grid):
+        super().__init__()
+        self.norm1, self.attn = nn.LayerNorm(dim), WindowAttention(dim, heads, window, shift_mask, grid)
+        self.norm2, self.fc1, self.act, self.fc2 = nn.LayerNorm(dim), nn.Linear(dim, mlp_dim), nn.GELU(), nn.Linear(mlp_dim, dim)
+
+    def forward(self, x):
+        x = self.attn(self.norm1(x)) + x
+        return self.fc2(self.act(self.fc1(self.norm2(x)))) + x
+
+
+class WindowViT(nn.Module):
+    """A few pre-norm window-attention blocks, alternately unmasked and masked, on a [B, dim, grid window, grid window] map: the map
+    is partitioned into grid^2 windows of window^2 tokens by plain reshapes ([B * nW, T, dim]), runs through the stack, is put back
+    (the reverse reshapes), averaged over its tokens and classified.  No roll between the blocks: the masked blocks exercise the mask's
+    arithmetic, not Swin's shifted geometry."""
+
+    def __init__(self, dim=128, heads=4, window=7, grid=2, depth=4, mlp_ratio=4, num_classes=1000):
+        super().__init__()
+        if dim % 64:
+            raise ValueError(f"WindowViT: dim {dim} is no multiple of 64")
+        self.dim, self.window, self.grid = dim, window, grid
+        self.blocks = nn.Sequential(*[WindowBlock(dim, heads, window, mlp_ratio * dim, bool(i % 2), grid) for i in range(depth)])
+        self.norm = nn.LayerNorm(dim)
+        self.head = nn.Linear(dim, num_classes)
+
+    def forward(self, x):
+        g, w, c = self.grid, self.window, self.dim
+        x = x.reshape(-1, c, g, w, g, w).permute(0, 2, 4, 3, 5, 1).reshape(-1, w * w, c)       # partition: [B nW, T, dim]
+        x = self.blocks(x)
+        x = x.reshape(-1, g, g, w, w, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, g * w * g * w, c)      # reverse: [B, all tokens, dim]
+        return self.head(self.norm(x.mean(1)))
+
+
 def _init(model):
     for m in model.modules():
         if isinstance(m, nn.Conv2d):
@@ -512,6 +595,12 @@ def vit_tiny(num_classes=1000):
 def vit_small(num_classes=1000):
     """ViT-S/16: dim 384, depth 12, 6 heads of 64, MLP 1536, 224^2 images (197 tokens)."""
     return ViT(224, 16, num_classes, dim=384, depth=12, heads=6, mlp_dim=1536)
+
+
+def window_vit(num_classes=1000, dim=128, heads=4, window=7, grid=2, depth=4):
+    """Window-attention blocks at Swin-T's stage-1 head shape (T = 49 tokens per window, heads of 32) on a [B, dim, 14, 14] map: 4 windows
+    per image, `depth` blocks, every second one with the shift mask."""
+    return WindowViT(dim, heads, window, grid, depth, 4, num_classes)
 
 
 def _named_option(option):

@@ -1136,6 +1136,43 @@ int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* o
                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                         dlmcq_stream_t stream);
 
+/* ---- Window attention softmax(scale q k^T + bias + mask) v, T <= 64: fp32 and / or the activation codes of the projection behind it ----
+ * The attention of a windowed transformer (csrc/window_attention.hip): one wave per (b, h) holds the whole T x T score tile, so there
+ * is no key stream, no running maximum and no rescale.  T = Tq = Tk.  For query row i of one (b, h), u = 2^-24:
+ *     a_ij = the k-ordered fmaf chain over D from +0 (v_mfma_f32_32x32x2_f32), as in dlmcq_attention_f32
+ *     s_ij = fl32(a_ij * scale)
+ *     s_ij = fl32(s_ij + bias[h bias_sh + i bias_st + j])              if bias
+ *     s_ij = fl32(s_ij + mask[(b % nW) mask_sw + i mask_st + j])       if mask     (bias first, then mask: Swin's order)
+ *     m    = max_j s_ij (NaNs dropped: a NaN score reaches p instead);  m~ = m, or 0 where m = -inf
+ *     p_ij = expf(fl32(s_ij - m~))            the device library's accurate expf (1 ulp)
+ *     l    = fl32(t_0 + t_1), t_h (h = bit 2 of the key index) the half's p_ij added one by one in ascending key order
+ *     w_g  = the chain fmaf(v_j[c], p_ij, w_g) from +0 over keys 8 g .. 8 g + 7 of a 32-key block in the order 0 4 1 5 2 6 3 7 (+ 8 g)
+ *     o_ic = fl32(fl32(w_0 + w_1) + fl32(w_2 + w_3)) of block 0, for T > 32 plus the same of block 1
+ *     out  = fl32(o_ic / l)                   a true division;  code = the quantiser of out, as in dlmcq_attention_f32 (plain codes only)
+ * A -inf bias or mask entry removes its key; a row whose every key is -inf is NaN (0 / 0, as torch's softmax) and its neighbours are
+ * untouched; NaNs in q, k, v and a +inf score propagate as in dlmcq_attention_f32.
+ * Against real arithmetic on the same fp32 inputs, nb = ceil(T / 32), t = how many of bias and mask are given, kappa = 2 (104 + 2 + 32 nb) + 1,
+ *     delta_i = max over the finite keys j of (D + 1) u |scale| sum_k |q_ik k_jk| + t u (|scale a*_ij| + |bias_ij| + |mask_ij|):
+ *     |out_ic - o*_ic| <= (2 delta_i + kappa u) sum_j p*_ij |v_jc| + 2^-126 max_j |v_jc|       (csrc/window_attention.hip derives it)
+ * No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.
+ *   q, k, v  fp32 views [B, H, T, D], D in {32, 64}, strides and alignment as in dlmcq_attention_f32 (the packed projection output in place)
+ *   bias     fp32 view [H, T, T] or NULL: head stride bias_sh, row stride bias_st >= T, both multiples of 4, unit stride in the key
+ *            index, 16-byte aligned.  A row is read in 16-byte pieces: the piece that holds key T - 1 is read whole, so the
+ *            (T + 3) / 4 * 4 floats of every row must be readable (what lies past key T - 1 is ignored)
+ *   mask     fp32 view [nW, T, T] or NULL, likewise (mask_sw, mask_st): row b % nW applies to batch element b.  nW is not read without it
+ *   out, codes   the merged heads through o_sb, o_sh, o_st, as in dlmcq_attention_f32; either may be NULL
+ * DLMCQ_EINVAL: B or H < 0, T not in 1 .. 64, D not 32 or 64, scale not finite, a q / k / v / out stride negative or no multiple of 4, a
+ * token stride below D, a bias or mask stride negative or no multiple of 4 or a row stride below T, a mask with nW < 1 or B % nW != 0,
+ * q / k / v NULL, both outputs NULL, an invalid quantiser, any control or layout bit or DLMCQ_EMIT_SHIFT128 in q_form.  DLMCQ_EALIGN:
+ * q / k / v / bias / mask / out not 16-byte aligned, codes not 4-byte aligned.  DLMCQ_ERANGE: B, H or B * H + 4 reaches 2^31.
+ * B * H == 0: DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+int dlmcq_window_attention_f32(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
+                               void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
+                               int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
+                               int64_t o_sb, int64_t o_sh, int64_t o_st, int64_t bias_sh, int64_t bias_st, int64_t mask_sw,
+                               int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                               int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 /* ---- A vision transformer's patch rows: an fp32 image batch to fp32 rows and / or the activation codes of the embedding ----
  * The rearrangement 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' of an image batch [B, C, gh p, gw p] into rows [B gh gw, p p C]:
  *     row (b gh + gy) gw + gx, column (py p + px) C + c  =  img[b sb + c sc + (gy p + py) sh + gx p + px]
