@@ -46,18 +46,6 @@ namespace dlmcq {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#define DLMCQ_AT_WAVES 4
-#define DLMCQ_AT_ROWS (32 * DLMCQ_AT_WAVES)      // query rows per workgroup
-#define DLMCQ_AT_KB 32                           // keys per block
-
-struct AttnArgs {
-  const float *q, *k, *v;
-  float* out;
-  int64_t qs[3], ks[3], vs[3], os[3];      // element strides (batch, head, token)
-  int H, Tq, Tk, tiles;
-  float scale;
-};
-
 template <int D>
 __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs a, ConvEpi ep) {
   constexpr int KS = D + 2, VS = D + 8, D4 = D / 4, CB = D / 32;
@@ -177,30 +165,20 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
 
 using namespace dlmcq;
 
-// The checks: geometry (sizes, D, strides, scale), emit_set_quantiser (csrc/conv_gap.h; plain codes only: the reader is a Linear
-// layer), an empty problem, emit_check_pointers, the 2^31 limits.
+// The checks: attention_args (csrc/conv_gap.h), shared with dlmcq_attention_f16.
 extern "C" int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
                                    int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
                                    int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
                                    const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                                    dlmcq_stream_t stream) {
-  if (B < 0 || H < 0 || Tq < 0 || Tk < 1 || (D != 32 && D != 64) || !(scale == scale) || !(scale > -3.402823466e+38f && scale < 3.402823466e+38f))
-    return DLMCQ_EINVAL;
   const int64_t strides[12] = {q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st};
-  for (int i = 0; i < 12; ++i)
-    if (strides[i] < 0 || strides[i] % 4 != 0) return DLMCQ_EINVAL;
-  if (q_st < D || k_st < D || v_st < D || o_st < D) return DLMCQ_EINVAL;      // (unit stride in D: a token's row does not overlap the next)
-  ConvEpi ep{};
-  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
-  if (rc != DLMCQ_OK) return rc;
-  if (B == 0 || H == 0 || Tq == 0) return DLMCQ_OK;
-  rc = emit_check_pointers({q, k, v}, {}, out, codes, 4);
-  if (rc != DLMCQ_OK) return rc;
-  constexpr int64_t LIM = 1ll << 31;
-  const int64_t tiles = (Tq + DLMCQ_AT_ROWS - 1) / DLMCQ_AT_ROWS;
-  if (B >= LIM || H >= LIM || Tq >= LIM || Tk >= LIM || B * H >= LIM || B * H * tiles >= LIM) return DLMCQ_ERANGE;
-  AttnArgs a{q, k, v, out, {q_sb, q_sh, q_st}, {k_sb, k_sh, k_st}, {v_sb, v_sh, v_st}, {o_sb, o_sh, o_st}, (int)H, (int)Tq, (int)Tk, (int)tiles, scale};
-  const dim3 grid((uint32_t)(B * H * tiles)), block(64 * DLMCQ_AT_WAVES);
+  AttnArgs a;
+  ConvEpi ep;
+  int64_t blocks;
+  const int rc = attention_args(a, ep, &blocks, q, k, v, out, codes, B, H, Tq, Tk, D, strides, scale, q_scale, q_zero_point, q_lo, q_hi, q_form,
+                                q_ste_g);
+  if (rc != DLMCQ_OK || blocks == 0) return rc;
+  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_AT_WAVES);
   if (D == 64) hipLaunchKernelGGL((attention_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
   else hipLaunchKernelGGL((attention_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
   return launch_status();

@@ -53,4 +53,46 @@ static inline int emit_check_pointers(std::initializer_list<const void*> require
   return (!aligned16(out) || ((uintptr_t)codes & (codes_align - 1))) ? DLMCQ_EALIGN : DLMCQ_OK;
 }
 
+// What the two attention entry points (attention.hip, attention_f16.hip) share: the kernel arguments and the host checks in front of
+// the launch.  A workgroup of either kernel owns DLMCQ_AT_ROWS query rows of one (b, h).
+#define DLMCQ_AT_WAVES 4
+#define DLMCQ_AT_ROWS (32 * DLMCQ_AT_WAVES)      // query rows per workgroup
+#define DLMCQ_AT_KB 32                           // keys per block
+
+struct AttnArgs {
+  const float *q, *k, *v;
+  float* out;
+  int64_t qs[3], ks[3], vs[3], os[3];      // element strides (batch, head, token)
+  int H, Tq, Tk, tiles;
+  float scale;
+};
+
+// The checks: geometry (sizes, D, strides, scale), emit_set_quantiser (plain codes only: the reader is a Linear layer), an empty
+// problem (DLMCQ_OK with *grid = 0: nothing to launch), emit_check_pointers, the 2^31 limits.  Else `a`, `ep` and *grid are set.
+static inline int attention_args(AttnArgs& a, ConvEpi& ep, int64_t* grid, const float* q, const float* k, const float* v, float* out,
+                                 void* codes, int64_t B, int64_t H, int64_t Tq, int64_t Tk, int64_t D, const int64_t (&strides)[12],
+                                 float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
+                                 float q_ste_g) {
+  *grid = 0;
+  if (B < 0 || H < 0 || Tq < 0 || Tk < 1 || (D != 32 && D != 64) || !(scale == scale) || !(scale > -3.402823466e+38f && scale < 3.402823466e+38f))
+    return DLMCQ_EINVAL;
+  for (int i = 0; i < 12; ++i)
+    if (strides[i] < 0 || strides[i] % 4 != 0) return DLMCQ_EINVAL;
+  for (int i = 2; i < 12; i += 3)
+    if (strides[i] < D) return DLMCQ_EINVAL;      // (unit stride in D: a token's row does not overlap the next)
+  ep = ConvEpi{};
+  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
+  if (rc != DLMCQ_OK) return rc;
+  if (B == 0 || H == 0 || Tq == 0) return DLMCQ_OK;
+  rc = emit_check_pointers({q, k, v}, {}, out, codes, 4);
+  if (rc != DLMCQ_OK) return rc;
+  constexpr int64_t LIM = 1ll << 31;
+  const int64_t tiles = (Tq + DLMCQ_AT_ROWS - 1) / DLMCQ_AT_ROWS;
+  if (B >= LIM || H >= LIM || Tq >= LIM || Tk >= LIM || B * H >= LIM || B * H * tiles >= LIM) return DLMCQ_ERANGE;
+  a = AttnArgs{q, k, v, out, {strides[0], strides[1], strides[2]}, {strides[3], strides[4], strides[5]}, {strides[6], strides[7], strides[8]},
+               {strides[9], strides[10], strides[11]}, (int)H, (int)Tq, (int)Tk, (int)tiles, scale};
+  *grid = B * H * tiles;
+  return DLMCQ_OK;
+}
+
 }  // namespace dlmcq

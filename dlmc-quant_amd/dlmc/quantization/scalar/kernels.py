@@ -1573,7 +1573,8 @@ def assemble_tokens(e, cls, pos):
     return out
 
 
-ATTENTION_DIMS = (32, 64)    # dlmcq_attention_f32: the head dimensions the kernel is built for
+ATTENTION_DIMS = (32, 64)    # dlmcq_attention_f32 / _f16: the head dimensions the kernels are built for
+ATTENTION_OPERANDS = ("f32", "f16")    # attention_quant(operands=...): the matrix-core operand type, dlmcq_attention_f32 / dlmcq_attention_f16
 
 
 def attention_views(q, k, v):
@@ -1591,13 +1592,19 @@ def attention_views(q, k, v):
     return True
 
 
-def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True):
+def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True, operands="f32"):
     """softmax(scale * q k^T) v of fp32 views `q` [B, H, Tq, D], `k`, `v` [B, H, Tk, D] (attention_views: read in place, the three
     slices of one packed projection included) by dlmcq_attention_f32: one flash forward on the f32 matrix cores - k-ordered fmaf
     chains, an online softmax over key blocks of 32 with the accurate expf, a true division at the end (include/dlmcq.h states the
     order and the bound); no mask, no dropout.  `merged`: the result as [B, Tq, H * D], the merge-heads permute + reshape a free view;
     else [B, H, Tq, D].  Returns `(out or None, codes or None)`: fp32 unless `want_out=False`, and with `emit=EmitCodes(...)` the
-    consumer's activation codes of the same values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error)."""
+    consumer's activation codes of the same values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error).
+    `operands="f16"`: dlmcq_attention_f16 instead - the same flash forward with q, k, v and the softmax weights rounded to f16 as
+    operands of the f16 matrix cores, fp32 everywhere else (csrc/attention_f16.hip states the arithmetic, the bound and the range
+    limit: inputs above 65504 in magnitude become infinite); recorded as PROFILE launch "attention_f16".  Opt-in: the default is the
+    fp32 kernel, bit for bit."""
+    if operands not in ATTENTION_OPERANDS:
+        raise ValueError(f"attention_quant: operands is one of {ATTENTION_OPERANDS}, not {operands!r}")
     N.require_gpu(q, k, v)
     if not attention_views(q, k, v):
         raise ValueError("attention_quant: fp32 views q [B, H, Tq, D], k, v [B, H, Tk, D], D in (32, 64), unit stride in D, strides "
@@ -1613,7 +1620,8 @@ def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True):
     shape = (b, tq, h * d) if merged else (b, h, tq, d)
     o_strides = (tq * h * d, d, h * d) if merged else (h * tq * d, tq * d, d)
     nbytes = 4 * b * h * d * (tq + 2 * tk) + b * h * tq * d * (4 * want_out + (emit is not None))
-    return _emit_launch("attention_quant", "attention", q, shape, emit, want_out, nbytes, lambda op, cp, *tail: N.lib.dlmcq_attention_f32(
+    entry, tag = (N.lib.dlmcq_attention_f16, "attention_f16") if operands == "f16" else (N.lib.dlmcq_attention_f32, "attention")
+    return _emit_launch("attention_quant", tag, q, shape, emit, want_out, nbytes, lambda op, cp, *tail: entry(
         N.ptr(q), N.ptr(k), N.ptr(v), op, cp, b, h, tq, tk, d, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o_strides, scale, *tail),
         ops=4 * b * h * tq * tk * d)
 

@@ -1489,10 +1489,15 @@ class AttentionLayer(_MapCodesLayer):
     graph's F.scaled_dot_product_attention call; `flatten`: the tail is `flatten(2)`, else the reshape's three shape arguments arrive
     at run time (graph values, checked there).  Not merged: [B, H, Tq, D], fp32 only.  The torch restatement - the graph's own ops,
     then K.fake_quant - runs for anything that is not three fp32 device views the kernel reads in place (K.attention_views) with
-    D in K.ATTENTION_DIMS, a merged width other than H * D or `c`.  Returns `(fp32 or None, codes or None)`."""
+    D in K.ATTENTION_DIMS, a merged width other than H * D or `c`.  `operands`: "f32" (csrc/attention.hip, the default) or "f16"
+    (csrc/attention_f16.hip: f16 operands on the f16 matrix cores, fp32 everywhere else; fuse_inference(attention="f16")) - the
+    kernel's operand type alone: the torch restatement is the same.  Returns `(fp32 or None, codes or None)`."""
 
-    def __init__(self, emit, want_out, c, scale, merged, sdpa=None, flatten=False):
+    def __init__(self, emit, want_out, c, scale, merged, sdpa=None, flatten=False, operands="f32"):
         super().__init__(emit, want_out, c, c, 0, False)
+        if operands not in K.ATTENTION_OPERANDS:
+            raise ValueError(f"AttentionLayer: operands is one of {K.ATTENTION_OPERANDS}, not {operands!r}")
+        self.operands = operands
         self.scale, self.merged, self.flatten = (None if scale is None else float(scale)), bool(merged), bool(flatten)
         self.sdpa = None if sdpa is None else dict(sdpa)
 
@@ -1523,7 +1528,7 @@ class AttentionLayer(_MapCodesLayer):
             return self._torch(q, k, v, shape)
         scale = q.shape[-1] ** -0.5 if self.scale is None else self.scale
         emit = None if self.emit is None else self.emit.emit(q.numel())
-        return K.attention_quant(q, k, v, scale, emit=emit, want_out=self.want_out, merged=self.merged)
+        return K.attention_quant(q, k, v, scale, emit=emit, want_out=self.want_out, merged=self.merged, operands=self.operands)
 
 
 _MATMUL_FNS = (torch.matmul, operator.matmul)
@@ -1640,8 +1645,8 @@ def _merge_heads_tail(node):
     return (perm, shape, tuple(sizes)) if ok else None
 
 
-def _attention_pass(gm, report, planned, dry_run):
-    """Attention (fuse_inference(attention=True)): the core `softmax(q k^T * c) v` (_attention_core) becomes one node (AttentionLayer,
+def _attention_pass(gm, report, planned, dry_run, operands="f32"):
+    """Attention (fuse_inference(attention=True), or attention="f16": the same nodes with `operands` "f16"): the core `softmax(q k^T * c) v` (_attention_core) becomes one node (AttentionLayer,
     csrc/attention.hip).  With the merge-heads tail behind it (_merge_heads_tail) the node stands where the reshape stood, returns
     [B, Tq, H * D], and the Linear plan layers reading it - one quantiser, as for a LayerNorm - take its codes; anyone else reads the
     fp32 values of the same launch.  Without the tail it stands where the second product stood and returns fp32 [B, H, Tq, D].
@@ -1658,11 +1663,12 @@ def _attention_pass(gm, report, planned, dry_run):
         if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
             taken = _CodeReaders(None, [], True, 0, 0, 0, False)
         ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, sdpa=sdpa,
-                    flatten=sizes is None)
+                    flatten=sizes is None, operands=operands)
         if shape is None:
             return _Splice(AttentionLayer, ctor, node, (q, k, v), [], made_of)
         return _Splice(AttentionLayer, ctor, shape, (q, k, v) + (sizes or ()), taken.takers, [shape, perm] + made_of)
     _run_node_pass(gm, report, "attention", "attentions", match, dry_run)
+    report.attention_operands = operands if report.attentions else None
 
 
 class WindowAttentionLayer(_MapCodesLayer):
@@ -2543,6 +2549,7 @@ class FusionReport:
         self.layer_norms = 0  # LayerNorms handing the Linear plan layers behind them their codes (fuse_inference(layer_norms=True))
         self.gelus = 0        # erf-form GELUs handing the plan layers behind them their codes (fuse_inference(gelu=True))
         self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
+        self.attention_operands = None   # "f32" or "f16": the matrix-core operand type of those nodes (attention=True / attention="f16"); None without any
         self.window_attentions = 0   # biased / masked window attention cores running as one launch (fuse_inference(window_attention=True))
         self.patch_rows = 0   # patch rearrangements handing the embedding its codes from one read of the image (fuse_inference(patch_embed=True))
         self.token_assemblies = 0   # class-token concatenations + position embeddings running as one launch (fuse_inference(patch_embed=True))
@@ -2582,6 +2589,7 @@ class FusionReport:
                 (f"layer norms on the plan={self.layer_norms}, " if self.layer_norms else "") +
                 (f"gelus on the plan={self.gelus}, " if self.gelus else "") +
                 (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
+                (f"attention operands={self.attention_operands}, " if self.attention_operands == "f16" else "") +
                 (f"window attentions on the plan={self.window_attentions}, " if self.window_attentions else "") +
                 (f"patch rows on the plan={self.patch_rows}, " if self.patch_rows else "") +
                 (f"token assemblies on the plan={self.token_assemblies}, " if self.token_assemblies else "") +
@@ -3282,6 +3290,10 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     anything that is not three fp32 device views the kernel reads in place (unit stride in D, strides multiples of 4 elements, 16-byte
     aligned, D 32 or 64), or a reshape that turns out not to merge the heads, takes the node's torch restatement: the graph's own ops.
     Runs after the LayerNorm and GELU passes.  Off by default: the plan without it is the plan as it was.
+    `attention="f16"`: the same cores, planned the same way, on csrc/attention_f16.hip - q, k, v and the softmax
+    weights rounded to f16 as operands of the f16 matrix cores, fp32 accumulation, softmax and division; its own stated arithmetic
+    and error bound, inputs above 65504 in magnitude become infinite.  `fusion_report.attention_operands` says which operand type the
+    nodes run ("f32" for `attention=True`); the torch restatement is the same.  Any other value is refused.
     `patch_embed=True`: what stands in front of a vision transformer's first block (`workloads.vit_small()`).  The
     rearrangement `reshape | view(-1, C, g1, p, g2, p) -> permute(0, 2, 4, 3, 5, 1) -> reshape | view(-1, g1 * g2, p * p * C)` - every
     size a Python int, each node read by the next alone, p % 4 == 0, a strip of g2 * p * p * C elements within 65536 - read by Linear
@@ -3340,6 +3352,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     second reader of an intermediate.  At run time anything the kernel refuses - more than 64 tokens, another head dimension, tensors
     that are not fp32 device views read in place, terms of another shape - takes the node's torch restatement: the graph's own ops.
     Runs after the LayerNorm, GELU and attention passes.  Off by default: the plan without it is the plan as it was."""
+    if not any(attention is v for v in (False, True)) and not (isinstance(attention, str) and attention == "f16"):
+        raise ValueError(f"fuse_inference: attention is False, True (fp32 operands) or 'f16', not {attention!r}")
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
         raise ValueError(f"fuse_inference: gap_head is False, True, 'separate' or 'fused', not {gap_head!r}")
     if model.training:
@@ -3375,7 +3389,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     if gelu:
         _gelu_pass(gm, report, planned, dry_run, dwpw)
     if attention:
-        _attention_pass(gm, report, planned, dry_run)
+        _attention_pass(gm, report, planned, dry_run, "f16" if attention == "f16" else "f32")
     if window_attention:      # (the cores with an additive term, which the attention pass leaves alone)
         _window_attention_pass(gm, report, planned, dry_run)
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)

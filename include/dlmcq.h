@@ -1136,6 +1136,31 @@ int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* o
                         const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
                         dlmcq_stream_t stream);
 
+/* ---- The same attention on the f16 matrix cores: fp32 in and out, f16 operands (opt-in) ----
+ * dlmcq_attention_f32's flash forward, arguments, views, strides, alignment, refusals, empty-problem rule and quantiser tail, with q, k,
+ * v and the softmax weights as f16 operands of v_mfma_f32_32x32x16_f16 (csrc/attention_f16.hip).  The fp32 inputs are read in place and
+ * rounded inside the kernel; nothing 16-bit touches memory.  h(x) = x rounded to f16, nearest even; e = 2^-11; u = 2^-24:
+ *     c    = fl32(scale * log2 e)             the scale folded into a base-2 exponent, rounded once on the host
+ *     a_ij = sum_k h(q_ik) h(k_jk)            exact products, fp32 accumulation; inside one MFMA neither the order nor round-to-nearest is claimed: bounded, not pinned
+ *     s_ij = fl32(a_ij * c);  keys past Tk - 1 hold -inf;  m', m~ as in dlmcq_attention_f32
+ *     al   = exp2(fl32(m - m~)),  p_ij = exp2(fl32(s_ij - m~))       the hardware exp2 (v_exp_f32, 1 ulp), not the library's expf
+ *     P_ij = h(p_ij)                          one rounding; below 2^-25 it is 0
+ *     l    = the fp32 sum of the ROUNDED weights P_ij (a balanced tree over a lane's 16, rescaled by al per block, two halves added last)
+ *     o_ic = fl32(o_ic * al) + sum_j h(v_jc) P_ij per block, exact products, fp32 accumulation (sums of integers below 2^24 are exact)
+ *     out_ic = fl32(o_ic / l)                 a true division;  code = the quantiser of out_ic, as in dlmcq_attention_f32 (plain codes only)
+ * Range: an input above 65504 in magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other, in k_j every row of
+ * the head, in v_j[c] channel c of every row of the head.  Not checked at run time.  NaNs and infinities propagate as in dlmcq_attention_f32.
+ * Against real arithmetic on the same fp32 inputs, with delta_i = ((2 e + e^2) + (2 D + 3) u) |scale| max_j sum_k |q_ik k_jk|, nb = ceil(Tk / 32),
+ * kappa = 2 (104 + 2 + 3 nb + 68 nb) + 1 and rho_i = expm1(2 delta_i + 3 e + 2^-20 + kappa u):
+ *     |out_ic - o*_ic| <= rho_i sum_j p*_ij |v_jc| + Tk 2^-24 max_j |v_jc| + 2^-25
+ * (csrc/attention_f16.hip derives it: two operand roundings per score term, one each of p and v, f16's subnormal range, the fp32 terms.)
+ * Arguments and return codes: dlmcq_attention_f32's, one for one. */
+int dlmcq_attention_f16(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
+                        int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
+                        int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
+                        const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g,
+                        dlmcq_stream_t stream);
+
 /* ---- Window attention softmax(scale q k^T + bias + mask) v, T <= 64: fp32 and / or the activation codes of the projection behind it ----
  * The attention of a windowed transformer (csrc/window_attention.hip): one wave per (b, h) holds the whole T x T score tile, so there
  * is no key stream, no running maximum and no rescale.  T = Tq = Tk.  For query row i of one (b, h), u = 2^-24:
