@@ -47,20 +47,6 @@
 
 namespace dlmcq {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define DLMCQ_WA_WAVES 4      // (b, h) pairs per workgroup
-#define DLMCQ_WA_TMAX 64
-
-struct WinAttnArgs {
-  const float *q, *k, *v, *bias, *mask;
-  float* out;
-  int64_t qs[3], ks[3], vs[3], os[3];      // element strides (batch, head, token)
-  int64_t bias_sh, bias_st, mask_sw, mask_st;
-  int H, T, nW, pairs;
-  float scale;
-};
-
 // row `row` of a [T, D] view as the operand of the 32x32x2 MFMA whose k steps walk D: element 2 s + half of the row in register s
 template <int D>
 __device__ __forceinline__ void load_operand_row(const float* base, int64_t row_stride, int row, int half, float (&r)[D / 2]) {
@@ -70,16 +56,6 @@ __device__ __forceinline__ void load_operand_row(const float* base, int64_t row_
     const f32x4 t = p[f];
     r[2 * f] = half ? t.y : t.x;
     r[2 * f + 1] = half ? t.w : t.z;
-  }
-}
-
-// s += the additive term's row `row` (this lane's query), keys key0 + 8 g .. + 3 in registers 4 g .. 4 g + 3: four 16-byte pieces
-__device__ __forceinline__ void add_term(f32x16& s, const float* row, int key0, int T) {
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int j = key0 + 8 * g;
-    const f32x4 t = *reinterpret_cast<const f32x4*>(row + (j < T ? j : 0));
-    s[4 * g] += t.x, s[4 * g + 1] += t.y, s[4 * g + 2] += t.z, s[4 * g + 3] += t.w;
   }
 }
 
@@ -201,34 +177,21 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
 
 using namespace dlmcq;
 
-// The checks, in map_codes_call's order: geometry (sizes, D, T, strides, scale, the additive terms' layout), emit_set_quantiser
-// (csrc/conv_gap.h; plain codes only: the reader is a Linear layer), an empty problem, emit_check_pointers, the 2^31 limits.
+// The checks: window_attention_args (csrc/conv_gap.h), shared with dlmcq_window_attention_f16.
 extern "C" int dlmcq_window_attention_f32(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
                                           void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
                                           int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
                                           int64_t o_sb, int64_t o_sh, int64_t o_st, int64_t bias_sh, int64_t bias_st, int64_t mask_sw,
                                           int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
                                           int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream) {
-  if (B < 0 || H < 0 || T < 1 || T > DLMCQ_WA_TMAX || (D != 32 && D != 64) || !(scale == scale) ||
-      !(scale > -3.402823466e+38f && scale < 3.402823466e+38f))
-    return DLMCQ_EINVAL;
   const int64_t strides[12] = {q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st};
-  for (int i = 0; i < 12; ++i)
-    if (strides[i] < 0 || strides[i] % 4 != 0) return DLMCQ_EINVAL;
-  if (q_st < D || k_st < D || v_st < D || o_st < D) return DLMCQ_EINVAL;      // (unit stride in D: a token's row does not overlap the next)
-  if (bias && (bias_sh < 0 || bias_sh % 4 != 0 || bias_st < T || bias_st % 4 != 0)) return DLMCQ_EINVAL;
-  if (mask && (nW < 1 || B % nW != 0 || mask_sw < 0 || mask_sw % 4 != 0 || mask_st < T || mask_st % 4 != 0)) return DLMCQ_EINVAL;
-  ConvEpi ep{};
-  int rc = emit_set_quantiser(ep, codes, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g, true);
-  if (rc != DLMCQ_OK) return rc;
-  if (B == 0 || H == 0) return DLMCQ_OK;
-  rc = emit_check_pointers({q, k, v}, {bias, mask}, out, codes, 4);
-  if (rc != DLMCQ_OK) return rc;
-  constexpr int64_t LIM = 1ll << 31;
-  if (B >= LIM || H >= LIM || B * H >= LIM - DLMCQ_WA_WAVES) return DLMCQ_ERANGE;
-  WinAttnArgs a{q, k, v, bias, mask, out, {q_sb, q_sh, q_st}, {k_sb, k_sh, k_st}, {v_sb, v_sh, v_st}, {o_sb, o_sh, o_st},
-                bias_sh, bias_st, mask_sw, mask_st, (int)H, (int)T, (int)(mask ? nW : 1), (int)(B * H), scale};
-  const dim3 grid((uint32_t)((B * H + DLMCQ_WA_WAVES - 1) / DLMCQ_WA_WAVES)), block(64 * DLMCQ_WA_WAVES);
+  WinAttnArgs a;
+  ConvEpi ep;
+  int64_t blocks;
+  const int rc = window_attention_args(a, ep, &blocks, q, k, v, bias, mask, out, codes, B, H, T, D, nW, strides, bias_sh, bias_st, mask_sw,
+                                       mask_st, scale, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
+  if (rc != DLMCQ_OK || blocks == 0) return rc;
+  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_WA_WAVES);
   if (D == 64) hipLaunchKernelGGL((window_attention_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
   else hipLaunchKernelGGL((window_attention_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
   return launch_status();

@@ -1626,7 +1626,8 @@ def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True, opera
         ops=4 * b * h * tq * tk * d)
 
 
-WINDOW_TOKENS = 64    # dlmcq_window_attention_f32: the most tokens of a window (one wave holds the T x T score tile)
+WINDOW_TOKENS = 64    # dlmcq_window_attention_f32 / _f16: the most tokens of a window (one wave holds the T x T score tile)
+WINDOW_ATTENTION_OPERANDS = ("f32", "f16")    # window_attention_quant(operands=...): dlmcq_window_attention_f32 / dlmcq_window_attention_f16
 
 
 def window_term_view(t, tokens):
@@ -1669,14 +1670,20 @@ def window_attention_views(q, k, v):
     return attention_views(q, k, v) and 1 <= q.shape[2] == k.shape[2] <= WINDOW_TOKENS
 
 
-def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want_out=True):
+def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want_out=True, operands="f32"):
     """softmax(scale * q k^T + bias + mask) v of fp32 views `q`, `k`, `v` [B, H, T, D] (window_attention_views: T <= 64, read in place, the
     three slices of one packed projection included) by dlmcq_window_attention_f32: one wave per (b, h), the whole score tile in registers
     (include/dlmcq.h states the order and the bound).  `bias`: fp32 [H, T, T] (or [1, H, T, T]) or None; `mask`: fp32 [nW, T, T] (or
     Swin's broadcast spellings [nW, 1, T, T], [1, nW, 1, T, T]) or None - row b % nW applies to batch element b, B % nW == 0; both are read
     in place where window_term_view holds, else copied - one copy per call - into rows padded to 4 floats; a [1, T, T] bias is shared by all heads.  Returns `(out or None, codes or None)`, the
     merged heads [B, T, H * D]: fp32 unless `want_out=False`, and with `emit=EmitCodes(...)` the consumer's activation codes of the same
-    values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error)."""
+    values (plain codes: the reader is a Linear layer; EmitCodes.shift128 is an error).
+    `operands="f16"`: dlmcq_window_attention_f16 instead - the same split, terms and outputs with q, k, v and the softmax weights rounded
+    to f16 as operands of the f16 matrix cores, fp32 everywhere else (csrc/window_attention_f16.hip states the arithmetic, the bound and
+    the range limit: inputs above 65504 in magnitude become infinite); recorded as PROFILE launch "window_attention_f16".  Opt-in: the
+    default is the fp32 kernel, bit for bit."""
+    if operands not in WINDOW_ATTENTION_OPERANDS:
+        raise ValueError(f"window_attention_quant: operands is one of {WINDOW_ATTENTION_OPERANDS}, not {operands!r}")
     N.require_gpu(q, k, v, *(t for t in (bias, mask) if t is not None))
     if not window_attention_views(q, k, v):
         raise ValueError("window_attention_quant: fp32 views q, k, v [B, H, T, D], T in 1 .. 64, D in (32, 64), unit stride in D, strides "
@@ -1696,8 +1703,10 @@ def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want
         raise ValueError(f"window_attention_quant: a mask of {nw} windows for a batch of {b}")
     terms = (bias is not None) + (mask is not None)
     nbytes = 4 * b * h * d * 3 * t + b * h * t * d * (4 * want_out + (emit is not None)) + 4 * t * t * (h * (bias is not None) + nw * (mask is not None))
-    return _emit_launch("window_attention_quant", "window_attention", q, (b, t, h * d), emit, want_out, nbytes,
-                        lambda op, cp, *tail: N.lib.dlmcq_window_attention_f32(
+    entry, tag = ((N.lib.dlmcq_window_attention_f16, "window_attention_f16") if operands == "f16" else
+                  (N.lib.dlmcq_window_attention_f32, "window_attention"))
+    return _emit_launch("window_attention_quant", tag, q, (b, t, h * d), emit, want_out, nbytes,
+                        lambda op, cp, *tail: entry(
                             N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(bt), N.ptr(mt), op, cp, b, h, t, d, nw, *q.stride()[:3], *k.stride()[:3],
                             *v.stride()[:3], t * h * d, d, h * d, bias_sh, bias_st, mask_sw, mask_st, scale, *tail),
                         ops=4 * b * h * t * t * d + terms * b * h * t * t)

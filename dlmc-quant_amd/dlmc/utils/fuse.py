@@ -1681,10 +1681,15 @@ class WindowAttentionLayer(_MapCodesLayer):
     the mask the graph's own nW - the second size of its five-size view, which the kernel path requires to be the mask's.  The torch
     restatement - the graph's own ops, then K.fake_quant - runs for anything the kernel refuses: T > 64, D not 32 or 64, tensors that
     are not fp32 device views read in place, terms of another shape, a merged width other than H * D or `c`.  Not merged: the kernel's
-    [B, T, H * D] permuted back to [B, H, T, D], fp32 only.  Returns `(fp32 or None, codes or None)`."""
+    [B, T, H * D] permuted back to [B, H, T, D], fp32 only.  `operands`: "f32" (csrc/window_attention.hip, the default) or "f16"
+    (csrc/window_attention_f16.hip: f16 operands on the f16 matrix cores, fp32 everywhere else; fuse_inference(window_attention="f16")) -
+    the kernel's operand type alone: the torch restatement is the same.  Returns `(fp32 or None, codes or None)`."""
 
-    def __init__(self, emit, want_out, c, scale, merged, pre_scaled, has_bias, has_mask, flatten=False):
+    def __init__(self, emit, want_out, c, scale, merged, pre_scaled, has_bias, has_mask, flatten=False, operands="f32"):
         super().__init__(emit, want_out, c, c, 0, False)
+        if operands not in K.WINDOW_ATTENTION_OPERANDS:
+            raise ValueError(f"WindowAttentionLayer: operands is one of {K.WINDOW_ATTENTION_OPERANDS}, not {operands!r}")
+        self.operands = operands
         self.scale, self.merged, self.flatten = float(scale), bool(merged), bool(flatten)
         self.pre_scaled, self.has_bias, self.has_mask = bool(pre_scaled), bool(has_bias), bool(has_mask)
 
@@ -1727,7 +1732,8 @@ class WindowAttentionLayer(_MapCodesLayer):
         if not ok:
             return self._torch(q, k, v, bias, mask, windows, shape)
         emit = None if self.emit is None else self.emit.emit(q.numel())
-        out, codes = K.window_attention_quant(q, k, v, self.scale, bias=bias, mask=mask, emit=emit, want_out=self.want_out)
+        out, codes = K.window_attention_quant(q, k, v, self.scale, bias=bias, mask=mask, emit=emit, want_out=self.want_out,
+                                              operands=self.operands)
         return (out, codes) if self.merged else (out.view(b, t, h, d).permute(0, 2, 1, 3), None)
 
 
@@ -1808,8 +1814,8 @@ def _window_attention_core(node, modules):
     return q, k, v, c, pre, bias, mask, made_of + nodes_
 
 
-def _window_attention_pass(gm, report, planned, dry_run):
-    """Window attention (fuse_inference(window_attention=True)): the core `softmax(q k^T * c + bias + mask) v` (_window_attention_core)
+def _window_attention_pass(gm, report, planned, dry_run, operands="f32"):
+    """Window attention (fuse_inference(window_attention=True), or window_attention="f16": the same nodes with `operands` "f16"): the core `softmax(q k^T * c + bias + mask) v` (_window_attention_core)
     becomes one node (WindowAttentionLayer, csrc/window_attention.hip); the merge-heads tail and the Linear code readers are the
     attention pass's.  The core without an additive term is not taken: it is `attention=True`'s."""
     def match(node, modules):
@@ -1824,12 +1830,13 @@ def _window_attention_pass(gm, report, planned, dry_run):
         if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
             taken = _CodeReaders(None, [], True, 0, 0, 0, False)
         ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, pre_scaled=pre,
-                    has_bias=bias is not None, has_mask=mask is not None, flatten=sizes is None)
+                    has_bias=bias is not None, has_mask=mask is not None, flatten=sizes is None, operands=operands)
         args = (q, k, v) + (() if bias is None else (bias,)) + (mask or ())
         if shape is None:
             return _Splice(WindowAttentionLayer, ctor, node, args, [], made_of)
         return _Splice(WindowAttentionLayer, ctor, shape, args + (sizes or ()), taken.takers, [shape, perm] + made_of)
     _run_node_pass(gm, report, "window_attention", "window_attentions", match, dry_run)
+    report.window_attention_operands = operands if report.window_attentions else None
 
 
 _GELU_ALPHA = 0.70710678118654752440      # 1 / sqrt(2): as a Python scalar torch multiplies an fp32 tensor by its fp32 rounding
@@ -2551,6 +2558,7 @@ class FusionReport:
         self.attentions = 0   # attention cores running as one flash-forward launch, codes to the projection (fuse_inference(attention=True))
         self.attention_operands = None   # "f32" or "f16": the matrix-core operand type of those nodes (attention=True / attention="f16"); None without any
         self.window_attentions = 0   # biased / masked window attention cores running as one launch (fuse_inference(window_attention=True))
+        self.window_attention_operands = None   # "f32" or "f16": the operand type of those nodes (window_attention=True / "f16"); None without any
         self.patch_rows = 0   # patch rearrangements handing the embedding its codes from one read of the image (fuse_inference(patch_embed=True))
         self.token_assemblies = 0   # class-token concatenations + position embeddings running as one launch (fuse_inference(patch_embed=True))
         self.patch_embed_left = []  # (graph node, why): candidates of the patch-embedding pass that were left as they are
@@ -2591,6 +2599,7 @@ class FusionReport:
                 (f"attentions on the plan={self.attentions}, " if self.attentions else "") +
                 (f"attention operands={self.attention_operands}, " if self.attention_operands == "f16" else "") +
                 (f"window attentions on the plan={self.window_attentions}, " if self.window_attentions else "") +
+                (f"window attention operands={self.window_attention_operands}, " if self.window_attention_operands == "f16" else "") +
                 (f"patch rows on the plan={self.patch_rows}, " if self.patch_rows else "") +
                 (f"token assemblies on the plan={self.token_assemblies}, " if self.token_assemblies else "") +
                 (f"patch embedding left alone={self.patch_embed_left}, " if self.patch_embed_left else "") +
@@ -3351,7 +3360,14 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     Left alone: the core without an additive term (that is `attention=True`'s, and the two flags do not meet), a term added in place, a
     second reader of an intermediate.  At run time anything the kernel refuses - more than 64 tokens, another head dimension, tensors
     that are not fp32 device views read in place, terms of another shape - takes the node's torch restatement: the graph's own ops.
-    Runs after the LayerNorm, GELU and attention passes.  Off by default: the plan without it is the plan as it was."""
+    Runs after the LayerNorm, GELU and attention passes.  Off by default: the plan without it is the plan as it was.
+    `window_attention="f16"`: the same cores, matched and planned the same way, on csrc/window_attention_f16.hip - q, k,
+    v and the softmax weights as f16 operands of the f16 matrix cores, the scale, bias, mask, softmax and division in fp32, fp32 in and
+    out; its own stated arithmetic and error bound, inputs above 65504 in magnitude become infinite.
+    `fusion_report.window_attention_operands` says which operand type the nodes run on ("f32", "f16", None without any).  `True` stays
+    the fp32 kernel, bit for bit.  Measured: DESIGN.md 5.33 (tools/window_attention_f16_compare.py).  Opt-in."""
+    if not any(window_attention is v for v in (False, True)) and not (isinstance(window_attention, str) and window_attention == "f16"):
+        raise ValueError(f"fuse_inference: window_attention is False, True (fp32 operands) or 'f16', not {window_attention!r}")
     if not any(attention is v for v in (False, True)) and not (isinstance(attention, str) and attention == "f16"):
         raise ValueError(f"fuse_inference: attention is False, True (fp32 operands) or 'f16', not {attention!r}")
     if not any(gap_head is v for v in (False, True)) and gap_head not in ("separate", "fused"):
@@ -3391,7 +3407,7 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     if attention:
         _attention_pass(gm, report, planned, dry_run, "f16" if attention == "f16" else "f32")
     if window_attention:      # (the cores with an additive term, which the attention pass leaves alone)
-        _window_attention_pass(gm, report, planned, dry_run)
+        _window_attention_pass(gm, report, planned, dry_run, "f16" if window_attention == "f16" else "f32")
     if gap_head:        # (before the chain / layout passes: the head reads its shortcut row-major)
         _gap_pass(gm, report, gap_head, planned, dry_run)
     if chain_pairs and (not dry_run or dry_run == "chains"):

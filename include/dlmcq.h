@@ -1198,6 +1198,34 @@ int dlmcq_window_attention_f32(const float* q, const float* k, const float* v, c
                                int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
                                int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- The same window attention on the f16 matrix cores: fp32 in and out, f16 operands (opt-in) ----
+ * dlmcq_window_attention_f32's arguments, views, strides, alignment, refusals, empty-problem rule and quantiser tail, one wave per
+ * (b, h), with q, k, v and the softmax weights as f16 operands of v_mfma_f32_32x32x16_f16 (csrc/window_attention_f16.hip).  The fp32
+ * inputs, bias and mask are read in place; nothing 16-bit touches memory.  h(x) = x rounded to f16, nearest even; e = 2^-11; u = 2^-24:
+ *     a_ij = sum_k h(q_ik) h(k_jk)            exact products, fp32 accumulation from +0; inside one MFMA neither the order nor round-to-nearest is claimed: bounded, not pinned
+ *     s_ij = fl32(a_ij * scale), then fl32(s_ij + bias) if bias, then fl32(s_ij + mask) if mask, in natural units (the scale is not folded);
+ *            keys past T - 1 hold -inf;  m = max_j s_ij (NaNs dropped);  m~ = m, or 0 where m = -inf
+ *     p_ij = exp2(fl32(fl32(s_ij - m~) * L)),  L = fl32(log2 e)       the hardware exp2 (v_exp_f32, 1 ulp)
+ *     P_ij = h(p_ij)                          one rounding; below 2^-25 it is 0
+ *     l    = the fp32 sum of the ROUNDED weights P_ij: a balanced tree over a lane's 16 per 32-key block, blocks ascending, the two lane halves added last
+ *     o_ic = sum_j h(v_jc) P_ij               two MFMAs per 32-key block from +0, exact products (sums of integers below 2^24 are exact); no rescale
+ *     out_ic = fl32(o_ic / l)                 a true division;  code = the quantiser of out_ic, as in dlmcq_attention_f32 (plain codes only)
+ * A -inf bias or mask entry removes its key; a row whose every key is -inf is NaN and no other row is.  Range: an input above 65504
+ * in magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other, in k_j every row of the head, in v_j[c] channel c
+ * of every row of the head.  Not checked at run time.
+ * Against real arithmetic on the same fp32 inputs, nb = ceil(T / 32), t = how many of bias and mask are given, kappa = 2 (3 * 104 + 2 + 68 nb) + 1,
+ *     delta_i = max over the finite keys j of ((2 e + e^2) + (2 D + 1) u) |scale| sum_k |q_ik k_jk| + t u (|scale a*_ij| + |bias_ij| + |mask_ij|),
+ *     rho_i = expm1(2 delta_i + 3 e + 2^-20 + kappa u):
+ *     |out_ic - o*_ic| <= rho_i sum_j p*_ij |v_jc| + T 2^-24 max_j |v_jc| + 2^-25          (csrc/window_attention_f16.hip derives it)
+ * No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.
+ * Arguments and return codes: dlmcq_window_attention_f32's, one for one. */
+int dlmcq_window_attention_f16(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
+                               void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
+                               int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
+                               int64_t o_sb, int64_t o_sh, int64_t o_st, int64_t bias_sh, int64_t bias_st, int64_t mask_sw,
+                               int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                               int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 /* ---- A vision transformer's patch rows: an fp32 image batch to fp32 rows and / or the activation codes of the embedding ----
  * The rearrangement 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' of an image batch [B, C, gh p, gw p] into rows [B gh gw, p p C]:
  *     row (b gh + gy) gw + gx, column (py p + px) C + c  =  img[b sb + c sc + (gy p + py) sh + gx p + px]
