@@ -27,9 +27,10 @@
 //     out_ic = fl32(o_ic / l) - a true division;  code = the consumer's quantiser of out_ic (EpiQuant::code4, plain codes)
 // Non-finite values and range: a -inf bias or mask entry removes its key (p = +0: it adds nothing to l or o); a row whose every key is
 // -inf has l = 0 and is NaN (0 / 0), and no other row is touched (a query lives in its own two lanes).  An input above 65504 in
-// magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other; in k_j every row of the head; in v_j[c] channel c of
-// every row of the head (inf * P, or inf * 0 = NaN) and no other channel.  Documented, not checked at run time.  NaNs and infinities
-// of the fp32 inputs propagate as in window_attention.hip.
+// magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other; in k_j[c] it reaches every row of the head - row i
+// is NaN where q_ic scale k_jc > 0 (s_ij = +inf) and loses key j where it is negative (s_ij = -inf: that row stays finite, as in torch's
+// unfused graph on the rounded operands); in v_j[c] channel c of every row of the head (inf * P, or inf * 0 = NaN) and no other channel.
+// Documented, not checked at run time.  NaNs and infinities of the fp32 inputs propagate as in window_attention.hip.
 // Error bound against real arithmetic on the same fp32 inputs (s*, p*, o* real), nb = ceil(T / 32), t = how many of bias, mask are given:
 //     delta_i = max over the finite keys j of ((2 e + e^2) + (2 D + 1) u) |scale| sum_k |q_ik k_jk| + t u (|scale a*_ij| + |bias_ij| + |mask_ij|)
 //     rho_i   = expm1(2 delta_i + 3 e + 2^-20 + kappa u),   kappa = 2 (3 * 104 + 2 + 68 nb) + 1

@@ -1211,8 +1211,9 @@ int dlmcq_window_attention_f32(const float* q, const float* k, const float* v, c
  *     o_ic = sum_j h(v_jc) P_ij               two MFMAs per 32-key block from +0, exact products (sums of integers below 2^24 are exact); no rescale
  *     out_ic = fl32(o_ic / l)                 a true division;  code = the quantiser of out_ic, as in dlmcq_attention_f32 (plain codes only)
  * A -inf bias or mask entry removes its key; a row whose every key is -inf is NaN and no other row is.  Range: an input above 65504
- * in magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other, in k_j every row of the head, in v_j[c] channel c
- * of every row of the head.  Not checked at run time.
+ * in magnitude is +-inf as an operand: in q_i it makes row i non-finite and no other, in k_j[c] row i of the head is NaN where
+ * q_ic scale k_jc > 0 and loses key j where it is negative (that row stays finite), in v_j[c] channel c of every row of the head.  Not
+ * checked at run time.
  * Against real arithmetic on the same fp32 inputs, nb = ceil(T / 32), t = how many of bias and mask are given, kappa = 2 (3 * 104 + 2 + 68 nb) + 1,
  *     delta_i = max over the finite keys j of ((2 e + e^2) + (2 D + 1) u) |scale| sum_k |q_ik k_jk| + t u (|scale a*_ij| + |bias_ij| + |mask_ij|),
  *     rho_i = expm1(2 delta_i + 3 e + 2^-20 + kappa u):
