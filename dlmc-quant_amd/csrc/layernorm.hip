@@ -26,31 +26,9 @@
 // One wave owns one row, four rows per 256-thread workgroup; a row is loaded once, as float4, into at most 32 registers per lane
 // (kernels for 1, 2, 4 and 8 quads per lane: C <= 256, 512, 1024, 2048) with PLAIN loads - the rows are the residual stream, which the
 // block's add reads again.  No LDS, no atomics, no scratch: a row's result depends neither on M nor on the row's index nor on the launch.
-#include "conv_gap.h"
+#include "ln_sums.h"      // ln_quad_sum, ln_tree_sum, ln_wave_sum, DLMCQ_LN_MAX_C: shared with swin_rows.hip
 
 namespace dlmcq {
-
-#define DLMCQ_LN_MAX_C 2048
-
-// the sum of one fp32 per lane over the wave: the same bits in all 64 lanes (a + b = b + a)
-__device__ __forceinline__ float ln_wave_sum(float t) {
-#pragma unroll
-  for (int off = DLMCQ_WAVE / 2; off > 0; off >>= 1) t = t + __shfl_xor(t, off, DLMCQ_WAVE);
-  return t;
-}
-
-// one quad's sum, and the lane's quad sums added pairwise in memory order (N a power of two): a balanced tree over the lane's elements
-__device__ __forceinline__ float ln_quad_sum(float x0, float x1, float x2, float x3) { return (x0 + x1) + (x2 + x3); }
-
-template <int N>
-__device__ __forceinline__ float ln_tree_sum(float (&t)[N]) {
-#pragma unroll
-  for (int w = N / 2; w > 0; w >>= 1) {
-#pragma unroll
-    for (int i = 0; i < w; ++i) t[i] = t[2 * i] + t[2 * i + 1];
-  }
-  return t[0];
-}
 
 // QPL: quads per lane; C4 <= 64 * QPL (the host picks the smallest that fits)
 template <int QPL>

@@ -1487,6 +1487,134 @@ def layernorm_quant(x, weight, bias, eps, emit=None, want_out=True):
         N.ptr(x), N.ptr(weight), N.ptr(bias), op, cp, m, c, float(eps), *tail))
 
 
+def swin_map_view(x):
+    """The strides (b, y, x) in floats with which dlmcq_layernorm_gather_rows_f32 and dlmcq_window_reverse_add_f32 read the token map
+    `x` [B, Hm, Wm, C] in place - an fp32 tensor (the device is the caller's to check), C % 4 == 0, unit stride in C, every other stride a multiple of 4 floats, a
+    pixel's channels, a line's pixels and an image's lines not overlapping the next (the contiguous residual stream viewed as a map, or a
+    row-padded buffer), 16-byte aligned - else None.  (The stride of a dimension of size 1 addresses nothing: the dense one is passed.)"""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.dtype == torch.float32):
+        return None
+    b, h, w, c = x.shape
+    if b < 1 or h < 1 or w < 1 or c < 4 or c % 4 or x.stride(3) != 1 or x.data_ptr() % 16:
+        return None
+    sx = x.stride(2) if w > 1 else c
+    sy = x.stride(1) if h > 1 else w * sx
+    sb = x.stride(0) if b > 1 else h * sy
+    ok = sx >= c and sy >= w * sx and sb >= h * sy and not (sx % 4 or sy % 4 or sb % 4)
+    return (sb, sy, sx) if ok else None
+
+
+def _shift_pair(name, shift):
+    """`shift` - one int for both axes, or (sy, sx) - as two ints."""
+    pair = (shift, shift) if isinstance(shift, int) else tuple(shift) if isinstance(shift, (tuple, list)) else ()
+    if len(pair) != 2 or not all(isinstance(s, int) and not isinstance(s, bool) for s in pair):
+        raise ValueError(f"{name}: shift is an int or a pair of ints, not {shift!r}")
+    return pair
+
+
+def window_rows_torch(x_map, window, shift):
+    """The shifted-window rows [B nW, window^2, C] of a token map [B, Hm, Wm, C] in torch ops: the roll by (-sy, -sx) (none for 0, 0),
+    then the partition reshape, permute and reshape."""
+    b, h, w, c = x_map.shape
+    sy, sx = _shift_pair("window_rows_torch", shift)
+    if sy or sx:
+        x_map = torch.roll(x_map, (-sy, -sx), (1, 2))
+    return x_map.reshape(b, h // window, window, w // window, window, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, window * window, c)
+
+
+def merge_rows_torch(x_map):
+    """The 2 x 2 patch-merge rows [B, Hm / 2 * Wm / 2, 4 C] of a token map [B, Hm, Wm, C] in torch ops: Swin's four slices and cat."""
+    b, h, w, c = x_map.shape
+    rows = torch.cat([x_map[:, 0::2, 0::2], x_map[:, 1::2, 0::2], x_map[:, 0::2, 1::2], x_map[:, 1::2, 1::2]], -1)
+    return rows.reshape(b, (h // 2) * (w // 2), 4 * c)
+
+
+def window_reverse_torch(yw, shape, window, shift):
+    """Window rows `yw` [B nW, window^2, C] back on the map `shape` = (B, Hm, Wm, C) in torch ops: the reverse reshape, permute and
+    reshape, then the roll by (+sy, +sx) (none for 0, 0)."""
+    b, h, w, c = shape
+    sy, sx = _shift_pair("window_reverse_torch", shift)
+    m = yw.reshape(b, h // window, w // window, window, window, c).permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, c)
+    return torch.roll(m, (sy, sx), (1, 2)) if sy or sx else m
+
+
+def _gather_rows(name, mode, x_map, weight, bias, eps, window, shift, width, shape, emit, want_out):
+    """layernorm_window_quant and layernorm_merge_quant behind their geometry checks: rows of `width` floats gathered from `x_map`, to
+    `(out or None, codes or None)` of `shape`."""
+    if not want_out and emit is None:
+        raise ValueError(f"{name}: nothing to produce (want_out=False without emit)")
+    if width > LAYERNORM_MAX_C:
+        raise ValueError(f"{name}: rows of {width} floats (at most {LAYERNORM_MAX_C})")
+    for what, t in (("weight", weight), ("bias", bias)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (width,)):
+            raise ValueError(f"{name}: an fp32 {what} of shape ({width},), not {t.dtype} {tuple(t.shape)}")
+    N.require_gpu(x_map, weight, bias)
+    x_map = x_map.detach()
+    strides = swin_map_view(x_map)
+    b, h, w, c = x_map.shape
+    weight, bias = _bias_c(weight), _bias_c(bias)
+    m = shape[0] * shape[1]
+    nbytes = m * width * (4 + 4 * want_out + (emit is not None)) + 4 * width * ((weight is not None) + (bias is not None))
+    return _emit_launch(name, "layernorm_gather", x_map, shape, emit, want_out, nbytes, lambda op, cp, *tail: N.lib.dlmcq_layernorm_gather_rows_f32(
+        N.ptr(x_map), N.ptr(weight), N.ptr(bias), op, cp, mode, b, h, w, c, *strides, window, *shift, float(eps), *tail))
+
+
+def _swin_map(name, x_map):
+    if swin_map_view(x_map) is None:
+        raise ValueError(f"{name}: an fp32 token map [B, Hm, Wm, C] read in place (C % 4 == 0, unit stride in C, strides multiples of 4 "
+                         f"floats, 16-byte aligned; swin_map_view), not {x_map.dtype} {tuple(x_map.shape)} with strides {tuple(x_map.stride())}")
+    return tuple(x_map.shape)
+
+
+def _window_geometry(name, h, w, window, shift):
+    sy, sx = _shift_pair(name, shift)
+    if not (isinstance(window, int) and window >= 1 and h % window == 0 and w % window == 0 and 0 <= sy < h and 0 <= sx < w):
+        raise ValueError(f"{name}: windows of {window!r} and shifts {(sy, sx)} do not fit a {h} x {w} map (Hm % window == Wm % window == 0, "
+                         "0 <= sy < Hm, 0 <= sx < Wm)")
+    return sy, sx
+
+
+def layernorm_window_quant(x_map, weight, bias, eps, window, shift, emit=None, want_out=True):
+    """nn.LayerNorm((C,)) of the shifted-window rows of a token map - `window_rows_torch(x_map, window, shift)` normalised - by
+    dlmcq_layernorm_gather_rows_f32 (csrc/swin_rows.hip): the map `x_map` [B, Hm, Wm, C] is read in place through its strides
+    (swin_map_view; anything else is a ValueError), the roll and the partition are row addresses.  `shift`: an int for both axes or
+    (sy, sx), 0 <= shift < the map's side.  Returns `(out or None, codes or None)`, both [B nW, window^2, C], with the bits of
+    layernorm_quant on the gathered rows; `weight`, `bias`, `eps`, `emit`, `want_out` as there."""
+    b, h, w, c = _swin_map("layernorm_window_quant", x_map)
+    shift = _window_geometry("layernorm_window_quant", h, w, window, shift)
+    shape = (b * (h // window) * (w // window), window * window, c)
+    return _gather_rows("layernorm_window_quant", N.GATHER_WINDOW, x_map, weight, bias, eps, window, shift, c, shape, emit, want_out)
+
+
+def layernorm_merge_quant(x_map, weight, bias, eps, emit=None, want_out=True):
+    """nn.LayerNorm((4 C,)) of the 2 x 2 patch-merge rows of a token map - `merge_rows_torch(x_map)` normalised - by
+    dlmcq_layernorm_gather_rows_f32: the map [B, Hm, Wm, C], Hm and Wm even, 4 C <= LAYERNORM_MAX_C, is read in place (swin_map_view;
+    anything else is a ValueError).  Returns `(out or None, codes or None)`, both [B, Hm / 2 * Wm / 2, 4 C]; the rest as
+    layernorm_window_quant."""
+    b, h, w, c = _swin_map("layernorm_merge_quant", x_map)
+    if h % 2 or w % 2:
+        raise ValueError(f"layernorm_merge_quant: a {h} x {w} map has no 2 x 2 merge")
+    shape = (b, (h // 2) * (w // 2), 4 * c)
+    return _gather_rows("layernorm_merge_quant", N.GATHER_MERGE, x_map, weight, bias, eps, 0, (0, 0), 4 * c, shape, emit, want_out)
+
+
+def window_reverse_add(yw, shortcut, window, shift):
+    """`shortcut + window_reverse_torch(yw, shortcut.shape, window, shift)` - the window reverse, the roll back and the residual add of a
+    Swin block - by dlmcq_window_reverse_add_f32 (csrc/swin_rows.hip): one IEEE add per element in one pass, the bits of torch's add.
+    `yw`: dense fp32 window rows of B nW window^2 C elements (copied when not contiguous); `shortcut`: the token map [B, Hm, Wm, C], read
+    in place (swin_map_view; anything else is a ValueError).  Returns a new contiguous fp32 map [B, Hm, Wm, C]."""
+    b, h, w, c = _swin_map("window_reverse_add", shortcut)
+    sy, sx = _window_geometry("window_reverse_add", h, w, window, shift)
+    if yw.dtype != torch.float32 or yw.numel() != b * h * w * c or yw.dim() < 1 or yw.shape[-1] != c:
+        raise ValueError(f"window_reverse_add: fp32 window rows [..., {c}] of {b * h * w} tokens, not {yw.dtype} {tuple(yw.shape)}")
+    N.require_gpu(yw, shortcut)
+    yw, shortcut = yw.detach().contiguous(), shortcut.detach()
+    out = torch.empty((b, h, w, c), dtype=torch.float32, device=shortcut.device)
+    PROFILE.launch("window_reverse_add", 12 * out.numel(), lambda: N.check(N.lib.dlmcq_window_reverse_add_f32(
+        N.ptr(yw), N.ptr(shortcut), N.ptr(out), b, h, w, c, *swin_map_view(shortcut), h * w * c, w * c, c, window, sy, sx, N.stream_ptr())))
+    return out
+
+
 PATCH_MAX_STRIP = 65536      # dlmcq_patch_rows_f32: elements of one (image, patch row) strip, whose codes are staged in LDS
 
 

@@ -1480,6 +1480,242 @@ def _layernorm_pass(gm, report, planned, dry_run):
     _run_node_pass(gm, report, "layernorm", "layer_norms", match, dry_run)
 
 
+def _norm_params_fp32(m):
+    return all(p is None or p.dtype == torch.float32 for p in (m.weight, m.bias))
+
+
+class WindowNormLayer(_MapCodesLayer):
+    """`norm(x).view(-1, Hm, Wm, C)` -> `torch.roll(., (-sy, -sx), (1, 2))` (none for no shift) -> the window partition
+    `reshape(-1, gy, ws, gx, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C)` straight to the activation codes of the Linear plan
+    layers that read the window rows (csrc/swin_rows.hip: dlmcq_layernorm_gather_rows_f32): the roll and the partition are row
+    addresses of the residual stream, read in place.  `norm`: the nn.LayerNorm, read at every call; `hw` = (Hm, Wm), `window`, `shift` =
+    (sy, sx): the geometry the graph spelled; `emit`, `want_out`, `c` as LayerNormLayer.  An input the kernel does not read in place
+    (not an fp32 device tensor of whole maps of width `c`, misaligned, parameters that are not fp32) takes the graph's own ops:
+    F.layer_norm, the view, the roll, the partition, then K.fake_quant.  Returns `(fp32 or None, codes)`, both [B nW, ws * ws, C]."""
+
+    def __init__(self, norm, emit, want_out, c, hw, window, shift):
+        super().__init__(emit, want_out, c, c, 0, False)
+        self.norm, self.hw, self.window, self.shift = norm, (int(hw[0]), int(hw[1])), int(window), (int(shift[0]), int(shift[1]))
+
+    def forward(self, x):
+        m, (hm, wm) = self.norm, self.hw
+        whole = x.dim() >= 1 and x.shape[-1] == self.c and x.numel() > 0 and x.numel() % (hm * wm * self.c) == 0
+        if whole and x.is_cuda and _norm_params_fp32(m) and K.swin_map_view(x.reshape(-1, hm, wm, self.c)) is not None:
+            return K.layernorm_window_quant(x.reshape(-1, hm, wm, self.c), m.weight, m.bias, m.eps, self.window, self.shift,
+                                            emit=self.emit.emit(x.numel()), want_out=self.want_out)
+        v = F.layer_norm(x, m.normalized_shape, m.weight, m.bias, m.eps).view(-1, hm, wm, self.c)
+        return self._torch_rows(K.window_rows_torch(v, self.window, self.shift))
+
+
+class MergeNormLayer(_MapCodesLayer):
+    """Swin's patch merging in front of its LayerNorm - `cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+    .view(-1, L / 4, 4 C)` -> nn.LayerNorm(4 C) - straight to the activation codes of the Linear plan layer behind it
+    (dlmcq_layernorm_gather_rows_f32 in its merge geometry): the four slices and the concatenation are row addresses of the map x
+    [B, Hm, Wm, C], read in place.  `c` = 4 C, the readers' in-features.  An input the kernel does not read in place takes the
+    graph's own ops, then F.layer_norm and K.fake_quant.  Returns `(fp32 or None, codes)`, both [B, Hm / 2 * Wm / 2, 4 C]."""
+
+    def __init__(self, norm, emit, want_out, c, hw):
+        super().__init__(emit, want_out, c, c, 0, False)
+        self.norm, self.hw = norm, (int(hw[0]), int(hw[1]))
+
+    def forward(self, x):
+        m = self.norm
+        ok = x.dim() == 4 and tuple(x.shape[1:]) == (*self.hw, self.c // 4) and x.shape[0] > 0 and x.is_cuda and _norm_params_fp32(m)
+        if ok and K.swin_map_view(x) is not None:
+            return K.layernorm_merge_quant(x, m.weight, m.bias, m.eps, emit=self.emit.emit(x.numel()), want_out=self.want_out)
+        return self._torch_rows(F.layer_norm(K.merge_rows_torch(x), m.normalized_shape, m.weight, m.bias, m.eps))
+
+
+class WindowAddLayer(nn.Module):
+    """The window reverse `yw.reshape(-1, gy, gx, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, Hm, Wm, C)`, the roll back
+    `torch.roll(., (sy, sx), (1, 2))` (none for no shift), `.view(-1, Hm * Wm, C)` and the residual add `+ x` as one launch
+    (csrc/swin_rows.hip: dlmcq_window_reverse_add_f32): fp32 [B, Hm * Wm, C], the bits of the torch ops.  Inputs the kernel does not
+    read in place (not fp32 device tensors of whole maps of width `c`, a shortcut that broadcasts, misaligned) run the graph's own ops."""
+
+    def __init__(self, c, hw, window, shift):
+        super().__init__()
+        self.c, self.hw, self.window, self.shift = int(c), (int(hw[0]), int(hw[1])), int(window), (int(shift[0]), int(shift[1]))
+
+    def forward(self, yw, x):
+        (hm, wm), c = self.hw, self.c
+        ok = (yw.is_cuda and x.is_cuda and yw.dtype == x.dtype == torch.float32 and yw.dim() >= 1 and yw.shape[-1] == c and x.dim() == 3 and
+              tuple(x.shape[1:]) == (hm * wm, c) and x.numel() == yw.numel() > 0)
+        if ok and K.swin_map_view(x.reshape(-1, hm, wm, c)) is not None:
+            return K.window_reverse_add(yw, x.reshape(-1, hm, wm, c), self.window, self.shift).view(-1, hm * wm, c)
+        b = yw.numel() // (hm * wm * c)
+        return K.window_reverse_torch(yw, (b, hm, wm, c), self.window, self.shift).reshape(-1, hm * wm, c) + x
+
+
+_WindowRows = collections.namedtuple("_WindowRows", "hw window shift c chain")      # chain: the rearrangement's nodes in graph order
+
+
+def _roll_of(node, src):
+    """(a, b) if `node` is torch.roll(src, (a, b), (1, 2)) - Python ints, positional or by keyword - else None."""
+    if not (isinstance(node, fx.Node) and node.op == "call_function" and node.target is torch.roll):
+        return None
+    names = ("input", "shifts", "dims")
+    if len(node.args) > 3 or not set(node.kwargs) <= set(names[len(node.args):]):
+        return None
+    given = dict(zip(names, node.args), **node.kwargs)
+    shifts, dims = given.get("shifts"), given.get("dims")
+    ok = (given.get("input") is src and isinstance(shifts, (tuple, list)) and len(shifts) == 2 and isinstance(dims, (tuple, list)) and
+          tuple(dims) == (1, 2) and all(isinstance(s, int) and not isinstance(s, bool) for s in shifts))
+    return tuple(shifts) if ok else None
+
+
+def _window_geometry(s4, s6, tokens_first):
+    """(Hm, Wm, ws, C) if the four sizes (-1, Hm, Wm, C) of the map and the six of its windowed form - (-1, gy, ws, gx, ws, C) with
+    `tokens_first=False` (the partition's input), (-1, gy, gx, ws, ws, C) with True (the reverse's) - state one geometry, else None."""
+    if s4 is None or s6 is None or len(s4) != 4 or len(s6) != 6 or s4[0] != -1 or s6[0] != -1:
+        return None
+    gy, gx, wy, wx = (s6[1], s6[2], s6[3], s6[4]) if tokens_first else (s6[1], s6[3], s6[2], s6[4])
+    hm, wm, c = s4[1:]
+    ok = min(gy, gx, wy, c) >= 1 and wy == wx and s6[5] == c and (hm, wm) == (gy * wy, gx * wx) and c % 4 == 0
+    return (hm, wm, wy, c) if ok else None
+
+
+_SWIN_ORDER = (0, 1, 3, 2, 4, 5)      # the permute of the window partition and of the reverse
+
+
+def _window_rows_of(norm):
+    """The _WindowRows behind graph node `norm` - `.view(-1, Hm, Wm, C)` -> [torch.roll(., (a, b), (1, 2))] -> the partition's reshape
+    to six sizes, permute _SWIN_ORDER and reshape to (-1, ws * ws, C), every size a Python int, every node read by the next alone - else
+    None.  The shift is (-a mod Hm, -b mod Wm)."""
+    view = _sole_user(norm)
+    s4 = _static_sizes(view, ("view", "reshape"))
+    if s4 is None:
+        return None
+    chain, nxt, shifts = [view], _sole_user(view), (0, 0)
+    rolled = _roll_of(nxt, view)
+    if rolled is not None:
+        chain, nxt, shifts = chain + [nxt], _sole_user(nxt), rolled
+    perm = _sole_user(nxt)
+    last = _sole_user(perm)
+    geo = _window_geometry(s4, _static_sizes(nxt, ("reshape", "view")), False)
+    s3 = _static_sizes(last, ("reshape", "view"))
+    if geo is None or _static_sizes(perm, ("permute",)) != _SWIN_ORDER or s3 is None:
+        return None
+    hm, wm, ws, c = geo
+    if s3 != (-1, ws * ws, c):
+        return None
+    return _WindowRows((hm, wm), ws, (-shifts[0] % hm, -shifts[1] % wm), c, tuple(chain + [nxt, perm, last]))
+
+
+def _window_reverse_of(view):
+    """The _WindowRows in front of graph node `view` = `.view(-1, Hm * Wm, C)` - the reverse's reshape to six sizes, permute _SWIN_ORDER,
+    reshape to (-1, Hm, Wm, C), [torch.roll(., (a, b), (1, 2))], every size a Python int, every node read by the next alone - else None.
+    The shift is (a mod Hm, b mod Wm); the chain ends with `view`."""
+    s3 = _static_sizes(view, ("view", "reshape"))
+    if s3 is None or len(s3) != 3:
+        return None
+    chain, src, shifts = [view], view.args[0], (0, 0)
+    if src.op == "call_function" and src.target is torch.roll and isinstance(src.args[0] if src.args else src.kwargs.get("input"), fx.Node):
+        inner = src.args[0] if src.args else src.kwargs["input"]
+        shifts = _roll_of(src, inner)
+        if shifts is None:
+            return None
+        chain, src = [src] + chain, inner
+    s4 = _static_sizes(src, ("reshape", "view"))
+    perm = src.args[0] if s4 is not None else None
+    first = perm.args[0] if _static_sizes(perm, ("permute",)) == _SWIN_ORDER else None
+    geo = _window_geometry(s4, _static_sizes(first, ("reshape", "view")), True)
+    if geo is None or any(_sole_user(n) is None for n in [first, perm, src] + chain[:-1]):
+        return None
+    hm, wm, ws, c = geo
+    if s3 != (-1, hm * wm, c):
+        return None
+    return _WindowRows((hm, wm), ws, (shifts[0] % hm, shifts[1] % wm), c, tuple([first, perm, src] + chain))
+
+
+def _plan_norm(node, modules, width):
+    """The nn.LayerNorm behind call_module `node` if the LayerNorm pass's rules hold for it at `width` channels, else None."""
+    m = modules.get(node.target) if node.op == "call_module" else None
+    if type(m) is not nn.LayerNorm or len(node.args) != 1 or node.kwargs or not isinstance(node.args[0], fx.Node):
+        return None
+    ok = tuple(m.normalized_shape) == (width,) and width % 4 == 0 and 4 <= width <= K.LAYERNORM_MAX_C and m.eps > 0 and math.isfinite(m.eps)
+    return m if ok else None
+
+
+def _linear_takers(planned, t, width):
+    """_code_readers of `t` where they are Linear plan layers of `width` in-features and nobody else reads `t` through another
+    quantiser (the LayerNorm pass's rule), else None."""
+    taken = _code_readers(planned, t, linear=True)
+    return taken if taken is not None and taken.c == width and all(planned[u].mod.weight.dim() == 2 for u in taken.takers) else None
+
+
+def _merge_rows_of(view):
+    """(map node, Hm, Wm, C, nodes) if `view` is `cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+    .view(-1, Hm / 2 * Wm / 2, 4 C)` of x = `.view(-1, Hm, Wm, C)` with Python ints, the slices read by the concatenation alone and x by
+    the four slices alone - else None."""
+    s3 = _static_sizes(view, ("view", "reshape"))
+    cat = view.args[0] if s3 is not None and len(s3) == 3 else None
+    if cat is None or not (cat.op == "call_function" and cat.target in (torch.cat, torch.concat, torch.concatenate) and cat.args):
+        return None
+    parts, given = cat.args[0], dict(zip(("dim",), cat.args[1:]), **cat.kwargs)
+    if not (isinstance(parts, (tuple, list)) and len(parts) == 4 and len(set(parts)) == 4 and set(given) == {"dim"} and given["dim"] in (-1, 3)):
+        return None
+    src = None
+    for part, (a, b) in zip(parts, ((0, 0), (1, 0), (0, 1), (1, 1))):
+        ok = (isinstance(part, fx.Node) and part.op == "call_function" and part.target is operator.getitem and _sole_user(part) is cat and
+              isinstance(part.args[1], tuple) and len(part.args[1]) == 3 and all(isinstance(s, slice) for s in part.args[1]))
+        if not ok or (src is not None and part.args[0] is not src):
+            return None
+        src, (s0, sy, sx) = part.args[0], part.args[1]
+        if s0 != slice(None) or (sy.start or 0, sy.stop, sy.step, sx.start or 0, sx.stop, sx.step) != (a, None, 2, b, None, 2):
+            return None
+    s4 = _static_sizes(src, ("view", "reshape"))
+    if s4 is None or len(s4) != 4 or s4[0] != -1 or len(src.users) != 4 or _sole_user(cat) is None:
+        return None
+    hm, wm, c = s4[1:]
+    if min(hm, wm, c) < 1 or hm % 2 or wm % 2 or c % 4 or s3 != (-1, (hm // 2) * (wm // 2), 4 * c):
+        return None
+    return src, hm, wm, c, (view, cat, *parts)
+
+
+def _swin_geometry_pass(gm, report, planned, dry_run):
+    """A Swin stage's row geometry (fuse_inference(swin_geometry=True)) as three kinds of plan node; what each takes is what its
+    class says, spelled exactly so - another permutation, a roll on other dims, a size that is no Python int, an intermediate with a
+    second reader and the graph keeps its own ops.  WindowAddLayer first, while the block's norm1 chain still stands: where the add's
+    shortcut also feeds a LayerNorm whose window rows are visible, the two geometries have to agree.  Then WindowNormLayer and
+    MergeNormLayer, under the LayerNorm pass's rules for the norm and its takers (one quantiser, Linear layers of the row width).
+    Runs before the LayerNorm pass, which would take a merge's LayerNorm behind the materialised concatenation."""
+    def add(node, modules):
+        if not _is_add(node) or _inplace_add(node):
+            return None
+        for view, short in (node.args, node.args[::-1]):
+            back = _window_reverse_of(view) if view is not short and _sole_user(view) is node else None
+            if back is None:
+                continue
+            ahead = [_window_rows_of(u) for u in short.users if _plan_norm(u, modules, back.c) is not None]
+            if any(f is not None and f[:4] != back[:4] for f in ahead):
+                return None
+            ctor = dict(c=back.c, hw=back.hw, window=back.window, shift=back.shift)
+            return _Splice(WindowAddLayer, ctor, node, (back.chain[0].args[0], short), (), (node,) + back.chain[::-1])
+        return None
+
+    def window(node, modules):
+        rows = _window_rows_of(node) if node.op == "call_module" else None
+        m = _plan_norm(node, modules, rows.c) if rows is not None else None
+        taken = _linear_takers(planned, rows.chain[-1], rows.c) if m is not None else None
+        if taken is None:
+            return None
+        ctor = dict(norm=m, emit=taken.emit, want_out=taken.want_out, c=rows.c, hw=rows.hw, window=rows.window, shift=rows.shift)
+        return _Splice(WindowNormLayer, ctor, rows.chain[-1], (node.args[0],), taken.takers, rows.chain[::-1] + (node,))
+
+    def merge(node, modules):
+        rows = _merge_rows_of(node.args[0]) if node.op == "call_module" and node.args and isinstance(node.args[0], fx.Node) else None
+        m = _plan_norm(node, modules, 4 * rows[3]) if rows is not None and _sole_user(node.args[0]) is node else None
+        taken = _linear_takers(planned, node, 4 * rows[3]) if m is not None else None
+        if taken is None:
+            return None
+        src, hm, wm, c, nodes = rows
+        ctor = dict(norm=m, emit=taken.emit, want_out=taken.want_out, c=4 * c, hw=(hm, wm))
+        return _Splice(MergeNormLayer, ctor, node, (src,), taken.takers, (node,) + nodes)
+    _run_node_pass(gm, report, "window_add", "window_adds", add, dry_run, outputs=1)
+    _run_node_pass(gm, report, "window_norm", "window_norms", window, dry_run)
+    _run_node_pass(gm, report, "merge_norm", "merge_norms", merge, dry_run)
+
+
 class AttentionLayer(_MapCodesLayer):
     """softmax(scale * q k^T) v of fp32 views [B, H, T, D] as one flash-forward launch (csrc/attention.hip), and - `merged` - the
     merge-heads `permute(0, 2, 1, 3)` + reshape behind it as a free view: the node returns [B, Tq, H * D] and hands the Linear plan
@@ -2559,6 +2795,9 @@ class FusionReport:
         self.attention_operands = None   # "f32" or "f16": the matrix-core operand type of those nodes (attention=True / attention="f16"); None without any
         self.window_attentions = 0   # biased / masked window attention cores running as one launch (fuse_inference(window_attention=True))
         self.window_attention_operands = None   # "f32" or "f16": the operand type of those nodes (window_attention=True / "f16"); None without any
+        self.window_norms = 0   # LayerNorms of shifted-window rows gathered from the token map, codes to the Linear behind (fuse_inference(swin_geometry=True))
+        self.merge_norms = 0    # LayerNorms of 2 x 2 patch-merge rows gathered from the token map (fuse_inference(swin_geometry=True))
+        self.window_adds = 0    # window reverse + roll back + residual add running as one launch (fuse_inference(swin_geometry=True))
         self.patch_rows = 0   # patch rearrangements handing the embedding its codes from one read of the image (fuse_inference(patch_embed=True))
         self.token_assemblies = 0   # class-token concatenations + position embeddings running as one launch (fuse_inference(patch_embed=True))
         self.patch_embed_left = []  # (graph node, why): candidates of the patch-embedding pass that were left as they are
@@ -2600,6 +2839,9 @@ class FusionReport:
                 (f"attention operands={self.attention_operands}, " if self.attention_operands == "f16" else "") +
                 (f"window attentions on the plan={self.window_attentions}, " if self.window_attentions else "") +
                 (f"window attention operands={self.window_attention_operands}, " if self.window_attention_operands == "f16" else "") +
+                (f"window norms on the plan={self.window_norms}, " if self.window_norms else "") +
+                (f"merge norms on the plan={self.merge_norms}, " if self.merge_norms else "") +
+                (f"window adds on the plan={self.window_adds}, " if self.window_adds else "") +
                 (f"patch rows on the plan={self.patch_rows}, " if self.patch_rows else "") +
                 (f"token assemblies on the plan={self.token_assemblies}, " if self.token_assemblies else "") +
                 (f"patch embedding left alone={self.patch_embed_left}, " if self.patch_embed_left else "") +
@@ -3142,7 +3384,7 @@ class _MainPass:
 def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int4=True, weight_blob=None, dwpw=False, block_layout=True,
                    relu6=True, act_offsets=False, gap_head=False, narrow_rows=False, pad_shortcuts=False, avg_pools=False,
                    recompute_shortcuts=None, gates=False, swish=False, dw5=False, layer_norms=False, gelu=False, attention=False,
-                   patch_embed=False, squeezes=False, hardswish=False, window_attention=False):
+                   patch_embed=False, squeezes=False, hardswish=False, window_attention=False, swin_geometry=False):
     """Return a `torch.fx.GraphModule` executing `model`'s calibrated quantised forward as the fused int8 plan.
     `pack_int4`: weight codes whose range fits 4 bits are stored packed and expanded by one launch per forward (PackedWeights4).
     `weight_blob`: an integer checkpoint (`dlmc.utils.export.export_quantized_state`) of the same model - the plan takes the
@@ -3365,7 +3607,24 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     v and the softmax weights as f16 operands of the f16 matrix cores, the scale, bias, mask, softmax and division in fp32, fp32 in and
     out; its own stated arithmetic and error bound, inputs above 65504 in magnitude become infinite.
     `fusion_report.window_attention_operands` says which operand type the nodes run on ("f32", "f16", None without any).  `True` stays
-    the fp32 kernel, bit for bit.  Measured: DESIGN.md 5.33 (tools/window_attention_f16_compare.py).  Opt-in."""
+    the fp32 kernel, bit for bit.  Measured: DESIGN.md 5.33 (tools/window_attention_f16_compare.py).  Opt-in.
+    `swin_geometry=True`: the row geometry of a Swin stage (`workloads.swin()`) as plan nodes on csrc/swin_rows.hip,
+    which reads the token map in place and turns the roll, the window partition / reverse and the patch merge into row addresses.
+    `norm(x).view(-1, Hm, Wm, C)` -> [`torch.roll(., (-s, -s), (1, 2))`] -> `reshape(-1, gy, ws, gx, ws, C).permute(0, 1, 3, 2, 4, 5)
+    .reshape(-1, ws * ws, C)` read by Linear plan layers of C in-features becomes a WindowNormLayer node that hands them their codes in
+    window order (`fusion_report.window_norms`); `cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+    .view(-1, L / 4, 4 C)` -> nn.LayerNorm(4 C) -> Linear plan layer a MergeNormLayer node (`.merge_norms`); the reverse
+    `reshape(-1, gy, gx, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, Hm, Wm, C)` -> [`torch.roll(., (s, s), (1, 2))`] ->
+    `.view(-1, L, C)` -> an out-of-place add with a graph value a WindowAddLayer node, fp32 only (`.window_adds`).  The LayerNorm and
+    its takers follow `layer_norms`' rules (one quantiser, a 2-D weight, the row width at most 2048); every size is a Python int, the
+    batch alone -1, and every intermediate is read once.  Left to their own ops: another permutation, a roll on other dims or with
+    other arguments, a backward shift that differs from the forward one where the add's shortcut also feeds the block's norm, sizes
+    read from a tensor.  At run time an input the kernels do not read in place takes the node's torch restatement: the graph's ops,
+    then F.layer_norm / K.fake_quant.  The gathered LayerNorm has the bits of K.layernorm_quant on the materialised rows and the add
+    the bits of torch's, so the plan equals the plan with the three wrappers replaced by a torch gather in front of K.layernorm_quant
+    and a torch add (tests/test_gpu_swin_plan.py); against the flag-off plan the logits differ as under `layer_norms` (torch's
+    summation order in the window and merge norms).  Runs after the main pass and before the LayerNorm pass.  Measured: DESIGN.md 5.34
+    (tools/swin_geometry_compare.py).  Off by default: the plan without it is the plan as it was."""
     if not any(window_attention is v for v in (False, True)) and not (isinstance(window_attention, str) and window_attention == "f16"):
         raise ValueError(f"fuse_inference: window_attention is False, True (fp32 operands) or 'f16', not {window_attention!r}")
     if not any(attention is v for v in (False, True)) and not (isinstance(attention, str) and attention == "f16"):
@@ -3400,6 +3659,8 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
         _avgpool_pass(gm, report, planned, dry_run)
     if patch_embed:     # (after the main pass, whose decision for the embedding stays; before the LayerNorm pass, which reads the token tensor)
         _patch_embed_pass(gm, report, planned, dry_run)
+    if swin_geometry:   # (beside the LayerNorm pass and before it: a merge's LayerNorm is taken with its gather, not behind the concatenation)
+        _swin_geometry_pass(gm, report, planned, dry_run)
     if layer_norms:     # (after the main pass, whose decisions for the Linear layers stay; before the head pass, like the average pools)
         _layernorm_pass(gm, report, planned, dry_run)
     if gelu:

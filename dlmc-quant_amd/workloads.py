@@ -536,6 +536,86 @@ class WindowViT(nn.Module):
         return self.head(self.norm(x.mean(1)))
 
 
+class SwinBlock(nn.Module):
+    """A Swin block (public architecture: Liu et al. 2021) on the residual stream [B, L, dim] of a `side` x `side` token map:
+    x = reverse(attn(partition(roll(norm(x))))) rolled back + x; x = ff(norm(x)) + x.  The map is rolled by (-shift, -shift) in front of
+    the window partition and back behind the reverse (no roll for shift 0); the partition and the reverse are WindowViT's reshapes on a
+    channels-last map.  Every size but the batch is a Python int."""
+
+    def __init__(self, dim, heads, window, shift, side, mlp_dim):
+        super().__init__()
+        if side % window or not 0 <= shift < window:
+            raise ValueError(f"SwinBlock: windows of {window} shifted by {shift} do not tile a {side} x {side} map")
+        self.dim, self.window, self.shift, self.side = dim, window, shift, side
+        self.norm1, self.attn = nn.LayerNorm(dim), WindowAttention(dim, heads, window, shift > 0, side // window)
+        self.norm2, self.fc1, self.act, self.fc2 = nn.LayerNorm(dim), nn.Linear(dim, mlp_dim), nn.GELU(), nn.Linear(mlp_dim, dim)
+
+    def forward(self, x):
+        c, w, s, side = self.dim, self.window, self.shift, self.side
+        g = side // w
+        h = self.norm1(x).view(-1, side, side, c)
+        if s > 0:
+            h = torch.roll(h, (-s, -s), (1, 2))
+        h = h.reshape(-1, g, w, g, w, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, w * w, c)        # partition: [B nW, T, dim]
+        h = self.attn(h)
+        h = h.reshape(-1, g, g, w, w, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, side, side, c)   # reverse: the map
+        if s > 0:
+            h = torch.roll(h, (s, s), (1, 2))
+        x = h.view(-1, side * side, c) + x
+        return self.fc2(self.act(self.fc1(self.norm2(x)))) + x
+
+
+class PatchMerging(nn.Module):
+    """Swin's downsampling between two stages: the four pixels of every 2 x 2 patch of the `side` x `side` map concatenated along the
+    channels ([B, L / 4, 4 dim]), a LayerNorm, a Linear to 2 dim without bias."""
+
+    def __init__(self, dim, side):
+        super().__init__()
+        if side % 2:
+            raise ValueError(f"PatchMerging: a {side} x {side} map has no 2 x 2 patches")
+        self.dim, self.side = dim, side
+        self.norm, self.reduce = nn.LayerNorm(4 * dim), nn.Linear(4 * dim, 2 * dim, bias=False)
+
+    def forward(self, x):
+        side, c = self.side, self.dim
+        x = x.view(-1, side, side, c)
+        x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+        return self.reduce(self.norm(x.view(-1, side * side // 4, 4 * c)))
+
+
+class SwinNet(nn.Module):
+    """The Swin transformer in plain torch: patches of `patch_size`^2 pixels embedded by a Linear on the flattened patch (ViT's
+    spelling) and a LayerNorm, then stages of SwinBlocks on [B, L, C] with a PatchMerging between two stages (the map halves, the
+    width doubles), WindowViT's head (LayerNorm -> Linear on the token mean).  A stage's window is min(window, the map's side); every
+    second block of a stage is shifted by half a window, none where the map is a single window.  The embedding has 3 patch_size^2 = 48
+    in-features at the default patch size: no multiple of 64, so it stays outside the int8 plan (utils/fuse.py's rule for every
+    Linear) and runs its own wrapper - expected; every other Linear's in-features are multiples of 64 where `dim` is."""
+
+    def __init__(self, num_classes=1000, dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=7, image_size=224, patch_size=4,
+                 mlp_ratio=4, channels=3):
+        super().__init__()
+        if dim % 64 or image_size % patch_size or len(depths) != len(heads):
+            raise ValueError(f"SwinNet: dim {dim} (a multiple of 64), image {image_size} / patch {patch_size}, {len(depths)} stages / {len(heads)} head counts")
+        self.patch, self.grid, self.channels = patch_size, image_size // patch_size, channels
+        self.embed, self.embed_norm = nn.Linear(channels * patch_size * patch_size, dim), nn.LayerNorm(dim)
+        side, c, layers = self.grid, dim, []
+        for i, (depth, h) in enumerate(zip(depths, heads)):
+            if i:
+                layers.append(PatchMerging(c, side))
+                side, c = side // 2, 2 * c
+            w = min(window, side)
+            layers += [SwinBlock(c, h, w, w // 2 if j % 2 and side > w else 0, side, mlp_ratio * c) for j in range(depth)]
+        self.stages = nn.Sequential(*layers)
+        self.norm = nn.LayerNorm(c)
+        self.head = nn.Linear(c, num_classes)
+
+    def forward(self, img):
+        p, g = self.patch, self.grid
+        x = img.reshape(-1, self.channels, g, p, g, p).permute(0, 2, 4, 3, 5, 1).reshape(-1, g * g, p * p * self.channels)
+        x = self.stages(self.embed_norm(self.embed(x)))
+        return self.head(self.norm(x.mean(1)))
+
+
 def _init(model):
     for m in model.modules():
         if isinstance(m, nn.Conv2d):
@@ -601,6 +681,13 @@ def window_vit(num_classes=1000, dim=128, heads=4, window=7, grid=2, depth=4):
     """Window-attention blocks at Swin-T's stage-1 head shape (T = 49 tokens per window, heads of 32) on a [B, dim, 14, 14] map: 4 windows
     per image, `depth` blocks, every second one with the shift mask."""
     return WindowViT(dim, heads, window, grid, depth, 4, num_classes)
+
+
+def swin(num_classes=1000, dim=128, depths=(2, 2, 18, 2), heads=(4, 8, 16, 32), window=7, image_size=224, patch_size=4):
+    """Swin at Swin-B's widths (dim 128: heads of 32, stages of 2 / 2 / 18 / 2 blocks on maps of 56 / 28 / 14 / 7 tokens a side, windows
+    of 7) - Swin-T's 96 is no multiple of 64, and the int8 plan takes no such Linear.  The roll, the window partition and reverse and
+    the patch merging are spelled as `fuse_inference(swin_geometry=True)` takes them."""
+    return SwinNet(num_classes, dim, depths, heads, window, image_size, patch_size)
 
 
 def _named_option(option):

@@ -1096,6 +1096,43 @@ int dlmcq_layernorm_rows_f32(const float* x, const float* gamma, const float* be
                              float eps, const float* q_scale, const float* q_zero_point, int32_t q_lo, int32_t q_hi, int32_t q_form,
                              float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- LayerNorm of rows gathered from an fp32 token map x[B, Hm, Wm, C]: a Swin block's shifted windows, a stage's 2 x 2 patch merge ----
+ * The map is a pointer and strides in floats (channel stride 1): the contiguous [B, L, C] residual stream, or a row-padded buffer, read
+ * in place.  Dense output rows [M, W], fp32 and / or the consumer's codes, row m gathered as `mode` says:
+ *   DLMCQ_GATHER_WINDOW  W = C, M = B (Hm / ws) (Wm / ws) ws^2: row ((b nWy + wy) nWx + wx) ws^2 + ty ws + tx is map pixel
+ *                        ((wy ws + ty + sy) mod Hm, (wx ws + tx + sx) mod Wm) - torch.roll(x, (-sy, -sx), (1, 2)), then the partition
+ *                        x.reshape(B, nWy, ws, nWx, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws ws, C)
+ *   DLMCQ_GATHER_MERGE   W = 4 C, M = B (Hm / 2) (Wm / 2): row (b, y2, x2) is four C-wide segments, segment k read from pixel
+ *                        (2 y2 + (k & 1), 2 x2 + (k >> 1)) - cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+ * A gathered row's result has the SAME BITS as dlmcq_layernorm_rows_f32 on that row materialised (width W): the operation order, the
+ * error bound, the quantiser (plain codes only) and the non-finite behaviour are that entry point's.  No LDS, no atomics, no scratch.
+ *   x        fp32 map, 16-byte aligned; stride_b / stride_y / stride_x floats between images / lines / pixels, each a multiple of 4,
+ *            stride_x >= C, stride_y >= Wm stride_x, stride_b >= Hm stride_y
+ *   gamma, beta  fp32 [W], 16-byte aligned, or NULL;  out  fp32 [M, W] dense, 16-byte aligned, or NULL;  codes  bytes [M, W], 4-byte
+ *            aligned, or NULL (needs q_scale)
+ *   ws, sy, sx   window side and the shifts, 0 <= sy < Hm, 0 <= sx < Wm (DLMCQ_GATHER_MERGE: ws is ignored, sy = sx = 0)
+ * DLMCQ_EINVAL: an unknown mode, B < 0, Hm or Wm < 1, C < 4, C % 4, W > 2048; window: ws < 1, Hm % ws, Wm % ws, a shift out of range;
+ * merge: Hm or Wm odd, a shift other than 0; a stride that is negative, no multiple of 4 or too short; eps not finite or not > 0; x
+ * NULL, both outputs NULL, an invalid quantiser or any flag in q_form.  DLMCQ_EALIGN as dlmcq_layernorm_rows_f32.  DLMCQ_ERANGE: B, Hm, Wm,
+ * M or M * W / 4 reaches 2^31.  M == 0: DLMCQ_OK, nothing launched.  A refused call writes nothing. */
+#define DLMCQ_GATHER_WINDOW 0
+#define DLMCQ_GATHER_MERGE 1
+int dlmcq_layernorm_gather_rows_f32(const float* x, const float* gamma, const float* beta, float* out, void* codes, int32_t mode, int64_t B,
+                                    int64_t Hm, int64_t Wm, int64_t C, int64_t stride_b, int64_t stride_y, int64_t stride_x, int64_t ws,
+                                    int64_t sy, int64_t sx, float eps, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                                    int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
+/* ---- Window reverse, roll back and residual add: out[b, y, x, :] = fl32(shortcut[b, y, x, :] + yw[row(b, y, x), :]) ----
+ * row(b, y, x) is the DLMCQ_GATHER_WINDOW row whose token sits at rolled position ((y - sy) mod Hm, (x - sx) mod Wm) - in torch terms
+ * shortcut + roll(reverse(yw), (+sy, +sx), (1, 2)) with reverse = yw.reshape(B, nWy, nWx, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B,
+ * Hm, Wm, C).  One IEEE add per element, the bits of torch's add; fp32 only.  No LDS, no atomics, no scratch.
+ *   yw        fp32 [B (Hm / ws) (Wm / ws) ws^2, C] dense;  shortcut, out  fp32 map views with strides as above;  all 16-byte aligned
+ * `out` must overlap neither yw nor the shortcut.  DLMCQ_EINVAL: the geometry and stride refusals above, a NULL pointer, an overlap.
+ * DLMCQ_EALIGN: a pointer not 16-byte aligned.  DLMCQ_ERANGE: B, Hm, Wm, B Hm Wm or B Hm Wm C / 4 reaches 2^31.  B == 0: DLMCQ_OK. */
+int dlmcq_window_reverse_add_f32(const float* yw, const float* shortcut, float* out, int64_t B, int64_t Hm, int64_t Wm, int64_t C,
+                                 int64_t sc_stride_b, int64_t sc_stride_y, int64_t sc_stride_x, int64_t out_stride_b, int64_t out_stride_y,
+                                 int64_t out_stride_x, int64_t ws, int64_t sy, int64_t sx, dlmcq_stream_t stream);
+
 /* ---- Scaled dot-product attention softmax(scale q k^T) v: fp32 and / or the activation codes of the projection behind it ----
  * One flash forward per query tile (csrc/attention.hip): nothing of size Tq x Tk touches memory.  No mask, no causal flag, no dropout.
  * For query row i of one (b, h), keys j = 0 .. Tk - 1 in blocks of 32 (the online softmax's key block), u = 2^-24:
