@@ -39,12 +39,9 @@
 // key blocks of 32 rows (17.3 KiB at D = 64, rows padded by 2 and 8 floats against bank conflicts).  A wave whose 32 rows lie past Tq
 // only loads; which wave that is rotates with the head index, so the idle waves spread over the SIMDs.  No atomics, no scratch: a
 // row's result depends neither on B, H, its (b, h) nor on the launch.
-#include "conv_gap.h"
+#include "attention_common.h"
 
 namespace dlmcq {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int D>
 __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs a, ConvEpi ep) {
@@ -62,15 +59,7 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
   const float* vb_ = a.v + b * a.vs[0] + h * a.vs[1];
 
   float qr[D / 2];      // q_i[2 s + half]: the B operand of k step s
-  if (active) {
-    const f32x4* qp = reinterpret_cast<const f32x4*>(a.q + b * a.qs[0] + h * a.qs[1] + (int64_t)(qi < a.Tq ? qi : a.Tq - 1) * a.qs[2]);
-#pragma unroll
-    for (int f = 0; f < D4; ++f) {
-      const f32x4 t = qp[f];
-      qr[2 * f] = half ? t.y : t.x;
-      qr[2 * f + 1] = half ? t.w : t.z;
-    }
-  }
+  if (active) load_operand_row<D>(a.q + b * a.qs[0] + h * a.qs[1], a.qs[2], qi < a.Tq ? qi : a.Tq - 1, half, qr);
   f32x16 o[CB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
@@ -100,17 +89,11 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
     for (int r = 0; r < 16; ++r) s[r] = 0.0f;
 #pragma unroll
     for (int st = 0; st < D / 2; ++st) s = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_k[col * KS + 2 * st + half], qr[st], s, 0, 0, 0);
-    const int key0 = kb * DLMCQ_AT_KB + 4 * half;
-    float bm = -__builtin_inff();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float t = s[r] * a.scale;
-      if (key0 + (r & 3) + 8 * (r >> 2) >= a.Tk) t = -__builtin_inff();
-      s[r] = t;
-      bm = fmaxf(bm, t);
-    }
-    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-    const float mn = fmaxf(m, bm);
+    for (int r = 0; r < 16; ++r) s[r] = s[r] * a.scale;
+    mask_tail(s, kb * DLMCQ_AT_KB + 4 * half, a.Tk);
+    const float bm = acc_max(-__builtin_inff(), s);
+    const float mn = fmaxf(m, fmaxf(bm, other_half(bm)));
     const float mu = mn == -__builtin_inff() ? 0.0f : mn;
     const float al = expf(m - mu);
     m = mn;
@@ -135,8 +118,8 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
       for (int rr = 0; rr < 4; ++rr) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const int r = 4 * g + rr, krow = (r & 3) + 8 * (r >> 2) + 4 * half;
-          t4[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_v[krow * VS + cb * 32 + col], s[r], t4[g], 0, 0, 0);
+          const int r = 4 * g + rr;
+          t4[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_v[acc_key(r, half) * VS + cb * 32 + col], s[r], t4[g], 0, 0, 0);
         }
       }
 #pragma unroll
@@ -145,27 +128,16 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES) void attention_kernel(AttnArgs
     }
   }
   if (!active) return;
-  l = l + __shfl_xor(l, 32, 64);
+  l = l + other_half(l);
   if (qi >= a.Tq) return;
-  const int64_t at = b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2];
-  const EpiQuant eq(ep);
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 v = f32x4{o[cb][4 * g] / l, o[cb][4 * g + 1] / l, o[cb][4 * g + 2] / l, o[cb][4 * g + 3] / l};
-      const int64_t e = at + cb * 32 + 8 * g + 4 * half;
-      if (a.out) *reinterpret_cast<f32x4*>(a.out + e) = v;
-      if (ep.codes) *reinterpret_cast<uint32_t*>(ep.codes + e) = eq.code4(v);
-    }
-  }
+  store_normalised<CB>(o, l, a.out, ep, EpiQuant(ep), b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2], half);
 }
 
 }  // namespace dlmcq
 
 using namespace dlmcq;
 
-// The checks: attention_args (csrc/conv_gap.h), shared with dlmcq_attention_f16.
+// The checks and the launch: attention_args, attention_launch (csrc/attention_common.h), shared with dlmcq_attention_f16.
 extern "C" int dlmcq_attention_f32(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
                                    int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
                                    int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
@@ -178,8 +150,5 @@ extern "C" int dlmcq_attention_f32(const float* q, const float* k, const float* 
   const int rc = attention_args(a, ep, &blocks, q, k, v, out, codes, B, H, Tq, Tk, D, strides, scale, q_scale, q_zero_point, q_lo, q_hi, q_form,
                                 q_ste_g);
   if (rc != DLMCQ_OK || blocks == 0) return rc;
-  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_AT_WAVES);
-  if (D == 64) hipLaunchKernelGGL((attention_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  else hipLaunchKernelGGL((attention_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  return launch_status();
+  return attention_launch(attention_kernel<64>, attention_kernel<32>, a, ep, blocks, 64 * DLMCQ_AT_WAVES, D, stream);
 }

@@ -67,21 +67,9 @@
 // and denominator are each off by at most Tk 2^-25 max_j |v_jc| relative to l: Tk 2^-24 max_j |v_jc|.  An f16-subnormal v (|v| < 2^-14)
 // is off by 2^-25, times weights that sum to 1.  No margin factor.  Measured ratios: DESIGN.md 5.32.
 // No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.
-#include "conv_gap.h"
+#include "attention_common.h"
 
 namespace dlmcq {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f16x2 h2(float a, float b) { return __builtin_convertvector(f32x2{a, b}, f16x2); }      // RNE, packed
-__device__ __forceinline__ f16x8 h8(const f32x4& a, const f32x4& b) {
-  const f16x2 p0 = h2(a.x, a.y), p1 = h2(a.z, a.w), p2 = h2(b.x, b.y), p3 = h2(b.z, b.w);
-  return f16x8{p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
-}
 
 template <int D>
 struct AttnF16 {
@@ -110,7 +98,7 @@ struct AttnF16 {
       st.k[it] = row4(kb_, a.ks[2], kb * DLMCQ_AT_KB + idx / D4, a.Tk, idx % D4);
     }
     if (VITEMS >= THREADS || tid < VITEMS) {      // (D = 32: waves 0 and 1)
-      const int pos = 2 * (tid / D4), key = (pos & 19) | ((pos & 4) << 1) | ((pos & 8) >> 1);      // bits 2 and 3 exchanged
+      const int key = swap23(2 * (tid / D4));
       st.v0 = row4(vb_, a.vs[2], kb * DLMCQ_AT_KB + key, a.Tk, tid % D4);
       st.v1 = row4(vb_, a.vs[2], kb * DLMCQ_AT_KB + key + 1, a.Tk, tid % D4);
     }
@@ -124,11 +112,8 @@ struct AttnF16 {
       *reinterpret_cast<f16x4*>(&lk[(idx / D4) * KROW + (idx % D4) * 4]) = f16x4{lo.x, lo.y, hi.x, hi.y};
     }
     if (VITEMS >= THREADS || tid < VITEMS) {
-      const int pos = 2 * (tid / D4), c = 4 * (tid % D4);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c) + pos]) = h2(st.v0.x, st.v1.x);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 1) + pos]) = h2(st.v0.y, st.v1.y);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 2) + pos]) = h2(st.v0.z, st.v1.z);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 3) + pos]) = h2(st.v0.w, st.v1.w);
+      const int c = 4 * (tid % D4);
+      store_v_pairs(lv, vrow(c), vrow(c + 1), vrow(c + 2), vrow(c + 3), 2 * (tid / D4), st.v0, st.v1);
     }
   }
 };
@@ -151,11 +136,7 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES, 4) void attention_f16_kernel(A
   typename T::Staged st;
   T::load(st, a, kb_, vb_, 0, tid);
   f16x8 qh[QS];      // h(q_i[16 s + 8 half .. + 7]): the B operand of score step s
-  if (active) {
-    const f32x4* qp = reinterpret_cast<const f32x4*>(a.q + b * a.qs[0] + h * a.qs[1] + (int64_t)(qi < a.Tq ? qi : a.Tq - 1) * a.qs[2]);
-#pragma unroll
-    for (int s = 0; s < QS; ++s) qh[s] = h8(qp[4 * s + 2 * half], qp[4 * s + 2 * half + 1]);
-  }
+  if (active) load_operand_f16<QS>(a.q + b * a.qs[0] + h * a.qs[1] + (int64_t)(qi < a.Tq ? qi : a.Tq - 1) * a.qs[2], half, qh);
   f32x16 o[CB];
 #pragma unroll
   for (int cb = 0; cb < CB; ++cb)
@@ -177,33 +158,16 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES, 4) void attention_f16_kernel(A
 #pragma unroll
       for (int t = 0; t < QS; ++t)
         s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(&lk[col * KROW + 16 * t + 8 * half]), qh[t], s, 0, 0, 0);
-      const int key0 = kb * DLMCQ_AT_KB + 4 * half;
-      float bm = -__builtin_inff();
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float t = s[r] * a.scale;
-        if (key0 + (r & 3) + 8 * (r >> 2) >= a.Tk) t = -__builtin_inff();
-        s[r] = t;
-        bm = fmaxf(bm, t);
-      }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
+      for (int r = 0; r < 16; ++r) s[r] = s[r] * a.scale;
+      mask_tail(s, kb * DLMCQ_AT_KB + 4 * half, a.Tk);
+      const float bm = acc_max(-__builtin_inff(), s);
+      const float mn = fmaxf(m, fmaxf(bm, other_half(bm)));
       const float mu = mn == -__builtin_inff() ? 0.0f : mn;
       const float al = __builtin_amdgcn_exp2f(m - mu);
       m = mn;
       f16x8 ph[2];
-      float x[16];
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const f16x2 p = h2(__builtin_amdgcn_exp2f(s[r] - mu), __builtin_amdgcn_exp2f(s[r + 1] - mu));
-        ph[r >> 3][r & 7] = p.x;
-        ph[r >> 3][(r & 7) + 1] = p.y;
-        x[r] = (float)p.x;
-        x[r + 1] = (float)p.y;
-      }
-      const float t0 = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
-      const float t1 = ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
-      l = l * al + (t0 + t1);
+      l = l * al + p_step_f16<true>(s, mu, ph);      // (the scale holds log2 e: the scores are in base-2 units)
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
 #pragma unroll
@@ -218,27 +182,17 @@ __global__ __launch_bounds__(64 * DLMCQ_AT_WAVES, 4) void attention_f16_kernel(A
     __syncthreads();      // (block kb + 1 is published; every read of block kb is done)
   }
   if (!active) return;
-  l = l + __shfl_xor(l, 32, 64);
+  l = l + other_half(l);
   if (qi >= a.Tq) return;
-  const int64_t at = b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2];
-  const EpiQuant eq(ep);
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 v = f32x4{o[cb][4 * g] / l, o[cb][4 * g + 1] / l, o[cb][4 * g + 2] / l, o[cb][4 * g + 3] / l};
-      const int64_t e = at + cb * 32 + 8 * g + 4 * half;
-      if (a.out) *reinterpret_cast<f32x4*>(a.out + e) = v;
-      if (ep.codes) *reinterpret_cast<uint32_t*>(ep.codes + e) = eq.code4(v);
-    }
-  }
+  store_normalised<CB>(o, l, a.out, ep, EpiQuant(ep), b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2], half);
 }
 
 }  // namespace dlmcq
 
 using namespace dlmcq;
 
-// The checks: attention_args (csrc/conv_gap.h), shared with dlmcq_attention_f32; the kernel takes c = fl32(scale log2 e) for the scale.
+// The checks and the launch: attention_args, attention_launch (csrc/attention_common.h), shared with dlmcq_attention_f32; the kernel
+// takes c = fl32(scale log2 e) for the scale.
 extern "C" int dlmcq_attention_f16(const float* q, const float* k, const float* v, float* out, void* codes, int64_t B, int64_t H, int64_t Tq,
                                    int64_t Tk, int64_t D, int64_t q_sb, int64_t q_sh, int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st,
                                    int64_t v_sb, int64_t v_sh, int64_t v_st, int64_t o_sb, int64_t o_sh, int64_t o_st, float scale,
@@ -252,8 +206,5 @@ extern "C" int dlmcq_attention_f16(const float* q, const float* k, const float* 
                                 q_ste_g);
   if (rc != DLMCQ_OK || blocks == 0) return rc;
   a.scale = (float)((double)scale * 1.4426950408889634074);
-  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_AT_WAVES);
-  if (D == 64) hipLaunchKernelGGL((attention_f16_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  else hipLaunchKernelGGL((attention_f16_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  return launch_status();
+  return attention_launch(attention_f16_kernel<64>, attention_f16_kernel<32>, a, ep, blocks, 64 * DLMCQ_AT_WAVES, D, stream);
 }

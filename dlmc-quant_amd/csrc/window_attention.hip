@@ -43,21 +43,9 @@
 // A workgroup is 4 waves = 4 consecutive (b, h): neighbouring heads of one window, which share the cache lines of the packed qkv rows.
 // LDS 40 KiB (D = 32) / 72 KiB (D = 64) per workgroup: two workgroups fit a CU at D = 64.  No atomics, no scratch: a row's result
 // depends neither on B, H, its (b, h) nor on the launch.
-#include "conv_gap.h"
+#include "attention_common.h"
 
 namespace dlmcq {
-
-// row `row` of a [T, D] view as the operand of the 32x32x2 MFMA whose k steps walk D: element 2 s + half of the row in register s
-template <int D>
-__device__ __forceinline__ void load_operand_row(const float* base, int64_t row_stride, int row, int half, float (&r)[D / 2]) {
-  const f32x4* p = reinterpret_cast<const f32x4*>(base + (int64_t)row * row_stride);
-#pragma unroll
-  for (int f = 0; f < D / 4; ++f) {
-    const f32x4 t = p[f];
-    r[2 * f] = half ? t.y : t.x;
-    r[2 * f + 1] = half ? t.w : t.z;
-  }
-}
 
 template <int D>
 __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(WinAttnArgs a, ConvEpi ep) {
@@ -109,16 +97,10 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
       for (int r = 0; r < 16; ++r) s[kb][r] = s[kb][r] * a.scale;
       if (bias) add_term(s[kb], bias + (int64_t)qrow * a.bias_st, key0, T);
       if (mask) add_term(s[kb], mask + (int64_t)qrow * a.mask_st, key0, T);
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (key0 + (r & 3) + 8 * (r >> 2) >= T) s[kb][r] = -__builtin_inff();
+      mask_tail(s[kb], key0, T);
     }
-    float m = -__builtin_inff();
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) m = fmaxf(m, s[kb][r]);
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    float m = acc_max(acc_max(-__builtin_inff(), s[0]), s[1]);
+    m = fmaxf(m, other_half(m));
     const float mu = m == -__builtin_inff() ? 0.0f : m;
     float l = 0.0f;
 #pragma unroll
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
         l = (kb | r) ? l + s[kb][r] : s[kb][r];
       }
     }
-    l = l + __shfl_xor(l, 32, 64);
+    l = l + other_half(l);
     const int64_t at = b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
@@ -149,8 +131,8 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
         for (int rr = 0; rr < 4; ++rr) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            const int r = 4 * g + rr, krow = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            t4[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_v[krow * VS + cb * 32 + col], s[kb][r], t4[g], 0, 0, 0);
+            const int r = 4 * g + rr;
+            t4[g] = __builtin_amdgcn_mfma_f32_32x32x2f32(lds_v[(kb * 32 + acc_key(r, half)) * VS + cb * 32 + col], s[kb][r], t4[g], 0, 0, 0);
           }
         }
 #pragma unroll
@@ -159,15 +141,7 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
           o[r] = kb ? o[r] + w : w;
         }
       }
-      if (qi < T) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = f32x4{o[4 * g] / l, o[4 * g + 1] / l, o[4 * g + 2] / l, o[4 * g + 3] / l};
-          const int64_t e = at + cb * 32 + 8 * g + 4 * half;
-          if (a.out) *reinterpret_cast<f32x4*>(a.out + e) = v;
-          if (ep.codes) *reinterpret_cast<uint32_t*>(ep.codes + e) = eq.code4(v);
-        }
-      }
+      if (qi < T) store_normalised<1>(&o, l, a.out, ep, eq, at + cb * 32, half);
       __builtin_amdgcn_sched_barrier(0);      // (one channel block's accumulators at a time)
     }
   }
@@ -177,7 +151,7 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES) void window_attention_kernel(W
 
 using namespace dlmcq;
 
-// The checks: window_attention_args (csrc/conv_gap.h), shared with dlmcq_window_attention_f16.
+// The checks and the launch: window_attention_args, attention_launch (csrc/attention_common.h), shared with dlmcq_window_attention_f16.
 extern "C" int dlmcq_window_attention_f32(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
                                           void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
                                           int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
@@ -191,8 +165,5 @@ extern "C" int dlmcq_window_attention_f32(const float* q, const float* k, const 
   const int rc = window_attention_args(a, ep, &blocks, q, k, v, bias, mask, out, codes, B, H, T, D, nW, strides, bias_sh, bias_st, mask_sw,
                                        mask_st, scale, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   if (rc != DLMCQ_OK || blocks == 0) return rc;
-  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_WA_WAVES);
-  if (D == 64) hipLaunchKernelGGL((window_attention_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  else hipLaunchKernelGGL((window_attention_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  return launch_status();
+  return attention_launch(window_attention_kernel<64>, window_attention_kernel<32>, a, ep, blocks, 64 * DLMCQ_WA_WAVES, D, stream);
 }

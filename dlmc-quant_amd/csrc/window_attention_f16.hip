@@ -75,33 +75,15 @@
 // 32 (s) + 16 (k) + 16 (q) + 16 (a term's pieces), then 16 (P) + 16 (o, one channel block at a time).  __launch_bounds__(256, 4): at
 // most 128 VGPRs; the compiler takes 115 / 83, no spill: 4 / 5 waves per SIMD (fp32 kernel: 2).  Table: DESIGN.md 5.33.
 // No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.
-#include "conv_gap.h"
+#include "attention_common.h"
 
 namespace dlmcq {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f16x2 h2(float a, float b) { return __builtin_convertvector(f32x2{a, b}, f16x2); }      // RNE, packed
-__device__ __forceinline__ f16x8 h8(const f32x4& a, const f32x4& b) {
-  const f16x2 p0 = h2(a.x, a.y), p1 = h2(a.z, a.w), p2 = h2(b.x, b.y), p3 = h2(b.z, b.w);
-  return f16x8{p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
-}
-__device__ __forceinline__ constexpr int swap23(int x) { return (x & ~12) | ((x & 4) << 1) | ((x & 8) >> 1); }      // bits 2 and 3 exchanged
 
 template <int D>
 struct WinF16 {
   static constexpr int D4 = D / 4, CB = D / 32, QS = D / 16;
   static constexpr int VSIZE = D * 72 + (D / 16) * 8;      // halves of one wave's v slice
   __device__ static constexpr int vrow(int c) { return c * 72 + (c >> 4) * 8; }
-
-  // h(row[16 s + 8 half .. + 7]), s = 0 .. QS - 1: the score MFMA's operand of this lane
-  __device__ static __forceinline__ void operand(const float* row, int half, f16x8 (&r)[QS]) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(row);
-#pragma unroll
-    for (int s = 0; s < QS; ++s) r[s] = h8(p[4 * s + 2 * half], p[4 * s + 2 * half + 1]);
-  }
 
   // v of the head -> lv, f16, channel-major, the keys in the operand's order, +0 past T - 1.  Item y of a lane: position pair
   // lane / D4 + (64 / D4) y (D = 32: with bits 2 and 3 exchanged, the bank rule of the header), channels 4 (lane % D4) .. + 3
@@ -114,10 +96,7 @@ struct WinF16 {
       f32x4 v1 = *reinterpret_cast<const f32x4*>(vb + (int64_t)(in1 ? key + 1 : T - 1) * stride + c);
       if (!in0) v0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       if (!in1) v1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      *reinterpret_cast<f16x2*>(&lv[vrow(c) + pos]) = h2(v0.x, v1.x);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 1) + pos]) = h2(v0.y, v1.y);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 2) + pos]) = h2(v0.z, v1.z);
-      *reinterpret_cast<f16x2*>(&lv[vrow(c + 3) + pos]) = h2(v0.w, v1.w);
+      store_v_pairs(lv, vrow(c), vrow(c + 1), vrow(c + 2), vrow(c + 3), pos, v0, v1);
     }
   }
 };
@@ -133,18 +112,17 @@ __device__ __forceinline__ void window_f16_tiles(const WinAttnArgs& a, const Con
   const float* bias = a.bias ? a.bias + h * a.bias_sh : nullptr;
   const float* mask = a.mask ? a.mask + (b % a.nW) * a.mask_sw : nullptr;
   const EpiQuant eq(ep);
-  const float L = 1.44269502162933349609375f;      // fl32(log2 e)
 #pragma unroll 1
   for (int qt = 0; qt < NKB; ++qt) {
     const int qi = qt * 32 + col, qrow = qi < T ? qi : T - 1;
     f16x8 qh[QS];      // h(q_i[16 s + 8 half .. + 7]): the B operand of score step s
-    W::operand(qb + (int64_t)qrow * a.qs[2], half, qh);
+    load_operand_f16<QS>(qb + (int64_t)qrow * a.qs[2], half, qh);
     f32x16 s[NKB];
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
       const int key = kb * 32 + col, key0 = kb * 32 + 4 * half;
       f16x8 kh[QS];      // h(k_j[16 s + 8 half .. + 7]), j = 32 kb + col: the A operand of score step s
-      W::operand(kb_ + (int64_t)(key < T ? key : T - 1) * a.ks[2], half, kh);
+      load_operand_f16<QS>(kb_ + (int64_t)(key < T ? key : T - 1) * a.ks[2], half, kh);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
 #pragma unroll
@@ -153,36 +131,22 @@ __device__ __forceinline__ void window_f16_tiles(const WinAttnArgs& a, const Con
       for (int r = 0; r < 16; ++r) s[kb][r] = s[kb][r] * a.scale;
       if (bias) add_term(s[kb], bias + (int64_t)qrow * a.bias_st, key0, T);
       if (mask) add_term(s[kb], mask + (int64_t)qrow * a.mask_st, key0, T);
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (key0 + (r & 3) + 8 * (r >> 2) >= T) s[kb][r] = -__builtin_inff();
+      mask_tail(s[kb], key0, T);
       __builtin_amdgcn_sched_barrier(0);      // (one block's operands and term pieces at a time)
     }
     float m = -__builtin_inff();
 #pragma unroll
-    for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) m = fmaxf(m, s[kb][r]);
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    for (int kb = 0; kb < NKB; ++kb) m = acc_max(m, s[kb]);
+    m = fmaxf(m, other_half(m));
     const float mu = m == -__builtin_inff() ? 0.0f : m;
     f16x8 ph[NKB][2];      // P^T: registers 8 t .. 8 t + 7 of block kb, the B operand of step t of O^T = v^T P^T
     float l = 0.0f;
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
-      float x[16];
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const f16x2 p = h2(__builtin_amdgcn_exp2f((s[kb][r] - mu) * L), __builtin_amdgcn_exp2f((s[kb][r + 1] - mu) * L));
-        ph[kb][r >> 3][r & 7] = p.x;
-        ph[kb][r >> 3][(r & 7) + 1] = p.y;
-        x[r] = (float)p.x;
-        x[r + 1] = (float)p.y;
-      }
-      const float t0 = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
-      const float t1 = ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
-      l = kb ? l + (t0 + t1) : t0 + t1;
+      const float t = p_step_f16<false>(s[kb], mu, ph[kb]);      // (natural units: the exponent's argument is (s - m~) * fl32(log2 e))
+      l = kb ? l + t : t;
     }
-    l = l + __shfl_xor(l, 32, 64);
+    l = l + other_half(l);
     const int64_t at = b * a.os[0] + h * a.os[1] + (int64_t)qi * a.os[2];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
@@ -195,15 +159,7 @@ __device__ __forceinline__ void window_f16_tiles(const WinAttnArgs& a, const Con
         for (int t = 0; t < 2; ++t)
           o = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(&lv[W::vrow(cb * 32 + col) + 32 * kb + 16 * t + 8 * half]),
                                                      ph[kb][t], o, 0, 0, 0);
-      if (qi < T) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = f32x4{o[4 * g] / l, o[4 * g + 1] / l, o[4 * g + 2] / l, o[4 * g + 3] / l};
-          const int64_t e = at + cb * 32 + 8 * g + 4 * half;
-          if (a.out) *reinterpret_cast<f32x4*>(a.out + e) = v;
-          if (ep.codes) *reinterpret_cast<uint32_t*>(ep.codes + e) = eq.code4(v);
-        }
-      }
+      if (qi < T) store_normalised<1>(&o, l, a.out, ep, eq, at + cb * 32, half);
       __builtin_amdgcn_sched_barrier(0);      // (one channel block's accumulators at a time)
     }
   }
@@ -233,7 +189,7 @@ __global__ __launch_bounds__(64 * DLMCQ_WA_WAVES, 4) void window_attention_f16_k
 
 using namespace dlmcq;
 
-// The checks: window_attention_args (csrc/conv_gap.h), shared with dlmcq_window_attention_f32.
+// The checks and the launch: window_attention_args, attention_launch (csrc/attention_common.h), shared with dlmcq_window_attention_f32.
 extern "C" int dlmcq_window_attention_f16(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
                                           void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
                                           int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
@@ -247,8 +203,5 @@ extern "C" int dlmcq_window_attention_f16(const float* q, const float* k, const 
   const int rc = window_attention_args(a, ep, &blocks, q, k, v, bias, mask, out, codes, B, H, T, D, nW, strides, bias_sh, bias_st, mask_sw,
                                        mask_st, scale, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   if (rc != DLMCQ_OK || blocks == 0) return rc;
-  const dim3 grid((uint32_t)blocks), block(64 * DLMCQ_WA_WAVES);
-  if (D == 64) hipLaunchKernelGGL((window_attention_f16_kernel<64>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  else hipLaunchKernelGGL((window_attention_f16_kernel<32>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), a, ep);
-  return launch_status();
+  return attention_launch(window_attention_f16_kernel<64>, window_attention_f16_kernel<32>, a, ep, blocks, 64 * DLMCQ_WA_WAVES, D, stream);
 }

@@ -1702,7 +1702,7 @@ def assemble_tokens(e, cls, pos):
 
 
 ATTENTION_DIMS = (32, 64)    # dlmcq_attention_f32 / _f16: the head dimensions the kernels are built for
-ATTENTION_OPERANDS = ("f32", "f16")    # attention_quant(operands=...): the matrix-core operand type, dlmcq_attention_f32 / dlmcq_attention_f16
+ATTENTION_OPERANDS = ("f32", "f16")    # attention_quant / window_attention_quant(operands=...): the matrix-core operand type, dlmcq_*_f32 / dlmcq_*_f16
 
 
 def attention_views(q, k, v):
@@ -1720,6 +1720,25 @@ def attention_views(q, k, v):
     return True
 
 
+def _attention_front(kernel, views, views_text, q, k, v, terms, scale, emit, want_out, operands):
+    """What attention_quant and window_attention_quant (`kernel`: "attention" / "window_attention") check before anything of their own:
+    `operands`, the device, the views (`views`, described by `views_text`), something to produce, a finite scale.  Returns q, k, v
+    detached, the scale as a float, and the entry point and PROFILE tag that `operands` picks."""
+    fn = kernel + "_quant"
+    if operands not in ATTENTION_OPERANDS:
+        raise ValueError(f"{fn}: operands is one of {ATTENTION_OPERANDS}, not {operands!r}")
+    N.require_gpu(q, k, v, *terms)
+    if not views(q, k, v):
+        raise ValueError(f"{fn}: fp32 views {views_text}, D in (32, 64), unit stride in D, strides multiples of 4 elements, 16-byte aligned")
+    if not want_out and emit is None:
+        raise ValueError(f"{fn}: nothing to produce (want_out=False without emit)")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"{fn}: a finite scale, not {scale}")
+    entry, tag = getattr(N.lib, f"dlmcq_{kernel}_{operands}"), (kernel if operands == "f32" else f"{kernel}_{operands}")
+    return q.detach(), k.detach(), v.detach(), scale, entry, tag
+
+
 def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True, operands="f32"):
     """softmax(scale * q k^T) v of fp32 views `q` [B, H, Tq, D], `k`, `v` [B, H, Tk, D] (attention_views: read in place, the three
     slices of one packed projection included) by dlmcq_attention_f32: one flash forward on the f32 matrix cores - k-ordered fmaf
@@ -1731,31 +1750,20 @@ def attention_quant(q, k, v, scale, emit=None, want_out=True, merged=True, opera
     operands of the f16 matrix cores, fp32 everywhere else (csrc/attention_f16.hip states the arithmetic, the bound and the range
     limit: inputs above 65504 in magnitude become infinite); recorded as PROFILE launch "attention_f16".  Opt-in: the default is the
     fp32 kernel, bit for bit."""
-    if operands not in ATTENTION_OPERANDS:
-        raise ValueError(f"attention_quant: operands is one of {ATTENTION_OPERANDS}, not {operands!r}")
-    N.require_gpu(q, k, v)
-    if not attention_views(q, k, v):
-        raise ValueError("attention_quant: fp32 views q [B, H, Tq, D], k, v [B, H, Tk, D], D in (32, 64), unit stride in D, strides "
-                         "multiples of 4 elements, 16-byte aligned")
-    if not want_out and emit is None:
-        raise ValueError("attention_quant: nothing to produce (want_out=False without emit)")
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError(f"attention_quant: a finite scale, not {scale}")
-    q, k, v = q.detach(), k.detach(), v.detach()
+    q, k, v, scale, entry, tag = _attention_front("attention", attention_views, "q [B, H, Tq, D], k, v [B, H, Tk, D]", q, k, v, (), scale,
+                                                  emit, want_out, operands)
     b, h, tq, d = q.shape
     tk = k.shape[2]
     shape = (b, tq, h * d) if merged else (b, h, tq, d)
     o_strides = (tq * h * d, d, h * d) if merged else (h * tq * d, tq * d, d)
     nbytes = 4 * b * h * d * (tq + 2 * tk) + b * h * tq * d * (4 * want_out + (emit is not None))
-    entry, tag = (N.lib.dlmcq_attention_f16, "attention_f16") if operands == "f16" else (N.lib.dlmcq_attention_f32, "attention")
     return _emit_launch("attention_quant", tag, q, shape, emit, want_out, nbytes, lambda op, cp, *tail: entry(
         N.ptr(q), N.ptr(k), N.ptr(v), op, cp, b, h, tq, tk, d, *q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *o_strides, scale, *tail),
         ops=4 * b * h * tq * tk * d)
 
 
 WINDOW_TOKENS = 64    # dlmcq_window_attention_f32 / _f16: the most tokens of a window (one wave holds the T x T score tile)
-WINDOW_ATTENTION_OPERANDS = ("f32", "f16")    # window_attention_quant(operands=...): dlmcq_window_attention_f32 / dlmcq_window_attention_f16
+WINDOW_ATTENTION_OPERANDS = ATTENTION_OPERANDS
 
 
 def window_term_view(t, tokens):
@@ -1810,18 +1818,8 @@ def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want
     to f16 as operands of the f16 matrix cores, fp32 everywhere else (csrc/window_attention_f16.hip states the arithmetic, the bound and
     the range limit: inputs above 65504 in magnitude become infinite); recorded as PROFILE launch "window_attention_f16".  Opt-in: the
     default is the fp32 kernel, bit for bit."""
-    if operands not in WINDOW_ATTENTION_OPERANDS:
-        raise ValueError(f"window_attention_quant: operands is one of {WINDOW_ATTENTION_OPERANDS}, not {operands!r}")
-    N.require_gpu(q, k, v, *(t for t in (bias, mask) if t is not None))
-    if not window_attention_views(q, k, v):
-        raise ValueError("window_attention_quant: fp32 views q, k, v [B, H, T, D], T in 1 .. 64, D in (32, 64), unit stride in D, strides "
-                         "multiples of 4 elements, 16-byte aligned")
-    if not want_out and emit is None:
-        raise ValueError("window_attention_quant: nothing to produce (want_out=False without emit)")
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError(f"window_attention_quant: a finite scale, not {scale}")
-    q, k, v = q.detach(), k.detach(), v.detach()
+    q, k, v, scale, entry, tag = _attention_front("window_attention", window_attention_views, "q, k, v [B, H, T, D], T in 1 .. 64", q, k, v,
+                                                  [t for t in (bias, mask) if t is not None], scale, emit, want_out, operands)
     b, h, t, d = q.shape
     bt, rows, bias_sh, bias_st = _window_term(bias.detach(), t, "bias") if bias is not None else (None, h, 0, 0)
     if rows not in (1, h):
@@ -1831,8 +1829,6 @@ def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want
         raise ValueError(f"window_attention_quant: a mask of {nw} windows for a batch of {b}")
     terms = (bias is not None) + (mask is not None)
     nbytes = 4 * b * h * d * 3 * t + b * h * t * d * (4 * want_out + (emit is not None)) + 4 * t * t * (h * (bias is not None) + nw * (mask is not None))
-    entry, tag = ((N.lib.dlmcq_window_attention_f16, "window_attention_f16") if operands == "f16" else
-                  (N.lib.dlmcq_window_attention_f32, "window_attention"))
     return _emit_launch("window_attention_quant", tag, q, (b, t, h * d), emit, want_out, nbytes,
                         lambda op, cp, *tail: entry(
                             N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(bt), N.ptr(mt), op, cp, b, h, t, d, nw, *q.stride()[:3], *k.stride()[:3],

@@ -1716,7 +1716,40 @@ def _swin_geometry_pass(gm, report, planned, dry_run):
     _run_node_pass(gm, report, "merge_norm", "merge_norms", merge, dry_run)
 
 
-class AttentionLayer(_MapCodesLayer):
+class _AttentionNode(_MapCodesLayer):
+    """What AttentionLayer and WindowAttentionLayer share: the `operands` argument, the rule for the merged shape and the tail of the
+    torch restatement."""
+
+    def __init__(self, emit, want_out, c, merged, flatten, operands):
+        super().__init__(emit, want_out, c, c, 0, False)
+        if operands not in K.ATTENTION_OPERANDS:
+            raise ValueError(f"{type(self).__name__}: operands is one of {K.ATTENTION_OPERANDS}, not {operands!r}")
+        self.operands = operands
+        self.merged, self.flatten = bool(merged), bool(flatten)
+
+    def _merges(self, q, shape):
+        """Whether the graph's tail merges the heads of the kernel's result for `q` [B, H, T, D] - flatten(2), or a reshape to
+        three dimensions, at most one of them -1, that is [B, T, H * D] - into a width the code reader takes."""
+        b, h, t, d = q.shape
+        want = [b, t, h * d]
+        if not self.flatten:
+            dims = [int(x) for x in shape]
+            free = [i for i, x in enumerate(dims) if x == -1]
+            if len(free) == 1 and all(x == y for i, (x, y) in enumerate(zip(dims, want)) if i != free[0]):
+                dims = want
+            if dims != want:
+                return False
+        return self.emit is None or h * d == self.c
+
+    def _torch_tail(self, o, shape):
+        """The unfused graph behind the second product: the merge-heads tail, the reader's quantise pass."""
+        if self.merged:
+            o = o.permute(0, 2, 1, 3)
+            o = o.flatten(2) if self.flatten else o.reshape(*shape)
+        return self._torch_rows(o) if self.emit is not None else (o, None)
+
+
+class AttentionLayer(_AttentionNode):
     """softmax(scale * q k^T) v of fp32 views [B, H, T, D] as one flash-forward launch (csrc/attention.hip), and - `merged` - the
     merge-heads `permute(0, 2, 1, 3)` + reshape behind it as a free view: the node returns [B, Tq, H * D] and hands the Linear plan
     layer that reads it (`to_out`) its activation codes from the same launch.  `emit`: the reader's activation quantiser or None (an
@@ -1730,11 +1763,8 @@ class AttentionLayer(_MapCodesLayer):
     kernel's operand type alone: the torch restatement is the same.  Returns `(fp32 or None, codes or None)`."""
 
     def __init__(self, emit, want_out, c, scale, merged, sdpa=None, flatten=False, operands="f32"):
-        super().__init__(emit, want_out, c, c, 0, False)
-        if operands not in K.ATTENTION_OPERANDS:
-            raise ValueError(f"AttentionLayer: operands is one of {K.ATTENTION_OPERANDS}, not {operands!r}")
-        self.operands = operands
-        self.scale, self.merged, self.flatten = (None if scale is None else float(scale)), bool(merged), bool(flatten)
+        super().__init__(emit, want_out, c, merged, flatten, operands)
+        self.scale = None if scale is None else float(scale)
         self.sdpa = None if sdpa is None else dict(sdpa)
 
     def _torch(self, q, k, v, shape):
@@ -1743,23 +1773,10 @@ class AttentionLayer(_MapCodesLayer):
             o = F.scaled_dot_product_attention(q, k, v, **self.sdpa)
         else:
             o = torch.matmul(torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * self.scale, dim=-1), v)
-        if self.merged:
-            o = o.permute(0, 2, 1, 3)
-            o = o.flatten(2) if self.flatten else o.reshape(*shape)
-        return self._torch_rows(o) if self.emit is not None else (o, None)
+        return self._torch_tail(o, shape)
 
     def forward(self, q, k, v, *shape):
-        ok = q.is_cuda and K.attention_views(q, k, v)
-        if ok and self.merged:
-            b, h, tq, d = q.shape
-            want = [b, tq, h * d]
-            if not self.flatten:      # (a reshape to three dimensions, at most one of them -1: the merged heads or something else)
-                dims = [int(x) for x in shape]
-                free = [i for i, x in enumerate(dims) if x == -1]
-                if len(free) == 1 and all(x == y for i, (x, y) in enumerate(zip(dims, want)) if i != free[0]):
-                    dims = want
-                ok = dims == want
-            ok = ok and (self.emit is None or h * d == self.c)
+        ok = q.is_cuda and K.attention_views(q, k, v) and (not self.merged or self._merges(q, shape))
         if not ok:
             return self._torch(q, k, v, shape)
         scale = q.shape[-1] ** -0.5 if self.scale is None else self.scale
@@ -1815,20 +1832,11 @@ def _attention_core(node, modules):
     scores = _softmax_of(attn, modules)
     if scores is None or not isinstance(v, fx.Node) or _sole_user(attn) is None or _sole_user(scores) is None:
         return None
-    if not _is_call(scores, _MUL_FNS, "mul") or len(scores.args) != 2:
+    scored = _scaled_scores(scores)
+    if scored is None or scored[3]:      # (the pre-scaled spelling matmul(q * c, k^T) is not this pass's: the window pass takes it)
         return None
-    dots, c = scores.args if isinstance(scores.args[0], fx.Node) else scores.args[::-1]
-    if not isinstance(c, float) or not math.isfinite(c) or _sole_user(dots) is None:
-        return None
-    if not _is_call(dots, _MATMUL_FNS, "matmul") or len(dots.args) != 2:
-        return None
-    q, kt = dots.args
-    if not isinstance(q, fx.Node) or _sole_user(kt) is None or not _is_call(kt, (torch.transpose,), "transpose") or len(kt.args) != 3:
-        return None
-    k, d0, d1 = kt.args
-    if not isinstance(k, fx.Node) or {d0, d1} not in ({-1, -2}, {2, 3}, {-1, 2}, {-2, 3}) or isinstance(d0, bool) or isinstance(d1, bool):
-        return None
-    return q, k, v, c, None, [node, attn, scores, dots, kt]
+    q, k, c, _, made_of = scored
+    return q, k, v, c, None, [node, attn] + made_of
 
 
 def _static_head_dim(node):
@@ -1881,6 +1889,24 @@ def _merge_heads_tail(node):
     return (perm, shape, tuple(sizes)) if ok else None
 
 
+def _attention_splice(cls, planned, node, q, args, made_of, **ctor):
+    """What the attention and the window attention pass do behind their cores: the plan node `cls` for the core ending in `node`, or
+    None for a head dimension the kernels are not built for, spelled as an int.  With the merge-heads tail behind the core
+    (_merge_heads_tail) the node stands where the reshape stood and the Linear plan layers reading it take its codes; if nobody takes
+    codes, or without the tail, it is an fp32-only node.  `args`: the node's inputs in front of the reshape's sizes; `ctor`: the
+    constructor arguments of `cls` that its core decides."""
+    if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:
+        return None
+    perm, shape, sizes = _merge_heads_tail(node) or (None, None, ())
+    taken = _code_readers(planned, shape, linear=True) if shape is not None else None
+    if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
+        taken = _CodeReaders(None, [], True, 0, 0, 0, False)
+    ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, merged=shape is not None, flatten=sizes is None, **ctor)
+    if shape is None:
+        return _Splice(cls, ctor, node, args, [], made_of)
+    return _Splice(cls, ctor, shape, args + (sizes or ()), taken.takers, [shape, perm] + made_of)
+
+
 def _attention_pass(gm, report, planned, dry_run, operands="f32"):
     """Attention (fuse_inference(attention=True), or attention="f16": the same nodes with `operands` "f16"): the core `softmax(q k^T * c) v` (_attention_core) becomes one node (AttentionLayer,
     csrc/attention.hip).  With the merge-heads tail behind it (_merge_heads_tail) the node stands where the reshape stood, returns
@@ -1892,22 +1918,12 @@ def _attention_pass(gm, report, planned, dry_run, operands="f32"):
         if core is None:
             return None
         q, k, v, scale, sdpa, made_of = core
-        if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:      # (a head dimension the kernel is not built for, spelled as an int)
-            return None
-        perm, shape, sizes = _merge_heads_tail(node) or (None, None, ())
-        taken = _code_readers(planned, shape, linear=True) if shape is not None else None
-        if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
-            taken = _CodeReaders(None, [], True, 0, 0, 0, False)
-        ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, sdpa=sdpa,
-                    flatten=sizes is None, operands=operands)
-        if shape is None:
-            return _Splice(AttentionLayer, ctor, node, (q, k, v), [], made_of)
-        return _Splice(AttentionLayer, ctor, shape, (q, k, v) + (sizes or ()), taken.takers, [shape, perm] + made_of)
+        return _attention_splice(AttentionLayer, planned, node, q, (q, k, v), made_of, scale=scale, sdpa=sdpa, operands=operands)
     _run_node_pass(gm, report, "attention", "attentions", match, dry_run)
     report.attention_operands = operands if report.attentions else None
 
 
-class WindowAttentionLayer(_MapCodesLayer):
+class WindowAttentionLayer(_AttentionNode):
     """softmax(scale * q k^T + bias + mask) v of fp32 views [B, H, T, D], T <= 64 - a windowed transformer's attention - as one launch
     (csrc/window_attention.hip: one wave per (window, head)), and the merge-heads tail behind it as a free view: the node returns
     [B, T, H * D] and hands the Linear plan layer that reads it its activation codes from the same launch.  `emit`, `want_out`, `c`,
@@ -1922,11 +1938,8 @@ class WindowAttentionLayer(_MapCodesLayer):
     the kernel's operand type alone: the torch restatement is the same.  Returns `(fp32 or None, codes or None)`."""
 
     def __init__(self, emit, want_out, c, scale, merged, pre_scaled, has_bias, has_mask, flatten=False, operands="f32"):
-        super().__init__(emit, want_out, c, c, 0, False)
-        if operands not in K.WINDOW_ATTENTION_OPERANDS:
-            raise ValueError(f"WindowAttentionLayer: operands is one of {K.WINDOW_ATTENTION_OPERANDS}, not {operands!r}")
-        self.operands = operands
-        self.scale, self.merged, self.flatten = float(scale), bool(merged), bool(flatten)
+        super().__init__(emit, want_out, c, merged, flatten, operands)
+        self.scale = float(scale)
         self.pre_scaled, self.has_bias, self.has_mask = bool(pre_scaled), bool(has_bias), bool(has_mask)
 
     def _torch(self, q, k, v, bias, mask, windows, shape):
@@ -1937,11 +1950,7 @@ class WindowAttentionLayer(_MapCodesLayer):
         if mask is not None:
             h, t = s.shape[1], s.shape[2]
             s = (s.view(-1, int(windows), h, t, s.shape[3]) + mask).view(-1, h, t, s.shape[3])
-        o = torch.matmul(torch.softmax(s, dim=-1), v)
-        if self.merged:
-            o = o.permute(0, 2, 1, 3)
-            o = o.flatten(2) if self.flatten else o.reshape(*shape)
-        return self._torch_rows(o) if self.emit is not None else (o, None)
+        return self._torch_tail(torch.matmul(torch.softmax(s, dim=-1), v), shape)
 
     def forward(self, q, k, v, *rest):
         terms = list(rest[:self.has_bias + 2 * self.has_mask])
@@ -1956,16 +1965,7 @@ class WindowAttentionLayer(_MapCodesLayer):
             if ok and mask is not None:
                 ok = (mask.dtype == torch.float32 and mask.dim() == 5 and tuple(mask.shape[2:]) == (1, t, t) and mask.shape[0] == 1
                       and int(windows) == mask.shape[1] and b % mask.shape[1] == 0)
-        if ok and self.merged:
-            want = [b, t, h * d]
-            if not self.flatten:      # (AttentionLayer's rule: a reshape to three dimensions that merges the heads)
-                dims = [int(x) for x in shape]
-                free = [i for i, x in enumerate(dims) if x == -1]
-                if len(free) == 1 and all(x == y for i, (x, y) in enumerate(zip(dims, want)) if i != free[0]):
-                    dims = want
-                ok = dims == want
-            ok = ok and (self.emit is None or h * d == self.c)
-        if not ok:
+        if not (ok and (not self.merged or self._merges(q, shape))):
             return self._torch(q, k, v, bias, mask, windows, shape)
         emit = None if self.emit is None else self.emit.emit(q.numel())
         out, codes = K.window_attention_quant(q, k, v, self.scale, bias=bias, mask=mask, emit=emit, want_out=self.want_out,
@@ -2059,18 +2059,9 @@ def _window_attention_pass(gm, report, planned, dry_run, operands="f32"):
         if core is None:
             return None
         q, k, v, scale, pre, bias, mask, made_of = core
-        if _static_head_dim(q) not in (None,) + K.ATTENTION_DIMS:
-            return None
-        perm, shape, sizes = _merge_heads_tail(node) or (None, None, ())
-        taken = _code_readers(planned, shape, linear=True) if shape is not None else None
-        if taken is None or any(planned[u].mod.weight.dim() != 2 for u in taken.takers):      # nobody takes codes: an fp32-only node
-            taken = _CodeReaders(None, [], True, 0, 0, 0, False)
-        ctor = dict(emit=taken.emit, want_out=taken.want_out, c=taken.c, scale=scale, merged=shape is not None, pre_scaled=pre,
-                    has_bias=bias is not None, has_mask=mask is not None, flatten=sizes is None, operands=operands)
-        args = (q, k, v) + (() if bias is None else (bias,)) + (mask or ())
-        if shape is None:
-            return _Splice(WindowAttentionLayer, ctor, node, args, [], made_of)
-        return _Splice(WindowAttentionLayer, ctor, shape, args + (sizes or ()), taken.takers, [shape, perm] + made_of)
+        return _attention_splice(WindowAttentionLayer, planned, node, q, (q, k, v) + (() if bias is None else (bias,)) + (mask or ()),
+                                 made_of, scale=scale, pre_scaled=pre, has_bias=bias is not None, has_mask=mask is not None,
+                                 operands=operands)
     _run_node_pass(gm, report, "window_attention", "window_attentions", match, dry_run)
     report.window_attention_operands = operands if report.window_attentions else None
 

@@ -153,13 +153,13 @@ def _p(v):
 
 
 def _at(q=1 << 12, k=1 << 13, v=1 << 14, out=1 << 15, codes=1 << 16, b=2, h=3, tq=17, tk=17, d=64, qs=None, ks=None, vs=None, os_=None,
-        att_scale=0.125, scale=1 << 17, zp=None, lo=0, hi=255, form=None, g=0.0):
+        att_scale=0.125, scale=1 << 17, zp=None, lo=0, hi=255, form=None, g=0.0, entry="dlmcq_attention_f32"):
     form = N.FORM_ZEROPOINT if form is None else form
     packed = (tq * 3 * h * d, d, 3 * h * d)
     qs, ks, vs = (packed if s is None else s for s in (qs, ks, vs))
     os_ = (tq * h * d, d, h * d) if os_ is None else os_
-    return N.lib.dlmcq_attention_f32(_p(q), _p(k), _p(v), _p(out), _p(codes), b, h, tq, tk, d, *qs, *ks, *vs, *os_, att_scale, _p(scale), _p(zp),
-                                     lo, hi, form, g, None)
+    return getattr(N.lib, entry)(_p(q), _p(k), _p(v), _p(out), _p(codes), b, h, tq, tk, d, *qs, *ks, *vs, *os_, att_scale, _p(scale), _p(zp),
+                                 lo, hi, form, g, None)
 
 
 REFUSED = {
@@ -186,12 +186,15 @@ REFUSED = {
 
 @pytest.mark.parametrize("name", sorted(REFUSED))
 def test_refusals_need_no_gpu(name):
-    """Nothing is launched on these placeholder pointers: every call is answered by the argument checks."""
+    """Nothing is launched on these placeholder pointers: every call is answered by the argument checks - of either entry point:
+    dlmcq_attention_f16 answers through the same attention_args (csrc/attention_common.h)."""
     kw, rc = REFUSED[name]
-    assert N.lib.dlmcq_strerror(rc) and _at(**kw) == rc
+    assert N.lib.dlmcq_strerror(rc) and _at(**kw) == rc and _at(entry="dlmcq_attention_f16", **kw) == rc
 
 
 def test_empty_problems_are_ok():
     dense = (64, 64, 64)
     assert _at(b=0) == 0 and _at(h=0, qs=dense, ks=dense, vs=dense, os_=dense) == 0 and _at(tq=0) == 0
     assert _at(b=0, q=None, k=None, v=None, out=None, codes=None) == 0 and _at(tq=0, d=32, out=None, codes=None, scale=None) == 0
+    f16 = "dlmcq_attention_f16"
+    assert _at(b=0, entry=f16) == 0 and _at(h=0, qs=dense, ks=dense, vs=dense, os_=dense, entry=f16) == 0 and _at(tq=0, entry=f16) == 0

@@ -16,12 +16,12 @@ from test_transformer_host import EALIGN, EINVAL, KEY, nodes, readers
 
 
 def _wa(q=1 << 12, k=1 << 13, v=1 << 14, bias=1 << 18, mask=1 << 19, out=1 << 15, codes=1 << 16, b=4, h=3, t=49, d=32, nw=2, bias_s=None,
-        mask_s=None, scale=1 << 17, lo=0, hi=255, form=N.FORM_ZEROPOINT):
+        mask_s=None, scale=1 << 17, lo=0, hi=255, form=N.FORM_ZEROPOINT, entry="dlmcq_window_attention_f32"):
     packed, pad = (t * 3 * max(h, 1) * d, d, 3 * max(h, 1) * d), (t + 3) // 4 * 4      # (h = 0: strides of one head)
     bias_s, mask_s = bias_s or (t * pad, pad), mask_s or (t * pad, pad)
     _p = lambda x: None if x is None else ctypes.c_void_p(x)  # noqa: E731
-    return N.lib.dlmcq_window_attention_f32(_p(q), _p(k), _p(v), _p(bias), _p(mask), _p(out), _p(codes), b, h, t, d, nw, *packed, *packed, *packed,
-                                            packed[0] // 3, d, packed[2] // 3, *bias_s, *mask_s, 0.125, _p(scale), None, lo, hi, form, 0.0, None)
+    return getattr(N.lib, entry)(_p(q), _p(k), _p(v), _p(bias), _p(mask), _p(out), _p(codes), b, h, t, d, nw, *packed, *packed, *packed,
+                                 packed[0] // 3, d, packed[2] // 3, *bias_s, *mask_s, 0.125, _p(scale), None, lo, hi, form, 0.0, None)
 
 
 ANSWERS = {      # (empty problems are DLMCQ_OK with nothing launched; nW is not read without a mask)
@@ -39,6 +39,7 @@ ANSWERS = {      # (empty problems are DLMCQ_OK with nothing launched; nW is not
 def test_return_codes_need_no_gpu(name):
     kw, rc = ANSWERS[name]
     assert _wa(**kw) == rc and len(N.SIGNATURES["dlmcq_window_attention_f32"][1]) == 36
+    assert _wa(entry="dlmcq_window_attention_f16", **kw) == rc      # (the same window_attention_args, csrc/attention_common.h)
 
 
 def test_window_vit_decisions():
