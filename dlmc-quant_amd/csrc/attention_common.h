@@ -1,9 +1,10 @@
-// What the four attention kernels (attention.hip, attention_f16.hip, window_attention.hip, window_attention_f16.hip) share: the kernel
+// What the five attention kernels (attention.hip, attention_f16.hip, window_attention.hip, window_attention_f16.hip,
+// window_attention_stream.hip) share: the kernel
 // arguments, the host checks and the launch behind them, and the device steps that are the same code in more than one of them - the
 // lane map, the operand loads, the f16 conversions and v's transposing pair stores, the f16 P step, the normalised store.  (The fp32
 // P V step is NOT here: as a helper it left the window kernel's code as good but cost the streaming kernel 0.4 % at ViT-S's shape,
 // twice the run-to-run spread - DESIGN.md 5.35 - so each fp32 kernel keeps its own copy.)  The arithmetic of every step is stated in
-// the header comment of the kernel that uses it; here stands the code, once.  Four translation units, not one: their per-file flags
+// the header comment of the kernel that uses it; here stands the code, once.  Five translation units, not one: their per-file flags
 // differ (csrc/Makefile).  Not part of the ABI.
 #pragma once
 
@@ -18,6 +19,8 @@ namespace dlmcq {
 // A workgroup of a window kernel (window_attention.hip, window_attention_f16.hip) is DLMCQ_WA_WAVES waves, one (b, h) each
 #define DLMCQ_WA_WAVES 4      // (b, h) pairs per workgroup
 #define DLMCQ_WA_TMAX 64
+// A workgroup of the streamed window kernel (window_attention_stream.hip) owns one (b, h) whole: ceil(T / 32) waves, a 32-query tile each
+#define DLMCQ_WS_TMAX 256
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -195,18 +198,19 @@ static inline int attention_args(AttnArgs& a, ConvEpi& ep, int64_t* grid, const 
   return DLMCQ_OK;
 }
 
-// The window entry points' checks (attention_checks; 1 <= T <= DLMCQ_WA_TMAX and the additive terms' layout).  DLMCQ_OK with
-// *grid = 0: nothing to launch.  Else `a`, `ep` and *grid (workgroups) are set.
+// The window entry points' checks (attention_checks; 1 <= T <= `tmax` - DLMCQ_WA_TMAX for the one-wave kernels, DLMCQ_WS_TMAX for the
+// streamed one - and the additive terms' layout).  DLMCQ_OK with *grid = 0: nothing to launch.  Else `a`, `ep` and *grid (workgroups
+// of DLMCQ_WA_WAVES pairs; the streamed kernel launches a.pairs instead) are set.
 static inline int window_attention_args(WinAttnArgs& a, ConvEpi& ep, int64_t* grid, const float* q, const float* k, const float* v,
                                         const float* bias, const float* mask, float* out, void* codes, int64_t B, int64_t H, int64_t T,
                                         int64_t D, int64_t nW, const int64_t (&strides)[12], int64_t bias_sh, int64_t bias_st,
                                         int64_t mask_sw, int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point,
-                                        int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g) {
+                                        int32_t q_lo, int32_t q_hi, int32_t q_form, float q_ste_g, int64_t tmax = DLMCQ_WA_TMAX) {
   *grid = 0;
   const bool bias_ok = !bias || (bias_sh >= 0 && bias_sh % 4 == 0 && bias_st >= T && bias_st % 4 == 0);
   const bool mask_ok = !mask || (nW >= 1 && B % nW == 0 && mask_sw >= 0 && mask_sw % 4 == 0 && mask_st >= T && mask_st % 4 == 0);
   bool launch;
-  const int rc = attention_checks(ep, &launch, T >= 1 && T <= DLMCQ_WA_TMAX && bias_ok && mask_ok, false, q, k, v, bias, mask, out, codes, B, H, D,
+  const int rc = attention_checks(ep, &launch, T >= 1 && T <= tmax && bias_ok && mask_ok, false, q, k, v, bias, mask, out, codes, B, H, D,
                                   strides, scale, q_scale, q_zero_point, q_lo, q_hi, q_form, q_ste_g);
   if (!launch) return rc;
   if (B * H >= (1ll << 31) - DLMCQ_WA_WAVES) return DLMCQ_ERANGE;

@@ -169,6 +169,7 @@ SIGNATURES = {
     "dlmcq_attention_f16": (ctypes.c_int, [_p, _p, _p, _p, _p] + [_i64] * 17 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_window_attention_f32": (ctypes.c_int, [_p] * 7 + [_i64] * 21 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_window_attention_f16": (ctypes.c_int, [_p] * 7 + [_i64] * 21 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
+    "dlmcq_window_attention_stream_f32": (ctypes.c_int, [_p] * 7 + [_i64] * 21 + [_f32, _p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_patch_rows_f32": (ctypes.c_int, [_p, _p, _p] + [_i64] * 8 + [_p, _p, _i32, _i32, _i32, _f32, _p]),
     "dlmcq_tokens_assemble_f32": (ctypes.c_int, [_p, _p, _p, _p] + [_i64] * 6 + [_p]),
     "dlmcq_conv2d_i8_nhwc_gap": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _p, _i32, _p, _p, _p,

@@ -1806,7 +1806,15 @@ def window_attention_views(q, k, v):
     return attention_views(q, k, v) and 1 <= q.shape[2] == k.shape[2] <= WINDOW_TOKENS
 
 
-def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want_out=True, operands="f32"):
+WINDOW_STREAM_TOKENS = 256    # dlmcq_window_attention_stream_f32: the most tokens of a window (one workgroup stages k and v of a head in LDS)
+
+
+def window_stream_views(q, k, v):
+    """Whether dlmcq_window_attention_stream_f32 reads `q`, `k`, `v` [B, H, T, D] in place: attention_views, and one T <= WINDOW_STREAM_TOKENS."""
+    return attention_views(q, k, v) and 1 <= q.shape[2] == k.shape[2] <= WINDOW_STREAM_TOKENS
+
+
+def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want_out=True, operands="f32", stream=None):
     """softmax(scale * q k^T + bias + mask) v of fp32 views `q`, `k`, `v` [B, H, T, D] (window_attention_views: T <= 64, read in place, the
     three slices of one packed projection included) by dlmcq_window_attention_f32: one wave per (b, h), the whole score tile in registers
     (include/dlmcq.h states the order and the bound).  `bias`: fp32 [H, T, T] (or [1, H, T, T]) or None; `mask`: fp32 [nW, T, T] (or
@@ -1817,9 +1825,20 @@ def window_attention_quant(q, k, v, scale, bias=None, mask=None, emit=None, want
     `operands="f16"`: dlmcq_window_attention_f16 instead - the same split, terms and outputs with q, k, v and the softmax weights rounded
     to f16 as operands of the f16 matrix cores, fp32 everywhere else (csrc/window_attention_f16.hip states the arithmetic, the bound and
     the range limit: inputs above 65504 in magnitude become infinite); recorded as PROFILE launch "window_attention_f16".  Opt-in: the
-    default is the fp32 kernel, bit for bit."""
-    q, k, v, scale, entry, tag = _attention_front("window_attention", window_attention_views, "q, k, v [B, H, T, D], T in 1 .. 64", q, k, v,
+    default is the fp32 kernel, bit for bit.
+    `stream`: which fp32 kernel.  None picks by T: T <= 64 the kernel above, 65 <= T <= 256 (window_stream_views) dlmcq_window_attention_stream_f32
+    - one workgroup per (b, h), k and v of the head in LDS, the keys folded in blocks of 32 (csrc/window_attention_stream.hip states the
+    arithmetic and the bound; the arguments, terms and outputs are the same), recorded as PROFILE launch "window_attention_stream".  True:
+    that kernel at any T <= 256; False: never.  With `operands="f16"` it is never taken: T > 64 or `stream=True` is the error of a view the
+    f16 kernel does not read."""
+    streamed = operands == "f32" and stream is not False and (bool(stream) or q.dim() == 4 and q.shape[2] > WINDOW_TOKENS)
+    views, limit = (window_stream_views, WINDOW_STREAM_TOKENS) if streamed else (window_attention_views, WINDOW_TOKENS)
+    if operands == "f16" and stream:
+        raise ValueError("window_attention_quant: stream=True is the fp32 kernel's; with f16 operands q, k, v [B, H, T, D], T in 1 .. 64")
+    q, k, v, scale, entry, tag = _attention_front("window_attention", views, f"q, k, v [B, H, T, D], T in 1 .. {limit}", q, k, v,
                                                   [t for t in (bias, mask) if t is not None], scale, emit, want_out, operands)
+    if streamed:
+        entry, tag = N.lib.dlmcq_window_attention_stream_f32, "window_attention_stream"
     b, h, t, d = q.shape
     bt, rows, bias_sh, bias_st = _window_term(bias.detach(), t, "bias") if bias is not None else (None, h, 0, 0)
     if rows not in (1, h):

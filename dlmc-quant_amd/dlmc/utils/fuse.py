@@ -1924,14 +1924,15 @@ def _attention_pass(gm, report, planned, dry_run, operands="f32"):
 
 
 class WindowAttentionLayer(_AttentionNode):
-    """softmax(scale * q k^T + bias + mask) v of fp32 views [B, H, T, D], T <= 64 - a windowed transformer's attention - as one launch
-    (csrc/window_attention.hip: one wave per (window, head)), and the merge-heads tail behind it as a free view: the node returns
+    """softmax(scale * q k^T + bias + mask) v of fp32 views [B, H, T, D], T <= 256 - a windowed transformer's attention - as one launch
+    (T <= 64: csrc/window_attention.hip, one wave per (window, head); 65 <= T <= 256, fp32 operands only:
+    csrc/window_attention_stream.hip, one workgroup per (window, head); K.window_attention_quant picks), and the merge-heads tail behind it as a free view: the node returns
     [B, T, H * D] and hands the Linear plan layer that reads it its activation codes from the same launch.  `emit`, `want_out`, `c`,
     `merged`, `flatten`: as AttentionLayer; `scale`: the graph's Python float; `pre_scaled`: the graph multiplies q, not the product;
     `has_bias` / `has_mask`: which additive terms arrive, in that order, behind q, k, v - the values the graph added (`bias.unsqueeze(0)`
     [1, H, T, T]; `mask.unsqueeze(1).unsqueeze(0)` [1, nW, 1, T, T]: K.window_attention_quant resolves the broadcast views), and behind
     the mask the graph's own nW - the second size of its five-size view, which the kernel path requires to be the mask's.  The torch
-    restatement - the graph's own ops, then K.fake_quant - runs for anything the kernel refuses: T > 64, D not 32 or 64, tensors that
+    restatement - the graph's own ops, then K.fake_quant - runs for anything the kernels refuse: T > 256 (with "f16" operands T > 64), D not 32 or 64, tensors that
     are not fp32 device views read in place, terms of another shape, a merged width other than H * D or `c`.  Not merged: the kernel's
     [B, T, H * D] permuted back to [B, H, T, D], fp32 only.  `operands`: "f32" (csrc/window_attention.hip, the default) or "f16"
     (csrc/window_attention_f16.hip: f16 operands on the f16 matrix cores, fp32 everywhere else; fuse_inference(window_attention="f16")) -
@@ -1957,7 +1958,7 @@ class WindowAttentionLayer(_AttentionNode):
         shape = rest[len(terms):]
         bias = terms.pop(0) if self.has_bias else None
         mask, windows = terms if self.has_mask else (None, None)
-        ok = q.is_cuda and K.window_attention_views(q, k, v)
+        ok = q.is_cuda and (K.window_attention_views(q, k, v) or (self.operands == "f32" and K.window_stream_views(q, k, v)))
         if ok:
             b, h, t, d = q.shape
             ok = bias is None or (bias.dtype == torch.float32 and bias.dim() in (3, 4) and tuple(bias.shape[-3:]) in ((h, t, t), (1, t, t))
@@ -2052,7 +2053,8 @@ def _window_attention_core(node, modules):
 
 def _window_attention_pass(gm, report, planned, dry_run, operands="f32"):
     """Window attention (fuse_inference(window_attention=True), or window_attention="f16": the same nodes with `operands` "f16"): the core `softmax(q k^T * c + bias + mask) v` (_window_attention_core)
-    becomes one node (WindowAttentionLayer, csrc/window_attention.hip); the merge-heads tail and the Linear code readers are the
+    becomes one node (WindowAttentionLayer; csrc/window_attention.hip up to 64 tokens a window, csrc/window_attention_stream.hip from
+    65 to 256 with fp32 operands, the node's torch restatement past that); the merge-heads tail and the Linear code readers are the
     attention pass's.  The core without an additive term is not taken: it is `attention=True`'s."""
     def match(node, modules):
         core = _window_attention_core(node, modules) if node.op in ("call_function", "call_method") else None
@@ -3588,15 +3590,18 @@ def fuse_inference(model, report=None, dry_run=False, chain_pairs=True, pack_int
     float, carrying at least one of `+ bias` (a graph value that broadcasts as [H, T, T] or [1, H, T, T]: the relative-position bias) and
     Swin's shift mask `(S.view(B // nW, nW, H, T, T) + mask.unsqueeze(1).unsqueeze(0)).view(-1, H, T, T)`, bias before mask, every
     intermediate read once - becomes one WindowAttentionLayer node (csrc/window_attention.hip: one wave per (window, head) holds the
-    whole score tile, T <= 64, D 32 or 64; the stated operation order and error bound of include/dlmcq.h;
+    whole score tile, T <= 64, D 32 or 64; from 65 to 256 tokens - Swin's 12 x 12 and 16 x 16 windows - csrc/window_attention_stream.hip:
+    one workgroup per (window, head), k and v in LDS, the keys folded in blocks of 32; the stated operation order and
+    error bound of include/dlmcq.h;
     `fusion_report.window_attentions` counts the nodes).  The merge-heads tail and the Linear code readers are `attention=True`'s.
     Left alone: the core without an additive term (that is `attention=True`'s, and the two flags do not meet), a term added in place, a
-    second reader of an intermediate.  At run time anything the kernel refuses - more than 64 tokens, another head dimension, tensors
+    second reader of an intermediate.  At run time anything the kernels refuse - more than 256 tokens, another head dimension, tensors
     that are not fp32 device views read in place, terms of another shape - takes the node's torch restatement: the graph's own ops.
     Runs after the LayerNorm, GELU and attention passes.  Off by default: the plan without it is the plan as it was.
     `window_attention="f16"`: the same cores, matched and planned the same way, on csrc/window_attention_f16.hip - q, k,
     v and the softmax weights as f16 operands of the f16 matrix cores, the scale, bias, mask, softmax and division in fp32, fp32 in and
-    out; its own stated arithmetic and error bound, inputs above 65504 in magnitude become infinite.
+    out; its own stated arithmetic and error bound, inputs above 65504 in magnitude become infinite; windows of more than 64 tokens take
+    the node's torch restatement.
     `fusion_report.window_attention_operands` says which operand type the nodes run on ("f32", "f16", None without any).  `True` stays
     the fp32 kernel, bit for bit.  Measured: DESIGN.md 5.33 (tools/window_attention_f16_compare.py).  Opt-in.
     `swin_geometry=True`: the row geometry of a Swin stage (`workloads.swin()`) as plan nodes on csrc/swin_rows.hip,

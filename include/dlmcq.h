@@ -1264,6 +1264,38 @@ int dlmcq_window_attention_f16(const float* q, const float* k, const float* v, c
                                int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
                                int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
 
+/* ---- Window attention past 64 tokens, T <= 256: one workgroup per (b, h), the keys streamed in blocks of 32 ----
+ * dlmcq_window_attention_f32's arguments, views, strides, alignment, terms, refusals, empty-problem rule and quantiser tail with the
+ * token limit 256 instead of 64 (csrc/window_attention_stream.hip): the 12 x 12 and 16 x 16 windows of Swin at 384^2, biased
+ * whole-image attention.  A workgroup of ceil(T / 32) waves owns one (b, h), a wave 32 queries; k and v of the head are staged in LDS
+ * once and every wave folds the key blocks by itself.  The scores are dlmcq_window_attention_f32's, the fold dlmcq_attention_f32's.
+ * For query row i of one (b, h), keys in blocks of 32, u = 2^-24:
+ *     a_ij = the k-ordered fmaf chain over D from +0 (v_mfma_f32_32x32x2_f32)
+ *     s_ij = fl32(a_ij * scale), then fl32(s_ij + bias[h bias_sh + i bias_st + j]) if bias, then fl32(s_ij + mask[(b % nW) mask_sw +
+ *            i mask_st + j]) if mask;  keys past T - 1 hold -inf
+ *     per block, m the running maximum (-inf at first):  m' = max(m, max_j s_ij) (NaNs dropped);  m~ = m', or 0 where m' = -inf
+ *     al   = expf(fl32(m - m~));  p_ij = expf(fl32(s_ij - m~))        the device library's accurate expf (1 ulp)
+ *     l_h  = fl32(fl32(l_h * al) + t_h), t_h (h = bit 2 of the key index) the half's 16 p_ij added one by one in ascending key order
+ *     w_g  = the chain fmaf(v_j[c], p_ij, w_g) from +0 over keys 8 g .. 8 g + 7 of the block in the order 0 4 1 5 2 6 3 7 (+ 8 g)
+ *     o_ic = fl32(fl32(o_ic * al) + fl32(fl32(w_0 + w_1) + fl32(w_2 + w_3)))
+ *     at the end l = fl32(l_0 + l_1), out = fl32(o_ic / l), a true division;  code = the quantiser of out (plain codes only)
+ * A -inf bias or mask entry removes its key; a key block that is all -inf for a row leaves that row's l and o as they were, before
+ * the row's first finite key and after it; a row whose every key is -inf is NaN (0 / 0) and its neighbours are untouched; NaNs in q,
+ * k, v and a +inf score propagate as in dlmcq_attention_f32.
+ * Against real arithmetic on the same fp32 inputs, nb = ceil(T / 32), t = how many of bias and mask are given,
+ * kappa = 2 (104 + 2 + 3 nb + 32 nb) + 1,
+ *     delta_i = max over the finite keys j of (D + 1) u |scale| sum_k |q_ik k_jk| + t u (|scale a*_ij| + |bias_ij| + |mask_ij|):
+ *     |out_ic - o*_ic| <= (2 delta_i + kappa u) sum_j p*_ij |v_jc| + 2^-126 max_j |v_jc|       (csrc/window_attention_stream.hip derives it)
+ * No atomics, no scratch: a row's result depends neither on B, H, its (b, h) nor on the launch.  T <= 64 is accepted (one or two waves);
+ * dlmcq_window_attention_f32 is the better choice there.
+ * Arguments and return codes: dlmcq_window_attention_f32's, one for one, but DLMCQ_EINVAL for T not in 1 .. 256. */
+int dlmcq_window_attention_stream_f32(const float* q, const float* k, const float* v, const float* bias, const float* mask, float* out,
+                                      void* codes, int64_t B, int64_t H, int64_t T, int64_t D, int64_t nW, int64_t q_sb, int64_t q_sh,
+                                      int64_t q_st, int64_t k_sb, int64_t k_sh, int64_t k_st, int64_t v_sb, int64_t v_sh, int64_t v_st,
+                                      int64_t o_sb, int64_t o_sh, int64_t o_st, int64_t bias_sh, int64_t bias_st, int64_t mask_sw,
+                                      int64_t mask_st, float scale, const float* q_scale, const float* q_zero_point, int32_t q_lo,
+                                      int32_t q_hi, int32_t q_form, float q_ste_g, dlmcq_stream_t stream);
+
 /* ---- A vision transformer's patch rows: an fp32 image batch to fp32 rows and / or the activation codes of the embedding ----
  * The rearrangement 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' of an image batch [B, C, gh p, gw p] into rows [B gh gw, p p C]:
  *     row (b gh + gy) gw + gx, column (py p + px) C + c  =  img[b sb + c sc + (gy p + py) sh + gx p + px]
